@@ -69,7 +69,13 @@ def parse_args(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="take the process-group path (RCCL gather included) even with one rank, so that a one-GPU box "
                          "exercises the collective calls")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MiB in all; see dump_outputs) so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def job_plan(args, world: int) -> dict:
@@ -183,6 +189,49 @@ def stream_digest(buf, n_bytes: int):
     w = x.contiguous().view(torch.int64)
     idx = torch.arange(w.numel(), dtype=torch.int64, device=buf.device) * 2 + 1
     return torch.stack([w.sum(), (w * idx).sum()])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 4 << 20       # values kept of an output larger than this: two float32 samples stay at 32 MiB
+
+
+def dump_positions(n: int, seed: int):
+    """Positions of an n-value output that --dump-outputs keeps: None (all of them, in order) when n <= DUMP_SAMPLE, else
+    DUMP_SAMPLE positions drawn with replacement by numpy's default_rng(seed), sorted - the same for the same n in every run"""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return None
+    return np.sort(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(out_dir, stego, packed, counts, frame_sse):
+    """--dump-outputs: what the last timed step returned to its caller, as float32 / float64 .npy files in out_dir.
+      stego.npy            stego pixels (the embed's output): [F, H, W], or the dump_positions(F*H*W, SEED) sample of the
+                           flattened batch when it is larger than DUMP_SAMPLE pixels
+      extracted.npy        the packed extracted bit stream, one value per byte (MSB-first bits, the extract's output; on rank 0
+                           of a multi-rank run the gathered slices of every rank, each trimmed to its own bytes), or the
+                           dump_positions(n_bytes, SEED + 1) sample of it
+      stego_frame_sse.npy  float64 [F]: per-frame sum of squared differences between stego and cover over EVERY pixel
+      counts.npy           float64 [bits embedded, bits extracted, payload bit errors over the whole stream]
+    stego: uint8 device tensor [F, H, W]; packed: uint8 host array; counts: three ints; frame_sse: int64 tensor [F]"""
+    import numpy as np
+    import torch
+    idx = dump_positions(stego.numel(), SEED)
+    if idx is None:
+        pixels = stego.cpu().numpy()
+    else:
+        pixels = stego.view(-1)[torch.from_numpy(idx).to(stego.device)].cpu().numpy()
+    idx = dump_positions(packed.size, SEED + 1)
+    arrays = {"stego": pixels.astype(np.float32),
+              "extracted": (packed if idx is None else packed[idx]).astype(np.float32),
+              "stego_frame_sse": frame_sse.cpu().numpy().astype(np.float64),
+              "counts": np.asarray(counts, dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def round_trip_verdict(parity_sample, bit_errors, delta, n_ac, gather_ok=None):
@@ -429,7 +478,7 @@ def main():
     gather_wait[0] = 0.0
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(events[k])
+        used, got = step(events[k])
     drain()                                  # every gather of the timed steps has completed
     torch.cuda.synchronize()
     if use_dist:
@@ -460,6 +509,12 @@ def main():
                  "sse")
     torch.cuda.synchronize()
     bit_errors = int(cnt.item())
+    if args.dump_outputs and rank == 0:      # before the exact-mode leg below reuses the extract buffer
+        if use_dist:
+            packed = torch.cat([gathered[last][r][: (c * per_frame_bits + 7) // 8].cpu() for r, (_, c) in enumerate(shares)])
+        else:
+            packed = extracted[:nbytes].cpu()
+        dump_outputs(args.dump_outputs, stego, packed.numpy(), (used, got, bit_errors), sse)
     gpu_sample_packed = None
     if rank == 0 and world == 1 and args.cpu_frames > 0:     # the timed extract's bits of the frames the oracle will redo below
         gpu_sample_packed = extracted[: (min(args.cpu_frames, F) * (cap // F) + 7) // 8].clone()

@@ -36,6 +36,11 @@ class _FakeLib:
 
 @pytest.fixture
 def fake(monkeypatch):
+    # in a run that includes the GPU tier, this process has used the real allocator: its free buffers go back to it before
+    # the stand-in takes over, and arrays still out in that run's hands stay outside the stand-in's accounting
+    gc.collect()
+    hostmem.trim()
+    monkeypatch.setattr(hostmem, "_live_bytes", 0)
     lib = _FakeLib()
     monkeypatch.setattr(native, "load", lambda: lib)
     hostmem.trim()
