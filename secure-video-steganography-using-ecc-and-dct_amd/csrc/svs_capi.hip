@@ -61,6 +61,32 @@ uint32_t knob(const char *name, uint32_t dflt) {
 constexpr uint32_t knob(const char *, uint32_t dflt) { return dflt; }
 #endif
 
+// Test hooks of the experiments library: SVS_GUARD_SCALE multiplies BETA's coefficients (the streaming embed kernels' guard,
+// make_guard), SVS_TIE_SCALE the tie margin of FAST extraction (make_qim).  Below 1 the result is NOT the reference's any
+// more: tests/test_gpu_guard_sensitivity.py uses them to show that the suite notices a bound that is too tight.
+// tests/hostemu applies the same float multiplications (emu_set_guard_scale / emu_set_tie_scale).
+void scale_guard(svs::QimParams &qp) {
+#if defined(SVS_EXPERIMENTS)
+    if (const char *sc = getenv("SVS_GUARD_SCALE")) {
+        const float f = (float)atof(sc);
+        qp.g_sum *= f; qp.g_resid *= f; qp.g_delta *= f;
+    }
+#else
+    (void)qp;
+#endif
+}
+
+void scale_tie(svs::QimParams &qp) {
+#if defined(SVS_EXPERIMENTS)
+    if (const char *sc = getenv("SVS_TIE_SCALE")) {
+        const float f = (float)atof(sc);
+        qp.tie_slope *= f; qp.tie2_sum *= f; qp.tie2_resid *= f; qp.tie2_c00 *= f; qp.tie2_max *= f;
+    }
+#else
+    (void)qp;
+#endif
+}
+
 // Occupancy cap: unused dynamic LDS such that at most `wg_per_cu` workgroups fit the CU's 160 KB (0 = no cap).  The
 // streaming kernels run FASTER with fewer waves in flight than their register count allows (measured sweeps in
 // profiles/history/r01_ab_occupancy.txt): fewer concurrent row streams per CU.
@@ -701,12 +727,7 @@ int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *pla
     if (words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
     const uint32_t *bw = reinterpret_cast<const uint32_t *>(d_bits_packed);
     svs::make_guard(delta, rows, &qp);
-#if defined(SVS_EXPERIMENTS)
-    if (const char *sc = getenv("SVS_GUARD_SCALE")) {   // NOT bit-identical any more when < 1 (experiments library only)
-        const float f = (float)atof(sc);
-        qp.g_sum *= f; qp.g_resid *= f; qp.g_delta *= f;
-    }
-#endif
+    scale_guard(qp);   // experiments library only
     int rc;
 #define SVS_GO(QM)                                                                                                   \
     rc = two ? launch_embed<QM, 2>(rows, total, st, d_gray, d_stego, g, qp, bw, bit_offset, use, (uint32_t)words)    \
@@ -745,6 +766,7 @@ int svs_extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delt
         g.xcd_chunk = tune.chunk;
         svs::QimParams qp;
         const int qm = make_qim(delta, &qp);     // the double mode only differs in requantisation: not needed here
+        scale_tie(qp);                           // experiments library only
         const int rows = rows_for(n);
         int rc;
         if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
@@ -1133,7 +1155,10 @@ int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_
     const bool exact = !streaming && (use > 0 || n_bits > 0);
     svs::QimParams qp;
     const int qm = make_qim(use == 0 ? 1.0 : delta, &qp);
-    if (streaming) svs::make_guard(delta, rows_n, &qp);
+    if (streaming) {
+        svs::make_guard(delta, rows_n, &qp);
+        scale_guard(qp);   // experiments library only
+    }
     g.xcd_chunk = knob("SVS_EMBED_XCD_CHUNK", kEighth);
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t *bw = reinterpret_cast<const uint32_t *>(d_bits_packed);
@@ -1188,6 +1213,7 @@ int svs_extract_bgr_dev(const uint8_t *d_bgr, int64_t bgr_row_pitch, int64_t bgr
     } else {
         svs::QimParams qp;
         const int qm = make_qim(delta, &qp);
+        scale_tie(qp);   // experiments library only
         g.xcd_chunk = knob("SVS_EXTRACT_XCD_CHUNK", rows_for(n) == 1 ? 32u : kEighth);
         const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
         const int rows = rows_for(n);

@@ -42,6 +42,22 @@ void embed_exact_pair_dispatch(Blk &a, Blk &b, uint32_t n, uint32_t nb_a, uint32
 
 bool g_constant_shortcut = false;   // exact == 3: constant blocks take forward_exact_paired_constant, as the replay kernel does
 
+// emu_set_guard_scale / emu_set_tie_scale: the experiments library's SVS_GUARD_SCALE / SVS_TIE_SCALE (csrc/svs_capi.hip
+// scale_guard / scale_tie), the same float multiplications of the QimParams fields
+float g_guard_scale = 1.0f, g_tie_scale = 1.0f;
+
+void scale_guard(svs::QimParams &qp) {
+    const float f = g_guard_scale;
+    qp.g_sum *= f; qp.g_resid *= f; qp.g_delta *= f;
+}
+
+void scale_tie(svs::QimParams &qp) {
+    const float f = g_tie_scale;
+    qp.tie_slope *= f; qp.tie2_sum *= f; qp.tie2_resid *= f; qp.tie2_c00 *= f; qp.tie2_max *= f;
+}
+
+uint8_t *g_replay_map = nullptr;   // emu_set_replay_map: one byte per block of the next emu_embed calls, 1 = handed to the replay
+
 bool g_generic_guarded2 = false;    // exact == 5: the two-row guard through its generic instantiation only
 
 // Two coefficient rows: the instantiation the KERNEL launches (csrc/svs_device.hpp embed_kernel, svs_capi.hip launch_embed) -
@@ -102,9 +118,54 @@ void extract_fast(int rows, const Blk &raw, uint32_t n, const svs::QimParams &d,
     }
 }
 
+// emu_set_extract_wave(64): step two of FAST extraction for EVERY block of an aligned group of 64 blocks in which one block
+// is a candidate, as the kernels do it (one wave ballot; extract_kernel / extract_bgr_kernel).  With the product's margin
+// that gives the per-block result (svs_block.hpp, extract_block); with a margin scaled below 1 (emu_set_tie_scale) it need not.
+int g_extract_wave = 0;   // 0: per block
+uint8_t *g_candidate_map = nullptr;   // emu_set_candidate_map: one byte per block, 1 = a candidate of step one (wave mode only)
+
+template <int QM>
+bool extract_cheap_dispatch(int rows, const Blk &raw, uint32_t n, const svs::QimParams &d, uint32_t &hi, uint32_t &lo, float &off) {
+    if (n == 10) return svs::extract_block_cheap<2, QM, 10>(raw.x, raw.y, n, d, hi, lo, off);
+    switch (rows) {
+        case 2: return svs::extract_block_cheap<2, QM>(raw.x, raw.y, n, d, hi, lo, off);
+        case 3: return svs::extract_block_cheap<3, QM>(raw.x, raw.y, n, d, hi, lo, off);
+        case 4: return svs::extract_block_cheap<4, QM>(raw.x, raw.y, n, d, hi, lo, off);
+        case 5: return svs::extract_block_cheap<5, QM>(raw.x, raw.y, n, d, hi, lo, off);
+        case 6: return svs::extract_block_cheap<6, QM>(raw.x, raw.y, n, d, hi, lo, off);
+        case 7: return svs::extract_block_cheap<7, QM>(raw.x, raw.y, n, d, hi, lo, off);
+        default: return svs::extract_block_cheap<8, QM>(raw.x, raw.y, n, d, hi, lo, off);
+    }
+}
+
+// one wave of FAST extraction (rows >= 2): blocks [g0, g0 + count) of `raws`
+template <int QM>
+void extract_fast_wave(int rows, const Blk *raws, uint64_t count, uint32_t n, const svs::QimParams &d, uint32_t *his, uint32_t *los,
+                       bool *cand, uint64_t *redone) {
+    float off[128];
+    bool any = false;
+    for (uint64_t i = 0; i < count; ++i) {
+        cand[i] = extract_cheap_dispatch<QM>(rows, raws[i], n, d, his[i], los[i], off[i]);
+        any = any || cand[i];
+    }
+    if (!any) return;
+    for (uint64_t i = 0; i < count; ++i) {
+        if (svs::extract_block_settle<QM>(raws[i].x, raws[i].y, n, d, his[i], off[i])) {
+            svs::extract_block_exact<8, QM>(raws[i].x, raws[i].y, n, d, his[i], los[i]);
+            if (redone) ++*redone;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+void emu_set_guard_scale(float f) { g_guard_scale = f; }
+void emu_set_tie_scale(float f) { g_tie_scale = f; }
+void emu_set_extract_wave(int blocks) { g_extract_wave = blocks; }   // 0: per block; 64: a wave of the extract kernels
+void emu_set_candidate_map(uint8_t *map) { g_candidate_map = map; }   // nullptr: off
+void emu_set_replay_map(uint8_t *map) { g_replay_map = map; }   // caller zeroes it; nullptr: off
 
 // frames: contiguous [F][H][W]; bits: packed MSB-first, padded by the caller to a multiple of 4 bytes
 uint64_t emu_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, double delta, int n_ac,
@@ -126,7 +187,10 @@ uint64_t emu_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, dou
     // guard's range; anything else is plain EXACT).  Every mode gives the reference's pixels.
     const bool in_range = delta >= SVS_GUARD_DELTA_MIN && delta <= SVS_GUARD_DELTA_MAX;
     const bool guarded = use > 0 && in_range && (exact == 4 || exact == 0) && svs::rows_for(n) <= 2;
-    if (guarded) svs::make_guard(delta, svs::rows_for(n), &qp);
+    if (guarded) {
+        svs::make_guard(delta, svs::rows_for(n), &qp);
+        scale_guard(qp);
+    }
     if ((exact == 4 || exact == 0) && !guarded) exact = 1;
     if (use == 0) {
         if (n_bits > 0) {  // nothing consumed -> every block entered and round-tripped (either mode: svs_embed_dev)
@@ -171,6 +235,7 @@ uint64_t emu_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, dou
                 raw.load(p, (size_t)W);
                 embed_exact_dispatch(raw, (uint32_t)n, nb, hi, lo, qp, dbl);
                 if (n_replayed) ++*n_replayed;
+                if (g_replay_map) g_replay_map[gb] = 1;
             }
         } else {
             embed_exact_dispatch(raw, (uint32_t)n, nb, hi, lo, qp, dbl);
@@ -193,6 +258,27 @@ uint64_t emu_extract(const uint8_t *gray, int F, int H, int W, double delta, int
     }
     svs::QimParams qp;
     const int qm = make_qim(delta, &qp);
+    scale_tie(qp);
+    if (g_extract_wave > 0 && !exact && svs::rows_for(n) >= 2 && (double)qp.delta_f >= SVS_FAST_EXTRACT_DELTA_MIN) {
+        const uint64_t wv = (uint64_t)(g_extract_wave > 128 ? 128 : g_extract_wave);
+        Blk raws[128];
+        uint32_t his[128], los[128];
+        for (uint64_t g0 = 0; g0 < total; g0 += wv) {
+            const uint64_t count = total - g0 < wv ? total - g0 : wv;
+            for (uint64_t i = 0; i < count; ++i) {
+                const uint64_t gb = g0 + i, f = gb / bpf, b = gb % bpf;
+                raws[i].load(gray + f * (uint64_t)H * W + (b / (W / 8)) * 8 * W + (b % (W / 8)) * 8, (size_t)W);
+            }
+            bool cand[128];
+            if (qm == svs::QM_POW2) extract_fast_wave<svs::QM_POW2>(svs::rows_for(n), raws, count, (uint32_t)n, qp, his, los, cand, n_redone);
+            else extract_fast_wave<svs::QM_F32>(svs::rows_for(n), raws, count, (uint32_t)n, qp, his, los, cand, n_redone);
+            if (g_candidate_map)
+                for (uint64_t i = 0; i < count; ++i) g_candidate_map[g0 + i] = cand[i];
+            for (uint64_t i = 0; i < count; ++i)
+                for (int k = 0; k < n; ++k) out_flags[(g0 + i) * n + k] = (uint8_t)svs::window_bit(his[i], los[i], k);
+        }
+        return total * n;
+    }
     for (uint64_t gb = 0; gb < total; ++gb) {
         const uint64_t f = gb / bpf, b = gb % bpf;
         const uint64_t by = b / (W / 8), bx = b % (W / 8);

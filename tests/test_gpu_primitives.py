@@ -37,7 +37,7 @@ def test_product_build_ignores_experiment_knobs(monkeypatch):
     """No environment variable can reroute a kernel of the shipped library or touch the parity guarantee of a flag.  The knobs
     that did in round 3 (SVS_GUARD_SCALE scaled the rigorous guard to zero, SVS_GUARDED_OFF / SVS_GUARDED2_OFF / SVS_EXACT_BPL /
     SVS_FIXED_N / SVS_EXTRACT_SHUFFLE picked other kernels) are compiled only into lib/variants/libsvsdct_exp.so
-    (-DSVS_EXPERIMENTS).  With all of them set the product build's output is still the oracle's, pixel for pixel and bit for
+    (-DSVS_EXPERIMENTS), as is SVS_TIE_SCALE (the tie margin of FAST extraction).  With all of them set the product build's output is still the oracle's, pixel for pixel and bit for
     bit - and the experiments library, where they ARE live, shows through its replay counter (a hook the product library does
     not have any more) that they reroute: SVS_GUARDED_OFF sends every block to the lane-per-block kernel, which counts nothing."""
     from oracle import qim_dct_oracle as orc          # checker only
@@ -73,7 +73,8 @@ def test_product_build_ignores_experiment_knobs(monkeypatch):
     knobs = (("SVS_GUARD_SCALE", "0"), ("SVS_GUARDED_OFF", "1"), ("SVS_GUARDED2_OFF", "1"), ("SVS_FAST_MAX_ROWS", "0"),
              ("SVS_EXACT_BPL", "2"), ("SVS_FIXED_N", "0"), ("SVS_EXTRACT_SHUFFLE", "1"), ("SVS_FAST_EXTRACT_U1", "1"),
              ("SVS_EMBED_BPL", "1"), ("SVS_EXTRACT_BPL", "2"), ("SVS_EMBED_XCD_CHUNK", "7"), ("SVS_EXTRACT_XCD_CHUNK", "5"),
-             ("SVS_EMBED_WG_PER_CU", "2"), ("SVS_EXTRACT_WG_PER_CU", "2"), ("SVS_STAGE_CHUNK_KB", "64"))
+             ("SVS_EMBED_WG_PER_CU", "2"), ("SVS_EXTRACT_WG_PER_CU", "2"), ("SVS_STAGE_CHUNK_KB", "64"),
+             ("SVS_TIE_SCALE", "0"))
     plain = run(native.load())
     exp = experiments_library()
     d_cnt = C.c_void_p()

@@ -239,6 +239,11 @@ def hostemu():
                                     ctypes.c_uint64]
     lib.emu_chunk_budget.restype = ctypes.c_uint64
     lib.emu_chunk_budget.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+    lib.emu_set_guard_scale.argtypes = [ctypes.c_float]
+    lib.emu_set_tie_scale.argtypes = [ctypes.c_float]
+    lib.emu_set_replay_map.argtypes = [ctypes.c_void_p]
+    lib.emu_set_extract_wave.argtypes = [ctypes.c_int]
+    lib.emu_set_candidate_map.argtypes = [ctypes.c_void_p]
     _EMU = lib
     return lib
 
@@ -270,18 +275,92 @@ def emu_embed(frames, delta, n_ac, bits, bit_offset=0, exact=False, replayed=Non
     return out, int(used)
 
 
-def emu_extract(frames, delta, n_ac, exact=False, redone=None):
-    """`redone`: optional list; receives the number of blocks FAST mode recomputed with the exact transform."""
+class emu_scales:
+    """`with emu_scales(guard=s, tie=t):` - hostemu's BETA / tie margin multiplied by s / t inside the block, as the
+    experiments library's SVS_GUARD_SCALE / SVS_TIE_SCALE do (1 = the product's bounds)"""
+
+    def __init__(self, guard=1.0, tie=1.0):
+        self.guard, self.tie = float(guard), float(tie)
+
+    def __enter__(self):
+        lib = hostemu()
+        lib.emu_set_guard_scale(self.guard)
+        lib.emu_set_tie_scale(self.tie)
+        return self
+
+    def __exit__(self, *exc):
+        lib = hostemu()
+        lib.emu_set_guard_scale(1.0)
+        lib.emu_set_tie_scale(1.0)
+        return False
+
+
+def emu_replay_map(frames, delta, n_ac, bits):
+    """-> bool per block (raster order over the batch): hostemu's guarded embed handed the block to the exact replay"""
     lib = hostemu()
+    frames = frames if frames.ndim == 3 else frames[None]
+    f, h, w = frames.shape
+    out = np.zeros(f * (h // 8) * (w // 8), np.uint8)
+    lib.emu_set_replay_map(out.ctypes.data)
+    try:
+        emu_embed(frames, delta, n_ac, bits)
+    finally:
+        lib.emu_set_replay_map(None)
+    return out.astype(bool)
+
+
+def emu_tie_candidates(frames, delta, n_ac):
+    """-> bool per block: step one of FAST extraction (n >= 8) flags the block as a candidate (wave mode of emu_extract)"""
+    lib = hostemu()
+    frames = frames if frames.ndim == 3 else frames[None]
+    f, h, w = frames.shape
+    out = np.zeros(f * (h // 8) * (w // 8), np.uint8)
+    lib.emu_set_candidate_map(out.ctypes.data)
+    try:
+        emu_extract(frames, delta, n_ac, wave=64)
+    finally:
+        lib.emu_set_candidate_map(None)
+    return out.astype(bool)
+
+
+def emu_extract(frames, delta, n_ac, exact=False, redone=None, wave=0):
+    """`redone`: optional list; receives the number of blocks FAST mode recomputed with the exact transform.  `wave` = 64:
+    FAST extraction's step two for every block of a wave with a candidate, as the kernels do it (0: per block)."""
+    lib = hostemu()
+    lib.emu_set_extract_wave(int(wave))
     frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
     f, h, w = frames.shape
     n = max(0, min(int(n_ac), 63))
     out = np.zeros(f * (h // 8) * (w // 8) * n, np.uint8)
     count = ctypes.c_uint64(0)
-    lib.emu_extract(frames.ctypes.data, f, h, w, float(delta), int(n_ac), out.ctypes.data, int(exact), ctypes.byref(count))
+    try:
+        lib.emu_extract(frames.ctypes.data, f, h, w, float(delta), int(n_ac), out.ctypes.data, int(exact), ctypes.byref(count))
+    finally:
+        lib.emu_set_extract_wave(0)
     if redone is not None:
         redone.append(int(count.value))
     return out
+
+
+def guard_corpus_case(arrays, meta, name):
+    """One setting of tests/golden/guard_corpus.npz (tests/golden/make_guard_corpus.py) as its frame is laid out:
+    -> dict(frame uint8 [H, W], bits 0/1 [blocks * n] (embed settings only), positions, stars).  The file holds the corpus
+    blocks, their payload bits and positions, a small filler library and each block's filler index; the frame is
+    rebuilt from them (filler blocks carry all-zero payload bits)."""
+    m = meta["embed"].get(name) or meta["extract"][name]
+    h, w = meta["frame_shape"][0], m.get("width", meta["frame_shape"][1])
+    blocks = arrays[name + "/filler"][arrays[name + "/filler_index"]]
+    positions = arrays[name + "/positions"].astype(np.int64)
+    corpus = arrays[name + "/blocks"]
+    blocks[positions] = corpus
+    frame = np.ascontiguousarray(blocks.reshape(h // 8, w // 8, 8, 8).transpose(0, 2, 1, 3).reshape(h, w))
+    case = dict(frame=frame, positions=positions, stars=arrays[name + "/stars"])
+    if name in meta["embed"]:
+        n = m["n_ac"]
+        bits = np.zeros((blocks.shape[0], n), np.uint8)
+        bits[positions] = np.unpackbits(arrays[name + "/bits"], count=len(positions) * n).reshape(-1, n)
+        case["bits"] = bits.reshape(-1)
+    return case
 
 
 def guarded_soak_cases(count=64, seed=77):
