@@ -151,7 +151,7 @@ SVS_HD float ubyte_to_float(uint32_t w) {
 // clip(pixel + floor(change)), which is what the callers pass in.
 template <int B>
 SVS_HD uint32_t put_pixel(float v, uint32_t old) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SVS_NO_CVT_PK_U8)
+#if defined(__HIP_DEVICE_COMPILE__)
     // v_cvt_pk_u8_f32 saturates to [0,255] and rounds to nearest even (measured on gfx950:
     // profiles/history/r01_cvt_pk_u8_probe.json) - exact for the integer-valued input it gets here.
     return __builtin_amdgcn_cvt_pk_u8_f32(v, B, old);
@@ -166,7 +166,7 @@ SVS_HD uint32_t put_pixel(float v, uint32_t old) {
 // does; rintf on the host)
 template <int B>
 SVS_HD uint32_t put_pixel_rne(float v, uint32_t old) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SVS_NO_CVT_PK_U8)
+#if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_cvt_pk_u8_f32(v, B, old);
 #else
     const float r = rintf(v);
@@ -186,7 +186,7 @@ SVS_HD uint32_t put_pixel_rne(float v, uint32_t old) {
 // round-to-nearest-even mode, which the closing s_setreg restores.
 SVS_HD void store_row_trunc(float p0, float p1, float p2, float p3, float p4, float p5, float p6, float p7, uint32_t &lo4,
                             uint32_t &hi4) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SVS_NO_CVT_PK_U8) && !defined(SVS_NO_RTZ_STORE)
+#if defined(__HIP_DEVICE_COMPILE__)
     uint32_t a, b;
     asm volatile(
         "s_nop 1\n\t"
@@ -220,12 +220,6 @@ SVS_HD void store_row_trunc(float p0, float p1, float p2, float p3, float p4, fl
 // Forward transform of the coefficient rows u < U of one block.
 // D[u][v] = sum_y sum_x a(u)a(v) p[y][x] cos((2y+1)u pi/16) cos((2x+1)v pi/16)
 // (vertical axis first, as the reference does: axis=0 then axis=1, config_and_setup.py:135).
-#ifndef SVS_PACKED_VERTICAL_U2
-#define SVS_PACKED_VERTICAL_U2 1
-#endif
-#ifndef SVS_PACKED_VERTICAL_U1
-#define SVS_PACKED_VERTICAL_U1 1
-#endif
 // Vertical pass for U = 2 on four columns held as the bytes of w[0..7]: the mirrored-row sums and differences the two
 // outputs need are exact integers, so they are formed on 16-bit lanes (even bytes and odd bytes of the dwords: two
 // columns per operation) and converted to float once - same values as the float path, fewer operations.
@@ -295,7 +289,7 @@ SVS_HD void forward_side(const float (&v0)[8], ForwardSide *side) {
 template <int U>
 SVS_HD void forward_rows(const uint32_t (&rx)[8], const uint32_t (&ry)[8], float (&D)[U][8], ForwardSide *side = nullptr) {
     float V[U][8];
-    if constexpr (U == 1 && SVS_PACKED_VERTICAL_U1) {
+    if constexpr (U == 1) {
         float a0[4], b0[4];
         vertical_u1_packed(rx, a0);
         vertical_u1_packed(ry, b0);
@@ -305,7 +299,7 @@ SVS_HD void forward_rows(const uint32_t (&rx)[8], const uint32_t (&ry)[8], float
         fdct8<8>(V[0], D[0]);
         return;
     }
-    if constexpr (U == 2 && SVS_PACKED_VERTICAL_U2) {
+    if constexpr (U == 2) {
         float a0[4], a1[4], b0[4], b1[4];
         vertical_u2_packed(rx, a0, a1);
         vertical_u2_packed(ry, b0, b1);
@@ -383,9 +377,6 @@ enum QuantMode { QM_F32 = 0, QM_DOUBLE = 1, QM_POW2 = 2 };
 // checks the shortcut against the division on 10^8 samples including every exact tie.
 template <int QM>
 SVS_HD int quant_index(float c, const QimParams &qp) {
-#if defined(SVS_QUANT_ALWAYS_DIVIDE)  // A/B build: the plain division everywhere
-    return (int)rintf(c / qp.delta_f);
-#endif
     if constexpr (QM == QM_POW2) {
         return (int)rintf(c * qp.inv_delta_f);
     } else {
@@ -920,16 +911,12 @@ SVS_HD float qim_change(float c, uint32_t bit, const QimParams &qp) {
         const float kMagic = 12582912.0f;   // 1.5 * 2^23
         const float t = c * qp.inv_delta_f;
         float m = t + kMagic;
-#if defined(SVS_QUANT_ALWAYS_DIVIDE)
-        m = rintf(c / qp.delta_f) + kMagic;
-#else
         if constexpr (QM != QM_POW2) {
             const float r = m - kMagic;
             const float miss = fabsf(fabsf(t - r) - 0.5f);       // distance of t from the nearest half-integer
             if (miss <= fabsf(t) * 4.76837158203125e-7f)          // see quant_index
                 m = rintf(c / qp.delta_f) + kMagic;
         }
-#endif
         const uint32_t mb = (__builtin_bit_cast(uint32_t, m) & ~1u) | bit;
         const float qf = __builtin_bit_cast(float, mb) - kMagic;
         return qf * qp.delta_f - c;
@@ -1307,7 +1294,10 @@ inline void make_guard(double delta, int rows, QimParams *qp) {
 // instruction a packed-FP32 one (v_pk_add / v_pk_mul / v_pk_fma_f32, each component rounding exactly like the scalar
 // operation).  Unlike embed_block_exact - which pairs two LINES of one block and has to transpose 2x2 sub-blocks between
 // the passes - the two blocks never exchange data, so the packed form costs no extra instructions: 2 x 928 scalar transform
-// operations become 928 packed ones.  Same results as two embed_block_exact calls, bit for bit.
+// operations become 928 packed ones.  Same results as two embed_block_exact calls, bit for bit.  No kernel runs it: as a
+// kernel (two blocks per lane) it measured SLOWER than the one-block form - a v_pk_*_f32 costs two issue slots on this chip,
+// and the 256-register footprint costs occupancy (profiles/history/r02_ab_exact_pair.txt).  The CPU tier still checks it
+// against embed_block_exact (tests/hostemu, exact == 2).
 template <int U, int QM>
 SVS_HD void embed_block_exact_pair(uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_t (&bx)[8], uint32_t (&by)[8], uint32_t n,
                                    uint32_t nb_a, uint32_t nb_b, uint32_t hi_a, uint32_t lo_a, uint32_t hi_b, uint32_t lo_b,

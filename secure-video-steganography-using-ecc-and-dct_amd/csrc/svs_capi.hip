@@ -46,12 +46,10 @@ svs::FastDiv make_div(uint32_t d) {
     return r;
 }
 
-// Experiment knobs.  The PRODUCT build reads no environment variable at all: every knob below is its compiled-in default
-// and `knob()` folds to a constant - no variable can reroute a kernel, let alone touch the parity guarantee of a flag
-// (round 3 evaluated ~10 getenv per svs_embed_dev call, and SVS_GUARD_SCALE silently made the
-// bit-identical mode non-identical).  `make variants` builds lib/variants/libsvsdct_exp.so with -DSVS_EXPERIMENTS, in which
-// the same names are read from the environment on every call - that library is what tools/ab_bench.py --env-sweep,
-// tools/occupancy_sweep.sh and the A/B scripts load (SVSDCT_LIB=...).
+// Experiment knobs.  The PRODUCT build reads no environment variable at all: `knob()` folds to its compiled-in default, so
+// no variable can reroute a kernel, let alone touch the parity guarantee of a flag.  The experiments
+// library (-DSVS_EXPERIMENTS, lib/variants/libsvsdct_exp.so) reads SVS_GUARDED_OFF and SVS_STAGE_CHUNK_KB from the
+// environment on every call; the tests and tools/ab_bench.py --env-sweep load it (SVSDCT_LIB=...).
 #if defined(SVS_EXPERIMENTS)
 uint32_t knob(const char *name, uint32_t dflt) {
     const char *v = getenv(name);
@@ -87,11 +85,9 @@ void scale_tie(svs::QimParams &qp) {
 #endif
 }
 
-// Occupancy cap: unused dynamic LDS such that at most `wg_per_cu` workgroups fit the CU's 160 KB (0 = no cap).  The
-// streaming kernels run FASTER with fewer waves in flight than their register count allows (measured sweeps in
-// profiles/history/r01_ab_occupancy.txt): fewer concurrent row streams per CU.
+// Occupancy cap: unused dynamic LDS such that at most `wg_per_cu` workgroups fit the CU's 160 KB.  The one-row embed kernel
+// runs FASTER with fewer waves in flight than its register count allows (see embed_wg_per_cu).
 uint32_t lds_pad_for(uint32_t wg_per_cu, uint32_t static_lds) {
-    if (wg_per_cu == 0) return 0;
     const uint32_t per_wg = (160u * 1024u / wg_per_cu) & ~255u;
     return per_wg > static_lds ? per_wg - static_lds : 0;
 }
@@ -135,15 +131,16 @@ uint64_t span_bytes(const svs_planes *p) {
 using svs::rows_for;
 
 // ---- launch tuning (measured on MI355X, 600 x 4K frames; profiles/history/r01_ab_variants.txt) ----------------
-// * workgroup -> tile mapping (svs::tile_id): giving each XCD-group a contiguous eighth of the batch
-//   lifts the embed kernel ~+6..12 % (reads and writes of one XCD stay on neighbouring DRAM pages) and is
-//   never worse than the identity map; the read-only extract kernel at one coefficient row prefers runs of
-//   32 tiles per XCD (+3 %).
-// * two blocks per lane (16-byte accesses) pays only for the embed kernel at one coefficient row; with
-//   more rows the extra registers cost occupancy (n = 10: -17 %).
-// Overrides in the experiments library only (-DSVS_EXPERIMENTS, see knob()): SVS_EMBED_XCD_CHUNK, SVS_EXTRACT_XCD_CHUNK,
-// SVS_EMBED_BPL, SVS_EXTRACT_BPL.
+// * workgroup -> tile mapping (svs::tile_id): giving each XCD-group a contiguous eighth of the batch lifts the embed kernels
+//   ~+6..12 % (reads and writes of one XCD stay on neighbouring DRAM pages) and is never worse than the identity map.  The
+//   read-only extract kernels (profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
+//   (+3 %); two rows (n = 8..15) - the identity map (+6.7 % at 600 x 4K, +4.4 % at 2 400 x 1080p over the contiguous eighth,
+//   equal at 300 x 1080p); more rows - VALU-bound, the map does not matter.
+// * two blocks per lane (16-byte accesses) pays only for the embed kernel at one coefficient row; with more rows the extra
+//   registers cost occupancy (n = 10: -17 %).
 constexpr uint32_t kEighth = 0xFFFFFFFFu;
+
+uint32_t extract_chunk(int rows) { return rows == 1 ? 32u : (rows == 2 ? 0u : kEighth); }
 
 bool rows_allow_two_blocks(const svs_planes *p, const void *a, const void *b) {
     return ((p->width / 8) % 2 == 0) && (p->row_pitch % 16 == 0) && (p->frame_pitch % 16 == 0) &&
@@ -152,42 +149,14 @@ bool rows_allow_two_blocks(const svs_planes *p, const void *a, const void *b) {
 
 using svs::make_qim;
 
-struct Tuning {
-    bool two_blocks;
-    uint32_t chunk;
-};
-
-#ifndef SVS_U2_BPL
-#define SVS_U2_BPL 1   // blocks per lane of the two-row embed kernel (build knob for the A/B)
-#endif
-Tuning embed_tuning(int rows, const svs_planes *p, const void *a, const void *b) {
-    Tuning t{rows == 1 || (rows == 2 && SVS_U2_BPL == 2), kEighth};
-    t.two_blocks = (rows == 1 || (rows == 2 && SVS_U2_BPL == 2)) && knob("SVS_EMBED_BPL", t.two_blocks ? 2 : 1) == 2;
-    t.chunk = knob("SVS_EMBED_XCD_CHUNK", t.chunk);
-    t.two_blocks = t.two_blocks && rows_allow_two_blocks(p, a, b);
-    return t;
-}
-
-Tuning extract_tuning(int rows, const svs_planes *p, const void *a) {
-    // tile map of the read-only kernels (A/B sweeps: profiles/history/r01_ab_variants.txt, profiles/history/r02_ab_extract_chunk.txt): one
-    // coefficient row - runs of 32 tiles per XCD; two rows (n = 8..15) - the identity map (+6.7 % at 600 x 4K, +4.4 % at
-    // 2 400 x 1080p over the contiguous eighth, equal at 300 x 1080p); more rows - VALU-bound, the map does not matter
-    Tuning t{false, rows == 1 ? 32u : (rows == 2 ? 0u : kEighth)};
-    t.two_blocks = rows <= 2 && knob("SVS_EXTRACT_BPL", 1) == 2;
-    t.chunk = knob("SVS_EXTRACT_XCD_CHUNK", t.chunk);
-    t.two_blocks = t.two_blocks && rows_allow_two_blocks(p, a, nullptr);
-    return t;
-}
-
-// default caps (workgroups of 256 threads per CU = waves per SIMD; 0 = whatever registers and LDS allow).  Round 6, the
-// integer-domain one-row embed kernel (66 - 71 VGPRs: 7 waves per SIMD uncapped): measured with pure copies, the rate of this
-// access pattern falls - and its dependence on where the buffers were placed grows - with the BYTES IN FLIGHT per SIMD (rows per
-// lane x waves: 8 x 4 behaves like 16 x 2 and 4 x 8, profiles/r06_stream_probe.txt); the kernel is fastest at 4 - 5 waves with
-// two blocks per lane (1.52 / 1.61 ms per 600 x 4K on fast / slow placements against 1.55 - 1.70 uncapped, the same at n = 1, 7
-// and at 1080p: profiles/r06_place_new_vs_old.txt, r06_caps.txt) and at 6 with one block per lane.  Every extract kernel, the
-// embed kernels with more rows, the exact kernels and a plain copy have always been fastest uncapped (tools/occupancy_sweep.sh).
-uint32_t embed_wg_per_cu(int rows, int bpl) { return rows == 1 ? (bpl == 2 ? 4u : 6u) : 0u; }
-uint32_t extract_wg_per_cu(int rows) { (void)rows; return 0; }
+// Occupancy cap of the one-row embed kernel (workgroups of 256 threads per CU = waves per SIMD).  Round 6, the integer-domain
+// kernel (66 - 71 VGPRs: 7 waves per SIMD uncapped): measured with pure copies, the rate of this access pattern falls - and its
+// dependence on where the buffers were placed grows - with the BYTES IN FLIGHT per SIMD (rows per lane x waves: 8 x 4 behaves
+// like 16 x 2 and 4 x 8, profiles/r06_stream_probe.txt); the kernel is fastest at 4 - 5 waves with two blocks per lane (1.52 /
+// 1.61 ms per 600 x 4K on fast / slow placements against 1.55 - 1.70 uncapped, the same at n = 1, 7 and at 1080p:
+// profiles/r06_place_new_vs_old.txt, r06_caps.txt) and at 6 with one block per lane.  Every other kernel has always been
+// fastest uncapped.
+uint32_t embed_wg_per_cu(int bpl) { return bpl == 2 ? 4u : 6u; }
 
 // Measurement hook of the EXPERIMENTS library only (svs_guard_counter_set): a device counter the streaming embed launches add
 // the number of blocks they redid exactly to.  The product library has neither the global nor the kernel parameter: no state
@@ -199,8 +168,7 @@ unsigned long long *g_guard_counter = nullptr;
 #define SVS_COUNTER_ARG
 #endif
 
-// static LDS of the one-row embed_kernel (the waves' worklists and transposition tiles; the two-row kernel with parked rows
-// has 29 696 B): only the experiments library's occupancy-cap knob uses it
+// static LDS of embed_row1_kernel (the waves' worklists and transposition tiles)
 constexpr uint32_t kEmbedLds = (SVS_WG / 64) * (SVS_GUARD_CAP * sizeof(svs::GuardEntry) + 8 * SVS_GUARD_TILE * sizeof(float));
 
 template <int QM, int BPL>
@@ -208,76 +176,44 @@ int launch_embed(int rows, uint64_t total, hipStream_t st, const uint8_t *gray, 
                  const svs::QimParams &qp, const uint32_t *bits, uint64_t bit_offset, uint64_t n_bits,
                  uint32_t n_words) {
     const dim3 grid((uint32_t)((total + SVS_WG * BPL - 1) / (SVS_WG * BPL)));
-    // (the occupancy cap is an experiments knob; the two-row kernel's parked form has 29 696 B of static LDS, the others kEmbedLds)
-    const uint32_t lds_pad = lds_pad_for(knob("SVS_EMBED_WG_PER_CU", embed_wg_per_cu(rows, BPL)),
-                                         rows == 2 && QM != svs::QM_POW2 ? 29696u : kEmbedLds);
-    if constexpr (BPL == 1) {
-        // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation of the two-row kernel
-        if (rows == 2 && g.n_ac == 10 && knob("SVS_FIXED_N", 1) != 0) {
-            hipLaunchKernelGGL((svs::embed_kernel<2, QM, 1, 10>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, bit_offset,
-                               n_bits, n_words SVS_COUNTER_ARG);
-            SVS_HIP(hipGetLastError());
-            return SVS_OK;
-        }
-    }
-    if (rows < 1 || rows > 2) return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d, %d blocks per lane", rows, BPL);
-    if (rows == 1) {   // one coefficient row: the integer-domain kernel (round 6; the round-5 kernel it replaced: commit a377b8d, experiments library, SVS_ROW1_OLD=1)
+    if (rows == 1) {   // one coefficient row: the integer-domain kernel (round 6), under its occupancy cap
+        const uint32_t lds_pad = lds_pad_for(embed_wg_per_cu(BPL), kEmbedLds);
         hipLaunchKernelGGL((svs::embed_row1_kernel<QM, BPL>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, bit_offset, n_bits,
                            n_words SVS_COUNTER_ARG);
-        SVS_HIP(hipGetLastError());
-        return SVS_OK;
-    }
-    if constexpr (BPL == 2) {
-#if SVS_U2_BPL == 2   // A/B build only: two adjacent blocks per lane with a joint replay need 150 VGPRs (3 waves per SIMD) and end
-                      // level with one block per lane (2.57 vs 2.57 ms per 600 x 4K, profiles/r04_ab_two_row.txt)
+    } else if (rows == 2 && BPL == 1) {
+        // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
         if (g.n_ac == 10)
-            hipLaunchKernelGGL((svs::embed_kernel<2, QM, 2, 10>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, bit_offset, n_bits,
+            hipLaunchKernelGGL((svs::embed_kernel<2, QM, 1, 10>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits, bit_offset, n_bits,
                                n_words SVS_COUNTER_ARG);
         else
-            hipLaunchKernelGGL((svs::embed_kernel<2, QM, 2>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, bit_offset, n_bits,
+            hipLaunchKernelGGL((svs::embed_kernel<2, QM, 1>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits, bit_offset, n_bits,
                                n_words SVS_COUNTER_ARG);
-#else
-        return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d with two blocks per lane", rows);
-#endif
     } else {
-        hipLaunchKernelGGL((svs::embed_kernel<2, QM, 1>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, bit_offset, n_bits,
-                           n_words SVS_COUNTER_ARG);
+        return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d, %d blocks per lane", rows, BPL);
     }
     SVS_HIP(hipGetLastError());
     return SVS_OK;
 }
 
-template <int QM, int BPL>
+template <int QM>
 int launch_extract(int rows, uint64_t total, hipStream_t st, const uint8_t *gray, const svs::Geometry &g,
                    const svs::QimParams &qp, uint8_t *out, uint64_t out_bytes) {
-    const dim3 grid((uint32_t)((total + SVS_WG * BPL - 1) / (SVS_WG * BPL)));
+    const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
     // n = 10 (the reference GUI's default) has a compile-time-n instantiation of the extract kernel: +1..7 %
     // (profiles/history/r01_ab_quant_exact.txt).  The same specialisation of the embed kernel measured SLOWER (-13 % at
     // 600 x 4K, n = 10) and n = 3 gains nothing (HBM-bound), so those stay on the run-time-n kernels.
-    const bool fixed_n = knob("SVS_FIXED_N", 1) != 0;   // experiment knob
-    const uint32_t lds_pad = lds_pad_for(knob("SVS_EXTRACT_WG_PER_CU", extract_wg_per_cu(rows)), 18432);
-    if (fixed_n && g.n_ac == 10) {
-        hipLaunchKernelGGL((svs::extract_kernel<2, QM, BPL, 10>), grid, dim3(SVS_WG), lds_pad, st, gray, g, qp, out, out_bytes);
+    if (g.n_ac == 10) {
+        hipLaunchKernelGGL((svs::extract_kernel<2, QM, 1, 10>), grid, dim3(SVS_WG), 0, st, gray, g, qp, out, out_bytes);
         SVS_HIP(hipGetLastError());
         return SVS_OK;
     }
 #define SVS_CASE(R)                                                                                                  \
     case R:                                                                                                          \
-        hipLaunchKernelGGL((svs::extract_kernel<R, QM, BPL>), grid, dim3(SVS_WG), lds_pad, st, gray, g, qp, out, out_bytes); \
+        hipLaunchKernelGGL((svs::extract_kernel<R, QM, 1>), grid, dim3(SVS_WG), 0, st, gray, g, qp, out, out_bytes); \
         break;
-    if constexpr (BPL == 2) {  // two blocks per lane is only instantiated for one or two coefficient rows
-        switch (rows) {
-            SVS_CASE(1) SVS_CASE(2)
-            default: return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d with two blocks per lane", rows);
-        }
-    } else {
-        switch (rows) {   // one row takes the pocketfft-identical kernel (launch_extract_exact); SVS_FAST_EXTRACT_U1 is an experiments knob
-#if defined(SVS_EXPERIMENTS)
-            SVS_CASE(1)
-#endif
-            SVS_CASE(2) SVS_CASE(3) SVS_CASE(4) SVS_CASE(5) SVS_CASE(6) SVS_CASE(7) SVS_CASE(8)
-            default: return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
-        }
+    switch (rows) {   // one row takes the pocketfft-identical kernel (launch_extract_exact)
+        SVS_CASE(2) SVS_CASE(3) SVS_CASE(4) SVS_CASE(5) SVS_CASE(6) SVS_CASE(7) SVS_CASE(8)
+        default: return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
     }
 #undef SVS_CASE
     SVS_HIP(hipGetLastError());
@@ -286,43 +222,21 @@ int launch_extract(int rows, uint64_t total, hipStream_t st, const uint8_t *gray
 
 int launch_embed_exact(int qm, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
                        const svs::Geometry &g, const svs::QimParams &qp, const uint32_t *bits, uint64_t bit_offset,
-                       uint64_t n_bits, uint32_t n_words, bool pair = false) {
-    const uint32_t lds_pad = lds_pad_for(knob("SVS_EMBED_WG_PER_CU", 0), 0);
+                       uint64_t n_bits, uint32_t n_words) {
     // the kernel's quantiser loop is instantiated for one or two coefficient rows (n <= 7: the benchmark's 3; n <= 15: the
     // reference GUI's 10) and for all eight (any n): fewer wave-uniform tests per block, same arithmetic
     const int rows = rows_for((int)g.n_ac);
-    if (pair) {   // two adjacent blocks per lane, transforms packed over the pair (embed_exact_pair_kernel)
-        const dim3 grid2((uint32_t)((total + 2 * SVS_WG - 1) / (2 * SVS_WG)));
-#define SVS_GO2(QM)                                                                                                         \
-    do {                                                                                                                    \
-        if (rows == 1 && g.n_ac > 0)                                                                                        \
-            hipLaunchKernelGGL((svs::embed_exact_pair_kernel<QM, 1>), grid2, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, \
-                               bit_offset, n_bits, n_words);                                                                \
-        else if (rows == 2)                                                                                                 \
-            hipLaunchKernelGGL((svs::embed_exact_pair_kernel<QM, 2>), grid2, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, \
-                               bit_offset, n_bits, n_words);                                                                \
-        else                                                                                                                \
-            hipLaunchKernelGGL((svs::embed_exact_pair_kernel<QM, 8>), grid2, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, \
-                               bit_offset, n_bits, n_words);                                                                \
-    } while (0)
-        if (qm == svs::QM_DOUBLE) SVS_GO2(svs::QM_DOUBLE);
-        else if (qm == svs::QM_POW2) SVS_GO2(svs::QM_POW2);
-        else SVS_GO2(svs::QM_F32);
-#undef SVS_GO2
-        SVS_HIP(hipGetLastError());
-        return SVS_OK;
-    }
     const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
 #define SVS_GO(QM)                                                                                                          \
     do {                                                                                                                    \
         if (rows == 1 && g.n_ac > 0)                                                                                        \
-            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 1>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits,     \
+            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 1>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits,       \
                                bit_offset, n_bits, n_words);                                                                \
         else if (rows == 2)                                                                                                 \
-            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 2>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits,     \
+            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 2>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits,       \
                                bit_offset, n_bits, n_words);                                                                \
         else                                                                                                                \
-            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 8>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits,     \
+            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 8>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits,       \
                                bit_offset, n_bits, n_words);                                                                \
     } while (0)
     if (qm == svs::QM_DOUBLE) SVS_GO(svs::QM_DOUBLE);
@@ -333,26 +247,16 @@ int launch_embed_exact(int qm, uint64_t total, hipStream_t st, const uint8_t *gr
     return SVS_OK;
 }
 
-#ifndef SVS_EXTRACT_EXACT_BPL
-#define SVS_EXTRACT_EXACT_BPL 1   // blocks per lane of the one-row pocketfft-identical extract kernel.  Round 4 took 2 (16-byte row loads) on one
-                                  // in-process A/B (medians 0.768 vs 0.806 ms per 600 x 4K); the same A/B on four more boxes and against the round-2
-                                  // library has one block per lane ahead by 0.1 - 3 % on every large batch and level at 300 x 1080p
-                                  // (37 instead of 54 VGPRs): profiles/r05_ab_extract_bpl.txt.  Back to 1.
-#endif
+// (Round 4 took two blocks per lane for the one-row pocketfft-identical extract kernel on one in-process A/B; the same A/B on
+// four more boxes and against the round-2 library has one block per lane ahead by 0.1 - 3 % on every large batch and level at
+// 300 x 1080p, 37 instead of 54 VGPRs: profiles/r05_ab_extract_bpl.txt.)
 template <int QM>
 int launch_extract_exact(int rows, uint64_t total, hipStream_t st, const uint8_t *gray, const svs::Geometry &g,
-                         const svs::QimParams &qp, uint8_t *out, uint64_t out_bytes, bool two_blocks = false) {
-    const uint32_t lds_pad = lds_pad_for(knob("SVS_EXTRACT_WG_PER_CU", extract_wg_per_cu(rows)), 4096);
-    if (two_blocks && rows == 1) {
-        const dim3 grid2((uint32_t)((total + 2 * SVS_WG - 1) / (2 * SVS_WG)));
-        hipLaunchKernelGGL((svs::extract_exact_kernel<1, QM, 2>), grid2, dim3(SVS_WG), lds_pad, st, gray, g, qp, out, out_bytes);
-        SVS_HIP(hipGetLastError());
-        return SVS_OK;
-    }
+                         const svs::QimParams &qp, uint8_t *out, uint64_t out_bytes) {
     const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
 #define SVS_CASE(R)                                                                                                  \
     case R:                                                                                                          \
-        hipLaunchKernelGGL((svs::extract_exact_kernel<R, QM>), grid, dim3(SVS_WG), lds_pad, st, gray, g, qp, out, out_bytes); \
+        hipLaunchKernelGGL((svs::extract_exact_kernel<R, QM>), grid, dim3(SVS_WG), 0, st, gray, g, qp, out, out_bytes); \
         break;
     switch (rows) {
         SVS_CASE(1) SVS_CASE(2) SVS_CASE(3) SVS_CASE(4) SVS_CASE(5) SVS_CASE(6) SVS_CASE(7) SVS_CASE(8)
@@ -524,16 +428,15 @@ int launch_embed_bgr(int rows, uint64_t total, hipStream_t st, const uint8_t *in
                             const svs::Geometry &g, const svs::ColourParams &c, const svs::QimParams &qp,
                             const uint32_t *bits, uint64_t bit_offset, uint64_t n_bits, uint32_t n_words) {
     const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
-    const uint32_t lds_pad = lds_pad_for(knob("SVS_EMBED_BGR_WG_PER_CU", 0), 16384);
     if constexpr (EXACT) {
-        hipLaunchKernelGGL((svs::embed_bgr_kernel<8, QM, true>), grid, dim3(SVS_WG), lds_pad, st, in, out, ref, g, c, qp, bits,
+        hipLaunchKernelGGL((svs::embed_bgr_kernel<8, QM, true>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
                            bit_offset, n_bits, n_words);
     } else {
         if (rows == 1)
-            hipLaunchKernelGGL((svs::embed_bgr_kernel<1, QM, false>), grid, dim3(SVS_WG), lds_pad, st, in, out, ref, g, c, qp, bits,
+            hipLaunchKernelGGL((svs::embed_bgr_kernel<1, QM, false>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
                                bit_offset, n_bits, n_words);
         else if (rows == 2)
-            hipLaunchKernelGGL((svs::embed_bgr_kernel<2, QM, false>), grid, dim3(SVS_WG), lds_pad, st, in, out, ref, g, c, qp, bits,
+            hipLaunchKernelGGL((svs::embed_bgr_kernel<2, QM, false>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
                                bit_offset, n_bits, n_words);
         else
             return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
@@ -582,15 +485,6 @@ int svs_device_arch(int device, char *buf, size_t buf_len) {
 int svs_malloc(void **dev_ptr, size_t bytes) {
     if (!dev_ptr) return fail(SVS_ERR_INVALID_ARG, "dev_ptr is NULL");
     *dev_ptr = nullptr;
-#if defined(SVS_EXPERIMENTS)
-    // experiment: physically contiguous device memory (hipDeviceMallocContiguous), falling back to a plain allocation
-    if (knob("SVS_MALLOC_CONTIG", 0) != 0 && bytes >= ((size_t)2 << 20)) {
-        if (hipExtMallocWithFlags(dev_ptr, bytes, hipDeviceMallocContiguous) == hipSuccess && *dev_ptr) return SVS_OK;
-        (void)hipGetLastError();
-        *dev_ptr = nullptr;
-        if (knob("SVS_MALLOC_CONTIG", 0) == 2) return fail(SVS_ERR_HIP, "contiguous allocation of %zu bytes failed", bytes);
-    }
-#endif
     SVS_HIP(hipMalloc(dev_ptr, bytes ? bytes : 4));
     return SVS_OK;
 }
@@ -676,9 +570,8 @@ int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *pla
         if (bit_offset + use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
     }
     const hipStream_t st = (hipStream_t)stream;
-    const Tuning tune = embed_tuning(rows_for(n), planes, d_gray, d_stego);
-    const bool two = tune.two_blocks;
-    g.xcd_chunk = tune.chunk;
+    const bool two = rows_for(n) == 1 && rows_allow_two_blocks(planes, d_gray, d_stego);
+    g.xcd_chunk = kEighth;
     svs::QimParams qp;
     const int qm = make_qim(use == 0 ? 1.0 : delta, &qp);
     if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
@@ -691,13 +584,8 @@ int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *pla
     const bool in_range = delta >= SVS_GUARD_DELTA_MIN && delta <= SVS_GUARD_DELTA_MAX;
     bool streaming = use > 0 && in_range && !(flags & SVS_EXACT_POCKETFFT) && rows <= 2;
 #if defined(SVS_EXPERIMENTS)
-    if (knob("SVS_GUARDED_OFF", 0) != 0 || (rows == 2 && knob("SVS_GUARDED2_OFF", 0) != 0)) streaming = false;   // A/B: exact kernel
+    if (knob("SVS_GUARDED_OFF", 0) != 0) streaming = false;   // test hook: the exact kernel
 #endif
-    // SVS_EXACT_BPL=2 (experiment knob): exact arithmetic on two adjacent blocks per lane with every transform instruction
-    // packed over the pair (embed_exact_pair_kernel).  Measured SLOWER than the one-block kernel (3.54 vs 3.16 ms at n = 3,
-    // 4.83 vs 3.38 ms at n = 10, profiles/history/r02_ab_exact_pair.txt): a v_pk_*_f32 costs two issue slots on this chip, so
-    // halving the instruction count buys nothing and the 256-register footprint costs occupancy.  Off by default.
-    const bool exact_pair = rows_allow_two_blocks(planes, d_gray, d_stego) && knob("SVS_EXACT_BPL", 1) == 2;
     if (!streaming) {
         if (use == 0 && n_bits == 0) {   // empty payload: the reference's loops break before the first block - a pure copy
             if (d_gray == d_stego) return SVS_OK;
@@ -705,19 +593,18 @@ int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *pla
             return two ? launch_embed<svs::QM_F32, 2>(1, total, st, d_gray, d_stego, g, qp, nullptr, 0, 0, 0)
                        : launch_embed<svs::QM_F32, 1>(1, total, st, d_gray, d_stego, g, qp, nullptr, 0, 0, 0);
         }
-        g.xcd_chunk = knob("SVS_EMBED_XCD_CHUNK", kEighth);
         if (use == 0) {
             // a non-empty payload of which nothing can be embedded (delta <= 0, no coefficients): the reference still
             // enters and round-trips every block (config_and_setup.py:143-145,166-169); only the exact arithmetic
             // reproduces what that does to the pixels, so every mode takes that kernel here
             g.n_ac = 0;
-            return launch_embed_exact(svs::QM_F32, total, st, d_gray, d_stego, g, qp, nullptr, 0, 1, 0, exact_pair);
+            return launch_embed_exact(svs::QM_F32, total, st, d_gray, d_stego, g, qp, nullptr, 0, 1, 0);
         }
         const uint64_t words_x = ((bit_offset + use + 7) / 8 + 3) / 4;
         if (words_x >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
         if (int rc = launch_embed_exact(qm, total, st, d_gray, d_stego, g, qp,
                                         reinterpret_cast<const uint32_t *>(d_bits_packed), bit_offset, use,
-                                        (uint32_t)words_x, exact_pair))
+                                        (uint32_t)words_x))
             return rc;
         if (n_embedded) *n_embedded = use;
         return SVS_OK;
@@ -762,8 +649,7 @@ int svs_extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delt
     if (!(delta > 0.0)) {
         SVS_HIP(hipMemsetAsync(d_bits_packed_out, 0, bytes, st));  // every bit '0' (config_and_setup.py:143-145)
     } else {
-        const Tuning tune = extract_tuning(rows_for(n), planes, d_gray);
-        g.xcd_chunk = tune.chunk;
+        g.xcd_chunk = extract_chunk(rows_for(n));
         svs::QimParams qp;
         const int qm = make_qim(delta, &qp);     // the double mode only differs in requantisation: not needed here
         scale_tie(qp);                           // experiments library only
@@ -782,40 +668,12 @@ int svs_extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delt
         // With one coefficient row (n <= 7) the pocketfft-identical forward transform costs 0.2-3 % (the kernel stays
         // HBM-bound; in-process A/B in profiles/history/r01_ab_quant_exact.txt), so FAST mode uses it too and extraction is
         // bit-identical to the reference for ANY input frame.  With more rows it costs ~17 % and stays opt-in.
-        // SVS_FAST_EXTRACT_U1=1 (experiment knob) selects the FMA-factored forward instead.
-#if defined(SVS_EXPERIMENTS)
-        if (rows == 1 && !(flags & SVS_EXACT_POCKETFFT) && knob("SVS_EXTRACT_SHUFFLE", 0) == 1) {
-            // layout experiment: LDS-staged tiles, 8 lanes per block, cross-lane vertical pass (svs_device.hpp)
-            const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
-            if (qm == svs::QM_POW2)
-                hipLaunchKernelGGL((svs::extract_shuffle_kernel<svs::QM_POW2>), grid, dim3(SVS_WG), 0, st, d_gray, g, qp,
-                                   d_bits_packed_out, bytes);
-            else
-                hipLaunchKernelGGL((svs::extract_shuffle_kernel<svs::QM_F32>), grid, dim3(SVS_WG), 0, st, d_gray, g, qp,
-                                   d_bits_packed_out, bytes);
-            SVS_HIP(hipGetLastError());
-            rc = SVS_OK;
-        } else
-#endif
-        if ((flags & SVS_EXACT_POCKETFFT) || (rows == 1 && knob("SVS_FAST_EXTRACT_U1", 0) == 0)) {
-            const bool two_x = rows == 1 && knob("SVS_EXTRACT_EXACT_BPL", SVS_EXTRACT_EXACT_BPL) == 2 &&
-                               rows_allow_two_blocks(planes, d_gray, nullptr);
-            rc = qm == svs::QM_POW2 ? launch_extract_exact<svs::QM_POW2>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes, two_x)
-                                    : launch_extract_exact<svs::QM_F32>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes, two_x);
-        } else if (qm == svs::QM_POW2)
-#if defined(SVS_EXPERIMENTS)   // two blocks per lane in the FMA-factored extract kernels: -3 % / +1.5 % (profiles/history/r02_ab_extract_bpl.txt), experiments library only
-            rc = tune.two_blocks ? launch_extract<svs::QM_POW2, 2>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes)
-                                 : launch_extract<svs::QM_POW2, 1>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
-#else
-            rc = launch_extract<svs::QM_POW2, 1>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
-#endif
+        if ((flags & SVS_EXACT_POCKETFFT) || rows == 1)
+            rc = qm == svs::QM_POW2 ? launch_extract_exact<svs::QM_POW2>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes)
+                                    : launch_extract_exact<svs::QM_F32>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
         else
-#if defined(SVS_EXPERIMENTS)
-            rc = tune.two_blocks ? launch_extract<svs::QM_F32, 2>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes)
-                                 : launch_extract<svs::QM_F32, 1>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
-#else
-            rc = launch_extract<svs::QM_F32, 1>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
-#endif
+            rc = qm == svs::QM_POW2 ? launch_extract<svs::QM_POW2>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes)
+                                    : launch_extract<svs::QM_F32>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
         if (rc) return rc;
     }
     if (n_bits_out) *n_bits_out = cap;
@@ -920,7 +778,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
     // one chunk (a frame below 8 MB): everything in order on one stream - no event, no second stream
     uint32_t n_chunks = 0;
     for_each_chunk(planes->n_frames, H, (size_t)rp, stage_chunk_bytes(span), [&](const Chunk &) { ++n_chunks; });
-    const bool serial = n_chunks <= 1 || knob("SVS_STAGE_MODE", 0) == 2;
+    const bool serial = n_chunks <= 1;
     hipStream_t up = c.st[0], st = serial ? c.st[0] : c.st[1];
     for_each_chunk(planes->n_frames, H, (size_t)rp, stage_chunk_bytes(span), [&](const Chunk &ch) {
         if (rc) return;
@@ -1159,7 +1017,7 @@ int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_
         svs::make_guard(delta, rows_n, &qp);
         scale_guard(qp);   // experiments library only
     }
-    g.xcd_chunk = knob("SVS_EMBED_XCD_CHUNK", kEighth);
+    g.xcd_chunk = kEighth;
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t *bw = reinterpret_cast<const uint32_t *>(d_bits_packed);
     uint64_t kernel_bits = use;
@@ -1214,7 +1072,7 @@ int svs_extract_bgr_dev(const uint8_t *d_bgr, int64_t bgr_row_pitch, int64_t bgr
         svs::QimParams qp;
         const int qm = make_qim(delta, &qp);
         scale_tie(qp);   // experiments library only
-        g.xcd_chunk = knob("SVS_EXTRACT_XCD_CHUNK", rows_for(n) == 1 ? 32u : kEighth);
+        g.xcd_chunk = rows_for(n) == 1 ? 32u : kEighth;
         const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
         const int rows = rows_for(n);
         // tiny steps: the rounding constant of the two-step extraction needs |c / delta| < 2^22 (as in svs_extract_dev)
@@ -1284,7 +1142,7 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
     int rc = SVS_OK;
     uint32_t n_chunks = 0;
     for_each_chunk(planes->n_frames, H, (size_t)rp3, stage_chunk_bytes(3 * px), [&](const Chunk &) { ++n_chunks; });
-    const bool serial = n_chunks <= 1 || knob("SVS_STAGE_MODE", 0) == 2;
+    const bool serial = n_chunks <= 1;
     hipStream_t up = c.st[0], st = serial ? c.st[0] : c.st[1];
     for_each_chunk(planes->n_frames, H, (size_t)rp3, stage_chunk_bytes(3 * px), [&](const Chunk &ch) {   // frames are tightly packed: every chunk is one run of bytes
         if (rc) return;
@@ -1460,7 +1318,6 @@ int svs_ref_copy_dev(const void *d_src, void *d_dst, uint64_t bytes, int mode, v
     const hipStream_t st = (hipStream_t)stream;
     const auto *s = reinterpret_cast<const svs::u32x4 *>(d_src);
     auto *d = reinterpret_cast<svs::u32x4 *>(d_dst);
-    const uint32_t pad = lds_pad_for(knob("SVS_COPY_WG_PER_CU", 0), 0);  // experiment knob
     if (mode == 8 || mode == 9) {   // 8: 16-byte loads + 8-byte stores, 9: 8-byte loads + 16-byte stores
         const dim3 grid((uint32_t)((bytes / 16 + 255) / 256));
         if (mode == 8) hipLaunchKernelGGL(svs::copy_mixed_kernel<1>, grid, dim3(256), 0, st, (const uint8_t *)d_src, (uint8_t *)d_dst, bytes);
@@ -1472,17 +1329,17 @@ int svs_ref_copy_dev(const void *d_src, void *d_dst, uint64_t bytes, int mode, v
         const uint64_t n8 = bytes / 8;
         const auto *s8 = reinterpret_cast<const svs::u32x2 *>(d_src);
         auto *d8 = reinterpret_cast<svs::u32x2 *>(d_dst);
-        if (mode == 6) hipLaunchKernelGGL(svs::copy8_kernel<1>, dim3((uint32_t)((n8 + 255) / 256)), dim3(256), pad, st, s8, d8, n8);
-        else hipLaunchKernelGGL(svs::copy8_kernel<0>, dim3((uint32_t)((n8 + 255) / 256)), dim3(256), pad, st, s8, d8, n8);
+        if (mode == 6) hipLaunchKernelGGL(svs::copy8_kernel<1>, dim3((uint32_t)((n8 + 255) / 256)), dim3(256), 0, st, s8, d8, n8);
+        else hipLaunchKernelGGL(svs::copy8_kernel<0>, dim3((uint32_t)((n8 + 255) / 256)), dim3(256), 0, st, s8, d8, n8);
         SVS_HIP(hipGetLastError());
         return SVS_OK;
     }
-    if (mode == 0) hipLaunchKernelGGL(svs::copy_kernel<0>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), pad, st, s, d, n16);
-    else if (mode == 3) hipLaunchKernelGGL(svs::copy_kernel<3>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), pad, st, s, d, n16);
-    else if (mode == 4) hipLaunchKernelGGL(svs::copy_kernel<4>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), pad, st, s, d, n16);
-    else if (mode == 5) hipLaunchKernelGGL(svs::copy_kernel<5>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), pad, st, s, d, n16);
-    else if (mode == 1) hipLaunchKernelGGL(svs::copy_kernel<1>, dim3(256 * 8), dim3(256), pad, st, s, d, n16);
-    else hipLaunchKernelGGL(svs::copy_kernel<2>, dim3(256 * 8), dim3(256), pad, st, s, d, n16);
+    if (mode == 0) hipLaunchKernelGGL(svs::copy_kernel<0>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, st, s, d, n16);
+    else if (mode == 3) hipLaunchKernelGGL(svs::copy_kernel<3>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, st, s, d, n16);
+    else if (mode == 4) hipLaunchKernelGGL(svs::copy_kernel<4>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, st, s, d, n16);
+    else if (mode == 5) hipLaunchKernelGGL(svs::copy_kernel<5>, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, st, s, d, n16);
+    else if (mode == 1) hipLaunchKernelGGL(svs::copy_kernel<1>, dim3(256 * 8), dim3(256), 0, st, s, d, n16);
+    else hipLaunchKernelGGL(svs::copy_kernel<2>, dim3(256 * 8), dim3(256), 0, st, s, d, n16);
     SVS_HIP(hipGetLastError());
     return SVS_OK;
 }

@@ -71,15 +71,10 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Frames are streamed exactly once: non-temporal loads/stores keep them from displacing each other
 // in L2 / Infinity Cache (measured on MI355X: embed +5 %, extract +11 %, profiles/history/r01_ab_variants.txt)
-#if !defined(SVS_NO_NONTEMPORAL)
 #define SVS_LD(p) __builtin_nontemporal_load(p)
 #define SVS_ST(v, p) __builtin_nontemporal_store(v, p)
-#else
-#define SVS_LD(p) (*(p))
-#define SVS_ST(v, p) (*(p) = (v))
-#endif
 
-// Lanes own one block (8-byte row accesses) or two horizontally adjacent blocks A|B (BPL = 2:
+// Lanes own one block (8-byte row accesses) or, in the one-row embed kernel, two horizontally adjacent blocks A|B (BPL = 2:
 // one 16-byte access per row).  Rows travel as native 2- / 4-dword vectors; the per-block arithmetic
 // works on plain scalar arrays filled from them (this exact shape is what hipcc scalarises fully -
 // structs of rows updated in place ended up in LDS).
@@ -98,7 +93,6 @@ __device__ __forceinline__ void load_rows(const uint8_t *src, int64_t row_pitch,
 
 template <int BPL>
 __device__ __forceinline__ void store_rows(uint8_t *dst, int64_t row_pitch, const typename RowVec<BPL>::type (&v)[8]) {
-#if !defined(SVS_NO_STORE_SC1)
     // write-through (sc1) stores: the line is not kept in the XCD's L2 (measured against non-temporal stores,
     // profiles/history/r01_ab_quant_exact.txt: one-shot copy 6.74 vs 6.55 TB/s; embed +1.5 % at n = 3, +9.5 % at n = 10).  The data registers must not be reused before
     // the store has read them: s_nop 1 inside the string (cdna_hip_programming.md section 5.7 item 1).
@@ -109,10 +103,6 @@ __device__ __forceinline__ void store_rows(uint8_t *dst, int64_t row_pitch, cons
         else
             asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst + r * row_pitch), "v"(v[r]) : "memory");
     }
-#else
-#pragma unroll
-    for (int r = 0; r < 8; ++r) SVS_ST(v[r], reinterpret_cast<typename RowVec<BPL>::type *>(dst + r * row_pitch));
-#endif
 }
 
 // Tail of the extract kernels: a wavefront's 64*BPL consecutive blocks produce exactly n*BPL aligned
@@ -247,151 +237,58 @@ __device__ __forceinline__ void extract_phase2(GuardEntry *entries, float *tile,
 }
 
 // ---------------------------------------------------------------------------------------
-// EXTRACT: one lane = BPL adjacent blocks; a wavefront's 64*BPL blocks produce exactly n*BPL
+// EXTRACT: one lane = one block; a wavefront's 64 blocks produce exactly n
 // aligned 64-bit words of the packed stream (stream bit = global block * n + i), assembled through
 // a wave-private LDS byte array and written with plain dword stores - no atomics, no pre-zeroed
 // output.  HBM traffic per block: 64 B read + n bits written.
 // ---------------------------------------------------------------------------------------
 #define SVS_EXTRACT_CAP 16   // worklist entries per wave and round of the extract kernels
+// BPL (blocks per lane) is always 1 here and in the other non-row1 kernels; it stays in their template parameter lists so that
+// the kernel symbols match the ones the traces under profiles/ name.
 template <int U, int QM, int BPL, int NFIX = 0>
 __global__ __launch_bounds__(SVS_WG) void extract_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                       const QimParams qp, uint8_t *__restrict__ out,
                                                       const uint64_t out_bytes) {
-    __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(BPL)];
+    static_assert(BPL == 1, "one block per lane");
+    __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
     __shared__ GuardEntry entries[SVS_WG / 64][SVS_EXTRACT_CAP];
     __shared__ float tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t tile = tile_id(g.xcd_chunk);
-    const uint32_t gblock = (tile * (uint32_t)SVS_WG + threadIdx.x) * BPL;
+    const uint32_t gblock = tile * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t n = g.n_ac;
 
-    // each block's bits, MSB first: bit i at position 63-i of hi:lo
-    uint32_t hi_a = 0, lo_a = 0, hi_b = 0, lo_b = 0;
-    uint32_t ax[8], ay[8], bx[8], by[8];
-    bool tie_a = false, tie_b = false;
-    float off_a = 0.0f, off_b = 0.0f;
+    // the block's bits, MSB first: bit i at position 63-i of hi:lo
+    uint32_t hi = 0, lo = 0, hb = 0, lb = 0;
+    uint32_t ax[8], ay[8];
+    bool tie = false;
+    float off = 0.0f;
     if (gblock < g.total_blocks) {
-        typename RowVec<BPL>::type v[8];
-        load_rows<BPL>(gray + block_offset(gblock, g), g.row_pitch, v);
+        u32x2 v[8];
+        load_rows<1>(gray + block_offset(gblock, g), g.row_pitch, v);
 #pragma unroll
         for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
-        tie_a = extract_block_cheap<U, QM, NFIX>(ax, ay, n, qp, hi_a, lo_a, off_a);      // -> candidate
-        if constexpr (BPL == 2) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { bx[r] = v[r].z; by[r] = v[r].w; }
-            tie_b = extract_block_cheap<U, QM, NFIX>(bx, by, n, qp, hi_b, lo_b, off_b);
-        }
+        tie = extract_block_cheap<U, QM, NFIX>(ax, ay, n, qp, hi, lo, off);      // -> candidate
     }
     // Step two only in waves with a candidate (svs_block.hpp): pocketfft's own flat index 4 and the per-block tie margin.
     // Stego frames at delta >= 8 have none: one ballot.  (Round 3 computed both for every block: +3..7 % on stego frames.)
-    if (__ballot(tie_a || tie_b) != 0) {
-        if (gblock < g.total_blocks) {
-            tie_a = extract_block_settle<QM>(ax, ay, n, qp, hi_a, off_a);
-            if constexpr (BPL == 2) tie_b = extract_block_settle<QM>(bx, by, n, qp, hi_b, off_b);
-        }
+    if (__ballot(tie) != 0) {
+        if (gblock < g.total_blocks) tie = extract_block_settle<QM>(ax, ay, n, qp, hi, off);
     }
     // A quantiser input within the per-block error bound of a rounding tie (svs_block.hpp, SVS_TIE2_*): those blocks get the
     // pocketfft-identical transform from eight lanes each (wave-private worklist).  Never taken on stego frames at delta >= 8.
-    extract_phase2<QM, BPL == 2, SVS_EXTRACT_CAP>(&entries[wave][0], &tiles[wave][0], lane, n, qp, tie_a, ax, ay, hi_a, lo_a,
-                                                  tie_b, bx, by, hi_b, lo_b);
-    emit_wave_bits<U, BPL>(&flags[wave][0], lane, ((uint64_t)tile * (uint32_t)SVS_WG + wave * 64u) * BPL, n, hi_a, lo_a,
-                           hi_b, lo_b, out, out_bytes);
+    extract_phase2<QM, false, SVS_EXTRACT_CAP>(&entries[wave][0], &tiles[wave][0], lane, n, qp, tie, ax, ay, hi, lo, false, ax, ay, hb, lb);
+    emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
 }
-
-#if defined(SVS_EXPERIMENTS)   // experiments library only (make variants -> lib/variants/libsvsdct_exp.so)
-// ---------------------------------------------------------------------------------------
-// Layout experiment (SVS_EXTRACT_SHUFFLE=1, one coefficient row, FAST arithmetic): the north-star's sketch taken
-// literally - tiles staged in LDS, 8 lanes per block (one pixel row each), the vertical pass as cross-lane (DPP)
-// butterflies, one coefficient per lane.  Kept for the A/B in profiles/history/r01_ab_layout.txt; the shipped kernels keep a
-// whole block in one lane.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float dpp_add(float x, int ctrl_is) {  // x + x from the partner lane
-    // ctrl_is: 0 = xor 1 (quad_perm 1,0,3,2), 1 = xor 2 (quad_perm 2,3,0,1), 2 = mirror inside the 8-lane group
-    const int xi = __builtin_bit_cast(int, x);
-    int yi;
-    if (ctrl_is == 0) yi = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-    else if (ctrl_is == 1) yi = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-    else yi = __builtin_amdgcn_update_dpp(0, xi, 0x141, 0xF, 0xF, false);
-    return x + __builtin_bit_cast(float, yi);
-}
-
-template <int QM>
-__global__ __launch_bounds__(SVS_WG) void extract_shuffle_kernel(const uint8_t *__restrict__ gray, const Geometry g,
-                                                               const QimParams qp, uint8_t *__restrict__ out,
-                                                               const uint64_t out_bytes) {
-    __shared__ __attribute__((aligned(16))) u32x2 tiles[SVS_WG / 64][8][64];
-    __shared__ uint32_t words[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t tile = tile_id(g.xcd_chunk);
-    const uint32_t gblock = tile * (uint32_t)SVS_WG + threadIdx.x, wave_first = gblock - lane;
-    const uint32_t n = g.n_ac;
-    if (gblock < g.total_blocks) {  // stage the wave's 64 blocks: coalesced 512-byte rows, as in the shipped kernels
-        typename RowVec<1>::type v[8];
-        load_rows<1>(gray + block_offset(gblock, g), g.row_pitch, v);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) tiles[wave][r][lane] = v[r];
-    }
-    uint32_t *mine = &words[wave][0];
-    for (uint32_t w = lane; w < 2u * n + 4u; w += 64u) mine[w] = 0u;
-    wave_lds_fence();
-    const uint32_t r = lane & 7u;
-    // this lane's row of the orthonormal DCT-II matrix: k_r(x) = a(r) cos((2x+1) r pi/16), times a(0) of the vertical pass
-    float kr[8];
-#pragma unroll
-    for (int x = 0; x < 8; ++x)
-        kr[x] = (r == 0 ? 0.35355339059327373f : 0.5f) * __cosf((float)((2 * x + 1) * (int)r) * 0.19634954084936207f) *
-                0.35355339059327373f;
-#pragma unroll 1
-    for (uint32_t p = 0; p < 8; ++p) {
-        const uint32_t blk = 8u * p + (lane >> 3);
-        const u32x2 v = tiles[wave][r][blk];
-        float s[8] = {ubyte_to_float<0>(v.x), ubyte_to_float<1>(v.x), ubyte_to_float<2>(v.x), ubyte_to_float<3>(v.x),
-                      ubyte_to_float<0>(v.y), ubyte_to_float<1>(v.y), ubyte_to_float<2>(v.y), ubyte_to_float<3>(v.y)};
-#pragma unroll
-        for (int x = 0; x < 8; ++x) s[x] = dpp_add(dpp_add(dpp_add(s[x], 0), 1), 2);  // column sums, in every lane
-        float c = s[0] * kr[0];
-#pragma unroll
-        for (int x = 1; x < 8; ++x) c = fmaf(s[x], kr[x], c);
-        // parity of every lane's coefficient as a wave mask (bit 8b + r), regrouped into the pass's 8n stream bits
-        // (block-major, coefficient 1 first) by a second ballot, then ORed into the wave's big-endian words by lane 0
-        const bool odd = r >= 1 && r <= n && wave_first + blk < g.total_blocks && ((uint32_t)quant_index<QM>(c, qp) & 1u);
-        const uint64_t m = __ballot(odd);
-        const uint32_t src = 8u * (lane / n) + (lane % n) + 1u;  // lane i < 8n picks block i / n, coefficient i % n + 1
-        const uint64_t packed = __ballot(lane < 8u * n && ((m >> (src & 63u)) & 1ull));  // stream bit i of the pass = bit i
-        if (lane == 0) {
-            const uint64_t be = __builtin_bitreverse64(packed);  // stream bit 0 -> bit 63
-            const uint32_t at = 8u * p * n, d = at >> 5, o = at & 31u;
-            const uint32_t hi = (uint32_t)(be >> 32), lo = (uint32_t)be;
-            atomicOr(&mine[d], hi >> o);
-            atomicOr(&mine[d + 1], __builtin_amdgcn_alignbit(hi, lo, o));
-            atomicOr(&mine[d + 2], __builtin_amdgcn_alignbit(lo, 0u, o));
-        }
-    }
-    wave_lds_fence();
-    const uint64_t wave_byte0 = ((uint64_t)tile * (uint32_t)SVS_WG + wave * 64u) * n / 8u;
-    for (uint32_t w = lane; w < 2u * n; w += 64u) {
-        const uint32_t word = __builtin_bswap32(mine[w]);
-        const uint64_t at = wave_byte0 + 4ull * w;
-        if (at + 4 <= out_bytes) {
-            *reinterpret_cast<uint32_t *>(out + at) = word;
-        } else {
-            for (uint32_t j = 0; j < 4 && at + j < out_bytes; ++j) out[at + j] = (uint8_t)(word >> (8 * j));
-        }
-    }
-}
-
-#endif  // SVS_EXPERIMENTS
 
 // ---------------------------------------------------------------------------------------
 // EXACT-mode kernels (pocketfft-identical arithmetic, svs_block.hpp "EXACT mode"): one block per lane.
 // The embed kernel transforms all 64 coefficients both ways (about 2 700 VALU instructions per block),
 // so it is VALU-bound at roughly 40 % of the fast kernel's rate; it exists for bit-identical output.
 // ---------------------------------------------------------------------------------------
-#ifndef SVS_EXACT_MIN_WAVES
-#define SVS_EXACT_MIN_WAVES 2  // waves per SIMD the exact embed kernel is register-allocated for (2: +1..3 % over 3; 4 spills 52 B and is 8 % slower)
-#endif
+// Register-allocated for 2 waves per SIMD: +1..3 % over 3; 4 spills 52 B and is 8 % slower.
 template <int QM, int U = 8>  // U: coefficient rows the quantiser loop covers (flat indices 1..n lie in rows < U)
-__global__ __launch_bounds__(SVS_WG, SVS_EXACT_MIN_WAVES) void embed_exact_kernel(const uint8_t *gray,  // may alias stego
+__global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *gray,  // may alias stego
                                                           uint8_t *stego, const Geometry g,
                                                           const QimParams qp,
                                                           const uint32_t *__restrict__ bits,
@@ -419,58 +316,9 @@ __global__ __launch_bounds__(SVS_WG, SVS_EXACT_MIN_WAVES) void embed_exact_kerne
     store_rows<1>(stego + off, g.row_pitch, v);
 }
 
-// EXACT embed, two adjacent blocks per lane (16-byte row accesses; needs an even number of blocks per row and 16-byte
-// aligned rows - the host checks): the transforms run as packed-FP32 instructions over the pair (svs_block.hpp,
-// embed_block_exact_pair).  Only the lane in which the payload budget ends can have its second block not entered; that
-// block is then copied, not round-tripped (:130,:132).
-#ifndef SVS_EXACT2_MIN_WAVES
-#define SVS_EXACT2_MIN_WAVES 2
-#endif
-template <int QM, int U>
-__global__ __launch_bounds__(SVS_WG, SVS_EXACT2_MIN_WAVES) void embed_exact_pair_kernel(const uint8_t *gray,  // may alias stego
-                                                          uint8_t *stego, const Geometry g, const QimParams qp,
-                                                          const uint32_t *__restrict__ bits, const uint64_t bit_offset,
-                                                          const uint64_t n_bits, const uint32_t n_words) {
-    const uint32_t gblock = (tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x) * 2u;
-    if (gblock >= g.total_blocks) return;
-    const int64_t off = block_offset(gblock, g);
-    typename RowVec<2>::type v[8];
-    load_rows<2>(gray + off, g.row_pitch, v);
-    const uint32_t n = g.n_ac;  // 0 = round-trip every block without touching a coefficient
-    const uint64_t first = (uint64_t)gblock * n;
-    if (first >= n_bits) {
-        if (stego != gray) store_rows<2>(stego + off, g.row_pitch, v);
-        return;
-    }
-    const bool b_entered = first + n < n_bits || n == 0;   // n == 0: every block is entered (n_bits = 1 then)
-    uint32_t ax[8], ay[8], bx[8], by[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; bx[r] = v[r].z; by[r] = v[r].w; }
-    uint32_t hi_a, lo_a, hi_b, lo_b;
-    payload_window(bits, n_words, bit_offset + first, hi_a, lo_a);
-    payload_window(bits, n_words, bit_offset + first + n, hi_b, lo_b);
-    embed_block_exact_pair<U, QM>(ax, ay, bx, by, n, block_budget(first, n_bits, n), block_budget(first + n, n_bits, n), hi_a,
-                                  lo_a, hi_b, lo_b, qp);
-    if (b_entered) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; v[r].z = bx[r]; v[r].w = by[r]; }
-        store_rows<2>(stego + off, g.row_pitch, v);
-    } else {  // the one lane the budget ends in: A is stored, B keeps (or gets a copy of) its original bytes
-        typename RowVec<1>::type h[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { h[r].x = ax[r]; h[r].y = ay[r]; }
-        store_rows<1>(stego + off, g.row_pitch, h);
-        if (stego != gray) {
-            load_rows<1>(gray + off + 8, g.row_pitch, h);
-            store_rows<1>(stego + off + 8, g.row_pitch, h);
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------
-// EMBED, streaming kernel (launched for two coefficient rows, n = 8..15, since round 6 - one row: embed_row1_kernel below; flags 0 and SVS_EXACT_GUARDED, include/svsdct.h): one lane = BPL adjacent blocks, grid = ceil(total_blocks / (SVS_WG*BPL))
-// workgroups of SVS_WG.  BPL = 2 (16-byte row accesses) needs an even number of blocks per row and 16-byte aligned rows
-// (the host checks) and is instantiated for one coefficient row only.
+// EMBED, streaming kernel (launched for two coefficient rows, n = 8..15, since round 6 - one row: embed_row1_kernel below; flags
+// 0 and SVS_EXACT_GUARDED, include/svsdct.h): one lane = one block, grid = ceil(total_blocks / SVS_WG) workgroups of SVS_WG.
 // HBM traffic per block: 64 B read + 64 B written + n payload bits read - nothing else, whatever the content.
 //   phase 1  lane = block: the cheap arithmetic (svs_block.hpp) - embed_block_guarded (n <= 7) / _guarded2 (n = 8..15):
 //            pocketfft-identical payload coefficients, sparse inverse, rigorous per-block error bound - the result is the
@@ -484,15 +332,12 @@ __global__ __launch_bounds__(SVS_WG, SVS_EXACT2_MIN_WAVES) void embed_exact_pair
 //            embed_block_exact, so the bits are the same; what changes is the shape: about 40 VGPRs and 300-450
 //            instructions per pass of 8 blocks instead of 140 VGPRs and 2 100 per pass of 64 - affordable inside the
 //            streaming kernel.  More than SVS_GUARD_CAP undecided blocks in a wave (flat content) take further rounds.
-//            With two coefficient rows the worklist is shared by the workgroup (guard_phase2_wg).
 //   phase 3  every lane stores its rows (its own result, or the one it collected from the worklist): the wave's stores
 //            cover whole 512-byte row segments - no partial lines, no second launch, no scratch buffer in HBM.
 // `gray` and `stego` may be the same buffer (in-place embedding, include/svsdct.h), so neither is __restrict__: every
 // lane loads its own rows before it stores them and touches nobody else's.
 // ---------------------------------------------------------------------------------------
-#ifndef SVS_GUARD_CAP
 #define SVS_GUARD_CAP 32    // worklist entries per wave and round (80 B each) of the one-row (rigorous guard) embed kernel
-#endif
 
 // px: the block's 16 row dwords (low, high per row) in LDS - original pixels in, exact stego pixels out
 // UROWS: coefficient rows that can hold payload (n <= 8 UROWS - 1); the quantiser loop covers only those
@@ -565,16 +410,6 @@ __device__ __forceinline__ bool guard_phase1(uint32_t (&ax)[8], uint32_t (&ay)[8
     if constexpr (U == 1) return embed_block_guarded<QM>(ax, ay, n, nb, hi, lo, qp);          // n <= 7: rigorous, 8 tests
     else return embed_block_guarded2<QM, NFIX>(ax, ay, n, nb, hi, lo, qp);                    // n = 8..15: rigorous, 64 tests
 }
-// the same with the window handed in (two blocks per lane: both windows come from one payload_qword)
-template <int U, int QM, int NFIX = 0>
-__device__ __forceinline__ bool guard_phase1_window(uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_t n, uint64_t first,
-                                                    const QimParams &qp, uint64_t n_bits, uint32_t hi) {
-    static_assert(U <= 2, "n <= 15");
-    const uint32_t nb = block_budget(first, n_bits, n);
-    if constexpr (U == 1) return embed_block_guarded<QM>(ax, ay, n, nb, hi, 0u, qp);
-    else return embed_block_guarded2<QM, NFIX>(ax, ay, n, nb, hi, 0u, qp);
-}
-
 // what phase 2 needs to rebuild a block's payload window (kept out of the lanes' registers on the common path)
 struct GuardPayload {
     const uint32_t *bits;
@@ -678,94 +513,20 @@ __device__ __forceinline__ uint32_t guard_phase2_slots(uint32_t *slots, u32x2 *m
     return total;
 }
 
-#ifndef SVS_U2_WGPOOL
-#define SVS_U2_WGPOOL 0      // two rows: 1 = worklist shared by the workgroup (guard_phase2_wg, A/B build only): measured SLOWER (2.74 vs
-                             // 2.65 ms per 600 x 4K, profiles/r04_ab_two_row.txt): the three barriers cost more than the passes saved
-#endif
-#if SVS_U2_WGPOOL
-// phase 2 at WORKGROUP scope (round 4; the two-row kernel, where 5-13 % of the blocks are undecided and the kernel is bound
-// by vector issue, not by HBM): the undecided blocks of all four waves share ONE worklist, and its passes of eight blocks
-// are dealt round-robin to the waves.  A wave-private worklist runs ceil(k / 8) passes for its own k blocks - 0.97 passes
-// per wave at 3 blocks (natural-like content, 5 %), 1.5 at 8.3 (noise, 13 %) - the shared one ceil(K / 8) for the workgroup's
-// K: 0.5 and 1.15 per wave.  Price: one LDS atomic per wave and three workgroup barriers (the wave-private form has none),
-// which is why the one-row kernel - HBM-bound, replay hidden - keeps the wave-private form.
-// `counter` must have been zeroed (and a barrier passed) before the first wave gets here.  Every thread of the workgroup
-// must call this (barriers inside).  Returns the workgroup's number of redone blocks.
-template <int QM, int CAPWG, bool KEPT>
-__device__ __forceinline__ uint32_t guard_phase2_wg(GuardEntry *entries, float *tile, uint32_t *counter, uint32_t lane, uint32_t wave,
-                                                    uint32_t n, const QimParams &qp, const GuardPayload &pl, bool und,
-                                                    uint64_t first, uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_t hi_kept) {
-    const uint64_t mask = __ballot(und);
-    uint32_t base = 0;
-    if (mask != 0) {   // wave-uniform
-        if (lane == 0) base = atomicAdd(counter, (uint32_t)__popcll(mask));
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    }
-    __syncthreads();                       // every wave's count is in
-    const uint32_t total = *counter;       // uniform over the workgroup; nobody writes it again
-    if (total == 0) return 0;
-    const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    for (uint32_t round0 = 0; round0 < total; round0 += (uint32_t)CAPWG) {   // uniform over the workgroup
-        const bool mine = und && slot >= round0 && slot < round0 + (uint32_t)CAPWG;
-        if (mine) {
-            GuardEntry *e = &entries[slot - round0];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { e->px[2 * r] = ax[r]; e->px[2 * r + 1] = ay[r]; }
-            uint32_t hi, lo;
-            if constexpr (KEPT) { hi = hi_kept; lo = 0; }
-            else payload_window(pl.bits, pl.n_words, pl.bit_offset + first, hi, lo);
-            e->hi = hi; e->lo = lo; e->nb = block_budget(first, pl.n_bits, n);
-        }
-        __syncthreads();
-        const uint32_t todo = min(total - round0, (uint32_t)CAPWG);
-        for (uint32_t at = 8u * wave; at < todo; at += 8u * (SVS_WG / 64)) {   // this wave's passes
-            const uint32_t idx = at + (lane >> 3);
-            if (idx < todo) {
-                GuardEntry *e = &entries[idx];
-                guard_replay8<QM, 2>(e->px, e->hi, e->lo, e->nb, tile + (lane >> 3) * SVS_GUARD_TILE, lane & 7u, n, qp);
-            }
-        }
-        __syncthreads();
-        if (mine) {
-            const GuardEntry *e = &entries[slot - round0];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { ax[r] = e->px[2 * r]; ay[r] = e->px[2 * r + 1]; }
-        }
-        if (round0 + (uint32_t)CAPWG < total) __syncthreads();   // the next round overwrites the entries
-    }
-    return total;
-}
-
-#endif  // SVS_U2_WGPOOL
-
 // Register targets (waves per SIMD) of the embed kernels: natural allocation.  (One row: 96 VGPRs, 5 waves; spills in the
 // replay cost 1.90 vs 1.71 ms.  Two rows: 103 VGPRs, 4 waves; a target of 5 waves spills 68 B and costs 3.26 vs 2.74 ms
 // per 600 x 4K, 6 waves 4.30 ms - profiles/r04_ab_two_row.txt.)
-#ifndef SVS_KEEP_WINDOW
-#define SVS_KEEP_WINDOW 1
-#endif
-#ifndef SVS_GUARD_CAP_WG
-#define SVS_GUARD_CAP_WG 64  // entries of the shared worklist per round (noise content: 33 undecided blocks per workgroup)
-#endif
-#ifndef SVS_U2_MIN_WAVES
-#define SVS_U2_MIN_WAVES 1   // natural allocation (about 100 VGPRs, 4 waves per SIMD)
-#endif
-template <int U>
-constexpr int kEmbedMinWaves = U == 2 ? SVS_U2_MIN_WAVES : 1;
+// Lanes past the end of the batch shadow its last block(s): they load and compute like everybody else, and never store.
 template <int BPL>
-__device__ __forceinline__ uint32_t row2_shadow(uint32_t gblock, const Geometry &g, bool &live) {
+__device__ __forceinline__ uint32_t shadow_block(uint32_t gblock, const Geometry &g, bool &live) {
     live = gblock < g.total_blocks;
     return live ? gblock : g.total_blocks - (uint32_t)BPL;   // the host launches with total_blocks >= BPL (a multiple of BPL)
 }
-// two rows, one block per lane: original rows parked in LDS and phase 1 in place (guard_phase2_slots: 68 instead of 103
-// VGPRs, 5 instead of 4 waves per SIMD, 29.7 KB of LDS per workgroup).  The kernel is bound by vector issue either way, and
-// which form the compiler schedules better depends on the quantiser: general delta (QM_F32, the GUI's default 20) 2.62 vs
-// 2.78 ms per 600 x 4K at n = 10 and 2.82 vs 2.93 at n = 15 in favour of the parked form, power-of-two delta 2.74 vs 2.65
-// against it - both orders of a 15-round A/B (profiles/r04_ab_two_row.txt).  1 = parked except for power-of-two delta,
-// 2 = always, 0 = never.
-#ifndef SVS_U2_INPLACE
-#define SVS_U2_INPLACE 1
-#endif
+// Two rows, except for power-of-two delta: original rows parked in LDS and phase 1 in place (guard_phase2_slots: 68 instead
+// of 103 VGPRs, 5 instead of 4 waves per SIMD, 29.7 KB of LDS per workgroup).  The kernel is bound by vector issue either
+// way, and which form the compiler schedules better depends on the quantiser: general delta (QM_F32, the GUI's default 20)
+// 2.62 vs 2.78 ms per 600 x 4K at n = 10 and 2.82 vs 2.93 at n = 15 in favour of the parked form, power-of-two delta 2.74 vs
+// 2.65 against it - both orders of a 15-round A/B (profiles/r04_ab_two_row.txt).
 // The experiments library (-DSVS_EXPERIMENTS) counts the blocks a launch redid exactly into a device counter (measurement
 // hook svs_guard_counter_set); the product kernels have no such parameter and the product library no such state.
 #if defined(SVS_EXPERIMENTS)
@@ -774,91 +535,61 @@ __device__ __forceinline__ uint32_t row2_shadow(uint32_t gblock, const Geometry 
 #define SVS_REPLAY_COUNTER_PARAM
 #endif
 template <int U, int QM, int BPL, int NFIX = 0>   // NFIX: compile-time n (two rows only; svs_capi.hip instantiates the GUI's default 10)
-__global__ __launch_bounds__(SVS_WG, kEmbedMinWaves<U>) void embed_kernel(const uint8_t *gray,
-                                                    uint8_t *stego, const Geometry g, const QimParams qp,
+__global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint8_t *stego, const Geometry g, const QimParams qp,
                                                     const uint32_t *__restrict__ bits, const uint64_t bit_offset,
                                                     const uint64_t n_bits, const uint32_t n_words SVS_REPLAY_COUNTER_PARAM) {
     static_assert(U == 2, "n = 8..15 (svs_capi.hip: one coefficient row runs embed_row1_kernel, more rows embed_exact_kernel in every mode)");
-    constexpr bool WGPOOL = U == 2 && BPL == 1 && SVS_U2_WGPOOL;
-    constexpr bool PARKED = U == 2 && BPL == 1 && !WGPOOL && (SVS_U2_INPLACE == 2 || (SVS_U2_INPLACE == 1 && QM != QM_POW2));
-    constexpr int CAP = WGPOOL ? SVS_GUARD_CAP_WG : SVS_GUARD_CAP;
+    static_assert(BPL == 1, "one block per lane (see extract_kernel)");
+    constexpr bool PARKED = QM != QM_POW2;
     // PARKED: per wave 64 slots of original rows + the worklist words; otherwise the worklist entries carry the rows
     __shared__ __attribute__((aligned(16))) uint32_t park[PARKED ? SVS_WG / 64 : 1][PARKED ? 64 * SVS_SLOT_DWORDS : 2];
     __shared__ u32x2 meta[PARKED ? SVS_WG / 64 : 1][PARKED ? 64 : 1];
-    __shared__ GuardEntry entries[PARKED ? 1 : (WGPOOL ? 1 : SVS_WG / 64)][PARKED ? 1 : CAP];
+    __shared__ GuardEntry entries[PARKED ? 1 : SVS_WG / 64][PARKED ? 1 : SVS_GUARD_CAP];
     __shared__ float tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#if SVS_U2_WGPOOL
-    __shared__ uint32_t wg_undecided;
-    if constexpr (WGPOOL) {
-        if (threadIdx.x == 0) wg_undecided = 0u;
-        __syncthreads();   // at the very start: no wave has work in flight yet
-    }
-#endif
     // (Round 5 tried block-row aligned tiles - a workgroup reads and writes ONE contiguous stretch, eight full pixel rows, at
     // the price of idle lanes - to bring the launch from the rate of a copy with this access pattern to that of a linear copy:
     // 1.73 vs 1.64 ms per 600 x 4K at n = 3, 3.15 vs 2.63 at n = 10, slower on every placement: profiles/r05_ab_row_tiles.txt.)
-    // lanes past the end of the batch shadow its last block(s) - they load and compute like everybody else and never store - so
-    // that the row registers are defined on one path only (round 6: no zero-initialised copies at the joins)
+    // Shadow lanes keep the row registers defined on one path only (round 6: no zero-initialised copies at the joins).
     bool live;
-    const uint32_t gblock = row2_shadow<BPL>((tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x) * BPL, g, live);
+    const uint32_t gblock = shadow_block<1>(tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x, g, live);
     const uint32_t n = g.n_ac;
-    bool und_a = false, und_b = false, write = false;
+    bool und = false, write = false;
     // n <= 15: the payload window of a block is its first word - kept in a register from phase 1, because re-reading it for
     // the worklist is a global load in the life of every wave that replays
-    constexpr bool KEPT = SVS_KEEP_WINDOW;
-    uint32_t hi_a = 0, hi_b = 0, nb_a = 0;
-    typename RowVec<BPL>::type v[8];
-    uint32_t ax[8], ay[8], bx[8], by[8];
+    uint32_t hi = 0, nb = 0;
+    u32x2 v[8];
+    uint32_t ax[8], ay[8];
     const int64_t off = block_offset(gblock, g);
-    load_rows<BPL>(gray + off, g.row_pitch, v);
+    load_rows<1>(gray + off, g.row_pitch, v);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        ax[r] = v[r].x; ay[r] = v[r].y;
-        if constexpr (BPL == 2) { bx[r] = v[r].z; by[r] = v[r].w; }
-    }
+    for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
     if (live) {
         const uint64_t first = (uint64_t)gblock * n;  // stream index of this lane's first bit
         write = stego != gray;                         // past the budget: byte-identical copy (the reference's loops `break`, :130,:132)
         if (first < n_bits) {
             write = true;
-            if constexpr (BPL == 2) {
-                // both blocks' windows from the two dwords at the lane's first stream bit (2 n <= 14 bits at one row)
-                const uint64_t q = payload_qword(bits, n_words, bit_offset + first);
-                const uint32_t sh = (uint32_t)((bit_offset + first) & 31u);
-                hi_a = window32(q, sh);
-                hi_b = window32(q, sh + n);
-                und_a = guard_phase1_window<U, QM, NFIX>(ax, ay, n, first, qp, n_bits, hi_a);
-                if constexpr (U == 2) SVS_SCHED_FENCE();   // one block at a time: interleaved, the two working sets need 150 VGPRs
-                if (first + n < n_bits)   // a budget of 0 (only the lane the payload ends in can see it) leaves block B as it is
-                    und_b = guard_phase1_window<U, QM, NFIX>(bx, by, n, first + n, qp, n_bits, hi_b);
-            } else if constexpr (PARKED) {
+            if constexpr (PARKED) {
                 // park the original rows (the exact replay reads them there), then phase 1 in place
                 u32x2 *slot = reinterpret_cast<u32x2 *>(&park[wave][lane * SVS_SLOT_DWORDS]);
 #pragma unroll
                 for (int r = 0; r < 8; ++r) slot[r] = v[r];
-                hi_a = window32(payload_qword(bits, n_words, bit_offset + first), (uint32_t)((bit_offset + first) & 31u));
-                nb_a = block_budget(first, n_bits, n);
-                und_a = embed_block_guarded2<QM, NFIX, true>(ax, ay, n, nb_a, hi_a, 0u, qp);
+                hi = window32(payload_qword(bits, n_words, bit_offset + first), (uint32_t)((bit_offset + first) & 31u));
+                nb = block_budget(first, n_bits, n);
+                und = embed_block_guarded2<QM, NFIX, true>(ax, ay, n, nb, hi, 0u, qp);
             } else {
-                und_a = guard_phase1<U, QM, NFIX>(ax, ay, n, first, qp, bits, bit_offset, n_bits, n_words, KEPT ? &hi_a : nullptr);
+                und = guard_phase1<U, QM, NFIX>(ax, ay, n, first, qp, bits, bit_offset, n_bits, n_words, &hi);
             }
         }
     }
-    const GuardPayload pl{bits, bit_offset, n_bits, n_words};
-    const uint64_t first_a = (uint64_t)gblock * n;
     uint32_t redone;
     if constexpr (PARKED) {
-        redone = guard_phase2_slots<QM>(&park[wave][0], &meta[wave][0], &tiles[wave][0], lane, n, qp, und_a, nb_a, hi_a, ax, ay);
-#if SVS_U2_WGPOOL
-    } else if constexpr (WGPOOL) {
-        redone = guard_phase2_wg<QM, CAP, KEPT>(&entries[0][0], &tiles[wave][0], &wg_undecided, lane, wave, n, qp, pl, und_a, first_a,
-                                                ax, ay, hi_a);
-        if (wave != 0) redone = 0;   // counted once per workgroup
-#endif
+        redone = guard_phase2_slots<QM>(&park[wave][0], &meta[wave][0], &tiles[wave][0], lane, n, qp, und, nb, hi, ax, ay);
     } else {
-        redone = guard_phase2<QM, BPL == 2, CAP, KEPT>(&entries[wave][0], &tiles[wave][0], lane, n, qp, pl, und_a, first_a, ax, ay,
-                                                       und_b, first_a + n, bx, by, hi_a, hi_b);
+        const GuardPayload pl{bits, bit_offset, n_bits, n_words};
+        const uint64_t first = (uint64_t)gblock * n;
+        redone = guard_phase2<QM, false, SVS_GUARD_CAP, true>(&entries[wave][0], &tiles[wave][0], lane, n, qp, pl, und, first, ax, ay,
+                                                              false, first, ax, ay, hi, 0u);
     }
 #if defined(SVS_EXPERIMENTS)
     if (replay_counter != nullptr && redone != 0 && lane == 0) atomicAdd(replay_counter, (unsigned long long)redone);
@@ -867,11 +598,8 @@ __global__ __launch_bounds__(SVS_WG, kEmbedMinWaves<U>) void embed_kernel(const 
 #endif
     if (write) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            v[r].x = ax[r]; v[r].y = ay[r];
-            if constexpr (BPL == 2) { v[r].z = bx[r]; v[r].w = by[r]; }
-        }
-        store_rows<BPL>(stego + off, g.row_pitch, v);
+        for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
+        store_rows<1>(stego + off, g.row_pitch, v);
     }
 }
 
@@ -970,13 +698,6 @@ struct Row1Args {
     uint32_t n_words;
 };
 
-// lanes past the end of the batch shadow its last block(s): they load and compute like everybody else, and never store
-template <int BPL>
-__device__ __forceinline__ uint32_t row1_shadow(uint32_t gblock, const Geometry &g, bool &live) {
-    live = gblock < g.total_blocks;
-    return live ? gblock : g.total_blocks - (uint32_t)BPL;   // the host launches with total_blocks >= BPL (a multiple of BPL)
-}
-
 // phases 1-3 for the rows `v` of global block(s) gb (already loaded from gray + off): decide / apply, exact replay of the
 // wave's undecided blocks, store.
 template <int QM, int BPL>
@@ -1053,7 +774,7 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
     __shared__ float tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     bool live;
-    const uint32_t gb = row1_shadow<BPL>((tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x) * BPL, g, live);
+    const uint32_t gb = shadow_block<BPL>((tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x) * BPL, g, live);
     const int64_t off = block_offset(gb, g);
     typename RowVec<BPL>::type v[8];
     load_rows<BPL>(gray + off, g.row_pitch, v);
@@ -1074,31 +795,26 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
 // every placement, 1.77 - 1.95 ms per 600 x 4K against 1.58 - 1.62, even with the arithmetic skipped: profiles/r06_stream_pipeline.txt.
 // What the one-shot launch has and the loop has not is the hardware's own pacing: a workgroup starts when another one ends.)
 
-template <int U, int QM, int BPL = 1>
+template <int U, int QM, int BPL = 1>   // BPL: see extract_kernel
 __global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                             const QimParams qp, uint8_t *__restrict__ out,
                                                             const uint64_t out_bytes) {
-    __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(BPL)];
+    static_assert(BPL == 1, "one block per lane");
+    __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t tile = tile_id(g.xcd_chunk);
-    const uint32_t gblock = (tile * (uint32_t)SVS_WG + threadIdx.x) * BPL;
+    const uint32_t gblock = tile * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t n = g.n_ac;
-    uint32_t hi_a = 0, lo_a = 0, hi_b = 0, lo_b = 0;
+    uint32_t hi = 0, lo = 0;
     if (gblock < g.total_blocks) {
-        typename RowVec<BPL>::type v[8];
-        load_rows<BPL>(gray + block_offset(gblock, g), g.row_pitch, v);
+        u32x2 v[8];
+        load_rows<1>(gray + block_offset(gblock, g), g.row_pitch, v);
         uint32_t ax[8], ay[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
-        extract_block_exact<U, QM>(ax, ay, n, qp, hi_a, lo_a);
-        if constexpr (BPL == 2) {   // two adjacent blocks per lane: 16-byte row loads (even block count per row, host-checked)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { ax[r] = v[r].z; ay[r] = v[r].w; }
-            extract_block_exact<U, QM>(ax, ay, n, qp, hi_b, lo_b);
-        }
+        extract_block_exact<U, QM>(ax, ay, n, qp, hi, lo);
     }
-    emit_wave_bits<U, BPL>(&flags[wave][0], lane, ((uint64_t)tile * (uint32_t)SVS_WG + wave * 64u) * BPL, n, hi_a, lo_a, hi_b, lo_b,
-                           out, out_bytes);
+    emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1321,7 +1037,7 @@ __device__ __forceinline__ WaveUnits wave_units(uint32_t lane, uint32_t wave_fir
     return w;
 }
 
-// Cooperative load of the wave's BGR rows (SVS_BGR_DIRECT_LOAD disables it): every load instruction covers 512
+// Cooperative load of the wave's BGR rows: every load instruction covers 512
 // contiguous bytes; the rows pass through a wave-private, double-buffered LDS row (2 x 192 units) from which each lane
 // picks its own 24 bytes and converts them to gray.  +6 % in extract_bgr_kernel over lanes loading their own rows at a
 // 24-byte stride (profiles/history/r01_aux_kernel_rates.txt).
@@ -1451,7 +1167,7 @@ __global__ __launch_bounds__(SVS_WG) void gray_to_bgr_kernel(const uint8_t *__re
     wave_store_gray_as_bgr(&tile[threadIdx.x >> 6][0][0], threadIdx.x & 63u, gblock, live, ax, ay, bgr, g, c);
 }
 
-// Stego rows leave through a wave-private LDS tile (SVS_BGR_DIRECT_STORE disables it): each lane parks its 8 stego gray
+// Stego rows leave through a wave-private LDS tile: each lane parks its 8 stego gray
 // bytes per row, then the wave writes the BGR row as 192 consecutive 8-byte units - unit u = bytes [8*(u%3), +8) of the
 // 24-byte row of the wave's block u/3 - so every store instruction covers 512 contiguous bytes instead of 8 bytes in
 // every 24.
@@ -1474,7 +1190,7 @@ __global__ __launch_bounds__(SVS_WG) void embed_bgr_kernel(const uint8_t *bgr_in
     // neutral in EXACT mode; all eight rows at once cost 100+ VGPRs and gained 1 % (profiles/history/r01_aux_kernel_rates.txt)
     wave_load_gray_halves(bgr_in, g, c, gblock - lane, lane, &lds_tile[wave][0][0], ax, ay);
     bool und = false;
-    constexpr bool KEPT = !EXACT && U <= 2 && SVS_KEEP_WINDOW;   // see embed_kernel
+    constexpr bool KEPT = !EXACT && U <= 2;   // see embed_kernel
     uint32_t hi_kept = 0;
     if (live) {
         if (gray_ref != nullptr) {  // the operator's first return value: the gray frame before embedding
@@ -1604,9 +1320,6 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const uint8_t *__rest
             va += sa - ha[j]; vb += sb - hb[j]; vaa += saa - haa[j]; vbb += sbb - hbb[j]; vab += sab - hab[j];
             ha[j] = sa; hb[j] = sb; haa[j] = saa; hbb[j] = sbb; hab[j] = sab;
             const int r = r0 + j;
-#if defined(SVS_SSIM_DIAG_NO_F64)
-            if (r >= 6 && r < rows && col_ok) acc += (double)(va + vb + vaa + vbb + vab);
-#else
             if (r >= 6 && r < rows && col_ok) {
                 const double ux = va * inv_np, uy = vb * inv_np;
                 const double vx = cov_norm * (vaa * inv_np - ux * ux), vy = cov_norm * (vbb * inv_np - uy * uy);
@@ -1614,7 +1327,6 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const uint8_t *__rest
                 const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2, B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
                 acc += (A1 * A2) / (B1 * B2);
             }
-#endif
         }
     }
 #pragma unroll

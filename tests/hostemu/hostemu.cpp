@@ -32,7 +32,7 @@ struct Blk {
     }
 };
 
-// two adjacent blocks through the packed pair form (what embed_exact_pair_kernel runs)
+// two adjacent blocks through the packed pair form (svs_block.hpp embed_block_exact_pair; no kernel runs it)
 void embed_exact_pair_dispatch(Blk &a, Blk &b, uint32_t n, uint32_t nb_a, uint32_t nb_b, uint32_t hi_a, uint32_t lo_a,
                                uint32_t hi_b, uint32_t lo_b, const svs::QimParams &qp, int qm) {
     if (qm == svs::QM_DOUBLE) svs::embed_block_exact_pair<8, svs::QM_DOUBLE>(a.x, a.y, b.x, b.y, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
@@ -218,7 +218,7 @@ uint64_t emu_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, dou
         uint32_t hi, lo;
         svs::payload_window(reinterpret_cast<const uint32_t *>(bits), n_words, bit_offset + first, hi, lo);
         if (exact == 2 && (W / 8) % 2 == 0 && gb % 2 == 0 && svs::block_budget(first + n, use, (uint32_t)n) > 0) {
-            // exact == 2: even/odd block pairs through the packed pair form, as embed_exact_pair_kernel does
+            // exact == 2: even/odd block pairs through the packed pair form
             Blk other;
             other.load(p + 8, (size_t)W);
             uint32_t hi_b, lo_b;

@@ -64,8 +64,8 @@ def test_larger_random_frames_against_oracle():
 
 
 def test_pair_form_equals_the_one_block_form(golden):
-    """embed_block_exact_pair (two adjacent blocks per lane, every transform instruction packed over the pair - what
-    embed_exact_pair_kernel runs) gives the bytes of embed_block_exact on every golden case, on partial budgets that end
+    """embed_block_exact_pair (two adjacent blocks at once, every transform instruction packed over the pair; no kernel
+    runs it) gives the bytes of embed_block_exact on every golden case, on partial budgets that end
     inside the first or the second block of a pair, and on random frames."""
     arrays, meta = golden
     for name in single_frame_cases(meta):
