@@ -56,7 +56,9 @@ extern "C" {
 #define SVS_ERR_CAPACITY (-4)     /* an output buffer is too small */
 
 /* `flags` of the embed / extract entry points.  EVERY value gives the reference's stego pixels and extracted bits, bit for
- * bit; the flags only choose between two kernel families.
+ * bit; the flags only choose between two kernel families.  (The one exception is SVS_KEEP_COLOUR below, which the fused
+ * colour embed alone accepts: there the GRAY of the output under the same weights is the reference's stego plane bit for
+ * bit, while the BGR bytes intentionally differ from COLOR_GRAY2BGR.)
  *   0 / SVS_EXACT_GUARDED  (identical in behaviour; SVS_EXACT_GUARDED is kept as a named value for ABI compatibility and is
  *                      what the Python layer passes by default.)  Embedding with n_ac <= 15 and 0.25 <= delta <= 4096 runs the
  *                      STREAMING kernel (csrc/svs_device.hpp): every block goes HBM -> registers -> HBM once; the kernel
@@ -83,6 +85,14 @@ extern "C" {
  * Every entry point is re-entrant and thread-safe.  The library reads no environment variable. */
 #define SVS_EXACT_POCKETFFT 1u
 #define SVS_EXACT_GUARDED 2u
+/* SVS_KEEP_COLOUR (svs_embed_bgr_dev / svs_embed_bgr only; every other entry point rejects it with SVS_ERR_INVALID_ARG):
+ * opt-in.  Stego pixels keep the cover's colour instead of B = G = R: each output pixel is the cover pixel c shifted by
+ * d = stego gray - gray(c) in all three channels, clamped to [0, 255], and - only where a channel clipped - walked channel by
+ * channel (decreasing weight) to the nearest pixel whose gray is the stego gray (csrc/svs_colour.hpp).  The gray of the
+ * output under the same weights is the reference's stego plane exactly, so extraction (which converts to gray first) gives
+ * the reference's bits; blocks past the payload budget and pixels whose gray did not change are the cover's bytes.  The
+ * default (flag clear) is still the reference's COLOR_GRAY2BGR output, byte for byte. */
+#define SVS_KEEP_COLOUR 0x100u
 
 /* Geometry of a batch of gray planes. */
 typedef struct svs_planes {
@@ -215,9 +225,10 @@ int svs_gray_to_bgr_dev(const uint8_t *d_gray, const svs_planes *planes, uint8_t
  *   d_gray_ref           : optional (NULL to skip) gray planes, geometry `planes`: the gray frame BEFORE embedding,
  *                          i.e. the operator's first return value (config_and_setup.py:112,172).
  *   planes               : n_frames / height / width of the clip and the pitches of d_gray_ref.
- *   weights, flags, bits : as svs_bgr_to_gray_dev / svs_embed_dev.  Every block of these frames is written (gray
- *                          replicated into B, G, R); pass only the frames that carry payload - the reference copies
- *                          the remaining frames in colour (embed_process.py:134-139). */
+ *   weights, flags, bits : as svs_bgr_to_gray_dev / svs_embed_dev, plus SVS_KEEP_COLOUR.  Every block of these frames
+ *                          is written (gray replicated into B, G, R; with SVS_KEEP_COLOUR the cover's colours shifted to
+ *                          the stego gray); pass only the frames that carry payload - the reference copies the remaining
+ *                          frames in colour (embed_process.py:134-139).  d_gray_ref is the cover gray in both forms. */
 int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_frame_pitch,
                       uint8_t *d_bgr_out, int64_t out_row_pitch, int64_t out_frame_pitch,
                       uint8_t *d_gray_ref, const svs_planes *planes, const uint32_t *weights,

@@ -423,20 +423,20 @@ size_t stage_chunk_bytes(uint64_t total) {
     return forced ? (size_t)forced << 10 : svs::stage_chunk_rule(total);
 }
 
-template <int QM, bool EXACT>
+template <int QM, bool EXACT, bool KEEP>
 int launch_embed_bgr(int rows, uint64_t total, hipStream_t st, const uint8_t *in, uint8_t *out, uint8_t *ref,
                             const svs::Geometry &g, const svs::ColourParams &c, const svs::QimParams &qp,
                             const uint32_t *bits, uint64_t bit_offset, uint64_t n_bits, uint32_t n_words) {
     const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
     if constexpr (EXACT) {
-        hipLaunchKernelGGL((svs::embed_bgr_kernel<8, QM, true>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
+        hipLaunchKernelGGL((svs::embed_bgr_kernel<8, QM, true, KEEP>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
                            bit_offset, n_bits, n_words);
     } else {
         if (rows == 1)
-            hipLaunchKernelGGL((svs::embed_bgr_kernel<1, QM, false>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
+            hipLaunchKernelGGL((svs::embed_bgr_kernel<1, QM, false, KEEP>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
                                bit_offset, n_bits, n_words);
         else if (rows == 2)
-            hipLaunchKernelGGL((svs::embed_bgr_kernel<2, QM, false>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
+            hipLaunchKernelGGL((svs::embed_bgr_kernel<2, QM, false, KEEP>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
                                bit_offset, n_bits, n_words);
         else
             return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
@@ -991,7 +991,8 @@ int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
     if (total == 0) return SVS_OK;
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR))
+        return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
     if (d_gray_ref && ((uintptr_t)d_gray_ref % 8)) return fail(SVS_ERR_INVALID_ARG, "gray pointer must be 8-byte aligned");
     svs::ColourParams c;
     if (int rc = colour_params(planes, d_bgr_in, in_row_pitch, in_frame_pitch, d_bgr_out, out_row_pitch, out_frame_pitch,
@@ -1034,15 +1035,19 @@ int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_
     }
     const int rows = rows_for((int)g.n_ac);
     int rc;
+    const bool keep = (flags & SVS_KEEP_COLOUR) != 0;
+#define SVS_GO2(QM, EX)                                                                                                  \
+    rc = keep ? launch_embed_bgr<QM, EX, true>(rows, total, st, d_bgr_in, d_bgr_out, d_gray_ref, g, c, qp, bw, bit_offset, \
+                                               kernel_bits, words)                                                        \
+              : launch_embed_bgr<QM, EX, false>(rows, total, st, d_bgr_in, d_bgr_out, d_gray_ref, g, c, qp, bw,            \
+                                                bit_offset, kernel_bits, words);
 #define SVS_GO(QM)                                                                                                       \
-    rc = exact ? launch_embed_bgr<QM, true>(rows, total, st, d_bgr_in, d_bgr_out, d_gray_ref, g, c, qp, bw, bit_offset,   \
-                                            kernel_bits, words)                                                           \
-               : launch_embed_bgr<QM, false>(rows, total, st, d_bgr_in, d_bgr_out, d_gray_ref, g, c, qp, bw, bit_offset,  \
-                                             kernel_bits, words);
+    if (exact) { SVS_GO2(QM, true) } else { SVS_GO2(QM, false) }
     if (qm == svs::QM_DOUBLE) { SVS_GO(svs::QM_DOUBLE) }
     else if (qm == svs::QM_POW2) { SVS_GO(svs::QM_POW2) }
     else { SVS_GO(svs::QM_F32) }
 #undef SVS_GO
+#undef SVS_GO2
     if (rc) return rc;
     if (n_embedded) *n_embedded = use;
     return SVS_OK;
@@ -1115,7 +1120,8 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
     if (total == 0) return SVS_OK;
     if (int rc = packed_planes_only(planes)) return rc;
     if (!bgr || !bgr_out) return fail(SVS_ERR_INVALID_ARG, "BGR pointer is NULL");
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR))
+        return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
     const int32_t H = planes->height, W = planes->width;
     const uint64_t px = (uint64_t)planes->n_frames * H * W;
     const uint64_t cap = total * (uint64_t)g.n_ac;

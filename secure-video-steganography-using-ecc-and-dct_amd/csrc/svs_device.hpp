@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "svs_block.hpp"
+#include "svs_colour.hpp"
 
 namespace svs {
 
@@ -1134,6 +1135,106 @@ __device__ __forceinline__ void wave_store_gray_as_bgr(u32x2 *mine, uint32_t lan
     }
 }
 
+// SVS_KEEP_COLOUR: the stego rows leave as the COVER's pixels shifted to the stego gray (svs_colour.hpp) instead of
+// B = G = R.  The wave re-reads the cover four rows at a time (the same 512-byte cooperative loads as wave_load_gray_halves,
+// units [0, 192) of the wave's 4 KB region); each lane takes its 24 bytes, adds d = stego - cover gray to B, G and R as
+// packed 16-bit lanes and parks the result at units [192, 384); only in a wave where some lane's sum left [0, 255] do the
+// pixels with a clipped channel get the exact rule, byte by byte through LDS.  The wave then stores the row as 512-byte
+// runs.  Every row is loaded before it is stored and a wave touches only its own blocks: bgr_in == bgr_out is safe.
+__device__ __forceinline__ void wave_store_keep_colour(u32x2 *region, uint32_t lane, uint32_t gblock,
+                                                       const uint32_t (&ax)[8], const uint32_t (&ay)[8],
+                                                       const uint8_t *bgr_in, uint8_t *bgr_out, const Geometry &g,
+                                                       const ColourParams &c) {
+    typedef int16_t i16x2 __attribute__((ext_vector_type(2)));
+    const auto pk_sub = [](uint32_t a, uint32_t b) {
+        return __builtin_bit_cast(uint32_t, __builtin_bit_cast(i16x2, a) - __builtin_bit_cast(i16x2, b));
+    };
+    u32x2 *cover = region, *shifted = region + 192;
+    const uint32_t wave_first = gblock - lane;
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half) {
+        const WaveUnits wu = wave_units(lane, wave_first, g.total_blocks);
+        u32x2 raw[4][3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const uint8_t *src = bgr_in + block_offset_bgr(wave_first + wu.owner[j], g, c.in_row_pitch, c.in_frame_pitch) +
+                                 8u * wu.part[j] + (int64_t)(4 * half) * c.in_row_pitch;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                u32x2 v; v.x = 0u; v.y = 0u;
+                if (wu.live[j]) v = SVS_LD(reinterpret_cast<const u32x2 *>(src + r * c.in_row_pitch));
+                raw[r][j] = v;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) cover[lane + 64 * j] = raw[r][j];
+            wave_lds_fence();
+            const u32x2 q0 = cover[3 * lane], q1 = cover[3 * lane + 1], q2 = cover[3 * lane + 2];
+            const uint32_t tlo = half == 0 ? ax[r] : ax[4 + r], thi = half == 0 ? ay[r] : ay[4 + r];
+            uint32_t glo, ghi;
+            bgr8_to_gray(q0, q1, q2, c, glo, ghi);
+            // d of pixels (0,1) (2,3) (4,5) (6,7) as 16-bit lanes, then of the twelve channel pairs of the 24 bytes
+            // B0G0 R0B1 G1R1 B2G2 R2B3 G3R3 B4G4 R4B5 G5R5 B6G6 R6B7 G7R7
+            const uint32_t d01 = pk_sub(__builtin_amdgcn_perm(0u, tlo, 0x0c010c00u), __builtin_amdgcn_perm(0u, glo, 0x0c010c00u));
+            const uint32_t d23 = pk_sub(__builtin_amdgcn_perm(0u, tlo, 0x0c030c02u), __builtin_amdgcn_perm(0u, glo, 0x0c030c02u));
+            const uint32_t d45 = pk_sub(__builtin_amdgcn_perm(0u, thi, 0x0c010c00u), __builtin_amdgcn_perm(0u, ghi, 0x0c010c00u));
+            const uint32_t d67 = pk_sub(__builtin_amdgcn_perm(0u, thi, 0x0c030c02u), __builtin_amdgcn_perm(0u, ghi, 0x0c030c02u));
+            const uint32_t lo = 0x01000100u, hi = 0x03020302u;   // (a, a) and (b, b) of a lane pair (a, b)
+            const uint32_t dd[12] = {__builtin_amdgcn_perm(0u, d01, lo), d01, __builtin_amdgcn_perm(0u, d01, hi),
+                                     __builtin_amdgcn_perm(0u, d23, lo), d23, __builtin_amdgcn_perm(0u, d23, hi),
+                                     __builtin_amdgcn_perm(0u, d45, lo), d45, __builtin_amdgcn_perm(0u, d45, hi),
+                                     __builtin_amdgcn_perm(0u, d67, lo), d67, __builtin_amdgcn_perm(0u, d67, hi)};
+            const uint32_t w[6] = {q0.x, q0.y, q1.x, q1.y, q2.x, q2.y};
+            uint32_t s[12], any = 0u;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                s[2 * k] = pk_add_i16(__builtin_amdgcn_perm(0u, w[k], 0x0c010c00u), dd[2 * k]);
+                s[2 * k + 1] = pk_add_i16(__builtin_amdgcn_perm(0u, w[k], 0x0c030c02u), dd[2 * k + 1]);
+                any |= s[2 * k] | s[2 * k + 1];
+            }
+            u32x2 o0, o1, o2;   // low bytes of the 16-bit lanes
+            o0.x = __builtin_amdgcn_perm(s[1], s[0], 0x06040200u); o0.y = __builtin_amdgcn_perm(s[3], s[2], 0x06040200u);
+            o1.x = __builtin_amdgcn_perm(s[5], s[4], 0x06040200u); o1.y = __builtin_amdgcn_perm(s[7], s[6], 0x06040200u);
+            o2.x = __builtin_amdgcn_perm(s[9], s[8], 0x06040200u); o2.y = __builtin_amdgcn_perm(s[11], s[10], 0x06040200u);
+            shifted[3 * lane] = o0; shifted[3 * lane + 1] = o1; shifted[3 * lane + 2] = o2;
+            const bool clipped = (any & 0xff00ff00u) != 0u;   // some lane < 0 (0xffxx) or > 255 (0x01xx)
+            if (__ballot(clipped) != 0ull) {
+                // the pixels with a clipped channel (byte 2m + h of the row belongs to pixel (2m + h) / 3), redone one at a
+                // time: the wave loops as often as its busiest lane has clipped pixels, not eight times
+                uint32_t todo = 0u;
+#pragma unroll
+                for (int m = 0; m < 12; ++m) {
+                    todo |= (s[m] & 0x0000ff00u) ? 1u << ((2 * m) / 3) : 0u;
+                    todo |= (s[m] & 0xff000000u) ? 1u << ((2 * m + 1) / 3) : 0u;
+                }
+                const uint8_t *cb = reinterpret_cast<const uint8_t *>(cover + 3 * lane);
+                uint8_t *ob = reinterpret_cast<uint8_t *>(shifted + 3 * lane);
+                while (todo != 0u) {
+                    const uint32_t p = (uint32_t)__builtin_ctz(todo);
+                    todo &= todo - 1u;
+                    uint32_t B = cb[3 * p], G = cb[3 * p + 1], R = cb[3 * p + 2];
+                    const uint32_t t = ((p < 4 ? tlo : thi) >> (8u * (p & 3u))) & 0xffu;
+                    keep_colour_pixel(B, G, R, t, c.wb, c.wg, c.wr, c.shift);
+                    ob[3 * p] = (uint8_t)B; ob[3 * p + 1] = (uint8_t)G; ob[3 * p + 2] = (uint8_t)R;
+                }
+            }
+            wave_lds_fence();
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                if (!wu.live[j]) continue;
+                const uint32_t owner = wu.owner[j], part = wu.part[j];
+                uint8_t *dst = bgr_out + block_offset_bgr(wave_first + owner, g, c.out_row_pitch, c.out_frame_pitch) + 8u * part +
+                               (int64_t)(4 * half + r) * c.out_row_pitch;
+                const u32x2 v = shifted[lane + 64 * j];
+                asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+            }
+            wave_lds_fence();   // the next row's writes into the region come after these reads
+        }
+    }
+}
+
 // Stand-alone conversions (svs_bgr_to_gray_dev / svs_gray_to_bgr_dev), block-structured like the operator so that they
 // share its coalesced row movers: 8x8 blocks, one lane per block.
 __global__ __launch_bounds__(SVS_WG) void bgr_to_gray_kernel(const uint8_t *__restrict__ bgr, uint8_t *__restrict__ gray,
@@ -1171,7 +1272,8 @@ __global__ __launch_bounds__(SVS_WG) void gray_to_bgr_kernel(const uint8_t *__re
 // bytes per row, then the wave writes the BGR row as 192 consecutive 8-byte units - unit u = bytes [8*(u%3), +8) of the
 // 24-byte row of the wave's block u/3 - so every store instruction covers 512 contiguous bytes instead of 8 bytes in
 // every 24.
-template <int U, int QM, bool EXACT>
+// KEEP (SVS_KEEP_COLOUR): the cover's colours shifted to the stego gray, wave_store_keep_colour; otherwise B = G = R.
+template <int U, int QM, bool EXACT, bool KEEP>
 __global__ __launch_bounds__(SVS_WG) void embed_bgr_kernel(const uint8_t *bgr_in,   // may alias bgr_out
                                                         uint8_t *bgr_out, uint8_t *__restrict__ gray_ref,
                                                         const Geometry g, const ColourParams c, const QimParams qp,
@@ -1220,7 +1322,10 @@ __global__ __launch_bounds__(SVS_WG) void embed_bgr_kernel(const uint8_t *bgr_in
         const uint64_t first = (uint64_t)gblock * g.n_ac;
         guard_phase2<QM, false, 16, KEPT>(entries, t, lane, g.n_ac, qp, pl, und, first, ax, ay, false, first, ax, ay, hi_kept, 0u);
     }
-    wave_store_gray_as_bgr(&lds_tile[wave][0][0], lane, gblock, live, ax, ay, bgr_out, g, c);
+    if constexpr (KEEP)
+        wave_store_keep_colour(&lds_tile[wave][0][0], lane, gblock, ax, ay, bgr_in, bgr_out, g, c);
+    else
+        wave_store_gray_as_bgr(&lds_tile[wave][0][0], lane, gblock, live, ax, ay, bgr_out, g, c);
 }
 
 // extract straight from interleaved BGR frames (gray computed on the fly).  One coefficient row: pocketfft-identical forward;

@@ -28,6 +28,10 @@ PIPELINE_DEPTH = int(os.environ.get("SVS_PIPELINE_DEPTH", "3"))     # batches in
 # (svs_embed_bgr_dev) instead of cv2.cvtColor on the host either side of the operator (:117-126).  Only used when the
 # device conversion reproduces this machine's cv2 bit for bit (svsdct.colour); otherwise the host conversion stays.
 FUSED_COLOUR = os.environ.get("SVS_FUSED_COLOUR", "0") == "1"
+# SVS_KEEP_COLOUR=1 (implies SVS_FUSED_COLOUR, behind the same cv2 check): the frames that carry payload keep the cover's
+# colours - each pixel shifted to the stego gray (SVS_KEEP_COLOUR, include/svsdct.h) - instead of the reference's
+# COLOR_GRAY2BGR.  Their BGR2GRAY is the reference's stego plane, so the receiver extracts the same bits.
+KEEP_COLOUR = os.environ.get("SVS_KEEP_COLOUR", "0") == "1"
 
 
 def _cv2():
@@ -115,12 +119,17 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     print(f"    Video output akan disimpan sebagai '{path_out}' (Codec: FFV1).")
 
     tabel_warna = None
-    if FUSED_COLOUR:
+    if FUSED_COLOUR or KEEP_COLOUR:
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
         except _colour.ColourMismatch as exc:
             print(f"    Info: jalur warna terfusi tidak dipakai ({exc}).")
+            if KEEP_COLOUR:
+                print("    Info: warna video sampul tidak dipertahankan.")
+    jaga_warna = bool(KEEP_COLOUR and tabel_warna)
+    if jaga_warna:
+        print("    Info: warna video sampul dipertahankan.")
     per_frame = _batch.capacity_bits(1, out_h, out_w, num_ac_coeffs)
     usable = per_frame if delta_kuantisasi > 0 else 0              # nothing can be embedded otherwise (:143-145)
     state = {"disisipkan": 0, "frame_num": 0, "first": None}
@@ -142,7 +151,9 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
             state["frame_num"] += 1
             bits_frame = min(usable, total_bits - state["disisipkan"])
             if state["frame_num"] == 1:
-                state["first"] = (np.array(gray_stack[0]), np.array(stego_stack[0]))
+                # colours kept: B != G != R, the stego plane is the output's gray (cv2's table = the device's, checked above)
+                stego0 = cv2.cvtColor(stego_bgr[0], cv2.COLOR_BGR2GRAY) if jaga_warna else stego_stack[0]
+                state["first"] = (np.array(gray_stack[0]), np.array(stego0))
             writer.write(stego_bgr[k] if stego_bgr is not None else cv2.cvtColor(stego_stack[k], cv2.COLOR_GRAY2BGR))
             state["disisipkan"] += bits_frame
             print(f"    Frame {state['frame_num']}: {bits_frame} bits disisipkan. "
@@ -161,7 +172,8 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
                 break
             stego_bgr, gray, used = _batch.embed_bgr_frames(np.stack(frames), delta_kuantisasi, num_ac_coeffs, payload,
                                                             bit_offset=state["disisipkan"],
-                                                            n_bits=total_bits - state["disisipkan"], weights=tabel_warna)
+                                                            n_bits=total_bits - state["disisipkan"], weights=tabel_warna,
+                                                            keep_colour=jaga_warna)
             expect = min(len(frames) * usable, total_bits - state["disisipkan"])
             if used != expect:
                 raise RuntimeError(f"embed kernel consumed {used} bits, expected {expect}")

@@ -257,18 +257,23 @@ def _weights_arg(weights):
     return w, w.ctypes.data
 
 
+def _bgr_flags(mode, keep_colour):
+    return mode_flags(mode) | (native.SVS_KEEP_COLOUR if keep_colour else 0)
+
+
 def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Planes, delta, n_ac,
                      d_bits_packed: int, bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
-                     weights=None, in_pitches=None, out_pitches=None) -> int:
+                     weights=None, in_pitches=None, out_pitches=None, keep_colour: bool = False) -> int:
     """Enqueue the fused BGR -> gray -> embed -> BGR kernel over packed (or pitched) interleaved BGR frames;
-    `d_gray_ref` (0 to skip) receives the gray frames before embedding.  Returns bits embedded."""
+    `d_gray_ref` (0 to skip) receives the gray frames before embedding.  keep_colour: stego pixels keep the cover's
+    colour (SVS_KEEP_COLOUR; their gray is the stego plane) instead of B = G = R.  Returns bits embedded."""
     irp, ifp = in_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     orp, ofp = out_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     keep, wptr = _weights_arg(weights)
     done = C.c_uint64(0)
     rc = native.load().svs_embed_bgr_dev(d_bgr_in, irp, ifp, d_bgr_out, orp, ofp, d_gray_ref or None,
                                          C.byref(planes), wptr, float(delta), int(n_ac), d_bits_packed,
-                                         int(bit_offset), int(n_bits), mode_flags(mode), C.byref(done),
+                                         int(bit_offset), int(n_bits), _bgr_flags(mode, keep_colour), C.byref(done),
                                          stream or None)
     native.check(rc, "svs_embed_bgr_dev")
     return int(done.value)
@@ -296,9 +301,10 @@ def _as_bgr_stack(frames: np.ndarray) -> np.ndarray:
 
 
 def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
-                     device: int = 0, mode: str | None = None, weights=None, want_gray: bool = True):
-    """BGR frames in, stego BGR frames out (one fused pass on the GPU).
-    Returns (stego_bgr uint8 [F,H,W,3], gray uint8 [F,H,W] or None, n_embedded)."""
+                     device: int = 0, mode: str | None = None, weights=None, want_gray: bool = True,
+                     keep_colour: bool = False):
+    """BGR frames in, stego BGR frames out (one fused pass on the GPU).  keep_colour: see embed_bgr_device.
+    Returns (stego_bgr uint8 [F,H,W,3], gray uint8 [F,H,W] (the cover's) or None, n_embedded)."""
     lib = native.load()
     native.ensure_device(device)
     stack = _as_bgr_stack(frames_bgr)
@@ -318,7 +324,7 @@ def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int 
     done = C.c_uint64(0)
     rc = lib.svs_embed_bgr(stack.ctypes.data, out.ctypes.data, gray.ctypes.data if want_gray else None,
                            C.byref(planes), wptr, float(delta), int(n_ac), packed.ctypes.data, int(bit_offset),
-                           int(n_bits), mode_flags(mode), C.byref(done))
+                           int(n_bits), _bgr_flags(mode, keep_colour), C.byref(done))
     native.check(rc, "svs_embed_bgr")
     used = int(done.value)
     return out, gray, used

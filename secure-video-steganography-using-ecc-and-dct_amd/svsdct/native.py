@@ -20,6 +20,7 @@ SVS_ERR_NO_DEVICE = -3
 SVS_ERR_CAPACITY = -4
 SVS_EXACT_POCKETFFT = 1      # flags bit: pocketfft-identical arithmetic (include/svsdct.h)
 SVS_EXACT_GUARDED = 2        # flags bit: the same bit-identical result through the guarded kernel where it applies
+SVS_KEEP_COLOUR = 0x100      # flags bit, fused colour embed only: stego pixels keep the cover's colour (include/svsdct.h)
 ABI_VERSION = 4
 
 

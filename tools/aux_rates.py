@@ -50,6 +50,8 @@ for mode in ("fast", "guarded", "exact"):
     timed(f"3-step chain {mode}", chain, 10 * px)
     timed(f"fused embed_bgr {mode}", lambda: batch.embed_bgr_device(bgr.data_ptr(), back.data_ptr(), 0, planes, delta, n_ac, bits.data_ptr(), 0, cap, st, mode=mode), 6 * px)
     timed(f"fused +gray ref {mode}", lambda: batch.embed_bgr_device(bgr.data_ptr(), back.data_ptr(), gray.data_ptr(), planes, delta, n_ac, bits.data_ptr(), 0, cap, st, mode=mode), 7 * px)
+    # SVS_KEEP_COLOUR: same 6 B/pixel of essential traffic (+3 B/pixel re-read of the cover, meant to be served from the Infinity Cache)
+    timed(f"keep-colour embed_bgr {mode}", lambda: batch.embed_bgr_device(bgr.data_ptr(), back.data_ptr(), 0, planes, delta, n_ac, bits.data_ptr(), 0, cap, st, mode=mode, keep_colour=True), 6 * px)
 def chain_x():
     native.check(lib.svs_bgr_to_gray_dev(back.data_ptr(), 3 * W, 3 * W * H, gray.data_ptr(), C.byref(planes), None, st), "x")
     batch.extract_device(gray.data_ptr(), planes, delta, n_ac, out_bits.data_ptr(), out_bits.numel(), st)
