@@ -2,6 +2,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC  (see csrc/Makefile)
 #include "svsdct.h"
 #include "svs_device.hpp"
+#include "svs_route.hpp"
 #include "svs_stage.hpp"
 
 #include <cstdarg>
@@ -9,10 +10,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
-#include <utility>
+#include <type_traits>
 
 namespace {
 
@@ -59,30 +58,20 @@ uint32_t knob(const char *name, uint32_t dflt) {
 constexpr uint32_t knob(const char *, uint32_t dflt) { return dflt; }
 #endif
 
-// Test hooks of the experiments library: SVS_GUARD_SCALE multiplies BETA's coefficients (the streaming embed kernels' guard,
-// make_guard), SVS_TIE_SCALE the tie margin of FAST extraction (make_qim).  Below 1 the result is NOT the reference's any
-// more: tests/test_gpu_guard_sensitivity.py uses them to show that the suite notices a bound that is too tight.
-// tests/hostemu applies the same float multiplications (emu_set_guard_scale / emu_set_tie_scale).
-void scale_guard(svs::QimParams &qp) {
+// The routing arguments of a call (svs_route.hpp).  Test hooks of the experiments library: SVS_GUARDED_OFF sends the gray
+// embed to the exact kernel and GUARDED extraction to the pocketfft-identical one; SVS_GUARD_SCALE multiplies BETA's
+// coefficients (the streaming embed kernels' guard), SVS_TIE_SCALE the tie margin of FAST extraction.  Below 1 the result is
+// NOT the reference's any more: tests/test_gpu_guard_sensitivity.py uses them to show that the suite notices a bound that is
+// too tight.  tests/hostemu applies the same scales (emu_set_guard_scale / emu_set_tie_scale).
+svs::RouteArgs route_args(double delta, const svs::Geometry &g, uint64_t total, uint64_t n_bits, uint64_t bit_offset,
+                          uint32_t flags, bool bgr) {
+    svs::RouteArgs a{delta, g.n_ac, total, n_bits, bit_offset, (flags & SVS_EXACT_POCKETFFT) != 0,
+                     (flags & SVS_EXACT_GUARDED) != 0, bgr, knob("SVS_GUARDED_OFF", 0) != 0, 1.0f, 1.0f};
 #if defined(SVS_EXPERIMENTS)
-    if (const char *sc = getenv("SVS_GUARD_SCALE")) {
-        const float f = (float)atof(sc);
-        qp.g_sum *= f; qp.g_resid *= f; qp.g_delta *= f;
-    }
-#else
-    (void)qp;
+    if (const char *sc = getenv("SVS_GUARD_SCALE")) a.guard_scale = (float)atof(sc);
+    if (const char *sc = getenv("SVS_TIE_SCALE")) a.tie_scale = (float)atof(sc);
 #endif
-}
-
-void scale_tie(svs::QimParams &qp) {
-#if defined(SVS_EXPERIMENTS)
-    if (const char *sc = getenv("SVS_TIE_SCALE")) {
-        const float f = (float)atof(sc);
-        qp.tie_slope *= f; qp.tie2_sum *= f; qp.tie2_resid *= f; qp.tie2_c00 *= f; qp.tie2_max *= f;
-    }
-#else
-    (void)qp;
-#endif
+    return a;
 }
 
 // Occupancy cap: unused dynamic LDS such that at most `wg_per_cu` workgroups fit the CU's 160 KB.  The one-row embed kernel
@@ -123,31 +112,35 @@ int make_geometry(const svs_planes *p, int n_ac, svs::Geometry *g, uint64_t *tot
     return SVS_OK;
 }
 
+// the planes of an extract call -> its geometry, blocks and capacity in bits (0: nothing to extract)
+int extract_geometry(const svs_planes *p, int n_ac, svs::Geometry *g, uint64_t *total, uint64_t *cap, uint64_t *n_bits_out) {
+    if (int rc = make_geometry(p, n_ac, g, total)) return rc;
+    if (n_bits_out) *n_bits_out = 0;
+    *cap = *total * (uint64_t)g->n_ac;
+    return SVS_OK;
+}
+
+int check_capacity(uint64_t need, uint64_t have, const char *unit) {
+    if (have >= need) return SVS_OK;
+    return fail(SVS_ERR_CAPACITY, "extract needs %llu %s, buffer has %llu", (unsigned long long)need, unit, (unsigned long long)have);
+}
+
 uint64_t span_bytes(const svs_planes *p) {
     if (p->n_frames == 0) return 0;
     return (uint64_t)(p->n_frames - 1) * p->frame_pitch + (uint64_t)(p->height - 1) * p->row_pitch + p->width;
 }
 
-using svs::rows_for;
-
 // ---- launch tuning (measured on MI355X, 600 x 4K frames; profiles/history/r01_ab_variants.txt) ----------------
 // * workgroup -> tile mapping (svs::tile_id): giving each XCD-group a contiguous eighth of the batch lifts the embed kernels
 //   ~+6..12 % (reads and writes of one XCD stay on neighbouring DRAM pages) and is never worse than the identity map.  The
-//   read-only extract kernels (profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
-//   (+3 %); two rows (n = 8..15) - the identity map (+6.7 % at 600 x 4K, +4.4 % at 2 400 x 1080p over the contiguous eighth,
-//   equal at 300 x 1080p); more rows - VALU-bound, the map does not matter.
+//   extract kernels' maps: svs_route.hpp.
 // * two blocks per lane (16-byte accesses) pays only for the embed kernel at one coefficient row; with more rows the extra
-//   registers cost occupancy (n = 10: -17 %).
-constexpr uint32_t kEighth = 0xFFFFFFFFu;
-
-uint32_t extract_chunk(int rows) { return rows == 1 ? 32u : (rows == 2 ? 0u : kEighth); }
-
+//   registers cost occupancy (n = 10: -17 %).  The one-row pocketfft-identical extract kernel keeps one block per lane: ahead
+//   by 0.1 - 3 % on every large batch and level at 300 x 1080p, 37 instead of 54 VGPRs (profiles/r05_ab_extract_bpl.txt).
 bool rows_allow_two_blocks(const svs_planes *p, const void *a, const void *b) {
     return ((p->width / 8) % 2 == 0) && (p->row_pitch % 16 == 0) && (p->frame_pitch % 16 == 0) &&
            ((uintptr_t)a % 16 == 0) && (b == nullptr || (uintptr_t)b % 16 == 0);
 }
-
-using svs::make_qim;
 
 // Occupancy cap of the one-row embed kernel (workgroups of 256 threads per CU = waves per SIMD).  Round 6, the integer-domain
 // kernel (66 - 71 VGPRs: 7 waves per SIMD uncapped): measured with pure copies, the rate of this access pattern falls - and its
@@ -164,131 +157,157 @@ uint32_t embed_wg_per_cu(int bpl) { return bpl == 2 ? 4u : 6u; }
 #if defined(SVS_EXPERIMENTS)
 unsigned long long *g_guard_counter = nullptr;
 #define SVS_COUNTER_ARG , g_guard_counter
-#else
-#define SVS_COUNTER_ARG
-#endif
 
-// static LDS of embed_row1_kernel (the waves' worklists and transposition tiles)
-constexpr uint32_t kEmbedLds = (SVS_WG / 64) * (SVS_GUARD_CAP * sizeof(svs::GuardEntry) + 8 * SVS_GUARD_TILE * sizeof(float));
-
-template <int QM, int BPL>
-int launch_embed(int rows, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego, const svs::Geometry &g,
-                 const svs::QimParams &qp, const uint32_t *bits, uint64_t bit_offset, uint64_t n_bits,
-                 uint32_t n_words) {
-    const dim3 grid((uint32_t)((total + SVS_WG * BPL - 1) / (SVS_WG * BPL)));
-    if (rows == 1) {   // one coefficient row: the integer-domain kernel (round 6), under its occupancy cap
-        const uint32_t lds_pad = lds_pad_for(embed_wg_per_cu(BPL), kEmbedLds);
-        hipLaunchKernelGGL((svs::embed_row1_kernel<QM, BPL>), grid, dim3(SVS_WG), lds_pad, st, gray, stego, g, qp, bits, bit_offset, n_bits,
-                           n_words SVS_COUNTER_ARG);
-    } else if (rows == 2 && BPL == 1) {
-        // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
-        if (g.n_ac == 10)
-            hipLaunchKernelGGL((svs::embed_kernel<2, QM, 1, 10>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits, bit_offset, n_bits,
-                               n_words SVS_COUNTER_ARG);
-        else
-            hipLaunchKernelGGL((svs::embed_kernel<2, QM, 1>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits, bit_offset, n_bits,
-                               n_words SVS_COUNTER_ARG);
-    } else {
-        return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d, %d blocks per lane", rows, BPL);
-    }
-    SVS_HIP(hipGetLastError());
-    return SVS_OK;
-}
-
-template <int QM>
-int launch_extract(int rows, uint64_t total, hipStream_t st, const uint8_t *gray, const svs::Geometry &g,
-                   const svs::QimParams &qp, uint8_t *out, uint64_t out_bytes) {
-    const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
-    // n = 10 (the reference GUI's default) has a compile-time-n instantiation of the extract kernel: +1..7 %
-    // (profiles/history/r01_ab_quant_exact.txt).  The same specialisation of the embed kernel measured SLOWER (-13 % at
-    // 600 x 4K, n = 10) and n = 3 gains nothing (HBM-bound), so those stay on the run-time-n kernels.
-    if (g.n_ac == 10) {
-        hipLaunchKernelGGL((svs::extract_kernel<2, QM, 1, 10>), grid, dim3(SVS_WG), 0, st, gray, g, qp, out, out_bytes);
-        SVS_HIP(hipGetLastError());
-        return SVS_OK;
-    }
-#define SVS_CASE(R)                                                                                                  \
-    case R:                                                                                                          \
-        hipLaunchKernelGGL((svs::extract_kernel<R, QM, 1>), grid, dim3(SVS_WG), 0, st, gray, g, qp, out, out_bytes); \
-        break;
-    switch (rows) {   // one row takes the pocketfft-identical kernel (launch_extract_exact)
-        SVS_CASE(2) SVS_CASE(3) SVS_CASE(4) SVS_CASE(5) SVS_CASE(6) SVS_CASE(7) SVS_CASE(8)
-        default: return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
-    }
-#undef SVS_CASE
-    SVS_HIP(hipGetLastError());
-    return SVS_OK;
-}
-
-int launch_embed_exact(int qm, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
-                       const svs::Geometry &g, const svs::QimParams &qp, const uint32_t *bits, uint64_t bit_offset,
-                       uint64_t n_bits, uint32_t n_words) {
-    // the kernel's quantiser loop is instantiated for one or two coefficient rows (n <= 7: the benchmark's 3; n <= 15: the
-    // reference GUI's 10) and for all eight (any n): fewer wave-uniform tests per block, same arithmetic
-    const int rows = rows_for((int)g.n_ac);
-    const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
-#define SVS_GO(QM)                                                                                                          \
-    do {                                                                                                                    \
-        if (rows == 1 && g.n_ac > 0)                                                                                        \
-            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 1>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits,       \
-                               bit_offset, n_bits, n_words);                                                                \
-        else if (rows == 2)                                                                                                 \
-            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 2>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits,       \
-                               bit_offset, n_bits, n_words);                                                                \
-        else                                                                                                                \
-            hipLaunchKernelGGL((svs::embed_exact_kernel<QM, 8>), grid, dim3(SVS_WG), 0, st, gray, stego, g, qp, bits,       \
-                               bit_offset, n_bits, n_words);                                                                \
-    } while (0)
-    if (qm == svs::QM_DOUBLE) SVS_GO(svs::QM_DOUBLE);
-    else if (qm == svs::QM_POW2) SVS_GO(svs::QM_POW2);
-    else SVS_GO(svs::QM_F32);
-#undef SVS_GO
-    SVS_HIP(hipGetLastError());
-    return SVS_OK;
-}
-
-// (Round 4 took two blocks per lane for the one-row pocketfft-identical extract kernel on one in-process A/B; the same A/B on
-// four more boxes and against the round-2 library has one block per lane ahead by 0.1 - 3 % on every large batch and level at
-// 300 x 1080p, 37 instead of 54 VGPRs: profiles/r05_ab_extract_bpl.txt.)
-template <int QM>
-int launch_extract_exact(int rows, uint64_t total, hipStream_t st, const uint8_t *gray, const svs::Geometry &g,
-                         const svs::QimParams &qp, uint8_t *out, uint64_t out_bytes) {
-    const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
-#define SVS_CASE(R)                                                                                                  \
-    case R:                                                                                                          \
-        hipLaunchKernelGGL((svs::extract_exact_kernel<R, QM>), grid, dim3(SVS_WG), 0, st, gray, g, qp, out, out_bytes); \
-        break;
-    switch (rows) {
-        SVS_CASE(1) SVS_CASE(2) SVS_CASE(3) SVS_CASE(4) SVS_CASE(5) SVS_CASE(6) SVS_CASE(7) SVS_CASE(8)
-        default: return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
-    }
-#undef SVS_CASE
-    SVS_HIP(hipGetLastError());
-    return SVS_OK;
-}
-
-struct DevBuf {  // RAII (measurement hooks of the experiments library)
+struct DevBuf {  // RAII (measurement hooks)
     void *p = nullptr;
     ~DevBuf() {
         if (p) (void)hipFree(p);
     }
 };
+#else
+#define SVS_COUNTER_ARG
+#endif
+
+// ---- kernel dispatch --------------------------------------------------------------------------------------------------
+// dispatch<Vs...>(v, f) calls f(std::integral_constant<int, v>) when v is one of Vs.  Each call site lists the values it
+// instantiates: the kernel families have exactly these instantiations, and nothing else is compiled.
+template <int V, int... Vs, class F>
+int dispatch(int v, F &&f) {
+    if (v == V) return f(std::integral_constant<int, V>{});
+    if constexpr (sizeof...(Vs) > 0) return dispatch<Vs...>(v, f);
+    else return fail(SVS_ERR_INVALID_ARG, "internal: no kernel instantiation for %d", v);
+}
+
+template <class F>
+int with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+dim3 grid_for(uint64_t total_blocks, int bpl = 1) { return dim3((uint32_t)((total_blocks + SVS_WG * bpl - 1) / (SVS_WG * bpl))); }
+
+template <class K, class... A>
+int launch(K kernel, dim3 grid, uint32_t lds, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(SVS_WG), lds, st, args...);
+    SVS_HIP(hipGetLastError());
+    return SVS_OK;
+}
+
+using svs::EmbedPath;
+using svs::ExtractPath;
+
+// svs_embed_dev's plan: embed_row1_kernel (one coefficient row, and the copy), embed_kernel<2> (two rows) or embed_exact_kernel.
+// `two`: two blocks per lane, where the plan and the buffers allow it.
+int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
+                 svs::Geometry g, const uint32_t *bits) {
+    g.n_ac = p.n_ac;
+    g.xcd_chunk = p.xcd_chunk;
+    const uint32_t words = (uint32_t)p.n_words;
+    return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
+        constexpr int QM = decltype(qm)::value;
+        if (p.path == EmbedPath::EXACT || p.path == EmbedPath::ROUND_TRIP)
+            // the exact kernel's quantiser loop is instantiated for one or two coefficient rows (n <= 7: the benchmark's 3;
+            // n <= 15: the reference GUI's 10) and for all eight (any n): fewer wave-uniform tests per block, same arithmetic
+            return dispatch<1, 2, 8>(p.rows, [&](auto u) {
+                return launch(svs::embed_exact_kernel<QM, decltype(u)::value>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
+                              p.bit_offset, p.n_bits, words);
+            });
+        if (p.rows == 2)   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
+            return g.n_ac == 10 ? launch(svs::embed_kernel<2, QM, 1, 10>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
+                                         p.bit_offset, p.n_bits, words SVS_COUNTER_ARG)
+                                : launch(svs::embed_kernel<2, QM, 1>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
+                                         p.bit_offset, p.n_bits, words SVS_COUNTER_ARG);
+        // one coefficient row: the integer-domain kernel (round 6), under its occupancy cap
+        return dispatch<1, 2>(two ? 2 : 1, [&](auto bpl) {
+            constexpr int BPL = decltype(bpl)::value;
+            return launch(svs::embed_row1_kernel<QM, BPL>, grid_for(total, BPL), lds_pad_for(embed_wg_per_cu(BPL), svs::kRow1StaticLds),
+                          st, gray, stego, g, p.qp, bits, p.bit_offset, p.n_bits, words SVS_COUNTER_ARG);
+        });
+    });
+}
+
+// svs_embed_bgr_dev's plan: embed_bgr_kernel<8, QM, true> (exact, round trip) or <1 | 2, QM, false> (streaming, convert)
+int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStream_t st, const uint8_t *in, uint8_t *out,
+                     uint8_t *ref, svs::Geometry g, const svs::ColourParams &c, const uint32_t *bits) {
+    g.n_ac = p.n_ac;
+    g.xcd_chunk = p.xcd_chunk;
+    const uint32_t words = (uint32_t)p.n_words;
+    const bool exact = p.path == EmbedPath::EXACT || p.path == EmbedPath::ROUND_TRIP;
+    return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
+        return with_bool(keep, [&](auto keep_c) {
+            constexpr int QM = decltype(qm)::value;
+            constexpr bool KEEP = decltype(keep_c)::value;
+            if (exact)
+                return launch(svs::embed_bgr_kernel<8, QM, true, KEEP>, grid_for(total), 0, st, in, out, ref, g, c, p.qp, bits,
+                              p.bit_offset, p.n_bits, words);
+            return dispatch<1, 2>(p.rows, [&](auto u) {
+                return launch(svs::embed_bgr_kernel<decltype(u)::value, QM, false, KEEP>, grid_for(total), 0, st, in, out, ref, g, c,
+                              p.qp, bits, p.bit_offset, p.n_bits, words);
+            });
+        });
+    });
+}
+
+// svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>
+int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
+                   uint64_t out_bytes) {
+    if (p.path == ExtractPath::ZEROS) {
+        SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
+        return SVS_OK;
+    }
+    g.xcd_chunk = p.xcd_chunk;
+    return dispatch<svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
+        constexpr int QM = decltype(qm)::value;
+        if (p.path == ExtractPath::EXACT)
+            return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
+                return launch(svs::extract_exact_kernel<decltype(r)::value, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes);
+            });
+        // n = 10 (the reference GUI's default) has a compile-time-n instantiation of the extract kernel: +1..7 %
+        // (profiles/history/r01_ab_quant_exact.txt).  The same specialisation of the embed kernel measured SLOWER (-13 % at
+        // 600 x 4K, n = 10) and n = 3 gains nothing (HBM-bound), so those stay on the run-time-n kernels.
+        if (g.n_ac == 10) return launch(svs::extract_kernel<2, QM, 1, 10>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes);
+        return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
+            return launch(svs::extract_kernel<decltype(r)::value, QM, 1>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes);
+        });
+    });
+}
+
+// svs_extract_bgr_dev's plan: extract_bgr_kernel<1..8, QM, false> (pocketfft-identical forward) or <2..8, QM, true> (FAST)
+int launch_extract_bgr(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *bgr, svs::Geometry g,
+                       const svs::ColourParams &c, uint8_t *out, uint64_t out_bytes) {
+    if (p.path == ExtractPath::ZEROS) {
+        SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
+        return SVS_OK;
+    }
+    g.xcd_chunk = p.xcd_chunk;
+    return dispatch<svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
+        constexpr int QM = decltype(qm)::value;
+        if (p.path == ExtractPath::FAST)
+            return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
+                return launch(svs::extract_bgr_kernel<decltype(r)::value, QM, true>, grid_for(total), 0, st, bgr, g, c, p.qp, out,
+                              out_bytes);
+            });
+        return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
+            return launch(svs::extract_bgr_kernel<decltype(r)::value, QM, false>, grid_for(total), 0, st, bgr, g, c, p.qp, out,
+                          out_bytes);
+        });
+    });
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Staging context of the HOST-pointer entry points (svs_embed / svs_extract, their _str and _bgr forms).
 // What the reference's per-frame call sites hit (embed_process.py:117-121, extract_process.py:64-68: NumPy arrays in, NumPy
 // arrays out), so it has to run at the rate of the PCIe link, not of hipMalloc:
-//   * one context per HOST THREAD (thread_local): two non-blocking streams and grow-only device buffers.  Nothing is
-//     allocated or freed per call once the buffers have grown to the largest call seen;
-//     svs_shutdown() (or the thread's exit) releases them.  No state carries RESULTS from one call to the next - a call
-//     leaves nothing behind that a later call reads - and two host threads never share a context, so the entry points stay
-//     re-entrant and thread-safe.
+//   * one context per HOST THREAD (thread_local): two non-blocking streams and device buffers that grow on demand.  Once
+//     they have grown to the largest call seen nothing is allocated or freed per call, except that a buffer above 64 MB
+//     which eight calls in a row used less than a quarter of is given back (stage_reserve).  Every call reserves all the
+//     buffers it needs at its entry, before it queues anything: hipFree waits for the device, and must not wait for the
+//     call's own work.  svs_shutdown() (or the thread's exit) releases them.  No state carries RESULTS from one call to the
+//     next - a call leaves nothing behind that a later call reads - and two host threads never share a context, so the
+//     entry points stay re-entrant and thread-safe.
 //   * the frames travel in chunks (whole frames, or bands of block rows of a large frame): every upload and kernel goes to
 //     the context's UP stream, in order; every download to its DOWN stream, behind an event recorded after the chunk's
 //     kernel - so chunk k+1's upload runs while chunk k's download does (the link is full duplex).  (Chunks dealt
-//     round-robin to three streams - the first form of this code - fall into lockstep: all three upload together, then
-//     all three download, and the batch moves at the SERIAL rate of the link, 26.6 instead of 40+ Gpixel/s,
-//     profiles/r05_pcie_rate.txt.)  The payload is uploaded once; every chunk indexes it by bit offset.
+//     round-robin to three streams fall into lockstep: all three upload together, then all three download, and the batch
+//     moves at the SERIAL rate of the link, 26.6 instead of 40+ Gpixel/s, profiles/r05_pcie_rate.txt.)  The payload is
+//     uploaded once; every chunk indexes it by bit offset.
 //   * a host buffer that is page-locked (svs_host_alloc, hipHostMalloc, hipHostRegister) is the source / target of the DMA
 //     itself; pageable memory goes through the runtime's staging (uploads at the same rate, downloads at about half of it,
 //     a FRESH pageable result array - page faults - at a quarter: hand the library page-locked OUTPUT buffers, as
@@ -378,20 +397,11 @@ int stage_h2d(hipStream_t st, void *d_dst, const void *h_src, size_t bytes) {
     return SVS_OK;
 }
 
-// device -> host on `st`; complete after stage_finish()
+// device -> host on `st`; complete when the call's streams are drained
 int stage_d2h(hipStream_t st, void *h_dst, const void *d_src, size_t bytes) {
     if (bytes == 0) return SVS_OK;
     SVS_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, st));
     return SVS_OK;
-}
-
-// end of a call: both streams drained (every copy into the caller's buffers has landed).  Also the error path: a call that
-// fails half way must not leave a DMA in flight into the caller's buffers.
-int stage_finish(HostStage &c) {
-    int rc = SVS_OK;
-    for (auto &s : c.st)
-        if (s && hipStreamSynchronize(s) != hipSuccess) rc = rc ? rc : fail(SVS_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
 }
 
 // the DOWN stream may start on what the UP stream has enqueued so far
@@ -402,20 +412,25 @@ int stage_handoff(HostStage &c) {
     return SVS_OK;
 }
 
-struct StageGuard {   // runs stage_finish on every exit path of an entry point
-    HostStage *c;
-    explicit StageGuard(HostStage *ctx) : c(ctx) {}
-    int done(int rc) {
-        const int e = stage_finish(*c);
-        c = nullptr;
-        return rc ? rc : e;
-    }
-    ~StageGuard() { if (c) (void)stage_finish(*c); }
-};
-
-using svs::Chunk;
-using svs::chunk_budget;
-using svs::for_each_chunk;
+// Runs body(context) on the calling thread's context, with the buffers the call uses reserved first (0 bytes: not used).
+// Both streams are drained before it returns, on the error path too: a call that fails half way must not leave a DMA in
+// flight into the caller's buffers.
+template <class Body>
+int staged(size_t frames, size_t second, size_t third, size_t bits, Body &&body) {
+    HostStage *ctx = nullptr;
+    if (int rc = stage_acquire(&ctx)) return rc;
+    HostStage &c = *ctx;
+    int rc = SVS_OK;
+    const size_t want[4] = {frames, second, third, bits};
+    Grow *const buf[4] = {&c.frames, &c.second, &c.third, &c.bits};
+    for (int i = 0; i < 4 && !rc; ++i)
+        if (want[i]) rc = stage_reserve(*buf[i], want[i]);
+    if (!rc) rc = body(c);
+    for (auto &s : c.st)
+        if (s && hipStreamSynchronize(s) != hipSuccess && !rc)
+            rc = fail(SVS_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
 
 // svs_stage.hpp's rule; the experiments library's SVS_STAGE_CHUNK_KB overrides it
 size_t stage_chunk_bytes(uint64_t total) {
@@ -423,25 +438,101 @@ size_t stage_chunk_bytes(uint64_t total) {
     return forced ? (size_t)forced << 10 : svs::stage_chunk_rule(total);
 }
 
-template <int QM, bool EXACT, bool KEEP>
-int launch_embed_bgr(int rows, uint64_t total, hipStream_t st, const uint8_t *in, uint8_t *out, uint8_t *ref,
-                            const svs::Geometry &g, const svs::ColourParams &c, const svs::QimParams &qp,
-                            const uint32_t *bits, uint64_t bit_offset, uint64_t n_bits, uint32_t n_words) {
-    const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
-    if constexpr (EXACT) {
-        hipLaunchKernelGGL((svs::embed_bgr_kernel<8, QM, true, KEEP>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
-                           bit_offset, n_bits, n_words);
-    } else {
-        if (rows == 1)
-            hipLaunchKernelGGL((svs::embed_bgr_kernel<1, QM, false, KEEP>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
-                               bit_offset, n_bits, n_words);
-        else if (rows == 2)
-            hipLaunchKernelGGL((svs::embed_bgr_kernel<2, QM, false, KEEP>), grid, dim3(SVS_WG), 0, st, in, out, ref, g, c, qp, bits,
-                               bit_offset, n_bits, n_words);
-        else
-            return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
+// The payload of a host-pointer embed call: packed MSB-first bits indexed by bit_offset, or `use` '0' / '1' characters
+// (ascii, bit_offset 0) that are uploaded as they are and packed on the device.  Of a packed payload only the bytes the call
+// reads go to the device - [first_byte, first_byte + bytes), first_byte dword aligned, the bit offset rebased onto it (a frame
+// loop that indexes one long stream by bit_offset stays O(batch) per call).
+struct HostPayload {
+    const uint8_t *packed;
+    const char *ascii;
+    uint64_t bit_offset, use;
+
+    uint64_t first_byte() const { return use ? (bit_offset / 32) * 4 : 0; }
+    uint64_t packed_bytes() const { return use ? (bit_offset + use + 7) / 8 - first_byte() : 0; }
+    uint64_t words() const { return (use + 31) / 32; }
+    size_t bits_bytes() const { return ascii ? 4 * words() + 8 : ((packed_bytes() + 3) / 4) * 4 + 4; }   // c.bits
+    size_t ascii_bytes() const { return ascii && use ? use + 32 : 0; }                                    // c.third
+
+    // queued on the UP stream, ahead of the kernels that read it -> the bit offset into c.bits
+    int stage(HostStage &c, uint64_t *rebased) const {
+        const hipStream_t up = c.st[0];
+        uint8_t *d = static_cast<uint8_t *>(c.bits.p);
+        const size_t alloc = bits_bytes();
+        *rebased = 0;
+        if (ascii) {
+            SVS_HIP(hipMemsetAsync(d + 4 * words(), 0, 8, up));
+            if (use == 0) return SVS_OK;
+            if (int rc = stage_h2d(up, c.third.p, ascii, use)) return rc;
+            const uint32_t blocks = (uint32_t)((words() + 255) / 256 < 2048 ? (words() + 255) / 256 : 2048);
+            hipLaunchKernelGGL(svs::ascii_to_packed_kernel, dim3(blocks), dim3(256), 0, up, static_cast<const uint8_t *>(c.third.p),
+                               use, reinterpret_cast<uint32_t *>(d), words());
+            SVS_HIP(hipGetLastError());
+            return SVS_OK;
+        }
+        *rebased = bit_offset - 8 * first_byte();
+        if (packed_bytes() == 0) {
+            SVS_HIP(hipMemsetAsync(d, 0, alloc, up));
+            return SVS_OK;
+        }
+        // the kernels read whole dwords: the tail behind the last payload byte must be defined (zero)
+        SVS_HIP(hipMemsetAsync(d + (alloc - 8), 0, 8, up));
+        return stage_h2d(up, d, packed + first_byte(), packed_bytes());
     }
-    SVS_HIP(hipGetLastError());
+};
+
+// The chunk pipeline of the host-pointer embed calls.  The frames (bpp bytes per pixel; the planes' pitches count pixels) go
+// from `src` to the same offsets of c.frames chunk by chunk: upload and embed(sub, off, bit_offset, budget, &done, up) on the UP
+// stream, then download(chunk, off, down) behind the chunk's event on the DOWN stream.  A batch of one chunk runs in order on
+// one stream - no event, no second stream.  `off` is the chunk's first byte; `rebased` the payload's first bit in c.bits.
+template <class Embed, class Download>
+int embed_chunks(HostStage &c, const svs_planes *p, int bpp, const uint8_t *src, uint32_t n, uint64_t use, uint64_t n_bits,
+                 uint64_t rebased, Embed &&embed, Download &&download, uint64_t *done_total) {
+    const int32_t H = p->height, W = p->width;
+    const int64_t rp = bpp * p->row_pitch, fp = bpp * p->frame_pitch, row_bytes = (int64_t)bpp * W;
+    const uint64_t wb = (uint64_t)W / 8, bpf = wb * ((uint64_t)H / 8);
+    // a non-empty payload that cannot be embedded (delta <= 0, n_ac = 0) must still reach the kernel as "non-empty": every
+    // block is then round-tripped, as in the reference
+    const uint64_t pass_bits = use ? use : (n_bits ? 1 : 0);
+    const size_t target = stage_chunk_bytes(bpp * span_bytes(p));
+    uint32_t n_chunks = 0;
+    svs::for_each_chunk(p->n_frames, H, (size_t)rp, target, [&](const svs::Chunk &) { ++n_chunks; });
+    const bool serial = n_chunks <= 1;
+    const hipStream_t up = c.st[0], down = serial ? c.st[0] : c.st[1];
+    uint8_t *d = static_cast<uint8_t *>(c.frames.p);
+    int rc = SVS_OK;
+    *done_total = 0;
+    svs::for_each_chunk(p->n_frames, H, (size_t)rp, target, [&](const svs::Chunk &ch) {
+        if (rc) return;
+        const int64_t off = (int64_t)ch.f0 * fp + (int64_t)ch.r0 * rp;
+        const size_t bytes = ch.nf == 1 ? (size_t)(ch.rows - 1) * rp + row_bytes : (size_t)(ch.nf - 1) * fp + (size_t)(H - 1) * rp + row_bytes;
+        if ((rc = stage_h2d(up, d + off, src + off, bytes))) return;
+        const svs_planes sub{ch.nf, ch.rows, W, 0, p->row_pitch, ch.nf == 1 ? ch.rows * p->row_pitch : p->frame_pitch};
+        const uint64_t g0 = (uint64_t)ch.f0 * bpf + (uint64_t)(ch.r0 / 8) * wb;
+        uint64_t done = 0;
+        if ((rc = embed(sub, off, rebased + (use ? g0 * n : 0), svs::chunk_budget(pass_bits, use, g0, n), &done, up))) return;
+        *done_total += done;
+        if (!serial && (rc = stage_handoff(c))) return;
+        rc = download(ch, off, down);
+    });
+    return rc;
+}
+
+// The staging of the host-pointer extract calls: `in_bytes` of `src` up, then device(d_in, d_bits, bits capacity, &n_bits, st)
+// and download(context, st).  The download is n_ac / 512 of the upload: nothing to overlap - one stream, one copy, one kernel
+// over the batch.  `third`: bytes of c.third the download uses.
+template <class Device, class Download>
+int extract_staged(const void *src, size_t in_bytes, uint64_t bytes, size_t third, uint64_t *n_bits_out, Device &&device,
+                   Download &&download) {
+    uint64_t got = 0;
+    if (int rc = staged(in_bytes, 0, third, bytes + 8, [&](HostStage &c) {
+            const hipStream_t st = c.st[0];
+            if (int rc = stage_h2d(st, c.frames.p, src, in_bytes)) return rc;
+            if (int rc = device(static_cast<const uint8_t *>(c.frames.p), static_cast<uint8_t *>(c.bits.p), bytes + 8, &got, st))
+                return rc;
+            return download(c, st);
+        }))
+        return rc;
+    if (n_bits_out) *n_bits_out = got;
     return SVS_OK;
 }
 
@@ -560,71 +651,20 @@ int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *pla
     if (!d_gray || !d_stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
     if (((uintptr_t)d_gray % 8) || ((uintptr_t)d_stego % 8))
         return fail(SVS_ERR_INVALID_ARG, "plane pointers must be 8-byte aligned");
-    const int n = (int)g.n_ac;
-    const uint64_t cap = total * (uint64_t)n;
-    uint64_t use = n_bits < cap ? n_bits : cap;
-    if (!(delta > 0.0) || n == 0) use = 0;  // nothing can be embedded (config_and_setup.py:143-145)
-    if (use > 0) {
+    const svs::EmbedPlan p = svs::plan_embed(route_args(delta, g, total, n_bits, bit_offset, flags, false));
+    if (p.use > 0) {
         if (!d_bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
         if ((uintptr_t)d_bits_packed % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
-        if (bit_offset + use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
+        if (bit_offset + p.use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
     }
-    const hipStream_t st = (hipStream_t)stream;
-    const bool two = rows_for(n) == 1 && rows_allow_two_blocks(planes, d_gray, d_stego);
-    g.xcd_chunk = kEighth;
-    svs::QimParams qp;
-    const int qm = make_qim(use == 0 ? 1.0 : delta, &qp);
     if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    const int rows = rows_for(n);
-    // Which kernel family (include/svsdct.h `flags`).  Every mode produces the reference's stego pixels; the flags only choose
-    // between two ways of getting them.  The streaming kernel (embed_kernel: cheap arithmetic, rigorous guard, in-kernel exact
-    // replay of the blocks it cannot decide) covers one and two coefficient rows (n <= 15) inside the guard's delta range and
-    // serves flags 0 and SVS_EXACT_GUARDED alike; everything else - n >= 16, delta outside the range, SVS_EXACT_POCKETFFT -
-    // runs the lane-per-block pocketfft kernel.
-    const bool in_range = delta >= SVS_GUARD_DELTA_MIN && delta <= SVS_GUARD_DELTA_MAX;
-    bool streaming = use > 0 && in_range && !(flags & SVS_EXACT_POCKETFFT) && rows <= 2;
-#if defined(SVS_EXPERIMENTS)
-    if (knob("SVS_GUARDED_OFF", 0) != 0) streaming = false;   // test hook: the exact kernel
-#endif
-    if (!streaming) {
-        if (use == 0 && n_bits == 0) {   // empty payload: the reference's loops break before the first block - a pure copy
-            if (d_gray == d_stego) return SVS_OK;
-            g.n_ac = 1;
-            return two ? launch_embed<svs::QM_F32, 2>(1, total, st, d_gray, d_stego, g, qp, nullptr, 0, 0, 0)
-                       : launch_embed<svs::QM_F32, 1>(1, total, st, d_gray, d_stego, g, qp, nullptr, 0, 0, 0);
-        }
-        if (use == 0) {
-            // a non-empty payload of which nothing can be embedded (delta <= 0, no coefficients): the reference still
-            // enters and round-trips every block (config_and_setup.py:143-145,166-169); only the exact arithmetic
-            // reproduces what that does to the pixels, so every mode takes that kernel here
-            g.n_ac = 0;
-            return launch_embed_exact(svs::QM_F32, total, st, d_gray, d_stego, g, qp, nullptr, 0, 1, 0);
-        }
-        const uint64_t words_x = ((bit_offset + use + 7) / 8 + 3) / 4;
-        if (words_x >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
-        if (int rc = launch_embed_exact(qm, total, st, d_gray, d_stego, g, qp,
-                                        reinterpret_cast<const uint32_t *>(d_bits_packed), bit_offset, use,
-                                        (uint32_t)words_x))
-            return rc;
-        if (n_embedded) *n_embedded = use;
-        return SVS_OK;
-    }
-    const uint64_t last_byte = (bit_offset + use + 7) / 8;
-    const uint64_t words = (last_byte + 3) / 4;
-    if (words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
-    const uint32_t *bw = reinterpret_cast<const uint32_t *>(d_bits_packed);
-    svs::make_guard(delta, rows, &qp);
-    scale_guard(qp);   // experiments library only
-    int rc;
-#define SVS_GO(QM)                                                                                                   \
-    rc = two ? launch_embed<QM, 2>(rows, total, st, d_gray, d_stego, g, qp, bw, bit_offset, use, (uint32_t)words)    \
-             : launch_embed<QM, 1>(rows, total, st, d_gray, d_stego, g, qp, bw, bit_offset, use, (uint32_t)words)
-    if (qm == svs::QM_DOUBLE) SVS_GO(svs::QM_DOUBLE);
-    else if (qm == svs::QM_POW2) SVS_GO(svs::QM_POW2);
-    else SVS_GO(svs::QM_F32);
-#undef SVS_GO
-    if (rc) return rc;
-    if (n_embedded) *n_embedded = use;
+    if (p.n_words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
+    if (p.path == EmbedPath::COPY && d_gray == d_stego) return SVS_OK;
+    const bool two = p.two_blocks && rows_allow_two_blocks(planes, d_gray, d_stego);
+    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g,
+                              p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr))
+        return rc;
+    if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
 }
 
@@ -632,86 +672,20 @@ int svs_extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delt
                     uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
                     void *stream) {
     svs::Geometry g;
-    uint64_t total = 0;
-    if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
-    if (n_bits_out) *n_bits_out = 0;
-    const int n = (int)g.n_ac;
-    const uint64_t cap = total * (uint64_t)n;
+    uint64_t total = 0, cap = 0;
+    if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (cap == 0) return SVS_OK;
     if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
     if ((uintptr_t)d_bits_packed_out % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
     const uint64_t bytes = (cap + 7) / 8;
-    if (out_capacity_bytes < bytes)
-        return fail(SVS_ERR_CAPACITY, "extract needs %llu bytes, buffer has %llu", (unsigned long long)bytes,
-                    (unsigned long long)out_capacity_bytes);
-    const hipStream_t st = (hipStream_t)stream;
-    if (!(delta > 0.0)) {
-        SVS_HIP(hipMemsetAsync(d_bits_packed_out, 0, bytes, st));  // every bit '0' (config_and_setup.py:143-145)
-    } else {
-        g.xcd_chunk = extract_chunk(rows_for(n));
-        svs::QimParams qp;
-        const int qm = make_qim(delta, &qp);     // the double mode only differs in requantisation: not needed here
-        scale_tie(qp);                           // experiments library only
-        const int rows = rows_for(n);
-        int rc;
-        if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-        // GUARDED extraction = the FAST kernels: their bits are the reference's for any input by construction (n <= 7: the
-        // pocketfft-identical forward; n >= 8: a block with a quantiser input inside the PROVEN per-block error bound of a
-        // rounding tie is recomputed with it, tools/guard_bound.py --tie), at 0.86 instead of 1.03 ms per 600 x 4K at n = 10.
-        // Outside the guard's delta range the flag means the pocketfft-identical kernels, as for embedding.
-        if (flags & SVS_EXACT_GUARDED)
-            flags = (delta >= SVS_GUARD_DELTA_MIN && delta <= SVS_GUARD_DELTA_MAX && knob("SVS_GUARDED_OFF", 0) == 0)   // knob: experiments library only
-                        ? 0u : SVS_EXACT_POCKETFFT;
-        // the FAST kernels with two and more rows round c / delta by adding 1.5 * 2^23, which needs |c / delta| < 2^22
-        if ((double)qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN) flags = SVS_EXACT_POCKETFFT;
-        // With one coefficient row (n <= 7) the pocketfft-identical forward transform costs 0.2-3 % (the kernel stays
-        // HBM-bound; in-process A/B in profiles/history/r01_ab_quant_exact.txt), so FAST mode uses it too and extraction is
-        // bit-identical to the reference for ANY input frame.  With more rows it costs ~17 % and stays opt-in.
-        if ((flags & SVS_EXACT_POCKETFFT) || rows == 1)
-            rc = qm == svs::QM_POW2 ? launch_extract_exact<svs::QM_POW2>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes)
-                                    : launch_extract_exact<svs::QM_F32>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
-        else
-            rc = qm == svs::QM_POW2 ? launch_extract<svs::QM_POW2>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes)
-                                    : launch_extract<svs::QM_F32>(rows, total, st, d_gray, g, qp, d_bits_packed_out, bytes);
-        if (rc) return rc;
-    }
+    if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
+    const svs::ExtractPlan p = svs::plan_extract(route_args(delta, g, total, 0, 0, flags, false));
+    // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
+    if (p.path != ExtractPath::ZEROS && (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)))
+        return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes)) return rc;
     if (n_bits_out) *n_bits_out = cap;
-    return SVS_OK;
-}
-
-// payload window of a host-pointer embed call: only the bytes this call reads go to the device - [first_byte, last_byte),
-// first_byte dword aligned, the bit offset rebased onto it (a frame loop that indexes one long stream by bit_offset stays
-// O(batch) per call).  Uploaded on the UP stream, ahead of the kernels that read it.
-static int stage_payload(HostStage &c, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t use, uint64_t *rebased) {
-    const uint64_t first_byte = use ? (bit_offset / 32) * 4 : 0;
-    const uint64_t bit_bytes = use ? (bit_offset + use + 7) / 8 - first_byte : 0;
-    const uint64_t bit_alloc = ((bit_bytes + 3) / 4) * 4 + 4;
-    if (int rc = stage_reserve(c.bits, bit_alloc)) return rc;
-    if (bit_bytes) {
-        // the kernels read whole dwords: the tail behind the last payload byte must be defined (zero)
-        SVS_HIP(hipMemsetAsync(static_cast<uint8_t *>(c.bits.p) + (bit_alloc - 8), 0, 8, c.st[0]));
-        if (int rc = stage_h2d(c.st[0], c.bits.p, bits_packed + first_byte, bit_bytes))
-            return rc;
-    } else {
-        SVS_HIP(hipMemsetAsync(c.bits.p, 0, bit_alloc, c.st[0]));
-    }
-    *rebased = bit_offset - 8 * first_byte;
-    return SVS_OK;
-}
-
-// the same for a payload of `use` '0' / '1' characters: uploaded as they are (one byte per bit) and packed on the device
-static int stage_payload_ascii(HostStage &c, const char *bits_ascii, uint64_t use) {
-    const uint64_t words = (use + 31) / 32, bit_alloc = 4 * words + 8;
-    if (int rc = stage_reserve(c.bits, bit_alloc)) return rc;
-    SVS_HIP(hipMemsetAsync(static_cast<uint8_t *>(c.bits.p) + 4 * words, 0, 8, c.st[0]));
-    if (use == 0) return SVS_OK;
-    if (int rc = stage_reserve(c.third, use + 32)) return rc;
-    if (int rc = stage_h2d(c.st[0], c.third.p, bits_ascii, use)) return rc;
-    const uint32_t blocks = (uint32_t)((words + 255) / 256 < 2048 ? (words + 255) / 256 : 2048);
-    hipLaunchKernelGGL(svs::ascii_to_packed_kernel, dim3(blocks), dim3(256), 0, c.st[0], static_cast<const uint8_t *>(c.third.p), use,
-                       static_cast<uint32_t *>(c.bits.p), words);
-    SVS_HIP(hipGetLastError());
     return SVS_OK;
 }
 
@@ -750,66 +724,47 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
     if (!(delta > 0.0)) use = 0;                   // nothing can be embedded (config_and_setup.py:143-145)
     if (use && !bits_packed && !bits_ascii) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
     if (use && bit_offset + use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
-    HostStage *ctx = nullptr;
-    if (int rc = stage_acquire(&ctx)) return rc;
-    HostStage &c = *ctx;
-    StageGuard guard(ctx);
-    if (int rc = stage_reserve(c.frames, span)) return guard.done(rc);
-    uint64_t rebased = 0;
-    if (bits_ascii) {
-        if (int rc = stage_payload_ascii(c, bits_ascii, use)) return guard.done(rc);
-    } else if (int rc = stage_payload(c, bits_packed, bit_offset, use, &rebased)) {
-        return guard.done(rc);
-    }
-    // a non-empty payload that cannot be embedded (delta <= 0, n_ac = 0) must still reach the kernel as "non-empty": every
-    // block is then round-tripped, as in the reference
-    const uint64_t pass_bits = use ? use : (n_bits ? 1 : 0);
+    const HostPayload payload{bits_packed, bits_ascii, bit_offset, use};
     const int32_t H = planes->height, W = planes->width;
     const int64_t rp = planes->row_pitch, fp = planes->frame_pitch;
     const bool rows_packed = rp == W, frames_packed = rows_packed && fp == (int64_t)H * W;
-    const uint64_t wb = (uint64_t)W / 8, bpf = wb * ((uint64_t)H / 8);
-    uint8_t *d = static_cast<uint8_t *>(c.frames.p);
-    uint64_t done_total = 0;
-    int rc = SVS_OK;
     // in-place embedding (stego overlaps gray) with a gray reference asked for: the reference must be taken BEFORE the first
-    // download lands in the source (a pageable download blocks, so it used to happen on every such call)
+    // download lands in the source (a pageable download blocks)
     const bool ref_first = gray_ref_out && gray_ref_out != gray && ranges_overlap(gray, stego, span);
-    if (ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
-    // one chunk (a frame below 8 MB): everything in order on one stream - no event, no second stream
-    uint32_t n_chunks = 0;
-    for_each_chunk(planes->n_frames, H, (size_t)rp, stage_chunk_bytes(span), [&](const Chunk &) { ++n_chunks; });
-    const bool serial = n_chunks <= 1;
-    hipStream_t up = c.st[0], st = serial ? c.st[0] : c.st[1];
-    for_each_chunk(planes->n_frames, H, (size_t)rp, stage_chunk_bytes(span), [&](const Chunk &ch) {
-        if (rc) return;
-        const int64_t off = (int64_t)ch.f0 * fp + (int64_t)ch.r0 * rp;
-        const size_t bytes = ch.nf == 1 ? (size_t)(ch.rows - 1) * rp + W : (size_t)(ch.nf - 1) * fp + (size_t)(H - 1) * rp + W;
-        if ((rc = stage_h2d(up, d + off, gray + off, bytes))) return;
-        const svs_planes sub{ch.nf, ch.rows, W, 0, rp, ch.nf == 1 ? (int64_t)ch.rows * rp : fp};
-        const uint64_t g0 = (uint64_t)ch.f0 * bpf + (uint64_t)(ch.r0 / 8) * wb;
-        uint64_t done = 0;
-        if ((rc = svs_embed_dev(d + off, d + off, &sub, delta, n_ac, static_cast<const uint8_t *>(c.bits.p),
-                                rebased + (use ? g0 * (uint64_t)g.n_ac : 0), chunk_budget(pass_bits, use, g0, g.n_ac), flags, &done, up)))
-            return;
-        done_total += done;
-        if (!serial && (rc = stage_handoff(c))) return;
-        // back: pixel bytes only (padding in the caller's stego buffer is left alone)
-        if (frames_packed || (rows_packed && ch.nf == 1)) {
-            rc = stage_d2h(st, stego + off, d + off, ch.nf == 1 ? (size_t)ch.rows * W : (size_t)ch.nf * H * W);
-        } else {
-            for (int32_t f = 0; f < ch.nf && !rc; ++f) {
-                const int64_t o = off + (int64_t)f * fp;
-                if (rows_packed) rc = stage_d2h(st, stego + o, d + o, (size_t)ch.rows * W);
-                else if (hipMemcpy2DAsync(stego + o, (size_t)rp, d + o, (size_t)rp, (size_t)W, (size_t)ch.rows, hipMemcpyDeviceToHost, st) != hipSuccess)
-                    rc = fail(SVS_ERR_HIP, "hipMemcpy2DAsync failed: %s", hipGetErrorString(hipGetLastError()));
-            }
-        }
-    });
-    // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the thread would
-    // only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first - that copy was made above.)
-    if (!rc && gray_ref_out && gray_ref_out != gray && !ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
-    rc = guard.done(rc);
-    if (rc) return rc;
+    uint64_t done_total = 0;
+    if (int rc = staged(span, 0, payload.ascii_bytes(), payload.bits_bytes(), [&](HostStage &c) {
+            uint64_t rebased = 0;
+            if (int rc = payload.stage(c, &rebased)) return rc;
+            if (ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
+            uint8_t *d = static_cast<uint8_t *>(c.frames.p);
+            const int rc = embed_chunks(
+                c, planes, 1, gray, g.n_ac, use, n_bits, rebased,
+                [&](const svs_planes &sub, int64_t off, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
+                    return svs_embed_dev(d + off, d + off, &sub, delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset,
+                                         budget, flags, done, up);
+                },
+                [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {
+                    // back: pixel bytes only (padding in the caller's stego buffer is left alone)
+                    if (frames_packed || (rows_packed && ch.nf == 1))
+                        return stage_d2h(st, stego + off, d + off, ch.nf == 1 ? (size_t)ch.rows * W : (size_t)ch.nf * H * W);
+                    for (int32_t f = 0; f < ch.nf; ++f) {
+                        const int64_t o = off + (int64_t)f * fp;
+                        if (rows_packed) {
+                            if (int rc = stage_d2h(st, stego + o, d + o, (size_t)ch.rows * W)) return rc;
+                        } else if (hipMemcpy2DAsync(stego + o, (size_t)rp, d + o, (size_t)rp, (size_t)W, (size_t)ch.rows,
+                                                    hipMemcpyDeviceToHost, st) != hipSuccess) {
+                            return fail(SVS_ERR_HIP, "hipMemcpy2DAsync failed: %s", hipGetErrorString(hipGetLastError()));
+                        }
+                    }
+                    return (int)SVS_OK;
+                },
+                &done_total);
+            // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
+            // thread would only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first.)
+            if (!rc && gray_ref_out && gray_ref_out != gray && !ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
+            return rc;
+        }))
+        return rc;
     if (n_embedded) *n_embedded = done_total;
     return SVS_OK;
 }
@@ -849,70 +804,41 @@ int svs_embed_str(const uint8_t *gray, uint8_t *gray_ref_out, uint8_t *stego, co
 int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, uint8_t *bits_packed_out,
                 uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
     svs::Geometry g;
-    uint64_t total = 0;
-    if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
-    if (n_bits_out) *n_bits_out = 0;
-    const uint64_t cap = total * (uint64_t)g.n_ac;
+    uint64_t total = 0, cap = 0;
+    if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     const uint64_t bytes = (cap + 7) / 8;
-    if (out_capacity_bytes < bytes)
-        return fail(SVS_ERR_CAPACITY, "extract needs %llu bytes, buffer has %llu", (unsigned long long)bytes,
-                    (unsigned long long)out_capacity_bytes);
-    const uint64_t span = span_bytes(planes);
-    HostStage *ctx = nullptr;
-    if (int rc = stage_acquire(&ctx)) return rc;
-    HostStage &c = *ctx;
-    StageGuard guard(ctx);
-    if (int rc = stage_reserve(c.frames, span)) return guard.done(rc);
-    if (int rc = stage_reserve(c.bits, bytes + 8)) return guard.done(rc);
-    // the download is n_ac / 512 of the upload: nothing to overlap - one stream, one copy, one kernel over the batch
-    hipStream_t st = c.st[0];
-    if (int rc = stage_h2d(st, c.frames.p, gray, span)) return guard.done(rc);
-    uint64_t got = 0;
-    if (int rc = svs_extract_dev(static_cast<const uint8_t *>(c.frames.p), planes, delta, n_ac, static_cast<uint8_t *>(c.bits.p),
-                                 bytes + 8, flags, &got, st))
-        return guard.done(rc);
-    if (int rc = stage_d2h(st, bits_packed_out, c.bits.p, bytes)) return guard.done(rc);
-    if (int rc = guard.done(SVS_OK)) return rc;
-    if (n_bits_out) *n_bits_out = got;
-    return SVS_OK;
+    if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
+    return extract_staged(
+        gray, span_bytes(planes), bytes, 0, n_bits_out,
+        [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
+            return svs_extract_dev(d_in, planes, delta, n_ac, d_bits, d_bytes, flags, got, st);
+        },
+        [&](HostStage &c, hipStream_t st) { return stage_d2h(st, bits_packed_out, c.bits.p, bytes); });
 }
 
 int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, char *bits_ascii_out,
                     uint64_t out_capacity_chars, uint32_t flags, uint64_t *n_bits_out) {
     svs::Geometry g;
-    uint64_t total = 0;
-    if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
-    if (n_bits_out) *n_bits_out = 0;
-    const uint64_t cap = total * (uint64_t)g.n_ac;
+    uint64_t total = 0, cap = 0;
+    if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_ascii_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
-    if (out_capacity_chars < cap)
-        return fail(SVS_ERR_CAPACITY, "extract needs %llu characters, buffer has %llu", (unsigned long long)cap,
-                    (unsigned long long)out_capacity_chars);
-    const uint64_t bytes = (cap + 7) / 8, span = span_bytes(planes);
-    HostStage *ctx = nullptr;
-    if (int rc = stage_acquire(&ctx)) return rc;
-    HostStage &c = *ctx;
-    StageGuard guard(ctx);
-    if (int rc = stage_reserve(c.frames, span)) return guard.done(rc);
-    if (int rc = stage_reserve(c.bits, bytes + 8)) return guard.done(rc);
-    if (int rc = stage_reserve(c.third, 8 * bytes + 8)) return guard.done(rc);
-    hipStream_t st = c.st[0];
-    if (int rc = stage_h2d(st, c.frames.p, gray, span)) return guard.done(rc);
-    uint64_t got = 0;
-    if (int rc = svs_extract_dev(static_cast<const uint8_t *>(c.frames.p), planes, delta, n_ac, static_cast<uint8_t *>(c.bits.p),
-                                 bytes + 8, flags, &got, st))
-        return guard.done(rc);
-    const uint32_t blocks = (uint32_t)((bytes + 255) / 256 < 4096 ? (bytes + 255) / 256 : 4096);
-    hipLaunchKernelGGL(svs::packed_to_ascii_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint8_t *>(c.bits.p), bytes,
-                       static_cast<svs::u32x2 *>(c.third.p));
-    if (hipGetLastError() != hipSuccess) return guard.done(fail(SVS_ERR_HIP, "packed_to_ascii_kernel launch failed"));
-    if (int rc = stage_d2h(st, bits_ascii_out, c.third.p, cap)) return guard.done(rc);
-    if (int rc = guard.done(SVS_OK)) return rc;
-    if (n_bits_out) *n_bits_out = got;
-    return SVS_OK;
+    if (int rc = check_capacity(cap, out_capacity_chars, "characters")) return rc;
+    const uint64_t bytes = (cap + 7) / 8;
+    return extract_staged(
+        gray, span_bytes(planes), bytes, 8 * bytes + 8, n_bits_out,
+        [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
+            return svs_extract_dev(d_in, planes, delta, n_ac, d_bits, d_bytes, flags, got, st);
+        },
+        [&](HostStage &c, hipStream_t st) {
+            const uint32_t blocks = (uint32_t)((bytes + 255) / 256 < 4096 ? (bytes + 255) / 256 : 4096);
+            hipLaunchKernelGGL(svs::packed_to_ascii_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint8_t *>(c.bits.p),
+                               bytes, static_cast<svs::u32x2 *>(c.third.p));
+            if (hipGetLastError() != hipSuccess) return fail(SVS_ERR_HIP, "packed_to_ascii_kernel launch failed");
+            return stage_d2h(st, bits_ascii_out, c.third.p, cap);
+        });
 }
 
 int svs_shutdown(void) {
@@ -940,7 +866,7 @@ int svs_bgr_to_gray_dev(const uint8_t *d_bgr, int64_t bgr_row_pitch, int64_t bgr
     if (w[3] < 1 || w[3] > 16 || w[0] + w[1] + w[2] != (1u << w[3]))
         return fail(SVS_ERR_INVALID_ARG, "weights must sum to 2^shift with 1 <= shift <= 16");
     svs::ColourParams c{bgr_row_pitch, bgr_frame_pitch, 0, 0, w[0], w[1], w[2], w[3]};
-    g.xcd_chunk = kEighth;
+    g.xcd_chunk = svs::kEighth;
     hipLaunchKernelGGL(svs::bgr_to_gray_kernel, dim3((uint32_t)((total + SVS_WG - 1) / SVS_WG)), dim3(SVS_WG), 0,
                        (hipStream_t)stream, d_bgr, d_gray, g, c);
     SVS_HIP(hipGetLastError());
@@ -956,7 +882,7 @@ int svs_gray_to_bgr_dev(const uint8_t *d_gray, const svs_planes *planes, uint8_t
     if (!d_gray || ((uintptr_t)d_gray % 8)) return fail(SVS_ERR_INVALID_ARG, "gray pointer NULL or unaligned");
     if (int rc = check_bgr(planes, d_bgr, bgr_row_pitch, bgr_frame_pitch)) return rc;
     svs::ColourParams c{0, 0, bgr_row_pitch, bgr_frame_pitch, 0, 0, 0, 0};
-    g.xcd_chunk = kEighth;
+    g.xcd_chunk = svs::kEighth;
     hipLaunchKernelGGL(svs::gray_to_bgr_kernel, dim3((uint32_t)((total + SVS_WG - 1) / SVS_WG)), dim3(SVS_WG), 0,
                        (hipStream_t)stream, d_gray, d_bgr, g, c);
     SVS_HIP(hipGetLastError());
@@ -999,57 +925,14 @@ int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_
                                weights, &c))
         return rc;
     if (!d_bgr_out) return fail(SVS_ERR_INVALID_ARG, "output pointer is NULL");
-    const int n = (int)g.n_ac;
-    const uint64_t cap = total * (uint64_t)n;
-    uint64_t use = n_bits < cap ? n_bits : cap;
-    if (!(delta > 0.0) || n == 0) use = 0;
-    if (use > 0 && (!d_bits_packed || ((uintptr_t)d_bits_packed % 4)))
+    const svs::EmbedPlan p = svs::plan_embed(route_args(delta, g, total, n_bits, bit_offset, flags, true));
+    if (p.use > 0 && (!d_bits_packed || ((uintptr_t)d_bits_packed % 4)))
         return fail(SVS_ERR_INVALID_ARG, "bits pointer NULL or not 4-byte aligned");
-    // kernel family as in svs_embed_dev: the streaming arithmetic (with its in-kernel exact replay) for one and two coefficient
-    // rows inside the guard's delta range, whatever the flags; the exact arithmetic otherwise, and whenever a non-empty
-    // payload cannot be embedded (every block is then round-tripped, which only it reproduces)
-    const int rows_n = rows_for(n);
-    const bool in_range = delta >= SVS_GUARD_DELTA_MIN && delta <= SVS_GUARD_DELTA_MAX;
-    const bool streaming = use > 0 && in_range && !(flags & SVS_EXACT_POCKETFFT) && rows_n <= 2;
-    const bool exact = !streaming && (use > 0 || n_bits > 0);
-    svs::QimParams qp;
-    const int qm = make_qim(use == 0 ? 1.0 : delta, &qp);
-    if (streaming) {
-        svs::make_guard(delta, rows_n, &qp);
-        scale_guard(qp);   // experiments library only
-    }
-    g.xcd_chunk = kEighth;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t *bw = reinterpret_cast<const uint32_t *>(d_bits_packed);
-    uint64_t kernel_bits = use;
-    uint32_t words = 0;
-    if (use == 0) {
-        // nothing to embed.  With a non-empty payload every block is still round-tripped (n_ac = 0 in the exact kernel);
-        // otherwise the frames are just converted BGR -> gray -> BGR
-        if (exact) { g.n_ac = 0; kernel_bits = 1; } else { g.n_ac = 1; kernel_bits = 0; }
-        bw = nullptr;
-    } else {
-        const uint64_t w64 = ((bit_offset + use + 7) / 8 + 3) / 4;
-        if (w64 >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
-        words = (uint32_t)w64;
-    }
-    const int rows = rows_for((int)g.n_ac);
-    int rc;
-    const bool keep = (flags & SVS_KEEP_COLOUR) != 0;
-#define SVS_GO2(QM, EX)                                                                                                  \
-    rc = keep ? launch_embed_bgr<QM, EX, true>(rows, total, st, d_bgr_in, d_bgr_out, d_gray_ref, g, c, qp, bw, bit_offset, \
-                                               kernel_bits, words)                                                        \
-              : launch_embed_bgr<QM, EX, false>(rows, total, st, d_bgr_in, d_bgr_out, d_gray_ref, g, c, qp, bw,            \
-                                                bit_offset, kernel_bits, words);
-#define SVS_GO(QM)                                                                                                       \
-    if (exact) { SVS_GO2(QM, true) } else { SVS_GO2(QM, false) }
-    if (qm == svs::QM_DOUBLE) { SVS_GO(svs::QM_DOUBLE) }
-    else if (qm == svs::QM_POW2) { SVS_GO(svs::QM_POW2) }
-    else { SVS_GO(svs::QM_F32) }
-#undef SVS_GO
-#undef SVS_GO2
-    if (rc) return rc;
-    if (n_embedded) *n_embedded = use;
+    if (p.n_words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
+    if (int rc = launch_embed_bgr(p, (flags & SVS_KEEP_COLOUR) != 0, total, (hipStream_t)stream, d_bgr_in, d_bgr_out, d_gray_ref, g,
+                                  c, p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr))
+        return rc;
+    if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
 }
 
@@ -1057,49 +940,16 @@ int svs_extract_bgr_dev(const uint8_t *d_bgr, int64_t bgr_row_pitch, int64_t bgr
                         const uint32_t *weights, double delta, int n_ac, uint8_t *d_bits_packed_out,
                         uint64_t out_capacity_bytes, uint64_t *n_bits_out, void *stream) {
     svs::Geometry g;
-    uint64_t total = 0;
-    if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
-    if (n_bits_out) *n_bits_out = 0;
-    const int n = (int)g.n_ac;
-    const uint64_t cap = total * (uint64_t)n;
+    uint64_t total = 0, cap = 0;
+    if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (cap == 0) return SVS_OK;
     svs::ColourParams c;
     if (int rc = colour_params(planes, d_bgr, bgr_row_pitch, bgr_frame_pitch, nullptr, 0, 0, weights, &c)) return rc;
     if (!d_bits_packed_out || ((uintptr_t)d_bits_packed_out % 4)) return fail(SVS_ERR_INVALID_ARG, "bits pointer NULL or unaligned");
     const uint64_t bytes = (cap + 7) / 8;
-    if (out_capacity_bytes < bytes)
-        return fail(SVS_ERR_CAPACITY, "extract needs %llu bytes, buffer has %llu", (unsigned long long)bytes,
-                    (unsigned long long)out_capacity_bytes);
-    const hipStream_t st = (hipStream_t)stream;
-    if (!(delta > 0.0)) {
-        SVS_HIP(hipMemsetAsync(d_bits_packed_out, 0, bytes, st));
-    } else {
-        svs::QimParams qp;
-        const int qm = make_qim(delta, &qp);
-        scale_tie(qp);   // experiments library only
-        g.xcd_chunk = rows_for(n) == 1 ? 32u : kEighth;
-        const dim3 grid((uint32_t)((total + SVS_WG - 1) / SVS_WG));
-        const int rows = rows_for(n);
-        // tiny steps: the rounding constant of the two-step extraction needs |c / delta| < 2^22 (as in svs_extract_dev)
-        const bool fastx = (double)qp.delta_f >= SVS_FAST_EXTRACT_DELTA_MIN;
-#define SVS_LAUNCH(R, QMV, FX)                                                                                               \
-    hipLaunchKernelGGL((svs::extract_bgr_kernel<R, QMV, FX>), grid, dim3(SVS_WG), 0, st, d_bgr, g, c, qp, d_bits_packed_out, bytes)
-#define SVS_CASE(R)                                                                                                      \
-    case R:                                                                                                              \
-        if (R >= 2 && fastx) {                                                                                           \
-            if (qm == svs::QM_POW2) SVS_LAUNCH(R, svs::QM_POW2, (R >= 2)); else SVS_LAUNCH(R, svs::QM_F32, (R >= 2));    \
-        } else {                                                                                                         \
-            if (qm == svs::QM_POW2) SVS_LAUNCH(R, svs::QM_POW2, false); else SVS_LAUNCH(R, svs::QM_F32, false);          \
-        }                                                                                                                \
-        break;
-        switch (rows) {
-            SVS_CASE(1) SVS_CASE(2) SVS_CASE(3) SVS_CASE(4) SVS_CASE(5) SVS_CASE(6) SVS_CASE(7) SVS_CASE(8)
-            default: return fail(SVS_ERR_INVALID_ARG, "internal: rows=%d", rows);
-        }
-#undef SVS_CASE
-#undef SVS_LAUNCH
-        SVS_HIP(hipGetLastError());
-    }
+    if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
+    const svs::ExtractPlan p = svs::plan_extract(route_args(delta, g, total, 0, 0, 0, true));
+    if (int rc = launch_extract_bgr(p, total, (hipStream_t)stream, d_bgr, g, c, d_bits_packed_out, bytes)) return rc;
     if (n_bits_out) *n_bits_out = cap;
     return SVS_OK;
 }
@@ -1122,52 +972,34 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
     if (!bgr || !bgr_out) return fail(SVS_ERR_INVALID_ARG, "BGR pointer is NULL");
     if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR))
         return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    const int32_t H = planes->height, W = planes->width;
-    const uint64_t px = (uint64_t)planes->n_frames * H * W;
+    const uint64_t px = (uint64_t)planes->n_frames * planes->height * planes->width;
     const uint64_t cap = total * (uint64_t)g.n_ac;
     uint64_t use = n_bits < cap ? n_bits : cap;
     if (!(delta > 0.0)) use = 0;
     if (use && !bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
     if (use && bit_offset + use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
-    HostStage *ctx = nullptr;
-    if (int rc = stage_acquire(&ctx)) return rc;
-    HostStage &c = *ctx;
-    StageGuard guard(ctx);
-    if (int rc = stage_reserve(c.frames, 3 * px)) return guard.done(rc);
-    if (int rc = stage_reserve(c.second, 3 * px)) return guard.done(rc);
-    if (gray_ref_out)
-        if (int rc = stage_reserve(c.third, px)) return guard.done(rc);
-    uint64_t rebased = 0;
-    if (int rc = stage_payload(c, bits_packed, bit_offset, use, &rebased)) return guard.done(rc);
-    const uint64_t pass_bits = use ? use : (n_bits ? 1 : 0);   // see svs_embed
-    const uint64_t wb = (uint64_t)W / 8, bpf = wb * ((uint64_t)H / 8);
-    const int64_t rp3 = 3 * (int64_t)W;
-    uint8_t *d_in = static_cast<uint8_t *>(c.frames.p), *d_out = static_cast<uint8_t *>(c.second.p),
-            *d_ref = gray_ref_out ? static_cast<uint8_t *>(c.third.p) : nullptr;
+    const HostPayload payload{bits_packed, nullptr, bit_offset, use};
     uint64_t done_total = 0;
-    int rc = SVS_OK;
-    uint32_t n_chunks = 0;
-    for_each_chunk(planes->n_frames, H, (size_t)rp3, stage_chunk_bytes(3 * px), [&](const Chunk &) { ++n_chunks; });
-    const bool serial = n_chunks <= 1;
-    hipStream_t up = c.st[0], st = serial ? c.st[0] : c.st[1];
-    for_each_chunk(planes->n_frames, H, (size_t)rp3, stage_chunk_bytes(3 * px), [&](const Chunk &ch) {   // frames are tightly packed: every chunk is one run of bytes
-        if (rc) return;
-        const uint64_t first_px = ((uint64_t)ch.f0 * H + ch.r0) * W, n_px = (uint64_t)ch.nf * ch.rows * W;
-        if ((rc = stage_h2d(up, d_in + 3 * first_px, bgr + 3 * first_px, 3 * n_px))) return;
-        const svs_planes sub{ch.nf, ch.rows, W, 0, W, (int64_t)ch.rows * W};
-        const uint64_t g0 = (uint64_t)ch.f0 * bpf + (uint64_t)(ch.r0 / 8) * wb;
-        uint64_t done = 0;
-        if ((rc = svs_embed_bgr_dev(d_in + 3 * first_px, rp3, rp3 * ch.rows, d_out + 3 * first_px, rp3, rp3 * ch.rows,
-                                    d_ref ? d_ref + first_px : nullptr, &sub, weights, delta, n_ac, static_cast<const uint8_t *>(c.bits.p),
-                                    rebased + (use ? g0 * (uint64_t)g.n_ac : 0), chunk_budget(pass_bits, use, g0, g.n_ac), flags, &done, up)))
-            return;
-        done_total += done;
-        if (!serial && (rc = stage_handoff(c))) return;
-        if ((rc = stage_d2h(st, bgr_out + 3 * first_px, d_out + 3 * first_px, 3 * n_px))) return;
-        if (d_ref) rc = stage_d2h(st, gray_ref_out + first_px, d_ref + first_px, n_px);
-    });
-    rc = guard.done(rc);
-    if (rc) return rc;
+    if (int rc = staged(3 * px, 3 * px, gray_ref_out ? px : 0, payload.bits_bytes(), [&](HostStage &c) {
+            uint64_t rebased = 0;
+            if (int rc = payload.stage(c, &rebased)) return rc;
+            uint8_t *d_in = static_cast<uint8_t *>(c.frames.p), *d_out = static_cast<uint8_t *>(c.second.p),
+                    *d_ref = gray_ref_out ? static_cast<uint8_t *>(c.third.p) : nullptr;
+            return embed_chunks(
+                c, planes, 3, bgr, g.n_ac, use, n_bits, rebased,
+                [&](const svs_planes &sub, int64_t off, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
+                    const int64_t rp = 3 * sub.row_pitch, fp = 3 * sub.frame_pitch;
+                    return svs_embed_bgr_dev(d_in + off, rp, fp, d_out + off, rp, fp, d_ref ? d_ref + off / 3 : nullptr, &sub, weights,
+                                             delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset, budget, flags, done, up);
+                },
+                [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {   // tightly packed frames: every chunk is one run of bytes
+                    const uint64_t n_px = (uint64_t)ch.nf * ch.rows * planes->width;
+                    if (int rc = stage_d2h(st, bgr_out + off, d_out + off, 3 * n_px)) return rc;
+                    return d_ref ? stage_d2h(st, gray_ref_out + off / 3, d_ref + off / 3, n_px) : (int)SVS_OK;
+                },
+                &done_total);
+        }))
+        return rc;
     if (n_embedded) *n_embedded = done_total;
     return SVS_OK;
 }
@@ -1175,35 +1007,21 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
 int svs_extract_bgr(const uint8_t *bgr, const svs_planes *planes, const uint32_t *weights, double delta, int n_ac,
                     uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint64_t *n_bits_out) {
     svs::Geometry g;
-    uint64_t total = 0;
-    if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
-    if (n_bits_out) *n_bits_out = 0;
-    const uint64_t cap = total * (uint64_t)g.n_ac;
+    uint64_t total = 0, cap = 0;
+    if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (cap == 0) return SVS_OK;
     if (int rc = packed_planes_only(planes)) return rc;
     if (!bgr || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "BGR/bits pointer is NULL");
     const uint64_t bytes = (cap + 7) / 8;
-    if (out_capacity_bytes < bytes)
-        return fail(SVS_ERR_CAPACITY, "extract needs %llu bytes, buffer has %llu", (unsigned long long)bytes,
-                    (unsigned long long)out_capacity_bytes);
+    if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
     const uint64_t px = (uint64_t)planes->n_frames * planes->height * planes->width;
-    HostStage *ctx = nullptr;
-    if (int rc = stage_acquire(&ctx)) return rc;
-    HostStage &c = *ctx;
-    StageGuard guard(ctx);
-    if (int rc = stage_reserve(c.frames, 3 * px)) return guard.done(rc);
-    if (int rc = stage_reserve(c.bits, bytes + 8)) return guard.done(rc);
-    hipStream_t st = c.st[0];
-    if (int rc = stage_h2d(st, c.frames.p, bgr, 3 * px)) return guard.done(rc);
     const int64_t rp = 3 * (int64_t)planes->width, fp = rp * planes->height;
-    uint64_t got = 0;
-    if (int rc = svs_extract_bgr_dev(static_cast<const uint8_t *>(c.frames.p), rp, fp, planes, weights, delta, n_ac,
-                                     static_cast<uint8_t *>(c.bits.p), bytes + 8, &got, st))
-        return guard.done(rc);
-    if (int rc = stage_d2h(st, bits_packed_out, c.bits.p, bytes)) return guard.done(rc);
-    if (int rc = guard.done(SVS_OK)) return rc;
-    if (n_bits_out) *n_bits_out = got;
-    return SVS_OK;
+    return extract_staged(
+        bgr, 3 * px, bytes, 0, n_bits_out,
+        [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
+            return svs_extract_bgr_dev(d_in, rp, fp, planes, weights, delta, n_ac, d_bits, d_bytes, got, st);
+        },
+        [&](HostStage &c, hipStream_t st) { return stage_d2h(st, bits_packed_out, c.bits.p, bytes); });
 }
 
 int svs_fill_synthetic_dev(uint8_t *d_frames, const svs_planes *planes, uint32_t seed, uint32_t first_frame,

@@ -766,13 +766,19 @@ __device__ __forceinline__ uint32_t row1_process(typename RowVec<BPL>::type (&v)
     return redone;
 }
 
+// static LDS of embed_row1_kernel: each wave's worklist and transposition tile.  The host sizes the kernel's occupancy cap on
+// it (svs_capi.hip, lds_pad_for).
+typedef GuardEntry Row1Entries[SVS_WG / 64][SVS_GUARD_CAP];
+typedef float Row1Tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
+constexpr uint32_t kRow1StaticLds = sizeof(Row1Entries) + sizeof(Row1Tiles);
+
 template <int QM, int BPL>
 __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray, uint8_t *stego, const Geometry g,
                                                           const QimParams qp, const uint32_t *__restrict__ bits,
                                                           const uint64_t bit_offset, const uint64_t n_bits,
                                                           const uint32_t n_words SVS_REPLAY_COUNTER_PARAM) {
-    __shared__ GuardEntry entries[SVS_WG / 64][SVS_GUARD_CAP];
-    __shared__ float tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
+    __shared__ Row1Entries entries;
+    __shared__ Row1Tiles tiles;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     bool live;
     const uint32_t gb = shadow_block<BPL>((tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x) * BPL, g, live);

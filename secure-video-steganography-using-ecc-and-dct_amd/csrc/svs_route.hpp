@@ -1,0 +1,131 @@
+// svs_route.hpp - which kernel family an embed or extract call of the C ABI runs, and with which quantiser, coefficient rows,
+// tile map and payload arguments (csrc/svs_capi.hip launches the plan).  Plain C++ (no HIP): tests/hostemu compiles it, so
+// the CPU tier runs the library's routing and checks it (tests/test_route_cpu.py).
+#pragma once
+#include <stdint.h>
+
+#include "svs_block.hpp"
+
+namespace svs {
+
+constexpr uint32_t kEighth = 0xFFFFFFFFu;   // tile_id() chunk: one contiguous eighth of the grid per XCD-group
+
+// The arguments that decide a call's route.  pocketfft / guarded are the SVS_EXACT_POCKETFFT / SVS_EXACT_GUARDED bits of the
+// call's flags; guarded_off, guard_scale and tie_scale are test hooks (the experiments library's SVS_GUARDED_OFF,
+// SVS_GUARD_SCALE and SVS_TIE_SCALE; the product passes false, 1, 1).
+struct RouteArgs {
+    double delta;
+    uint32_t n_ac;            // clamped to 0..63
+    uint64_t total_blocks;
+    uint64_t n_bits;          // payload bits the caller offers (embed)
+    uint64_t bit_offset;      // (embed)
+    bool pocketfft, guarded;
+    bool bgr;                 // the fused colour calls (svs_embed_bgr_dev / svs_extract_bgr_dev)
+    bool guarded_off;         // reaches the gray calls only
+    float guard_scale, tie_scale;
+};
+
+// COPY: nothing to embed and an empty payload - the reference's loops break before the first block.  Gray: a byte copy through
+// embed_row1_kernel<QM_F32> (none when the call is in place); BGR: the BGR -> gray -> BGR conversion of embed_bgr_kernel<1>.
+// ROUND_TRIP: a non-empty payload of which nothing can be embedded (delta <= 0, no coefficients): the reference still enters
+// and round-trips every block (config_and_setup.py:143-145,166-169), which only the exact arithmetic reproduces - the exact
+// kernel with n_ac = 0 and one pass bit.
+// EXACT: the lane-per-block pocketfft arithmetic.  STREAMING: the cheap arithmetic with its rigorous guard and in-kernel exact
+// replay of the blocks it cannot decide.  Every path produces the reference's stego pixels.
+enum class EmbedPath { COPY, ROUND_TRIP, EXACT, STREAMING };
+
+struct EmbedPlan {
+    EmbedPath path;
+    int qm;                   // QuantMode of the instantiation
+    int rows;                 // coefficient rows of the instantiation (EXACT / ROUND_TRIP: the U of the exact kernel)
+    bool two_blocks;          // embed_row1_kernel may take two blocks per lane where the buffers allow it
+    uint32_t n_ac;            // Geometry::n_ac of the launch
+    uint32_t xcd_chunk;
+    QimParams qp;
+    uint64_t use;             // payload bits embedded (*n_embedded)
+    uint64_t bit_offset, n_bits, n_words;   // the kernel's payload arguments; n_words >= 2^32: too large for one call
+};
+
+// Which kernel family (include/svsdct.h `flags`).  The streaming kernels cover one and two coefficient rows (n <= 15) inside the
+// guard's delta range and serve flags 0 and SVS_EXACT_GUARDED alike; everything else - n >= 16, delta outside the range,
+// SVS_EXACT_POCKETFFT - runs the lane-per-block pocketfft kernel.
+inline EmbedPlan plan_embed(const RouteArgs &a) {
+    EmbedPlan p{};
+    const uint32_t n = a.n_ac;
+    const uint64_t cap = a.total_blocks * n;
+    p.use = a.n_bits < cap ? a.n_bits : cap;
+    if (!(a.delta > 0.0) || n == 0) p.use = 0;   // nothing can be embedded (config_and_setup.py:143-145)
+    const int rows = rows_for((int)n);
+    const bool in_range = a.delta >= SVS_GUARD_DELTA_MIN && a.delta <= SVS_GUARD_DELTA_MAX;
+    const bool streaming = p.use > 0 && in_range && !a.pocketfft && rows <= 2 && !(a.guarded_off && !a.bgr);
+    p.xcd_chunk = kEighth;
+    const int qm = make_qim(p.use == 0 ? 1.0 : a.delta, &p.qp);
+    if (p.use > 0) {
+        p.path = streaming ? EmbedPath::STREAMING : EmbedPath::EXACT;
+        p.qm = qm;
+        p.n_ac = n;
+        p.bit_offset = a.bit_offset;
+        p.n_bits = p.use;
+        p.n_words = ((a.bit_offset + p.use + 7) / 8 + 3) / 4;
+        // the BGR exact kernel covers all eight rows; the gray one has instantiations for one, two and eight
+        p.rows = streaming || (!a.bgr && rows <= 2) ? rows : 8;
+        p.two_blocks = streaming && !a.bgr && rows == 1;
+        if (streaming) {
+            make_guard(a.delta, rows, &p.qp);
+            p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;
+        }
+        return p;
+    }
+    // nothing to embed: the gray calls take the F32 instantiations, the BGR calls those of make_qim(1.0); only the BGR calls
+    // pass their bit_offset on
+    p.path = a.n_bits == 0 ? EmbedPath::COPY : EmbedPath::ROUND_TRIP;
+    p.qm = a.bgr ? qm : QM_F32;
+    p.n_ac = p.path == EmbedPath::COPY ? 1 : 0;
+    p.rows = p.path == EmbedPath::COPY ? 1 : 8;
+    p.two_blocks = p.path == EmbedPath::COPY && !a.bgr && rows == 1;
+    p.bit_offset = a.bgr ? a.bit_offset : 0;
+    p.n_bits = p.path == EmbedPath::COPY ? 0 : 1;
+    return p;
+}
+
+// ZEROS: delta <= 0 - every bit '0' (config_and_setup.py:143-145).  EXACT: the pocketfft-identical forward transform.  FAST:
+// the FMA-factored forward whose bits are the reference's for any input by construction (a block with a quantiser input within
+// the proven error bound of a rounding tie is recomputed with the pocketfft-identical one).
+enum class ExtractPath { ZEROS, EXACT, FAST };
+
+struct ExtractPlan {
+    ExtractPath path;
+    int qm;                   // QM_F32 or QM_POW2: the double mode only differs in requantisation, not needed here
+    int rows;
+    uint32_t xcd_chunk;
+    QimParams qp;
+};
+
+// Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
+// (+3 %); two rows of the gray kernel (n = 8..15) - the identity map (+6.7 % at 600 x 4K, +4.4 % at 2 400 x 1080p over the
+// contiguous eighth); more rows - VALU-bound, the map does not matter.
+inline ExtractPlan plan_extract(const RouteArgs &a) {
+    ExtractPlan p{};
+    if (!(a.delta > 0.0)) {
+        p.path = ExtractPath::ZEROS;
+        return p;
+    }
+    p.rows = rows_for((int)a.n_ac);
+    p.xcd_chunk = p.rows == 1 ? 32u : (p.rows == 2 && !a.bgr ? 0u : kEighth);
+    p.qm = make_qim(a.delta, &p.qp) == QM_POW2 ? QM_POW2 : QM_F32;
+    const float t = a.tie_scale;
+    p.qp.tie_slope *= t; p.qp.tie2_sum *= t; p.qp.tie2_resid *= t; p.qp.tie2_c00 *= t; p.qp.tie2_max *= t;
+    // GUARDED = FAST inside the guard's delta range (n >= 8: 0.86 instead of 1.03 ms per 600 x 4K at n = 10), the
+    // pocketfft-identical kernels outside it, as for embedding.  The BGR call has no flags.
+    bool exact = a.pocketfft;
+    if (a.guarded) exact = !(a.delta >= SVS_GUARD_DELTA_MIN && a.delta <= SVS_GUARD_DELTA_MAX && !a.guarded_off);
+    if (a.bgr) exact = false;
+    // the FAST kernels with two and more rows round c / delta by adding 1.5 * 2^23, which needs |c / delta| < 2^22.  With one
+    // row the pocketfft-identical forward costs 0.2-3 % (the kernel stays HBM-bound; profiles/history/r01_ab_quant_exact.txt),
+    // so FAST mode uses it too; with more rows it costs ~17 % and stays opt-in.
+    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1) exact = true;
+    p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
+    return p;
+}
+
+}  // namespace svs

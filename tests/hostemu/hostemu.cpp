@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "svs_block.hpp"
+#include "svs_route.hpp"
 #include "svs_stage.hpp"
 
 namespace {
@@ -42,18 +43,13 @@ void embed_exact_pair_dispatch(Blk &a, Blk &b, uint32_t n, uint32_t nb_a, uint32
 
 bool g_constant_shortcut = false;   // exact == 3: constant blocks take forward_exact_paired_constant, as the replay kernel does
 
-// emu_set_guard_scale / emu_set_tie_scale: the experiments library's SVS_GUARD_SCALE / SVS_TIE_SCALE (csrc/svs_capi.hip
-// scale_guard / scale_tie), the same float multiplications of the QimParams fields
+// emu_set_guard_scale / emu_set_tie_scale: the experiments library's SVS_GUARD_SCALE / SVS_TIE_SCALE, applied by the routing
 float g_guard_scale = 1.0f, g_tie_scale = 1.0f;
 
-void scale_guard(svs::QimParams &qp) {
-    const float f = g_guard_scale;
-    qp.g_sum *= f; qp.g_resid *= f; qp.g_delta *= f;
-}
+// the library's routing (csrc/svs_route.hpp) of a gray call
 
-void scale_tie(svs::QimParams &qp) {
-    const float f = g_tie_scale;
-    qp.tie_slope *= f; qp.tie2_sum *= f; qp.tie2_resid *= f; qp.tie2_c00 *= f; qp.tie2_max *= f;
+svs::RouteArgs route(double delta, uint32_t n, uint64_t total, uint64_t n_bits, uint64_t bit_offset, bool pocketfft, bool guarded) {
+    return svs::RouteArgs{delta, n, total, n_bits, bit_offset, pocketfft, guarded, false, false, g_guard_scale, g_tie_scale};
 }
 
 uint8_t *g_replay_map = nullptr;   // emu_set_replay_map: one byte per block of the next emu_embed calls, 1 = handed to the replay
@@ -172,28 +168,22 @@ uint64_t emu_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, dou
                    const uint8_t *bits, uint64_t bits_bytes, uint64_t bit_offset, uint64_t n_bits, int exact,
                    uint64_t *n_replayed) {
     if (n_replayed) *n_replayed = 0;
+    // exact: 0 = flags 0, 1 = SVS_EXACT_POCKETFFT, 4 = SVS_EXACT_GUARDED, routed as svs_embed_dev routes them.  The test-only
+    // modes route as 1 (2: even/odd block pairs through the packed pair form; 3: the constant shortcut) and as 4 (5: the
+    // two-row guard through its generic instantiation).  Every mode gives the reference's pixels.
     g_constant_shortcut = exact == 3;
     g_generic_guarded2 = exact == 5;
-    if (exact == 5) exact = 4;
     const int n = n_ac < 0 ? 0 : (n_ac > 63 ? 63 : n_ac);
     const uint64_t bpf = (uint64_t)(H / 8) * (W / 8), total = bpf * F;
     std::memcpy(stego, gray, (size_t)F * H * W);
-    uint64_t use = n_bits < total * n ? n_bits : total * n;
-    if (!(delta > 0.0) || n == 0) use = 0;
-    svs::QimParams qp;
-    const int dbl = make_qim(use ? delta : 1.0, &qp);
-    // exact == 0 (flags 0) and exact == 4 (SVS_EXACT_GUARDED): the cheap path wherever its rigorous error bound decides every
-    // pixel, the exact arithmetic elsewhere (same routing as svs_embed_dev: one or two coefficient rows, delta inside the
-    // guard's range; anything else is plain EXACT).  Every mode gives the reference's pixels.
-    const bool in_range = delta >= SVS_GUARD_DELTA_MIN && delta <= SVS_GUARD_DELTA_MAX;
-    const bool guarded = use > 0 && in_range && (exact == 4 || exact == 0) && svs::rows_for(n) <= 2;
-    if (guarded) {
-        svs::make_guard(delta, svs::rows_for(n), &qp);
-        scale_guard(qp);
-    }
-    if ((exact == 4 || exact == 0) && !guarded) exact = 1;
+    const svs::EmbedPlan plan = svs::plan_embed(route(delta, (uint32_t)n, total, n_bits, bit_offset, exact >= 1 && exact <= 3,
+                                                      exact == 4 || exact == 5));
+    const uint64_t use = plan.use;
+    const svs::QimParams &qp = plan.qp;
+    const int dbl = plan.qm;
+    const bool guarded = plan.path == svs::EmbedPath::STREAMING;
     if (use == 0) {
-        if (n_bits > 0) {  // nothing consumed -> every block entered and round-tripped (either mode: svs_embed_dev)
+        if (plan.path == svs::EmbedPath::ROUND_TRIP) {  // nothing consumed -> every block entered and round-tripped
             for (uint64_t gb = 0; gb < total; ++gb) {
                 const uint64_t f = gb / bpf, b = gb % bpf;
                 uint8_t *p = stego + f * (uint64_t)H * W + (b / (W / 8)) * 8 * W + (b % (W / 8)) * 8;
@@ -252,14 +242,15 @@ uint64_t emu_extract(const uint8_t *gray, int F, int H, int W, double delta, int
     const int n = n_ac < 0 ? 0 : (n_ac > 63 ? 63 : n_ac);
     const uint64_t bpf = (uint64_t)(H / 8) * (W / 8), total = bpf * F;
     if (n == 0) return 0;
-    if (!(delta > 0.0)) {
+    // exact != 0: SVS_EXACT_POCKETFFT, routed as svs_extract_dev routes it
+    const svs::ExtractPlan plan = svs::plan_extract(route(delta, (uint32_t)n, total, 0, 0, exact != 0, false));
+    if (plan.path == svs::ExtractPath::ZEROS) {
         std::memset(out_flags, 0, total * n);
         return total * n;
     }
-    svs::QimParams qp;
-    const int qm = make_qim(delta, &qp);
-    scale_tie(qp);
-    if (g_extract_wave > 0 && !exact && svs::rows_for(n) >= 2 && (double)qp.delta_f >= SVS_FAST_EXTRACT_DELTA_MIN) {
+    const svs::QimParams &qp = plan.qp;
+    const int qm = plan.qm, rows = plan.rows;
+    if (g_extract_wave > 0 && plan.path == svs::ExtractPath::FAST) {
         const uint64_t wv = (uint64_t)(g_extract_wave > 128 ? 128 : g_extract_wave);
         Blk raws[128];
         uint32_t his[128], los[128];
@@ -270,8 +261,8 @@ uint64_t emu_extract(const uint8_t *gray, int F, int H, int W, double delta, int
                 raws[i].load(gray + f * (uint64_t)H * W + (b / (W / 8)) * 8 * W + (b % (W / 8)) * 8, (size_t)W);
             }
             bool cand[128];
-            if (qm == svs::QM_POW2) extract_fast_wave<svs::QM_POW2>(svs::rows_for(n), raws, count, (uint32_t)n, qp, his, los, cand, n_redone);
-            else extract_fast_wave<svs::QM_F32>(svs::rows_for(n), raws, count, (uint32_t)n, qp, his, los, cand, n_redone);
+            if (qm == svs::QM_POW2) extract_fast_wave<svs::QM_POW2>(rows, raws, count, (uint32_t)n, qp, his, los, cand, n_redone);
+            else extract_fast_wave<svs::QM_F32>(rows, raws, count, (uint32_t)n, qp, his, los, cand, n_redone);
             if (g_candidate_map)
                 for (uint64_t i = 0; i < count; ++i) g_candidate_map[g0 + i] = cand[i];
             for (uint64_t i = 0; i < count; ++i)
@@ -286,12 +277,11 @@ uint64_t emu_extract(const uint8_t *gray, int F, int H, int W, double delta, int
         Blk raw;
         raw.load(p, (size_t)W);
         uint32_t hi, lo;
-        if (exact || svs::rows_for(n) == 1 || (double)qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN) {   // as svs_extract_dev routes: one row
-            // and tiny steps use the pocketfft-identical forward in both modes
+        if (plan.path == svs::ExtractPath::EXACT) {
             if (qm == svs::QM_POW2) svs::extract_block_exact<8, svs::QM_POW2>(raw.x, raw.y, (uint32_t)n, qp, hi, lo);
             else svs::extract_block_exact<8, svs::QM_F32>(raw.x, raw.y, (uint32_t)n, qp, hi, lo);
-        } else if (qm == svs::QM_POW2) extract_fast<svs::QM_POW2>(svs::rows_for(n), raw, (uint32_t)n, qp, hi, lo, n_redone);
-        else extract_fast<svs::QM_F32>(svs::rows_for(n), raw, (uint32_t)n, qp, hi, lo, n_redone);
+        } else if (qm == svs::QM_POW2) extract_fast<svs::QM_POW2>(rows, raw, (uint32_t)n, qp, hi, lo, n_redone);
+        else extract_fast<svs::QM_F32>(rows, raw, (uint32_t)n, qp, hi, lo, n_redone);
         for (int i = 0; i < n; ++i) out_flags[gb * n + i] = (uint8_t)svs::window_bit(hi, lo, i);
     }
     return total * n;
@@ -376,6 +366,26 @@ uint64_t emu_plan_chunks(int32_t n_frames, int32_t H, uint64_t row_bytes, uint64
                             ++k;
                         });
     return k;
+}
+
+// the routing of the C ABI (csrc/svs_route.hpp) for tests/test_route_cpu.py.  embed: out = {path, rows, qm, xcd_chunk, n_ac,
+// two_blocks, use, bit_offset, n_bits, n_words}; extract: out = {path, rows, qm, xcd_chunk}.  n_ac is clamped as the library does.
+void emu_plan_embed(double delta, int n_ac, uint64_t total, uint64_t n_bits, uint64_t bit_offset, int pocketfft, int guarded, int bgr,
+                    int guarded_off, int64_t *out) {
+    const uint32_t n = n_ac < 0 ? 0 : (n_ac > 63 ? 63 : n_ac);
+    const svs::EmbedPlan p = svs::plan_embed(svs::RouteArgs{delta, n, total, n_bits, bit_offset, pocketfft != 0, guarded != 0, bgr != 0,
+                                                            guarded_off != 0, 1.0f, 1.0f});
+    const int64_t v[10] = {(int64_t)p.path, p.rows, p.qm, p.xcd_chunk, p.n_ac, p.two_blocks, (int64_t)p.use, (int64_t)p.bit_offset,
+                           (int64_t)p.n_bits, (int64_t)p.n_words};
+    std::memcpy(out, v, sizeof v);
+}
+
+void emu_plan_extract(double delta, int n_ac, uint64_t total, int pocketfft, int guarded, int bgr, int guarded_off, int64_t *out) {
+    const uint32_t n = n_ac < 0 ? 0 : (n_ac > 63 ? 63 : n_ac);
+    const svs::ExtractPlan p = svs::plan_extract(svs::RouteArgs{delta, n, total, 0, 0, pocketfft != 0, guarded != 0, bgr != 0,
+                                                                guarded_off != 0, 1.0f, 1.0f});
+    const int64_t v[4] = {(int64_t)p.path, p.rows, p.qm, p.xcd_chunk};
+    std::memcpy(out, v, sizeof v);
 }
 
 uint64_t emu_chunk_budget(uint64_t pass_bits, uint64_t use, uint64_t g0, uint32_t n) { return svs::chunk_budget(pass_bits, use, g0, n); }

@@ -210,7 +210,8 @@ def hostemu():
         return _EMU
     src = os.path.join(REPO, "tests", "hostemu", "hostemu.cpp")
     out = os.path.join(REPO, "tests", "hostemu", "libsvs_hostemu.so")
-    deps = [src, os.path.join(CSRC, "svs_block.hpp"), os.path.join(CSRC, "svs_stage.hpp")]
+    deps = [src, os.path.join(CSRC, "svs_block.hpp"), os.path.join(CSRC, "svs_stage.hpp"),
+            os.path.join(CSRC, "svs_route.hpp")]
     stale = not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
     if stale and os.path.exists(out) and os.path.exists("/dev/kfd"):
         stale = False      # on a GPU box use the library built by build(): no compiler child processes there
