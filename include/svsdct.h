@@ -205,6 +205,48 @@ int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta,
                     char *bits_ascii_out, uint64_t out_capacity_chars, uint32_t flags,
                     uint64_t *n_bits_out);
 
+/* ---- the operator with a keyed block order -------------------------------------------------------------
+ * Opt-in.  Without an order, the payload fills the blocks of each frame in raster order from the top-left block, as in the
+ * reference: a payload that fills part of a frame's capacity sits in its top rows, where a frame difference shows it.  With
+ * an order, stream slot j of frame f of the call - stream bits bit_offset + (f*N + j)*n_ac ... + n_ac - 1, N = (H/8)*(W/8) -
+ * goes to block sigma_t(j) of that frame, t = first_frame + f: a key-seeded permutation of the frame's blocks
+ * (csrc/svs_order.hpp; svsdct/order.py restates it).  Frames keep the stream ranges they have without an order; only the
+ * blocks inside a frame are reordered.  Every block is still embedded or extracted exactly as the reference does it, so
+ *     ordered embed(F)   = P^-1(reference embed(P(F)))     ordered extract(S) = reference extract(P(S))
+ * where P moves block sigma_t(j) of frame t to raster position j - stego pixels included, in every mode.
+ * The permutation is NOT cryptographic: it hides where the payload sits from a look at the frame; confidentiality comes
+ * from encrypting the payload.  Sender and receiver must use the same key and the same clip frame index for every frame.
+ *   order : NULL = the call without an order (the same kernels, the same bytes).  Otherwise key (every value valid, 0
+ *           included), first_frame (the clip index of the call's first frame), reserved (must be 0, else
+ *           SVS_ERR_INVALID_ARG).
+ * Every other argument, flag and contract is that of svs_embed_dev / svs_embed / svs_extract_dev / svs_extract.  A keyed
+ * extract clears its output range on the call's stream and ORs each block's bits into it with 32-bit atomics; it writes no
+ * byte that the call without an order does not write.  The fused colour calls and the _str calls have no ordered form. */
+typedef struct svs_block_order {
+    uint64_t key;
+    uint32_t first_frame;   /* clip index of the call's first frame: frame f uses t = first_frame + f */
+    uint32_t reserved;      /* must be 0 */
+} svs_block_order;
+
+int svs_embed_ordered_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
+                          const svs_block_order *order, double delta, int n_ac,
+                          const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                          uint32_t flags, uint64_t *n_embedded, void *stream);
+
+int svs_extract_ordered_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order,
+                            double delta, int n_ac, uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes,
+                            uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+/* Host-pointer forms, through the same staging context as svs_embed / svs_extract.  A keyed embed stages whole frames
+ * (a frame's blocks can take any slot of its stream range), so a batch is never cut inside a frame. */
+int svs_embed_ordered(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                      double delta, int n_ac, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                      uint32_t flags, uint64_t *n_embedded);
+
+int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta,
+                        int n_ac, uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
+                        uint64_t *n_bits_out);
+
 /* ---- colour plumbing around the operator (device resident) --------------------------------------------
  * Interleaved 8-bit BGR frames [frame][row][col][3] <-> gray planes.  bgr_row_pitch / bgr_frame_pitch in bytes,
  * multiples of 4; BGR base pointers 4-byte aligned.

@@ -194,9 +194,10 @@ using svs::EmbedPath;
 using svs::ExtractPath;
 
 // svs_embed_dev's plan: embed_row1_kernel (one coefficient row, and the copy), embed_kernel<2> (two rows) or embed_exact_kernel.
-// `two`: two blocks per lane, where the plan and the buffers allow it.
+// `two`: two blocks per lane, where the plan and the buffers allow it.  A keyed plan (p.keyed, `ord` its order) launches the
+// KEYED instantiation of the same kernel family, with the order as the last argument.
 int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
-                 svs::Geometry g, const uint32_t *bits) {
+                 svs::Geometry g, const uint32_t *bits, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}) {
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
     const uint32_t words = (uint32_t)p.n_words;
@@ -206,19 +207,31 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
             // the exact kernel's quantiser loop is instantiated for one or two coefficient rows (n <= 7: the benchmark's 3;
             // n <= 15: the reference GUI's 10) and for all eight (any n): fewer wave-uniform tests per block, same arithmetic
             return dispatch<1, 2, 8>(p.rows, [&](auto u) {
-                return launch(svs::embed_exact_kernel<QM, decltype(u)::value>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
+                constexpr int U = decltype(u)::value;
+                if (p.keyed)
+                    return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g,
+                                  p.qp, bits, p.bit_offset, p.n_bits, words, ord);
+                return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
                               p.bit_offset, p.n_bits, words);
             });
-        if (p.rows == 2)   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
+        if (p.rows == 2) {   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
+            if (p.keyed)
+                return launch(svs::embed_kernel<2, QM, 1, 0, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g, p.qp,
+                              bits, p.bit_offset, p.n_bits, words SVS_COUNTER_ARG, ord);
             return g.n_ac == 10 ? launch(svs::embed_kernel<2, QM, 1, 10>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
                                          p.bit_offset, p.n_bits, words SVS_COUNTER_ARG)
                                 : launch(svs::embed_kernel<2, QM, 1>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
                                          p.bit_offset, p.n_bits, words SVS_COUNTER_ARG);
+        }
         // one coefficient row: the integer-domain kernel (round 6), under its occupancy cap
         return dispatch<1, 2>(two ? 2 : 1, [&](auto bpl) {
             constexpr int BPL = decltype(bpl)::value;
-            return launch(svs::embed_row1_kernel<QM, BPL>, grid_for(total, BPL), lds_pad_for(embed_wg_per_cu(BPL), svs::kRow1StaticLds),
-                          st, gray, stego, g, p.qp, bits, p.bit_offset, p.n_bits, words SVS_COUNTER_ARG);
+            const uint32_t lds = lds_pad_for(embed_wg_per_cu(BPL), svs::kRow1StaticLds);
+            if (p.keyed)
+                return launch(svs::embed_row1_kernel<QM, BPL, true, svs::BlockOrderArgs>, grid_for(total, BPL), lds, st, gray, stego, g,
+                              p.qp, bits, p.bit_offset, p.n_bits, words SVS_COUNTER_ARG, ord);
+            return launch(svs::embed_row1_kernel<QM, BPL>, grid_for(total, BPL), lds, st, gray, stego, g, p.qp, bits, p.bit_offset,
+                          p.n_bits, words SVS_COUNTER_ARG);
         });
     });
 }
@@ -245,19 +258,27 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
     });
 }
 
-// svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>
+// svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>.  A keyed plan ORs every block's bits into its
+// slot with global atomics (svs_device.hpp, or_bits_global): the output is cleared first, on the same stream.
 int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
-                   uint64_t out_bytes) {
-    if (p.path == ExtractPath::ZEROS) {
-        SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
-        return SVS_OK;
-    }
+                   uint64_t out_bytes, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}) {
+    if (p.path == ExtractPath::ZEROS || p.keyed) SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
+    if (p.path == ExtractPath::ZEROS) return SVS_OK;
     g.xcd_chunk = p.xcd_chunk;
     return dispatch<svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
         if (p.path == ExtractPath::EXACT)
             return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
-                return launch(svs::extract_exact_kernel<decltype(r)::value, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes);
+                constexpr int U = decltype(r)::value;
+                if (p.keyed)
+                    return launch(svs::extract_exact_kernel<U, QM, 1, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, g, p.qp,
+                                  out, out_bytes, ord);
+                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes);
+            });
+        if (p.keyed)
+            return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
+                return launch(svs::extract_kernel<decltype(r)::value, QM, 1, 0, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray,
+                              g, p.qp, out, out_bytes, ord);
             });
         // n = 10 (the reference GUI's default) has a compile-time-n instantiation of the extract kernel: +1..7 %
         // (profiles/history/r01_ab_quant_exact.txt).  The same specialisation of the embed kernel measured SLOWER (-13 % at
@@ -481,19 +502,22 @@ struct HostPayload {
 };
 
 // The chunk pipeline of the host-pointer embed calls.  The frames (bpp bytes per pixel; the planes' pitches count pixels) go
-// from `src` to the same offsets of c.frames chunk by chunk: upload and embed(sub, off, bit_offset, budget, &done, up) on the UP
-// stream, then download(chunk, off, down) behind the chunk's event on the DOWN stream.  A batch of one chunk runs in order on
-// one stream - no event, no second stream.  `off` is the chunk's first byte; `rebased` the payload's first bit in c.bits.
+// from `src` to the same offsets of c.frames chunk by chunk: upload and embed(sub, off, f0, bit_offset, budget, &done, up) on
+// the UP stream, then download(chunk, off, down) behind the chunk's event on the DOWN stream.  A batch of one chunk runs in
+// order on one stream - no event, no second stream.  `off` is the chunk's first byte, f0 its first frame; `rebased` the
+// payload's first bit in c.bits.  whole_frames: no chunk cuts a frame into bands (a keyed order spreads a frame's payload
+// over all its blocks).
 template <class Embed, class Download>
 int embed_chunks(HostStage &c, const svs_planes *p, int bpp, const uint8_t *src, uint32_t n, uint64_t use, uint64_t n_bits,
-                 uint64_t rebased, Embed &&embed, Download &&download, uint64_t *done_total) {
+                 uint64_t rebased, Embed &&embed, Download &&download, uint64_t *done_total, bool whole_frames = false) {
     const int32_t H = p->height, W = p->width;
     const int64_t rp = bpp * p->row_pitch, fp = bpp * p->frame_pitch, row_bytes = (int64_t)bpp * W;
     const uint64_t wb = (uint64_t)W / 8, bpf = wb * ((uint64_t)H / 8);
     // a non-empty payload that cannot be embedded (delta <= 0, n_ac = 0) must still reach the kernel as "non-empty": every
     // block is then round-tripped, as in the reference
     const uint64_t pass_bits = use ? use : (n_bits ? 1 : 0);
-    const size_t target = stage_chunk_bytes(bpp * span_bytes(p));
+    size_t target = stage_chunk_bytes(bpp * span_bytes(p));
+    if (whole_frames && target < (size_t)H * rp) target = (size_t)H * rp;
     uint32_t n_chunks = 0;
     svs::for_each_chunk(p->n_frames, H, (size_t)rp, target, [&](const svs::Chunk &) { ++n_chunks; });
     const bool serial = n_chunks <= 1;
@@ -509,7 +533,7 @@ int embed_chunks(HostStage &c, const svs_planes *p, int bpp, const uint8_t *src,
         const svs_planes sub{ch.nf, ch.rows, W, 0, p->row_pitch, ch.nf == 1 ? ch.rows * p->row_pitch : p->frame_pitch};
         const uint64_t g0 = (uint64_t)ch.f0 * bpf + (uint64_t)(ch.r0 / 8) * wb;
         uint64_t done = 0;
-        if ((rc = embed(sub, off, rebased + (use ? g0 * n : 0), svs::chunk_budget(pass_bits, use, g0, n), &done, up))) return;
+        if ((rc = embed(sub, off, ch.f0, rebased + (use ? g0 * n : 0), svs::chunk_budget(pass_bits, use, g0, n), &done, up))) return;
         *done_total += done;
         if (!serial && (rc = stage_handoff(c))) return;
         rc = download(ch, off, down);
@@ -640,18 +664,37 @@ uint64_t svs_capacity_bits(const svs_planes *p, int n_ac) {
 
 uint64_t svs_packed_bytes(uint64_t n_bits) { return (n_bits + 7) / 8; }
 
-int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, double delta, int n_ac,
-                  const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-                  uint64_t *n_embedded, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// the order argument of the ordered entry points: NULL (no order) or a valid one
+int check_order(const svs_block_order *order) {
+    if (order && order->reserved != 0) return fail(SVS_ERR_INVALID_ARG, "svs_block_order.reserved must be 0");
+    return SVS_OK;
+}
+
+// the kernels' form of an order for a batch of `bpf` blocks per frame
+svs::BlockOrderArgs order_args(const svs_block_order *order, const svs::Geometry &g) {
+    return order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{};
+}
+
+// svs_embed_dev and svs_embed_ordered_dev (order NULL: the call without an order)
+int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order, double delta,
+              int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+              uint64_t *n_embedded, void *stream) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
+    if (int rc = check_order(order)) return rc;
     if (total == 0) return SVS_OK;
     if (!d_gray || !d_stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
     if (((uintptr_t)d_gray % 8) || ((uintptr_t)d_stego % 8))
         return fail(SVS_ERR_INVALID_ARG, "plane pointers must be 8-byte aligned");
-    const svs::EmbedPlan p = svs::plan_embed(route_args(delta, g, total, n_bits, bit_offset, flags, false));
+    svs::RouteArgs ra = route_args(delta, g, total, n_bits, bit_offset, flags, false);
+    ra.keyed = order != nullptr;
+    const svs::EmbedPlan p = svs::plan_embed(ra);
     if (p.use > 0) {
         if (!d_bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
         if ((uintptr_t)d_bits_packed % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
@@ -662,31 +705,62 @@ int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *pla
     if (p.path == EmbedPath::COPY && d_gray == d_stego) return SVS_OK;
     const bool two = p.two_blocks && rows_allow_two_blocks(planes, d_gray, d_stego);
     if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g,
-                              p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr))
+                              p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr, order_args(order, g)))
         return rc;
     if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
 }
 
-int svs_extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, int n_ac,
-                    uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
-                    void *stream) {
+// svs_extract_dev and svs_extract_ordered_dev
+int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
+                uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
+    if (int rc = check_order(order)) return rc;
     if (cap == 0) return SVS_OK;
     if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
     if ((uintptr_t)d_bits_packed_out % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
     const uint64_t bytes = (cap + 7) / 8;
     if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
-    const svs::ExtractPlan p = svs::plan_extract(route_args(delta, g, total, 0, 0, flags, false));
+    svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
+    ra.keyed = order != nullptr;
+    const svs::ExtractPlan p = svs::plan_extract(ra);
     // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
     if (p.path != ExtractPath::ZEROS && (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)))
         return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes)) return rc;
+    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, order_args(order, g))) return rc;
     if (n_bits_out) *n_bits_out = cap;
     return SVS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, double delta, int n_ac,
+                  const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                  uint64_t *n_embedded, void *stream) {
+    return embed_dev(d_gray, d_stego, planes, nullptr, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream);
+}
+
+int svs_embed_ordered_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                          double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                          uint32_t flags, uint64_t *n_embedded, void *stream) {
+    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream);
+}
+
+int svs_extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, int n_ac,
+                    uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
+                    void *stream) {
+    return extract_dev(d_gray, planes, nullptr, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream);
+}
+
+int svs_extract_ordered_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, double delta,
+                            int n_ac, uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
+                            uint64_t *n_bits_out, void *stream) {
+    return extract_dev(d_gray, planes, order, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream);
 }
 
 static bool ranges_overlap(const void *a, const void *b, uint64_t span) {
@@ -708,13 +782,15 @@ static void copy_gray_reference(uint8_t *dst, const uint8_t *gray, const svs_pla
 
 // svs_embed (payload = packed MSB-first bits, indexed by bit_offset) and svs_embed_str (payload = n_bits '0' / '1' characters,
 // bit_offset = 0) share everything but the way the payload reaches the device
+// (svs_embed_ordered: a packed payload and an order)
 static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out, const svs_planes *planes, double delta, int n_ac,
                       const uint8_t *bits_packed, const char *bits_ascii, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-                      uint64_t *n_embedded) {
+                      uint64_t *n_embedded, const svs_block_order *order = nullptr) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
+    if (int rc = check_order(order)) return rc;
     if (total == 0) return SVS_OK;
     if (!gray || !stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
     if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
@@ -739,7 +815,12 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
             uint8_t *d = static_cast<uint8_t *>(c.frames.p);
             const int rc = embed_chunks(
                 c, planes, 1, gray, g.n_ac, use, n_bits, rebased,
-                [&](const svs_planes &sub, int64_t off, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
+                [&](const svs_planes &sub, int64_t off, int32_t f0, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
+                    if (order) {   // whole frames: the chunk's first frame is clip frame order->first_frame + f0
+                        const svs_block_order o{order->key, order->first_frame + (uint32_t)f0, 0u};
+                        return embed_dev(d + off, d + off, &sub, &o, delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset,
+                                         budget, flags, done, up);
+                    }
                     return svs_embed_dev(d + off, d + off, &sub, delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset,
                                          budget, flags, done, up);
                 },
@@ -758,7 +839,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                     }
                     return (int)SVS_OK;
                 },
-                &done_total);
+                &done_total, order != nullptr);
             // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
             // thread would only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first.)
             if (!rc && gray_ref_out && gray_ref_out != gray && !ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
@@ -772,6 +853,12 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
 int svs_embed(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, double delta, int n_ac,
               const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
     return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded);
+}
+
+int svs_embed_ordered(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order, double delta,
+                      int n_ac, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                      uint64_t *n_embedded) {
+    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded, order);
 }
 
 // every character '0' or '1'?  One OR-reduction over the bytes (vectorised: about 0.05 ms per million characters)
@@ -803,9 +890,15 @@ int svs_embed_str(const uint8_t *gray, uint8_t *gray_ref_out, uint8_t *stego, co
 
 int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, uint8_t *bits_packed_out,
                 uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
+    return svs_extract_ordered(gray, planes, nullptr, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out);
+}
+
+int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
+                        uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
+    if (int rc = check_order(order)) return rc;
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     const uint64_t bytes = (cap + 7) / 8;
@@ -813,7 +906,7 @@ int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int
     return extract_staged(
         gray, span_bytes(planes), bytes, 0, n_bits_out,
         [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
-            return svs_extract_dev(d_in, planes, delta, n_ac, d_bits, d_bytes, flags, got, st);
+            return extract_dev(d_in, planes, order, delta, n_ac, d_bits, d_bytes, flags, got, st);
         },
         [&](HostStage &c, hipStream_t st) { return stage_d2h(st, bits_packed_out, c.bits.p, bytes); });
 }
@@ -987,7 +1080,7 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
                     *d_ref = gray_ref_out ? static_cast<uint8_t *>(c.third.p) : nullptr;
             return embed_chunks(
                 c, planes, 3, bgr, g.n_ac, use, n_bits, rebased,
-                [&](const svs_planes &sub, int64_t off, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
+                [&](const svs_planes &sub, int64_t off, int32_t, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
                     const int64_t rp = 3 * sub.row_pitch, fp = 3 * sub.frame_pitch;
                     return svs_embed_bgr_dev(d_in + off, rp, fp, d_out + off, rp, fp, d_ref ? d_ref + off / 3 : nullptr, &sub, weights,
                                              delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset, budget, flags, done, up);

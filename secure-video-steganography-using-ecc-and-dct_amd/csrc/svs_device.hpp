@@ -7,6 +7,7 @@
 
 #include "svs_block.hpp"
 #include "svs_colour.hpp"
+#include "svs_order.hpp"
 
 namespace svs {
 
@@ -150,6 +151,49 @@ __device__ __forceinline__ void emit_wave_bits(uint32_t *mine, uint32_t lane, ui
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Keyed block order (svs_order.hpp).  A KEYED instantiation takes one BlockOrderArgs after its last parameter (the parameter
+// pack `Order`, one element exactly when KEYED); the unkeyed ones take none, so their parameter lists and their code are
+// what they were before the order existed.  Pixels still move in raster order - every lane loads and stores its own
+// block(s), coalesced - and only a block's place in the payload stream changes: block i of call frame f takes stream bits
+// (f N + sigma_t^-1(i)) n .. + n - 1, t = first_frame + f.  Payload reads become one scattered 8-byte read per block.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ BlockOrderArgs order_arg() { return BlockOrderArgs{}; }
+__device__ __forceinline__ BlockOrderArgs order_arg(const BlockOrderArgs &o) { return o; }
+
+// first stream bit of global block gblock (KEYED: of its slot), and of its right neighbour gblock + 1 (same frame: the
+// two-block layout needs an even number of blocks per block row) in *second
+template <bool KEYED>
+__device__ __forceinline__ uint64_t stream_first(uint32_t gblock, uint32_t n, const Geometry &g, const BlockOrderArgs &o,
+                                                 uint64_t *second = nullptr) {
+    if constexpr (!KEYED) {
+        return (uint64_t)gblock * n;
+    } else {
+        const uint32_t f = fast_div(gblock, g.by_bpf);
+        const uint32_t i = gblock - f * g.by_bpf.div;
+        const RoundKeys rk = round_keys(o, o.first_frame + f);
+        const uint64_t frame0 = (uint64_t)f * g.by_bpf.div;
+        if (second) *second = (frame0 + block_to_slot(i + 1u, o, rk)) * n;
+        return (frame0 + block_to_slot(i, o, rk)) * n;
+    }
+}
+
+// KEYED extraction: a block's n bits (hi:lo, MSB first from bit 63) ORed into the packed output at stream bit `pos` with
+// 32-bit global atomics (the call has cleared the output first).  Only dwords that receive a 1 bit are touched; a 1 bit lies
+// below the call's capacity, and what the OR adds to the last, partial dword past it is 0.
+template <int U>
+__device__ __forceinline__ void or_bits_global(uint8_t *out, uint64_t pos, uint32_t hi, uint32_t lo) {
+    uint32_t *w = reinterpret_cast<uint32_t *>(out) + (pos >> 5);
+    const uint32_t o = (uint32_t)(pos & 31u);
+    const uint32_t x0 = hi >> o, x1 = __builtin_amdgcn_alignbit(hi, lo, o);
+    if (x0) atomicOr(&w[0], __builtin_bswap32(x0));   // stream bit p -> bit 7 - p % 8 of byte p / 8
+    if (x1) atomicOr(&w[1], __builtin_bswap32(x1));
+    if constexpr (U > 4) {                               // o + n > 64 needs n > 32
+        const uint32_t x2 = __builtin_amdgcn_alignbit(lo, 0u, o);
+        if (x2) atomicOr(&w[2], __builtin_bswap32(x2));
+    }
+}
+
 struct GuardEntry {
     uint32_t px[16];   // rows as (low dword, high dword) pairs: the original pixels in, the exact stego pixels out
     uint32_t hi, lo;   // payload window of the block
@@ -246,11 +290,12 @@ __device__ __forceinline__ void extract_phase2(GuardEntry *entries, float *tile,
 #define SVS_EXTRACT_CAP 16   // worklist entries per wave and round of the extract kernels
 // BPL (blocks per lane) is always 1 here and in the other non-row1 kernels; it stays in their template parameter lists so that
 // the kernel symbols match the ones the traces under profiles/ name.
-template <int U, int QM, int BPL, int NFIX = 0>
+template <int U, int QM, int BPL, int NFIX = 0, bool KEYED = false, class... Order>
 __global__ __launch_bounds__(SVS_WG) void extract_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                       const QimParams qp, uint8_t *__restrict__ out,
-                                                      const uint64_t out_bytes) {
+                                                      const uint64_t out_bytes, const Order... order) {
     static_assert(BPL == 1, "one block per lane");
+    static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
     __shared__ GuardEntry entries[SVS_WG / 64][SVS_EXTRACT_CAP];
     __shared__ float tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
@@ -279,7 +324,11 @@ __global__ __launch_bounds__(SVS_WG) void extract_kernel(const uint8_t *__restri
     // A quantiser input within the per-block error bound of a rounding tie (svs_block.hpp, SVS_TIE2_*): those blocks get the
     // pocketfft-identical transform from eight lanes each (wave-private worklist).  Never taken on stego frames at delta >= 8.
     extract_phase2<QM, false, SVS_EXTRACT_CAP>(&entries[wave][0], &tiles[wave][0], lane, n, qp, tie, ax, ay, hi, lo, false, ax, ay, hb, lb);
-    emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
+    if constexpr (KEYED) {
+        if (gblock < g.total_blocks) or_bits_global<U>(out, stream_first<true>(gblock, n, g, order_arg(order...)), hi, lo);
+    } else {
+        emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -288,20 +337,21 @@ __global__ __launch_bounds__(SVS_WG) void extract_kernel(const uint8_t *__restri
 // so it is VALU-bound at roughly 40 % of the fast kernel's rate; it exists for bit-identical output.
 // ---------------------------------------------------------------------------------------
 // Register-allocated for 2 waves per SIMD: +1..3 % over 3; 4 spills 52 B and is 8 % slower.
-template <int QM, int U = 8>  // U: coefficient rows the quantiser loop covers (flat indices 1..n lie in rows < U)
+template <int QM, int U = 8, bool KEYED = false, class... Order>  // U: coefficient rows the quantiser loop covers (flat indices 1..n lie in rows < U)
 __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *gray,  // may alias stego
                                                           uint8_t *stego, const Geometry g,
                                                           const QimParams qp,
                                                           const uint32_t *__restrict__ bits,
                                                           const uint64_t bit_offset, const uint64_t n_bits,
-                                                          const uint32_t n_words) {
+                                                          const uint32_t n_words, const Order... order) {
+    static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
     if (gblock >= g.total_blocks) return;
     const int64_t off = block_offset(gblock, g);
     typename RowVec<1>::type v[8];
     load_rows<1>(gray + off, g.row_pitch, v);
     const uint32_t n = g.n_ac;  // 0 = round-trip every block without touching a coefficient
-    const uint64_t first = (uint64_t)gblock * n;
+    const uint64_t first = stream_first<KEYED>(gblock, n, g, order_arg(order...));
     if (first >= n_bits) {
         if (stego != gray) store_rows<1>(stego + off, g.row_pitch, v);
         return;
@@ -535,10 +585,12 @@ __device__ __forceinline__ uint32_t shadow_block(uint32_t gblock, const Geometry
 #else
 #define SVS_REPLAY_COUNTER_PARAM
 #endif
-template <int U, int QM, int BPL, int NFIX = 0>   // NFIX: compile-time n (two rows only; svs_capi.hip instantiates the GUI's default 10)
+template <int U, int QM, int BPL, int NFIX = 0, bool KEYED = false, class... Order>   // NFIX: compile-time n (two rows only; svs_capi.hip instantiates the GUI's default 10)
 __global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint8_t *stego, const Geometry g, const QimParams qp,
                                                     const uint32_t *__restrict__ bits, const uint64_t bit_offset,
-                                                    const uint64_t n_bits, const uint32_t n_words SVS_REPLAY_COUNTER_PARAM) {
+                                                    const uint64_t n_bits, const uint32_t n_words SVS_REPLAY_COUNTER_PARAM,
+                                                    const Order... order) {
+    static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     static_assert(U == 2, "n = 8..15 (svs_capi.hip: one coefficient row runs embed_row1_kernel, more rows embed_exact_kernel in every mode)");
     static_assert(BPL == 1, "one block per lane (see extract_kernel)");
     constexpr bool PARKED = QM != QM_POW2;
@@ -565,8 +617,10 @@ __global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint
     load_rows<1>(gray + off, g.row_pitch, v);
 #pragma unroll
     for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
+    uint64_t first_keyed = 0;   // KEYED: the slot's first stream bit, computed once
+    if constexpr (KEYED) first_keyed = stream_first<true>(gblock, n, g, order_arg(order...));
     if (live) {
-        const uint64_t first = (uint64_t)gblock * n;  // stream index of this lane's first bit
+        const uint64_t first = KEYED ? first_keyed : (uint64_t)gblock * n;  // stream index of this lane's first bit
         write = stego != gray;                         // past the budget: byte-identical copy (the reference's loops `break`, :130,:132)
         if (first < n_bits) {
             write = true;
@@ -588,7 +642,7 @@ __global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint
         redone = guard_phase2_slots<QM>(&park[wave][0], &meta[wave][0], &tiles[wave][0], lane, n, qp, und, nb, hi, ax, ay);
     } else {
         const GuardPayload pl{bits, bit_offset, n_bits, n_words};
-        const uint64_t first = (uint64_t)gblock * n;
+        const uint64_t first = KEYED ? first_keyed : (uint64_t)gblock * n;
         redone = guard_phase2<QM, false, SVS_GUARD_CAP, true>(&entries[wave][0], &tiles[wave][0], lane, n, qp, pl, und, first, ax, ay,
                                                               false, first, ax, ay, hi, 0u);
     }
@@ -650,10 +704,10 @@ __device__ __forceinline__ void row1_collect(const GuardEntry *e, typename RowVe
 }
 
 // phase 2 of the one-row kernel: guard_phase2 on the row vectors (the payload windows are kept from phase 1)
-template <int QM, int BPL, int CAP>
+template <int QM, int BPL, int CAP, bool KEYED = false>   // KEYED: block B's first stream bit is first_b, not first_a + n
 __device__ __forceinline__ uint32_t row1_phase2(GuardEntry *entries, float *tile, uint32_t lane, uint32_t n, const QimParams &qp,
-                                                uint64_t n_bits, bool und_a, bool und_b, uint64_t first_a, uint32_t hi_a, uint32_t hi_b,
-                                                typename RowVec<BPL>::type (&v)[8]) {
+                                                uint64_t n_bits, bool und_a, bool und_b, uint64_t first_a, uint64_t first_b, uint32_t hi_a,
+                                                uint32_t hi_b, typename RowVec<BPL>::type (&v)[8]) {
     const uint64_t mask_a = __ballot(und_a);
     const uint64_t mask_b = BPL == 2 ? __ballot(und_b) : 0ull;
     if ((mask_a | mask_b) == 0) return 0;   // wave-uniform: the common case costs two ballots
@@ -671,7 +725,7 @@ __device__ __forceinline__ uint32_t row1_phase2(GuardEntry *entries, float *tile
         if (mine_b) {
             GuardEntry *e = &entries[rank_b - base];
             row1_deposit<BPL>(e, v, 1);
-            e->hi = hi_b; e->lo = 0u; e->nb = block_budget(first_a + n, n_bits, n);
+            e->hi = hi_b; e->lo = 0u; e->nb = block_budget(KEYED ? first_b : first_a + n, n_bits, n);
         }
         wave_lds_fence();
         const uint32_t todo = min(total - base, (uint32_t)CAP);
@@ -699,22 +753,32 @@ struct Row1Args {
     uint32_t n_words;
 };
 
+// The stream positions of a lane's block(s): unkeyed, block B follows block A in the stream and both windows come from A's
+// payload qword; keyed, each block has its own slot and its own qword.  A keyed block past the budget is left as it is
+// (the reference's loops `break` before its slot) - it never reaches the arithmetic.
+struct Row1Slots {
+    uint64_t first_a, first_b;
+    uint64_t q_b;
+};
+
 // phases 1-3 for the rows `v` of global block(s) gb (already loaded from gray + off): decide / apply, exact replay of the
 // wave's undecided blocks, store.
-template <int QM, int BPL>
+template <int QM, int BPL, bool KEYED = false>
 __device__ __forceinline__ uint32_t row1_process(typename RowVec<BPL>::type (&v)[8], uint32_t gb, bool live, int64_t off, uint64_t q,
                                                  const Geometry &g, const QimParams &qp, const Row1Args &a, GuardEntry *entries,
-                                                 float *tile, uint32_t lane) {
+                                                 float *tile, uint32_t lane, const Row1Slots &ks = Row1Slots{}) {
     const uint32_t n = g.n_ac;
-    const uint64_t first = (uint64_t)gb * n;   // stream index of this lane's first bit
+    const uint64_t first = KEYED ? ks.first_a : (uint64_t)gb * n;   // stream index of this lane's first bit
+    const uint64_t first_b = ks.first_b;   // KEYED only (unkeyed: first + n, formed where it is used)
+    const bool has_a = !KEYED || first < a.n_bits, has_b = BPL == 2 && (!KEYED || first_b < a.n_bits);
     bool und_a = false, und_b = false, clip = false;
     uint32_t hi_a = 0, hi_b = 0;
     ColumnDeltas ca = {0u, 0u, 0u, 0u}, cb = {0u, 0u, 0u, 0u};
-    if (live && first < a.n_bits) {
+    if (live && (KEYED ? (has_a || has_b) : first < a.n_bits)) {
         const uint32_t sh = (uint32_t)((a.bit_offset + first) & 31u);
         hi_a = window32(q, sh);
-        uint32_t flags;
-        {
+        uint32_t flags = 0;
+        if (has_a) {
             uint32_t rx[8], ry[8];
             row1_block<BPL>(v, 0, rx, ry);
             flags = guard_decide_int<QM>(rx, ry, n, block_budget(first, a.n_bits, n), hi_a, qp, ca);
@@ -724,11 +788,13 @@ __device__ __forceinline__ uint32_t row1_process(typename RowVec<BPL>::type (&v)
         clip = flags == SVS_ROW1_MAY_CLIP;
         if constexpr (BPL == 2) {
             SVS_SCHED_FENCE();   // one block at a time
-            hi_b = window32(q, sh + n);
+            hi_b = KEYED ? window32(ks.q_b, (uint32_t)((a.bit_offset + first_b) & 31u)) : window32(q, sh + n);
+        }
+        if (BPL == 2 && has_b) {
             uint32_t rx[8], ry[8];
             row1_block<BPL>(v, 1, rx, ry);
             // a budget of 0 (only the lane the payload ends in can see it) leaves block B as it is: all its deltas are 0
-            flags = guard_decide_int<QM>(rx, ry, n, block_budget(first + n, a.n_bits, n), hi_b, qp, cb);
+            flags = guard_decide_int<QM>(rx, ry, n, block_budget(KEYED ? first_b : first + n, a.n_bits, n), hi_b, qp, cb);
             und_b = (flags & SVS_ROW1_UNDECIDED) != 0;
             if (und_b) { cb.e_lo = 0u; cb.o_lo = 0u; cb.e_hi = 0u; cb.o_hi = 0u; }
             clip = clip || flags == SVS_ROW1_MAY_CLIP;
@@ -760,9 +826,10 @@ __device__ __forceinline__ uint32_t row1_process(typename RowVec<BPL>::type (&v)
             SVS_SCHED_FENCE();   // row by row: scheduled for latency, this rare path would set the kernel's register count
         }
     }
-    const uint32_t redone = row1_phase2<QM, BPL, SVS_GUARD_CAP>(entries, tile, lane, n, qp, a.n_bits, und_a, und_b, first, hi_a, hi_b, v);
+    const uint32_t redone = row1_phase2<QM, BPL, SVS_GUARD_CAP, KEYED>(entries, tile, lane, n, qp, a.n_bits, und_a, und_b, first,
+                                                                       first_b, hi_a, hi_b, v);
     // past the budget: byte-identical copy (the reference's loops `break`, :130,:132)
-    if (live && (a.stego != a.gray || first < a.n_bits)) store_rows<BPL>(a.stego + off, g.row_pitch, v);
+    if (live && (a.stego != a.gray || (KEYED ? has_a || has_b : first < a.n_bits))) store_rows<BPL>(a.stego + off, g.row_pitch, v);
     return redone;
 }
 
@@ -772,11 +839,12 @@ typedef GuardEntry Row1Entries[SVS_WG / 64][SVS_GUARD_CAP];
 typedef float Row1Tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
 constexpr uint32_t kRow1StaticLds = sizeof(Row1Entries) + sizeof(Row1Tiles);
 
-template <int QM, int BPL>
+template <int QM, int BPL, bool KEYED = false, class... Order>
 __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray, uint8_t *stego, const Geometry g,
                                                           const QimParams qp, const uint32_t *__restrict__ bits,
                                                           const uint64_t bit_offset, const uint64_t n_bits,
-                                                          const uint32_t n_words SVS_REPLAY_COUNTER_PARAM) {
+                                                          const uint32_t n_words SVS_REPLAY_COUNTER_PARAM, const Order... order) {
+    static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ Row1Entries entries;
     __shared__ Row1Tiles tiles;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -788,8 +856,17 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
     const Row1Args a{gray, stego, bits, bit_offset, n_bits, n_words};
     const uint32_t n = g.n_ac;
     uint64_t q = 0;
-    if (live && (uint64_t)gb * n < n_bits) q = payload_qword(bits, n_words, bit_offset + (uint64_t)gb * n);
-    const uint32_t redone = row1_process<QM, BPL>(v, gb, live, off, q, g, qp, a, &entries[wave][0], &tiles[wave][0], lane);
+    uint32_t redone;
+    if constexpr (KEYED) {   // two blocks per lane: two qword reads, one per slot
+        Row1Slots ks{0, 0, 0};
+        ks.first_a = stream_first<true>(gb, n, g, order_arg(order...), BPL == 2 ? &ks.first_b : nullptr);
+        if (live && ks.first_a < n_bits) q = payload_qword(bits, n_words, bit_offset + ks.first_a);
+        if (BPL == 2 && live && ks.first_b < n_bits) ks.q_b = payload_qword(bits, n_words, bit_offset + ks.first_b);
+        redone = row1_process<QM, BPL, true>(v, gb, live, off, q, g, qp, a, &entries[wave][0], &tiles[wave][0], lane, ks);
+    } else {
+        if (live && (uint64_t)gb * n < n_bits) q = payload_qword(bits, n_words, bit_offset + (uint64_t)gb * n);
+        redone = row1_process<QM, BPL>(v, gb, live, off, q, g, qp, a, &entries[wave][0], &tiles[wave][0], lane);
+    }
 #if defined(SVS_EXPERIMENTS)
     if (replay_counter != nullptr && redone != 0 && lane == 0) atomicAdd(replay_counter, (unsigned long long)redone);
 #else
@@ -802,11 +879,12 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
 // every placement, 1.77 - 1.95 ms per 600 x 4K against 1.58 - 1.62, even with the arithmetic skipped: profiles/r06_stream_pipeline.txt.
 // What the one-shot launch has and the loop has not is the hardware's own pacing: a workgroup starts when another one ends.)
 
-template <int U, int QM, int BPL = 1>   // BPL: see extract_kernel
+template <int U, int QM, int BPL = 1, bool KEYED = false, class... Order>   // BPL: see extract_kernel
 __global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                             const QimParams qp, uint8_t *__restrict__ out,
-                                                            const uint64_t out_bytes) {
+                                                            const uint64_t out_bytes, const Order... order) {
     static_assert(BPL == 1, "one block per lane");
+    static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t tile = tile_id(g.xcd_chunk);
@@ -820,18 +898,16 @@ __global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__
 #pragma unroll
         for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
         extract_block_exact<U, QM>(ax, ay, n, qp, hi, lo);
+        if constexpr (KEYED) or_bits_global<U>(out, stream_first<true>(gblock, n, g, order_arg(order...)), hi, lo);
     }
-    emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
+    if constexpr (!KEYED)
+        emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
 }
 
 // ---------------------------------------------------------------------------------------
 // measurement helpers
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lowbias32(uint32_t h) {
-    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
-    return h;
-}
-
+// lowbias32: svs_order.hpp
 // 8 pixels per thread per step; same hash as svsdct/synth.py
 __global__ __launch_bounds__(256) void fill_synthetic_kernel(uint8_t *__restrict__ frames, int32_t n_frames,
                                                              int32_t height, int32_t width, int64_t row_pitch,

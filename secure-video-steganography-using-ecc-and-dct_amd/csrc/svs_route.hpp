@@ -23,6 +23,7 @@ struct RouteArgs {
     bool bgr;                 // the fused colour calls (svs_embed_bgr_dev / svs_extract_bgr_dev)
     bool guarded_off;         // reaches the gray calls only
     float guard_scale, tie_scale;
+    bool keyed = false;       // a keyed block order (svs_embed_ordered_dev / svs_extract_ordered_dev; gray calls only)
 };
 
 // COPY: nothing to embed and an empty payload - the reference's loops break before the first block.  Gray: a byte copy through
@@ -39,6 +40,7 @@ struct EmbedPlan {
     int qm;                   // QuantMode of the instantiation
     int rows;                 // coefficient rows of the instantiation (EXACT / ROUND_TRIP: the U of the exact kernel)
     bool two_blocks;          // embed_row1_kernel may take two blocks per lane where the buffers allow it
+    bool keyed;               // the KEYED instantiation of the family (STREAMING / EXACT only: the other paths do not depend on order)
     uint32_t n_ac;            // Geometry::n_ac of the launch
     uint32_t xcd_chunk;
     QimParams qp;
@@ -70,6 +72,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         // the BGR exact kernel covers all eight rows; the gray one has instantiations for one, two and eight
         p.rows = streaming || (!a.bgr && rows <= 2) ? rows : 8;
         p.two_blocks = streaming && !a.bgr && rows == 1;
+        p.keyed = a.keyed;
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;
@@ -99,6 +102,7 @@ struct ExtractPlan {
     int rows;
     uint32_t xcd_chunk;
     QimParams qp;
+    bool keyed;               // the KEYED instantiation of the family (not ZEROS: all bits 0 in any order)
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -125,6 +129,7 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     // so FAST mode uses it too; with more rows it costs ~17 % and stays opt-in.
     if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1) exact = true;
     p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
+    p.keyed = a.keyed;
     return p;
 }
 

@@ -20,6 +20,7 @@ from config_and_setup import (bitstream_ke_bytes, buat_pasangan_kunci_ecc, buat_
                               serialisasi_kunci_publik_ecc_compressed, setup_kunci_ecc)  # noqa: F401
 from svsdct import batch as _batch
 from svsdct import framing as _framing
+from svsdct import order as _order
 from svsdct.pipeline import FramePipeline, SlotFeeder, read_ahead
 
 BATCH_FRAMES = int(os.environ.get("SVS_BATCH_FRAMES", "32"))
@@ -32,6 +33,19 @@ FUSED_COLOUR = os.environ.get("SVS_FUSED_COLOUR", "0") == "1"
 # colours - each pixel shifted to the stego gray (SVS_KEEP_COLOUR, include/svsdct.h) - instead of the reference's
 # COLOR_GRAY2BGR.  Their BGR2GRAY is the reference's stego plane, so the receiver extracts the same bits.
 KEEP_COLOUR = os.environ.get("SVS_KEEP_COLOUR", "0") == "1"
+# SVS_BLOCK_KEY=<integer, int(x, 0)> (read per call): keyed block order - the blocks of video frame k take that frame's bits
+# in a key-seeded order (svsdct/order.py, include/svsdct.h) instead of raster order from the top-left block, so a payload
+# that fills part of a frame is spread over all of it.  The receiver needs the same key.  Unset: the reference's order, byte
+# for byte.  Not with SVS_KEEP_COLOUR (the fused colour kernels have no keyed form: refused); with SVS_FUSED_COLOUR the
+# host-conversion gray path runs.
+
+
+def _keyed(block_key=None, **kw):
+    """keyword arguments of a keyed call (block order): none at all without a key, so the unkeyed loop makes exactly the calls it
+    made before the order existed"""
+    if block_key is None:
+        return {}
+    return kw if kw else {"block_key": block_key}
 
 
 def _cv2():
@@ -91,6 +105,14 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     print(f"  Gambar Rahasia: '{path_gambar_rahasia}'")
     print(f"  Video Input: '{path_video_input}'")
     print(f"  Parameter: DELTA={delta_kuantisasi}, Koefisien AC per Blok={num_ac_coeffs}")
+    try:
+        kunci_blok = _order.key_from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"    Error: SVS_BLOCK_KEY tidak valid ({exc}).")
+        return False, None, None
+    if kunci_blok is not None and KEEP_COLOUR:
+        print("    Error: SVS_BLOCK_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR.")
+        return False, None, None
 
     payload = _siapkan_payload(path_gambar_rahasia, kunci_publik_ecc_penerima_bytes_compressed)
     if payload is None:
@@ -119,7 +141,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     print(f"    Video output akan disimpan sebagai '{path_out}' (Codec: FFV1).")
 
     tabel_warna = None
-    if FUSED_COLOUR or KEEP_COLOUR:
+    if (FUSED_COLOUR or KEEP_COLOUR) and kunci_blok is None:     # keyed order: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -187,7 +209,8 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         per_batch = BATCH_FRAMES if carrying is None else max(1, min(BATCH_FRAMES, carrying))
         n_batches = PIPELINE_DEPTH if carrying is None else -(-carrying // per_batch)
         with FramePipeline(out_h, out_w, per_batch, delta_kuantisasi, num_ac_coeffs,
-                           depth=max(1, min(PIPELINE_DEPTH, n_batches)), mode=_batch.host_level_mode()) as pipe:
+                           depth=max(1, min(PIPELINE_DEPTH, n_batches)), mode=_batch.host_level_mode(),
+                           **_keyed(block_key=kunci_blok)) as pipe:
             pipe.set_payload(payload)
             rencana = {"sisa": carrying}
 
@@ -207,7 +230,8 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
 
             def kirim(slot, k, n):
                 offset = k * per_batch * usable
-                used = pipe.submit_embed(slot, n, bit_offset=min(offset, total_bits))
+                used = pipe.submit_embed(slot, n, bit_offset=min(offset, total_bits),
+                                         **_keyed(first_frame=k * per_batch, block_key=kunci_blok))
                 return used, min(n * usable, max(0, total_bits - offset))
 
             with SlotFeeder(pipe, isi, kirim) as feeder:

@@ -18,6 +18,7 @@ from config_and_setup import (bytes_ke_bitstream, buat_shared_secret_ecdh, dekri
                               hitung_sha3_256, setup_kunci_ecc)  # noqa: F401
 from svsdct import batch as _batch
 from svsdct import framing as _framing
+from svsdct import order as _order
 from svsdct.pipeline import FramePipeline, SlotFeeder
 
 BATCH_FRAMES = int(os.environ.get("SVS_BATCH_FRAMES", "32"))
@@ -26,6 +27,8 @@ _MIN_HEADER_BITS = _framing.HEADER_BITS_STANDARD        # 976 (extract_process.p
 # SVS_FUSED_COLOUR=1: bits are extracted straight from the colour frames (svs_extract_bgr_dev) when the device
 # BGR -> gray reproduces this machine's cv2 (svsdct.colour); see embed_process.py
 FUSED_COLOUR = os.environ.get("SVS_FUSED_COLOUR", "0") == "1"
+# SVS_BLOCK_KEY (read per call): the sender's keyed block order (embed_process.py); frame k of the video is clip frame k.
+# With SVS_FUSED_COLOUR the host-conversion gray path runs.
 
 
 def _cv2():
@@ -40,11 +43,12 @@ def _gagal(pesan, cap=None):
     return False
 
 
-def _extract_frames(frames, delta, n_ac, tabel_warna=None):
+def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0):
     if tabel_warna:                                            # frames are colour: convert + extract in one kernel
         packed, n_bits = _batch.extract_bgr_frames(np.stack(frames), delta, n_ac, weights=tabel_warna)
     else:
-        packed, n_bits = _batch.extract_frames(np.stack(frames), delta, n_ac)
+        keyed = {} if block_key is None else {"block_key": block_key, "first_frame": first_frame}
+        packed, n_bits = _batch.extract_frames(np.stack(frames), delta, n_ac, **keyed)
     return np.unpackbits(packed, count=n_bits)
 
 
@@ -56,6 +60,11 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
     print("\n=== MEMULAI PROSES EKSTRAKSI GAMBAR DARI VIDEO ===")
     print(f"  Stego Video: '{path_stego_video}'")
     print(f"  Parameter: DELTA={delta_kuantisasi}, Koefisien AC per Blok={num_ac_coeffs}")
+    try:
+        kunci_blok = _order.key_from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"  Error: SVS_BLOCK_KEY tidak valid ({exc}).")
+        return False
     cv2 = _cv2()
     cap = cv2.VideoCapture(path_stego_video)
     if not cap.isOpened():
@@ -69,7 +78,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
         return False
     per_frame = _batch.capacity_bits(1, h, w, num_ac_coeffs)
     tabel_warna = None
-    if FUSED_COLOUR:
+    if FUSED_COLOUR and kunci_blok is None:                    # keyed order: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -93,7 +102,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
             cap.release()
             return False
         print(f"    Mengekstrak bit dari frame video ke-{frame_num}...")
-        bits = _extract_frames([gray], delta_kuantisasi, num_ac_coeffs, tabel_warna)
+        bits = _extract_frames([gray], delta_kuantisasi, num_ac_coeffs, tabel_warna, kunci_blok, frame_num - 1)
         if bits.size == 0:
             print(f"  Error: Tidak ada bit diekstrak dari frame ke-{frame_num}.")
             cap.release()
@@ -146,9 +155,11 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
             # overlapped staging: batch k+1 is decoded (feeder thread) while batch k is copied to the GPU, extracted and
             # copied back and the bits of batch k-1 are unpacked here
             per_batch = max(1, min(BATCH_FRAMES, lagi))
+            awal = frame_num                                        # clip index of the first frame of batch 0
             with FramePipeline(h, w, per_batch, delta_kuantisasi, num_ac_coeffs,
                                depth=max(1, min(PIPELINE_DEPTH, -(-lagi // per_batch))),
-                               mode=_batch.host_level_mode()) as pipe:
+                               mode=_batch.host_level_mode(),
+                               **({} if kunci_blok is None else {"block_key": kunci_blok})) as pipe:
                 rencana = {"lagi": lagi}
 
                 def isi(slot):
@@ -162,7 +173,12 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
                     rencana["lagi"] -= n
                     return n
 
-                with SlotFeeder(pipe, isi, lambda slot, k, n: pipe.submit_extract(slot, n)) as feeder:
+                def kirim(slot, k, n):
+                    if kunci_blok is None:
+                        return pipe.submit_extract(slot, n)
+                    return pipe.submit_extract(slot, n, first_frame=awal + k * per_batch)
+
+                with SlotFeeder(pipe, isi, kirim) as feeder:
                     for slot, k, n, _ in feeder:
                         packed, n_bits = pipe.extract_result(slot)
                         pieces.append(np.unpackbits(packed, count=n_bits))

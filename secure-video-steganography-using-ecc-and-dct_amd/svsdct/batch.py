@@ -19,7 +19,8 @@ import numpy as np
 
 from . import native
 from .hostmem import pinned_empty
-from .native import Planes
+from .native import BlockOrder, Planes
+from .order import check_key
 
 MAX_AC = 63
 
@@ -114,13 +115,31 @@ def _as_stack(frames: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+def block_order(key, first_frame: int = 0) -> BlockOrder | None:
+    """the C ABI's svs_block_order for a block key (None: no order); raises unless 0 <= key < 2**64 and
+    0 <= first_frame < 2**32"""
+    if key is None:
+        return None
+    first_frame = int(first_frame)
+    if not 0 <= first_frame < (1 << 32):
+        raise ValueError(f"first_frame {first_frame} outside 0 .. 2**32 - 1")
+    return BlockOrder(check_key(key), first_frame, 0)
+
+
+def _order_ref(order: BlockOrder | None):
+    return C.byref(order) if order is not None else None
+
+
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
-                 device: int = 0, mode: str | None = None):
+                 device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
     `bit_offset` is the first one used);  n_bits : bits available from bit_offset (default: rest).
+    block_key : None (the reference's raster order) or an integer key 0 <= key < 2**64: the blocks of each frame take the
+    frame's bits in a keyed order (svsdct/order.py); frame f of the stack is clip frame first_frame + f.
     Returns (stego uint8 [F,H,W], n_embedded)."""
+    order = block_order(block_key, first_frame)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -136,15 +155,24 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     stego = pinned_empty(stack.shape)      # page-locked: the download lands in it by DMA, no staging copy, no page faults
     done = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    rc = lib.svs_embed(stack.ctypes.data, stego.ctypes.data, C.byref(planes), float(delta), int(n_ac),
-                       packed.ctypes.data, int(bit_offset), int(n_bits), mode_flags(mode), C.byref(done))
-    native.check(rc, "svs_embed")
+    if order is None:
+        rc = lib.svs_embed(stack.ctypes.data, stego.ctypes.data, C.byref(planes), float(delta), int(n_ac),
+                           packed.ctypes.data, int(bit_offset), int(n_bits), mode_flags(mode), C.byref(done))
+        native.check(rc, "svs_embed")
+    else:
+        rc = lib.svs_embed_ordered(stack.ctypes.data, stego.ctypes.data, C.byref(planes), C.byref(order), float(delta),
+                                   int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits), mode_flags(mode),
+                                   C.byref(done))
+        native.check(rc, "svs_embed_ordered")
     return stego, int(done.value)
 
 
-def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None):
-    """Extract the packed bit stream of a stack of gray frames on the GPU.
+def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
+                   first_frame: int = 0):
+    """Extract the packed bit stream of a stack of gray frames on the GPU.  block_key / first_frame: as embed_frames (the
+    sender's key and clip frame index).
     Returns (packed uint8 [ceil(n_bits/8)], n_bits)."""
+    order = block_order(block_key, first_frame)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -153,9 +181,14 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     out = np.zeros(max(4, (cap + 7) // 8 + (-((cap + 7) // 8)) % 4), np.uint8)
     got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    rc = lib.svs_extract(stack.ctypes.data, C.byref(planes), float(delta), int(n_ac), out.ctypes.data,
-                         out.size, mode_flags(mode), C.byref(got))
-    native.check(rc, "svs_extract")
+    if order is None:
+        rc = lib.svs_extract(stack.ctypes.data, C.byref(planes), float(delta), int(n_ac), out.ctypes.data,
+                             out.size, mode_flags(mode), C.byref(got))
+        native.check(rc, "svs_extract")
+    else:
+        rc = lib.svs_extract_ordered(stack.ctypes.data, C.byref(planes), C.byref(order), float(delta), int(n_ac),
+                                     out.ctypes.data, out.size, mode_flags(mode), C.byref(got))
+        native.check(rc, "svs_extract_ordered")
     n = int(got.value)
     return out[: (n + 7) // 8], n
 
@@ -226,24 +259,38 @@ def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: s
 
 # ---- device-pointer level -------------------------------------------------------------------
 def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_packed: int,
-                 bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None) -> int:
-    """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded."""
+                 bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
+                 order: BlockOrder | None = None) -> int:
+    """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
+    native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev."""
     done = C.c_uint64(0)
-    rc = native.load().svs_embed_dev(d_gray, d_stego, C.byref(planes), float(delta), int(n_ac), d_bits_packed,
-                                     int(bit_offset), int(n_bits), mode_flags(mode), C.byref(done),
-                                     stream or None)
-    native.check(rc, "svs_embed_dev")
+    if order is None:
+        rc = native.load().svs_embed_dev(d_gray, d_stego, C.byref(planes), float(delta), int(n_ac), d_bits_packed,
+                                         int(bit_offset), int(n_bits), mode_flags(mode), C.byref(done),
+                                         stream or None)
+        native.check(rc, "svs_embed_dev")
+    else:
+        rc = native.load().svs_embed_ordered_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), float(delta),
+                                                 int(n_ac), d_bits_packed, int(bit_offset), int(n_bits), mode_flags(mode),
+                                                 C.byref(done), stream or None)
+        native.check(rc, "svs_embed_ordered_dev")
     return int(done.value)
 
 
 def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
-                   stream: int = 0, mode: str | None = None) -> int:
-    """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields."""
+                   stream: int = 0, mode: str | None = None, order: BlockOrder | None = None) -> int:
+    """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order: as embed_device."""
     got = C.c_uint64(0)
-    rc = native.load().svs_extract_dev(d_gray, C.byref(planes), float(delta), int(n_ac), d_bits_out,
-                                       int(out_capacity_bytes), mode_flags(mode), C.byref(got),
-                                       stream or None)
-    native.check(rc, "svs_extract_dev")
+    if order is None:
+        rc = native.load().svs_extract_dev(d_gray, C.byref(planes), float(delta), int(n_ac), d_bits_out,
+                                           int(out_capacity_bytes), mode_flags(mode), C.byref(got),
+                                           stream or None)
+        native.check(rc, "svs_extract_dev")
+    else:
+        rc = native.load().svs_extract_ordered_dev(d_gray, C.byref(planes), _order_ref(order), float(delta), int(n_ac),
+                                                   d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got),
+                                                   stream or None)
+        native.check(rc, "svs_extract_ordered_dev")
     return int(got.value)
 
 

@@ -40,9 +40,15 @@ class Planes(C.Structure):
         return cls(n_frames, height, width, 0, width, height * width)
 
 
+class BlockOrder(C.Structure):
+    """struct svs_block_order: the keyed block order of the ordered entry points (include/svsdct.h, svsdct/order.py)"""
+    _fields_ = [("key", C.c_uint64), ("first_frame", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 _u8p = C.c_void_p   # device or host byte pointers are passed as integers / c_void_p
 _u64p = C.POINTER(C.c_uint64)
 _PL = C.POINTER(Planes)
+_BO = C.POINTER(BlockOrder)
 
 # name -> (restype, argtypes); every symbol include/svsdct.h declares
 SIGNATURES = {
@@ -68,6 +74,13 @@ SIGNATURES = {
     "svs_embed": (C.c_int, [_u8p, _u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
     "svs_embed_str": (C.c_int, [_u8p, _u8p, _u8p, _PL, C.c_double, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_extract_str": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_embed_ordered_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                         _u64p, C.c_void_p]),
+    "svs_extract_ordered_dev": (C.c_int, [_u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p,
+                                           C.c_void_p]),
+    "svs_embed_ordered": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                     _u64p]),
+    "svs_extract_ordered": (C.c_int, [_u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_extract_dev": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
     "svs_extract": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_bgr_to_gray_dev": (C.c_int, [_u8p, C.c_int64, C.c_int64, _u8p, _PL, C.c_void_p, C.c_void_p]),

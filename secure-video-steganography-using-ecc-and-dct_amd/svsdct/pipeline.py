@@ -48,9 +48,12 @@ def _device(nbytes: int):
 
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
-                 mode: str | None = None, device: int = 0):
+                 mode: str | None = None, device: int = 0, block_key=None):
+        """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
+        clip index of its batch's first frame."""
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
+        self.block_key = batch.block_order(block_key).key if block_key is not None else None
         native.ensure_device(device)
         self.lib = native.load()
         self.device = device
@@ -98,16 +101,19 @@ class FramePipeline:
     def _planes(self, n_frames: int) -> Planes:
         return Planes.contiguous(n_frames, self.h, self.w)
 
-    def submit_embed(self, slot: int, n_frames: int, bit_offset: int) -> int:
+    def _order(self, first_frame: int):
+        return batch.block_order(self.block_key, first_frame) if self.block_key is not None else None
+
+    def submit_embed(self, slot: int, n_frames: int, bit_offset: int, first_frame: int = 0) -> int:
         """Enqueue H2D -> embed -> D2H for the first n_frames frames of the slot; returns the bits this batch
-        will carry.  Does not wait."""
+        will carry.  Does not wait.  first_frame: clip index of the batch's first frame (keyed block order)."""
         s = self._slots[slot]
         nbytes = n_frames * self.h * self.w
         left = max(0, self._payload_bits - bit_offset)
         native.check(self.lib.svs_memcpy_h2d(s["d_frames"], s["hin_p"], nbytes, s["stream"]), "svs_memcpy_h2d")
         used = batch.embed_device(s["d_frames"].value, s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac,
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
-                                  stream=s["stream"].value, mode=self.mode)
+                                  stream=s["stream"].value, mode=self.mode, order=self._order(first_frame))
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
         return used
@@ -119,12 +125,14 @@ class FramePipeline:
         native.check(self.lib.svs_stream_synchronize(s["stream"]), "svs_stream_synchronize")
         return s["hout"][: s["frames"]]
 
-    def submit_extract(self, slot: int, n_frames: int) -> int:
+    def submit_extract(self, slot: int, n_frames: int, first_frame: int = 0) -> int:
+        """Enqueue H2D -> extract -> D2H of the bits; first_frame: as submit_embed."""
         s = self._slots[slot]
         nbytes = n_frames * self.h * self.w
         native.check(self.lib.svs_memcpy_h2d(s["d_frames"], s["hin_p"], nbytes, s["stream"]), "svs_memcpy_h2d")
         got = batch.extract_device(s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac, s["d_bits"].value,
-                                   self._bits_bytes, stream=s["stream"].value, mode=self.mode)
+                                   self._bits_bytes, stream=s["stream"].value, mode=self.mode,
+                                   order=self._order(first_frame))
         native.check(self.lib.svs_memcpy_d2h(s["hbits_p"], s["d_bits"], (got + 7) // 8, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, got
         return got

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """A/B timing of kernel build variants in ONE process, interleaved rounds (guide rule 24).
 
-usage: python tools/ab_bench.py [--frames 600] [--rounds 15] [--n-ac 3] [--delta 8] [--h 2160 --w 3840] lib1.so lib2.so ...
+usage: python tools/ab_bench.py [--frames 600] [--rounds 15] [--n-ac 3] [--delta 8] [--h 2160 --w 3840] [--key K] lib1.so ...
+--key K: every library is also timed with the keyed block order K (svs_embed_ordered_dev / svs_extract_ordered_dev), keyed
+and unkeyed calls alternated in the same rounds (profiles/block_order_rates.txt).
 Reports median / min kernel time (HIP events on the launch stream) and algorithmic GB/s, and checks that
 every variant produces byte-identical stego frames and extracted bits.
 """
@@ -19,6 +21,7 @@ ap.add_argument("--h", type=int, default=2160); ap.add_argument("--w", type=int,
 ap.add_argument("--mode", default="fast", choices=["fast", "guarded", "exact"])
 ap.add_argument("--env-sweep", default="", help="NAME=v1,v2,...: sweep one environment knob on the first lib - which must be "
                 "lib/variants/libsvsdct_exp.so (make -C csrc exp): the product library reads no environment variable")
+ap.add_argument("--key", type=lambda x: int(x, 0), default=None, help="also time the keyed block order with this key")
 ap.add_argument("libs", nargs="+")
 a = ap.parse_args()
 FLAGS = {"fast": 0, "exact": 1, "guarded": 2}[a.mode]       # SVS_EXACT_POCKETFFT = 1, SVS_EXACT_GUARDED = 2
@@ -37,6 +40,9 @@ libs = [(os.path.basename(p).replace("libsvsdct", "").replace(".so", "") or "bas
 if a.env_sweep:
     _name, _vals = a.env_sweep.split("=")
     libs = [(f"{_name}={v}", libs[0][1], v) for v in _vals.split(",")]
+if a.key is not None:
+    libs = [v for name, lib, env_value in libs for v in ((name, lib, env_value), (name + "+key", lib, env_value))]
+ORDER = native.BlockOrder(a.key or 0, 0, 0)
 dev = torch.device("cuda", 0); torch.cuda.set_device(0)
 F, H, W, n = a.frames, a.h, a.w, a.n_ac
 planes = Planes.contiguous(F, H, W)
@@ -56,11 +62,20 @@ for r in range(a.rounds + 2):
         if env_value is not None:
             os.environ[_name] = env_value
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        keyed = name.endswith("+key")
         e[0].record()
-        rc = lib.svs_embed_dev(gray.data_ptr(), stego.data_ptr(), C.byref(planes), a.delta, n, pay.data_ptr(), 0, cap, FLAGS, C.byref(done), st)
+        if keyed:
+            rc = lib.svs_embed_ordered_dev(gray.data_ptr(), stego.data_ptr(), C.byref(planes), C.byref(ORDER), a.delta, n, pay.data_ptr(),
+                                           0, cap, FLAGS, C.byref(done), st)
+        else:
+            rc = lib.svs_embed_dev(gray.data_ptr(), stego.data_ptr(), C.byref(planes), a.delta, n, pay.data_ptr(), 0, cap, FLAGS, C.byref(done), st)
         assert rc == 0, lib.svs_last_error()
         e[1].record()
-        rc = lib.svs_extract_dev(stego.data_ptr(), C.byref(planes), a.delta, n, ext.data_ptr(), ext.numel(), FLAGS, C.byref(done), st)
+        if keyed:
+            rc = lib.svs_extract_ordered_dev(stego.data_ptr(), C.byref(planes), C.byref(ORDER), a.delta, n, ext.data_ptr(), ext.numel(),
+                                             FLAGS, C.byref(done), st)
+        else:
+            rc = lib.svs_extract_dev(stego.data_ptr(), C.byref(planes), a.delta, n, ext.data_ptr(), ext.numel(), FLAGS, C.byref(done), st)
         assert rc == 0, lib.svs_last_error()
         e[2].record()
         torch.cuda.synchronize()
