@@ -93,6 +93,23 @@ extern "C" {
  * the reference's bits; blocks past the payload budget and pixels whose gray did not change are the cover's bytes.  The
  * default (flag clear) is still the reference's COLOR_GRAY2BGR output, byte for byte. */
 #define SVS_KEEP_COLOUR 0x100u
+/* SVS_READBACK (the gray embed calls: svs_embed_dev, svs_embed, svs_embed_str, svs_embed_ordered_dev, svs_embed_ordered and
+ * the svs_embed_readback* calls below; the extract calls and the fused colour calls reject it with SVS_ERR_INVALID_ARG -
+ * colour support is follow-up work): opt-in.  The reference's own stego can fail to decode: it clips the inverse transform to
+ * [0, 255] and truncates it (config_and_setup.py:166-171), and in blocks near black or white (letterbox bars, flat or
+ * saturated areas) that moves payload coefficients across a decision boundary - one wrong bit makes the receiver's AES-GCM
+ * reject the whole payload.  With the flag the call first produces exactly the stego it produces without it, then reads
+ * every block that carries payload bits back with the exact extraction arithmetic (the block the budget ends in: its first
+ * bits only).  A block that reads back keeps its bytes - on content without failures the output is byte-identical to the
+ * call without the flag.  A block that does not is repaired in place by a bounded, deterministic search (csrc/svs_readback.hpp:
+ * over-relaxed corrections towards the nearest lattice point of each wanted bit, the block shifted off 0 / 255 where its range
+ * allows, rounded to nearest, at most 16 steps) and accepted only when the exact read-back confirms every one of its bits; a
+ * block the search cannot repair keeps the reference's bytes and is counted.  Repaired blocks are no longer the reference's
+ * pixels (a letterbox bar is lifted off 0: visibly lighter blocks, lower PSNR), which is why the flag is opt-in.  What the
+ * search leaves: blocks that clip at both ends (no shift helps) and small delta (delta = 4, n_ac = 3: a few blocks per
+ * frame); at small delta it can also overshoot, and a few accepted blocks per frame decode but are visibly destroyed.  The receiver is unchanged: any extract call decodes the result.  The call needs the reference's stego as its start
+ * and not the cover, so in-place calls keep working.  Only svs_embed_readback* report the counts. */
+#define SVS_READBACK 0x200u
 
 /* Geometry of a batch of gray planes. */
 typedef struct svs_planes {
@@ -246,6 +263,24 @@ int svs_embed_ordered(const uint8_t *gray, uint8_t *stego, const svs_planes *pla
 int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta,
                         int n_ac, uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
                         uint64_t *n_bits_out);
+
+/* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
+ * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:
+ *   d_counts : NULL, or a device buffer of two uint64 (8-byte aligned) that the call ADDS {blocks repaired, blocks left
+ *              unrepaired} into, on the call's stream.
+ *   counts   : NULL, or receives the counts of the whole call when it returns (every staging chunk included). */
+typedef struct svs_readback_counts {
+    uint64_t repaired;     /* blocks that did not read back and were repaired */
+    uint64_t unrepaired;   /* blocks that did not read back and kept the reference's bytes */
+} svs_readback_counts;
+
+int svs_embed_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                           double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                           uint32_t flags, uint64_t *n_embedded, uint64_t *d_counts, void *stream);
+
+int svs_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order, double delta,
+                       int n_ac, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                       uint64_t *n_embedded, svs_readback_counts *counts);
 
 /* ---- colour plumbing around the operator (device resident) --------------------------------------------
  * Interleaved 8-bit BGR frames [frame][row][col][3] <-> gray planes.  bgr_row_pitch / bgr_frame_pitch in bytes,

@@ -236,6 +236,26 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
     });
 }
 
+// SVS_READBACK: readback_kernel<rows, QM> over the stego planes the embed has just written, on the same stream, with the
+// embed's payload arguments (the plan's rows are 1 or 2 for n <= 15, else 8: the quantiser loop's coefficient rows)
+int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uint8_t *stego, svs::Geometry g, const uint32_t *bits,
+                    uint64_t *counts, const svs::BlockOrderArgs &ord) {
+    g.n_ac = p.n_ac;
+    g.xcd_chunk = svs::kEighth;
+    const uint32_t words = (uint32_t)p.n_words;
+    auto *c = reinterpret_cast<unsigned long long *>(counts);
+    return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
+        constexpr int QM = decltype(qm)::value;
+        return dispatch<1, 2, 8>(p.rows, [&](auto u) {
+            constexpr int U = decltype(u)::value;
+            if (p.keyed)
+                return launch(svs::readback_kernel<U, QM, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
+                              p.bit_offset, p.n_bits, words, c, ord);
+            return launch(svs::readback_kernel<U, QM>, grid_for(total), 0, st, stego, g, p.qp, bits, p.bit_offset, p.n_bits, words, c);
+        });
+    });
+}
+
 // svs_embed_bgr_dev's plan: embed_bgr_kernel<8, QM, true> (exact, round trip) or <1 | 2, QM, false> (streaming, convert)
 int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStream_t st, const uint8_t *in, uint8_t *out,
                      uint8_t *ref, svs::Geometry g, const svs::ColourParams &c, const uint32_t *bits) {
@@ -679,10 +699,13 @@ svs::BlockOrderArgs order_args(const svs_block_order *order, const svs::Geometry
     return order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{};
 }
 
-// svs_embed_dev and svs_embed_ordered_dev (order NULL: the call without an order)
+constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_READBACK;
+
+// svs_embed_dev, svs_embed_ordered_dev (order NULL: the call without an order) and svs_embed_readback_dev (d_counts: the
+// read-back counts, device, added to; NULL for none)
 int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order, double delta,
               int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-              uint64_t *n_embedded, void *stream) {
+              uint64_t *n_embedded, void *stream, uint64_t *d_counts = nullptr) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
@@ -694,19 +717,22 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
         return fail(SVS_ERR_INVALID_ARG, "plane pointers must be 8-byte aligned");
     svs::RouteArgs ra = route_args(delta, g, total, n_bits, bit_offset, flags, false);
     ra.keyed = order != nullptr;
+    ra.readback = (flags & SVS_READBACK) != 0;
     const svs::EmbedPlan p = svs::plan_embed(ra);
     if (p.use > 0) {
         if (!d_bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
         if ((uintptr_t)d_bits_packed % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
         if (bit_offset + p.use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
     }
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (flags & ~kGrayEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (d_counts && ((uintptr_t)d_counts % 8)) return fail(SVS_ERR_INVALID_ARG, "counts pointer must be 8-byte aligned");
     if (p.n_words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
     if (p.path == EmbedPath::COPY && d_gray == d_stego) return SVS_OK;
     const bool two = p.two_blocks && rows_allow_two_blocks(planes, d_gray, d_stego);
-    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g,
-                              p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr, order_args(order, g)))
-        return rc;
+    const uint32_t *bits = p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr;
+    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g, bits, order_args(order, g))) return rc;
+    if (p.readback && p.use > 0)
+        if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, d_counts, order_args(order, g))) return rc;
     if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
 }
@@ -718,6 +744,7 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (int rc = check_order(order)) return rc;
+    if (flags & SVS_READBACK) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK is an embed flag");
     if (cap == 0) return SVS_OK;
     if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
@@ -783,17 +810,19 @@ static void copy_gray_reference(uint8_t *dst, const uint8_t *gray, const svs_pla
 // svs_embed (payload = packed MSB-first bits, indexed by bit_offset) and svs_embed_str (payload = n_bits '0' / '1' characters,
 // bit_offset = 0) share everything but the way the payload reaches the device
 // (svs_embed_ordered: a packed payload and an order)
+// (svs_embed_readback: counts receives the read-back counts; the other calls pass NULL)
 static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out, const svs_planes *planes, double delta, int n_ac,
                       const uint8_t *bits_packed, const char *bits_ascii, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-                      uint64_t *n_embedded, const svs_block_order *order = nullptr) {
+                      uint64_t *n_embedded, const svs_block_order *order = nullptr, svs_readback_counts *counts = nullptr) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
+    if (counts) *counts = svs_readback_counts{0, 0};
     if (int rc = check_order(order)) return rc;
     if (total == 0) return SVS_OK;
     if (!gray || !stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (flags & ~kGrayEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
     const uint64_t span = span_bytes(planes);
     const uint64_t cap = total * (uint64_t)g.n_ac;
     uint64_t use = n_bits < cap ? n_bits : cap;
@@ -808,21 +837,25 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
     // download lands in the source (a pageable download blocks)
     const bool ref_first = gray_ref_out && gray_ref_out != gray && ranges_overlap(gray, stego, span);
     uint64_t done_total = 0;
-    if (int rc = staged(span, 0, payload.ascii_bytes(), payload.bits_bytes(), [&](HostStage &c) {
+    // the read-back counts of the whole call: two u64 in c.bits behind the payload, cleared before the first chunk, added to by
+    // every chunk's readback_kernel, downloaded after the last
+    const bool readback = counts && (flags & SVS_READBACK);
+    const size_t counts_at = (payload.bits_bytes() + 7) & ~(size_t)7;
+    uint64_t got_counts[2] = {0, 0};
+    if (int rc = staged(span, 0, payload.ascii_bytes(), readback ? counts_at + 16 : payload.bits_bytes(), [&](HostStage &c) {
             uint64_t rebased = 0;
             if (int rc = payload.stage(c, &rebased)) return rc;
+            uint64_t *d_counts = readback ? reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c.bits.p) + counts_at) : nullptr;
+            if (d_counts) SVS_HIP(hipMemsetAsync(d_counts, 0, 16, c.st[0]));
             if (ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
             uint8_t *d = static_cast<uint8_t *>(c.frames.p);
             const int rc = embed_chunks(
                 c, planes, 1, gray, g.n_ac, use, n_bits, rebased,
                 [&](const svs_planes &sub, int64_t off, int32_t f0, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
-                    if (order) {   // whole frames: the chunk's first frame is clip frame order->first_frame + f0
-                        const svs_block_order o{order->key, order->first_frame + (uint32_t)f0, 0u};
-                        return embed_dev(d + off, d + off, &sub, &o, delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset,
-                                         budget, flags, done, up);
-                    }
-                    return svs_embed_dev(d + off, d + off, &sub, delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset,
-                                         budget, flags, done, up);
+                    // keyed: whole frames - the chunk's first frame is clip frame order->first_frame + f0
+                    const svs_block_order o{order ? order->key : 0u, order ? order->first_frame + (uint32_t)f0 : 0u, 0u};
+                    return embed_dev(d + off, d + off, &sub, order ? &o : nullptr, delta, n_ac, static_cast<const uint8_t *>(c.bits.p),
+                                     chunk_offset, budget, flags, done, up, d_counts);
                 },
                 [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {
                     // back: pixel bytes only (padding in the caller's stego buffer is left alone)
@@ -840,6 +873,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                     return (int)SVS_OK;
                 },
                 &done_total, order != nullptr);
+            if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, 16, hipMemcpyDeviceToHost, c.st[0]));
             // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
             // thread would only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first.)
             if (!rc && gray_ref_out && gray_ref_out != gray && !ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
@@ -847,6 +881,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
         }))
         return rc;
     if (n_embedded) *n_embedded = done_total;
+    if (readback) *counts = svs_readback_counts{got_counts[0], got_counts[1]};
     return SVS_OK;
 }
 
@@ -859,6 +894,21 @@ int svs_embed_ordered(const uint8_t *gray, uint8_t *stego, const svs_planes *pla
                       int n_ac, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                       uint64_t *n_embedded) {
     return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded, order);
+}
+
+int svs_embed_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                           double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                           uint32_t flags, uint64_t *n_embedded, uint64_t *d_counts, void *stream) {
+    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK, n_embedded,
+                     stream, d_counts);
+}
+
+int svs_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order, double delta,
+                       int n_ac, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                       uint64_t *n_embedded, svs_readback_counts *counts) {
+    svs_readback_counts none;
+    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags | SVS_READBACK,
+                      n_embedded, order, counts ? counts : &none);
 }
 
 // every character '0' or '1'?  One OR-reduction over the bytes (vectorised: about 0.05 ms per million characters)
@@ -899,6 +949,7 @@ int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (int rc = check_order(order)) return rc;
+    if (flags & SVS_READBACK) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK is an embed flag");
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     const uint64_t bytes = (cap + 7) / 8;
@@ -916,6 +967,7 @@ int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta,
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
+    if (flags & SVS_READBACK) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK is an embed flag");
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_ascii_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if (int rc = check_capacity(cap, out_capacity_chars, "characters")) return rc;

@@ -8,6 +8,7 @@
 #include "svs_block.hpp"
 #include "svs_colour.hpp"
 #include "svs_order.hpp"
+#include "svs_readback.hpp"
 
 namespace svs {
 
@@ -902,6 +903,177 @@ __global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__
     }
     if constexpr (!KEYED)
         emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
+}
+
+// ---------------------------------------------------------------------------------------
+// READ-BACK pass (SVS_READBACK, include/svsdct.h): launched on the call's stream after the embed kernel, in place on the
+// stego planes.
+//   check   one lane per block, each block read once: lanes whose block carries payload bits (the block's slot with a keyed
+//           order, as the ordered embed kernels map it) read it back with the exact extraction arithmetic against the same
+//           payload words the embed used (svs_readback.hpp readback_block_ok: extract_exact_kernel's forward transform on
+//           the payload rows).  A block that reads back is not written.  Waves without a failing block end after a ballot.
+//   repair  the wave's failing blocks are compacted into a wave-private LDS worklist (ballot + mbcnt: their rows and
+//           payload window, SVS_RB_CAP per round); the whole wave then repairs them eight lanes per block (repair8: lane r
+//           transforms column r and row r, the block's lines meet in an LDS tile) - eight blocks at a time.  Owners of repaired blocks read
+//           the accepted rows back and store them; an unrepaired block is not written (the reference's bytes stay).
+// Counts: one 64-bit atomic per wave and kind into counts[0] (repaired) / counts[1] (left unrepaired), NULL for none.
+// ---------------------------------------------------------------------------------------
+#define SVS_RB_SLOT 16   // dwords of a worklist entry's rows: row y = (dword 2y, dword 2y + 1)
+#define SVS_RB_CAP 32    // worklist entries per wave and round (18 KB of LDS per workgroup in all: eight workgroups per CU)
+
+__device__ __forceinline__ uint32_t group8_or(uint32_t v) {
+    v |= (uint32_t)__shfl_xor((int)v, 1, 64);
+    v |= (uint32_t)__shfl_xor((int)v, 2, 64);
+    return v | (uint32_t)__shfl_xor((int)v, 4, 64);
+}
+__device__ __forceinline__ float group8_min(float v) {
+    v = fminf(v, __shfl_xor(v, 1, 64));
+    v = fminf(v, __shfl_xor(v, 2, 64));
+    return fminf(v, __shfl_xor(v, 4, 64));
+}
+__device__ __forceinline__ float group8_max(float v) {
+    v = fmaxf(v, __shfl_xor(v, 1, 64));
+    v = fmaxf(v, __shfl_xor(v, 2, 64));
+    return fmaxf(v, __shfl_xor(v, 4, 64));
+}
+
+// pocketfft's forward transform of the block in `px` from eight lanes: lane r transforms pixel column r, then coefficient
+// row r (forward_exact's operations, per line) -> c = coefficient row r.  t: the group's 64-float tile.
+__device__ __forceinline__ void forward8(const uint32_t *px, float *t, uint32_t r, float (&c)[8]) {
+    float col[8], out[8];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) col[y] = (float)((px[2 * y + (r >> 2)] >> (8 * (r & 3))) & 0xffu);
+    pf::dct2_8(col, out);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[8 * u + r] = out[u];
+    wave_lds_fence();
+    float row[8];
+#pragma unroll
+    for (int x = 0; x < 8; ++x) row[x] = t[8 * r + x];
+    wave_lds_fence();
+    pf::dct2_8(row, c);
+}
+
+// svs_readback.hpp repair_block on eight lanes (r = 0..7) of one worklist entry: px = its rows in LDS (in: the reference's
+// stego; out: the last iterate), t = the group's tile.  The same operations on the same values, so the same bytes; true (in
+// all eight lanes) when an iterate read back.
+template <int QM>
+__device__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+    float c[8], T[8];
+    forward8(px, t, r, c);
+    repair_targets_row<QM>(c, (int)r, nb, hi, lo, qp, T);
+#pragma unroll 1
+    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
+        const float scale = 1.0f + 0.5f * (float)it;
+        float d[8], col[8], out[8], row[8], y[8];
+        repair_correction_row(T, c, (int)r, nb, scale, d);
+#pragma unroll
+        for (int x = 0; x < 8; ++x) t[8 * r + x] = d[x];            // coefficient row r
+        wave_lds_fence();
+#pragma unroll
+        for (int u = 0; u < 8; ++u) col[u] = t[8 * u + r];          // coefficient column r
+        wave_lds_fence();
+        pf::dct3_8(col, out);                                        // -> column r of P
+#pragma unroll
+        for (int v = 0; v < 8; ++v) t[8 * v + r] = out[v];
+        wave_lds_fence();
+#pragma unroll
+        for (int x = 0; x < 8; ++x) col[x] = t[8 * r + x];          // row r of P
+        wave_lds_fence();
+        pf::dct3_8(col, row);
+        float mn = 1e30f, mx = -1e30f;
+        repair_add_row(px[2 * r], px[2 * r + 1], row, y, mn, mx);
+        const float s = repair_shift(group8_min(mn), group8_max(mx));
+        uint32_t lo4, hi4;
+        repair_store_row(y, s, lo4, hi4);
+        px[2 * r] = lo4;
+        px[2 * r + 1] = hi4;
+        wave_lds_fence();
+        forward8(px, t, r, c);
+        if (group8_or(row_misses<QM>(c, (int)r, nb, hi, lo, qp) ? 1u : 0u) == 0) return true;
+    }
+    return false;
+}
+
+template <int U, int QM, bool KEYED = false, class... Order>
+__global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const Geometry g, const QimParams qp,
+                                                         const uint32_t *__restrict__ bits, const uint64_t bit_offset,
+                                                         const uint64_t n_bits, const uint32_t n_words,
+                                                         unsigned long long *counts, const Order... order) {
+    static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
+    __shared__ uint32_t slots[SVS_WG / 64][SVS_RB_CAP * SVS_RB_SLOT];
+    __shared__ u32x4 meta[SVS_WG / 64][SVS_RB_CAP];
+    __shared__ float tiles[SVS_WG / 64][8 * 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
+    const uint32_t n = g.n_ac;
+    uint32_t nb = 0;
+    uint64_t first = 0;
+    if (gblock < g.total_blocks) {
+        first = stream_first<KEYED>(gblock, n, g, order_arg(order...));
+        nb = block_budget(first, n_bits, n);
+    }
+    if (__ballot(nb > 0) == 0) return;   // wave-uniform
+    bool bad = false;
+    int64_t off = 0;
+    u32x2 v[8];
+    uint32_t hi = 0, lo = 0;
+    if (nb > 0) {
+        off = block_offset(gblock, g);
+        load_rows<1>(stego + off, g.row_pitch, v);
+        uint32_t ax[8], ay[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
+        payload_window(bits, n_words, bit_offset + first, hi, lo);
+        bad = !readback_block_ok<U, QM>(ax, ay, nb, hi, lo, qp);
+    }
+    const uint64_t mask = __ballot(bad);
+    if (mask == 0) return;               // wave-uniform: content without failures
+    const uint32_t total = (uint32_t)__popcll(mask);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    uint32_t *wslots = &slots[wave][0];
+    u32x4 *wmeta = &meta[wave][0];
+    const uint32_t grp = lane >> 3, r = lane & 7u;
+    uint32_t status = 0;
+#pragma unroll 1
+    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries
+        const bool mine = bad && rank >= base && rank < base + SVS_RB_CAP;
+        if (mine) {   // the rows are read again (the block's own bytes, still unwritten): no registers held across rounds
+            load_rows<1>(stego + off, g.row_pitch, v);
+            uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
+#pragma unroll
+            for (int y = 0; y < 8; ++y) { e[2 * y] = v[y].x; e[2 * y + 1] = v[y].y; }
+            u32x4 m; m.x = hi; m.y = lo; m.z = nb; m.w = 0u;
+            wmeta[rank - base] = m;
+        }
+        wave_lds_fence();
+        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
+#pragma unroll 1
+        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time
+            const uint32_t idx = at + grp;
+            if (idx < count) {
+                const u32x4 m = wmeta[idx];
+                const bool ok = repair8<QM>(wslots + idx * SVS_RB_SLOT, &tiles[wave][64 * grp], r, m.z, m.x, m.y, qp);
+                if (r == 0) wmeta[idx].w = ok ? 1u : 2u;
+            }
+            wave_lds_fence();
+        }
+        if (mine) {
+            status = wmeta[rank - base].w;
+            if (status == 1) {
+                const uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
+#pragma unroll
+                for (int y = 0; y < 8; ++y) { v[y].x = e[2 * y]; v[y].y = e[2 * y + 1]; }
+                store_rows<1>(stego + off, g.row_pitch, v);
+            }
+        }
+        wave_lds_fence();
+    }
+    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
+    if (counts && lane == 0) {
+        if (rep) atomicAdd(&counts[0], (unsigned long long)__popcll(rep));
+        if (left) atomicAdd(&counts[1], (unsigned long long)__popcll(left));
+    }
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1,0 +1,203 @@
+// svs_readback.hpp - per-block arithmetic of the opt-in read-back pass (SVS_READBACK, include/svsdct.h): read a stego block
+// back with the reference's extraction arithmetic and, where its payload bits do not come back, search for a block whose
+// bits do.  Plain C++ on register values, like svs_block.hpp: csrc/svs_device.hpp checks one block per lane and repairs
+// one block on eight lanes with the per-line steps below (readback_kernel, repair8); tests/readback builds the one-lane
+// form with g++ for the CPU tier.  Both builds use -ffp-contract=off; the repair
+// rounds to nearest after float arithmetic, so host and device must execute the same operations in the same order: the
+// transforms are svs_block.hpp's pocketfft replays (their fmaf only where it is exact), every other operation below is one
+// IEEE float32 operation (no FMA), and min / max and the final rounding are exact.
+//
+// Why a block fails: the reference clips the inverse transform to [0, 255] and truncates it (config_and_setup.py:166-171).
+// In a block near black or white the clipping - and anywhere the truncation - moves payload coefficients, and one moved
+// across a QIM decision boundary reads back as the wrong bit.  The receiver only sees uint8 pixels, so the sender may store
+// any block that the reference's extraction decodes to the right bits; the receiver stays as it is.
+#pragma once
+#include <stdint.h>
+
+#include "svs_block.hpp"
+
+namespace svs {
+
+#define SVS_READBACK_ITERS 16   // repair iterations per block (each: one correction, one exact read-back)
+
+// the first nb bits of the MSB-first window hi:lo as a mask pair
+SVS_HD void readback_mask(uint32_t nb, uint32_t &mhi, uint32_t &mlo) {
+    mhi = nb >= 32 ? 0xffffffffu : (nb == 0 ? 0u : 0xffffffffu << (32 - nb));
+    mlo = nb <= 32 ? 0u : (nb >= 64 ? 0xffffffffu : 0xffffffffu << (64 - nb));
+}
+
+// do the first nb payload coefficients of the pocketfft coefficients D carry the window's bits?  The quantiser is the
+// extraction's (config_and_setup.py:160-161; QM_DOUBLE divides as QM_F32 does)
+template <int U, int QM>
+SVS_HD bool readback_bits_ok(const float (&D)[8][8], uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+    uint32_t h = 0, l = 0;
+#pragma unroll
+    for (int k = 1; k < 8 * U; ++k) {
+        if ((uint32_t)k <= nb) {
+            const uint32_t bit = (uint32_t)quant_index<QM>(D[k >> 3][k & 7], qp) & 1u;
+            const int i = k - 1;
+            if (i < 32) h |= bit << ((31 - i) & 31);
+            else l |= bit << ((63 - i) & 31);
+        }
+    }
+    uint32_t mhi, mlo;
+    readback_mask(nb, mhi, mlo);
+    return ((h ^ hi) & mhi) == 0 && ((l ^ lo) & mlo) == 0;
+}
+
+// the read-back of one block with the extraction's own arithmetic - the reference's bits for any input - only the first nb
+// coefficients compared.  Two coefficient rows (n = 8..15): FAST extraction's FMA-factored forward with its proven tie margin
+// (svs_block.hpp extract_block), the block redone with the pocketfft-identical transform when a quantiser input lies within
+// the margin of a tie.  One row, and eight (its FAST form needs 203 instead of 144 VGPRs): extract_block_exact's
+// pocketfft-identical forward transform.
+template <int U, int QM>
+SVS_HD bool readback_block_ok(const uint32_t (&rx)[8], const uint32_t (&ry)[8], uint32_t nb, uint32_t hi, uint32_t lo,
+                              const QimParams &qp) {
+    if (U == 2 && qp.delta_f >= SVS_FAST_EXTRACT_DELTA_MIN) {
+        uint32_t h, l;
+        if (!extract_block<U, QM>(rx, ry, nb, qp, h, l)) {
+            uint32_t mhi, mlo;
+            readback_mask(nb, mhi, mlo);
+            return ((h ^ hi) & mhi) == 0 && ((l ^ lo) & mlo) == 0;
+        }
+    }
+    float D[8][8];
+    forward_exact(rx, ry, D);
+    return readback_bits_ok<U, QM>(D, nb, hi, lo, qp);
+}
+
+// Repair of a block that does not read back (rx / ry: its stego rows, in and out).  Bounded and deterministic:
+//   target  T_k = the lattice point q' delta of the wanted parity nearest to the block's coefficient c_k (k = 1..nb): the
+//           centre of the nearest decision cell that gives the bit
+//   step    for it = 0 .. SVS_READBACK_ITERS - 1:
+//             y = X + IDCT((T - c) * (1 + it / 2))        (over-relaxed: without it, rounding absorbs corrections below half
+//                                                          a grey level and the search stalls)
+//             y += s, one constant that lifts the block off 0 or lowers it below 255 where its range allows (a constant
+//                                                          only moves DC, which carries no payload)
+//             X = clip(round-half-even(y), 0, 255);  c = the exact forward coefficients of X
+//             accept when c reads back every bit (the exact read-back above)
+// The gain grows with `it` and X moves from the previous iterate, so the search can also overshoot: at small delta (4) and
+// at n = 63 on high-contrast blocks an accepted iterate can be far from the reference's block.  Those blocks do decode;
+// tests/test_readback_cpu.py measures how many there are.
+// The search is written per LINE of the block (coefficient row u, pixel row y) so that the device can run one block on
+// eight lanes (csrc/svs_device.hpp repair8) with exactly these operations: the transforms between the steps are
+// pocketfft's per line, the min / max over the block and the shift are exact.  repair_block below is the one-lane form.
+
+// targets of coefficient row u (flat indices 8u .. 8u + 7; only 1 .. nb are used)
+template <int QM>
+SVS_HD void repair_targets_row(const float (&c)[8], int u, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp,
+                               float (&T)[8]) {
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const int k = 8 * u + v;
+        T[v] = 0.0f;
+        if (k >= 1 && (uint32_t)k <= nb) {
+            const int bit = (int)window_bit(hi, lo, k - 1);
+            int q = quant_index<QM>(c[v], qp);
+            if ((q & 1) != bit) q = c[v] * qp.inv_delta_f >= (float)q ? q + 1 : q - 1;
+            T[v] = (float)q * qp.delta_f;
+        }
+    }
+}
+
+// the over-relaxed correction of coefficient row u
+SVS_HD void repair_correction_row(const float (&T)[8], const float (&c)[8], int u, uint32_t nb, float scale, float (&d)[8]) {
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const int k = 8 * u + v;
+        d[v] = (k >= 1 && (uint32_t)k <= nb) ? (T[v] - c[v]) * scale : 0.0f;
+    }
+}
+
+// does coefficient row u miss a payload bit?
+template <int QM>
+SVS_HD bool row_misses(const float (&c)[8], int u, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+    bool miss = false;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const int k = 8 * u + v;
+        if (k >= 1 && (uint32_t)k <= nb)
+            miss |= ((uint32_t)quant_index<QM>(c[v], qp) & 1u) != window_bit(hi, lo, k - 1);
+    }
+    return miss;
+}
+
+// pixel row (8 bytes in lo4 / hi4) plus the inverse transform's row: the float pixels y, and their min / max folded in
+SVS_HD void repair_add_row(uint32_t lo4, uint32_t hi4, const float (&row)[8], float (&y)[8], float &mn, float &mx) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+        const float a = (float)((lo4 >> (8 * x)) & 0xffu) + row[x];
+        const float b = (float)((hi4 >> (8 * x)) & 0xffu) + row[4 + x];
+        y[x] = a;
+        y[4 + x] = b;
+        mn = fminf(mn, fminf(a, b));
+        mx = fmaxf(mx, fmaxf(a, b));
+    }
+}
+
+// the constant that takes the block off 0 / below 255 where its range allows
+SVS_HD float repair_shift(float mn, float mx) {
+    const float span = mx - mn;
+    if (mn < 0.0f && span <= 255.0f) return -mn;
+    if (mx > 255.0f && span <= 255.0f) return 255.0f - mx;
+    return 0.0f;
+}
+
+// shifted, rounded to nearest and clipped: the row's new bytes
+SVS_HD void repair_store_row(const float (&y)[8], float s, uint32_t &lo4, uint32_t &hi4) {
+    uint32_t a = 0, b = 0;
+    a = put_pixel_rne<0>(y[0] + s, a); a = put_pixel_rne<1>(y[1] + s, a);
+    a = put_pixel_rne<2>(y[2] + s, a); a = put_pixel_rne<3>(y[3] + s, a);
+    b = put_pixel_rne<0>(y[4] + s, b); b = put_pixel_rne<1>(y[5] + s, b);
+    b = put_pixel_rne<2>(y[6] + s, b); b = put_pixel_rne<3>(y[7] + s, b);
+    lo4 = a;
+    hi4 = b;
+}
+
+// the one-lane form (host emulation; the device repairs with eight lanes per block)
+template <int U, int QM>
+SVS_HD bool repair_block(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+    float c[8][8], T[8][8];
+    forward_exact(rx, ry, c);
+    for (int u = 0; u < 8; ++u) repair_targets_row<QM>(c[u], u, nb, hi, lo, qp, T[u]);
+    uint32_t px[8], py[8];
+    for (int r = 0; r < 8; ++r) { px[r] = rx[r]; py[r] = ry[r]; }
+    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
+        const float scale = 1.0f + 0.5f * (float)it;   // exact
+        // the correction's inverse transform: columns (axis 0) first, then rows, as the reference inverts
+        float d[8][8], P[8][8], Y[8][8];
+        for (int u = 0; u < 8; ++u) repair_correction_row(T[u], c[u], u, nb, scale, d[u]);
+        for (int x = 0; x < 8; ++x) {
+            float col[8], out[8];
+            for (int u = 0; u < 8; ++u) col[u] = d[u][x];
+            pf::dct3_8(col, out);
+            for (int y = 0; y < 8; ++y) P[y][x] = out[y];
+        }
+        float mn = 1e30f, mx = -1e30f;
+        for (int y = 0; y < 8; ++y) {
+            float row[8];
+            pf::dct3_8(P[y], row);
+            repair_add_row(px[y], py[y], row, Y[y], mn, mx);
+        }
+        const float s = repair_shift(mn, mx);
+        for (int y = 0; y < 8; ++y) repair_store_row(Y[y], s, px[y], py[y]);
+        forward_exact(px, py, c);
+        bool miss = false;
+        for (int u = 0; u < U; ++u) miss |= row_misses<QM>(c[u], u, nb, hi, lo, qp);
+        if (!miss) {
+            for (int r = 0; r < 8; ++r) { rx[r] = px[r]; ry[r] = py[r]; }
+            return true;
+        }
+    }
+    return false;
+}
+
+// The whole per-block step of the read-back pass: 0 = the block reads back (untouched), 1 = repaired in place, 2 = could not
+// be repaired (untouched: the reference's stego block stays)
+template <int U, int QM>
+SVS_HD uint32_t readback_step(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+    if (readback_block_ok<U, QM>(rx, ry, nb, hi, lo, qp)) return 0;
+    return repair_block<U, QM>(rx, ry, nb, hi, lo, qp) ? 1u : 2u;
+}
+
+}  // namespace svs

@@ -24,6 +24,7 @@ struct RouteArgs {
     bool guarded_off;         // reaches the gray calls only
     float guard_scale, tie_scale;
     bool keyed = false;       // a keyed block order (svs_embed_ordered_dev / svs_extract_ordered_dev; gray calls only)
+    bool readback = false;    // SVS_READBACK (gray embed calls only)
 };
 
 // COPY: nothing to embed and an empty payload - the reference's loops break before the first block.  Gray: a byte copy through
@@ -41,6 +42,7 @@ struct EmbedPlan {
     int rows;                 // coefficient rows of the instantiation (EXACT / ROUND_TRIP: the U of the exact kernel)
     bool two_blocks;          // embed_row1_kernel may take two blocks per lane where the buffers allow it
     bool keyed;               // the KEYED instantiation of the family (STREAMING / EXACT only: the other paths do not depend on order)
+    bool readback;            // SVS_READBACK: readback_kernel follows the embed (only when payload bits are embedded)
     uint32_t n_ac;            // Geometry::n_ac of the launch
     uint32_t xcd_chunk;
     QimParams qp;
@@ -73,6 +75,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.rows = streaming || (!a.bgr && rows <= 2) ? rows : 8;
         p.two_blocks = streaming && !a.bgr && rows == 1;
         p.keyed = a.keyed;
+        p.readback = a.readback;
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;

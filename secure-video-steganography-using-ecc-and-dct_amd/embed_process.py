@@ -38,6 +38,12 @@ KEEP_COLOUR = os.environ.get("SVS_KEEP_COLOUR", "0") == "1"
 # that fills part of a frame is spread over all of it.  The receiver needs the same key.  Unset: the reference's order, byte
 # for byte.  Not with SVS_KEEP_COLOUR (the fused colour kernels have no keyed form: refused); with SVS_FUSED_COLOUR the
 # host-conversion gray path runs.
+# SVS_READBACK=1 (opt-in): every frame block that carries payload is read back with the reference's extraction, and a block
+# that the reference's clipping or truncation made unreadable (letterbox bars, flat black or white areas) is repaired
+# (SVS_READBACK, include/svsdct.h) - otherwise one such block makes the receiver's AES-GCM reject the payload.  Repaired blocks
+# are no longer the reference's pixels.  One line reports the totals, and a warning names blocks left unrepaired.  The gray
+# path only: refused together with SVS_FUSED_COLOUR / SVS_KEEP_COLOUR.
+READBACK = os.environ.get("SVS_READBACK", "0") == "1"
 
 
 def _keyed(block_key=None, **kw):
@@ -113,6 +119,9 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if kunci_blok is not None and KEEP_COLOUR:
         print("    Error: SVS_BLOCK_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR.")
         return False, None, None
+    if READBACK and (FUSED_COLOUR or KEEP_COLOUR):
+        raise ValueError("SVS_READBACK=1 cannot be combined with SVS_FUSED_COLOUR / SVS_KEEP_COLOUR: "
+                         "the fused colour path has no read-back")
 
     payload = _siapkan_payload(path_gambar_rahasia, kunci_publik_ecc_penerima_bytes_compressed)
     if payload is None:
@@ -210,7 +219,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         n_batches = PIPELINE_DEPTH if carrying is None else -(-carrying // per_batch)
         with FramePipeline(out_h, out_w, per_batch, delta_kuantisasi, num_ac_coeffs,
                            depth=max(1, min(PIPELINE_DEPTH, n_batches)), mode=_batch.host_level_mode(),
-                           **_keyed(block_key=kunci_blok)) as pipe:
+                           **_keyed(block_key=kunci_blok), **({"readback": True} if READBACK else {})) as pipe:
             pipe.set_payload(payload)
             rencana = {"sisa": carrying}
 
@@ -240,6 +249,12 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
                         raise RuntimeError(f"embed kernel consumed {used} bits, expected {expect}")
                     tulis(pipe.input(slot)[:n], pipe.embed_result(slot))
                     feeder.release(slot)
+            if READBACK:
+                rb = pipe.readback_counts()
+                print(f"    Read-back: {rb.repaired} blok diperbaiki, {rb.unrepaired} blok tidak dapat diperbaiki.")
+                if rb.unrepaired:
+                    print(f"    Warning: {rb.unrepaired} blok tidak terbaca kembali dengan benar; "
+                          "payload kemungkinan gagal didekripsi.")
     disisipkan = state["disisipkan"]
     selesai = usable > 0 and disisipkan >= total_bits
     if selesai:

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -130,15 +131,24 @@ def _order_ref(order: BlockOrder | None):
     return C.byref(order) if order is not None else None
 
 
+class ReadbackCounts(NamedTuple):
+    """what an SVS_READBACK embed did: blocks that did not read back and were repaired / kept the reference's bytes"""
+    repaired: int
+    unrepaired: int
+
+
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
-                 device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0):
+                 device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
     `bit_offset` is the first one used);  n_bits : bits available from bit_offset (default: rest).
     block_key : None (the reference's raster order) or an integer key 0 <= key < 2**64: the blocks of each frame take the
     frame's bits in a keyed order (svsdct/order.py); frame f of the stack is clip frame first_frame + f.
-    Returns (stego uint8 [F,H,W], n_embedded)."""
+    readback : opt-in (SVS_READBACK, include/svsdct.h): every block that carries payload is read back with the reference's
+    extraction and repaired where the reference's clipping or truncation lost a bit; repaired blocks are not the reference's
+    pixels any more.
+    Returns (stego uint8 [F,H,W], n_embedded), with readback (stego, n_embedded, ReadbackCounts)."""
     order = block_order(block_key, first_frame)
     lib = native.load()
     native.ensure_device(device)
@@ -155,6 +165,13 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     stego = pinned_empty(stack.shape)      # page-locked: the download lands in it by DMA, no staging copy, no page faults
     done = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
+    if readback:
+        counts = native.ReadbackCounts()
+        rc = lib.svs_embed_readback(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), float(delta),
+                                    int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits), mode_flags(mode),
+                                    C.byref(done), C.byref(counts))
+        native.check(rc, "svs_embed_readback")
+        return stego, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
     if order is None:
         rc = lib.svs_embed(stack.ctypes.data, stego.ctypes.data, C.byref(planes), float(delta), int(n_ac),
                            packed.ctypes.data, int(bit_offset), int(n_bits), mode_flags(mode), C.byref(done))
@@ -260,11 +277,18 @@ def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: s
 # ---- device-pointer level -------------------------------------------------------------------
 def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_packed: int,
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
-                 order: BlockOrder | None = None) -> int:
+                 order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
-    native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev."""
+    native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
+    read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
+    it adds {repaired, unrepaired} into."""
     done = C.c_uint64(0)
-    if order is None:
+    if readback:
+        rc = native.load().svs_embed_readback_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), float(delta),
+                                                  int(n_ac), d_bits_packed, int(bit_offset), int(n_bits), mode_flags(mode),
+                                                  C.byref(done), d_counts or None, stream or None)
+        native.check(rc, "svs_embed_readback_dev")
+    elif order is None:
         rc = native.load().svs_embed_dev(d_gray, d_stego, C.byref(planes), float(delta), int(n_ac), d_bits_packed,
                                          int(bit_offset), int(n_bits), mode_flags(mode), C.byref(done),
                                          stream or None)

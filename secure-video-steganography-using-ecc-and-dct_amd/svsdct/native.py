@@ -21,6 +21,7 @@ SVS_ERR_CAPACITY = -4
 SVS_EXACT_POCKETFFT = 1      # flags bit: pocketfft-identical arithmetic (include/svsdct.h)
 SVS_EXACT_GUARDED = 2        # flags bit: the same bit-identical result through the guarded kernel where it applies
 SVS_KEEP_COLOUR = 0x100      # flags bit, fused colour embed only: stego pixels keep the cover's colour (include/svsdct.h)
+SVS_READBACK = 0x200         # flags bit, gray embed only: read every payload block back, repair the ones that fail (include/svsdct.h)
 ABI_VERSION = 4
 
 
@@ -38,6 +39,11 @@ class Planes(C.Structure):
     @classmethod
     def contiguous(cls, n_frames: int, height: int, width: int) -> "Planes":
         return cls(n_frames, height, width, 0, width, height * width)
+
+
+class ReadbackCounts(C.Structure):
+    """struct svs_readback_counts: blocks repaired / left unrepaired by an SVS_READBACK call"""
+    _fields_ = [("repaired", C.c_uint64), ("unrepaired", C.c_uint64)]
 
 
 class BlockOrder(C.Structure):
@@ -81,6 +87,10 @@ SIGNATURES = {
     "svs_embed_ordered": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                      _u64p]),
     "svs_extract_ordered": (C.c_int, [_u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                          _u64p, C.c_void_p, C.c_void_p]),
+    "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                      _u64p, C.POINTER(ReadbackCounts)]),
     "svs_extract_dev": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
     "svs_extract": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_bgr_to_gray_dev": (C.c_int, [_u8p, C.c_int64, C.c_int64, _u8p, _PL, C.c_void_p, C.c_void_p]),

@@ -48,9 +48,10 @@ def _device(nbytes: int):
 
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
-                 mode: str | None = None, device: int = 0, block_key=None):
+                 mode: str | None = None, device: int = 0, block_key=None, readback: bool = False):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
-        clip index of its batch's first frame."""
+        clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
+        (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals."""
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
         self.block_key = batch.block_order(block_key).key if block_key is not None else None
@@ -76,6 +77,12 @@ class FramePipeline:
                                     d_bits=_device(self._bits_bytes), frames=0, bits=0))
         self._d_payload = None
         self._payload_bits = 0
+        self.readback = bool(readback)
+        self._d_counts = None
+        if self.readback:   # {repaired, unrepaired} of every batch, added to on the device
+            self._d_counts = _device(16)
+            native.check(self.lib.svs_memset(self._d_counts, 0, 16, None), "svs_memset")
+            native.check(self.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
 
     def bind_thread(self) -> None:
         """Call once on any other thread that is going to use this pipeline (HIP's current device is per thread)."""
@@ -113,7 +120,8 @@ class FramePipeline:
         native.check(self.lib.svs_memcpy_h2d(s["d_frames"], s["hin_p"], nbytes, s["stream"]), "svs_memcpy_h2d")
         used = batch.embed_device(s["d_frames"].value, s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac,
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
-                                  stream=s["stream"].value, mode=self.mode, order=self._order(first_frame))
+                                  stream=s["stream"].value, mode=self.mode, order=self._order(first_frame),
+                                  readback=self.readback, d_counts=self._d_counts.value if self._d_counts else 0)
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
         return used
@@ -143,6 +151,17 @@ class FramePipeline:
         native.check(self.lib.svs_stream_synchronize(s["stream"]), "svs_stream_synchronize")
         return s["hbits"][: (s["bits"] + 7) // 8], s["bits"]
 
+    def readback_counts(self) -> "batch.ReadbackCounts":
+        """(repaired, unrepaired) blocks over every embed batch submitted so far (waits for all slots)"""
+        if not self.readback:
+            raise RuntimeError("the pipeline was created without readback")
+        for s in self._slots:
+            native.check(self.lib.svs_stream_synchronize(s["stream"]), "svs_stream_synchronize")
+        out = np.zeros(2, np.uint64)
+        native.check(self.lib.svs_memcpy_d2h(out.ctypes.data, self._d_counts, 16, None), "svs_memcpy_d2h")
+        native.check(self.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+        return batch.ReadbackCounts(int(out[0]), int(out[1]))
+
     def close(self) -> None:
         for s in self._slots:
             self.lib.svs_stream_synchronize(s["stream"])
@@ -155,6 +174,9 @@ class FramePipeline:
         if self._d_payload is not None:
             self.lib.svs_free(self._d_payload)
             self._d_payload = None
+        if self._d_counts is not None:
+            self.lib.svs_free(self._d_counts)
+            self._d_counts = None
         native.release_thread_context()      # the per-frame operator calls of this thread (first-frame PSNR pair, ...) grew one
 
     def __enter__(self):

@@ -1,0 +1,68 @@
+// CPU build of csrc/svs_readback.hpp for tests/test_readback_cpu.py and tests/test_readback_gpu.py: the read-back pass of
+// SVS_READBACK (csrc/svs_device.hpp readback_kernel) block by block on the host, with the library's own routing
+// (svs_route.hpp), payload windows and keyed block order.  Build: g++ -O2 -ffp-contract=off -std=c++17 -shared -fPIC.
+#include <cstdint>
+#include <cstring>
+
+#include "svs_order.hpp"
+#include "svs_readback.hpp"
+#include "svs_route.hpp"
+
+namespace {
+
+template <int QM>
+uint32_t step_qm(int rows, uint32_t (&x)[8], uint32_t (&y)[8], uint32_t nb, uint32_t hi, uint32_t lo, const svs::QimParams &qp) {
+    if (rows == 1) return svs::readback_step<1, QM>(x, y, nb, hi, lo, qp);
+    if (rows == 2) return svs::readback_step<2, QM>(x, y, nb, hi, lo, qp);
+    return svs::readback_step<8, QM>(x, y, nb, hi, lo, qp);
+}
+
+}  // namespace
+
+extern "C" {
+
+// In place on stego [F][H][W] (contiguous): the reference's stego of the same call.  bits: packed MSB-first, padded to a
+// multiple of 4 bytes; the call embedded min(n_bits, capacity) bits from bit_offset on.  keyed: the ordered call's order
+// (key, first_frame).  status[block] (optional): 0 reads back, 1 repaired, 2 left unrepaired, 3 carries no payload.
+// counts[0] / counts[1]: repaired / unrepaired.  Returns the bits the call embedded.
+uint64_t rb_readback(uint8_t *stego, int F, int H, int W, double delta, int n_ac, const uint8_t *bits, uint64_t bits_bytes,
+                     uint64_t bit_offset, uint64_t n_bits, int keyed, uint64_t key, uint32_t first_frame, uint64_t *counts,
+                     uint8_t *status) {
+    counts[0] = counts[1] = 0;
+    const uint32_t n = (uint32_t)(n_ac < 0 ? 0 : (n_ac > 63 ? 63 : n_ac));
+    const uint64_t wb = (uint64_t)W / 8, bpf = wb * (uint64_t)(H / 8), total = bpf * (uint64_t)F;
+    svs::RouteArgs ra{delta, n, total, n_bits, bit_offset, false, true, false, false, 1.0f, 1.0f};
+    ra.keyed = keyed != 0;
+    ra.readback = true;
+    const svs::EmbedPlan p = svs::plan_embed(ra);
+    if (status) std::memset(status, 3, total);
+    if (p.use == 0) return 0;
+    const svs::BlockOrderArgs ord = svs::make_block_order(key, first_frame, (uint32_t)bpf);
+    const uint32_t n_words = (uint32_t)(bits_bytes / 4);
+    for (uint64_t gb = 0; gb < total; ++gb) {
+        const uint64_t f = gb / bpf, b = gb % bpf;
+        const uint64_t slot = keyed ? svs::block_to_slot((uint32_t)b, ord, svs::round_keys(ord, ord.first_frame + (uint32_t)f)) : b;
+        const uint64_t first = (f * bpf + slot) * n;
+        const uint32_t nb = svs::block_budget(first, p.n_bits, n);
+        if (nb == 0) continue;
+        uint8_t *px = stego + f * (uint64_t)H * W + (b / wb) * 8 * (uint64_t)W + (b % wb) * 8;
+        uint32_t x[8], y[8];
+        for (int r = 0; r < 8; ++r) { std::memcpy(&x[r], px + r * W, 4); std::memcpy(&y[r], px + r * W + 4, 4); }
+        uint32_t hi, lo;
+        svs::payload_window(reinterpret_cast<const uint32_t *>(bits), n_words, p.bit_offset + first, hi, lo);
+        uint32_t st = 0;
+        if (p.qm == svs::QM_DOUBLE) st = step_qm<svs::QM_DOUBLE>(p.rows, x, y, nb, hi, lo, p.qp);
+        else if (p.qm == svs::QM_POW2) st = step_qm<svs::QM_POW2>(p.rows, x, y, nb, hi, lo, p.qp);
+        else st = step_qm<svs::QM_F32>(p.rows, x, y, nb, hi, lo, p.qp);
+        if (st == 1) {
+            for (int r = 0; r < 8; ++r) { std::memcpy(px + r * W, &x[r], 4); std::memcpy(px + r * W + 4, &y[r], 4); }
+            ++counts[0];
+        } else if (st == 2) {
+            ++counts[1];
+        }
+        if (status) status[gb] = (uint8_t)st;
+    }
+    return p.use;
+}
+
+}
