@@ -284,11 +284,12 @@ int svs_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *pl
 
 /* ---- colour plumbing around the operator (device resident) --------------------------------------------
  * Interleaved 8-bit BGR frames [frame][row][col][3] <-> gray planes.  bgr_row_pitch / bgr_frame_pitch in bytes,
- * multiples of 4; BGR base pointers 4-byte aligned.
+ * multiples of 8 (3*width always is); BGR base pointers 8-byte aligned, as for the fused calls below.
  * svs_bgr_to_gray_dev replaces cv2.cvtColor(frame, COLOR_BGR2GRAY) (config_and_setup.py:112): OpenCV's fixed-point
  * (B*wb + G*wg + R*wr + 2^(shift-1)) >> shift.  weights = {wb, wg, wr, shift}; NULL = {3735, 19235, 9798, 15}
- * (OpenCV 4's 15-bit table; older builds use {1868, 9617, 4899, 14}).  Parity with cv2 is UNPINNED (cv2 is not
- * available in the build image) - a caller that has cv2 should compare once at start-up.
+ * (OpenCV 4's 15-bit table; older builds use {1868, 9617, 4899, 14}); wb + wg + wr must equal 2^shift exactly.
+ * Parity with cv2 is UNPINNED (cv2 is not available in the build image) - a caller that has cv2 should compare once
+ * at start-up.
  * svs_gray_to_bgr_dev replaces cv2.cvtColor(stego, COLOR_GRAY2BGR) (embed_process.py:126): B = G = R = gray. */
 int svs_bgr_to_gray_dev(const uint8_t *d_bgr, int64_t bgr_row_pitch, int64_t bgr_frame_pitch, uint8_t *d_gray,
                         const svs_planes *planes, const uint32_t *weights, void *stream);
@@ -328,7 +329,7 @@ int svs_extract_bgr(const uint8_t *bgr, const svs_planes *planes, const uint32_t
                     uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint64_t *n_bits_out);
 
 /* ---- measurement helpers (synthetic inputs and on-device checks for bench.py / tests) ------ */
-/* value = lo + hash32(seed, first_frame + f, y, x) % span  - same hash as svsdct/synth.py */
+/* value = lo + hash32(seed, first_frame + f, y, x) % span  - same hash as svsdct/synth.py; 1 <= span, lo + span <= 256 */
 int svs_fill_synthetic_dev(uint8_t *d_frames, const svs_planes *planes, uint32_t seed,
                            uint32_t first_frame, uint32_t lo, uint32_t span, void *stream);
 /* packed Bernoulli(1/2) stream, bit i = lowbias32(seed*0x632BE5AB + first_bit + i) >> 31;
@@ -342,8 +343,11 @@ int svs_frame_sse_dev(const uint8_t *d_a, const uint8_t *d_b, const svs_planes *
 /* mean SSIM per frame -> d_ssim[n_frames] (double, device), as skimage.metrics.structural_similarity with its
  * defaults for 2-D uint8 input (7x7 uniform window, K1 .01, K2 .03, sample covariance, float64) - the call
  * behind the reference's evaluation.calc_ssim (evaluation.py:21-26).  d_data_range[n_frames] (double, device)
- * gives skimage's data_range per frame; pass NULL to use the reference's quirk, max - min of frame b.
- * d_workspace: at least svs_ssim_workspace_bytes(planes) bytes of device memory (8-byte aligned).  H, W >= 7. */
+ * gives skimage's data_range per frame; pass NULL to use the reference's quirk, max - min of frame b.  A data range
+ * of 0 (with NULL: a flat frame b, C1 = C2 = 0) gives skimage's result: a window's value is NaN where its denominator
+ * is 0 (a window flat in both frames), and so is the frame's mean - a flat frame against itself yields NaN.
+ * d_workspace: at least svs_ssim_workspace_bytes(planes) bytes of device memory.  d_a, d_b, d_data_range, d_ssim and
+ * d_workspace 8-byte aligned.  H, W >= 7. */
 uint64_t svs_ssim_workspace_bytes(const svs_planes *planes);
 int svs_frame_ssim_dev(const uint8_t *d_a, const uint8_t *d_b, const svs_planes *planes,
                        const double *d_data_range, double *d_ssim, void *d_workspace, void *stream);

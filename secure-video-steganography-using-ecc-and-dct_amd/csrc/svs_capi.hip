@@ -991,10 +991,18 @@ int svs_shutdown(void) {
     return SVS_OK;
 }
 
+// the BGR row movers (load_bgr_row, wave_load_gray, wave_store_gray_as_bgr) access rows 8 bytes at a time
 static int check_bgr(const svs_planes *p, const void *bgr, int64_t rp, int64_t fp) {
-    if (!bgr || ((uintptr_t)bgr % 4)) return fail(SVS_ERR_INVALID_ARG, "BGR pointer NULL or not 4-byte aligned");
-    if (rp < 3 * (int64_t)p->width || (rp % 4) || fp < rp * p->height || (fp % 4))
-        return fail(SVS_ERR_INVALID_ARG, "BGR pitches must cover 3*width bytes per row and be multiples of 4");
+    if (!bgr || ((uintptr_t)bgr % 8)) return fail(SVS_ERR_INVALID_ARG, "BGR pointer NULL or not 8-byte aligned");
+    if (rp < 3 * (int64_t)p->width || (rp % 8) || fp < rp * p->height || (fp % 8))
+        return fail(SVS_ERR_INVALID_ARG, "BGR pitches must cover 3*width bytes per row and be multiples of 8");
+    return SVS_OK;
+}
+
+// {wb, wg, wr, shift}: the sum taken in 64 bits, so that no weight above 2^shift can wrap it back to 2^shift
+static int check_weights(const uint32_t *w) {
+    if (w[3] < 1 || w[3] > 16 || (uint64_t)w[0] + w[1] + w[2] != (1ull << w[3]))
+        return fail(SVS_ERR_INVALID_ARG, "weights must sum to 2^shift with 1 <= shift <= 16");
     return SVS_OK;
 }
 
@@ -1008,8 +1016,7 @@ int svs_bgr_to_gray_dev(const uint8_t *d_bgr, int64_t bgr_row_pitch, int64_t bgr
     if (int rc = check_bgr(planes, d_bgr, bgr_row_pitch, bgr_frame_pitch)) return rc;
     const uint32_t dflt[4] = {3735u, 19235u, 9798u, 15u};
     const uint32_t *w = weights ? weights : dflt;
-    if (w[3] < 1 || w[3] > 16 || w[0] + w[1] + w[2] != (1u << w[3]))
-        return fail(SVS_ERR_INVALID_ARG, "weights must sum to 2^shift with 1 <= shift <= 16");
+    if (int rc = check_weights(w)) return rc;
     svs::ColourParams c{bgr_row_pitch, bgr_frame_pitch, 0, 0, w[0], w[1], w[2], w[3]};
     g.xcd_chunk = svs::kEighth;
     hipLaunchKernelGGL(svs::bgr_to_gray_kernel, dim3((uint32_t)((total + SVS_WG - 1) / SVS_WG)), dim3(SVS_WG), 0,
@@ -1046,8 +1053,7 @@ static int colour_params(const svs_planes *p, const void *in, int64_t irp, int64
     }
     const uint32_t dflt[4] = {3735u, 19235u, 9798u, 15u};
     const uint32_t *w = weights ? weights : dflt;
-    if (w[3] < 1 || w[3] > 16 || w[0] + w[1] + w[2] != (1u << w[3]))
-        return fail(SVS_ERR_INVALID_ARG, "weights must sum to 2^shift with 1 <= shift <= 16");
+    if (int rc = check_weights(w)) return rc;
     c->in_row_pitch = irp; c->in_frame_pitch = ifp; c->out_row_pitch = orp; c->out_frame_pitch = ofp;
     c->wb = w[0]; c->wg = w[1]; c->wr = w[2]; c->shift = w[3];
     return SVS_OK;
@@ -1176,7 +1182,7 @@ int svs_fill_synthetic_dev(uint8_t *d_frames, const svs_planes *planes, uint32_t
     if (int rc = make_geometry(planes, 1, &g, &total)) return rc;
     if (total == 0) return SVS_OK;
     if (!d_frames || ((uintptr_t)d_frames % 8)) return fail(SVS_ERR_INVALID_ARG, "frames pointer NULL or unaligned");
-    if (span == 0 || lo + span > 256) return fail(SVS_ERR_INVALID_ARG, "need span >= 1 and lo + span <= 256");
+    if (span == 0 || span > 256 || lo > 256 - span) return fail(SVS_ERR_INVALID_ARG, "need span >= 1 and lo + span <= 256");
     hipLaunchKernelGGL(svs::fill_synthetic_kernel, dim3(4096), dim3(256), 0, (hipStream_t)stream, d_frames,
                        planes->n_frames, planes->height, planes->width, planes->row_pitch, planes->frame_pitch, seed,
                        first_frame, lo, span);
@@ -1226,7 +1232,9 @@ int svs_frame_ssim_dev(const uint8_t *d_a, const uint8_t *d_b, const svs_planes 
     if (int rc = make_geometry(planes, 1, &g, &total)) return rc;
     if (total == 0) return SVS_OK;
     if (!d_a || !d_b || !d_ssim || !d_workspace) return fail(SVS_ERR_INVALID_ARG, "NULL pointer");
-    if (((uintptr_t)d_ssim % 8) || ((uintptr_t)d_workspace % 8)) return fail(SVS_ERR_INVALID_ARG, "pointers must be 8-byte aligned");
+    if (((uintptr_t)d_a % 8) || ((uintptr_t)d_b % 8) || ((uintptr_t)d_data_range % 8) || ((uintptr_t)d_ssim % 8) ||
+        ((uintptr_t)d_workspace % 8))
+        return fail(SVS_ERR_INVALID_ARG, "pointers must be 8-byte aligned");
     if (planes->n_frames > 65535) return fail(SVS_ERR_INVALID_ARG, "at most 65535 frames per call");
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t gx = (uint32_t)(((uint64_t)(planes->width - 6) + 255) / 256);

@@ -1640,8 +1640,8 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const uint8_t *__rest
     const int t = threadIdx.x;
     const uint8_t *pa = a + (int64_t)f * frame_pitch, *pb = b + (int64_t)f * frame_pitch;
     const double R = data_range[f];
-    const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
-    const double inv_np = 1.0 / 49.0, cov_norm = 49.0 / 48.0;
+    // C1 and C2 scaled by 49^2 and 49 * 48, the denominators of the means and the sample (co)variances: see below
+    const double C1 = 2401.0 * ((0.01 * R) * (0.01 * R)), C2 = 2352.0 * ((0.03 * R) * (0.03 * R));
     // ring of the last 7 horizontal 7-sums of the five moments; slot = input row % 7, so with rows handled in groups
     // of 7 every slot index below is a compile-time constant
     uint32_t ha[7], hb[7], haa[7], hbb[7], hab[7];
@@ -1680,10 +1680,15 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const uint8_t *__rest
             ha[j] = sa; hb[j] = sb; haa[j] = saa; hbb[j] = sbb; hab[j] = sab;
             const int r = r0 + j;
             if (r >= 6 && r < rows && col_ok) {
-                const double ux = va * inv_np, uy = vb * inv_np;
-                const double vx = cov_norm * (vaa * inv_np - ux * ux), vy = cov_norm * (vbb * inv_np - uy * uy);
-                const double vxy = cov_norm * (vab * inv_np - ux * uy);
-                const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2, B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
+                // skimage's four terms, those of the means (sum / 49) scaled by 49^2 and those of the sample (co)variances
+                // by 49 * 48: apart from C1, C2 they are exact integers below 2^29 - 2 sum(x) sum(y), sum(x)^2 + sum(y)^2,
+                // and the numerators 49 sum(xy) - sum(x) sum(y) (>= 0 for the variances: Cauchy-Schwarz).  A flat window's
+                // variance is exactly 0, so with a data range of 0 (C1 = C2 = 0) a window flat in both frames gives
+                // skimage's 0 / 0 = NaN.
+                const uint32_t nx = 49u * vaa - va * va, ny = 49u * vbb - vb * vb;
+                const int32_t nxy = (int32_t)(49u * vab - va * vb);
+                const double A1 = (double)(2u * va * vb) + C1, B1 = (double)(va * va + vb * vb) + C1;
+                const double A2 = (double)(2 * nxy) + C2, B2 = (double)(nx + ny) + C2;
                 acc += (A1 * A2) / (B1 * B2);
             }
         }

@@ -114,16 +114,16 @@ KERNEL_CASES = _cases()
 HELPER_KERNELS = {
     "ascii_to_packed_kernel": "tests/test_gpu_parity.py::test_string_payload_entry_points_equal_the_packed_ones",
     "packed_to_ascii_kernel": "tests/test_gpu_parity.py::test_string_payload_entry_points_equal_the_packed_ones",
-    "fill_synthetic_kernel": "tests/test_gpu_parity.py::test_guarded_mode_full_batch_equals_exact_kernel_on_device",
-    "fill_bits_kernel": "tests/test_gpu_parity.py::test_guarded_mode_full_batch_equals_exact_kernel_on_device",
-    "frame_sse_kernel": "tests/test_gpu_parity.py::test_guarded_mode_full_batch_equals_exact_kernel_on_device",
-    "bit_errors_kernel": "tests/test_gpu_parity.py::test_full_baseline_batch_on_device_properties",
-    "frame_minmax_kernel": "tests/test_gpu_parity.py::test_device_psnr_and_ssim_evaluators",
-    "frame_range_finish_kernel": "tests/test_gpu_parity.py::test_device_psnr_and_ssim_evaluators",
-    "ssim_partial_kernel": "tests/test_gpu_parity.py::test_device_psnr_and_ssim_evaluators",
-    "ssim_finish_kernel": "tests/test_gpu_parity.py::test_device_psnr_and_ssim_evaluators",
-    "bgr_to_gray_kernel": "tests/test_gpu_parity.py::test_device_colour_conversions",
-    "gray_to_bgr_kernel": "tests/test_gpu_parity.py::test_device_colour_conversions",
+    "fill_synthetic_kernel": "tests/test_helper_kernels_gpu.py::test_fill_synthetic_frames_counters_and_padding",
+    "fill_bits_kernel": "tests/test_helper_kernels_gpu.py::test_fill_bits_counters_past_2_to_the_32",
+    "frame_sse_kernel": "tests/test_helper_kernels_gpu.py::test_frame_sse_many_frames_and_pitched",
+    "bit_errors_kernel": "tests/test_helper_kernels_gpu.py::test_bit_errors_lengths_and_tail_masks",
+    "frame_minmax_kernel": "tests/test_helper_kernels_gpu.py::test_ssim_and_data_range_at_tile_band_and_row_group_edges",
+    "frame_range_finish_kernel": "tests/test_helper_kernels_gpu.py::test_ssim_and_data_range_at_tile_band_and_row_group_edges",
+    "ssim_partial_kernel": "tests/test_helper_kernels_gpu.py::test_ssim_and_data_range_at_tile_band_and_row_group_edges",
+    "ssim_finish_kernel": "tests/test_helper_kernels_gpu.py::test_ssim_and_data_range_at_tile_band_and_row_group_edges",
+    "bgr_to_gray_kernel": "tests/test_helper_kernels_gpu.py::test_colour_conversions_pitched_with_sentinels",
+    "gray_to_bgr_kernel": "tests/test_helper_kernels_gpu.py::test_colour_conversions_pitched_with_sentinels",
 }
 DISPATCHED_FAMILIES = ("embed_row1_kernel", "embed_kernel", "embed_exact_kernel", "readback_kernel", "embed_bgr_kernel",
                        "extract_kernel", "extract_exact_kernel", "extract_bgr_kernel")
