@@ -195,36 +195,104 @@ __device__ __forceinline__ void or_bits_global(uint8_t *out, uint64_t pos, uint3
     }
 }
 
-struct GuardEntry {
+// A worklist entry: one block for the eight-lane exact replay.  8-byte aligned because row1_deposit / row1_collect move its rows
+// as 8-byte LDS accesses.
+struct alignas(8) GuardEntry {
     uint32_t px[16];   // rows as (low dword, high dword) pairs: the original pixels in, the exact stego pixels out
     uint32_t hi, lo;   // payload window of the block
     uint32_t nb;       // bits the block takes
     uint32_t pad;
 };
+static_assert(sizeof(GuardEntry) == 80 && sizeof(GuardEntry) % 8 == 0, "80-byte entries, rows 8-byte aligned");
 #define SVS_GUARD_TILE 72   // floats per block of the transposition tile: element (i, j) at 9 i + j; 72 = 8 (mod 64) keeps the
                             // eight groups of a wave on different LDS banks in both directions
 
-// FAST extraction, second path: a block with a quantiser input inside the per-block tie margin (svs_block.hpp SVS_TIE2_*)
-// gets the pocketfft-identical forward transform - by EIGHT LANES PER BLOCK, as in the embed kernels' replay: lane r of a
-// group transforms column r, then row r, then takes coefficient column r and quantises its coefficients k = 8 u + r of the
-// rows u the payload uses; the bits are ORed into the entry.  About 200 instructions per pass of 8 blocks, against 580 for
-// every wave that had such a lane when the whole block was redone by its own lane (round 2).
-template <int QM>
-__device__ __forceinline__ void extract_replay8(GuardEntry *e, float *t, uint32_t r, uint32_t n, const QimParams &qp) {
+// ---------------------------------------------------------------------------------------
+// Exact replays, EIGHT LANES PER BLOCK: the blocks that a kernel's fast arithmetic cannot decide are redone with pocketfft's
+// arithmetic (svs::pf, the same operation sequence per line as the lane-per-block forms of svs_block.hpp / svs_readback.hpp).
+// Lane r of a group of eight transforms column r, then row r, of its block; the lines meet in the group's transposition tile t,
+// element (i, j) at S i + j (S = 9: SVS_GUARD_TILE, embed / extract; S = 8: read-back's 64-float tiles).
+// ---------------------------------------------------------------------------------------
+// forward: the block's pixel column r, then coefficient row r -> c[v] = D[r][v]
+template <int S>
+__device__ __forceinline__ void forward8(const uint32_t *px, float *t, uint32_t r, float (&c)[8]) {
     float a[8], b[8];
-    {
-        const uint32_t sh = 8u * (r & 3u), half = r >> 2;
 #pragma unroll
-        for (int y = 0; y < 8; ++y) a[y] = (float)((e->px[2 * y + half] >> sh) & 0xffu);
-    }
+    for (int y = 0; y < 8; ++y) a[y] = (float)((px[2 * y + (r >> 2)] >> (8u * (r & 3u))) & 0xffu);
     pf::dct2_8(a, b);                       // b[u] = V[u][r]
 #pragma unroll
-    for (int u = 0; u < 8; ++u) t[9 * u + r] = b[u];
+    for (int u = 0; u < 8; ++u) t[S * u + r] = b[u];
     wave_lds_fence();
 #pragma unroll
-    for (int x = 0; x < 8; ++x) a[x] = t[9 * r + x];   // V[r][x]
+    for (int x = 0; x < 8; ++x) a[x] = t[S * r + x];   // V[r][x]
     wave_lds_fence();
-    pf::dct2_8(a, b);                       // b[v] = D[r][v]
+    pf::dct2_8(a, c);
+}
+
+// inverse: coefficient column r (c[u] = D[u][r]), vertical first (config_and_setup.py:168), then pixel row r -> p[x] = P[r][x]
+template <int S>
+__device__ __forceinline__ void inverse8(const float (&c)[8], float *t, uint32_t r, float (&p)[8]) {
+    float a[8], b[8];
+    pf::dct3_8(c, b);                       // b[y] = column r of the vertical inverse
+#pragma unroll
+    for (int y = 0; y < 8; ++y) t[S * y + r] = b[y];
+    wave_lds_fence();
+#pragma unroll
+    for (int x = 0; x < 8; ++x) a[x] = t[S * r + x];
+    pf::dct3_8(a, p);
+}
+
+// this lane's rank among the lanes of `mask` (the lanes below it whose bit is set)
+__device__ __forceinline__ uint32_t wave_rank(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The wave-private worklist of the replays (ballot + mbcnt: no atomics, no barrier).  mine[j]: this lane's block j (one or two
+// blocks per lane) is to be redone.  The entries are numbered block 0's in lane order, then block 1's, and go in rounds of CAP:
+//   deposit(j, e)      the owner of block j fills entry e (0 .. CAP - 1) of the round
+//   replay(e, grp, r)  lanes 8 grp .. 8 grp + 7 redo entry e, lane r = lane & 7 - eight entries per pass
+//   collect(j, e)      the owner takes block j's result back
+// Returns the number of entries - 0, wave-uniform, after the ballot alone when no lane has one.
+template <int CAP, int B, class Deposit, class Replay, class Collect>
+__device__ __forceinline__ uint32_t wave_worklist(const bool (&mine)[B], uint32_t lane, Deposit &&deposit, Replay &&replay,
+                                                  Collect &&collect) {
+    static_assert(B == 1 || B == 2, "one or two blocks per lane");
+    uint64_t mask[B], any = 0;
+    uint32_t rank[B], total = 0;
+#pragma unroll
+    for (int j = 0; j < B; ++j) { mask[j] = __ballot(mine[j]); any |= mask[j]; }
+    if (any == 0) return 0;                 // wave-uniform
+#pragma unroll
+    for (int j = 0; j < B; ++j) { rank[j] = total + wave_rank(mask[j]); total += (uint32_t)__popcll(mask[j]); }
+    const uint32_t grp = lane >> 3, r = lane & 7u;
+    for (uint32_t base = 0; base < total; base += (uint32_t)CAP) {   // wave-uniform
+        bool in[B];
+#pragma unroll
+        for (int j = 0; j < B; ++j) in[j] = mine[j] && rank[j] >= base && rank[j] < base + (uint32_t)CAP;
+#pragma unroll
+        for (int j = 0; j < B; ++j)
+            if (in[j]) deposit(j, rank[j] - base);
+        wave_lds_fence();
+        const uint32_t todo = min(total - base, (uint32_t)CAP);
+        for (uint32_t at = 0; at < todo; at += 8u)
+            if (at + grp < todo) replay(at + grp, grp, r);
+        wave_lds_fence();
+#pragma unroll
+        for (int j = 0; j < B; ++j)
+            if (in[j]) collect(j, rank[j] - base);
+        if constexpr (CAP < 64) wave_lds_fence();   // the next round overwrites the entries
+    }
+    return total;
+}
+
+// FAST extraction, second path: a block with a quantiser input inside the per-block tie margin (svs_block.hpp SVS_TIE2_*)
+// gets the pocketfft-identical forward transform on eight lanes; lane r then takes coefficient column r and quantises its
+// coefficients k = 8 u + r of the rows u the payload uses; the bits are ORed into the entry.  About 200 instructions per pass
+// of 8 blocks, against 580 for every wave that had such a lane when the whole block was redone by its own lane (round 2).
+template <int QM>
+__device__ __forceinline__ void extract_replay8(GuardEntry *e, float *t, uint32_t r, uint32_t n, const QimParams &qp) {
+    float b[8];
+    forward8<9>(e->px, t, r, b);            // b[v] = D[r][v]
 #pragma unroll
     for (int v = 0; v < 8; ++v) t[9 * r + v] = b[v];
     wave_lds_fence();
@@ -244,42 +312,19 @@ __device__ __forceinline__ void extract_replay8(GuardEntry *e, float *t, uint32_
 }
 
 // the wave's tie blocks through the worklist (CAP entries per round); on return hi/lo of those blocks hold the reference's bits
-template <int QM, bool TWO, int CAP>
+template <int QM, int CAP>
 __device__ __forceinline__ void extract_phase2(GuardEntry *entries, float *tile, uint32_t lane, uint32_t n, const QimParams &qp,
-                                               bool tie_a, const uint32_t (&ax)[8], const uint32_t (&ay)[8], uint32_t &hi_a, uint32_t &lo_a,
-                                               bool tie_b, const uint32_t (&bx)[8], const uint32_t (&by)[8], uint32_t &hi_b, uint32_t &lo_b) {
-    const uint64_t mask_a = __ballot(tie_a);
-    const uint64_t mask_b = TWO ? __ballot(tie_b) : 0ull;
-    if ((mask_a | mask_b) == 0) return;     // wave-uniform; always the case on stego frames
-    const uint32_t n_a = (uint32_t)__popcll(mask_a), total = n_a + (uint32_t)__popcll(mask_b);
-    const uint32_t rank_a = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask_a >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask_a, 0u));
-    const uint32_t rank_b = n_a + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask_b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask_b, 0u));
-    for (uint32_t base = 0; base < total; base += (uint32_t)CAP) {   // wave-uniform
-        const bool mine_a = tie_a && rank_a >= base && rank_a < base + (uint32_t)CAP;
-        const bool mine_b = TWO && tie_b && rank_b >= base && rank_b < base + (uint32_t)CAP;
-        if (mine_a) {
-            GuardEntry *e = &entries[rank_a - base];
+                                               bool tie, const uint32_t (&ax)[8], const uint32_t (&ay)[8], uint32_t &hi, uint32_t &lo) {
+    wave_worklist<CAP>(
+        {tie}, lane,
+        [&](int, uint32_t i) {
+            GuardEntry *e = &entries[i];
 #pragma unroll
             for (int r = 0; r < 8; ++r) { e->px[2 * r] = ax[r]; e->px[2 * r + 1] = ay[r]; }
             e->hi = 0; e->lo = 0;
-        }
-        if (mine_b) {
-            GuardEntry *e = &entries[rank_b - base];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { e->px[2 * r] = bx[r]; e->px[2 * r + 1] = by[r]; }
-            e->hi = 0; e->lo = 0;
-        }
-        wave_lds_fence();
-        const uint32_t todo = min(total - base, (uint32_t)CAP);
-        for (uint32_t first = 0; first < todo; first += 8u) {
-            const uint32_t idx = first + (lane >> 3);
-            if (idx < todo) extract_replay8<QM>(&entries[idx], tile + (lane >> 3) * SVS_GUARD_TILE, lane & 7u, n, qp);
-        }
-        wave_lds_fence();
-        if (mine_a) { hi_a = entries[rank_a - base].hi; lo_a = entries[rank_a - base].lo; }
-        if (mine_b) { hi_b = entries[rank_b - base].hi; lo_b = entries[rank_b - base].lo; }
-        wave_lds_fence();
-    }
+        },
+        [&](uint32_t i, uint32_t grp, uint32_t r) { extract_replay8<QM>(&entries[i], tile + grp * SVS_GUARD_TILE, r, n, qp); },
+        [&](int, uint32_t i) { hi = entries[i].hi; lo = entries[i].lo; });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -306,7 +351,7 @@ __global__ __launch_bounds__(SVS_WG) void extract_kernel(const uint8_t *__restri
     const uint32_t n = g.n_ac;
 
     // the block's bits, MSB first: bit i at position 63-i of hi:lo
-    uint32_t hi = 0, lo = 0, hb = 0, lb = 0;
+    uint32_t hi = 0, lo = 0;
     uint32_t ax[8], ay[8];
     bool tie = false;
     float off = 0.0f;
@@ -324,7 +369,7 @@ __global__ __launch_bounds__(SVS_WG) void extract_kernel(const uint8_t *__restri
     }
     // A quantiser input within the per-block error bound of a rounding tie (svs_block.hpp, SVS_TIE2_*): those blocks get the
     // pocketfft-identical transform from eight lanes each (wave-private worklist).  Never taken on stego frames at delta >= 8.
-    extract_phase2<QM, false, SVS_EXTRACT_CAP>(&entries[wave][0], &tiles[wave][0], lane, n, qp, tie, ax, ay, hi, lo, false, ax, ay, hb, lb);
+    extract_phase2<QM, SVS_EXTRACT_CAP>(&entries[wave][0], &tiles[wave][0], lane, n, qp, tie, ax, ay, hi, lo);
     if constexpr (KEYED) {
         if (gblock < g.total_blocks) or_bits_global<U>(out, stream_first<true>(gblock, n, g, order_arg(order...)), hi, lo);
     } else {
@@ -397,20 +442,7 @@ template <int QM, int UROWS = 8>
 __device__ __forceinline__ void guard_replay8(uint32_t *px, uint32_t hi, uint32_t lo, uint32_t nb, float *t, uint32_t r, uint32_t n,
                                               const QimParams &qp) {
     float a[8], b[8];
-    // vertical forward transform of pixel column r
-    {
-        const uint32_t sh = 8u * (r & 3u), half = r >> 2;
-#pragma unroll
-        for (int y = 0; y < 8; ++y) a[y] = (float)((px[2 * y + half] >> sh) & 0xffu);
-    }
-    pf::dct2_8(a, b);                       // b[u] = V[u][r]
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[9 * u + r] = b[u];
-    wave_lds_fence();
-#pragma unroll
-    for (int x = 0; x < 8; ++x) a[x] = t[9 * r + x];   // V[r][x]
-    wave_lds_fence();
-    pf::dct2_8(a, b);                       // b[v] = D[r][v]: coefficient row r
+    forward8<9>(px, t, r, b);   // b[v] = D[r][v]: coefficient row r
     // to coefficient COLUMNS (what the vertical inverse wants): lane r takes D[u][r], u = 0..7
 #pragma unroll
     for (int v = 0; v < 8; ++v) t[9 * r + v] = b[v];
@@ -435,13 +467,7 @@ __device__ __forceinline__ void guard_replay8(uint32_t *px, uint32_t hi, uint32_
             a[u] = ((uint32_t)i < nb) ? cn : c;
         }
     }
-    pf::dct3_8(a, b);                       // vertical inverse first (axis 0, :168): b[y] = P[y][r]
-#pragma unroll
-    for (int y = 0; y < 8; ++y) t[9 * y + r] = b[y];
-    wave_lds_fence();
-#pragma unroll
-    for (int v = 0; v < 8; ++v) a[v] = t[9 * r + v];   // P[r][v]
-    pf::dct3_8(a, b);                       // pixel row r
+    inverse8<9>(a, t, r, b);   // pixel row r
     uint32_t lo4, hi4;
     store_row_trunc(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], lo4, hi4);   // np.uint8(np.clip(.)) (:171)
     px[2 * r] = lo4;
@@ -469,100 +495,57 @@ struct GuardPayload {
     uint32_t n_words;
 };
 
-// phase 2: the wave's undecided blocks (a: first block of every lane, b: second block when two blocks per lane; their rows
-// still hold the ORIGINAL pixels, first_a / first_b are their first stream bits) through the worklist `entries` (CAP entries)
-// and the transposition tile `tile` (8 * SVS_GUARD_TILE floats), both private to the wave.  On return the rows of undecided
-// blocks hold the exact stego pixels.  Returns the number of blocks redone.
-template <int QM, bool TWO, int CAP = SVS_GUARD_CAP, bool KEPT = false, int UROWS = 2>
+// phase 2: the wave's undecided blocks (their rows still hold the ORIGINAL pixels; `first` is the lane's first stream bit)
+// through the worklist `entries` (CAP entries) and the transposition tile `tile` (8 * SVS_GUARD_TILE floats), both private to
+// the wave.  On return the rows of undecided blocks hold the exact stego pixels.  Returns the number of blocks redone.
+template <int QM, int CAP = SVS_GUARD_CAP, bool KEPT = false, int UROWS = 2>
 __device__ __forceinline__ uint32_t guard_phase2(GuardEntry *entries, float *tile, uint32_t lane, uint32_t n,
                                                  const QimParams &qp, const GuardPayload &pl,
-                                                 bool und_a, uint64_t first_a, uint32_t (&ax)[8], uint32_t (&ay)[8],
-                                                 bool und_b, uint64_t first_b, uint32_t (&bx)[8], uint32_t (&by)[8],
-                                                 uint32_t hi_a = 0, uint32_t hi_b = 0) {
-    const uint64_t mask_a = __ballot(und_a);
-    const uint64_t mask_b = TWO ? __ballot(und_b) : 0ull;
-    if ((mask_a | mask_b) == 0) return 0;   // wave-uniform: the common case costs two ballots
-    const uint32_t n_a = (uint32_t)__popcll(mask_a), total = n_a + (uint32_t)__popcll(mask_b);
-    const uint32_t rank_a = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask_a >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask_a, 0u));
-    const uint32_t rank_b = n_a + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask_b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask_b, 0u));
-    for (uint32_t base = 0; base < total; base += (uint32_t)CAP) {   // wave-uniform
-        const bool mine_a = und_a && rank_a >= base && rank_a < base + (uint32_t)CAP;
-        const bool mine_b = TWO && und_b && rank_b >= base && rank_b < base + (uint32_t)CAP;
-        if (mine_a) {
-            GuardEntry *e = &entries[rank_a - base];
+                                                 bool und, uint64_t first, uint32_t (&ax)[8], uint32_t (&ay)[8],
+                                                 uint32_t hi_kept = 0) {
+    return wave_worklist<CAP>(
+        {und}, lane,
+        [&](int, uint32_t i) {
+            GuardEntry *e = &entries[i];
 #pragma unroll
             for (int r = 0; r < 8; ++r) { e->px[2 * r] = ax[r]; e->px[2 * r + 1] = ay[r]; }
             uint32_t hi, lo;
-            if constexpr (KEPT) { hi = hi_a; lo = 0; }   // n <= 15: the window's first word, still in a register from phase 1
-            else payload_window(pl.bits, pl.n_words, pl.bit_offset + first_a, hi, lo);
-            e->hi = hi; e->lo = lo; e->nb = block_budget(first_a, pl.n_bits, n);
-        }
-        if (mine_b) {
-            GuardEntry *e = &entries[rank_b - base];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { e->px[2 * r] = bx[r]; e->px[2 * r + 1] = by[r]; }
-            uint32_t hi, lo;
-            if constexpr (KEPT) { hi = hi_b; lo = 0; }
-            else payload_window(pl.bits, pl.n_words, pl.bit_offset + first_b, hi, lo);
-            e->hi = hi; e->lo = lo; e->nb = block_budget(first_b, pl.n_bits, n);
-        }
-        wave_lds_fence();
-        const uint32_t todo = min(total - base, (uint32_t)CAP);
-        for (uint32_t first = 0; first < todo; first += 8u) {
-            const uint32_t idx = first + (lane >> 3);
-            if (idx < todo) {
-                GuardEntry *e = &entries[idx];
-                guard_replay8<QM, UROWS>(e->px, e->hi, e->lo, e->nb, tile + (lane >> 3) * SVS_GUARD_TILE, lane & 7u, n, qp);
-            }
-        }
-        wave_lds_fence();
-        if (mine_a) {
-            const GuardEntry *e = &entries[rank_a - base];
+            if constexpr (KEPT) { hi = hi_kept; lo = 0; }   // n <= 15: the window's first word, still in a register from phase 1
+            else payload_window(pl.bits, pl.n_words, pl.bit_offset + first, hi, lo);
+            e->hi = hi; e->lo = lo; e->nb = block_budget(first, pl.n_bits, n);
+        },
+        [&](uint32_t i, uint32_t grp, uint32_t r) {
+            GuardEntry *e = &entries[i];
+            guard_replay8<QM, UROWS>(e->px, e->hi, e->lo, e->nb, tile + grp * SVS_GUARD_TILE, r, n, qp);
+        },
+        [&](int, uint32_t i) {
+            const GuardEntry *e = &entries[i];
 #pragma unroll
             for (int r = 0; r < 8; ++r) { ax[r] = e->px[2 * r]; ay[r] = e->px[2 * r + 1]; }
-        }
-        if (mine_b) {
-            const GuardEntry *e = &entries[rank_b - base];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) { bx[r] = e->px[2 * r]; by[r] = e->px[2 * r + 1]; }
-        }
-        wave_lds_fence();   // the next round overwrites the entries
-    }
-    return total;
+        });
 }
 
 // phase 2 over PARKED rows (round 4; the two-row kernel): every lane has written its block's original rows to its slot of a
 // wave-private LDS array before phase 1 (slot = lane, SVS_SLOT_DWORDS apart), so phase 1 works in place and an undecided block
 // needs no deposit: the worklist is a list of {slot, budget, payload window} words, the exact replay reads and writes the
-// slots, and the owners of undecided blocks read theirs back.  No rounds: the worklist holds all 64 lanes if it must.
+// slots, and the owners of undecided blocks read theirs back.  One round: the worklist holds all 64 lanes if it must.
 #define SVS_SLOT_DWORDS 18   // 16 row dwords + 2: 8-byte aligned, and 16 consecutive lanes hit 16 different even banks
 template <int QM>
 __device__ __forceinline__ uint32_t guard_phase2_slots(uint32_t *slots, u32x2 *meta, float *tile, uint32_t lane, uint32_t n,
                                                        const QimParams &qp, bool und, uint32_t nb, uint32_t hi,
                                                        uint32_t (&ax)[8], uint32_t (&ay)[8]) {
-    const uint64_t mask = __ballot(und);
-    if (mask == 0) return 0;   // wave-uniform
-    const uint32_t total = (uint32_t)__popcll(mask);
-    if (und) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        u32x2 m; m.x = lane | (nb << 8); m.y = hi;
-        meta[rank] = m;
-    }
-    wave_lds_fence();
-    for (uint32_t at = 0; at < total; at += 8u) {   // wave-uniform
-        const uint32_t idx = at + (lane >> 3);
-        if (idx < total) {
-            const u32x2 m = meta[idx];
-            guard_replay8<QM, 2>(slots + (m.x & 0xffu) * SVS_SLOT_DWORDS, m.y, 0u, m.x >> 8, tile + (lane >> 3) * SVS_GUARD_TILE, lane & 7u, n, qp);
-        }
-    }
-    wave_lds_fence();
-    if (und) {
-        const u32x2 *mine = reinterpret_cast<const u32x2 *>(slots + lane * SVS_SLOT_DWORDS);
+    return wave_worklist<64>(
+        {und}, lane,
+        [&](int, uint32_t i) { u32x2 m; m.x = lane | (nb << 8); m.y = hi; meta[i] = m; },
+        [&](uint32_t i, uint32_t grp, uint32_t r) {
+            const u32x2 m = meta[i];
+            guard_replay8<QM, 2>(slots + (m.x & 0xffu) * SVS_SLOT_DWORDS, m.y, 0u, m.x >> 8, tile + grp * SVS_GUARD_TILE, r, n, qp);
+        },
+        [&](int, uint32_t) {
+            const u32x2 *mine = reinterpret_cast<const u32x2 *>(slots + lane * SVS_SLOT_DWORDS);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { const u32x2 v = mine[r]; ax[r] = v.x; ay[r] = v.y; }
-    }
-    return total;
+            for (int r = 0; r < 8; ++r) { const u32x2 v = mine[r]; ax[r] = v.x; ay[r] = v.y; }
+        });
 }
 
 // Register targets (waves per SIMD) of the embed kernels: natural allocation.  (One row: 96 VGPRs, 5 waves; spills in the
@@ -644,8 +627,7 @@ __global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint
     } else {
         const GuardPayload pl{bits, bit_offset, n_bits, n_words};
         const uint64_t first = KEYED ? first_keyed : (uint64_t)gblock * n;
-        redone = guard_phase2<QM, false, SVS_GUARD_CAP, true>(&entries[wave][0], &tiles[wave][0], lane, n, qp, pl, und, first, ax, ay,
-                                                              false, first, ax, ay, hi, 0u);
+        redone = guard_phase2<QM, SVS_GUARD_CAP, true>(&entries[wave][0], &tiles[wave][0], lane, n, qp, pl, und, first, ax, ay, hi);
     }
 #if defined(SVS_EXPERIMENTS)
     if (replay_counter != nullptr && redone != 0 && lane == 0) atomicAdd(replay_counter, (unsigned long long)redone);
@@ -704,45 +686,28 @@ __device__ __forceinline__ void row1_collect(const GuardEntry *e, typename RowVe
     }
 }
 
-// phase 2 of the one-row kernel: guard_phase2 on the row vectors (the payload windows are kept from phase 1)
+// phase 2 of the one-row kernel: guard_phase2 on the row vectors, one or two blocks per lane (the payload windows are kept
+// from phase 1)
 template <int QM, int BPL, int CAP, bool KEYED = false>   // KEYED: block B's first stream bit is first_b, not first_a + n
 __device__ __forceinline__ uint32_t row1_phase2(GuardEntry *entries, float *tile, uint32_t lane, uint32_t n, const QimParams &qp,
                                                 uint64_t n_bits, bool und_a, bool und_b, uint64_t first_a, uint64_t first_b, uint32_t hi_a,
                                                 uint32_t hi_b, typename RowVec<BPL>::type (&v)[8]) {
-    const uint64_t mask_a = __ballot(und_a);
-    const uint64_t mask_b = BPL == 2 ? __ballot(und_b) : 0ull;
-    if ((mask_a | mask_b) == 0) return 0;   // wave-uniform: the common case costs two ballots
-    const uint32_t n_a = (uint32_t)__popcll(mask_a), total = n_a + (uint32_t)__popcll(mask_b);
-    const uint32_t rank_a = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask_a >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask_a, 0u));
-    const uint32_t rank_b = n_a + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask_b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask_b, 0u));
-    for (uint32_t base = 0; base < total; base += (uint32_t)CAP) {   // wave-uniform
-        const bool mine_a = und_a && rank_a >= base && rank_a < base + (uint32_t)CAP;
-        const bool mine_b = BPL == 2 && und_b && rank_b >= base && rank_b < base + (uint32_t)CAP;
-        if (mine_a) {
-            GuardEntry *e = &entries[rank_a - base];
-            row1_deposit<BPL>(e, v, 0);
-            e->hi = hi_a; e->lo = 0u; e->nb = block_budget(first_a, n_bits, n);
-        }
-        if (mine_b) {
-            GuardEntry *e = &entries[rank_b - base];
-            row1_deposit<BPL>(e, v, 1);
-            e->hi = hi_b; e->lo = 0u; e->nb = block_budget(KEYED ? first_b : first_a + n, n_bits, n);
-        }
-        wave_lds_fence();
-        const uint32_t todo = min(total - base, (uint32_t)CAP);
-        for (uint32_t first = 0; first < todo; first += 8u) {
-            const uint32_t idx = first + (lane >> 3);
-            if (idx < todo) {
-                GuardEntry *e = &entries[idx];
-                guard_replay8<QM, 1>(e->px, e->hi, e->lo, e->nb, tile + (lane >> 3) * SVS_GUARD_TILE, lane & 7u, n, qp);
-            }
-        }
-        wave_lds_fence();
-        if (mine_a) row1_collect<BPL>(&entries[rank_a - base], v, 0);
-        if (mine_b) row1_collect<BPL>(&entries[rank_b - base], v, 1);
-        wave_lds_fence();   // the next round overwrites the entries
-    }
-    return total;
+    bool und[BPL];
+    und[0] = und_a;
+    if constexpr (BPL == 2) und[1] = und_b;
+    return wave_worklist<CAP>(
+        und, lane,
+        [&](int j, uint32_t i) {
+            GuardEntry *e = &entries[i];
+            row1_deposit<BPL>(e, v, j);
+            e->hi = j ? hi_b : hi_a; e->lo = 0u;
+            e->nb = block_budget(j ? (KEYED ? first_b : first_a + n) : first_a, n_bits, n);
+        },
+        [&](uint32_t i, uint32_t grp, uint32_t r) {
+            GuardEntry *e = &entries[i];
+            guard_replay8<QM, 1>(e->px, e->hi, e->lo, e->nb, tile + grp * SVS_GUARD_TILE, r, n, qp);
+        },
+        [&](int j, uint32_t i) { row1_collect<BPL>(&entries[i], v, j); });
 }
 
 // what the lanes of a launch share (kernel arguments, in SGPRs)
@@ -937,35 +902,18 @@ __device__ __forceinline__ float group8_max(float v) {
     return fmaxf(v, __shfl_xor(v, 4, 64));
 }
 
-// pocketfft's forward transform of the block in `px` from eight lanes: lane r transforms pixel column r, then coefficient
-// row r (forward_exact's operations, per line) -> c = coefficient row r.  t: the group's 64-float tile.
-__device__ __forceinline__ void forward8(const uint32_t *px, float *t, uint32_t r, float (&c)[8]) {
-    float col[8], out[8];
-#pragma unroll
-    for (int y = 0; y < 8; ++y) col[y] = (float)((px[2 * y + (r >> 2)] >> (8 * (r & 3))) & 0xffu);
-    pf::dct2_8(col, out);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[8 * u + r] = out[u];
-    wave_lds_fence();
-    float row[8];
-#pragma unroll
-    for (int x = 0; x < 8; ++x) row[x] = t[8 * r + x];
-    wave_lds_fence();
-    pf::dct2_8(row, c);
-}
-
 // svs_readback.hpp repair_block on eight lanes (r = 0..7) of one worklist entry: px = its rows in LDS (in: the reference's
-// stego; out: the last iterate), t = the group's tile.  The same operations on the same values, so the same bytes; true (in
-// all eight lanes) when an iterate read back.
+// stego; out: the last iterate), t = the group's 64-float tile.  The same operations on the same values, so the same bytes;
+// true (in all eight lanes) when an iterate read back.
 template <int QM>
 __device__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
     float c[8], T[8];
-    forward8(px, t, r, c);
+    forward8<8>(px, t, r, c);
     repair_targets_row<QM>(c, (int)r, nb, hi, lo, qp, T);
 #pragma unroll 1
     for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
         const float scale = 1.0f + 0.5f * (float)it;
-        float d[8], col[8], out[8], row[8], y[8];
+        float d[8], col[8], row[8], y[8];
         repair_correction_row(T, c, (int)r, nb, scale, d);
 #pragma unroll
         for (int x = 0; x < 8; ++x) t[8 * r + x] = d[x];            // coefficient row r
@@ -973,14 +921,8 @@ __device__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_
 #pragma unroll
         for (int u = 0; u < 8; ++u) col[u] = t[8 * u + r];          // coefficient column r
         wave_lds_fence();
-        pf::dct3_8(col, out);                                        // -> column r of P
-#pragma unroll
-        for (int v = 0; v < 8; ++v) t[8 * v + r] = out[v];
+        inverse8<8>(col, t, r, row);                                 // row r of P
         wave_lds_fence();
-#pragma unroll
-        for (int x = 0; x < 8; ++x) col[x] = t[8 * r + x];          // row r of P
-        wave_lds_fence();
-        pf::dct3_8(col, row);
         float mn = 1e30f, mx = -1e30f;
         repair_add_row(px[2 * r], px[2 * r + 1], row, y, mn, mx);
         const float s = repair_shift(group8_min(mn), group8_max(mx));
@@ -989,7 +931,7 @@ __device__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_
         px[2 * r] = lo4;
         px[2 * r + 1] = hi4;
         wave_lds_fence();
-        forward8(px, t, r, c);
+        forward8<8>(px, t, r, c);
         if (group8_or(row_misses<QM>(c, (int)r, nb, hi, lo, qp) ? 1u : 0u) == 0) return true;
     }
     return false;
@@ -1030,7 +972,9 @@ __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const 
     const uint64_t mask = __ballot(bad);
     if (mask == 0) return;               // wave-uniform: content without failures
     const uint32_t total = (uint32_t)__popcll(mask);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    const uint32_t rank = wave_rank(mask);
+    // The worklist written out rather than through wave_worklist: the rounds and passes stay loops (#pragma unroll 1) with a
+    // fence after every pass, and through the driver readback_kernel<8, 2, true> took 125 instead of 118 VGPRs.
     uint32_t *wslots = &slots[wave][0];
     u32x4 *wmeta = &meta[wave][0];
     const uint32_t grp = lane >> 3, r = lane & 7u;
@@ -1534,7 +1478,7 @@ __global__ __launch_bounds__(SVS_WG) void embed_bgr_kernel(const uint8_t *bgr_in
                                                         const uint32_t *__restrict__ bits, const uint64_t bit_offset,
                                                         const uint64_t n_bits, const uint32_t n_words) {
     // one wave-private 4 KB region per wave: row staging of the cooperative load, then (streaming arithmetic) the worklist and transposition
-    // tile of the exact replay (svs::guard_phase2, 16 entries per round), then the stego tile of the cooperative store
+    // tile of the exact replay (guard_phase2 with 16 entries per round), then the stego tile of the cooperative store
     __shared__ __attribute__((aligned(16))) u32x2 lds_tile[SVS_WG / 64][8][64];
     static_assert(16 * sizeof(GuardEntry) + 8 * SVS_GUARD_TILE * sizeof(float) <= 8 * 64 * sizeof(u32x2), "wave region too small");
     const uint32_t tile = tile_id(g.xcd_chunk);
@@ -1573,8 +1517,7 @@ __global__ __launch_bounds__(SVS_WG) void embed_bgr_kernel(const uint8_t *bgr_in
         GuardEntry *entries = reinterpret_cast<GuardEntry *>(&lds_tile[wave][0][0]);
         float *t = reinterpret_cast<float *>(entries + 16);
         const GuardPayload pl{bits, bit_offset, n_bits, n_words};
-        const uint64_t first = (uint64_t)gblock * g.n_ac;
-        guard_phase2<QM, false, 16, KEPT>(entries, t, lane, g.n_ac, qp, pl, und, first, ax, ay, false, first, ax, ay, hi_kept, 0u);
+        guard_phase2<QM, 16, KEPT>(entries, t, lane, g.n_ac, qp, pl, und, (uint64_t)gblock * g.n_ac, ax, ay, hi_kept);
     }
     if constexpr (KEEP)
         wave_store_keep_colour(&lds_tile[wave][0][0], lane, gblock, ax, ay, bgr_in, bgr_out, g, c);
@@ -1610,8 +1553,7 @@ __global__ __launch_bounds__(SVS_WG) void extract_bgr_kernel(const uint8_t *__re
         if (__ballot(tie) != 0) {
             if (gblock < g.total_blocks) tie = extract_block_settle<QM>(ax, ay, n, qp, hi, off);
         }
-        uint32_t hb = 0, lb = 0;
-        extract_phase2<QM, false, SVS_EXTRACT_CAP>(&entries[wave][0], &tiles[wave][0], lane, n, qp, tie, ax, ay, hi, lo, false, ax, ay, hb, lb);
+        extract_phase2<QM, SVS_EXTRACT_CAP>(&entries[wave][0], &tiles[wave][0], lane, n, qp, tie, ax, ay, hi, lo);
     } else {
         if (gblock < g.total_blocks) extract_block_exact<U, QM>(ax, ay, n, qp, hi, lo);
     }

@@ -1,7 +1,8 @@
 // svs_readback.hpp - per-block arithmetic of the opt-in read-back pass (SVS_READBACK, include/svsdct.h): read a stego block
 // back with the reference's extraction arithmetic and, where its payload bits do not come back, search for a block whose
 // bits do.  Plain C++ on register values, like svs_block.hpp: csrc/svs_device.hpp checks one block per lane and repairs
-// one block on eight lanes with the per-line steps below (readback_kernel, repair8); tests/readback builds the one-lane
+// one block on eight lanes with the per-line steps below and the embed kernels' eight-lane forward / inverse passes
+// (readback_kernel, repair8: forward8 / inverse8 on 64-float tiles); tests/readback builds the one-lane
 // form with g++ for the CPU tier.  Both builds use -ffp-contract=off; the repair
 // rounds to nearest after float arithmetic, so host and device must execute the same operations in the same order: the
 // transforms are svs_block.hpp's pocketfft replays (their fmaf only where it is exact), every other operation below is one
