@@ -94,8 +94,8 @@ extern "C" {
  * default (flag clear) is still the reference's COLOR_GRAY2BGR output, byte for byte. */
 #define SVS_KEEP_COLOUR 0x100u
 /* SVS_READBACK (the gray embed calls: svs_embed_dev, svs_embed, svs_embed_str, svs_embed_ordered_dev, svs_embed_ordered and
- * the svs_embed_readback* calls below; the extract calls and the fused colour calls reject it with SVS_ERR_INVALID_ARG -
- * colour support is follow-up work): opt-in.  The reference's own stego can fail to decode: it clips the inverse transform to
+ * the svs_embed_readback* calls below; the extract calls and svs_embed_bgr / svs_embed_bgr_dev reject it with
+ * SVS_ERR_INVALID_ARG - the fused colour embed with read-back is svs_embed_bgr_readback* below): opt-in.  The reference's own stego can fail to decode: it clips the inverse transform to
  * [0, 255] and truncates it (config_and_setup.py:166-171), and in blocks near black or white (letterbox bars, flat or
  * saturated areas) that moves payload coefficients across a decision boundary - one wrong bit makes the receiver's AES-GCM
  * reject the whole payload.  With the flag the call first produces exactly the stego it produces without it, then reads
@@ -327,6 +327,28 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
                   uint64_t n_bits, uint32_t flags, uint64_t *n_embedded);
 int svs_extract_bgr(const uint8_t *bgr, const svs_planes *planes, const uint32_t *weights, double delta, int n_ac,
                     uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint64_t *n_bits_out);
+
+/* The fused colour embed with read-back and repair: svs_embed_bgr_dev / svs_embed_bgr followed, on the call's stream, by the
+ * read-back pass in place on the BGR output (SVS_READBACK accepted and implied; flags: the mode bits and SVS_KEEP_COLOUR;
+ * no keyed block order).  d_counts / counts as in svs_embed_readback*.  With gray() the call's fixed-point gray (weights),
+ * G = gray(cover) and R = the stego planes and counts svs_embed_readback (order NULL) gives for G with the same delta,
+ * n_ac, payload, bit_offset and mode bits:
+ *   plain            the output is B = G = R = R's stego, byte for byte: gray_to_bgr(svs_embed_readback(bgr_to_gray(cover))).
+ *   SVS_KEEP_COLOUR  a block that reads back keeps the bytes svs_embed_bgr_dev(..., SVS_KEEP_COLOUR) writes.  In a repaired
+ *                    block every pixel is the keep-colour pixel (csrc/svs_colour.hpp) of P and t', P = the pixel the
+ *                    keep-colour embed wrote (the pass works in place on the output: d_bgr_in == d_bgr_out is allowed),
+ *                    t' = the repaired gray.  So gray(output) == R's stego exactly, a pixel whose gray the repair did not
+ *                    change keeps its bytes, and an unrepaired block keeps its bytes.
+ * The counts equal R's.  d_gray_ref / gray_ref_out stay the cover gray.  Blocks past the payload budget are not touched by
+ * the pass; on content without failures the output is byte-identical to svs_embed_bgr_dev / svs_embed_bgr. */
+int svs_embed_bgr_readback_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_frame_pitch,
+                               uint8_t *d_bgr_out, int64_t out_row_pitch, int64_t out_frame_pitch,
+                               uint8_t *d_gray_ref, const svs_planes *planes, const uint32_t *weights,
+                               double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                               uint32_t flags, uint64_t *n_embedded, uint64_t *d_counts, void *stream);
+int svs_embed_bgr_readback(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, const svs_planes *planes,
+                           const uint32_t *weights, double delta, int n_ac, const uint8_t *bits_packed, uint64_t bit_offset,
+                           uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, svs_readback_counts *counts);
 
 /* ---- measurement helpers (synthetic inputs and on-device checks for bench.py / tests) ------ */
 /* value = lo + hash32(seed, first_frame + f, y, x) % span  - same hash as svsdct/synth.py; 1 <= span, lo + span <= 256 */

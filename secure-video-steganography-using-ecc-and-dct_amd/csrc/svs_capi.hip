@@ -237,45 +237,61 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
 }
 
 // SVS_READBACK: readback_kernel<rows, QM> over the stego planes the embed has just written, on the same stream, with the
-// embed's payload arguments (the plan's rows are 1 or 2 for n <= 15, else 8: the quantiser loop's coefficient rows)
+// embed's payload arguments (the plan's rows are 1 or 2 for n <= 15, else 8: the quantiser loop's coefficient rows).
+// The colour calls pass their BGR output as `stego`, its pitches and the call's weights in `colour`, and form = SVS_RB_BGR:
+// they run the colour body of their quantiser mode, which lives in one instantiation (plain and keep-colour output alike).
 int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uint8_t *stego, svs::Geometry g, const uint32_t *bits,
-                    uint64_t *counts, const svs::BlockOrderArgs &ord) {
+                    uint64_t *counts, const svs::BlockOrderArgs &ord, const svs::ColourParams &colour = svs::ColourParams{},
+                    uint32_t form = SVS_RB_GRAY) {
     g.n_ac = p.n_ac;
     g.xcd_chunk = svs::kEighth;
     const uint32_t words = (uint32_t)p.n_words;
     auto *c = reinterpret_cast<unsigned long long *>(counts);
+    if (form != SVS_RB_GRAY)   // the one instantiation that holds the colour bodies (svs_device.hpp SVS_RB_HOSTS_COLOUR)
+        return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
+                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_BGR + p.qm), svs::BlockOrderArgs{});
     return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
         return dispatch<1, 2, 8>(p.rows, [&](auto u) {
             constexpr int U = decltype(u)::value;
             if (p.keyed)
                 return launch(svs::readback_kernel<U, QM, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words, c, ord);
-            return launch(svs::readback_kernel<U, QM>, grid_for(total), 0, st, stego, g, p.qp, bits, p.bit_offset, p.n_bits, words, c);
+                              p.bit_offset, p.n_bits, words, c, colour, form, ord);
+            return launch(svs::readback_kernel<U, QM>, grid_for(total), 0, st, stego, g, p.qp, bits, p.bit_offset, p.n_bits, words, c,
+                          colour, form);
         });
     });
 }
 
-// svs_embed_bgr_dev's plan: embed_bgr_kernel<8, QM, true> (exact, round trip) or <1 | 2, QM, false> (streaming, convert)
+// svs_embed_bgr_dev's plan: embed_bgr_kernel<8, QM, true> (exact, round trip) or <1 | 2, QM, false> (streaming, convert).
+// A plan with the read-back bit (svs_embed_bgr_readback_dev) is followed by readback_kernel in its colour form, in place on
+// `out` (counts: device, added to; NULL for none).
 int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStream_t st, const uint8_t *in, uint8_t *out,
-                     uint8_t *ref, svs::Geometry g, const svs::ColourParams &c, const uint32_t *bits) {
+                     uint8_t *ref, svs::Geometry g, const svs::ColourParams &c, const uint32_t *bits, uint64_t *counts = nullptr) {
+    const svs::Geometry planes = g;
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
     const uint32_t words = (uint32_t)p.n_words;
     const bool exact = p.path == EmbedPath::EXACT || p.path == EmbedPath::ROUND_TRIP;
-    return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
-        return with_bool(keep, [&](auto keep_c) {
-            constexpr int QM = decltype(qm)::value;
-            constexpr bool KEEP = decltype(keep_c)::value;
-            if (exact)
-                return launch(svs::embed_bgr_kernel<8, QM, true, KEEP>, grid_for(total), 0, st, in, out, ref, g, c, p.qp, bits,
-                              p.bit_offset, p.n_bits, words);
-            return dispatch<1, 2>(p.rows, [&](auto u) {
-                return launch(svs::embed_bgr_kernel<decltype(u)::value, QM, false, KEEP>, grid_for(total), 0, st, in, out, ref, g, c,
-                              p.qp, bits, p.bit_offset, p.n_bits, words);
+    if (int rc = dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
+            return with_bool(keep, [&](auto keep_c) {
+                constexpr int QM = decltype(qm)::value;
+                constexpr bool KEEP = decltype(keep_c)::value;
+                if (exact)
+                    return launch(svs::embed_bgr_kernel<8, QM, true, KEEP>, grid_for(total), 0, st, in, out, ref, g, c, p.qp, bits,
+                                  p.bit_offset, p.n_bits, words);
+                return dispatch<1, 2>(p.rows, [&](auto u) {
+                    return launch(svs::embed_bgr_kernel<decltype(u)::value, QM, false, KEEP>, grid_for(total), 0, st, in, out, ref, g,
+                                  c, p.qp, bits, p.bit_offset, p.n_bits, words);
+                });
             });
-        });
-    });
+        }))
+        return rc;
+    if (!(p.readback && p.use > 0)) return SVS_OK;
+    svs::ColourParams in_place = c;   // the pass reads and writes the output
+    in_place.in_row_pitch = c.out_row_pitch;
+    in_place.in_frame_pitch = c.out_frame_pitch;
+    return launch_readback(p, total, st, out, planes, bits, counts, svs::BlockOrderArgs{}, in_place, SVS_RB_BGR);
 }
 
 // svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>.  A keyed plan ORs every block's bits into its
@@ -1059,32 +1075,56 @@ static int colour_params(const svs_planes *p, const void *in, int64_t irp, int64
     return SVS_OK;
 }
 
-int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_frame_pitch, uint8_t *d_bgr_out,
-                      int64_t out_row_pitch, int64_t out_frame_pitch, uint8_t *d_gray_ref, const svs_planes *planes,
-                      const uint32_t *weights, double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset,
-                      uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, void *stream) {
+constexpr uint32_t kBgrEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR;
+
+// svs_embed_bgr_dev (allowed = kBgrEmbedFlags: SVS_READBACK is refused) and svs_embed_bgr_readback_dev (the flag accepted and
+// implied; d_counts: the read-back counts, device, added to; NULL for none)
+static int embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_frame_pitch, uint8_t *d_bgr_out,
+                         int64_t out_row_pitch, int64_t out_frame_pitch, uint8_t *d_gray_ref, const svs_planes *planes,
+                         const uint32_t *weights, double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset,
+                         uint64_t n_bits, uint32_t flags, uint32_t allowed, uint64_t *n_embedded, uint64_t *d_counts, void *stream) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
     if (total == 0) return SVS_OK;
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR))
-        return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (flags & ~allowed) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
     if (d_gray_ref && ((uintptr_t)d_gray_ref % 8)) return fail(SVS_ERR_INVALID_ARG, "gray pointer must be 8-byte aligned");
+    if (d_counts && ((uintptr_t)d_counts % 8)) return fail(SVS_ERR_INVALID_ARG, "counts pointer must be 8-byte aligned");
     svs::ColourParams c;
     if (int rc = colour_params(planes, d_bgr_in, in_row_pitch, in_frame_pitch, d_bgr_out, out_row_pitch, out_frame_pitch,
                                weights, &c))
         return rc;
     if (!d_bgr_out) return fail(SVS_ERR_INVALID_ARG, "output pointer is NULL");
-    const svs::EmbedPlan p = svs::plan_embed(route_args(delta, g, total, n_bits, bit_offset, flags, true));
+    svs::RouteArgs ra = route_args(delta, g, total, n_bits, bit_offset, flags, true);
+    ra.readback = (allowed & SVS_READBACK) != 0;
+    const svs::EmbedPlan p = svs::plan_embed(ra);
     if (p.use > 0 && (!d_bits_packed || ((uintptr_t)d_bits_packed % 4)))
         return fail(SVS_ERR_INVALID_ARG, "bits pointer NULL or not 4-byte aligned");
     if (p.n_words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
     if (int rc = launch_embed_bgr(p, (flags & SVS_KEEP_COLOUR) != 0, total, (hipStream_t)stream, d_bgr_in, d_bgr_out, d_gray_ref, g,
-                                  c, p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr))
+                                  c, p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr, d_counts))
         return rc;
     if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
+}
+
+int svs_embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_frame_pitch, uint8_t *d_bgr_out,
+                      int64_t out_row_pitch, int64_t out_frame_pitch, uint8_t *d_gray_ref, const svs_planes *planes,
+                      const uint32_t *weights, double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset,
+                      uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, void *stream) {
+    return embed_bgr_dev(d_bgr_in, in_row_pitch, in_frame_pitch, d_bgr_out, out_row_pitch, out_frame_pitch, d_gray_ref, planes,
+                         weights, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, kBgrEmbedFlags, n_embedded, nullptr, stream);
+}
+
+int svs_embed_bgr_readback_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t in_frame_pitch, uint8_t *d_bgr_out,
+                               int64_t out_row_pitch, int64_t out_frame_pitch, uint8_t *d_gray_ref, const svs_planes *planes,
+                               const uint32_t *weights, double delta, int n_ac, const uint8_t *d_bits_packed,
+                               uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, uint64_t *d_counts,
+                               void *stream) {
+    return embed_bgr_dev(d_bgr_in, in_row_pitch, in_frame_pitch, d_bgr_out, out_row_pitch, out_frame_pitch, d_gray_ref, planes,
+                         weights, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, kBgrEmbedFlags | SVS_READBACK, n_embedded,
+                         d_counts, stream);
 }
 
 int svs_extract_bgr_dev(const uint8_t *d_bgr, int64_t bgr_row_pitch, int64_t bgr_frame_pitch, const svs_planes *planes,
@@ -1111,18 +1151,21 @@ static int packed_planes_only(const svs_planes *p) {
     return SVS_OK;
 }
 
-int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, const svs_planes *planes,
-                  const uint32_t *weights, double delta, int n_ac, const uint8_t *bits_packed, uint64_t bit_offset,
-                  uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
+// svs_embed_bgr (counts NULL: SVS_READBACK is refused) and svs_embed_bgr_readback (counts: the read-back counts of the whole
+// call, summed over the staging chunks as embed_host does)
+static int embed_bgr_host(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, const svs_planes *planes,
+                          const uint32_t *weights, double delta, int n_ac, const uint8_t *bits_packed, uint64_t bit_offset,
+                          uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, svs_readback_counts *counts) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
+    if (counts) *counts = svs_readback_counts{0, 0};
     if (total == 0) return SVS_OK;
     if (int rc = packed_planes_only(planes)) return rc;
     if (!bgr || !bgr_out) return fail(SVS_ERR_INVALID_ARG, "BGR pointer is NULL");
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR))
-        return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    const uint32_t allowed = kBgrEmbedFlags | (counts ? SVS_READBACK : 0u);
+    if (flags & ~allowed) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
     const uint64_t px = (uint64_t)planes->n_frames * planes->height * planes->width;
     const uint64_t cap = total * (uint64_t)g.n_ac;
     uint64_t use = n_bits < cap ? n_bits : cap;
@@ -1131,17 +1174,23 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
     if (use && bit_offset + use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
     const HostPayload payload{bits_packed, nullptr, bit_offset, use};
     uint64_t done_total = 0;
-    if (int rc = staged(3 * px, 3 * px, gray_ref_out ? px : 0, payload.bits_bytes(), [&](HostStage &c) {
+    // the read-back counts: two u64 in c.bits behind the payload, as in embed_host
+    const size_t counts_at = (payload.bits_bytes() + 7) & ~(size_t)7;
+    uint64_t got_counts[2] = {0, 0};
+    if (int rc = staged(3 * px, 3 * px, gray_ref_out ? px : 0, counts ? counts_at + 16 : payload.bits_bytes(), [&](HostStage &c) {
             uint64_t rebased = 0;
             if (int rc = payload.stage(c, &rebased)) return rc;
+            uint64_t *d_counts = counts ? reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c.bits.p) + counts_at) : nullptr;
+            if (d_counts) SVS_HIP(hipMemsetAsync(d_counts, 0, 16, c.st[0]));
             uint8_t *d_in = static_cast<uint8_t *>(c.frames.p), *d_out = static_cast<uint8_t *>(c.second.p),
                     *d_ref = gray_ref_out ? static_cast<uint8_t *>(c.third.p) : nullptr;
-            return embed_chunks(
+            const int rc = embed_chunks(
                 c, planes, 3, bgr, g.n_ac, use, n_bits, rebased,
                 [&](const svs_planes &sub, int64_t off, int32_t, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
                     const int64_t rp = 3 * sub.row_pitch, fp = 3 * sub.frame_pitch;
-                    return svs_embed_bgr_dev(d_in + off, rp, fp, d_out + off, rp, fp, d_ref ? d_ref + off / 3 : nullptr, &sub, weights,
-                                             delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset, budget, flags, done, up);
+                    return embed_bgr_dev(d_in + off, rp, fp, d_out + off, rp, fp, d_ref ? d_ref + off / 3 : nullptr, &sub, weights,
+                                         delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset, budget, flags, allowed,
+                                         done, d_counts, up);
                 },
                 [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {   // tightly packed frames: every chunk is one run of bytes
                     const uint64_t n_px = (uint64_t)ch.nf * ch.rows * planes->width;
@@ -1149,10 +1198,28 @@ int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, c
                     return d_ref ? stage_d2h(st, gray_ref_out + off / 3, d_ref + off / 3, n_px) : (int)SVS_OK;
                 },
                 &done_total);
+            if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, 16, hipMemcpyDeviceToHost, c.st[0]));
+            return rc;
         }))
         return rc;
     if (n_embedded) *n_embedded = done_total;
+    if (counts) *counts = svs_readback_counts{got_counts[0], got_counts[1]};
     return SVS_OK;
+}
+
+int svs_embed_bgr(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, const svs_planes *planes,
+                  const uint32_t *weights, double delta, int n_ac, const uint8_t *bits_packed, uint64_t bit_offset,
+                  uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
+    return embed_bgr_host(bgr, bgr_out, gray_ref_out, planes, weights, delta, n_ac, bits_packed, bit_offset, n_bits, flags,
+                          n_embedded, nullptr);
+}
+
+int svs_embed_bgr_readback(const uint8_t *bgr, uint8_t *bgr_out, uint8_t *gray_ref_out, const svs_planes *planes,
+                           const uint32_t *weights, double delta, int n_ac, const uint8_t *bits_packed, uint64_t bit_offset,
+                           uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, svs_readback_counts *counts) {
+    svs_readback_counts none;
+    return embed_bgr_host(bgr, bgr_out, gray_ref_out, planes, weights, delta, n_ac, bits_packed, bit_offset, n_bits, flags,
+                          n_embedded, counts ? counts : &none);
 }
 
 int svs_extract_bgr(const uint8_t *bgr, const svs_planes *planes, const uint32_t *weights, double delta, int n_ac,

@@ -871,6 +871,53 @@ __global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__
 }
 
 // ---------------------------------------------------------------------------------------
+// Interleaved BGR rows (the colour plumbing further down, and the colour form of the read-back pass)
+// ---------------------------------------------------------------------------------------
+struct ColourParams {
+    int64_t in_row_pitch, in_frame_pitch;    // BGR input
+    int64_t out_row_pitch, out_frame_pitch;  // BGR output
+    uint32_t wb, wg, wr, shift;              // (B*wb + G*wg + R*wr + 2^(shift-1)) >> shift
+};
+
+__device__ __forceinline__ int64_t block_offset_bgr(uint32_t gblock, const Geometry &g, int64_t row_pitch,
+                                                    int64_t frame_pitch) {
+    const uint32_t frame = fast_div(gblock, g.by_bpf);
+    const uint32_t in_frame = gblock - frame * g.by_bpf.div;
+    const uint32_t brow = fast_div(in_frame, g.by_wb);
+    const uint32_t bcol = in_frame - brow * g.by_wb.div;
+    return (int64_t)frame * frame_pitch + (int64_t)(brow * 8u) * row_pitch + (int64_t)(bcol * 24u);
+}
+
+// One block row of interleaved BGR = 24 bytes at an 8-byte aligned address: three 8-byte accesses.  (A 16-byte +
+// an 8-byte access is no faster for loads and 1.7x SLOWER for stores - the 16-byte half is misaligned half the time.)
+__device__ __forceinline__ void load_bgr_row(const uint8_t *p, u32x2 &q0, u32x2 &q1, u32x2 &q2) {
+    const u32x2 *row = reinterpret_cast<const u32x2 *>(p);
+    q0 = SVS_LD(row); q1 = SVS_LD(row + 1); q2 = SVS_LD(row + 2);
+}
+__device__ __forceinline__ void store_bgr_row(uint8_t *p, const u32x2 &q0, const u32x2 &q1, const u32x2 &q2) {
+    u32x2 *row = reinterpret_cast<u32x2 *>(p);
+    SVS_ST(q0, row); SVS_ST(q1, row + 1); SVS_ST(q2, row + 2);
+}
+
+// 8 interleaved BGR pixels (6 dwords) -> 8 gray bytes (2 dwords)
+__device__ __forceinline__ void bgr8_to_gray(const u32x2 &q0, const u32x2 &q1, const u32x2 &q2, const ColourParams &c,
+                                             uint32_t &lo4, uint32_t &hi4) {
+    const uint32_t w[6] = {q0.x, q0.y, q1.x, q1.y, q2.x, q2.y};
+    const uint32_t half = 1u << (c.shift - 1);
+    uint32_t px[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int b0 = 3 * j, b1 = 3 * j + 1, b2 = 3 * j + 2;
+        const uint32_t B = (w[b0 >> 2] >> (8 * (b0 & 3))) & 0xffu, G = (w[b1 >> 2] >> (8 * (b1 & 3))) & 0xffu,
+                       R = (w[b2 >> 2] >> (8 * (b2 & 3))) & 0xffu;
+        // B, G, R < 2^8 and the weights <= 2^16: 24-bit multiplies (full rate) are exact
+        px[j] = (__umul24(B, c.wb) + __umul24(G, c.wg) + __umul24(R, c.wr) + half) >> c.shift;
+    }
+    lo4 = px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24);
+    hi4 = px[4] | (px[5] << 8) | (px[6] << 16) | (px[7] << 24);
+}
+
+// ---------------------------------------------------------------------------------------
 // READ-BACK pass (SVS_READBACK, include/svsdct.h): launched on the call's stream after the embed kernel, in place on the
 // stego planes.
 //   check   one lane per block, each block read once: lanes whose block carries payload bits (the block's slot with a keyed
@@ -937,16 +984,176 @@ __device__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_
     return false;
 }
 
+// The colour form (svs_embed_bgr_readback_dev): the same pass in place on the fused colour embed's interleaved BGR output
+// (c: its pitches in out_*, the call's weights).  Check and repair work on gray(BGR), the call's fixed-point gray, so they
+// are the gray pass's; only the way a block's rows come in and leave differs.  A body of its own behind the kernel's
+// wave-uniform `form` argument - no instantiation of its own, and the gray body above it stays as it was.  Raster order
+// only: the colour calls have no keyed order.
+//   check   every block that carries payload is deposited in the worklist - its gray rows computed from its 24-byte rows -
+//           and read back on eight lanes (reads_back8)
+//   repair  the failing entries, as in the gray form
+//   store   keep_colour_pixel(P, t') for the pixels whose gray the repair changed, P = the pixel in the buffer, t' = the
+//           repaired gray - the other pixels keep their bytes.  After the plain embed P = (g, g, g) and the result is
+//           (t', t', t'); after the keep-colour embed it is the cover's colour shifted: one store serves both.
+#define SVS_RB_GRAY 0u
+#define SVS_RB_BGR 1u
+static_assert(64 * 6 <= 8 * 64, "one 24-byte row per lane fits the wave's tiles");
+
+// gray rows of one block from its BGR rows into a worklist entry, a row at a time (only failing blocks come here)
+__device__ __forceinline__ void deposit_bgr_as_gray(const uint8_t *src, int64_t row_pitch, const ColourParams &c, uint32_t *e) {
+#pragma unroll 1
+    for (int y = 0; y < 8; ++y) {
+        u32x2 q0, q1, q2;
+        load_bgr_row(src + (int64_t)y * row_pitch, q0, q1, q2);
+        uint32_t lo4, hi4;
+        bgr8_to_gray(q0, q1, q2, c, lo4, hi4);
+        e[2 * y] = lo4;
+        e[2 * y + 1] = hi4;
+    }
+}
+
+// A repaired block leaves in its colours, a row at a time: the pixels whose gray the repair changed are redone with the exact
+// rule (svs_colour.hpp), one at a time through the lane's 24 bytes of LDS (`row`); a row without such a pixel is not written.
+__device__ __forceinline__ void store_entry_as_bgr(const uint32_t *e, uint8_t *dst, int64_t row_pitch, const ColourParams &c,
+                                                   u32x2 *row) {
+#pragma unroll 1
+    for (int y = 0; y < 8; ++y) {
+        uint8_t *p = dst + (int64_t)y * row_pitch;
+        u32x2 q0, q1, q2;
+        load_bgr_row(p, q0, q1, q2);
+        uint32_t glo, ghi;
+        bgr8_to_gray(q0, q1, q2, c, glo, ghi);
+        const uint32_t tlo = e[2 * y], thi = e[2 * y + 1];
+        const uint32_t xlo = glo ^ tlo, xhi = ghi ^ thi;
+        if ((xlo | xhi) == 0u) continue;
+        uint32_t todo = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            todo |= ((xlo >> (8 * j)) & 0xffu) ? 1u << j : 0u;
+            todo |= ((xhi >> (8 * j)) & 0xffu) ? 1u << (4 + j) : 0u;
+        }
+        row[0] = q0; row[1] = q1; row[2] = q2;
+        uint8_t *pb = reinterpret_cast<uint8_t *>(row);
+        while (todo != 0u) {
+            const uint32_t i = (uint32_t)__builtin_ctz(todo);
+            todo &= todo - 1u;
+            uint32_t B = pb[3 * i], G = pb[3 * i + 1], R = pb[3 * i + 2];
+            const uint32_t t = ((i < 4 ? tlo : thi) >> (8u * (i & 3u))) & 0xffu;
+            keep_colour_pixel(B, G, R, t, c.wb, c.wg, c.wr, c.shift);
+            pb[3 * i] = (uint8_t)B; pb[3 * i + 1] = (uint8_t)G; pb[3 * i + 2] = (uint8_t)R;
+        }
+        store_bgr_row(p, row[0], row[1], row[2]);
+    }
+}
+
+// does the worklist entry px read back?  Eight lanes: the forward transform and acceptance test of repair8, so the verdict is
+// readback_block_ok's (the exact read-back) for every number of coefficient rows
+template <int QM>
+__device__ __forceinline__ bool reads_back8(const uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_t hi, uint32_t lo,
+                                            const QimParams &qp) {
+    float c[8];
+    forward8<8>(px, t, r, c);
+    return group8_or(row_misses<QM>(c, (int)r, nb, hi, lo, qp) ? 1u : 0u) == 0;
+}
+
+// wslots / wmeta / wtiles: the wave's part of readback_kernel's three LDS arrays.  Every block that carries payload goes
+// through the worklist and is CHECKED on eight lanes too (reads_back8): the lane-per-block check of the gray form, fed from BGR,
+// took up to 132 VGPRs with eight coefficient rows - a wave per SIMD of the gray form's - while this body stays within the
+// repair's registers; the arithmetic per block is the same sixteen 8-point transforms, spread over eight lanes.
+template <int QM>
+__device__ __forceinline__ void readback_colour(uint32_t *wslots, u32x4 *wmeta, float *wtiles, uint8_t *bgr, const Geometry &g,
+                                                const QimParams &qp, const uint32_t *__restrict__ bits, const uint64_t bit_offset,
+                                                const uint64_t n_bits, const uint32_t n_words, unsigned long long *counts,
+                                                const ColourParams &c) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
+    const uint32_t n = g.n_ac;
+    uint32_t nb = 0;
+    uint64_t first = 0;
+    if (gblock < g.total_blocks) {
+        first = (uint64_t)gblock * n;
+        nb = block_budget(first, n_bits, n);
+    }
+    const uint64_t mask = __ballot(nb > 0);
+    if (mask == 0) return;               // wave-uniform
+    const uint32_t total = (uint32_t)__popcll(mask);
+    const uint32_t rank = wave_rank(mask);
+    const uint32_t grp = lane >> 3, r = lane & 7u;
+    int64_t off = 0;
+    if (nb > 0) off = block_offset_bgr(gblock, g, c.out_row_pitch, c.out_frame_pitch);
+    uint32_t status = 0;
+#pragma unroll 1
+    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries
+        const bool mine = nb > 0 && rank >= base && rank < base + SVS_RB_CAP;
+        if (mine) {
+            deposit_bgr_as_gray(bgr + off, c.out_row_pitch, c, wslots + (rank - base) * SVS_RB_SLOT);
+            u32x4 m; m.z = nb; m.w = 0u;
+            uint32_t hi, lo;
+            payload_window(bits, n_words, bit_offset + first, hi, lo);
+            m.x = hi; m.y = lo;
+            wmeta[rank - base] = m;
+        }
+        wave_lds_fence();
+        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
+#pragma unroll 1
+        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time
+            const uint32_t idx = at + grp;
+            if (idx < count) {
+                const u32x4 m = wmeta[idx];
+                uint32_t *px = wslots + idx * SVS_RB_SLOT;
+                float *t = wtiles + 64 * grp;
+                if (!reads_back8<QM>(px, t, r, m.z, m.x, m.y, qp)) {   // uniform over the entry's eight lanes
+                    wave_lds_fence();
+                    const bool ok = repair8<QM>(px, t, r, m.z, m.x, m.y, qp);
+                    if (r == 0) wmeta[idx].w = ok ? 1u : 2u;
+                }
+            }
+            wave_lds_fence();
+        }
+        if (mine) {
+            status = wmeta[rank - base].w;
+            if (status == 1)   // the tiles are free between the passes: 24 bytes of them per lane
+                store_entry_as_bgr(wslots + (rank - base) * SVS_RB_SLOT, bgr + off, c.out_row_pitch, c,
+                                   reinterpret_cast<u32x2 *>(wtiles) + 3 * lane);
+        }
+        wave_lds_fence();
+    }
+    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
+    if (counts && lane == 0) {
+        if (rep) atomicAdd(&counts[0], (unsigned long long)__popcll(rep));
+        if (left) atomicAdd(&counts[1], (unsigned long long)__popcll(left));
+    }
+}
+
+// form = SVS_RB_GRAY: `stego` = the gray planes of g, c unused.  form = SVS_RB_BGR + the call's QuantMode: `stego` = the BGR
+// output, readback_colour - in ONE instantiation only.  The colour body depends on the quantiser mode alone (not on U, and it
+// has no order), so all three of its forms live in the instantiation whose gray body leaves the most registers free,
+// readback_kernel<8, QM_POW2, true, BlockOrderArgs> (118 VGPRs), and every colour call launches that one: the other seventeen
+// are the gray pass's code as it was.  (The colour body next to the gray one cost every instantiation that held both 2 - 9
+// VGPRs, and the eight-row ones with a step that is no power of two a wave per SIMD.)
+#define SVS_RB_HOSTS_COLOUR(U, QM, KEYED) ((U) == 8 && (QM) == QM_POW2 && (KEYED))
 template <int U, int QM, bool KEYED = false, class... Order>
 __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const Geometry g, const QimParams qp,
                                                          const uint32_t *__restrict__ bits, const uint64_t bit_offset,
                                                          const uint64_t n_bits, const uint32_t n_words,
-                                                         unsigned long long *counts, const Order... order) {
+                                                         unsigned long long *counts, const ColourParams c, const uint32_t form,
+                                                         const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t slots[SVS_WG / 64][SVS_RB_CAP * SVS_RB_SLOT];
     __shared__ u32x4 meta[SVS_WG / 64][SVS_RB_CAP];
     __shared__ float tiles[SVS_WG / 64][8 * 64];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if constexpr (SVS_RB_HOSTS_COLOUR(U, QM, KEYED)) {
+        if (form != SVS_RB_GRAY) {   // a kernel argument: wave-uniform; form - SVS_RB_BGR = the call's quantiser mode
+            uint32_t *ws = &slots[wave][0];
+            u32x4 *wm = &meta[wave][0];
+            float *wt = &tiles[wave][0];
+            if (form == SVS_RB_BGR + QM_F32) readback_colour<QM_F32>(ws, wm, wt, stego, g, qp, bits, bit_offset, n_bits, n_words, counts, c);
+            else if (form == SVS_RB_BGR + QM_DOUBLE) readback_colour<QM_DOUBLE>(ws, wm, wt, stego, g, qp, bits, bit_offset, n_bits, n_words, counts, c);
+            else readback_colour<QM_POW2>(ws, wm, wt, stego, g, qp, bits, bit_offset, n_bits, n_words, counts, c);
+            return;
+        }
+    }
     const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t n = g.n_ac;
     uint32_t nb = 0;
@@ -1163,50 +1370,7 @@ __global__ __launch_bounds__(256) void bit_errors_kernel(const uint8_t *__restri
 // block = 8 rows x 24 bytes; stego pixels are written as B = G = R = gray (cv2.COLOR_GRAY2BGR).  Every block
 // of these frames is converted; blocks past the payload budget carry their gray value unchanged.
 // ---------------------------------------------------------------------------------------
-struct ColourParams {
-    int64_t in_row_pitch, in_frame_pitch;    // BGR input
-    int64_t out_row_pitch, out_frame_pitch;  // BGR output
-    uint32_t wb, wg, wr, shift;              // (B*wb + G*wg + R*wr + 2^(shift-1)) >> shift
-};
-
-__device__ __forceinline__ int64_t block_offset_bgr(uint32_t gblock, const Geometry &g, int64_t row_pitch,
-                                                    int64_t frame_pitch) {
-    const uint32_t frame = fast_div(gblock, g.by_bpf);
-    const uint32_t in_frame = gblock - frame * g.by_bpf.div;
-    const uint32_t brow = fast_div(in_frame, g.by_wb);
-    const uint32_t bcol = in_frame - brow * g.by_wb.div;
-    return (int64_t)frame * frame_pitch + (int64_t)(brow * 8u) * row_pitch + (int64_t)(bcol * 24u);
-}
-
-// One block row of interleaved BGR = 24 bytes at an 8-byte aligned address: three 8-byte accesses.  (A 16-byte +
-// an 8-byte access is no faster for loads and 1.7x SLOWER for stores - the 16-byte half is misaligned half the time.)
-__device__ __forceinline__ void load_bgr_row(const uint8_t *p, u32x2 &q0, u32x2 &q1, u32x2 &q2) {
-    const u32x2 *row = reinterpret_cast<const u32x2 *>(p);
-    q0 = SVS_LD(row); q1 = SVS_LD(row + 1); q2 = SVS_LD(row + 2);
-}
-__device__ __forceinline__ void store_bgr_row(uint8_t *p, const u32x2 &q0, const u32x2 &q1, const u32x2 &q2) {
-    u32x2 *row = reinterpret_cast<u32x2 *>(p);
-    SVS_ST(q0, row); SVS_ST(q1, row + 1); SVS_ST(q2, row + 2);
-}
-
-// 8 interleaved BGR pixels (6 dwords) -> 8 gray bytes (2 dwords)
-__device__ __forceinline__ void bgr8_to_gray(const u32x2 &q0, const u32x2 &q1, const u32x2 &q2, const ColourParams &c,
-                                             uint32_t &lo4, uint32_t &hi4) {
-    const uint32_t w[6] = {q0.x, q0.y, q1.x, q1.y, q2.x, q2.y};
-    const uint32_t half = 1u << (c.shift - 1);
-    uint32_t px[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int b0 = 3 * j, b1 = 3 * j + 1, b2 = 3 * j + 2;
-        const uint32_t B = (w[b0 >> 2] >> (8 * (b0 & 3))) & 0xffu, G = (w[b1 >> 2] >> (8 * (b1 & 3))) & 0xffu,
-                       R = (w[b2 >> 2] >> (8 * (b2 & 3))) & 0xffu;
-        // B, G, R < 2^8 and the weights <= 2^16: 24-bit multiplies (full rate) are exact
-        px[j] = (__umul24(B, c.wb) + __umul24(G, c.wg) + __umul24(R, c.wr) + half) >> c.shift;
-    }
-    lo4 = px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24);
-    hi4 = px[4] | (px[5] << 8) | (px[6] << 16) | (px[7] << 24);
-}
-
+// (ColourParams, block_offset_bgr, load_bgr_row / store_bgr_row and bgr8_to_gray stand above the read-back pass, which uses them)
 // 8 gray bytes -> 8 interleaved BGR pixels with B = G = R: six byte permutes (v_perm_b32 selects bytes 0-3 from
 // its second operand, 4-7 from its first)
 __device__ __forceinline__ void gray8_to_bgr(uint32_t lo4, uint32_t hi4, u32x2 &q0, u32x2 &q1, u32x2 &q2) {

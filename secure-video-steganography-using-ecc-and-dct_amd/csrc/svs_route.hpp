@@ -24,7 +24,7 @@ struct RouteArgs {
     bool guarded_off;         // reaches the gray calls only
     float guard_scale, tie_scale;
     bool keyed = false;       // a keyed block order (svs_embed_ordered_dev / svs_extract_ordered_dev; gray calls only)
-    bool readback = false;    // SVS_READBACK (gray embed calls only)
+    bool readback = false;    // SVS_READBACK (the gray embed calls; svs_embed_bgr_readback*)
 };
 
 // COPY: nothing to embed and an empty payload - the reference's loops break before the first block.  Gray: a byte copy through

@@ -42,8 +42,14 @@ KEEP_COLOUR = os.environ.get("SVS_KEEP_COLOUR", "0") == "1"
 # that the reference's clipping or truncation made unreadable (letterbox bars, flat black or white areas) is repaired
 # (SVS_READBACK, include/svsdct.h) - otherwise one such block makes the receiver's AES-GCM reject the payload.  Repaired blocks
 # are no longer the reference's pixels.  One line reports the totals, and a warning names blocks left unrepaired.  The gray
-# path only: refused together with SVS_FUSED_COLOUR / SVS_KEEP_COLOUR.
+# path only: refused together with SVS_FUSED_COLOUR / SVS_KEEP_COLOUR (the colour form has a switch of its own, below).
 READBACK = os.environ.get("SVS_READBACK", "0") == "1"
+# SVS_READBACK_COLOUR=1 (opt-in): the same read-back and repair on the fused colour path (svs_embed_bgr_readback,
+# include/svsdct.h).  Implies SVS_FUSED_COLOUR behind the same cv2 check and combines with SVS_KEEP_COLOUR: repaired blocks keep
+# the cover's colours, shifted to the repaired gray.  Where the cv2 check fails the gray read-back path runs instead (its
+# output is the plain colour form's, byte for byte).  Refused together with SVS_BLOCK_KEY (no keyed colour form) and with
+# SVS_READBACK (one switch per path).
+READBACK_COLOUR = os.environ.get("SVS_READBACK_COLOUR", "0") == "1"
 
 
 def _keyed(block_key=None, **kw):
@@ -119,9 +125,13 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if kunci_blok is not None and KEEP_COLOUR:
         print("    Error: SVS_BLOCK_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR.")
         return False, None, None
+    if READBACK_COLOUR and READBACK:
+        raise ValueError("SVS_READBACK_COLOUR=1 cannot be combined with SVS_READBACK=1: one switch per path")
+    if READBACK_COLOUR and kunci_blok is not None:
+        raise ValueError("SVS_READBACK_COLOUR=1 cannot be combined with SVS_BLOCK_KEY: the fused colour path has no keyed form")
     if READBACK and (FUSED_COLOUR or KEEP_COLOUR):
         raise ValueError("SVS_READBACK=1 cannot be combined with SVS_FUSED_COLOUR / SVS_KEEP_COLOUR: "
-                         "the fused colour path has no read-back")
+                         "the read-back of the fused colour path is SVS_READBACK_COLOUR=1")
 
     payload = _siapkan_payload(path_gambar_rahasia, kunci_publik_ecc_penerima_bytes_compressed)
     if payload is None:
@@ -150,7 +160,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     print(f"    Video output akan disimpan sebagai '{path_out}' (Codec: FFV1).")
 
     tabel_warna = None
-    if (FUSED_COLOUR or KEEP_COLOUR) and kunci_blok is None:     # keyed order: the host-conversion gray path
+    if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None:   # keyed order: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -158,12 +168,21 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
             print(f"    Info: jalur warna terfusi tidak dipakai ({exc}).")
             if KEEP_COLOUR:
                 print("    Info: warna video sampul tidak dipertahankan.")
+            if READBACK_COLOUR:
+                print("    Info: read-back dijalankan pada jalur abu-abu (SVS_READBACK).")
     jaga_warna = bool(KEEP_COLOUR and tabel_warna)
     if jaga_warna:
         print("    Info: warna video sampul dipertahankan.")
     per_frame = _batch.capacity_bits(1, out_h, out_w, num_ac_coeffs)
     usable = per_frame if delta_kuantisasi > 0 else 0              # nothing can be embedded otherwise (:143-145)
     state = {"disisipkan": 0, "frame_num": 0, "first": None}
+    readback_abu = READBACK or (READBACK_COLOUR and not tabel_warna)   # the gray pipeline's read-back
+
+    def lapor_readback(diperbaiki, tersisa):
+        print(f"    Read-back: {diperbaiki} blok diperbaiki, {tersisa} blok tidak dapat diperbaiki.")
+        if tersisa:
+            print(f"    Warning: {tersisa} blok tidak terbaca kembali dengan benar; "
+                  "payload kemungkinan gagal didekripsi.")
 
     def baca(n):
         """decode up to n frames, cropped; gray unless the fused colour path takes them as they are"""
@@ -196,21 +215,28 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if tabel_warna:
         # fused colour path (opt-in): synchronous batches through svs_embed_bgr
         sisa = carrying
+        rb_total = [0, 0]
         while not habis and (sisa is None or sisa > 0):
             frames = baca(BATCH_FRAMES if sisa is None else min(BATCH_FRAMES, sisa))
             if not frames:
                 habis = True
                 break
-            stego_bgr, gray, used = _batch.embed_bgr_frames(np.stack(frames), delta_kuantisasi, num_ac_coeffs, payload,
-                                                            bit_offset=state["disisipkan"],
-                                                            n_bits=total_bits - state["disisipkan"], weights=tabel_warna,
-                                                            keep_colour=jaga_warna)
+            hasil = _batch.embed_bgr_frames(np.stack(frames), delta_kuantisasi, num_ac_coeffs, payload,
+                                            bit_offset=state["disisipkan"], n_bits=total_bits - state["disisipkan"],
+                                            weights=tabel_warna, keep_colour=jaga_warna,
+                                            **({"readback": True} if READBACK_COLOUR else {}))
+            stego_bgr, gray, used = hasil[:3]
+            if READBACK_COLOUR:
+                rb_total[0] += hasil[3].repaired
+                rb_total[1] += hasil[3].unrepaired
             expect = min(len(frames) * usable, total_bits - state["disisipkan"])
             if used != expect:
                 raise RuntimeError(f"embed kernel consumed {used} bits, expected {expect}")
             tulis(gray, stego_bgr[..., 0], stego_bgr)
             if sisa is not None:
                 sisa -= len(frames)
+        if READBACK_COLOUR:
+            lapor_readback(*rb_total)
     else:
         # Overlapped staging: batch k+1 is decoded (feeder thread) while batch k is on the GPU (H2D copy,
         # kernel and D2H copy run asynchronously on the slot's stream) and batch k-1 is encoded (this thread); the payload is
@@ -219,7 +245,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         n_batches = PIPELINE_DEPTH if carrying is None else -(-carrying // per_batch)
         with FramePipeline(out_h, out_w, per_batch, delta_kuantisasi, num_ac_coeffs,
                            depth=max(1, min(PIPELINE_DEPTH, n_batches)), mode=_batch.host_level_mode(),
-                           **_keyed(block_key=kunci_blok), **({"readback": True} if READBACK else {})) as pipe:
+                           **_keyed(block_key=kunci_blok), **({"readback": True} if readback_abu else {})) as pipe:
             pipe.set_payload(payload)
             rencana = {"sisa": carrying}
 
@@ -249,12 +275,9 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
                         raise RuntimeError(f"embed kernel consumed {used} bits, expected {expect}")
                     tulis(pipe.input(slot)[:n], pipe.embed_result(slot))
                     feeder.release(slot)
-            if READBACK:
+            if readback_abu:
                 rb = pipe.readback_counts()
-                print(f"    Read-back: {rb.repaired} blok diperbaiki, {rb.unrepaired} blok tidak dapat diperbaiki.")
-                if rb.unrepaired:
-                    print(f"    Warning: {rb.unrepaired} blok tidak terbaca kembali dengan benar; "
-                          "payload kemungkinan gagal didekripsi.")
+                lapor_readback(rb.repaired, rb.unrepaired)
     disisipkan = state["disisipkan"]
     selesai = usable > 0 and disisipkan >= total_bits
     if selesai:

@@ -334,14 +334,24 @@ def _bgr_flags(mode, keep_colour):
 
 def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Planes, delta, n_ac,
                      d_bits_packed: int, bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
-                     weights=None, in_pitches=None, out_pitches=None, keep_colour: bool = False) -> int:
+                     weights=None, in_pitches=None, out_pitches=None, keep_colour: bool = False, readback: bool = False,
+                     d_counts: int = 0) -> int:
     """Enqueue the fused BGR -> gray -> embed -> BGR kernel over packed (or pitched) interleaved BGR frames;
     `d_gray_ref` (0 to skip) receives the gray frames before embedding.  keep_colour: stego pixels keep the cover's
-    colour (SVS_KEEP_COLOUR; their gray is the stego plane) instead of B = G = R.  Returns bits embedded."""
+    colour (SVS_KEEP_COLOUR; their gray is the stego plane) instead of B = G = R.  readback: the read-back pass follows on
+    the same stream, in place on the BGR output (svs_embed_bgr_readback_dev); d_counts: 0, or a device buffer of two uint64
+    that the call adds {repaired, unrepaired} into.  Returns bits embedded."""
     irp, ifp = in_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     orp, ofp = out_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     keep, wptr = _weights_arg(weights)
     done = C.c_uint64(0)
+    if readback:
+        rc = native.load().svs_embed_bgr_readback_dev(d_bgr_in, irp, ifp, d_bgr_out, orp, ofp, d_gray_ref or None,
+                                                      C.byref(planes), wptr, float(delta), int(n_ac), d_bits_packed,
+                                                      int(bit_offset), int(n_bits), _bgr_flags(mode, keep_colour),
+                                                      C.byref(done), d_counts or None, stream or None)
+        native.check(rc, "svs_embed_bgr_readback_dev")
+        return int(done.value)
     rc = native.load().svs_embed_bgr_dev(d_bgr_in, irp, ifp, d_bgr_out, orp, ofp, d_gray_ref or None,
                                          C.byref(planes), wptr, float(delta), int(n_ac), d_bits_packed,
                                          int(bit_offset), int(n_bits), _bgr_flags(mode, keep_colour), C.byref(done),
@@ -373,9 +383,12 @@ def _as_bgr_stack(frames: np.ndarray) -> np.ndarray:
 
 def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                      device: int = 0, mode: str | None = None, weights=None, want_gray: bool = True,
-                     keep_colour: bool = False):
-    """BGR frames in, stego BGR frames out (one fused pass on the GPU).  keep_colour: see embed_bgr_device.
-    Returns (stego_bgr uint8 [F,H,W,3], gray uint8 [F,H,W] (the cover's) or None, n_embedded)."""
+                     keep_colour: bool = False, readback: bool = False):
+    """BGR frames in, stego BGR frames out (one fused pass on the GPU).  keep_colour: see embed_bgr_device.  readback: the
+    blocks whose payload bits do not read back are repaired in place on the BGR output (svs_embed_bgr_readback,
+    include/svsdct.h).
+    Returns (stego_bgr uint8 [F,H,W,3], gray uint8 [F,H,W] (the cover's) or None, n_embedded), with readback
+    (stego_bgr, gray, n_embedded, ReadbackCounts)."""
     lib = native.load()
     native.ensure_device(device)
     stack = _as_bgr_stack(frames_bgr)
@@ -393,6 +406,13 @@ def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int 
     gray = pinned_empty((f, h, w)) if want_gray else None
     keep, wptr = _weights_arg(weights)
     done = C.c_uint64(0)
+    if readback:
+        counts = native.ReadbackCounts()
+        rc = lib.svs_embed_bgr_readback(stack.ctypes.data, out.ctypes.data, gray.ctypes.data if want_gray else None,
+                                        C.byref(planes), wptr, float(delta), int(n_ac), packed.ctypes.data, int(bit_offset),
+                                        int(n_bits), _bgr_flags(mode, keep_colour), C.byref(done), C.byref(counts))
+        native.check(rc, "svs_embed_bgr_readback")
+        return out, gray, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
     rc = lib.svs_embed_bgr(stack.ctypes.data, out.ctypes.data, gray.ctypes.data if want_gray else None,
                            C.byref(planes), wptr, float(delta), int(n_ac), packed.ctypes.data, int(bit_offset),
                            int(n_bits), _bgr_flags(mode, keep_colour), C.byref(done))

@@ -102,6 +102,11 @@ SIGNATURES = {
     "svs_embed_bgr": (C.c_int, [_u8p, _u8p, _u8p, _PL, C.c_void_p, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64,
                                  C.c_uint32, _u64p]),
     "svs_extract_bgr": (C.c_int, [_u8p, _PL, C.c_void_p, C.c_double, C.c_int, _u8p, C.c_uint64, _u64p]),
+    "svs_embed_bgr_readback_dev": (C.c_int, [_u8p, C.c_int64, C.c_int64, _u8p, C.c_int64, C.c_int64, _u8p, _PL, C.c_void_p,
+                                              C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p, C.c_void_p,
+                                              C.c_void_p]),
+    "svs_embed_bgr_readback": (C.c_int, [_u8p, _u8p, _u8p, _PL, C.c_void_p, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64,
+                                          C.c_uint32, _u64p, C.POINTER(ReadbackCounts)]),
     "svs_fill_synthetic_dev": (C.c_int, [_u8p, _PL, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "svs_fill_bits_dev": (C.c_int, [_u8p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p]),
     "svs_frame_sse_dev": (C.c_int, [_u8p, _u8p, _PL, C.c_void_p, C.c_void_p]),
