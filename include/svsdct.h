@@ -110,6 +110,33 @@ extern "C" {
  * frame); at small delta it can also overshoot, and a few accepted blocks per frame decode but are visibly destroyed.  The receiver is unchanged: any extract call decodes the result.  The call needs the reference's stego as its start
  * and not the cover, so in-place calls keep working.  Only svs_embed_readback* report the counts. */
 #define SVS_READBACK 0x200u
+/* SVS_NEAREST (every embed call: svs_embed_dev, svs_embed, svs_embed_str, svs_embed_ordered*, svs_embed_readback*, svs_embed_bgr*,
+ * svs_embed_bgr_readback*; every extract call rejects it with SVS_ERR_INVALID_ARG before any device work): opt-in.  It combines
+ * freely with the mode bits, SVS_KEEP_COLOUR, SVS_READBACK and a block order.  The reference forces a coefficient's parity in a
+ * fixed direction: when the index q = round_half_even(c / delta) has the wrong parity it writes q + 1 for bit 1 and q - 1 for
+ * bit 0 (config_and_setup.py:150-155), which is the FARTHER of the two neighbouring lattice points for half of those
+ * coefficients - a move of up to 1.5 delta.  With the flag the move goes to the nearer one:
+ *     q (float32 division, round half to even) is the reference's; when its parity equals the bit, q is requantised as always;
+ *     otherwise, with c0 = the float32 value written for q (float(q * delta): (float)q * (float)delta, or the once-rounded
+ *     double product when delta is not a float32), q' = q + 1 if c > c0, q' = q - 1 if c < c0, and the reference's choice (+1
+ *     for bit 1, -1 for bit 0) if c == c0; q' is requantised.
+ * The side comes from c0 and not from c / delta - q, so the rule has no division-rounding corner.  A forced coefficient moves
+ * by at most delta (plus rounding); in the coefficient domain the expected distortion falls from 7/12 delta^2 to 1/3 delta^2.
+ * Everything else is the reference's: coefficient order and bit budget, the partial block, byte-identical blocks past the
+ * budget, the delta <= 0 and n_ac = 0 routes (the flag has no effect there; an empty payload is still a copy), the pocketfft
+ * inverse, clip, truncate.  With SVS_READBACK the read-back pass starts from the stego this rule wrote.
+ * Cost: the outputs are NO LONGER the reference's stego pixels (a block whose bits already match everywhere is).  The receiver is
+ * unchanged - extraction reads only q mod 2, any extract call decodes the result - and the default (flag clear) is
+ * byte-identical to before.  Measured with the CPU oracle, one 480 x 640 frame, full-capacity random payload, PSNR against the
+ * cover in dB, reference -> nearest (payload bit errors of the frame, reference -> nearest); "noise" is uniform in [16, 240):
+ *     noise  n_ac = 3  delta = 8    44.95 -> 46.87  (0 -> 0)          noise  n_ac = 63 delta = 8    32.43 -> 34.84  (0 -> 0)
+ *     noise  n_ac = 10 delta = 8    40.25 -> 42.50  (0 -> 0)          noise in [0, 256), n_ac = 63, delta = 8 (clips)
+ *     noise  n_ac = 10 delta = 20   32.48 -> 34.88  (0 -> 0)                                        32.53 -> 34.93  (268 -> 6)
+ *     smooth n_ac = 10 delta = 20   32.83 -> 34.27  (0 -> 0)          noise  n_ac = 3  delta = 4    49.27 -> 50.46  (218 -> 161)
+ *     noise  n_ac = 7  delta = 2    50.38 -> 51.05  (7626 -> 7998)
+ * 1.4 - 2.4 dB at the settings the application offers; delta >= 8 stays error-free where the reference's stego is; only
+ * delta = 2, where the reference's own stego already fails, gets slightly worse. */
+#define SVS_NEAREST 0x800u
 
 /* Geometry of a batch of gray planes. */
 typedef struct svs_planes {

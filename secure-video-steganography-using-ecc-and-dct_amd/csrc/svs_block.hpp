@@ -396,6 +396,45 @@ SVS_HD int quant_index(float c, const QimParams &qp) {
 SVS_HD int force_parity(int q, int bit) { return (q & ~1) | bit; }
 SVS_HD int quant_index_by_division(float c, float delta_f) { return (int)rintf(c / delta_f); }
 
+// the float32 value written for index q: `float(q * delta)` (config_and_setup.py:156)
+template <int QM>
+SVS_HD float requantised(int q, const QimParams &qp) {
+    if constexpr (QM == QM_DOUBLE) return (float)((double)q * qp.delta_d);
+    else return (float)q * qp.delta_f;
+}
+
+// SVS_NEAREST (include/svsdct.h): force_parity moves a wrong parity in a fixed direction - +1 for bit 1, -1 for bit 0 - which
+// is the FARTHER of the two neighbouring lattice points for half of the coefficients (a move of up to 1.5 delta).  This rule
+// goes to the nearer one: with c0 = the value written for the unforced index q, q + 1 if c > c0, q - 1 if c < c0, and the
+// reference's choice when c == c0 (a coefficient that is exactly 0, as every AC coefficient of a constant block).  The move
+// is at most delta plus rounding; the receiver reads q mod 2 and does not change.  The side is taken from c0 and not from
+// c / delta - q: no division-rounding corner, and the multiply is the one the requantisation has anyway.
+template <int QM>
+SVS_HD int nearest_parity(int q, int bit, float c, const QimParams &qp) {
+    const float c0 = requantised<QM>(q, qp);
+    const int dir = c > c0 ? 1 : (c < c0 ? -1 : 2 * bit - 1);
+    return q + (((q ^ bit) & 1) ? dir : 0);
+}
+
+// What the EMBED bodies take: the quantiser parameters plus the rule that forces a wrong parity.  A type of its own, so that
+// QimParams - a by-value argument of every kernel, the extract kernels included - keeps its layout.  A plain QimParams
+// converts to the reference's rule.  The kernels build it from a wave-uniform argument (Geometry::pad, set from the plan) as a
+// compile-time constant on either side of ONE branch around their whole body (svs_device.hpp), so inside a body every test
+// of `nearest` folds away and the default rule's instruction stream is what it was before the flag existed.
+struct QimRule : QimParams {
+    uint32_t nearest;   // SVS_NEAREST (include/svsdct.h): nearest_parity instead of force_parity
+    SVS_HD QimRule(const QimParams &p, uint32_t nearest_ = 0u) : QimParams(p), nearest(nearest_) {}
+};
+
+// One payload coefficient through the quantiser, integer form: the value that replaces c.  NEAREST is a compile-time
+// argument of this FUNCTION: the exact bodies choose between the two forms of their quantiser loop with one test of
+// qp.nearest per block (a constant inside a kernel's body, see QimRule).
+template <int QM, bool NEAREST>
+SVS_HD float qim_target(float c, int bit, const QimParams &qp) {
+    const int q = quant_index<QM>(c, qp);
+    return requantised<QM>(NEAREST ? nearest_parity<QM>(q, bit, c, qp) : force_parity(q, bit), qp);
+}
+
 // 64 stream bits starting at stream bit s of an MSB-first packed buffer viewed as dwords
 // (touches at most dwords s/32 .. s/32+2, each only if below n_words)
 SVS_HD void payload_window(const uint32_t *bits, uint32_t n_words, uint64_t s, uint32_t &hi, uint32_t &lo) {
@@ -816,27 +855,29 @@ SVS_HD void forward_exact_paired_constant(float v, pf::f32x2 (&D2)[4][8]) {
 
 // `constant_block`: the caller knows (wave-uniformly) that all 64 pixels are equal - the forward pass is then the two-line
 // shortcut above (host emulation of flat content; the device replay transforms every block in full)
-template <int U, int QM>
-SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo,
-                              const QimParams &qp, bool constant_block = false) {
-    using pf::f32x2;
-    f32x2 D2[4][8];
-    if (constant_block) forward_exact_paired_constant(ubyte_to_float<0>(rx[0]), D2);
-    else forward_exact_paired(rx, ry, D2);
+template <int U, int QM, bool NEAREST>
+SVS_HD void qim_exact_paired(pf::f32x2 (&D2)[4][8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo, const QimRule &qp) {
 #pragma unroll
     for (int k = 1; k < 8 * U; ++k) {
         if ((uint32_t)k <= n) {  // wave-uniform
             const int i = k - 1;
             const int bit = (int)window_bit(hi, lo, i);
             const float c = D2[k >> 4][k & 7][(k >> 3) & 1];
-            int q = quant_index<QM>(c, qp);
-            q = force_parity(q, bit);
-            float cn;
-            if constexpr (QM == QM_DOUBLE) cn = (float)((double)q * qp.delta_d);
-            else cn = (float)q * qp.delta_f;
+            const float cn = qim_target<QM, NEAREST>(c, bit, qp);
             D2[k >> 4][k & 7][(k >> 3) & 1] = ((uint32_t)i < nb) ? cn : c;
         }
     }
+}
+
+template <int U, int QM>
+SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo,
+                              const QimRule &qp, bool constant_block = false) {
+    using pf::f32x2;
+    f32x2 D2[4][8];
+    if (constant_block) forward_exact_paired_constant(ubyte_to_float<0>(rx[0]), D2);
+    else forward_exact_paired(rx, ry, D2);
+    if (qp.nearest) qim_exact_paired<U, QM, true>(D2, n, nb, hi, lo, qp);
+    else qim_exact_paired<U, QM, false>(D2, n, nb, hi, lo, qp);
     f32x2 P2[4][8];  // vertical inverse of coefficient-column pairs: P2[p][y] = (P[y][2p], P[y][2p+1])
 #pragma unroll
     for (int p2 = 0; p2 < 4; ++p2) {
@@ -891,6 +932,10 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
 #define SVS_GUARD_KE 31.05         // per unit of ||X - mean||_2 (the (2 -> 1) norm is at least 30.66: the bound is tight)
 #define SVS_GUARD_KD_U1 19.61      // per unit of 1.5 delta + 0.01, at most 7 modified coefficients (incl. the kernel's own sparse inverse)
 #define SVS_GUARD_KD_U2 54.78      // at most 15 modified coefficients
+// SVS_NEAREST changes a coefficient by at most delta plus rounding (nearest_parity), the reference's rule by up to 1.5 delta:
+// the KD term - and the 16-bit range of the packed column deltas - assume 1.5 delta, so the same BETA bounds both rules.  It
+// is merely not tight under the flag (g_delta could shrink by a third there; not done: a change of the flagged share of blocks
+// wants its own soak).
 #define SVS_GUARD_UEFF (5.9604644775390625e-8 * (1.0 + 0.0009765625))
 // delta range the guarded path is used for (outside it the caller takes the exact kernel): below, the changes are smaller
 // than BETA and every block would be flagged; above, BETA itself exceeds 1/8
@@ -902,10 +947,14 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
 // q in the low mantissa bits of the sum (|t| < 2^22: delta >= 1/4 and |c| <= 2040 here), so the parity is forced on the bit
 // pattern and q' comes back by subtracting the constant - no conversion to an integer and back (those are 1.6-slot
 // instructions, profiles/r04_valu_issue_rate.txt).  Same results as quant_index / force_parity (tests: guarded mode vs the oracle).
-template <int QM>
+// NEAREST (SVS_NEAREST, nearest_parity): q +- 1 is +- 1 on the bit pattern of m as well (an ulp at 1.5 * 2^23 is 1), and the side
+// is a compare of c with the unforced q delta and a select - no branch.  A compile-time argument of this FUNCTION: the
+// callers choose between the two forms of their quantiser loop with one test of qp.nearest per block (QimRule).
+template <int QM, bool NEAREST = false>
 SVS_HD float qim_change(float c, uint32_t bit, const QimParams &qp) {
     if constexpr (QM == QM_DOUBLE) {
-        const int q = force_parity(quant_index<QM>(c, qp), (int)bit);
+        const int q0 = quant_index<QM>(c, qp);
+        const int q = NEAREST ? nearest_parity<QM>(q0, (int)bit, c, qp) : force_parity(q0, (int)bit);
         return (float)((double)q * qp.delta_d) - c;
     } else {
         const float kMagic = 12582912.0f;   // 1.5 * 2^23
@@ -917,7 +966,14 @@ SVS_HD float qim_change(float c, uint32_t bit, const QimParams &qp) {
             if (miss <= fabsf(t) * 4.76837158203125e-7f)          // see quant_index
                 m = rintf(c / qp.delta_f) + kMagic;
         }
-        const uint32_t mb = (__builtin_bit_cast(uint32_t, m) & ~1u) | bit;
+        uint32_t mb = __builtin_bit_cast(uint32_t, m);
+        if constexpr (NEAREST) {
+            const float c0 = (m - kMagic) * qp.delta_f;
+            const uint32_t dir = c > c0 ? 1u : (c < c0 ? ~0u : 2u * bit - 1u);
+            mb += ((mb ^ bit) & 1u) ? dir : 0u;
+        } else {
+            mb = (mb & ~1u) | bit;
+        }
         const float qf = __builtin_bit_cast(float, mb) - kMagic;
         return qf * qp.delta_f - c;
     }
@@ -1011,13 +1067,26 @@ SVS_HD uint32_t pk_clamp_u8_i16(uint32_t a) {   // lane-wise clamp of signed 16-
 #endif
 }
 
+// the quantiser loops of the streaming bodies: coefficient row 0 (flat indices 1..7) and rows 0 and 1 (1..15) replaced by
+// their changes, 0 where nothing is embedded.  NEAREST as in qim_change; the budget is applied by the caller.
+template <int QM, bool NEAREST>
+SVS_HD void qim_changes_row0(float (&D)[8], uint32_t n, uint32_t hi, const QimParams &qp) {
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+        float change = 0.0f;
+        if ((uint32_t)k <= n)  // wave-uniform; the budget is applied below, for the one block it concerns
+            change = qim_change<QM, NEAREST>(D[k], (hi >> (32 - k)) & 1u, qp);
+        D[k] = change;
+    }
+}
+
 // -> SVS_ROW1_* flags and the column deltas (meaningful unless SVS_ROW1_UNDECIDED).
 // (A compile-time coefficient count - n = 3, BASELINE configs[2] - removes a quarter of the instructions and changes nothing
 // measurable: the kernel's arithmetic is hidden behind its memory traffic, 1.6144 vs 1.6056 ms per 600 x 4K in a same-process
 // A/B.  Not instantiated.)
 template <int QM>
 SVS_HD uint32_t guard_decide_int(const uint32_t (&rx)[8], const uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi,
-                                 const QimParams &qp, ColumnDeltas &cd) {
+                                 const QimRule &qp, ColumnDeltas &cd) {
     float V[8];
     uint32_t S = 0, Q = 0, mn = 0x00ff00ffu, mx = 0u;
 #pragma unroll
@@ -1045,13 +1114,8 @@ SVS_HD uint32_t guard_decide_int(const uint32_t (&rx)[8], const uint32_t (&ry)[8
     float D[8];
     pf::dct2_8(V, D);   // row 0 of the coefficient matrix, bit-identical to scipy's
     SVS_SCHED_FENCE();
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        float change = 0.0f;
-        if ((uint32_t)k <= n)  // wave-uniform; the budget is applied below, for the one block it concerns
-            change = qim_change<QM>(D[k], (hi >> (32 - k)) & 1u, qp);
-        D[k] = change;
-    }
+    if (qp.nearest) qim_changes_row0<QM, true>(D, n, hi, qp);
+    else qim_changes_row0<QM, false>(D, n, hi, qp);
     if (nb < n) {   // the block the payload ends in: coefficients past the budget stay as they are (config_and_setup.py:141)
 #pragma unroll
         for (int k = 1; k < 8; ++k)
@@ -1114,7 +1178,7 @@ SVS_HD void apply_deltas_clipped(uint32_t (&rx)[8], uint32_t (&ry)[8], const Col
 // store form per WAVE instead of per lane)
 template <int QM>
 SVS_HD bool embed_block_guarded(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo,
-                                const QimParams &qp) {
+                                const QimRule &qp) {
     (void)lo;   // one coefficient row: the window is its first word
     ColumnDeltas cd;
     const uint32_t flags = guard_decide_int<QM>(rx, ry, n, nb, hi, qp, cd);
@@ -1191,9 +1255,21 @@ SVS_HD void vertical_pf01_packed(const uint32_t (&w)[8], float (&v0)[4], float (
 // INPLACE: the stego bytes replace the pixels of rx / ry as they are computed (each column touches only its own byte of the
 // row dwords) and an UNDECIDED block is left half-written - for a caller that has parked the original rows elsewhere (the
 // two-row kernel parks them in LDS, where the exact replay wants them anyway: 16 registers and 16 moves less).
+template <int QM, bool NEAREST>
+SVS_HD void qim_changes_rows01(float (&D0)[8], float (&D1)[8], uint32_t n, uint32_t hi, uint32_t lo, const QimParams &qp) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        float change = 0.0f;
+        if (k >= 1 && (uint32_t)k <= n)  // wave-uniform; the budget is applied below, for the one block it concerns
+            change = qim_change<QM, NEAREST>(k < 8 ? D0[k] : D1[k - 8], window_bit(hi, lo, k - 1), qp);
+        if (k < 8) D0[k] = change;
+        else D1[k - 8] = change;
+    }
+}
+
 template <int QM, int NFIX = 0, bool INPLACE = false>
 SVS_HD bool embed_block_guarded2(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n_rt, uint32_t nb, uint32_t hi, uint32_t lo,
-                                 const QimParams &qp) {
+                                 const QimRule &qp) {
     static_assert(NFIX == 0 || (NFIX >= 8 && NFIX <= 15), "two coefficient rows");
     const uint32_t n = NFIX ? (uint32_t)NFIX : n_rt;
     float V0[8], V1[8];
@@ -1213,14 +1289,8 @@ SVS_HD bool embed_block_guarded2(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t 
     float D0[8], D1[8];
     pf::dct2_8(V0, D0);
     pf::dct2_8(V1, D1);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        float change = 0.0f;
-        if (k >= 1 && (uint32_t)k <= n)  // wave-uniform; the budget is applied below, for the one block it concerns
-            change = qim_change<QM>(k < 8 ? D0[k] : D1[k - 8], window_bit(hi, lo, k - 1), qp);
-        if (k < 8) D0[k] = change;
-        else D1[k - 8] = change;
-    }
+    if (qp.nearest) qim_changes_rows01<QM, true>(D0, D1, n, hi, lo, qp);
+    else qim_changes_rows01<QM, false>(D0, D1, n, hi, lo, qp);
     if (nb < n) {   // the block the payload ends in (see embed_block): coefficients past the budget stay as they are
 #pragma unroll
         for (int k = 1; k < 16; ++k) {
@@ -1298,10 +1368,28 @@ inline void make_guard(double delta, int rows, QimParams *qp) {
 // kernel (two blocks per lane) it measured SLOWER than the one-block form - a v_pk_*_f32 costs two issue slots on this chip,
 // and the 256-register footprint costs occupancy (profiles/history/r02_ab_exact_pair.txt).  The CPU tier still checks it
 // against embed_block_exact (tests/hostemu, exact == 2).
+template <int U, int QM, bool NEAREST>
+SVS_HD void qim_exact_pair(pf::f32x2 (&D)[8][8], uint32_t n, uint32_t nb_a, uint32_t nb_b, uint32_t hi_a, uint32_t lo_a, uint32_t hi_b,
+                           uint32_t lo_b, const QimParams &qp) {
+#pragma unroll
+    for (int k = 1; k < 8 * U; ++k) {
+        if ((uint32_t)k <= n) {  // wave-uniform
+            const int i = k - 1;
+#pragma unroll
+            for (int which = 0; which < 2; ++which) {
+                const int bit = (int)window_bit(which ? hi_b : hi_a, which ? lo_b : lo_a, i);
+                const float c = D[k >> 3][k & 7][which];
+                const float cn = qim_target<QM, NEAREST>(c, bit, qp);
+                D[k >> 3][k & 7][which] = ((uint32_t)i < (which ? nb_b : nb_a)) ? cn : c;
+            }
+        }
+    }
+}
+
 template <int U, int QM>
 SVS_HD void embed_block_exact_pair(uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_t (&bx)[8], uint32_t (&by)[8], uint32_t n,
                                    uint32_t nb_a, uint32_t nb_b, uint32_t hi_a, uint32_t lo_a, uint32_t hi_b, uint32_t lo_b,
-                                   const QimParams &qp) {
+                                   const QimRule &qp) {
     using pf::f32x2;
     f32x2 D[8][8];  // D[u][v] = (coefficient of A, coefficient of B)
     {
@@ -1326,23 +1414,8 @@ SVS_HD void embed_block_exact_pair(uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_
             SVS_SCHED_FENCE();
         }
     }
-#pragma unroll
-    for (int k = 1; k < 8 * U; ++k) {
-        if ((uint32_t)k <= n) {  // wave-uniform
-            const int i = k - 1;
-#pragma unroll
-            for (int which = 0; which < 2; ++which) {
-                const int bit = (int)window_bit(which ? hi_b : hi_a, which ? lo_b : lo_a, i);
-                const float c = D[k >> 3][k & 7][which];
-                int q = quant_index<QM>(c, qp);
-                q = force_parity(q, bit);
-                float cn;
-                if constexpr (QM == QM_DOUBLE) cn = (float)((double)q * qp.delta_d);
-                else cn = (float)q * qp.delta_f;
-                D[k >> 3][k & 7][which] = ((uint32_t)i < (which ? nb_b : nb_a)) ? cn : c;
-            }
-        }
-    }
+    if (qp.nearest) qim_exact_pair<U, QM, true>(D, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
+    else qim_exact_pair<U, QM, false>(D, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
     f32x2 P[8][8];  // after the vertical inverse (axis 0 first, :168): P[y][v]
 #pragma unroll
     for (int v = 0; v < 8; ++v) {

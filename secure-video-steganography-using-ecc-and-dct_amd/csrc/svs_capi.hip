@@ -71,6 +71,7 @@ svs::RouteArgs route_args(double delta, const svs::Geometry &g, uint64_t total, 
     if (const char *sc = getenv("SVS_GUARD_SCALE")) a.guard_scale = (float)atof(sc);
     if (const char *sc = getenv("SVS_TIE_SCALE")) a.tie_scale = (float)atof(sc);
 #endif
+    a.nearest = (flags & SVS_NEAREST) != 0;
     return a;
 }
 
@@ -200,6 +201,7 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
                  svs::Geometry g, const uint32_t *bits, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}) {
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
+    g.pad = p.nearest ? 1u : 0u;
     const uint32_t words = (uint32_t)p.n_words;
     return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
@@ -271,6 +273,7 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
     const svs::Geometry planes = g;
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
+    g.pad = p.nearest ? 1u : 0u;
     const uint32_t words = (uint32_t)p.n_words;
     const bool exact = p.path == EmbedPath::EXACT || p.path == EmbedPath::ROUND_TRIP;
     if (int rc = dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
@@ -715,7 +718,7 @@ svs::BlockOrderArgs order_args(const svs_block_order *order, const svs::Geometry
     return order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{};
 }
 
-constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_READBACK;
+constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_READBACK | SVS_NEAREST;
 
 // svs_embed_dev, svs_embed_ordered_dev (order NULL: the call without an order) and svs_embed_readback_dev (d_counts: the
 // read-back counts, device, added to; NULL for none)
@@ -760,7 +763,7 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (int rc = check_order(order)) return rc;
-    if (flags & SVS_READBACK) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK is an embed flag");
+    if (flags & (SVS_READBACK | SVS_NEAREST)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK and SVS_NEAREST are embed flags");
     if (cap == 0) return SVS_OK;
     if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
@@ -965,7 +968,7 @@ int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (int rc = check_order(order)) return rc;
-    if (flags & SVS_READBACK) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK is an embed flag");
+    if (flags & (SVS_READBACK | SVS_NEAREST)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK and SVS_NEAREST are embed flags");
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     const uint64_t bytes = (cap + 7) / 8;
@@ -983,7 +986,7 @@ int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta,
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
-    if (flags & SVS_READBACK) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK is an embed flag");
+    if (flags & (SVS_READBACK | SVS_NEAREST)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK and SVS_NEAREST are embed flags");
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_ascii_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if (int rc = check_capacity(cap, out_capacity_chars, "characters")) return rc;
@@ -1075,7 +1078,7 @@ static int colour_params(const svs_planes *p, const void *in, int64_t irp, int64
     return SVS_OK;
 }
 
-constexpr uint32_t kBgrEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR;
+constexpr uint32_t kBgrEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR | SVS_NEAREST;
 
 // svs_embed_bgr_dev (allowed = kBgrEmbedFlags: SVS_READBACK is refused) and svs_embed_bgr_readback_dev (the flag accepted and
 // implied; d_counts: the read-back counts, device, added to; NULL for none)

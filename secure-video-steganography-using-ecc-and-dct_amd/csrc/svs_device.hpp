@@ -29,7 +29,7 @@ struct Geometry {
     uint32_t total_blocks;  // n_frames * blocks per frame   (< 2^31)
     uint32_t n_ac;          // 1..63
     uint32_t xcd_chunk;     // tile_id() chunk (0 = identity)
-    uint32_t pad;
+    uint32_t pad;           // embed launches: 1 = SVS_NEAREST (the plan's `nearest`; the kernels' QimRule), else 0
     int64_t row_pitch;
     int64_t frame_pitch;
 };
@@ -391,26 +391,32 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
                                                           const uint64_t bit_offset, const uint64_t n_bits,
                                                           const uint32_t n_words, const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
-    const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
-    if (gblock >= g.total_blocks) return;
-    const int64_t off = block_offset(gblock, g);
-    typename RowVec<1>::type v[8];
-    load_rows<1>(gray + off, g.row_pitch, v);
-    const uint32_t n = g.n_ac;  // 0 = round-trip every block without touching a coefficient
-    const uint64_t first = stream_first<KEYED>(gblock, n, g, order_arg(order...));
-    if (first >= n_bits) {
-        if (stego != gray) store_rows<1>(stego + off, g.row_pitch, v);
-        return;
-    }
-    uint32_t ax[8], ay[8];
+    // SVS_NEAREST: ONE wave-uniform branch around the whole body, the rule a compile-time constant on either side (QimRule).
+    // A `return` inside the body leaves the body, and nothing follows the two calls.
+    const auto body = [&](const QimRule qp) __attribute__((always_inline)) {
+        const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
+        if (gblock >= g.total_blocks) return;
+        const int64_t off = block_offset(gblock, g);
+        typename RowVec<1>::type v[8];
+        load_rows<1>(gray + off, g.row_pitch, v);
+        const uint32_t n = g.n_ac;  // 0 = round-trip every block without touching a coefficient
+        const uint64_t first = stream_first<KEYED>(gblock, n, g, order_arg(order...));
+        if (first >= n_bits) {
+            if (stego != gray) store_rows<1>(stego + off, g.row_pitch, v);
+            return;
+        }
+        uint32_t ax[8], ay[8];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
-    uint32_t hi, lo;
-    payload_window(bits, n_words, bit_offset + first, hi, lo);
-    embed_block_exact<U, QM>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp);
+        for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
+        uint32_t hi, lo;
+        payload_window(bits, n_words, bit_offset + first, hi, lo);
+        embed_block_exact<U, QM>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
-    store_rows<1>(stego + off, g.row_pitch, v);
+        for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
+        store_rows<1>(stego + off, g.row_pitch, v);
+    };
+    if (g.pad) body(QimRule(qp, 1u));
+    else body(QimRule(qp, 0u));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -436,11 +442,29 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
 // ---------------------------------------------------------------------------------------
 #define SVS_GUARD_CAP 32    // worklist entries per wave and round (80 B each) of the one-row (rigorous guard) embed kernel
 
+// QIM on flat indices k = 8 u + r in 1..n (config_and_setup.py:139-158): one coefficient per lane and row, so a wave
+// runs n / 8 + 1 quantiser sequences, each on all the lanes that have a coefficient.  NEAREST: qim_target (svs_block.hpp)
+template <int QM, int UROWS, bool NEAREST>
+__device__ __forceinline__ void qim_replay8(float (&a)[8], uint32_t hi, uint32_t lo, uint32_t nb, uint32_t r, uint32_t n,
+                                            const QimRule &qp) {
+#pragma unroll
+    for (int u = 0; u < UROWS; ++u) {
+        const uint32_t k = 8u * u + r;
+        if (k >= 1u && k <= n) {
+            const int i = (int)k - 1;
+            const int bit = (int)window_bit(hi, lo, i);
+            const float c = a[u];
+            const float cn = qim_target<QM, NEAREST>(c, bit, qp);
+            a[u] = ((uint32_t)i < nb) ? cn : c;
+        }
+    }
+}
+
 // px: the block's 16 row dwords (low, high per row) in LDS - original pixels in, exact stego pixels out
 // UROWS: coefficient rows that can hold payload (n <= 8 UROWS - 1); the quantiser loop covers only those
 template <int QM, int UROWS = 8>
 __device__ __forceinline__ void guard_replay8(uint32_t *px, uint32_t hi, uint32_t lo, uint32_t nb, float *t, uint32_t r, uint32_t n,
-                                              const QimParams &qp) {
+                                              const QimRule &qp) {
     float a[8], b[8];
     forward8<9>(px, t, r, b);   // b[v] = D[r][v]: coefficient row r
     // to coefficient COLUMNS (what the vertical inverse wants): lane r takes D[u][r], u = 0..7
@@ -450,23 +474,8 @@ __device__ __forceinline__ void guard_replay8(uint32_t *px, uint32_t hi, uint32_
 #pragma unroll
     for (int u = 0; u < 8; ++u) a[u] = t[9 * u + r];
     wave_lds_fence();
-    // QIM on flat indices k = 8 u + r in 1..n (config_and_setup.py:139-158): one coefficient per lane and row, so a wave
-    // runs n / 8 + 1 quantiser sequences, each on all the lanes that have a coefficient
-#pragma unroll
-    for (int u = 0; u < UROWS; ++u) {
-        const uint32_t k = 8u * u + r;
-        if (k >= 1u && k <= n) {
-            const int i = (int)k - 1;
-            const int bit = (int)window_bit(hi, lo, i);
-            const float c = a[u];
-            int q = quant_index<QM>(c, qp);
-            q = force_parity(q, bit);
-            float cn;
-            if constexpr (QM == QM_DOUBLE) cn = (float)((double)q * qp.delta_d);
-            else cn = (float)q * qp.delta_f;
-            a[u] = ((uint32_t)i < nb) ? cn : c;
-        }
-    }
+    if (qp.nearest) qim_replay8<QM, UROWS, true>(a, hi, lo, nb, r, n, qp);
+    else qim_replay8<QM, UROWS, false>(a, hi, lo, nb, r, n, qp);
     inverse8<9>(a, t, r, b);   // pixel row r
     uint32_t lo4, hi4;
     store_row_trunc(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], lo4, hi4);   // np.uint8(np.clip(.)) (:171)
@@ -478,7 +487,7 @@ __device__ __forceinline__ void guard_replay8(uint32_t *px, uint32_t hi, uint32_
 // pixels are left untouched (svs_block.hpp decides before it writes).  -> undecided
 template <int U, int QM, int NFIX = 0>
 __device__ __forceinline__ bool guard_phase1(uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_t n, uint64_t first,
-                                             const QimParams &qp, const uint32_t *__restrict__ bits,
+                                             const QimRule &qp, const uint32_t *__restrict__ bits,
                                              uint64_t bit_offset, uint64_t n_bits, uint32_t n_words,
                                              uint32_t *keep_hi = nullptr) {
     const uint32_t hi = window32(payload_qword(bits, n_words, bit_offset + first), (uint32_t)((bit_offset + first) & 31u)), lo = 0;
@@ -500,7 +509,7 @@ struct GuardPayload {
 // the wave.  On return the rows of undecided blocks hold the exact stego pixels.  Returns the number of blocks redone.
 template <int QM, int CAP = SVS_GUARD_CAP, bool KEPT = false, int UROWS = 2>
 __device__ __forceinline__ uint32_t guard_phase2(GuardEntry *entries, float *tile, uint32_t lane, uint32_t n,
-                                                 const QimParams &qp, const GuardPayload &pl,
+                                                 const QimRule &qp, const GuardPayload &pl,
                                                  bool und, uint64_t first, uint32_t (&ax)[8], uint32_t (&ay)[8],
                                                  uint32_t hi_kept = 0) {
     return wave_worklist<CAP>(
@@ -532,7 +541,7 @@ __device__ __forceinline__ uint32_t guard_phase2(GuardEntry *entries, float *til
 #define SVS_SLOT_DWORDS 18   // 16 row dwords + 2: 8-byte aligned, and 16 consecutive lanes hit 16 different even banks
 template <int QM>
 __device__ __forceinline__ uint32_t guard_phase2_slots(uint32_t *slots, u32x2 *meta, float *tile, uint32_t lane, uint32_t n,
-                                                       const QimParams &qp, bool und, uint32_t nb, uint32_t hi,
+                                                       const QimRule &qp, bool und, uint32_t nb, uint32_t hi,
                                                        uint32_t (&ax)[8], uint32_t (&ay)[8]) {
     return wave_worklist<64>(
         {und}, lane,
@@ -583,62 +592,68 @@ __global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint
     __shared__ u32x2 meta[PARKED ? SVS_WG / 64 : 1][PARKED ? 64 : 1];
     __shared__ GuardEntry entries[PARKED ? 1 : SVS_WG / 64][PARKED ? 1 : SVS_GUARD_CAP];
     __shared__ float tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    // (Round 5 tried block-row aligned tiles - a workgroup reads and writes ONE contiguous stretch, eight full pixel rows, at
-    // the price of idle lanes - to bring the launch from the rate of a copy with this access pattern to that of a linear copy:
-    // 1.73 vs 1.64 ms per 600 x 4K at n = 3, 3.15 vs 2.63 at n = 10, slower on every placement: profiles/r05_ab_row_tiles.txt.)
-    // Shadow lanes keep the row registers defined on one path only (round 6: no zero-initialised copies at the joins).
-    bool live;
-    const uint32_t gblock = shadow_block<1>(tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x, g, live);
-    const uint32_t n = g.n_ac;
-    bool und = false, write = false;
-    // n <= 15: the payload window of a block is its first word - kept in a register from phase 1, because re-reading it for
-    // the worklist is a global load in the life of every wave that replays
-    uint32_t hi = 0, nb = 0;
-    u32x2 v[8];
-    uint32_t ax[8], ay[8];
-    const int64_t off = block_offset(gblock, g);
-    load_rows<1>(gray + off, g.row_pitch, v);
+    // SVS_NEAREST: ONE wave-uniform branch around the whole body, the rule a compile-time constant on either side (QimRule).
+    // A `return` inside the body leaves the body, and nothing follows the two calls.
+    const auto body = [&](const QimRule qp) __attribute__((always_inline)) {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        // (Round 5 tried block-row aligned tiles - a workgroup reads and writes ONE contiguous stretch, eight full pixel rows, at
+        // the price of idle lanes - to bring the launch from the rate of a copy with this access pattern to that of a linear copy:
+        // 1.73 vs 1.64 ms per 600 x 4K at n = 3, 3.15 vs 2.63 at n = 10, slower on every placement: profiles/r05_ab_row_tiles.txt.)
+        // Shadow lanes keep the row registers defined on one path only (round 6: no zero-initialised copies at the joins).
+        bool live;
+        const uint32_t gblock = shadow_block<1>(tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x, g, live);
+        const uint32_t n = g.n_ac;
+        bool und = false, write = false;
+        // n <= 15: the payload window of a block is its first word - kept in a register from phase 1, because re-reading it for
+        // the worklist is a global load in the life of every wave that replays
+        uint32_t hi = 0, nb = 0;
+        u32x2 v[8];
+        uint32_t ax[8], ay[8];
+        const int64_t off = block_offset(gblock, g);
+        load_rows<1>(gray + off, g.row_pitch, v);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
-    uint64_t first_keyed = 0;   // KEYED: the slot's first stream bit, computed once
-    if constexpr (KEYED) first_keyed = stream_first<true>(gblock, n, g, order_arg(order...));
-    if (live) {
-        const uint64_t first = KEYED ? first_keyed : (uint64_t)gblock * n;  // stream index of this lane's first bit
-        write = stego != gray;                         // past the budget: byte-identical copy (the reference's loops `break`, :130,:132)
-        if (first < n_bits) {
-            write = true;
-            if constexpr (PARKED) {
-                // park the original rows (the exact replay reads them there), then phase 1 in place
-                u32x2 *slot = reinterpret_cast<u32x2 *>(&park[wave][lane * SVS_SLOT_DWORDS]);
+        for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
+        uint64_t first_keyed = 0;   // KEYED: the slot's first stream bit, computed once
+        if constexpr (KEYED) first_keyed = stream_first<true>(gblock, n, g, order_arg(order...));
+        if (live) {
+            const uint64_t first = KEYED ? first_keyed : (uint64_t)gblock * n;  // stream index of this lane's first bit
+            write = stego != gray;                         // past the budget: byte-identical copy (the reference's loops `break`, :130,:132)
+            if (first < n_bits) {
+                write = true;
+                if constexpr (PARKED) {
+                    // park the original rows (the exact replay reads them there), then phase 1 in place
+                    u32x2 *slot = reinterpret_cast<u32x2 *>(&park[wave][lane * SVS_SLOT_DWORDS]);
 #pragma unroll
-                for (int r = 0; r < 8; ++r) slot[r] = v[r];
-                hi = window32(payload_qword(bits, n_words, bit_offset + first), (uint32_t)((bit_offset + first) & 31u));
-                nb = block_budget(first, n_bits, n);
-                und = embed_block_guarded2<QM, NFIX, true>(ax, ay, n, nb, hi, 0u, qp);
-            } else {
-                und = guard_phase1<U, QM, NFIX>(ax, ay, n, first, qp, bits, bit_offset, n_bits, n_words, &hi);
+                    for (int r = 0; r < 8; ++r) slot[r] = v[r];
+                    hi = window32(payload_qword(bits, n_words, bit_offset + first), (uint32_t)((bit_offset + first) & 31u));
+                    nb = block_budget(first, n_bits, n);
+                    und = embed_block_guarded2<QM, NFIX, true>(ax, ay, n, nb, hi, 0u, qp);
+                } else {
+                    und = guard_phase1<U, QM, NFIX>(ax, ay, n, first, qp, bits, bit_offset, n_bits, n_words, &hi);
+                }
             }
         }
-    }
-    uint32_t redone;
-    if constexpr (PARKED) {
-        redone = guard_phase2_slots<QM>(&park[wave][0], &meta[wave][0], &tiles[wave][0], lane, n, qp, und, nb, hi, ax, ay);
-    } else {
-        const GuardPayload pl{bits, bit_offset, n_bits, n_words};
-        const uint64_t first = KEYED ? first_keyed : (uint64_t)gblock * n;
-        redone = guard_phase2<QM, SVS_GUARD_CAP, true>(&entries[wave][0], &tiles[wave][0], lane, n, qp, pl, und, first, ax, ay, hi);
-    }
+        uint32_t redone;
+        if constexpr (PARKED) {
+            redone = guard_phase2_slots<QM>(&park[wave][0], &meta[wave][0], &tiles[wave][0], lane, n, qp, und, nb, hi, ax, ay);
+        } else {
+            const GuardPayload pl{bits, bit_offset, n_bits, n_words};
+            const uint64_t first = KEYED ? first_keyed : (uint64_t)gblock * n;
+            redone = guard_phase2<QM, SVS_GUARD_CAP, true>(&entries[wave][0], &tiles[wave][0], lane, n, qp, pl, und, first, ax, ay, hi);
+        }
 #if defined(SVS_EXPERIMENTS)
-    if (replay_counter != nullptr && redone != 0 && lane == 0) atomicAdd(replay_counter, (unsigned long long)redone);
+        if (replay_counter != nullptr && redone != 0 && lane == 0) atomicAdd(replay_counter, (unsigned long long)redone);
 #else
-    (void)redone;
+        (void)redone;
 #endif
-    if (write) {
+        if (write) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
-        store_rows<1>(stego + off, g.row_pitch, v);
-    }
+            for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
+            store_rows<1>(stego + off, g.row_pitch, v);
+        }
+    };
+    if (g.pad) body(QimRule(qp, 1u));
+    else body(QimRule(qp, 0u));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -689,7 +704,7 @@ __device__ __forceinline__ void row1_collect(const GuardEntry *e, typename RowVe
 // phase 2 of the one-row kernel: guard_phase2 on the row vectors, one or two blocks per lane (the payload windows are kept
 // from phase 1)
 template <int QM, int BPL, int CAP, bool KEYED = false>   // KEYED: block B's first stream bit is first_b, not first_a + n
-__device__ __forceinline__ uint32_t row1_phase2(GuardEntry *entries, float *tile, uint32_t lane, uint32_t n, const QimParams &qp,
+__device__ __forceinline__ uint32_t row1_phase2(GuardEntry *entries, float *tile, uint32_t lane, uint32_t n, const QimRule &qp,
                                                 uint64_t n_bits, bool und_a, bool und_b, uint64_t first_a, uint64_t first_b, uint32_t hi_a,
                                                 uint32_t hi_b, typename RowVec<BPL>::type (&v)[8]) {
     bool und[BPL];
@@ -731,7 +746,7 @@ struct Row1Slots {
 // wave's undecided blocks, store.
 template <int QM, int BPL, bool KEYED = false>
 __device__ __forceinline__ uint32_t row1_process(typename RowVec<BPL>::type (&v)[8], uint32_t gb, bool live, int64_t off, uint64_t q,
-                                                 const Geometry &g, const QimParams &qp, const Row1Args &a, GuardEntry *entries,
+                                                 const Geometry &g, const QimRule &qp, const Row1Args &a, GuardEntry *entries,
                                                  float *tile, uint32_t lane, const Row1Slots &ks = Row1Slots{}) {
     const uint32_t n = g.n_ac;
     const uint64_t first = KEYED ? ks.first_a : (uint64_t)gb * n;   // stream index of this lane's first bit
@@ -813,31 +828,37 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ Row1Entries entries;
     __shared__ Row1Tiles tiles;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    bool live;
-    const uint32_t gb = shadow_block<BPL>((tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x) * BPL, g, live);
-    const int64_t off = block_offset(gb, g);
-    typename RowVec<BPL>::type v[8];
-    load_rows<BPL>(gray + off, g.row_pitch, v);
-    const Row1Args a{gray, stego, bits, bit_offset, n_bits, n_words};
-    const uint32_t n = g.n_ac;
-    uint64_t q = 0;
-    uint32_t redone;
-    if constexpr (KEYED) {   // two blocks per lane: two qword reads, one per slot
-        Row1Slots ks{0, 0, 0};
-        ks.first_a = stream_first<true>(gb, n, g, order_arg(order...), BPL == 2 ? &ks.first_b : nullptr);
-        if (live && ks.first_a < n_bits) q = payload_qword(bits, n_words, bit_offset + ks.first_a);
-        if (BPL == 2 && live && ks.first_b < n_bits) ks.q_b = payload_qword(bits, n_words, bit_offset + ks.first_b);
-        redone = row1_process<QM, BPL, true>(v, gb, live, off, q, g, qp, a, &entries[wave][0], &tiles[wave][0], lane, ks);
-    } else {
-        if (live && (uint64_t)gb * n < n_bits) q = payload_qword(bits, n_words, bit_offset + (uint64_t)gb * n);
-        redone = row1_process<QM, BPL>(v, gb, live, off, q, g, qp, a, &entries[wave][0], &tiles[wave][0], lane);
-    }
+    // SVS_NEAREST: ONE wave-uniform branch around the whole body, the rule a compile-time constant on either side (QimRule).
+    // A `return` inside the body leaves the body, and nothing follows the two calls.
+    const auto body = [&](const QimRule qp) __attribute__((always_inline)) {
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        bool live;
+        const uint32_t gb = shadow_block<BPL>((tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x) * BPL, g, live);
+        const int64_t off = block_offset(gb, g);
+        typename RowVec<BPL>::type v[8];
+        load_rows<BPL>(gray + off, g.row_pitch, v);
+        const Row1Args a{gray, stego, bits, bit_offset, n_bits, n_words};
+        const uint32_t n = g.n_ac;
+        uint64_t q = 0;
+        uint32_t redone;
+        if constexpr (KEYED) {   // two blocks per lane: two qword reads, one per slot
+            Row1Slots ks{0, 0, 0};
+            ks.first_a = stream_first<true>(gb, n, g, order_arg(order...), BPL == 2 ? &ks.first_b : nullptr);
+            if (live && ks.first_a < n_bits) q = payload_qword(bits, n_words, bit_offset + ks.first_a);
+            if (BPL == 2 && live && ks.first_b < n_bits) ks.q_b = payload_qword(bits, n_words, bit_offset + ks.first_b);
+            redone = row1_process<QM, BPL, true>(v, gb, live, off, q, g, qp, a, &entries[wave][0], &tiles[wave][0], lane, ks);
+        } else {
+            if (live && (uint64_t)gb * n < n_bits) q = payload_qword(bits, n_words, bit_offset + (uint64_t)gb * n);
+            redone = row1_process<QM, BPL>(v, gb, live, off, q, g, qp, a, &entries[wave][0], &tiles[wave][0], lane);
+        }
 #if defined(SVS_EXPERIMENTS)
-    if (replay_counter != nullptr && redone != 0 && lane == 0) atomicAdd(replay_counter, (unsigned long long)redone);
+        if (replay_counter != nullptr && redone != 0 && lane == 0) atomicAdd(replay_counter, (unsigned long long)redone);
 #else
-    (void)redone;
+        (void)redone;
 #endif
+    };
+    if (g.pad) body(QimRule(qp, 1u));
+    else body(QimRule(qp, 0u));
 }
 
 // (Round 6 also ran this kernel as a PERSISTENT, software-pipelined loop - few workgroups per CU, each loading the rows of its
@@ -1638,13 +1659,17 @@ __global__ __launch_bounds__(SVS_WG) void gray_to_bgr_kernel(const uint8_t *__re
 template <int U, int QM, bool EXACT, bool KEEP>
 __global__ __launch_bounds__(SVS_WG) void embed_bgr_kernel(const uint8_t *bgr_in,   // may alias bgr_out
                                                         uint8_t *bgr_out, uint8_t *__restrict__ gray_ref,
-                                                        const Geometry g, const ColourParams c, const QimParams qp,
+                                                        const Geometry g, const ColourParams c, const QimParams qp_arg,
                                                         const uint32_t *__restrict__ bits, const uint64_t bit_offset,
                                                         const uint64_t n_bits, const uint32_t n_words) {
     // one wave-private 4 KB region per wave: row staging of the cooperative load, then (streaming arithmetic) the worklist and transposition
     // tile of the exact replay (guard_phase2 with 16 entries per round), then the stego tile of the cooperative store
     __shared__ __attribute__((aligned(16))) u32x2 lds_tile[SVS_WG / 64][8][64];
     static_assert(16 * sizeof(GuardEntry) + 8 * SVS_GUARD_TILE * sizeof(float) <= 8 * 64 * sizeof(u32x2), "wave region too small");
+    // SVS_NEAREST: the rule stays a run-time value here and the bodies test it once per block.  (Two copies of the whole body,
+    // as in the gray kernels, take the allocation of the larger one: 124 -> 132 and 167 -> 169 VGPRs, a wave per SIMD less.)
+    const QimRule rule(qp_arg, g.pad);
+    const QimRule &qp = rule;
     const uint32_t tile = tile_id(g.xcd_chunk);
     const uint32_t gblock = tile * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;

@@ -25,6 +25,7 @@ struct RouteArgs {
     float guard_scale, tie_scale;
     bool keyed = false;       // a keyed block order (svs_embed_ordered_dev / svs_extract_ordered_dev; gray calls only)
     bool readback = false;    // SVS_READBACK (the gray embed calls; svs_embed_bgr_readback*)
+    bool nearest = false;     // SVS_NEAREST (every embed call)
 };
 
 // COPY: nothing to embed and an empty payload - the reference's loops break before the first block.  Gray: a byte copy through
@@ -43,6 +44,7 @@ struct EmbedPlan {
     bool two_blocks;          // embed_row1_kernel may take two blocks per lane where the buffers allow it
     bool keyed;               // the KEYED instantiation of the family (STREAMING / EXACT only: the other paths do not depend on order)
     bool readback;            // SVS_READBACK: readback_kernel follows the embed (only when payload bits are embedded)
+    bool nearest;             // SVS_NEAREST: Geometry::pad of the embed launch (the kernels' QimRule)
     uint32_t n_ac;            // Geometry::n_ac of the launch
     uint32_t xcd_chunk;
     QimParams qp;
@@ -76,6 +78,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.two_blocks = streaming && !a.bgr && rows == 1;
         p.keyed = a.keyed;
         p.readback = a.readback;
+        p.nearest = a.nearest;                // STREAMING and EXACT only: the other paths have no coefficient to force
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;

@@ -22,6 +22,7 @@ SVS_EXACT_POCKETFFT = 1      # flags bit: pocketfft-identical arithmetic (includ
 SVS_EXACT_GUARDED = 2        # flags bit: the same bit-identical result through the guarded kernel where it applies
 SVS_KEEP_COLOUR = 0x100      # flags bit, fused colour embed only: stego pixels keep the cover's colour (include/svsdct.h)
 SVS_READBACK = 0x200         # flags bit, gray embed only: read every payload block back, repair the ones that fail (include/svsdct.h)
+SVS_NEAREST = 0x800          # flags bit, every embed call: a wrong parity moves to the nearer lattice point (include/svsdct.h)
 ABI_VERSION = 4
 
 

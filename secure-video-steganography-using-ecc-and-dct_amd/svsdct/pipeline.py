@@ -48,10 +48,12 @@ def _device(nbytes: int):
 
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
-                 mode: str | None = None, device: int = 0, block_key=None, readback: bool = False):
+                 mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
+                 nearest: bool = False):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
-        (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals."""
+        (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
+        towards the nearer lattice point (SVS_NEAREST, include/svsdct.h)."""
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
         self.block_key = batch.block_order(block_key).key if block_key is not None else None
@@ -78,6 +80,7 @@ class FramePipeline:
         self._d_payload = None
         self._payload_bits = 0
         self.readback = bool(readback)
+        self.nearest = bool(nearest)
         self._d_counts = None
         if self.readback:   # {repaired, unrepaired} of every batch, added to on the device
             self._d_counts = _device(16)
@@ -121,7 +124,8 @@ class FramePipeline:
         used = batch.embed_device(s["d_frames"].value, s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac,
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
                                   stream=s["stream"].value, mode=self.mode, order=self._order(first_frame),
-                                  readback=self.readback, d_counts=self._d_counts.value if self._d_counts else 0)
+                                  readback=self.readback, d_counts=self._d_counts.value if self._d_counts else 0,
+                                  nearest=self.nearest)
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
         return used
