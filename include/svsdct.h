@@ -291,6 +291,66 @@ int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs
                         int n_ac, uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
                         uint64_t *n_bits_out);
 
+/* ---- the operator with a coefficient selection ---------------------------------------------------------
+ * Opt-in.  Without a selection the payload goes into flat row-major coefficients 1..n_ac of each block, as in the reference:
+ * at n_ac = 3 only the horizontal frequencies (0,1), (0,2), (0,3) carry bits, at the GUI's default 10 the whole first row and
+ * almost nothing vertical.  A SELECTION is an ordered list of `count` distinct flat row-major indices in 1..63 (index
+ * 8*u + v is vertical frequency u, horizontal v; DC, index 0, is never selectable): stream bit i of a block goes to
+ * coefficient index[i] instead of 1 + i, and extraction emits q mod 2 of coefficient index[i] at block-local position i.
+ * Everything else is the reference's, with n_ac = count: frames and blocks take the same stream ranges, count bits per block;
+ * the block the budget ends in has only its first coefficients (in selection order) modified; blocks past the budget are
+ * byte-identical to the cover; delta <= 0, an empty payload and count = 0 take the routes of n_ac = 0; float32 division,
+ * round half to even, the q +- 1 rule (or SVS_NEAREST), float(q * delta), pocketfft inverse, clip, truncate.  Two identities
+ * hold exactly: the selection 1, 2, .., n gives the bytes and bits of the call without a selection at n_ac = n, in every mode
+ * (and runs its kernels); and for any frames, selected extraction equals the n_ac = 63 extraction with each block's 63 bits
+ * gathered at index[i] - 1.  Capacity is n_frames * (H/8) * (W/8) * count.  Sender and receiver must agree on the selection.
+ * Why: the transform is orthonormal, so the distortion per forced coefficient does not depend on which one it is (PSNR
+ * against the cover moves by less than 0.1 dB), but robustness does - with only row-0 coefficients modified the truncation
+ * errors are perfectly correlated down the columns, which is what costs the reference's own stego bits at small delta.  CPU
+ * oracle, one 480 x 640 frame of noise in [16, 240), full-capacity random payload, payload bit errors of row-major / zig-zag
+ * from scan position 1 / zig-zag from 6:  delta = 4, count = 3 (14 400 bits): 235 / 113 / 54;  delta = 2, count = 7
+ * (33 600): 7 660 / 356 / 191;  delta >= 8: 0 / 0 / 0.
+ * Cost: any selection but the prefix runs the lane-per-block SVS_EXACT_POCKETFFT kernels whatever the mode bits say (the
+ * streaming embed guard and the FAST extract margins are derived for row-major prefixes only): 0.34 - 0.42 of the HBM
+ * roofline against 0.78 for the default n_ac <= 7 embed.  The ratio of a selected call to the SVS_EXACT_POCKETFFT call at the
+ * same n_ac has NOT been measured on a GPU yet: tools/coeff_select_rates.py measures it at 200 x 4K (counts 3, 10, 63) and
+ * writes profiles/coeff_select_rates.txt.  Both run the same quantiser steps; the selected loop adds scalar table reads and
+ * covers all 63 positions with a wave-uniform test each, where the n_ac <= 15 exact kernels cover one or two rows.
+ * There is no read-back, no colour and no _str form.
+ *   coeffs : the selection; the unused tail of index must be 0.  NULL, an index of 0 or above 63, a duplicate, count > 63 or
+ *            a non-zero tail: SVS_ERR_INVALID_ARG before any device work.
+ *   order  : NULL or a keyed block order, as in the ordered calls (a keyed host embed stages whole frames).
+ *   flags  : the mode bits are accepted and do not change the output; SVS_NEAREST on embed (rejected on extract, as
+ *            elsewhere); SVS_READBACK, SVS_KEEP_COLOUR and anything else: SVS_ERR_INVALID_ARG.
+ * Every other argument and contract is that of the ordered calls. */
+typedef struct svs_coeffs {
+    uint8_t count;       /* 0..63 */
+    uint8_t index[63];   /* index[i]: the coefficient of a block's stream bit i; index[count..] must be 0 */
+} svs_coeffs;
+
+#define SVS_SCAN_ROW_MAJOR 0
+#define SVS_SCAN_ZIGZAG 1   /* JPEG zig-zag: 0, 1, 8, 16, 9, 2, 3, 10, ...; position 0 is DC */
+/* out = scan positions first .. first + count - 1 of the scan (first >= 1, count >= 0, first + count <= 64; else
+ * SVS_ERR_INVALID_ARG).  Host only: needs no GPU. */
+int svs_coeffs_scan(svs_coeffs *out, int scan, int first, int count);
+
+int svs_embed_select_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                         const svs_coeffs *coeffs, double delta, const uint8_t *d_bits_packed, uint64_t bit_offset,
+                         uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, void *stream);
+
+int svs_extract_select_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order,
+                           const svs_coeffs *coeffs, double delta, uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes,
+                           uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+/* Host-pointer forms, through the same staging context as svs_embed_ordered / svs_extract_ordered. */
+int svs_embed_select(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                     const svs_coeffs *coeffs, double delta, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                     uint32_t flags, uint64_t *n_embedded);
+
+int svs_extract_select(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                       double delta, uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
+                       uint64_t *n_bits_out);
+
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:
  *   d_counts : NULL, or a device buffer of two uint64 (8-byte aligned) that the call ADDS {blocks repaired, blocks left

@@ -464,6 +464,43 @@ SVS_HD uint32_t window_bit(uint32_t hi, uint32_t lo, int i) {
     return ((i < 32) ? (hi >> ((31 - i) & 31)) : (lo >> ((63 - i) & 31))) & 1u;
 }
 
+// A coefficient SELECTION (include/svsdct.h svs_coeffs) in the form the exact bodies read it: the inverse table.  Byte k & 3
+// of w[k >> 2] is the block-local stream slot that flat row-major coefficient k carries, 0xFF for none; count = slots per
+// block.  count == 0: no selection - the row-major prefix 1..n of the call.  The quantiser loops stay unrolled over k, so
+// slot(k) has a compile-time position (a scalar shift and mask of a kernel-argument dword) and the coefficient registers
+// keep compile-time indices; only the slot - which bit of the payload window - is a run-time, wave-uniform value.
+struct CoeffTable {
+    uint32_t w[16];
+    uint32_t count;
+    SVS_HD uint32_t slot(int k) const { return (w[k >> 2] >> (8 * (k & 3))) & 0xFFu; }
+};
+
+// host side: the table of `count` indices; false unless they are distinct and in 1..63 (count <= 63)
+inline bool make_coeff_table(const uint8_t *index, uint32_t count, CoeffTable *t) {
+    for (int i = 0; i < 16; ++i) t->w[i] = 0xFFFFFFFFu;
+    t->count = 0;
+    if (count > 63) return false;
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t k = index[i];
+        if (k < 1 || k > 63 || t->slot((int)k) != 0xFFu) return false;
+        t->w[k >> 2] &= ~(0xFFu << (8 * (k & 3))) | (i << (8 * (k & 3)));
+    }
+    t->count = count;
+    return true;
+}
+
+// the selection 1, 2, .., count: what a call without a selection does at n_ac = count
+inline bool coeff_table_is_prefix(const CoeffTable &t) {
+    for (uint32_t k = 1; k <= t.count; ++k)
+        if (t.slot((int)k) != k - 1) return false;
+    return true;
+}
+
+// bit s (0 = first; run-time, wave-uniform) of the 64-bit MSB-first window hi:lo; (63 - s) & 31 == (31 - s) & 31
+SVS_HD uint32_t window_bit_at(uint32_t hi, uint32_t lo, uint32_t s) {
+    return ((s < 32u ? hi : lo) >> ((31u - s) & 31u)) & 1u;
+}
+
 // bits a block takes from a budget of n_bits when its first stream bit is `first`
 // (config_and_setup.py:130,132,141)
 SVS_HD uint32_t block_budget(uint64_t first, uint64_t n_bits, uint32_t n) {
@@ -869,14 +906,37 @@ SVS_HD void qim_exact_paired(pf::f32x2 (&D2)[4][8], uint32_t n, uint32_t nb, uin
     }
 }
 
+// The same loop for a coefficient selection (CoeffTable): coefficient k carries stream slot sel.slot(k) of the block when that
+// is below sel.count (0xFF is not), and takes payload while the slot is inside the block's budget nb.  k stays a compile-time
+// index; the slot is wave-uniform.  The prefix table 1..n gives qim_exact_paired's result.
+template <int QM, bool NEAREST>
+SVS_HD void qim_exact_selected(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, uint32_t nb, uint32_t hi, uint32_t lo,
+                               const QimRule &qp) {
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        const uint32_t s = sel.slot(k);
+        if (s < sel.count) {  // wave-uniform
+            const int bit = (int)window_bit_at(hi, lo, s);
+            const float c = D2[k >> 4][k & 7][(k >> 3) & 1];
+            const float cn = qim_target<QM, NEAREST>(c, bit, qp);
+            D2[k >> 4][k & 7][(k >> 3) & 1] = (s < nb) ? cn : c;
+        }
+    }
+}
+
+// `sel`: NULL (the row-major prefix 1..n) or a selection; then n is not read, nb counts slots of the selection.  The callers
+// pass a compile-time NULL or the address of a by-value kernel argument, so the test folds on either side.
 template <int U, int QM>
 SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo,
-                              const QimRule &qp, bool constant_block = false) {
+                              const QimRule &qp, bool constant_block = false, const CoeffTable *sel = nullptr) {
     using pf::f32x2;
     f32x2 D2[4][8];
     if (constant_block) forward_exact_paired_constant(ubyte_to_float<0>(rx[0]), D2);
     else forward_exact_paired(rx, ry, D2);
-    if (qp.nearest) qim_exact_paired<U, QM, true>(D2, n, nb, hi, lo, qp);
+    if (sel) {
+        if (qp.nearest) qim_exact_selected<QM, true>(D2, *sel, nb, hi, lo, qp);
+        else qim_exact_selected<QM, false>(D2, *sel, nb, hi, lo, qp);
+    } else if (qp.nearest) qim_exact_paired<U, QM, true>(D2, n, nb, hi, lo, qp);
     else qim_exact_paired<U, QM, false>(D2, n, nb, hi, lo, qp);
     f32x2 P2[4][8];  // vertical inverse of coefficient-column pairs: P2[p][y] = (P[y][2p], P[y][2p+1])
 #pragma unroll
@@ -1453,6 +1513,26 @@ SVS_HD void extract_block_exact(const uint32_t (&rx)[8], const uint32_t (&ry)[8]
             const int i = k - 1;
             if (i < 32) hi |= bit << ((31 - i) & 31);
             else lo |= bit << ((63 - i) & 31);
+        }
+    }
+}
+
+// EXACT extract with a coefficient selection: the parity of coefficient k lands at window position sel.slot(k) (instead of
+// k - 1); the caller packs sel.count bits per block as always
+template <int QM>
+SVS_HD void extract_block_exact_selected(const uint32_t (&rx)[8], const uint32_t (&ry)[8], const CoeffTable &sel,
+                                         const QimParams &qp, uint32_t &hi, uint32_t &lo) {
+    float D[8][8];
+    forward_exact(rx, ry, D);
+    hi = 0;
+    lo = 0;
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        const uint32_t s = sel.slot(k);
+        if (s < sel.count) {  // wave-uniform
+            const uint32_t bit = ((uint32_t)quant_index<QM>(D[k >> 3][k & 7], qp) & 1u) << ((31u - s) & 31u);
+            if (s < 32u) hi |= bit;
+            else lo |= bit;
         }
     }
 }

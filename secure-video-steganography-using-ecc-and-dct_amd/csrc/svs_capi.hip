@@ -198,7 +198,9 @@ using svs::ExtractPath;
 // `two`: two blocks per lane, where the plan and the buffers allow it.  A keyed plan (p.keyed, `ord` its order) launches the
 // KEYED instantiation of the same kernel family, with the order as the last argument.
 int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
-                 svs::Geometry g, const uint32_t *bits, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}) {
+                 svs::Geometry g, const uint32_t *bits, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{},
+                 const svs::CoeffTable *coeffs = nullptr) {
+    const svs::CoeffTable sel = p.selected && coeffs ? *coeffs : svs::CoeffTable{};   // count 0: the row-major prefix
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
     g.pad = p.nearest ? 1u : 0u;
@@ -212,9 +214,9 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
                 constexpr int U = decltype(u)::value;
                 if (p.keyed)
                     return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g,
-                                  p.qp, bits, p.bit_offset, p.n_bits, words, ord);
+                                  p.qp, bits, p.bit_offset, p.n_bits, words, sel, ord);
                 return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words);
+                              p.bit_offset, p.n_bits, words, sel);
             });
         if (p.rows == 2) {   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
             if (p.keyed)
@@ -300,7 +302,8 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
 // svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>.  A keyed plan ORs every block's bits into its
 // slot with global atomics (svs_device.hpp, or_bits_global): the output is cleared first, on the same stream.
 int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
-                   uint64_t out_bytes, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}) {
+                   uint64_t out_bytes, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}, const svs::CoeffTable *coeffs = nullptr) {
+    const svs::CoeffTable sel = p.selected && coeffs ? *coeffs : svs::CoeffTable{};   // count 0: the row-major prefix
     if (p.path == ExtractPath::ZEROS || p.keyed) SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
     if (p.path == ExtractPath::ZEROS) return SVS_OK;
     g.xcd_chunk = p.xcd_chunk;
@@ -311,8 +314,8 @@ int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, co
                 constexpr int U = decltype(r)::value;
                 if (p.keyed)
                     return launch(svs::extract_exact_kernel<U, QM, 1, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, g, p.qp,
-                                  out, out_bytes, ord);
-                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes);
+                                  out, out_bytes, sel, ord);
+                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes, sel);
             });
         if (p.keyed)
             return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
@@ -718,13 +721,28 @@ svs::BlockOrderArgs order_args(const svs_block_order *order, const svs::Geometry
     return order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{};
 }
 
+// The selection of the select entry points -> the kernels' table.  *coeffs = NULL when the selection is the prefix 1..count:
+// the call is then the one without a selection at n_ac = count, streaming kernels included.
+int check_coeffs(const svs_coeffs *c, svs::CoeffTable *table, const svs::CoeffTable **coeffs) {
+    if (!c) return fail(SVS_ERR_INVALID_ARG, "coeffs is NULL");
+    if (c->count > 63) return fail(SVS_ERR_INVALID_ARG, "svs_coeffs.count %u exceeds 63", (unsigned)c->count);
+    for (int i = c->count; i < 63; ++i)
+        if (c->index[i] != 0) return fail(SVS_ERR_INVALID_ARG, "svs_coeffs.index[%d] behind count must be 0", i);
+    if (!svs::make_coeff_table(c->index, c->count, table))
+        return fail(SVS_ERR_INVALID_ARG, "svs_coeffs.index must hold distinct flat indices in 1..63 (DC is never selectable)");
+    *coeffs = svs::coeff_table_is_prefix(*table) ? nullptr : table;
+    return SVS_OK;
+}
+
+constexpr uint32_t kSelectEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_NEAREST;
+
 constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_READBACK | SVS_NEAREST;
 
 // svs_embed_dev, svs_embed_ordered_dev (order NULL: the call without an order) and svs_embed_readback_dev (d_counts: the
 // read-back counts, device, added to; NULL for none)
 int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order, double delta,
               int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-              uint64_t *n_embedded, void *stream, uint64_t *d_counts = nullptr) {
+              uint64_t *n_embedded, void *stream, uint64_t *d_counts = nullptr, const svs::CoeffTable *coeffs = nullptr) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
@@ -737,6 +755,7 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
     svs::RouteArgs ra = route_args(delta, g, total, n_bits, bit_offset, flags, false);
     ra.keyed = order != nullptr;
     ra.readback = (flags & SVS_READBACK) != 0;
+    ra.coeffs = coeffs;   // the select calls: n_ac == coeffs->count
     const svs::EmbedPlan p = svs::plan_embed(ra);
     if (p.use > 0) {
         if (!d_bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
@@ -749,7 +768,7 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
     if (p.path == EmbedPath::COPY && d_gray == d_stego) return SVS_OK;
     const bool two = p.two_blocks && rows_allow_two_blocks(planes, d_gray, d_stego);
     const uint32_t *bits = p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr;
-    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g, bits, order_args(order, g))) return rc;
+    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g, bits, order_args(order, g), coeffs)) return rc;
     if (p.readback && p.use > 0)
         if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, d_counts, order_args(order, g))) return rc;
     if (n_embedded) *n_embedded = p.use;
@@ -758,7 +777,8 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
 
 // svs_extract_dev and svs_extract_ordered_dev
 int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
-                uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream) {
+                uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream,
+                const svs::CoeffTable *coeffs = nullptr) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
@@ -772,11 +792,13 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block
     if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
     svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
     ra.keyed = order != nullptr;
+    ra.coeffs = coeffs;   // the select calls: n_ac == coeffs->count
     const svs::ExtractPlan p = svs::plan_extract(ra);
     // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
     if (p.path != ExtractPath::ZEROS && (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)))
         return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, order_args(order, g))) return rc;
+    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, order_args(order, g), coeffs))
+        return rc;
     if (n_bits_out) *n_bits_out = cap;
     return SVS_OK;
 }
@@ -832,7 +854,8 @@ static void copy_gray_reference(uint8_t *dst, const uint8_t *gray, const svs_pla
 // (svs_embed_readback: counts receives the read-back counts; the other calls pass NULL)
 static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out, const svs_planes *planes, double delta, int n_ac,
                       const uint8_t *bits_packed, const char *bits_ascii, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-                      uint64_t *n_embedded, const svs_block_order *order = nullptr, svs_readback_counts *counts = nullptr) {
+                      uint64_t *n_embedded, const svs_block_order *order = nullptr, svs_readback_counts *counts = nullptr,
+                      const svs::CoeffTable *coeffs = nullptr) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
@@ -874,7 +897,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                     // keyed: whole frames - the chunk's first frame is clip frame order->first_frame + f0
                     const svs_block_order o{order ? order->key : 0u, order ? order->first_frame + (uint32_t)f0 : 0u, 0u};
                     return embed_dev(d + off, d + off, &sub, order ? &o : nullptr, delta, n_ac, static_cast<const uint8_t *>(c.bits.p),
-                                     chunk_offset, budget, flags, done, up, d_counts);
+                                     chunk_offset, budget, flags, done, up, d_counts, coeffs);
                 },
                 [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {
                     // back: pixel bytes only (padding in the caller's stego buffer is left alone)
@@ -962,8 +985,10 @@ int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int
     return svs_extract_ordered(gray, planes, nullptr, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out);
 }
 
-int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
-                        uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
+// svs_extract_ordered (order NULL: svs_extract) and svs_extract_select
+static int extract_host(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
+                        uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
+                        const svs::CoeffTable *coeffs = nullptr) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
@@ -976,9 +1001,77 @@ int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs
     return extract_staged(
         gray, span_bytes(planes), bytes, 0, n_bits_out,
         [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
-            return extract_dev(d_in, planes, order, delta, n_ac, d_bits, d_bytes, flags, got, st);
+            return extract_dev(d_in, planes, order, delta, n_ac, d_bits, d_bytes, flags, got, st, coeffs);
         },
         [&](HostStage &c, hipStream_t st) { return stage_d2h(st, bits_packed_out, c.bits.p, bytes); });
+}
+
+int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
+                        uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
+    return extract_host(gray, planes, order, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out);
+}
+
+// ---- coefficient selection ------------------------------------------------------------------------------------------
+// JPEG zig-zag scan of the 8 x 8 block as flat row-major indices; position 0 is DC
+static const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+int svs_coeffs_scan(svs_coeffs *out, int scan, int first, int count) {
+    if (!out) return fail(SVS_ERR_INVALID_ARG, "out is NULL");
+    if (scan != SVS_SCAN_ROW_MAJOR && scan != SVS_SCAN_ZIGZAG) return fail(SVS_ERR_INVALID_ARG, "unknown scan %d", scan);
+    if (first < 1 || count < 0 || count > 63 || first + count > 64)
+        return fail(SVS_ERR_INVALID_ARG, "scan positions %d..%d are not inside 1..63", first, first + count - 1);
+    memset(out, 0, sizeof *out);
+    out->count = (uint8_t)count;
+    for (int i = 0; i < count; ++i) out->index[i] = scan == SVS_SCAN_ZIGZAG ? kZigzag[first + i] : (uint8_t)(first + i);
+    return SVS_OK;
+}
+
+// The select calls are the ordered calls at n_ac = coeffs->count with the selection's table; the prefix 1..count passes no
+// table and is the ordered call itself.  The selection and the flags are checked before anything else.
+int svs_embed_select_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                         const svs_coeffs *coeffs, double delta, const uint8_t *d_bits_packed, uint64_t bit_offset,
+                         uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, void *stream) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
+    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits and SVS_NEAREST", flags);
+    return embed_dev(d_gray, d_stego, planes, order, delta, coeffs->count, d_bits_packed, bit_offset, n_bits, flags, n_embedded,
+                     stream, nullptr, sel);
+}
+
+int svs_embed_select(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                     const svs_coeffs *coeffs, double delta, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                     uint32_t flags, uint64_t *n_embedded) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
+    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits and SVS_NEAREST", flags);
+    return embed_host(gray, stego, nullptr, planes, delta, coeffs->count, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded,
+                      order, nullptr, sel);
+}
+
+int svs_extract_select_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                           double delta, uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
+                           uint64_t *n_bits_out, void *stream) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
+    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED))
+        return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select extract takes the mode bits only", flags);
+    return extract_dev(d_gray, planes, order, delta, coeffs->count, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream,
+                       sel);
+}
+
+int svs_extract_select(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                       double delta, uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
+    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED))
+        return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select extract takes the mode bits only", flags);
+    return extract_host(gray, planes, order, delta, coeffs->count, bits_packed_out, out_capacity_bytes, flags, n_bits_out, sel);
 }
 
 int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, char *bits_ascii_out,

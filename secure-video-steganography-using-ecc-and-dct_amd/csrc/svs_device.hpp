@@ -389,11 +389,14 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
                                                           const QimParams qp,
                                                           const uint32_t *__restrict__ bits,
                                                           const uint64_t bit_offset, const uint64_t n_bits,
-                                                          const uint32_t n_words, const Order... order) {
+                                                          const uint32_t n_words, const CoeffTable sel,
+                                                          const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     // SVS_NEAREST: ONE wave-uniform branch around the whole body, the rule a compile-time constant on either side (QimRule).
-    // A `return` inside the body leaves the body, and nothing follows the two calls.
-    const auto body = [&](const QimRule qp) __attribute__((always_inline)) {
+    // A `return` inside the body leaves the body, and nothing follows the calls.
+    // A coefficient selection (sel.count != 0; the U = 8 instantiations only - svs_route.hpp plans no other for one) is a
+    // second such branch: `table` is a compile-time NULL on the side without one, which is the body as it was.
+    const auto body = [&](const QimRule qp, const CoeffTable *table) __attribute__((always_inline)) {
         const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
         if (gblock >= g.total_blocks) return;
         const int64_t off = block_offset(gblock, g);
@@ -410,13 +413,20 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
         for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
         uint32_t hi, lo;
         payload_window(bits, n_words, bit_offset + first, hi, lo);
-        embed_block_exact<U, QM>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp);
+        embed_block_exact<U, QM>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp, false, table);
 #pragma unroll
         for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
         store_rows<1>(stego + off, g.row_pitch, v);
     };
-    if (g.pad) body(QimRule(qp, 1u));
-    else body(QimRule(qp, 0u));
+    if constexpr (U == 8) {
+        if (sel.count) {   // Geometry::n_ac == sel.count: the stream ranges and the block budget are those of n_ac slots
+            if (g.pad) body(QimRule(qp, 1u), &sel);
+            else body(QimRule(qp, 0u), &sel);
+            return;
+        }
+    }
+    if (g.pad) body(QimRule(qp, 1u), nullptr);
+    else body(QimRule(qp, 0u), nullptr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -869,7 +879,8 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
 template <int U, int QM, int BPL = 1, bool KEYED = false, class... Order>   // BPL: see extract_kernel
 __global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                             const QimParams qp, uint8_t *__restrict__ out,
-                                                            const uint64_t out_bytes, const Order... order) {
+                                                            const uint64_t out_bytes, const CoeffTable sel,
+                                                            const Order... order) {
     static_assert(BPL == 1, "one block per lane");
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
@@ -884,7 +895,11 @@ __global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__
         uint32_t ax[8], ay[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
-        extract_block_exact<U, QM>(ax, ay, n, qp, hi, lo);
+        // a coefficient selection (U = 8 only; n == sel.count): one wave-uniform branch around the block's arithmetic
+        bool selected = false;
+        if constexpr (U == 8) selected = sel.count != 0;
+        if (selected) extract_block_exact_selected<QM>(ax, ay, sel, qp, hi, lo);
+        else extract_block_exact<U, QM>(ax, ay, n, qp, hi, lo);
         if constexpr (KEYED) or_bits_global<U>(out, stream_first<true>(gblock, n, g, order_arg(order...)), hi, lo);
     }
     if constexpr (!KEYED)

@@ -26,7 +26,16 @@ struct RouteArgs {
     bool keyed = false;       // a keyed block order (svs_embed_ordered_dev / svs_extract_ordered_dev; gray calls only)
     bool readback = false;    // SVS_READBACK (the gray embed calls; svs_embed_bgr_readback*)
     bool nearest = false;     // SVS_NEAREST (every embed call)
+    // a coefficient selection (svs_embed_select* / svs_extract_select*; gray calls only): NULL for none, else its table with
+    // count == n_ac.  The prefix 1..n_ac plans exactly as no selection does; any other one runs the lane-per-block exact
+    // kernels in every mode - the streaming embed guard and the FAST extract margins (tools/guard_bound.py) are derived for
+    // row-major prefixes only.
+    const CoeffTable *coeffs = nullptr;
 };
+
+inline bool route_selected(const RouteArgs &a) {
+    return a.coeffs && a.coeffs->count != 0 && !coeff_table_is_prefix(*a.coeffs);
+}
 
 // COPY: nothing to embed and an empty payload - the reference's loops break before the first block.  Gray: a byte copy through
 // embed_row1_kernel<QM_F32> (none when the call is in place); BGR: the BGR -> gray -> BGR conversion of embed_bgr_kernel<1>.
@@ -50,6 +59,7 @@ struct EmbedPlan {
     QimParams qp;
     uint64_t use;             // payload bits embedded (*n_embedded)
     uint64_t bit_offset, n_bits, n_words;   // the kernel's payload arguments; n_words >= 2^32: too large for one call
+    bool selected;            // the launch passes the call's CoeffTable (EXACT with rows = 8 only), else an empty one
 };
 
 // Which kernel family (include/svsdct.h `flags`).  The streaming kernels cover one and two coefficient rows (n <= 15) inside the
@@ -61,9 +71,10 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
     const uint64_t cap = a.total_blocks * n;
     p.use = a.n_bits < cap ? a.n_bits : cap;
     if (!(a.delta > 0.0) || n == 0) p.use = 0;   // nothing can be embedded (config_and_setup.py:143-145)
-    const int rows = rows_for((int)n);
+    const bool selected = route_selected(a);
+    const int rows = selected ? 8 : rows_for((int)n);
     const bool in_range = a.delta >= SVS_GUARD_DELTA_MIN && a.delta <= SVS_GUARD_DELTA_MAX;
-    const bool streaming = p.use > 0 && in_range && !a.pocketfft && rows <= 2 && !(a.guarded_off && !a.bgr);
+    const bool streaming = p.use > 0 && in_range && !a.pocketfft && rows <= 2 && !(a.guarded_off && !a.bgr);   // never selected: rows = 8
     p.xcd_chunk = kEighth;
     const int qm = make_qim(p.use == 0 ? 1.0 : a.delta, &p.qp);
     if (p.use > 0) {
@@ -79,6 +90,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.keyed = a.keyed;
         p.readback = a.readback;
         p.nearest = a.nearest;                // STREAMING and EXACT only: the other paths have no coefficient to force
+        p.selected = selected;                // likewise: the other paths touch no coefficient
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;
@@ -109,6 +121,7 @@ struct ExtractPlan {
     uint32_t xcd_chunk;
     QimParams qp;
     bool keyed;               // the KEYED instantiation of the family (not ZEROS: all bits 0 in any order)
+    bool selected;            // the launch passes the call's CoeffTable (EXACT with rows = 8 only), else an empty one
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -120,7 +133,8 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
         p.path = ExtractPath::ZEROS;
         return p;
     }
-    p.rows = rows_for((int)a.n_ac);
+    p.selected = route_selected(a);
+    p.rows = p.selected ? 8 : rows_for((int)a.n_ac);
     p.xcd_chunk = p.rows == 1 ? 32u : (p.rows == 2 && !a.bgr ? 0u : kEighth);
     p.qm = make_qim(a.delta, &p.qp) == QM_POW2 ? QM_POW2 : QM_F32;
     const float t = a.tie_scale;
@@ -133,7 +147,7 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     // the FAST kernels with two and more rows round c / delta by adding 1.5 * 2^23, which needs |c / delta| < 2^22.  With one
     // row the pocketfft-identical forward costs 0.2-3 % (the kernel stays HBM-bound; profiles/history/r01_ab_quant_exact.txt),
     // so FAST mode uses it too; with more rows it costs ~17 % and stays opt-in.
-    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1) exact = true;
+    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected) exact = true;
     p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
     p.keyed = a.keyed;
     return p;

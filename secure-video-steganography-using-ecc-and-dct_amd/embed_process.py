@@ -19,6 +19,7 @@ from config_and_setup import (bitstream_ke_bytes, buat_pasangan_kunci_ecc, buat_
                               enkripsi_aes_gcm, hitung_sha3_256, persiapkan_file_input,  # noqa: F401
                               serialisasi_kunci_publik_ecc_compressed, setup_kunci_ecc)  # noqa: F401
 from svsdct import batch as _batch
+from svsdct import coeffs as _coeffs
 from svsdct import framing as _framing
 from svsdct import order as _order
 from svsdct.pipeline import FramePipeline, SlotFeeder, read_ahead
@@ -54,6 +55,11 @@ READBACK_COLOUR = os.environ.get("SVS_READBACK_COLOUR", "0") == "1"
 # instead of the reference's fixed direction (SVS_NEAREST, include/svsdct.h): about 2 dB more PSNR at the same delta.  The stego
 # frames are no longer the reference's pixels; the receiver does not change.  Allowed with every other switch.
 NEAREST = os.environ.get("SVS_NEAREST", "0") == "1"
+# SVS_COEFFS (read per call, opt-in): which coefficients of a block carry the payload (svsdct/coeffs.py) - "zigzag",
+# "zigzag:<first scan position>", "rowmajor" or a comma-separated list of num_ac_coeffs distinct flat indices in 1..63.  Unset:
+# the reference's row-major coefficients 1..num_ac_coeffs, today's bytes.  The receiver must set the same value.  The gray path
+# only (with SVS_FUSED_COLOUR the host-conversion gray path runs); refused together with SVS_KEEP_COLOUR, SVS_READBACK and
+# SVS_READBACK_COLOUR (a selection has no colour and no read-back form).  Allowed with SVS_BLOCK_KEY and SVS_NEAREST.
 
 
 def _keyed(block_key=None, **kw):
@@ -126,6 +132,14 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     except (TypeError, ValueError) as exc:
         print(f"    Error: SVS_BLOCK_KEY tidak valid ({exc}).")
         return False, None, None
+    try:
+        pilihan = _coeffs.from_env(_batch.clamp_ac(num_ac_coeffs))
+    except (TypeError, ValueError) as exc:
+        print(f"    Error: SVS_COEFFS tidak valid ({exc}).")
+        return False, None, None
+    if pilihan is not None and (KEEP_COLOUR or READBACK or READBACK_COLOUR):
+        print("    Error: SVS_COEFFS tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK atau SVS_READBACK_COLOUR.")
+        return False, None, None
     if kunci_blok is not None and KEEP_COLOUR:
         print("    Error: SVS_BLOCK_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR.")
         return False, None, None
@@ -164,7 +178,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     print(f"    Video output akan disimpan sebagai '{path_out}' (Codec: FFV1).")
 
     tabel_warna = None
-    if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None:   # keyed order: the host-conversion gray path
+    if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None and pilihan is None:   # keyed order, selection: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -183,6 +197,9 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if NEAREST:
         print("    Info: paritas koefisien dipaksa ke titik kisi terdekat (SVS_NEAREST).")
     terdekat = {"nearest": True} if NEAREST else {}                # no keyword at all when off: the calls stay what they were
+    if pilihan is not None:
+        print(f"    Info: koefisien pembawa payload dipilih (SVS_COEFFS): {list(pilihan)}")
+        terdekat = dict(terdekat, coeffs=pilihan)                  # the gray pipeline's keywords (the colour path is off)
     readback_abu = READBACK or (READBACK_COLOUR and not tabel_warna)   # the gray pipeline's read-back
 
     def lapor_readback(diperbaiki, tersisa):

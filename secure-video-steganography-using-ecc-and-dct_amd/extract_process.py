@@ -17,6 +17,7 @@ from config_and_setup import (bytes_ke_bitstream, buat_shared_secret_ecdh, dekri
                               derive_kunci_aes_dari_shared_secret, deserialisasi_kunci_publik_ecc_compressed,
                               hitung_sha3_256, setup_kunci_ecc)  # noqa: F401
 from svsdct import batch as _batch
+from svsdct import coeffs as _coeffs
 from svsdct import framing as _framing
 from svsdct import order as _order
 from svsdct.pipeline import FramePipeline, SlotFeeder
@@ -29,6 +30,7 @@ _MIN_HEADER_BITS = _framing.HEADER_BITS_STANDARD        # 976 (extract_process.p
 FUSED_COLOUR = os.environ.get("SVS_FUSED_COLOUR", "0") == "1"
 # SVS_BLOCK_KEY (read per call): the sender's keyed block order (embed_process.py); frame k of the video is clip frame k.
 # With SVS_FUSED_COLOUR the host-conversion gray path runs.
+# SVS_COEFFS (read per call): the sender's payload coefficient selection (embed_process.py); likewise the gray path.
 
 
 def _cv2():
@@ -43,11 +45,13 @@ def _gagal(pesan, cap=None):
     return False
 
 
-def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0):
+def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0, coeffs=None):
     if tabel_warna:                                            # frames are colour: convert + extract in one kernel
         packed, n_bits = _batch.extract_bgr_frames(np.stack(frames), delta, n_ac, weights=tabel_warna)
     else:
         keyed = {} if block_key is None else {"block_key": block_key, "first_frame": first_frame}
+        if coeffs is not None:
+            keyed["coeffs"] = coeffs
         packed, n_bits = _batch.extract_frames(np.stack(frames), delta, n_ac, **keyed)
     return np.unpackbits(packed, count=n_bits)
 
@@ -65,6 +69,11 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
     except (TypeError, ValueError) as exc:
         print(f"  Error: SVS_BLOCK_KEY tidak valid ({exc}).")
         return False
+    try:
+        pilihan = _coeffs.from_env(_batch.clamp_ac(num_ac_coeffs))
+    except (TypeError, ValueError) as exc:
+        print(f"  Error: SVS_COEFFS tidak valid ({exc}).")
+        return False
     cv2 = _cv2()
     cap = cv2.VideoCapture(path_stego_video)
     if not cap.isOpened():
@@ -78,7 +87,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
         return False
     per_frame = _batch.capacity_bits(1, h, w, num_ac_coeffs)
     tabel_warna = None
-    if FUSED_COLOUR and kunci_blok is None:                    # keyed order: the host-conversion gray path
+    if FUSED_COLOUR and kunci_blok is None and pilihan is None:   # keyed order, selection: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -102,7 +111,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
             cap.release()
             return False
         print(f"    Mengekstrak bit dari frame video ke-{frame_num}...")
-        bits = _extract_frames([gray], delta_kuantisasi, num_ac_coeffs, tabel_warna, kunci_blok, frame_num - 1)
+        bits = _extract_frames([gray], delta_kuantisasi, num_ac_coeffs, tabel_warna, kunci_blok, frame_num - 1, pilihan)
         if bits.size == 0:
             print(f"  Error: Tidak ada bit diekstrak dari frame ke-{frame_num}.")
             cap.release()
@@ -159,7 +168,8 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
             with FramePipeline(h, w, per_batch, delta_kuantisasi, num_ac_coeffs,
                                depth=max(1, min(PIPELINE_DEPTH, -(-lagi // per_batch))),
                                mode=_batch.host_level_mode(),
-                               **({} if kunci_blok is None else {"block_key": kunci_blok})) as pipe:
+                               **({} if kunci_blok is None else {"block_key": kunci_blok}),
+                               **({} if pilihan is None else {"coeffs": pilihan})) as pipe:
                 rencana = {"lagi": lagi}
 
                 def isi(slot):

@@ -18,6 +18,7 @@ from typing import NamedTuple
 
 import numpy as np
 
+from . import coeffs as _coeffs
 from . import native
 from .hostmem import pinned_empty
 from .native import BlockOrder, Planes
@@ -136,6 +137,22 @@ def _order_ref(order: BlockOrder | None):
     return C.byref(order) if order is not None else None
 
 
+def _coeffs_arg(coeffs, n_ac, readback=False):
+    """`coeffs` of a gray call -> None (no selection) or the C ABI's svs_coeffs.  A spec string ("zigzag", "zigzag:6",
+    "rowmajor") resolves with the call's n_ac; an explicit list must have len == n_ac (svsdct/coeffs.py)."""
+    sel = _coeffs.selection(coeffs, clamp_ac(n_ac))
+    if sel is None:
+        return None
+    if readback:
+        raise ValueError("a coefficient selection has no read-back form (readback=True)")
+    return _coeffs.native_coeffs(sel)
+
+
+def _no_coeffs(coeffs):
+    if coeffs is not None:
+        raise ValueError("a coefficient selection has no colour form: convert to gray and use the gray calls")
+
+
 class ReadbackCounts(NamedTuple):
     """what an SVS_READBACK embed did: blocks that did not read back and were repaired / kept the reference's bytes"""
     repaired: int
@@ -144,7 +161,7 @@ class ReadbackCounts(NamedTuple):
 
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
-                 nearest: bool = False):
+                 nearest: bool = False, coeffs=None):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
@@ -157,8 +174,13 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     nearest : opt-in (SVS_NEAREST, include/svsdct.h): a coefficient whose parity has to change moves to the nearer of its two
     neighbouring lattice points instead of the reference's fixed direction - about 2 dB more PSNR, the same receiver; the
     stego pixels are not the reference's any more.
+    coeffs : None (the reference's row-major coefficients 1..n_ac) or a payload coefficient selection (svsdct/coeffs.py:
+    "zigzag", "zigzag:<first>", "rowmajor" or a list of n_ac distinct flat indices in 1..63): stream bit i of a block goes
+    to coefficient index[i].  It combines with block_key, first_frame, nearest and mode (any selection but the prefix runs
+    the exact kernels in every mode); ValueError with readback.  The receiver must use the same selection.
     Returns (stego uint8 [F,H,W], n_embedded), with readback (stego, n_embedded, ReadbackCounts)."""
     order = block_order(block_key, first_frame)
+    sel = _coeffs_arg(coeffs, n_ac, readback)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -181,7 +203,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
                                     C.byref(done), C.byref(counts))
         native.check(rc, "svs_embed_readback")
         return stego, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
-    if order is None:
+    if sel is not None:
+        rc = lib.svs_embed_select(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), C.byref(sel),
+                                  float(delta), packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest),
+                                  C.byref(done))
+        native.check(rc, "svs_embed_select")
+    elif order is None:
         rc = lib.svs_embed(stack.ctypes.data, stego.ctypes.data, C.byref(planes), float(delta), int(n_ac),
                            packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest), C.byref(done))
         native.check(rc, "svs_embed")
@@ -194,11 +221,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
 
 
 def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
-                   first_frame: int = 0):
+                   first_frame: int = 0, coeffs=None):
     """Extract the packed bit stream of a stack of gray frames on the GPU.  block_key / first_frame: as embed_frames (the
-    sender's key and clip frame index).
+    sender's key and clip frame index).  coeffs: as embed_frames (the sender's selection).
     Returns (packed uint8 [ceil(n_bits/8)], n_bits)."""
     order = block_order(block_key, first_frame)
+    sel = _coeffs_arg(coeffs, n_ac)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -207,7 +235,11 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     out = np.zeros(max(4, (cap + 7) // 8 + (-((cap + 7) // 8)) % 4), np.uint8)
     got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    if order is None:
+    if sel is not None:
+        rc = lib.svs_extract_select(stack.ctypes.data, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
+                                    out.ctypes.data, out.size, mode_flags(mode), C.byref(got))
+        native.check(rc, "svs_extract_select")
+    elif order is None:
         rc = lib.svs_extract(stack.ctypes.data, C.byref(planes), float(delta), int(n_ac), out.ctypes.data,
                              out.size, mode_flags(mode), C.byref(got))
         native.check(rc, "svs_extract")
@@ -287,14 +319,21 @@ def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: s
 def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_packed: int,
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
-                 nearest: bool = False) -> int:
+                 nearest: bool = False, coeffs=None) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
     native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
     read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
-    it adds {repaired, unrepaired} into.  nearest: SVS_NEAREST, as embed_frames."""
+    it adds {repaired, unrepaired} into.  nearest: SVS_NEAREST, as embed_frames.  coeffs: a payload coefficient selection,
+    as embed_frames (svs_embed_select_dev)."""
     done = C.c_uint64(0)
     flags = embed_flags(mode, nearest)
-    if readback:
+    sel = _coeffs_arg(coeffs, n_ac, readback)
+    if sel is not None:
+        rc = native.load().svs_embed_select_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
+                                                d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done),
+                                                stream or None)
+        native.check(rc, "svs_embed_select_dev")
+    elif readback:
         rc = native.load().svs_embed_readback_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), float(delta),
                                                   int(n_ac), d_bits_packed, int(bit_offset), int(n_bits), flags,
                                                   C.byref(done), d_counts or None, stream or None)
@@ -313,10 +352,16 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
 
 
 def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
-                   stream: int = 0, mode: str | None = None, order: BlockOrder | None = None) -> int:
-    """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order: as embed_device."""
+                   stream: int = 0, mode: str | None = None, order: BlockOrder | None = None, coeffs=None) -> int:
+    """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order, coeffs: as embed_device."""
     got = C.c_uint64(0)
-    if order is None:
+    sel = _coeffs_arg(coeffs, n_ac)
+    if sel is not None:
+        rc = native.load().svs_extract_select_dev(d_gray, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
+                                                  d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got),
+                                                  stream or None)
+        native.check(rc, "svs_extract_select_dev")
+    elif order is None:
         rc = native.load().svs_extract_dev(d_gray, C.byref(planes), float(delta), int(n_ac), d_bits_out,
                                            int(out_capacity_bytes), mode_flags(mode), C.byref(got),
                                            stream or None)
@@ -346,12 +391,13 @@ def _bgr_flags(mode, keep_colour, nearest=False):
 def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Planes, delta, n_ac,
                      d_bits_packed: int, bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                      weights=None, in_pitches=None, out_pitches=None, keep_colour: bool = False, readback: bool = False,
-                     d_counts: int = 0, nearest: bool = False) -> int:
+                     d_counts: int = 0, nearest: bool = False, coeffs=None) -> int:
     """Enqueue the fused BGR -> gray -> embed -> BGR kernel over packed (or pitched) interleaved BGR frames;
     `d_gray_ref` (0 to skip) receives the gray frames before embedding.  keep_colour: stego pixels keep the cover's
     colour (SVS_KEEP_COLOUR; their gray is the stego plane) instead of B = G = R.  readback: the read-back pass follows on
     the same stream, in place on the BGR output (svs_embed_bgr_readback_dev); d_counts: 0, or a device buffer of two uint64
     that the call adds {repaired, unrepaired} into.  nearest: SVS_NEAREST, as embed_frames.  Returns bits embedded."""
+    _no_coeffs(coeffs)
     irp, ifp = in_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     orp, ofp = out_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     keep, wptr = _weights_arg(weights)
@@ -372,8 +418,9 @@ def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Pla
 
 
 def extract_bgr_device(d_bgr: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
-                       stream: int = 0, weights=None, pitches=None) -> int:
+                       stream: int = 0, weights=None, pitches=None, coeffs=None) -> int:
     """Enqueue extraction straight from interleaved BGR frames; returns the number of bits the batch yields."""
+    _no_coeffs(coeffs)
     rp, fp = pitches or (3 * planes.width, 3 * planes.width * planes.height)
     keep, wptr = _weights_arg(weights)
     got = C.c_uint64(0)
@@ -394,12 +441,13 @@ def _as_bgr_stack(frames: np.ndarray) -> np.ndarray:
 
 def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                      device: int = 0, mode: str | None = None, weights=None, want_gray: bool = True,
-                     keep_colour: bool = False, readback: bool = False, nearest: bool = False):
+                     keep_colour: bool = False, readback: bool = False, nearest: bool = False, coeffs=None):
     """BGR frames in, stego BGR frames out (one fused pass on the GPU).  keep_colour: see embed_bgr_device.  readback: the
     blocks whose payload bits do not read back are repaired in place on the BGR output (svs_embed_bgr_readback,
     include/svsdct.h).  nearest: SVS_NEAREST, as embed_frames.
     Returns (stego_bgr uint8 [F,H,W,3], gray uint8 [F,H,W] (the cover's) or None, n_embedded), with readback
     (stego_bgr, gray, n_embedded, ReadbackCounts)."""
+    _no_coeffs(coeffs)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_bgr_stack(frames_bgr)

@@ -52,10 +52,19 @@ class BlockOrder(C.Structure):
     _fields_ = [("key", C.c_uint64), ("first_frame", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Coeffs(C.Structure):
+    """struct svs_coeffs: the payload coefficient selection of the select entry points (include/svsdct.h, svsdct/coeffs.py)"""
+    _fields_ = [("count", C.c_uint8), ("index", C.c_uint8 * 63)]
+
+
+SVS_SCAN_ROW_MAJOR = 0
+SVS_SCAN_ZIGZAG = 1
+
 _u8p = C.c_void_p   # device or host byte pointers are passed as integers / c_void_p
 _u64p = C.POINTER(C.c_uint64)
 _PL = C.POINTER(Planes)
 _BO = C.POINTER(BlockOrder)
+_CO = C.POINTER(Coeffs)
 
 # name -> (restype, argtypes); every symbol include/svsdct.h declares
 SIGNATURES = {
@@ -88,6 +97,12 @@ SIGNATURES = {
     "svs_embed_ordered": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                      _u64p]),
     "svs_extract_ordered": (C.c_int, [_u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_coeffs_scan": (C.c_int, [_CO, C.c_int, C.c_int, C.c_int]),
+    "svs_embed_select_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, C.c_double, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p,
+                                        C.c_void_p]),
+    "svs_extract_select_dev": (C.c_int, [_u8p, _PL, _BO, _CO, C.c_double, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
+    "svs_embed_select": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, C.c_double, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_extract_select": (C.c_int, [_u8p, _PL, _BO, _CO, C.c_double, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                           _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,

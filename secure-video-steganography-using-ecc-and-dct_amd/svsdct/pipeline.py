@@ -30,6 +30,7 @@ import threading
 import numpy as np
 
 from . import batch, native
+from . import coeffs as _coeffs
 from .native import Planes
 
 
@@ -49,14 +50,18 @@ def _device(nbytes: int):
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
-                 nearest: bool = False):
+                 nearest: bool = False, coeffs=None):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
-        towards the nearer lattice point (SVS_NEAREST, include/svsdct.h)."""
+        towards the nearer lattice point (SVS_NEAREST, include/svsdct.h).  coeffs: None or a payload coefficient selection
+        for every batch, as batch.embed_frames (resolved once with n_ac; ValueError with readback)."""
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
         self.block_key = batch.block_order(block_key).key if block_key is not None else None
+        self.coeffs = _coeffs.selection(coeffs, batch.clamp_ac(n_ac))
+        if self.coeffs is not None and readback:
+            raise ValueError("a coefficient selection has no read-back form (readback=True)")
         native.ensure_device(device)
         self.lib = native.load()
         self.device = device
@@ -125,7 +130,7 @@ class FramePipeline:
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
                                   stream=s["stream"].value, mode=self.mode, order=self._order(first_frame),
                                   readback=self.readback, d_counts=self._d_counts.value if self._d_counts else 0,
-                                  nearest=self.nearest)
+                                  nearest=self.nearest, coeffs=self.coeffs)
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
         return used
@@ -144,7 +149,7 @@ class FramePipeline:
         native.check(self.lib.svs_memcpy_h2d(s["d_frames"], s["hin_p"], nbytes, s["stream"]), "svs_memcpy_h2d")
         got = batch.extract_device(s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac, s["d_bits"].value,
                                    self._bits_bytes, stream=s["stream"].value, mode=self.mode,
-                                   order=self._order(first_frame))
+                                   order=self._order(first_frame), coeffs=self.coeffs)
         native.check(self.lib.svs_memcpy_d2h(s["hbits_p"], s["d_bits"], (got + 7) // 8, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, got
         return got
