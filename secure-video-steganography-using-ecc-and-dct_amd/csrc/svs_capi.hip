@@ -33,17 +33,7 @@ int fail(int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail(SVS_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-svs::FastDiv make_div(uint32_t d) {
-    // q = (n * mul) >> shift is exact for n < 2^31:  shift = 31 + ceil(log2 d), mul = ceil(2^shift / d)
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    svs::FastDiv r;
-    r.shift = 31 + l;
-    r.mul = (uint32_t)(((1ull << r.shift) + d - 1) / d);
-    r.div = d;
-    r.pad = 0;
-    return r;
-}
+using svs::make_div;   // svs_index.hpp
 
 // Experiment knobs.  The PRODUCT build reads no environment variable at all: `knob()` folds to its compiled-in default, so
 // no variable can reroute a kernel, let alone touch the parity guarantee of a flag.  The experiments
@@ -1104,7 +1094,15 @@ int svs_shutdown(void) {
 }
 
 // the BGR row movers (load_bgr_row, wave_load_gray, wave_store_gray_as_bgr) access rows 8 bytes at a time
+// block_offset_bgr takes the byte column of a block, 24 * (blocks before it in the row), in 32 bits
+static int check_bgr_width(const svs_planes *p) {
+    if (3 * (int64_t)p->width >= (1ll << 32))
+        return fail(SVS_ERR_INVALID_ARG, "BGR rows of %d pixels are 4 GiB or longer; at most 1431655760 pixels per row", p->width);
+    return SVS_OK;
+}
+
 static int check_bgr(const svs_planes *p, const void *bgr, int64_t rp, int64_t fp) {
+    if (int rc = check_bgr_width(p)) return rc;
     if (!bgr || ((uintptr_t)bgr % 8)) return fail(SVS_ERR_INVALID_ARG, "BGR pointer NULL or not 8-byte aligned");
     if (rp < 3 * (int64_t)p->width || (rp % 8) || fp < rp * p->height || (fp % 8))
         return fail(SVS_ERR_INVALID_ARG, "BGR pitches must cover 3*width bytes per row and be multiples of 8");
@@ -1157,6 +1155,7 @@ static int colour_params(const svs_planes *p, const void *in, int64_t irp, int64
                          int64_t ofp, const uint32_t *weights, svs::ColourParams *c) {
     const void *ptrs[2] = {in, out};
     const int64_t rps[2] = {irp, orp}, fps[2] = {ifp, ofp};
+    if (int rc = check_bgr_width(p)) return rc;
     for (int i = 0; i < 2; ++i) {
         if (i == 1 && !out) break;
         if (!ptrs[i] || ((uintptr_t)ptrs[i] % 8)) return fail(SVS_ERR_INVALID_ARG, "BGR pointer NULL or not 8-byte aligned");
@@ -1197,6 +1196,7 @@ static int embed_bgr_dev(const uint8_t *d_bgr_in, int64_t in_row_pitch, int64_t 
     const svs::EmbedPlan p = svs::plan_embed(ra);
     if (p.use > 0 && (!d_bits_packed || ((uintptr_t)d_bits_packed % 4)))
         return fail(SVS_ERR_INVALID_ARG, "bits pointer NULL or not 4-byte aligned");
+    if (p.use > 0 && bit_offset + p.use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
     if (p.n_words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
     if (int rc = launch_embed_bgr(p, (flags & SVS_KEEP_COLOUR) != 0, total, (hipStream_t)stream, d_bgr_in, d_bgr_out, d_gray_ref, g,
                                   c, p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr, d_counts))

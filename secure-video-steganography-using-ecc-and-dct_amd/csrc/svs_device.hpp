@@ -7,67 +7,21 @@
 
 #include "svs_block.hpp"
 #include "svs_colour.hpp"
+#include "svs_index.hpp"
 #include "svs_order.hpp"
 #include "svs_readback.hpp"
 
 namespace svs {
 
-// ---------------------------------------------------------------------------------------
-// geometry shared by all kernels; division by W/8 and by blocks-per-frame is done with
-// host-computed multipliers (exact for dividends < 2^31)
-// ---------------------------------------------------------------------------------------
-struct FastDiv {
-    uint32_t mul;
-    uint32_t shift;  // 31..62
-    uint32_t div;
-    uint32_t pad;
-};
-
-struct Geometry {
-    FastDiv by_wb;          // divide by blocks per block-row
-    FastDiv by_bpf;         // divide by blocks per frame
-    uint32_t total_blocks;  // n_frames * blocks per frame   (< 2^31)
-    uint32_t n_ac;          // 1..63
-    uint32_t xcd_chunk;     // tile_id() chunk (0 = identity)
-    uint32_t pad;           // embed launches: 1 = SVS_NEAREST (the plan's `nearest`; the kernels' QimRule), else 0
-    int64_t row_pitch;
-    int64_t frame_pitch;
-};
-
-__device__ __forceinline__ uint32_t fast_div(uint32_t n, const FastDiv &d) {
-    return (uint32_t)(((uint64_t)n * d.mul) >> d.shift);
-}
-
-// byte offset of the top-left pixel of global block `gblock` (frames in order, raster inside)
-__device__ __forceinline__ int64_t block_offset(uint32_t gblock, const Geometry &g) {
-    const uint32_t frame = fast_div(gblock, g.by_bpf);
-    const uint32_t in_frame = gblock - frame * g.by_bpf.div;
-    const uint32_t brow = fast_div(in_frame, g.by_wb);
-    const uint32_t bcol = in_frame - brow * g.by_wb.div;
-    return (int64_t)frame * g.frame_pitch + (int64_t)(brow * 8u) * g.row_pitch + (int64_t)(bcol * 8u);
-}
+// FastDiv, Geometry, fast_div, block_offset, block_offset_bgr: svs_index.hpp (plain C++, the CPU tier tests it)
 
 #ifndef SVS_WG
 #define SVS_WG 256  // threads per workgroup of the embed / extract kernels
 #endif
 
-// Workgroup -> tile mapping.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 names the
-// group that shares an XCD and its L2).  With chunk C > 0, the workgroups of one XCD take C consecutive
-// tiles at a time: tiles [g*8C + x*C, g*8C + (x+1)*C) go to XCD-group x in round g, so each XCD streams
-// runs of C adjacent tiles.  C = 0 is the identity; C = 0xFFFFFFFF gives every XCD-group one contiguous eighth of the grid.  Placement only affects speed, never results.
-__device__ __forceinline__ uint32_t tile_id(uint32_t chunk) {
-    const uint32_t i = blockIdx.x;
-    if (chunk == 0) return i;
-    if (chunk == 0xFFFFFFFFu) {  // one contiguous eighth of the grid per XCD-group (bijective for any grid)
-        const uint32_t n = gridDim.x, q = n / 8u, r = n % 8u, x = i % 8u;
-        return (x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + i / 8u;
-    }
-    const uint32_t span = 8u * chunk;
-    const uint32_t full = (gridDim.x / span) * span;  // tiles covered by whole rounds
-    if (i >= full) return i;
-    const uint32_t x = i % 8u, j = i / 8u;
-    return (j / chunk) * span + x * chunk + (j % chunk);
-}
+// Workgroup -> tile mapping (svs_index.hpp, tile_of): chunk = 0 is the identity, C > 0 runs of C tiles per XCD-group,
+// kEighth one contiguous eighth of the grid per XCD-group.  Placement only affects speed, never results.
+__device__ __forceinline__ uint32_t tile_id(uint32_t chunk) { return tile_of(blockIdx.x, gridDim.x, chunk); }
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -167,16 +121,8 @@ __device__ __forceinline__ BlockOrderArgs order_arg(const BlockOrderArgs &o) { r
 template <bool KEYED>
 __device__ __forceinline__ uint64_t stream_first(uint32_t gblock, uint32_t n, const Geometry &g, const BlockOrderArgs &o,
                                                  uint64_t *second = nullptr) {
-    if constexpr (!KEYED) {
-        return (uint64_t)gblock * n;
-    } else {
-        const uint32_t f = fast_div(gblock, g.by_bpf);
-        const uint32_t i = gblock - f * g.by_bpf.div;
-        const RoundKeys rk = round_keys(o, o.first_frame + f);
-        const uint64_t frame0 = (uint64_t)f * g.by_bpf.div;
-        if (second) *second = (frame0 + block_to_slot(i + 1u, o, rk)) * n;
-        return (frame0 + block_to_slot(i, o, rk)) * n;
-    }
+    if constexpr (!KEYED) return stream_first_raster(gblock, n);
+    else return stream_first_keyed(gblock, n, g.by_bpf, o, second);
 }
 
 // KEYED extraction: a block's n bits (hi:lo, MSB first from bit 63) ORed into the packed output at stream bit `pos` with
@@ -915,14 +861,7 @@ struct ColourParams {
     uint32_t wb, wg, wr, shift;              // (B*wb + G*wg + R*wr + 2^(shift-1)) >> shift
 };
 
-__device__ __forceinline__ int64_t block_offset_bgr(uint32_t gblock, const Geometry &g, int64_t row_pitch,
-                                                    int64_t frame_pitch) {
-    const uint32_t frame = fast_div(gblock, g.by_bpf);
-    const uint32_t in_frame = gblock - frame * g.by_bpf.div;
-    const uint32_t brow = fast_div(in_frame, g.by_wb);
-    const uint32_t bcol = in_frame - brow * g.by_wb.div;
-    return (int64_t)frame * frame_pitch + (int64_t)(brow * 8u) * row_pitch + (int64_t)(bcol * 24u);
-}
+// block_offset_bgr(gblock, g, row_pitch, frame_pitch): svs_index.hpp
 
 // One block row of interleaved BGR = 24 bytes at an 8-byte aligned address: three 8-byte accesses.  (A 16-byte +
 // an 8-byte access is no faster for loads and 1.7x SLOWER for stores - the 16-byte half is misaligned half the time.)

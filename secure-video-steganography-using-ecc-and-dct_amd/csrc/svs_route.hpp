@@ -5,10 +5,9 @@
 #include <stdint.h>
 
 #include "svs_block.hpp"
+#include "svs_index.hpp"   // kEighth, the tile map the plans name
 
 namespace svs {
-
-constexpr uint32_t kEighth = 0xFFFFFFFFu;   // tile_id() chunk: one contiguous eighth of the grid per XCD-group
 
 // The arguments that decide a call's route.  pocketfft / guarded are the SVS_EXACT_POCKETFFT / SVS_EXACT_GUARDED bits of the
 // call's flags; guarded_off, guard_scale and tie_scale are test hooks (the experiments library's SVS_GUARDED_OFF,
@@ -83,7 +82,8 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.n_ac = n;
         p.bit_offset = a.bit_offset;
         p.n_bits = p.use;
-        p.n_words = ((a.bit_offset + p.use + 7) / 8 + 3) / 4;
+        const uint64_t end = a.bit_offset + p.use;   // the callers refuse a sum that wraps
+        p.n_words = end / 32 + (end % 32 != 0);      // dwords that hold bits [0, end): no rounding term that could wrap
         // the BGR exact kernel covers all eight rows; the gray one has instantiations for one, two and eight
         p.rows = streaming || (!a.bgr && rows <= 2) ? rows : 8;
         p.two_blocks = streaming && !a.bgr && rows == 1;

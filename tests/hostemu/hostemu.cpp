@@ -1,8 +1,8 @@
 // hostemu.cpp - TEST INFRASTRUCTURE ONLY (never loaded by the product package).
 //
 // Runs csrc/svs_block.hpp - the exact per-block arithmetic and bit bookkeeping the gfx950 kernels
-// execute - on the CPU, block by block, so that the CPU-only test tier (and ASan/UBSan) can check
-// it against the oracle without a GPU.  The lane/wave mapping, HBM access and LDS bit packing of
+// execute - and csrc/svs_index.hpp - their tile maps, divisions and offsets - on the CPU, block by
+// block, so that the CPU-only test tier (and ASan/UBSan) can check it against the oracle without a GPU.  The lane/wave mapping, HBM access and LDS bit packing of
 // the kernels are NOT modelled here; those are covered by the -m gpu tests.
 // Build: g++ -O2 -ffp-contract=off -std=c++17 -shared -fPIC -I<csrc> hostemu.cpp -o libsvs_hostemu.so
 #include <cmath>
@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "svs_block.hpp"
+#include "svs_index.hpp"
 #include "svs_route.hpp"
 #include "svs_stage.hpp"
 
@@ -389,6 +390,65 @@ void emu_plan_extract(double delta, int n_ac, uint64_t total, int pocketfft, int
 }
 
 uint64_t emu_chunk_budget(uint64_t pass_bits, uint64_t use, uint64_t g0, uint32_t n) { return svs::chunk_budget(pass_bits, use, g0, n); }
+
+// ---- the index arithmetic of the kernels (csrc/svs_index.hpp) and the payload readers, for tests/test_index_arithmetic_cpu.py ----
+
+// make_div(d) -> out = {mul, shift, div}
+void emu_make_div(uint32_t d, uint32_t *out) {
+    const svs::FastDiv f = svs::make_div(d);
+    out[0] = f.mul; out[1] = f.shift; out[2] = f.div;
+}
+
+// fast_div(n[i], make_div(d)) for i < count
+void emu_fast_div(const uint32_t *n, uint64_t count, uint32_t d, uint32_t *out) {
+    const svs::FastDiv f = svs::make_div(d);
+    for (uint64_t i = 0; i < count; ++i) out[i] = svs::fast_div(n[i], f);
+}
+
+// tile_of(i, grid, chunk) for every i < grid
+void emu_tile_of(uint32_t grid, uint32_t chunk, uint32_t *out) {
+    for (uint32_t i = 0; i < grid; ++i) out[i] = svs::tile_of(i, grid, chunk);
+}
+
+uint32_t emu_tile_of_one(uint32_t i, uint32_t grid, uint32_t chunk) { return svs::tile_of(i, grid, chunk); }
+
+// block_offset (bgr == 0) / block_offset_bgr of blocks gblock[i], geometry filled as the library's make_geometry fills it
+void emu_block_offset(const uint32_t *gblock, uint64_t count, uint32_t wb, uint32_t bpf, int64_t row_pitch, int64_t frame_pitch,
+                      int bgr, int64_t *out) {
+    svs::Geometry g{};
+    g.by_wb = svs::make_div(wb);
+    g.by_bpf = svs::make_div(bpf);
+    g.row_pitch = row_pitch;
+    g.frame_pitch = frame_pitch;
+    for (uint64_t i = 0; i < count; ++i)
+        out[i] = bgr ? svs::block_offset_bgr(gblock[i], g, row_pitch, frame_pitch) : svs::block_offset(gblock[i], g);
+}
+
+// stream_first of blocks gblock[i]: raster (keyed == 0) or under the keyed order of (key, first_frame); second, when not
+// NULL, receives the right neighbour's (keyed only)
+void emu_stream_first(const uint32_t *gblock, uint64_t count, uint32_t n, uint32_t bpf, int keyed, uint64_t key, uint32_t first_frame,
+                      uint64_t *first, uint64_t *second) {
+    const svs::FastDiv by_bpf = svs::make_div(bpf);
+    const svs::BlockOrderArgs o = svs::make_block_order(key, first_frame, bpf);
+    for (uint64_t i = 0; i < count; ++i) {
+        if (!keyed) first[i] = svs::stream_first_raster(gblock[i], n);
+        else first[i] = svs::stream_first_keyed(gblock[i], n, by_bpf, o, second ? &second[i] : nullptr);
+    }
+}
+
+// payload_window / payload_qword at stream bit s of a buffer of n_words dwords of which only dwords [word_base, word_base +
+// the caller's array) exist: `window` holds those, and the readers see it through a pointer biased by word_base
+void emu_payload_window(const uint32_t *window, uint64_t word_base, uint32_t n_words, uint64_t s, uint32_t *hi_lo) {
+    const uint32_t *bits = reinterpret_cast<const uint32_t *>(reinterpret_cast<uintptr_t>(window) - 4u * (uintptr_t)word_base);
+    svs::payload_window(bits, n_words, s, hi_lo[0], hi_lo[1]);
+}
+
+uint64_t emu_payload_qword(const uint32_t *window, uint64_t word_base, uint32_t n_words, uint64_t s) {
+    const uint32_t *bits = reinterpret_cast<const uint32_t *>(reinterpret_cast<uintptr_t>(window) - 4u * (uintptr_t)word_base);
+    return svs::payload_qword(bits, n_words, s);
+}
+
+uint32_t emu_window32(uint64_t q, uint32_t sh) { return svs::window32(q, sh); }
 
 void emu_idct8(const float *X, float *x) {
     float a[8], b[8];

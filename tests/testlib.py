@@ -211,7 +211,7 @@ def hostemu():
     src = os.path.join(REPO, "tests", "hostemu", "hostemu.cpp")
     out = os.path.join(REPO, "tests", "hostemu", "libsvs_hostemu.so")
     deps = [src, os.path.join(CSRC, "svs_block.hpp"), os.path.join(CSRC, "svs_stage.hpp"),
-            os.path.join(CSRC, "svs_route.hpp")]
+            os.path.join(CSRC, "svs_route.hpp"), os.path.join(CSRC, "svs_index.hpp"), os.path.join(CSRC, "svs_order.hpp")]
     stale = not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
     if stale and os.path.exists(out) and os.path.exists("/dev/kfd"):
         stale = False      # on a GPU box use the library built by build(): no compiler child processes there
