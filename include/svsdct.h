@@ -137,6 +137,43 @@ extern "C" {
  * 1.4 - 2.4 dB at the settings the application offers; delta >= 8 stays error-free where the reference's stego is; only
  * delta = 2, where the reference's own stego already fails, gets slightly worse. */
 #define SVS_NEAREST 0x800u
+/* SVS_MINMOVE (every embed call, as SVS_NEAREST; every extract call rejects it with SVS_ERR_INVALID_ARG before any device work):
+ * opt-in minimum-move embedding.  It combines freely with the mode bits, SVS_KEEP_COLOUR, SVS_READBACK, a block order and a
+ * coefficient selection.  The other rules write every payload coefficient ONTO a lattice point q' delta.  The receiver only
+ * needs it INSIDE the decision cell of q' - within delta / 2 of the point - and far enough from the cell's edge to survive the
+ * one disturbance on the way, the clip-and-truncate of the stego pixels.  That disturbance is bounded: the truncation error of
+ * a pixel is in (-1, 0], an AC basis function b_k sums to 0, so in a block that does not clip the error of coefficient
+ * k = 8 u + v is at most 0.5 sum|b_k| = 0.5 S_u S_v, with S_u = sum_x |a_u cos((2 x + 1) u pi / 16)|, a_0 = sqrt(1/8),
+ * a_u = 1/2: between 3.284 and 4.0, and attained (e = -1 where b_k > 0, else 0).  The rule, float32 throughout, the same
+ * operations in the same order on host and device, for a payload coefficient c with bit b at flat index k (under a
+ * coefficient selection k is the selected index):
+ *     t    = SVS_NEAREST's index: q (float32 division, round half to even) if its parity is b, else its q +- 1.  The flag
+ *            implies the nearest direction: setting SVS_NEAREST as well changes nothing;
+ *     c_t  = the float32 value written for t today (float(t * delta));
+ *     h    = (float)(0.5 * (double)delta), rounded once on the host;  r_k = fmaxf(0, h - MARGIN[k]);
+ *     c'   = fminf(fmaxf(c, c_t - r_k), c_t + r_k):  a coefficient inside the band keeps its forward-transform value exactly.
+ * MARGIN[k] = (float)(0.5 S_u S_v + 0.0625) is a table of constants (csrc/svs_block.hpp, derivation above it); the 1/16 covers
+ * the float32 noise of the round trip and the quantiser's division rounding.  The margin is the derived bound and not a tuning
+ * knob: a uniform 2.0 already loses bits.  For delta <= 6.69 every r_k is 0 and the output is SVS_NEAREST's, byte for byte.
+ * A coefficient moves by at most delta (plus rounding), so the streaming kernels and their guard take the rule as they are.
+ * Everything else is the reference's: stream order and budget, the partial block, byte-identical blocks past the budget, the
+ * delta <= 0, n_ac = 0 and empty-payload routes (the flag has no effect there), the pocketfft inverse of all 64 coefficients,
+ * clip, truncate.  With SVS_READBACK the read-back pass starts from the stego this rule wrote.
+ * Cost: the stego is NEITHER the reference's NOR the nearest rule's pixels.  Limit: the guarantee excludes blocks that clip at
+ * 0 / 255 (their error is not bounded by the margin); SVS_READBACK is the remedy there and combines with the flag.  The
+ * receiver is unchanged and the default (flag clear) is byte-identical to before.
+ * Measured ON THE CPU with the oracle's pieces (tests/minmove_lib.py model_embed), one 480 x 640 frame, full-capacity random
+ * payload; PSNR against the cover in dB / payload bit errors, reference | SVS_NEAREST | SVS_MINMOVE:
+ *     noise  n_ac = 10 delta = 20 (the GUI's default)  32.50 / 0 | 34.90 / 0 | 39.71 / 0
+ *     noise  n_ac = 3  delta = 20                      37.62 / 0 | 39.96 / 0 | 44.45 / 0
+ *     noise  n_ac = 10 delta = 12                      36.85 / 0 | 39.18 / 0 | 41.82 / 0
+ *     noise  n_ac = 10 delta = 40                      26.53 / 0 | 28.90 / 0 | 35.64 / 0
+ *     noise  n_ac = 63 delta = 20                      24.59 / 2 | 26.97 / 0 | 32.00 / 0
+ *     noise  n_ac = 10 delta = 8                       40.22 / 0 | 42.49 / 0 | 43.00 / 0
+ *     smooth n_ac = 10 delta = 20                      32.80 / 0 | 34.31 / 0 | 38.39 / 0
+ *     smooth n_ac = 63 delta = 20                      25.05 / 168 | 26.18 / 0 | 30.25 / 0
+ * (0x400 is deliberately not a flag.) */
+#define SVS_MINMOVE 0x1000u
 
 /* Geometry of a batch of gray planes. */
 typedef struct svs_planes {

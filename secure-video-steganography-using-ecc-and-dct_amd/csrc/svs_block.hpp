@@ -416,23 +416,80 @@ SVS_HD int nearest_parity(int q, int bit, float c, const QimParams &qp) {
     return q + (((q ^ bit) & 1) ? dir : 0);
 }
 
+// SVS_MINMOVE (include/svsdct.h): the receiver needs a payload coefficient INSIDE the decision cell of its index, within
+// delta / 2 of the lattice point c_t, and far enough from the cell's edge to survive the one disturbance between embedder and
+// receiver: the clip-and-truncate of the stego pixels.  In a block that does not clip, the truncation error of a pixel is in
+// (-1, 0]; an AC basis function b_k (k = 8 u + v) sums to 0, so the error of coefficient k is sum_x b_k(x) e(x) with e in
+// (-1, 0]^64, at most 0.5 * sum |b_k| = 0.5 * S_u * S_v in magnitude, where S_u = sum_x |a_u cos((2 x + 1) u pi / 16)|,
+// a_0 = sqrt(1/8), a_u = 1/2: S = {2.828427, 2.562915, 2.613126, 2.562915, 2.828427, 2.562915, 2.613126, 2.562915}.  The
+// pattern e = -1 where b_k > 0, else 0, reaches it: the bound is tight, between 3.284 (S_1 S_1 / 2) and 4.0 (S_0 S_4 / 2).
+// MARGIN[k] = (float)(0.5 * S_u * S_v + 0.0625): the 1/16 covers the float32 noise of the round trip (the guard's BETA is
+// about 1e-3) and the division rounding of the quantiser.  Entry 0 (DC, never a payload coefficient) is not used.
+// tests/test_minmove_cpu.py recomputes the table and shows that the bound is attained.
+SVS_HD float minmove_margin(uint32_t k) {
+    static constexpr float MARGIN[64] = {   // [8 u + v]; entry 0 is the DC position's: never a payload coefficient
+        4.0625f,    3.6870098f, 3.758018f,  3.6870098f, 4.0625f,    3.6870098f, 3.758018f,  3.6870098f,
+        3.6870098f, 3.346768f,  3.4111104f, 3.346768f,  3.6870098f, 3.346768f,  3.4111104f, 3.346768f,
+        3.758018f,  3.4111104f, 3.4767137f, 3.4111104f, 3.758018f,  3.4111104f, 3.4767137f, 3.4111104f,
+        3.6870098f, 3.346768f,  3.4111104f, 3.346768f,  3.6870098f, 3.346768f,  3.4111104f, 3.346768f,
+        4.0625f,    3.6870098f, 3.758018f,  3.6870098f, 4.0625f,    3.6870098f, 3.758018f,  3.6870098f,
+        3.6870098f, 3.346768f,  3.4111104f, 3.346768f,  3.6870098f, 3.346768f,  3.4111104f, 3.346768f,
+        3.758018f,  3.4111104f, 3.4767137f, 3.4111104f, 3.758018f,  3.4111104f, 3.4767137f, 3.4111104f,
+        3.6870098f, 3.346768f,  3.4111104f, 3.346768f,  3.6870098f, 3.346768f,  3.4111104f, 3.346768f};
+    return MARGIN[k & 63u];
+}
+
+// How a payload coefficient is written.  REFERENCE: the lattice point of the reference's forced index.  NEAREST: the lattice
+// point of nearest_parity's index.  MINMOVE: nearest_parity's lattice point c_t is only the centre of a band - the
+// coefficient is clamped into [c_t - r_k, c_t + r_k], r_k = max(0, delta / 2 - MARGIN[k]), and keeps its forward-transform
+// value when it is already inside.  With every r_k = 0 (delta <= 6.69) that is NEAREST.
+enum QimRuleKind { RULE_REFERENCE = 0, RULE_NEAREST = 1, RULE_MINMOVE = 2 };
+
 // What the EMBED bodies take: the quantiser parameters plus the rule that forces a wrong parity.  A type of its own, so that
 // QimParams - a by-value argument of every kernel, the extract kernels included - keeps its layout.  A plain QimParams
 // converts to the reference's rule.  The kernels build it from a wave-uniform argument (Geometry::pad, set from the plan) as a
-// compile-time constant on either side of ONE branch around their whole body (svs_device.hpp), so inside a body every test
-// of `nearest` folds away and the default rule's instruction stream is what it was before the flag existed.
+// compile-time constant on every side of ONE branch around their whole body (svs_device.hpp), so inside a body every test
+// of `kind` folds away and the default rule's instruction stream is what it was before the flags existed.
 struct QimRule : QimParams {
-    uint32_t nearest;   // SVS_NEAREST (include/svsdct.h): nearest_parity instead of force_parity
-    SVS_HD QimRule(const QimParams &p, uint32_t nearest_ = 0u) : QimParams(p), nearest(nearest_) {}
+    uint32_t kind;      // QimRuleKind: RULE_REFERENCE, RULE_NEAREST (SVS_NEAREST: nearest_parity instead of force_parity) or
+                        // RULE_MINMOVE (SVS_MINMOVE: nearest_parity and the band)
+    float half_cell;    // SVS_MINMOVE: h = (float)(0.5 * (double)delta), rounded once on the host; not read otherwise
+    SVS_HD QimRule(const QimParams &p, uint32_t kind_ = 0u, float half_cell_ = 0.0f)
+        : QimParams(p), kind(kind_), half_cell(half_cell_) {}
 };
 
-// One payload coefficient through the quantiser, integer form: the value that replaces c.  NEAREST is a compile-time
-// argument of this FUNCTION: the exact bodies choose between the two forms of their quantiser loop with one test of
-// qp.nearest per block (a constant inside a kernel's body, see QimRule).
-template <int QM, bool NEAREST>
-SVS_HD float qim_target(float c, int bit, const QimParams &qp) {
+// The rule in one existing 32-bit word of the launch (Geometry::pad): 0 = the reference's, 1 = SVS_NEAREST, anything else =
+// SVS_MINMOVE and the word is the bit pattern of h.  A positive float32 is never 0, and it is 1 only as the smallest
+// denormal; h = 0 (delta below 2^-149) is sent as 1 too: with such an h every r_k is 0 and the rule IS the nearest one.
+SVS_HD uint32_t rule_word(bool nearest, bool minmove, float half_cell) {
+    if (!minmove) return nearest ? 1u : 0u;
+    const uint32_t w = __builtin_bit_cast(uint32_t, half_cell);
+    return w > 1u ? w : 1u;
+}
+SVS_HD QimRule rule_from_word(const QimParams &p, uint32_t w) {
+    return w > 1u ? QimRule(p, (uint32_t)RULE_MINMOVE, __builtin_bit_cast(float, w)) : QimRule(p, w);
+}
+
+// r_k of SVS_MINMOVE for flat index k (0 under the other rules: not evaluated there).  k is a compile-time constant in the
+// lane-per-block loops (the margin is then a literal) and a lane's own index in the 8-lane replays (a table read).
+template <int RULE>
+SVS_HD float qim_band(const QimRule &qp, uint32_t k) {
+    if constexpr (RULE == RULE_MINMOVE) return fmaxf(0.0f, qp.half_cell - minmove_margin(k));
+    else return 0.0f;
+}
+
+// c clamped into the band of half-width r around the lattice point ct (SVS_MINMOVE; float32, this order on host and device)
+SVS_HD float minmove_clamp(float c, float ct, float r) { return fminf(fmaxf(c, ct - r), ct + r); }
+
+// One payload coefficient through the quantiser, integer form: the value that replaces c.  RULE (a QimRuleKind; `true` is
+// RULE_NEAREST) is a compile-time argument of this FUNCTION: the exact bodies choose between the forms of their quantiser loop
+// with one test of qp.kind per block (a constant inside a kernel's body, see QimRule).  r: qim_band of the coefficient.
+template <int QM, int RULE>
+SVS_HD float qim_target(float c, int bit, const QimParams &qp, float r = 0.0f) {
     const int q = quant_index<QM>(c, qp);
-    return requantised<QM>(NEAREST ? nearest_parity<QM>(q, bit, c, qp) : force_parity(q, bit), qp);
+    const float ct = requantised<QM>(RULE != RULE_REFERENCE ? nearest_parity<QM>(q, bit, c, qp) : force_parity(q, bit), qp);
+    if constexpr (RULE == RULE_MINMOVE) return minmove_clamp(c, ct, r);
+    else return ct;
 }
 
 // 64 stream bits starting at stream bit s of an MSB-first packed buffer viewed as dwords
@@ -892,7 +949,7 @@ SVS_HD void forward_exact_paired_constant(float v, pf::f32x2 (&D2)[4][8]) {
 
 // `constant_block`: the caller knows (wave-uniformly) that all 64 pixels are equal - the forward pass is then the two-line
 // shortcut above (host emulation of flat content; the device replay transforms every block in full)
-template <int U, int QM, bool NEAREST>
+template <int U, int QM, int RULE>
 SVS_HD void qim_exact_paired(pf::f32x2 (&D2)[4][8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo, const QimRule &qp) {
 #pragma unroll
     for (int k = 1; k < 8 * U; ++k) {
@@ -900,7 +957,7 @@ SVS_HD void qim_exact_paired(pf::f32x2 (&D2)[4][8], uint32_t n, uint32_t nb, uin
             const int i = k - 1;
             const int bit = (int)window_bit(hi, lo, i);
             const float c = D2[k >> 4][k & 7][(k >> 3) & 1];
-            const float cn = qim_target<QM, NEAREST>(c, bit, qp);
+            const float cn = qim_target<QM, RULE>(c, bit, qp, qim_band<RULE>(qp, (uint32_t)k));
             D2[k >> 4][k & 7][(k >> 3) & 1] = ((uint32_t)i < nb) ? cn : c;
         }
     }
@@ -908,8 +965,9 @@ SVS_HD void qim_exact_paired(pf::f32x2 (&D2)[4][8], uint32_t n, uint32_t nb, uin
 
 // The same loop for a coefficient selection (CoeffTable): coefficient k carries stream slot sel.slot(k) of the block when that
 // is below sel.count (0xFF is not), and takes payload while the slot is inside the block's budget nb.  k stays a compile-time
-// index; the slot is wave-uniform.  The prefix table 1..n gives qim_exact_paired's result.
-template <int QM, bool NEAREST>
+// index; the slot is wave-uniform.  The prefix table 1..n gives qim_exact_paired's result.  SVS_MINMOVE: the band is that of
+// the coefficient's flat index k, whatever slot it carries.
+template <int QM, int RULE>
 SVS_HD void qim_exact_selected(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, uint32_t nb, uint32_t hi, uint32_t lo,
                                const QimRule &qp) {
 #pragma unroll
@@ -918,7 +976,7 @@ SVS_HD void qim_exact_selected(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, uin
         if (s < sel.count) {  // wave-uniform
             const int bit = (int)window_bit_at(hi, lo, s);
             const float c = D2[k >> 4][k & 7][(k >> 3) & 1];
-            const float cn = qim_target<QM, NEAREST>(c, bit, qp);
+            const float cn = qim_target<QM, RULE>(c, bit, qp, qim_band<RULE>(qp, (uint32_t)k));
             D2[k >> 4][k & 7][(k >> 3) & 1] = (s < nb) ? cn : c;
         }
     }
@@ -934,10 +992,12 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
     if (constant_block) forward_exact_paired_constant(ubyte_to_float<0>(rx[0]), D2);
     else forward_exact_paired(rx, ry, D2);
     if (sel) {
-        if (qp.nearest) qim_exact_selected<QM, true>(D2, *sel, nb, hi, lo, qp);
-        else qim_exact_selected<QM, false>(D2, *sel, nb, hi, lo, qp);
-    } else if (qp.nearest) qim_exact_paired<U, QM, true>(D2, n, nb, hi, lo, qp);
-    else qim_exact_paired<U, QM, false>(D2, n, nb, hi, lo, qp);
+        if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_selected<QM, RULE_MINMOVE>(D2, *sel, nb, hi, lo, qp);
+        else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_selected<QM, RULE_NEAREST>(D2, *sel, nb, hi, lo, qp);
+        else qim_exact_selected<QM, RULE_REFERENCE>(D2, *sel, nb, hi, lo, qp);
+    } else if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_paired<U, QM, RULE_MINMOVE>(D2, n, nb, hi, lo, qp);
+    else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_paired<U, QM, RULE_NEAREST>(D2, n, nb, hi, lo, qp);
+    else qim_exact_paired<U, QM, RULE_REFERENCE>(D2, n, nb, hi, lo, qp);
     f32x2 P2[4][8];  // vertical inverse of coefficient-column pairs: P2[p][y] = (P[y][2p], P[y][2p+1])
 #pragma unroll
     for (int p2 = 0; p2 < 4; ++p2) {
@@ -996,6 +1056,11 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
 // the KD term - and the 16-bit range of the packed column deltas - assume 1.5 delta, so the same BETA bounds both rules.  It
 // is merely not tight under the flag (g_delta could shrink by a third there; not done: a change of the flagged share of blocks
 // wants its own soak).
+// SVS_MINMOVE writes a value between the coefficient and SVS_NEAREST's lattice point, so its change is at most delta plus
+// rounding as well.  tools/guard_bound.py uses two facts about the written value cn_k and no other: it is a float32 that the
+// exact arithmetic writes verbatim (D' = D with cn_k in place), and |cn_k - c_k| <= 1.5 delta + 0.01.  Neither needs cn_k to
+// be a lattice point; a coefficient that stays (cn_k = D_k, change 0) is an unmodified one to the analysis.  So the streaming
+// bodies take the rule with the same BETA.
 #define SVS_GUARD_UEFF (5.9604644775390625e-8 * (1.0 + 0.0009765625))
 // delta range the guarded path is used for (outside it the caller takes the exact kernel): below, the changes are smaller
 // than BETA and every block would be flagged; above, BETA itself exceeds 1/8
@@ -1009,13 +1074,17 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
 // instructions, profiles/r04_valu_issue_rate.txt).  Same results as quant_index / force_parity (tests: guarded mode vs the oracle).
 // NEAREST (SVS_NEAREST, nearest_parity): q +- 1 is +- 1 on the bit pattern of m as well (an ulp at 1.5 * 2^23 is 1), and the side
 // is a compare of c with the unforced q delta and a select - no branch.  A compile-time argument of this FUNCTION: the
-// callers choose between the two forms of their quantiser loop with one test of qp.nearest per block (QimRule).
-template <int QM, bool NEAREST = false>
-SVS_HD float qim_change(float c, uint32_t bit, const QimParams &qp) {
+// callers choose between the two forms of their quantiser loop with one test of qp.kind per block (QimRule).
+// RULE_MINMOVE (SVS_MINMOVE): the change to the clamped value, minmove_clamp of c around that lattice point with the band r
+// (qim_band) - 0 exactly for a coefficient inside its band.
+template <int QM, int RULE = RULE_REFERENCE>
+SVS_HD float qim_change(float c, uint32_t bit, const QimParams &qp, float r = 0.0f) {
     if constexpr (QM == QM_DOUBLE) {
         const int q0 = quant_index<QM>(c, qp);
-        const int q = NEAREST ? nearest_parity<QM>(q0, (int)bit, c, qp) : force_parity(q0, (int)bit);
-        return (float)((double)q * qp.delta_d) - c;
+        const int q = RULE != RULE_REFERENCE ? nearest_parity<QM>(q0, (int)bit, c, qp) : force_parity(q0, (int)bit);
+        const float ct = (float)((double)q * qp.delta_d);
+        if constexpr (RULE == RULE_MINMOVE) return minmove_clamp(c, ct, r) - c;
+        else return ct - c;
     } else {
         const float kMagic = 12582912.0f;   // 1.5 * 2^23
         const float t = c * qp.inv_delta_f;
@@ -1027,7 +1096,7 @@ SVS_HD float qim_change(float c, uint32_t bit, const QimParams &qp) {
                 m = rintf(c / qp.delta_f) + kMagic;
         }
         uint32_t mb = __builtin_bit_cast(uint32_t, m);
-        if constexpr (NEAREST) {
+        if constexpr (RULE != RULE_REFERENCE) {
             const float c0 = (m - kMagic) * qp.delta_f;
             const uint32_t dir = c > c0 ? 1u : (c < c0 ? ~0u : 2u * bit - 1u);
             mb += ((mb ^ bit) & 1u) ? dir : 0u;
@@ -1035,7 +1104,8 @@ SVS_HD float qim_change(float c, uint32_t bit, const QimParams &qp) {
             mb = (mb & ~1u) | bit;
         }
         const float qf = __builtin_bit_cast(float, mb) - kMagic;
-        return qf * qp.delta_f - c;
+        if constexpr (RULE == RULE_MINMOVE) return minmove_clamp(c, qf * qp.delta_f, r) - c;
+        else return qf * qp.delta_f - c;
     }
 }
 
@@ -1129,13 +1199,13 @@ SVS_HD uint32_t pk_clamp_u8_i16(uint32_t a) {   // lane-wise clamp of signed 16-
 
 // the quantiser loops of the streaming bodies: coefficient row 0 (flat indices 1..7) and rows 0 and 1 (1..15) replaced by
 // their changes, 0 where nothing is embedded.  NEAREST as in qim_change; the budget is applied by the caller.
-template <int QM, bool NEAREST>
-SVS_HD void qim_changes_row0(float (&D)[8], uint32_t n, uint32_t hi, const QimParams &qp) {
+template <int QM, int RULE>
+SVS_HD void qim_changes_row0(float (&D)[8], uint32_t n, uint32_t hi, const QimRule &qp) {
 #pragma unroll
     for (int k = 1; k < 8; ++k) {
         float change = 0.0f;
         if ((uint32_t)k <= n)  // wave-uniform; the budget is applied below, for the one block it concerns
-            change = qim_change<QM, NEAREST>(D[k], (hi >> (32 - k)) & 1u, qp);
+            change = qim_change<QM, RULE>(D[k], (hi >> (32 - k)) & 1u, qp, qim_band<RULE>(qp, (uint32_t)k));
         D[k] = change;
     }
 }
@@ -1174,8 +1244,9 @@ SVS_HD uint32_t guard_decide_int(const uint32_t (&rx)[8], const uint32_t (&ry)[8
     float D[8];
     pf::dct2_8(V, D);   // row 0 of the coefficient matrix, bit-identical to scipy's
     SVS_SCHED_FENCE();
-    if (qp.nearest) qim_changes_row0<QM, true>(D, n, hi, qp);
-    else qim_changes_row0<QM, false>(D, n, hi, qp);
+    if (qp.kind == (uint32_t)RULE_MINMOVE) qim_changes_row0<QM, RULE_MINMOVE>(D, n, hi, qp);
+    else if (qp.kind == (uint32_t)RULE_NEAREST) qim_changes_row0<QM, RULE_NEAREST>(D, n, hi, qp);
+    else qim_changes_row0<QM, RULE_REFERENCE>(D, n, hi, qp);
     if (nb < n) {   // the block the payload ends in: coefficients past the budget stay as they are (config_and_setup.py:141)
 #pragma unroll
         for (int k = 1; k < 8; ++k)
@@ -1315,13 +1386,13 @@ SVS_HD void vertical_pf01_packed(const uint32_t (&w)[8], float (&v0)[4], float (
 // INPLACE: the stego bytes replace the pixels of rx / ry as they are computed (each column touches only its own byte of the
 // row dwords) and an UNDECIDED block is left half-written - for a caller that has parked the original rows elsewhere (the
 // two-row kernel parks them in LDS, where the exact replay wants them anyway: 16 registers and 16 moves less).
-template <int QM, bool NEAREST>
-SVS_HD void qim_changes_rows01(float (&D0)[8], float (&D1)[8], uint32_t n, uint32_t hi, uint32_t lo, const QimParams &qp) {
+template <int QM, int RULE>
+SVS_HD void qim_changes_rows01(float (&D0)[8], float (&D1)[8], uint32_t n, uint32_t hi, uint32_t lo, const QimRule &qp) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         float change = 0.0f;
         if (k >= 1 && (uint32_t)k <= n)  // wave-uniform; the budget is applied below, for the one block it concerns
-            change = qim_change<QM, NEAREST>(k < 8 ? D0[k] : D1[k - 8], window_bit(hi, lo, k - 1), qp);
+            change = qim_change<QM, RULE>(k < 8 ? D0[k] : D1[k - 8], window_bit(hi, lo, k - 1), qp, qim_band<RULE>(qp, (uint32_t)k));
         if (k < 8) D0[k] = change;
         else D1[k - 8] = change;
     }
@@ -1349,8 +1420,9 @@ SVS_HD bool embed_block_guarded2(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t 
     float D0[8], D1[8];
     pf::dct2_8(V0, D0);
     pf::dct2_8(V1, D1);
-    if (qp.nearest) qim_changes_rows01<QM, true>(D0, D1, n, hi, lo, qp);
-    else qim_changes_rows01<QM, false>(D0, D1, n, hi, lo, qp);
+    if (qp.kind == (uint32_t)RULE_MINMOVE) qim_changes_rows01<QM, RULE_MINMOVE>(D0, D1, n, hi, lo, qp);
+    else if (qp.kind == (uint32_t)RULE_NEAREST) qim_changes_rows01<QM, RULE_NEAREST>(D0, D1, n, hi, lo, qp);
+    else qim_changes_rows01<QM, RULE_REFERENCE>(D0, D1, n, hi, lo, qp);
     if (nb < n) {   // the block the payload ends in (see embed_block): coefficients past the budget stay as they are
 #pragma unroll
         for (int k = 1; k < 16; ++k) {
@@ -1428,9 +1500,9 @@ inline void make_guard(double delta, int rows, QimParams *qp) {
 // kernel (two blocks per lane) it measured SLOWER than the one-block form - a v_pk_*_f32 costs two issue slots on this chip,
 // and the 256-register footprint costs occupancy (profiles/history/r02_ab_exact_pair.txt).  The CPU tier still checks it
 // against embed_block_exact (tests/hostemu, exact == 2).
-template <int U, int QM, bool NEAREST>
+template <int U, int QM, int RULE>
 SVS_HD void qim_exact_pair(pf::f32x2 (&D)[8][8], uint32_t n, uint32_t nb_a, uint32_t nb_b, uint32_t hi_a, uint32_t lo_a, uint32_t hi_b,
-                           uint32_t lo_b, const QimParams &qp) {
+                           uint32_t lo_b, const QimRule &qp) {
 #pragma unroll
     for (int k = 1; k < 8 * U; ++k) {
         if ((uint32_t)k <= n) {  // wave-uniform
@@ -1439,7 +1511,7 @@ SVS_HD void qim_exact_pair(pf::f32x2 (&D)[8][8], uint32_t n, uint32_t nb_a, uint
             for (int which = 0; which < 2; ++which) {
                 const int bit = (int)window_bit(which ? hi_b : hi_a, which ? lo_b : lo_a, i);
                 const float c = D[k >> 3][k & 7][which];
-                const float cn = qim_target<QM, NEAREST>(c, bit, qp);
+                const float cn = qim_target<QM, RULE>(c, bit, qp, qim_band<RULE>(qp, (uint32_t)k));
                 D[k >> 3][k & 7][which] = ((uint32_t)i < (which ? nb_b : nb_a)) ? cn : c;
             }
         }
@@ -1474,8 +1546,9 @@ SVS_HD void embed_block_exact_pair(uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_
             SVS_SCHED_FENCE();
         }
     }
-    if (qp.nearest) qim_exact_pair<U, QM, true>(D, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
-    else qim_exact_pair<U, QM, false>(D, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
+    if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_pair<U, QM, RULE_MINMOVE>(D, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
+    else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_pair<U, QM, RULE_NEAREST>(D, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
+    else qim_exact_pair<U, QM, RULE_REFERENCE>(D, n, nb_a, nb_b, hi_a, lo_a, hi_b, lo_b, qp);
     f32x2 P[8][8];  // after the vertical inverse (axis 0 first, :168): P[y][v]
 #pragma unroll
     for (int v = 0; v < 8; ++v) {

@@ -62,6 +62,7 @@ svs::RouteArgs route_args(double delta, const svs::Geometry &g, uint64_t total, 
     if (const char *sc = getenv("SVS_TIE_SCALE")) a.tie_scale = (float)atof(sc);
 #endif
     a.nearest = (flags & SVS_NEAREST) != 0;
+    a.minmove = (flags & SVS_MINMOVE) != 0;
     return a;
 }
 
@@ -193,7 +194,7 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
     const svs::CoeffTable sel = p.selected && coeffs ? *coeffs : svs::CoeffTable{};   // count 0: the row-major prefix
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
-    g.pad = p.nearest ? 1u : 0u;
+    g.pad = svs::rule_word(p.nearest, p.minmove, p.half_cell);
     const uint32_t words = (uint32_t)p.n_words;
     return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
@@ -265,7 +266,7 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
     const svs::Geometry planes = g;
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
-    g.pad = p.nearest ? 1u : 0u;
+    g.pad = svs::rule_word(p.nearest, p.minmove, p.half_cell);
     const uint32_t words = (uint32_t)p.n_words;
     const bool exact = p.path == EmbedPath::EXACT || p.path == EmbedPath::ROUND_TRIP;
     if (int rc = dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
@@ -724,9 +725,9 @@ int check_coeffs(const svs_coeffs *c, svs::CoeffTable *table, const svs::CoeffTa
     return SVS_OK;
 }
 
-constexpr uint32_t kSelectEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_NEAREST;
+constexpr uint32_t kSelectEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_NEAREST | SVS_MINMOVE;
 
-constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_READBACK | SVS_NEAREST;
+constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_READBACK | SVS_NEAREST | SVS_MINMOVE;
 
 // svs_embed_dev, svs_embed_ordered_dev (order NULL: the call without an order) and svs_embed_readback_dev (d_counts: the
 // read-back counts, device, added to; NULL for none)
@@ -773,7 +774,7 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (int rc = check_order(order)) return rc;
-    if (flags & (SVS_READBACK | SVS_NEAREST)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK and SVS_NEAREST are embed flags");
+    if (flags & (SVS_READBACK | SVS_NEAREST | SVS_MINMOVE)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK, SVS_NEAREST and SVS_MINMOVE are embed flags");
     if (cap == 0) return SVS_OK;
     if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
@@ -983,7 +984,7 @@ static int extract_host(const uint8_t *gray, const svs_planes *planes, const svs
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
     if (int rc = check_order(order)) return rc;
-    if (flags & (SVS_READBACK | SVS_NEAREST)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK and SVS_NEAREST are embed flags");
+    if (flags & (SVS_READBACK | SVS_NEAREST | SVS_MINMOVE)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK, SVS_NEAREST and SVS_MINMOVE are embed flags");
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     const uint64_t bytes = (cap + 7) / 8;
@@ -1026,7 +1027,7 @@ int svs_embed_select_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_plan
     svs::CoeffTable table;
     const svs::CoeffTable *sel = nullptr;
     if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
-    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits and SVS_NEAREST", flags);
+    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE", flags);
     return embed_dev(d_gray, d_stego, planes, order, delta, coeffs->count, d_bits_packed, bit_offset, n_bits, flags, n_embedded,
                      stream, nullptr, sel);
 }
@@ -1037,7 +1038,7 @@ int svs_embed_select(const uint8_t *gray, uint8_t *stego, const svs_planes *plan
     svs::CoeffTable table;
     const svs::CoeffTable *sel = nullptr;
     if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
-    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits and SVS_NEAREST", flags);
+    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE", flags);
     return embed_host(gray, stego, nullptr, planes, delta, coeffs->count, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded,
                       order, nullptr, sel);
 }
@@ -1069,7 +1070,7 @@ int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta,
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
-    if (flags & (SVS_READBACK | SVS_NEAREST)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK and SVS_NEAREST are embed flags");
+    if (flags & (SVS_READBACK | SVS_NEAREST | SVS_MINMOVE)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK, SVS_NEAREST and SVS_MINMOVE are embed flags");
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_ascii_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if (int rc = check_capacity(cap, out_capacity_chars, "characters")) return rc;
@@ -1170,7 +1171,7 @@ static int colour_params(const svs_planes *p, const void *in, int64_t irp, int64
     return SVS_OK;
 }
 
-constexpr uint32_t kBgrEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR | SVS_NEAREST;
+constexpr uint32_t kBgrEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_KEEP_COLOUR | SVS_NEAREST | SVS_MINMOVE;
 
 // svs_embed_bgr_dev (allowed = kBgrEmbedFlags: SVS_READBACK is refused) and svs_embed_bgr_readback_dev (the flag accepted and
 // implied; d_counts: the read-back counts, device, added to; NULL for none)

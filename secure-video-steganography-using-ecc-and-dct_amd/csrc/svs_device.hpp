@@ -338,7 +338,8 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
                                                           const uint32_t n_words, const CoeffTable sel,
                                                           const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
-    // SVS_NEAREST: ONE wave-uniform branch around the whole body, the rule a compile-time constant on either side (QimRule).
+    // SVS_NEAREST, SVS_MINMOVE: ONE wave-uniform branch around the whole body, the rule a compile-time constant on every side
+    // (QimRule; under SVS_MINMOVE its half_cell is the launch's, the kind is the constant: rule_from_word with a word > 1).
     // A `return` inside the body leaves the body, and nothing follows the calls.
     // A coefficient selection (sel.count != 0; the U = 8 instantiations only - svs_route.hpp plans no other for one) is a
     // second such branch: `table` is a compile-time NULL on the side without one, which is the body as it was.
@@ -366,12 +367,14 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
     };
     if constexpr (U == 8) {
         if (sel.count) {   // Geometry::n_ac == sel.count: the stream ranges and the block budget are those of n_ac slots
-            if (g.pad) body(QimRule(qp, 1u), &sel);
+            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &sel);
+            else if (g.pad) body(QimRule(qp, 1u), &sel);
             else body(QimRule(qp, 0u), &sel);
             return;
         }
     }
-    if (g.pad) body(QimRule(qp, 1u), nullptr);
+    if (g.pad > 1u) body(rule_from_word(qp, g.pad), nullptr);
+    else if (g.pad) body(QimRule(qp, 1u), nullptr);
     else body(QimRule(qp, 0u), nullptr);
 }
 
@@ -399,8 +402,9 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
 #define SVS_GUARD_CAP 32    // worklist entries per wave and round (80 B each) of the one-row (rigorous guard) embed kernel
 
 // QIM on flat indices k = 8 u + r in 1..n (config_and_setup.py:139-158): one coefficient per lane and row, so a wave
-// runs n / 8 + 1 quantiser sequences, each on all the lanes that have a coefficient.  NEAREST: qim_target (svs_block.hpp)
-template <int QM, int UROWS, bool NEAREST>
+// runs n / 8 + 1 quantiser sequences, each on all the lanes that have a coefficient.  RULE: qim_target (svs_block.hpp); k is
+// the lane's own here, so the band of SVS_MINMOVE comes from a read of the margin table
+template <int QM, int UROWS, int RULE>
 __device__ __forceinline__ void qim_replay8(float (&a)[8], uint32_t hi, uint32_t lo, uint32_t nb, uint32_t r, uint32_t n,
                                             const QimRule &qp) {
 #pragma unroll
@@ -410,7 +414,7 @@ __device__ __forceinline__ void qim_replay8(float (&a)[8], uint32_t hi, uint32_t
             const int i = (int)k - 1;
             const int bit = (int)window_bit(hi, lo, i);
             const float c = a[u];
-            const float cn = qim_target<QM, NEAREST>(c, bit, qp);
+            const float cn = qim_target<QM, RULE>(c, bit, qp, qim_band<RULE>(qp, k));
             a[u] = ((uint32_t)i < nb) ? cn : c;
         }
     }
@@ -430,8 +434,9 @@ __device__ __forceinline__ void guard_replay8(uint32_t *px, uint32_t hi, uint32_
 #pragma unroll
     for (int u = 0; u < 8; ++u) a[u] = t[9 * u + r];
     wave_lds_fence();
-    if (qp.nearest) qim_replay8<QM, UROWS, true>(a, hi, lo, nb, r, n, qp);
-    else qim_replay8<QM, UROWS, false>(a, hi, lo, nb, r, n, qp);
+    if (qp.kind == (uint32_t)RULE_MINMOVE) qim_replay8<QM, UROWS, RULE_MINMOVE>(a, hi, lo, nb, r, n, qp);
+    else if (qp.kind == (uint32_t)RULE_NEAREST) qim_replay8<QM, UROWS, RULE_NEAREST>(a, hi, lo, nb, r, n, qp);
+    else qim_replay8<QM, UROWS, RULE_REFERENCE>(a, hi, lo, nb, r, n, qp);
     inverse8<9>(a, t, r, b);   // pixel row r
     uint32_t lo4, hi4;
     store_row_trunc(b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], lo4, hi4);   // np.uint8(np.clip(.)) (:171)
@@ -548,8 +553,8 @@ __global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint
     __shared__ u32x2 meta[PARKED ? SVS_WG / 64 : 1][PARKED ? 64 : 1];
     __shared__ GuardEntry entries[PARKED ? 1 : SVS_WG / 64][PARKED ? 1 : SVS_GUARD_CAP];
     __shared__ float tiles[SVS_WG / 64][8 * SVS_GUARD_TILE];
-    // SVS_NEAREST: ONE wave-uniform branch around the whole body, the rule a compile-time constant on either side (QimRule).
-    // A `return` inside the body leaves the body, and nothing follows the two calls.
+    // SVS_NEAREST, SVS_MINMOVE: ONE wave-uniform branch around the whole body, the rule a compile-time constant on every side
+    // (QimRule).  A `return` inside the body leaves the body, and nothing follows the calls.
     const auto body = [&](const QimRule qp) __attribute__((always_inline)) {
         const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
         // (Round 5 tried block-row aligned tiles - a workgroup reads and writes ONE contiguous stretch, eight full pixel rows, at
@@ -608,7 +613,8 @@ __global__ __launch_bounds__(SVS_WG) void embed_kernel(const uint8_t *gray, uint
             store_rows<1>(stego + off, g.row_pitch, v);
         }
     };
-    if (g.pad) body(QimRule(qp, 1u));
+    if (g.pad > 1u) body(rule_from_word(qp, g.pad));
+    else if (g.pad) body(QimRule(qp, 1u));
     else body(QimRule(qp, 0u));
 }
 
@@ -784,8 +790,8 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ Row1Entries entries;
     __shared__ Row1Tiles tiles;
-    // SVS_NEAREST: ONE wave-uniform branch around the whole body, the rule a compile-time constant on either side (QimRule).
-    // A `return` inside the body leaves the body, and nothing follows the two calls.
+    // SVS_NEAREST, SVS_MINMOVE: ONE wave-uniform branch around the whole body, the rule a compile-time constant on every side
+    // (QimRule).  A `return` inside the body leaves the body, and nothing follows the calls.
     const auto body = [&](const QimRule qp) __attribute__((always_inline)) {
         const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
         bool live;
@@ -813,7 +819,8 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
         (void)redone;
 #endif
     };
-    if (g.pad) body(QimRule(qp, 1u));
+    if (g.pad > 1u) body(rule_from_word(qp, g.pad));
+    else if (g.pad) body(QimRule(qp, 1u));
     else body(QimRule(qp, 0u));
 }
 
@@ -1620,9 +1627,13 @@ __global__ __launch_bounds__(SVS_WG) void embed_bgr_kernel(const uint8_t *bgr_in
     // tile of the exact replay (guard_phase2 with 16 entries per round), then the stego tile of the cooperative store
     __shared__ __attribute__((aligned(16))) u32x2 lds_tile[SVS_WG / 64][8][64];
     static_assert(16 * sizeof(GuardEntry) + 8 * SVS_GUARD_TILE * sizeof(float) <= 8 * 64 * sizeof(u32x2), "wave region too small");
-    // SVS_NEAREST: the rule stays a run-time value here and the bodies test it once per block.  (Two copies of the whole body,
-    // as in the gray kernels, take the allocation of the larger one: 124 -> 132 and 167 -> 169 VGPRs, a wave per SIMD less.)
-    const QimRule rule(qp_arg, g.pad);
+    // SVS_NEAREST, SVS_MINMOVE: the rule stays a run-time value here and the bodies test it once per block (two compares of a
+    // wave-uniform word).  Two copies of the whole body, as in the gray kernels, take the allocation of the larger one: 124 ->
+    // 132 and 167 -> 169 VGPRs, a wave per SIMD less.  The same holds for a single branch around the body with only the
+    // SVS_MINMOVE side a constant: the keep-colour forms go 124 -> 132 and 168 -> 169 VGPRs, 4 -> 3 and 3 -> 2 waves.  With the
+    // run-time rule no form loses a wave (the plain one-row form grows from 82 to 93 VGPRs, the limit of 5 waves is 96) and the
+    // flag-clear time is inside the spread of the build before the flag: profiles/minmove_resources.txt, minmove_rates.txt.
+    const QimRule rule = rule_from_word(qp_arg, g.pad);
     const QimRule &qp = rule;
     const uint32_t tile = tile_id(g.xcd_chunk);
     const uint32_t gblock = tile * (uint32_t)SVS_WG + threadIdx.x;

@@ -35,7 +35,7 @@ struct Geometry {
     uint32_t total_blocks;  // n_frames * blocks per frame   (< 2^31)
     uint32_t n_ac;          // 1..63
     uint32_t xcd_chunk;     // tile_id() chunk (0 = identity)
-    uint32_t pad;           // embed launches: 1 = SVS_NEAREST (the plan's `nearest`; the kernels' QimRule), else 0
+    uint32_t pad;           // embed launches: the rule (svs_block.hpp rule_word): 0, 1 = SVS_NEAREST, else SVS_MINMOVE and the bits of h
     int64_t row_pitch;
     int64_t frame_pitch;
 };

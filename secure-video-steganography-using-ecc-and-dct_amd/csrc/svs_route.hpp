@@ -25,6 +25,7 @@ struct RouteArgs {
     bool keyed = false;       // a keyed block order (svs_embed_ordered_dev / svs_extract_ordered_dev; gray calls only)
     bool readback = false;    // SVS_READBACK (the gray embed calls; svs_embed_bgr_readback*)
     bool nearest = false;     // SVS_NEAREST (every embed call)
+    bool minmove = false;     // SVS_MINMOVE (every embed call)
     // a coefficient selection (svs_embed_select* / svs_extract_select*; gray calls only): NULL for none, else its table with
     // count == n_ac.  The prefix 1..n_ac plans exactly as no selection does; any other one runs the lane-per-block exact
     // kernels in every mode - the streaming embed guard and the FAST extract margins (tools/guard_bound.py) are derived for
@@ -53,6 +54,8 @@ struct EmbedPlan {
     bool keyed;               // the KEYED instantiation of the family (STREAMING / EXACT only: the other paths do not depend on order)
     bool readback;            // SVS_READBACK: readback_kernel follows the embed (only when payload bits are embedded)
     bool nearest;             // SVS_NEAREST: Geometry::pad of the embed launch (the kernels' QimRule)
+    bool minmove;             // SVS_MINMOVE: likewise (rule_word(nearest, minmove, half_cell)); implies the nearest direction
+    float half_cell;          // SVS_MINMOVE: h = (float)(0.5 * (double)delta), rounded here once for host and device
     uint32_t n_ac;            // Geometry::n_ac of the launch
     uint32_t xcd_chunk;
     QimParams qp;
@@ -90,6 +93,8 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.keyed = a.keyed;
         p.readback = a.readback;
         p.nearest = a.nearest;                // STREAMING and EXACT only: the other paths have no coefficient to force
+        p.minmove = a.minmove;                // likewise
+        p.half_cell = a.minmove ? (float)(0.5 * a.delta) : 0.0f;
         p.selected = selected;                // likewise: the other paths touch no coefficient
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);

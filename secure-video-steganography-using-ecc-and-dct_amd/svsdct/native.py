@@ -23,6 +23,7 @@ SVS_EXACT_GUARDED = 2        # flags bit: the same bit-identical result through 
 SVS_KEEP_COLOUR = 0x100      # flags bit, fused colour embed only: stego pixels keep the cover's colour (include/svsdct.h)
 SVS_READBACK = 0x200         # flags bit, gray embed only: read every payload block back, repair the ones that fail (include/svsdct.h)
 SVS_NEAREST = 0x800          # flags bit, every embed call: a wrong parity moves to the nearer lattice point (include/svsdct.h)
+SVS_MINMOVE = 0x1000         # flags bit, every embed call: a coefficient moves only as far as its decision cell asks (include/svsdct.h)
 ABI_VERSION = 4
 
 

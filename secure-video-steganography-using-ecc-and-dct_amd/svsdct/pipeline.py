@@ -50,11 +50,12 @@ def _device(nbytes: int):
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
-                 nearest: bool = False, coeffs=None):
+                 nearest: bool = False, coeffs=None, minmove: bool = False):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
-        towards the nearer lattice point (SVS_NEAREST, include/svsdct.h).  coeffs: None or a payload coefficient selection
+        towards the nearer lattice point (SVS_NEAREST, include/svsdct.h).  minmove: every embed batch moves a payload coefficient
+        only as far as its decision cell asks (SVS_MINMOVE, include/svsdct.h).  coeffs: None or a payload coefficient selection
         for every batch, as batch.embed_frames (resolved once with n_ac; ValueError with readback)."""
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
@@ -86,6 +87,7 @@ class FramePipeline:
         self._payload_bits = 0
         self.readback = bool(readback)
         self.nearest = bool(nearest)
+        self.minmove = bool(minmove)
         self._d_counts = None
         if self.readback:   # {repaired, unrepaired} of every batch, added to on the device
             self._d_counts = _device(16)
@@ -130,7 +132,7 @@ class FramePipeline:
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
                                   stream=s["stream"].value, mode=self.mode, order=self._order(first_frame),
                                   readback=self.readback, d_counts=self._d_counts.value if self._d_counts else 0,
-                                  nearest=self.nearest, coeffs=self.coeffs)
+                                  nearest=self.nearest, coeffs=self.coeffs, minmove=self.minmove)
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
         return used
