@@ -388,6 +388,82 @@ int svs_extract_select(const uint8_t *gray, const svs_planes *planes, const svs_
                        double delta, uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
                        uint64_t *n_bits_out);
 
+/* ---- the operator with a keyed dither (dither modulation, DM-QIM) ---------------------------------------
+ * Opt-in.  Every embed rule (the reference's, SVS_NEAREST, SVS_MINMOVE) quantises onto the lattice q * delta anchored at 0, so
+ * a stego frame announces itself - its recomputed payload coefficients sit within 0.5 S_u S_v <= 4.0 of a multiple of delta,
+ * a comb in the histogram of c mod delta that anyone can test for - and anyone who knows delta and n_ac (the application's
+ * defaults are public) reads the bits.  With a dither both sides shift the lattice of every payload coefficient by a
+ * key-derived offset d in [-delta, delta).  QIM distortion is shift invariant, so it costs no distortion; the transform, the
+ * inverse, the budget, the block order and the embedding rule do not change.
+ * The rule is a FORMAT: sender and receiver must compute the same thing.  For clip frame t = first_frame + f, raster block
+ * index i inside the frame (the block's physical position, not its stream slot: the rule does not depend on a keyed order)
+ * and flat row-major coefficient index k in 1..63, with lb = lowbias32 (csrc/svs_order.hpp) and all integer
+ * arithmetic mod 2^32:
+ *     seed = lb(lb(hi32(key) ^ 0x85EBCA6B) ^ lo32(key))      (not the block order's seed: one key may serve both)
+ *     s_t  = lb(seed ^ t)
+ *     s_b  = lb(s_t + i * 0x9E3779B1)
+ *     h    = lb(s_b ^ (k * 0x632BE5AB))
+ *     r    = (float)(h >> 8) * 2^-23 - 1.0f                  (exact in float32, in [-1, 1))
+ *     d    = r * (float)delta                                (one float32 multiply)
+ * The dither covers a whole parity period [-delta, delta), not [-delta/2, delta/2): with the half range a receiver with the
+ * wrong key still reads 75 % of the bits (the difference of two dithers is triangular on (-delta, delta), P(|x| > delta/2) =
+ * 1/4); with the full period the wrong-key bit error rate is 1/2.
+ *   embed, payload coefficient c, bit b:  c' = c - d (one float32 subtract);  cn' = what the call's rule writes for (c', b)
+ *            (reference, SVS_NEAREST or SVS_MINMOVE; the minimum-move band is that of flat index k);  the written value is c
+ *            itself when cn' equals c' bitwise, else cn' + d (one float32 add) - a coefficient that the minimum-move rule
+ *            leaves alone keeps its forward-transform value exactly.
+ *   extract: bit = quant_index(c - d) & 1, with the same subtract.
+ * Everything else is the reference's: stream ranges and the block budget, the block the budget ends in, byte-identical blocks
+ * past the budget, the delta <= 0, n_ac = 0 and empty-payload routes (the bytes of the call without a dither), the
+ * pocketfft inverse of all 64 coefficients, clip and truncate.  Every float step is a single IEEE float32 operation with no
+ * contraction, in the same order on the host build of the block bodies and on the device.
+ * lowbias32 is NOT a cryptographic generator (as csrc/svs_order.hpp says of the block order).  The dither removes the keyless
+ * test and the keyless read; the payload's confidentiality remains AES-GCM's.
+ * Measured on the CPU model (tests/test_dither_cpu.py: one 240 x 320 frame of noise in [64, 192), delta = 20, n_ac = 10, full
+ * payload, reference rule): the share of recomputed payload coefficients within delta/4 of a multiple of delta is 1.000
+ * without a dither and 0.502 with one; bit errors 0 with the right key, a bit error rate of 0.498 with another key and 0.506
+ * for the extract without a dither; PSNR against the cover 32.42 / 34.85 / 39.64 dB without a dither and 32.47 / 34.89 / 39.70
+ * with one (reference / SVS_NEAREST / SVS_MINMOVE).
+ * Cost: a dithered call always runs the lane-per-block SVS_EXACT_POCKETFFT kernels with all eight coefficient rows, whatever
+ * the mode bits say (the streaming embed guard and the FAST extract tie margins are derived for an undithered quantiser
+ * input), behind one wave-uniform branch in their eight-row instantiations; on top of that come one integer hash and two float
+ * operations per payload coefficient.  tools/dither_rates.py times it against the SVS_EXACT_POCKETFFT call at the same n_ac
+ * and against the selected call, at 200 x 4K (n_ac = 3, 10, 63).
+ * There is no read-back, no colour and no _str form.
+ *   order  : NULL or a keyed block order, as in the ordered calls.
+ *   coeffs : NULL (the row-major prefix 1..n_ac) or a coefficient selection, checked as in the select calls; n_ac is then
+ *            ignored and the selection's count rules.  The dither of a coefficient is that of its flat index k, whatever slot
+ *            it carries.
+ *   dither : required.  NULL or reserved != 0: SVS_ERR_INVALID_ARG before any device work.  When order is given too, the two
+ *            first_frame values must be equal (else SVS_ERR_INVALID_ARG): a caller cannot desynchronise them silently.
+ *   flags  : the mode bits are accepted and change nothing; SVS_NEAREST and SVS_MINMOVE on embed (rejected on extract, as
+ *            elsewhere); SVS_READBACK, SVS_KEEP_COLOUR, 0x400 and anything else: SVS_ERR_INVALID_ARG.
+ * The host-pointer forms go through the per-thread staging context and stage whole frames, as the keyed calls do, so that a
+ * chunk boundary never changes a block's (t, i).  Every other argument and contract is that of the ordered calls. */
+typedef struct svs_dither {
+    uint64_t key;           /* every value valid, 0 included */
+    uint32_t first_frame;   /* clip index of the call's first frame: frame f uses t = first_frame + f */
+    uint32_t reserved;      /* must be 0 */
+} svs_dither;
+
+int svs_embed_dithered_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                           const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
+                           const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                           uint64_t *n_embedded, void *stream);
+
+int svs_extract_dithered_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order,
+                             const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
+                             uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
+                             void *stream);
+
+int svs_embed_dithered(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                       const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac, const uint8_t *bits_packed,
+                       uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded);
+
+int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                         const svs_dither *dither, double delta, int n_ac, uint8_t *bits_packed_out, uint64_t out_capacity_bytes,
+                         uint32_t flags, uint64_t *n_bits_out);
+
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:
  *   d_counts : NULL, or a device buffer of two uint64 (8-byte aligned) that the call ADDS {blocks repaired, blocks left

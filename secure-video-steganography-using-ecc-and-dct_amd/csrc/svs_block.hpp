@@ -25,6 +25,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "svs_order.hpp"   // lowbias32 (the keyed dither)
+
 #if defined(__HIPCC__)
 #define SVS_HD __host__ __device__ __forceinline__
 #else
@@ -492,6 +494,52 @@ SVS_HD float qim_target(float c, int bit, const QimParams &qp, float r = 0.0f) {
     else return ct;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Keyed dither modulation (svs_embed_dithered* / svs_extract_dithered*, include/svsdct.h): both sides shift the lattice of
+// every payload coefficient by a key-derived offset d in [-delta, delta), a whole parity period.  A format: sender and receiver
+// must compute the same d, so nothing here may change.  For clip frame t = first_frame + f, raster block i of the frame (its
+// physical position, whatever its stream slot) and flat row-major coefficient k, all integer arithmetic mod 2^32:
+//   seed = lb(lb(hi32(key) ^ 0x85EBCA6B) ^ lo32(key))     (dither_seed; not the block order's seed: one key may serve both)
+//   s_t = lb(seed ^ t);  s_b = lb(s_t + i * 0x9E3779B1)   (dither_block_seed)
+//   h = lb(s_b ^ (k * 0x632BE5AB));  r = (float)(h >> 8) * 2^-23 - 1  (exact, in [-1, 1));  d = r * (float)delta
+// NOT a cryptographic generator (lb = lowbias32, as svs_order.hpp says of the order): it removes the keyless comb test and the
+// keyless read of the bits; confidentiality remains AES-GCM's.  Every float step is one IEEE float32 operation (build with
+// -ffp-contract=off), the same on host and device.
+// ---------------------------------------------------------------------------------------------------------------------
+
+SVS_HD uint32_t dither_seed(uint64_t key) {
+    return lowbias32(lowbias32((uint32_t)(key >> 32) ^ 0x85EBCA6Bu) ^ (uint32_t)key);
+}
+
+// s_b of raster block i of clip frame t
+SVS_HD uint32_t dither_block_seed(uint32_t seed, uint32_t t, uint32_t i) {
+    return lowbias32(lowbias32(seed ^ t) + i * 0x9E3779B1u);
+}
+
+// d of coefficient k (a compile-time index in the lane-per-block loops: k * 0x632BE5AB is then a literal)
+SVS_HD float dither_value(uint32_t s_b, uint32_t k, float delta_f) {
+    const uint32_t h = lowbias32(s_b ^ (k * 0x632BE5ABu));
+    const float r = (float)(h >> 8) * 0x1p-23f - 1.0f;   // 24 bits: the conversion, the power-of-two product and the sum are exact
+    return r * delta_f;
+}
+
+// One payload coefficient through the dithered quantiser: today's rule on c' = c - d, moved back by d.  A coefficient the
+// rule leaves alone (SVS_MINMOVE inside its band: cn' is c' bit for bit) keeps its forward-transform value exactly, not
+// (c - d) + d.  The minimum-move band is that of flat index k.
+template <int QM, int RULE>
+SVS_HD float dithered_target(float c, int bit, const QimRule &qp, uint32_t k, uint32_t s_b) {
+    const float d = dither_value(s_b, k, qp.delta_f);
+    const float cp = c - d;
+    const float cn = qim_target<QM, RULE>(cp, bit, qp, qim_band<RULE>(qp, k));
+    return __builtin_bit_cast(uint32_t, cn) == __builtin_bit_cast(uint32_t, cp) ? c : cn + d;
+}
+
+// the receiver's side: the parity of the index of c - d
+template <int QM>
+SVS_HD uint32_t dithered_parity(float c, const QimParams &qp, uint32_t k, uint32_t s_b) {
+    return (uint32_t)quant_index<QM>(c - dither_value(s_b, k, qp.delta_f), qp) & 1u;
+}
+
 // 64 stream bits starting at stream bit s of an MSB-first packed buffer viewed as dwords
 // (touches at most dwords s/32 .. s/32+2, each only if below n_words)
 SVS_HD void payload_window(const uint32_t *bits, uint32_t n_words, uint64_t s, uint32_t &hi, uint32_t &lo) {
@@ -532,6 +580,14 @@ struct CoeffTable {
     SVS_HD uint32_t slot(int k) const { return (w[k >> 2] >> (8 * (k & 3))) & 0xFFu; }
 };
 
+struct DitherArgs {          // by-value argument of the two exact kernels (read by their U = 8 instantiations only)
+    uint32_t seed;           // dither_seed(key)
+    uint32_t first_frame;    // frame f of the call is clip frame first_frame + f
+    uint32_t on;             // 0: no dither - the kernel's side that was there before the dither
+    CoeffTable sel;          // on: the call's selection, or the prefix table of n_ac (make_prefix_table) - never empty.  The
+                             // dithered side's own copy: read from the kernel's `sel` as well, that table went to scratch.
+};
+
 // host side: the table of `count` indices; false unless they are distinct and in 1..63 (count <= 63)
 inline bool make_coeff_table(const uint8_t *index, uint32_t count, CoeffTable *t) {
     for (int i = 0; i < 16; ++i) t->w[i] = 0xFFFFFFFFu;
@@ -544,6 +600,15 @@ inline bool make_coeff_table(const uint8_t *index, uint32_t count, CoeffTable *t
     }
     t->count = count;
     return true;
+}
+
+// the table of the selection 1, 2, .., n (n <= 63): the dithered calls without a selection run the selected loops with it
+inline CoeffTable make_prefix_table(uint32_t n) {
+    uint8_t index[63];
+    for (uint32_t i = 0; i < 63; ++i) index[i] = (uint8_t)(i + 1);
+    CoeffTable t;
+    make_coeff_table(index, n < 63u ? n : 63u, &t);
+    return t;
 }
 
 // the selection 1, 2, .., count: what a call without a selection does at n_ac = count
@@ -982,16 +1047,40 @@ SVS_HD void qim_exact_selected(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, uin
     }
 }
 
+// The dithered calls: the same loop with dithered_target and the block's s_b instead of qim_target - the hash and two more float
+// operations, for the coefficients behind the wave-uniform slot test only.  A dithered call without a selection brings the
+// prefix table (make_prefix_table), so this one loop serves both.  Written as a recursion over K: 63 copies of this larger body
+// are more than the compiler unrolls on a pragma, and a loop left rolled indexes the table and the coefficients at run time
+// (the table went to 72 bytes of scratch).
+template <int QM, int RULE, int K = 1>
+SVS_HD void qim_exact_selected_dithered(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, uint32_t nb, uint32_t hi, uint32_t lo,
+                                        const QimRule &qp, uint32_t s_b) {
+    const uint32_t s = sel.slot(K);
+    if (s < sel.count) {  // wave-uniform
+        const float c = D2[K >> 4][K & 7][(K >> 3) & 1];
+        const float cn = dithered_target<QM, RULE>(c, (int)window_bit_at(hi, lo, s), qp, (uint32_t)K, s_b);
+        D2[K >> 4][K & 7][(K >> 3) & 1] = (s < nb) ? cn : c;
+    }
+    if constexpr (K < 63) qim_exact_selected_dithered<QM, RULE, K + 1>(D2, sel, nb, hi, lo, qp, s_b);
+}
+
 // `sel`: NULL (the row-major prefix 1..n) or a selection; then n is not read, nb counts slots of the selection.  The callers
 // pass a compile-time NULL or the address of a by-value kernel argument, so the test folds on either side.
-template <int U, int QM>
+// DITH (the dithered calls; U = 8, and `sel` is never NULL: the call's selection or the prefix table of n): the selected loop
+// with the block's s_b (dither_block_seed); everything around it is the same.
+template <int U, int QM, bool DITH = false>
 SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo,
-                              const QimRule &qp, bool constant_block = false, const CoeffTable *sel = nullptr) {
+                              const QimRule &qp, bool constant_block = false, const CoeffTable *sel = nullptr, uint32_t s_b = 0u) {
     using pf::f32x2;
+    static_assert(!DITH || U == 8, "a dithered call covers all eight coefficient rows");
     f32x2 D2[4][8];
     if (constant_block) forward_exact_paired_constant(ubyte_to_float<0>(rx[0]), D2);
     else forward_exact_paired(rx, ry, D2);
-    if (sel) {
+    if constexpr (DITH) {
+        if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_selected_dithered<QM, RULE_MINMOVE>(D2, *sel, nb, hi, lo, qp, s_b);
+        else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_selected_dithered<QM, RULE_NEAREST>(D2, *sel, nb, hi, lo, qp, s_b);
+        else qim_exact_selected_dithered<QM, RULE_REFERENCE>(D2, *sel, nb, hi, lo, qp, s_b);
+    } else if (sel) {
         if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_selected<QM, RULE_MINMOVE>(D2, *sel, nb, hi, lo, qp);
         else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_selected<QM, RULE_NEAREST>(D2, *sel, nb, hi, lo, qp);
         else qim_exact_selected<QM, RULE_REFERENCE>(D2, *sel, nb, hi, lo, qp);
@@ -1572,9 +1661,11 @@ SVS_HD void embed_block_exact_pair(uint32_t (&ax)[8], uint32_t (&ay)[8], uint32_
 }
 
 // EXACT extract: parity bits of round(c_k/delta) with pocketfft-identical coefficients
-template <int U, int QM>
+// DITH (the dithered calls; U = 8 only): the parity of the index of c - d, d from the block's s_b
+template <int U, int QM, bool DITH = false>
 SVS_HD void extract_block_exact(const uint32_t (&rx)[8], const uint32_t (&ry)[8], uint32_t n, const QimParams &qp,
-                                uint32_t &hi, uint32_t &lo) {
+                                uint32_t &hi, uint32_t &lo, uint32_t s_b = 0u) {
+    static_assert(!DITH || U == 8, "a dithered call covers all eight coefficient rows");
     float D[8][8];
     forward_exact(rx, ry, D);
     hi = 0;
@@ -1582,7 +1673,9 @@ SVS_HD void extract_block_exact(const uint32_t (&rx)[8], const uint32_t (&ry)[8]
 #pragma unroll
     for (int k = 1; k < 8 * U; ++k) {
         if ((uint32_t)k <= n) {  // wave-uniform
-            const uint32_t bit = (uint32_t)quant_index<QM>(D[k >> 3][k & 7], qp) & 1u;
+            uint32_t bit;
+            if constexpr (DITH) bit = dithered_parity<QM>(D[k >> 3][k & 7], qp, (uint32_t)k, s_b);
+            else bit = (uint32_t)quant_index<QM>(D[k >> 3][k & 7], qp) & 1u;
             const int i = k - 1;
             if (i < 32) hi |= bit << ((31 - i) & 31);
             else lo |= bit << ((63 - i) & 31);
@@ -1592,9 +1685,9 @@ SVS_HD void extract_block_exact(const uint32_t (&rx)[8], const uint32_t (&ry)[8]
 
 // EXACT extract with a coefficient selection: the parity of coefficient k lands at window position sel.slot(k) (instead of
 // k - 1); the caller packs sel.count bits per block as always
-template <int QM>
+template <int QM, bool DITH = false>
 SVS_HD void extract_block_exact_selected(const uint32_t (&rx)[8], const uint32_t (&ry)[8], const CoeffTable &sel,
-                                         const QimParams &qp, uint32_t &hi, uint32_t &lo) {
+                                         const QimParams &qp, uint32_t &hi, uint32_t &lo, uint32_t s_b = 0u) {
     float D[8][8];
     forward_exact(rx, ry, D);
     hi = 0;
@@ -1603,7 +1696,10 @@ SVS_HD void extract_block_exact_selected(const uint32_t (&rx)[8], const uint32_t
     for (int k = 1; k < 64; ++k) {
         const uint32_t s = sel.slot(k);
         if (s < sel.count) {  // wave-uniform
-            const uint32_t bit = ((uint32_t)quant_index<QM>(D[k >> 3][k & 7], qp) & 1u) << ((31u - s) & 31u);
+            uint32_t parity;
+            if constexpr (DITH) parity = dithered_parity<QM>(D[k >> 3][k & 7], qp, (uint32_t)k, s_b);
+            else parity = (uint32_t)quant_index<QM>(D[k >> 3][k & 7], qp) & 1u;
+            const uint32_t bit = parity << ((31u - s) & 31u);
             if (s < 32u) hi |= bit;
             else lo |= bit;
         }

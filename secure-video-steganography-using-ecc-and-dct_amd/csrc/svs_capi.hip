@@ -190,8 +190,12 @@ using svs::ExtractPath;
 // KEYED instantiation of the same kernel family, with the order as the last argument.
 int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
                  svs::Geometry g, const uint32_t *bits, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{},
-                 const svs::CoeffTable *coeffs = nullptr) {
+                 const svs::CoeffTable *coeffs = nullptr, const svs::DitherArgs &dith = svs::DitherArgs{}) {
     const svs::CoeffTable sel = p.selected && coeffs ? *coeffs : svs::CoeffTable{};   // count 0: the row-major prefix
+    // on only where the plan says so (EXACT, rows = 8); the dithered side runs the selected loop alone, with the prefix table of
+    // n_ac where the call has no selection
+    const svs::DitherArgs dth{dith.seed, dith.first_frame, p.dithered ? 1u : 0u,
+                              !p.dithered ? svs::CoeffTable{} : sel.count ? sel : svs::make_prefix_table((uint32_t)p.n_ac)};
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
     g.pad = svs::rule_word(p.nearest, p.minmove, p.half_cell);
@@ -205,9 +209,9 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
                 constexpr int U = decltype(u)::value;
                 if (p.keyed)
                     return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g,
-                                  p.qp, bits, p.bit_offset, p.n_bits, words, sel, ord);
+                                  p.qp, bits, p.bit_offset, p.n_bits, words, sel, dth, ord);
                 return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words, sel);
+                              p.bit_offset, p.n_bits, words, sel, dth);
             });
         if (p.rows == 2) {   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
             if (p.keyed)
@@ -293,8 +297,11 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
 // svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>.  A keyed plan ORs every block's bits into its
 // slot with global atomics (svs_device.hpp, or_bits_global): the output is cleared first, on the same stream.
 int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
-                   uint64_t out_bytes, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}, const svs::CoeffTable *coeffs = nullptr) {
+                   uint64_t out_bytes, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}, const svs::CoeffTable *coeffs = nullptr,
+                   const svs::DitherArgs &dith = svs::DitherArgs{}) {
     const svs::CoeffTable sel = p.selected && coeffs ? *coeffs : svs::CoeffTable{};   // count 0: the row-major prefix
+    // on only where the plan says so (EXACT, rows = 8); the extract kernel reads the selection from `sel` on either side
+    const svs::DitherArgs dth{dith.seed, dith.first_frame, p.dithered ? 1u : 0u, svs::CoeffTable{}};
     if (p.path == ExtractPath::ZEROS || p.keyed) SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
     if (p.path == ExtractPath::ZEROS) return SVS_OK;
     g.xcd_chunk = p.xcd_chunk;
@@ -305,8 +312,8 @@ int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, co
                 constexpr int U = decltype(r)::value;
                 if (p.keyed)
                     return launch(svs::extract_exact_kernel<U, QM, 1, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, g, p.qp,
-                                  out, out_bytes, sel, ord);
-                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes, sel);
+                                  out, out_bytes, sel, dth, ord);
+                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes, sel, dth);
             });
         if (p.keyed)
             return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
@@ -712,6 +719,21 @@ svs::BlockOrderArgs order_args(const svs_block_order *order, const svs::Geometry
     return order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{};
 }
 
+// the dither argument of the dithered entry points: required; its first_frame must be the order's when both are given (a
+// caller must not desynchronise them silently)
+int check_dither(const svs_dither *dither, const svs_block_order *order) {
+    if (!dither) return fail(SVS_ERR_INVALID_ARG, "dither is NULL");
+    if (dither->reserved != 0) return fail(SVS_ERR_INVALID_ARG, "svs_dither.reserved must be 0");
+    if (order && order->first_frame != dither->first_frame)
+        return fail(SVS_ERR_INVALID_ARG, "svs_dither.first_frame %u differs from svs_block_order.first_frame %u",
+                    (unsigned)dither->first_frame, (unsigned)order->first_frame);
+    return SVS_OK;
+}
+
+svs::DitherArgs dither_args(const svs_dither *dither) {
+    return dither ? svs::DitherArgs{svs::dither_seed(dither->key), dither->first_frame, 1u, svs::CoeffTable{}} : svs::DitherArgs{};
+}
+
 // The selection of the select entry points -> the kernels' table.  *coeffs = NULL when the selection is the prefix 1..count:
 // the call is then the one without a selection at n_ac = count, streaming kernels included.
 int check_coeffs(const svs_coeffs *c, svs::CoeffTable *table, const svs::CoeffTable **coeffs) {
@@ -733,7 +755,8 @@ constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | S
 // read-back counts, device, added to; NULL for none)
 int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order, double delta,
               int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-              uint64_t *n_embedded, void *stream, uint64_t *d_counts = nullptr, const svs::CoeffTable *coeffs = nullptr) {
+              uint64_t *n_embedded, void *stream, uint64_t *d_counts = nullptr, const svs::CoeffTable *coeffs = nullptr,
+              const svs_dither *dither = nullptr) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
@@ -747,6 +770,7 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
     ra.keyed = order != nullptr;
     ra.readback = (flags & SVS_READBACK) != 0;
     ra.coeffs = coeffs;   // the select calls: n_ac == coeffs->count
+    ra.dithered = dither != nullptr;
     const svs::EmbedPlan p = svs::plan_embed(ra);
     if (p.use > 0) {
         if (!d_bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
@@ -759,7 +783,9 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
     if (p.path == EmbedPath::COPY && d_gray == d_stego) return SVS_OK;
     const bool two = p.two_blocks && rows_allow_two_blocks(planes, d_gray, d_stego);
     const uint32_t *bits = p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr;
-    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g, bits, order_args(order, g), coeffs)) return rc;
+    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g, bits, order_args(order, g), coeffs,
+                              dither_args(dither)))
+        return rc;
     if (p.readback && p.use > 0)
         if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, d_counts, order_args(order, g))) return rc;
     if (n_embedded) *n_embedded = p.use;
@@ -769,7 +795,7 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
 // svs_extract_dev and svs_extract_ordered_dev
 int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
                 uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream,
-                const svs::CoeffTable *coeffs = nullptr) {
+                const svs::CoeffTable *coeffs = nullptr, const svs_dither *dither = nullptr) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
@@ -784,11 +810,13 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block
     svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
     ra.keyed = order != nullptr;
     ra.coeffs = coeffs;   // the select calls: n_ac == coeffs->count
+    ra.dithered = dither != nullptr;
     const svs::ExtractPlan p = svs::plan_extract(ra);
     // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
     if (p.path != ExtractPath::ZEROS && (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)))
         return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, order_args(order, g), coeffs))
+    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, order_args(order, g), coeffs,
+                                dither_args(dither)))
         return rc;
     if (n_bits_out) *n_bits_out = cap;
     return SVS_OK;
@@ -846,7 +874,7 @@ static void copy_gray_reference(uint8_t *dst, const uint8_t *gray, const svs_pla
 static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out, const svs_planes *planes, double delta, int n_ac,
                       const uint8_t *bits_packed, const char *bits_ascii, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                       uint64_t *n_embedded, const svs_block_order *order = nullptr, svs_readback_counts *counts = nullptr,
-                      const svs::CoeffTable *coeffs = nullptr) {
+                      const svs::CoeffTable *coeffs = nullptr, const svs_dither *dither = nullptr) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
@@ -887,8 +915,10 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                 [&](const svs_planes &sub, int64_t off, int32_t f0, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
                     // keyed: whole frames - the chunk's first frame is clip frame order->first_frame + f0
                     const svs_block_order o{order ? order->key : 0u, order ? order->first_frame + (uint32_t)f0 : 0u, 0u};
+                    // dithered: whole frames too, so that a chunk boundary never changes a block's (t, i)
+                    const svs_dither di{dither ? dither->key : 0u, dither ? dither->first_frame + (uint32_t)f0 : 0u, 0u};
                     return embed_dev(d + off, d + off, &sub, order ? &o : nullptr, delta, n_ac, static_cast<const uint8_t *>(c.bits.p),
-                                     chunk_offset, budget, flags, done, up, d_counts, coeffs);
+                                     chunk_offset, budget, flags, done, up, d_counts, coeffs, dither ? &di : nullptr);
                 },
                 [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {
                     // back: pixel bytes only (padding in the caller's stego buffer is left alone)
@@ -905,7 +935,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                     }
                     return (int)SVS_OK;
                 },
-                &done_total, order != nullptr);
+                &done_total, order != nullptr || dither != nullptr);
             if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, 16, hipMemcpyDeviceToHost, c.st[0]));
             // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
             // thread would only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first.)
@@ -979,7 +1009,7 @@ int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int
 // svs_extract_ordered (order NULL: svs_extract) and svs_extract_select
 static int extract_host(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
                         uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
-                        const svs::CoeffTable *coeffs = nullptr) {
+                        const svs::CoeffTable *coeffs = nullptr, const svs_dither *dither = nullptr) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
@@ -992,7 +1022,7 @@ static int extract_host(const uint8_t *gray, const svs_planes *planes, const svs
     return extract_staged(
         gray, span_bytes(planes), bytes, 0, n_bits_out,
         [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
-            return extract_dev(d_in, planes, order, delta, n_ac, d_bits, d_bytes, flags, got, st, coeffs);
+            return extract_dev(d_in, planes, order, delta, n_ac, d_bits, d_bytes, flags, got, st, coeffs, dither);
         },
         [&](HostStage &c, hipStream_t st) { return stage_d2h(st, bits_packed_out, c.bits.p, bytes); });
 }
@@ -1063,6 +1093,69 @@ int svs_extract_select(const uint8_t *gray, const svs_planes *planes, const svs_
     if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED))
         return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select extract takes the mode bits only", flags);
     return extract_host(gray, planes, order, delta, coeffs->count, bits_packed_out, out_capacity_bytes, flags, n_bits_out, sel);
+}
+
+// ---- keyed dither modulation ----------------------------------------------------------------------------------------
+// The dithered calls are the ordered calls (with a selection: the select calls) with the dither handed down to the plan.  The
+// dither, the selection and the flags are checked before anything else.  coeffs NULL: the row-major prefix 1..n_ac; else n_ac
+// is ignored and the selection's count rules (*sel = NULL for a prefix selection: the call without one at n_ac = count).
+static int dithered_args(const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither, uint32_t flags,
+                         uint32_t allowed, const char *what, svs::CoeffTable *table, const svs::CoeffTable **sel, int *n_ac) {
+    if (int rc = check_dither(dither, order)) return rc;
+    *sel = nullptr;
+    if (coeffs) {
+        if (int rc = check_coeffs(coeffs, table, sel)) return rc;
+        *n_ac = coeffs->count;
+    }
+    if (flags & ~allowed) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: %s", flags, what);
+    return SVS_OK;
+}
+static const char kDitheredEmbedFlags[] = "a dithered embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE";
+static const char kDitheredExtractFlags[] = "a dithered extract takes the mode bits only";
+
+int svs_embed_dithered_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                           const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
+                           const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                           uint64_t *n_embedded, void *stream) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = dithered_args(order, coeffs, dither, flags, kSelectEmbedFlags, kDitheredEmbedFlags, &table, &sel, &n_ac)) return rc;
+    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream,
+                     nullptr, sel, dither);
+}
+
+int svs_embed_dithered(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                       const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac, const uint8_t *bits_packed,
+                       uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = dithered_args(order, coeffs, dither, flags, kSelectEmbedFlags, kDitheredEmbedFlags, &table, &sel, &n_ac)) return rc;
+    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded, order,
+                      nullptr, sel, dither);
+}
+
+int svs_extract_dithered_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order,
+                             const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
+                             uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
+                             void *stream) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = dithered_args(order, coeffs, dither, flags, SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED, kDitheredExtractFlags, &table,
+                               &sel, &n_ac))
+        return rc;
+    return extract_dev(d_gray, planes, order, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, sel,
+                       dither);
+}
+
+int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                         const svs_dither *dither, double delta, int n_ac, uint8_t *bits_packed_out, uint64_t out_capacity_bytes,
+                         uint32_t flags, uint64_t *n_bits_out) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = dithered_args(order, coeffs, dither, flags, SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED, kDitheredExtractFlags, &table,
+                               &sel, &n_ac))
+        return rc;
+    return extract_host(gray, planes, order, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out, sel, dither);
 }
 
 int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, char *bits_ascii_out,

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "svs_block.hpp"
 #include "svs_colour.hpp"
 #include "svs_index.hpp"
@@ -115,6 +117,12 @@ __device__ __forceinline__ void emit_wave_bits(uint32_t *mine, uint32_t lane, ui
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ BlockOrderArgs order_arg() { return BlockOrderArgs{}; }
 __device__ __forceinline__ BlockOrderArgs order_arg(const BlockOrderArgs &o) { return o; }
+
+// s_b of global block gblock (svs_block.hpp): per lane - a wave may straddle two frames
+__device__ __forceinline__ uint32_t dither_seed_of(uint32_t gblock, const Geometry &g, const DitherArgs &d) {
+    const uint32_t f = fast_div(gblock, g.by_bpf);
+    return dither_block_seed(d.seed, d.first_frame + f, gblock - f * g.by_bpf.div);
+}
 
 // first stream bit of global block gblock (KEYED: of its slot), and of its right neighbour gblock + 1 (same frame: the
 // two-block layout needs an even number of blocks per block row) in *second
@@ -336,14 +344,16 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
                                                           const uint32_t *__restrict__ bits,
                                                           const uint64_t bit_offset, const uint64_t n_bits,
                                                           const uint32_t n_words, const CoeffTable sel,
-                                                          const Order... order) {
+                                                          const DitherArgs dith, const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     // SVS_NEAREST, SVS_MINMOVE: ONE wave-uniform branch around the whole body, the rule a compile-time constant on every side
     // (QimRule; under SVS_MINMOVE its half_cell is the launch's, the kind is the constant: rule_from_word with a word > 1).
     // A `return` inside the body leaves the body, and nothing follows the calls.
     // A coefficient selection (sel.count != 0; the U = 8 instantiations only - svs_route.hpp plans no other for one) is a
     // second such branch: `table` is a compile-time NULL on the side without one, which is the body as it was.
-    const auto body = [&](const QimRule qp, const CoeffTable *table) __attribute__((always_inline)) {
+    // A keyed dither (dith.on; the U = 8 instantiations only - svs_route.hpp plans no other for one) is a third: `dithered` is a
+    // compile-time false on every side that was there before, which keeps its code; the dithered side has its own three copies.
+    const auto body = [&](const QimRule qp, const CoeffTable *table, auto dithered) __attribute__((always_inline)) {
         const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
         if (gblock >= g.total_blocks) return;
         const int64_t off = block_offset(gblock, g);
@@ -360,22 +370,34 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
         for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
         uint32_t hi, lo;
         payload_window(bits, n_words, bit_offset + first, hi, lo);
-        embed_block_exact<U, QM>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp, false, table);
+        if constexpr (decltype(dithered)::value)
+            embed_block_exact<U, QM, true>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp, false, table,
+                                           dither_seed_of(gblock, g, dith));
+        else
+            embed_block_exact<U, QM>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp, false, table);
 #pragma unroll
         for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
         store_rows<1>(stego + off, g.row_pitch, v);
     };
+    constexpr std::false_type plain{};
     if constexpr (U == 8) {
+        if (dith.on) {     // wave-uniform; `sel` is the call's selection or the prefix table of n_ac: one selected loop serves both
+            constexpr std::true_type dithered{};
+            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &dith.sel, dithered);
+            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered);
+            else body(QimRule(qp, 0u), &dith.sel, dithered);
+            return;
+        }
         if (sel.count) {   // Geometry::n_ac == sel.count: the stream ranges and the block budget are those of n_ac slots
-            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &sel);
-            else if (g.pad) body(QimRule(qp, 1u), &sel);
-            else body(QimRule(qp, 0u), &sel);
+            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &sel, plain);
+            else if (g.pad) body(QimRule(qp, 1u), &sel, plain);
+            else body(QimRule(qp, 0u), &sel, plain);
             return;
         }
     }
-    if (g.pad > 1u) body(rule_from_word(qp, g.pad), nullptr);
-    else if (g.pad) body(QimRule(qp, 1u), nullptr);
-    else body(QimRule(qp, 0u), nullptr);
+    if (g.pad > 1u) body(rule_from_word(qp, g.pad), nullptr, plain);
+    else if (g.pad) body(QimRule(qp, 1u), nullptr, plain);
+    else body(QimRule(qp, 0u), nullptr, plain);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -829,34 +851,58 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
 // every placement, 1.77 - 1.95 ms per 600 x 4K against 1.58 - 1.62, even with the arithmetic skipped: profiles/r06_stream_pipeline.txt.
 // What the one-shot launch has and the loop has not is the hardware's own pacing: a workgroup starts when another one ends.)
 
+// The eight-row instantiations are register-allocated for the six waves per SIMD they ran at before the dithered side joined
+// them (75 - 80 VGPRs; each side fits on its own, left alone the allocator takes 81 - 85 for the pair); a minimum of 1 is the
+// default of the others.
 template <int U, int QM, int BPL = 1, bool KEYED = false, class... Order>   // BPL: see extract_kernel
-__global__ __launch_bounds__(SVS_WG) void extract_exact_kernel(const uint8_t *__restrict__ gray, const Geometry g,
+__global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                             const QimParams qp, uint8_t *__restrict__ out,
                                                             const uint64_t out_bytes, const CoeffTable sel,
-                                                            const Order... order) {
+                                                            const DitherArgs dith, const Order... order) {
     static_assert(BPL == 1, "one block per lane");
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t tile = tile_id(g.xcd_chunk);
-    const uint32_t gblock = tile * (uint32_t)SVS_WG + threadIdx.x;
-    const uint32_t n = g.n_ac;
-    uint32_t hi = 0, lo = 0;
-    if (gblock < g.total_blocks) {
-        u32x2 v[8];
-        load_rows<1>(gray + block_offset(gblock, g), g.row_pitch, v);
-        uint32_t ax[8], ay[8];
+    // A keyed dither (dith.on; the U = 8 instantiations only - svs_route.hpp plans no other for one): ONE wave-uniform branch
+    // around the whole body, as in embed_exact_kernel; `dithered` is a compile-time false on the side that was there before.
+    // (The dithered forms as two more alternatives beside the selection's branch, sharing the loads and the tail, took 136
+    // instead of 77 VGPRs and three waves per SIMD from the calls without a dither.)
+    const auto body = [&](auto dithered) __attribute__((always_inline)) {
+        constexpr bool DITH = decltype(dithered)::value;
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        const uint32_t tile = tile_id(g.xcd_chunk);
+        const uint32_t gblock = tile * (uint32_t)SVS_WG + threadIdx.x;
+        const uint32_t n = g.n_ac;
+        uint32_t hi = 0, lo = 0;
+        if (gblock < g.total_blocks) {
+            u32x2 v[8];
+            load_rows<1>(gray + block_offset(gblock, g), g.row_pitch, v);
+            uint32_t ax[8], ay[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
-        // a coefficient selection (U = 8 only; n == sel.count): one wave-uniform branch around the block's arithmetic
-        bool selected = false;
-        if constexpr (U == 8) selected = sel.count != 0;
-        if (selected) extract_block_exact_selected<QM>(ax, ay, sel, qp, hi, lo);
-        else extract_block_exact<U, QM>(ax, ay, n, qp, hi, lo);
-        if constexpr (KEYED) or_bits_global<U>(out, stream_first<true>(gblock, n, g, order_arg(order...)), hi, lo);
+            for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
+            // a coefficient selection (U = 8 only; n == sel.count): one wave-uniform branch around the block's arithmetic
+            bool selected = false;
+            if constexpr (U == 8) selected = sel.count != 0;
+            if constexpr (DITH) {
+                // the prefix form and the selected form, as on the side without a dither
+                const uint32_t s_b = dither_seed_of(gblock, g, dith);
+                if (selected) extract_block_exact_selected<QM, true>(ax, ay, sel, qp, hi, lo, s_b);
+                else extract_block_exact<U, QM, true>(ax, ay, n, qp, hi, lo, s_b);
+            } else {
+                if (selected) extract_block_exact_selected<QM>(ax, ay, sel, qp, hi, lo);
+                else extract_block_exact<U, QM>(ax, ay, n, qp, hi, lo);
+            }
+            if constexpr (KEYED) or_bits_global<U>(out, stream_first<true>(gblock, n, g, order_arg(order...)), hi, lo);
+        }
+        if constexpr (!KEYED)
+            emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
+    };
+    if constexpr (U == 8) {
+        if (dith.on) {     // wave-uniform
+            body(std::true_type{});
+            return;
+        }
     }
-    if constexpr (!KEYED)
-        emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
+    body(std::false_type{});
 }
 
 // ---------------------------------------------------------------------------------------

@@ -31,6 +31,10 @@ struct RouteArgs {
     // kernels in every mode - the streaming embed guard and the FAST extract margins (tools/guard_bound.py) are derived for
     // row-major prefixes only.
     const CoeffTable *coeffs = nullptr;
+    // a keyed dither (svs_embed_dithered* / svs_extract_dithered*; gray calls only): the lane-per-block exact kernels with all
+    // eight coefficient rows in every mode, as a non-prefix selection - the streaming guard and the FAST extract tie margins
+    // are derived for an undithered quantiser input
+    bool dithered = false;
 };
 
 inline bool route_selected(const RouteArgs &a) {
@@ -62,6 +66,7 @@ struct EmbedPlan {
     uint64_t use;             // payload bits embedded (*n_embedded)
     uint64_t bit_offset, n_bits, n_words;   // the kernel's payload arguments; n_words >= 2^32: too large for one call
     bool selected;            // the launch passes the call's CoeffTable (EXACT with rows = 8 only), else an empty one
+    bool dithered;            // the launch switches the exact kernel's dithered side on (EXACT with rows = 8 only)
 };
 
 // Which kernel family (include/svsdct.h `flags`).  The streaming kernels cover one and two coefficient rows (n <= 15) inside the
@@ -74,9 +79,9 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
     p.use = a.n_bits < cap ? a.n_bits : cap;
     if (!(a.delta > 0.0) || n == 0) p.use = 0;   // nothing can be embedded (config_and_setup.py:143-145)
     const bool selected = route_selected(a);
-    const int rows = selected ? 8 : rows_for((int)n);
+    const int rows = selected || a.dithered ? 8 : rows_for((int)n);
     const bool in_range = a.delta >= SVS_GUARD_DELTA_MIN && a.delta <= SVS_GUARD_DELTA_MAX;
-    const bool streaming = p.use > 0 && in_range && !a.pocketfft && rows <= 2 && !(a.guarded_off && !a.bgr);   // never selected: rows = 8
+    const bool streaming = p.use > 0 && in_range && !a.pocketfft && rows <= 2 && !(a.guarded_off && !a.bgr);   // never selected or dithered: rows = 8
     p.xcd_chunk = kEighth;
     const int qm = make_qim(p.use == 0 ? 1.0 : a.delta, &p.qp);
     if (p.use > 0) {
@@ -96,6 +101,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.minmove = a.minmove;                // likewise
         p.half_cell = a.minmove ? (float)(0.5 * a.delta) : 0.0f;
         p.selected = selected;                // likewise: the other paths touch no coefficient
+        p.dithered = a.dithered;              // likewise (EXACT with rows = 8)
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;
@@ -127,6 +133,7 @@ struct ExtractPlan {
     QimParams qp;
     bool keyed;               // the KEYED instantiation of the family (not ZEROS: all bits 0 in any order)
     bool selected;            // the launch passes the call's CoeffTable (EXACT with rows = 8 only), else an empty one
+    bool dithered;            // the launch switches the exact kernel's dithered side on (EXACT with rows = 8; not ZEROS)
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -139,7 +146,8 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
         return p;
     }
     p.selected = route_selected(a);
-    p.rows = p.selected ? 8 : rows_for((int)a.n_ac);
+    p.dithered = a.dithered;
+    p.rows = p.selected || p.dithered ? 8 : rows_for((int)a.n_ac);
     p.xcd_chunk = p.rows == 1 ? 32u : (p.rows == 2 && !a.bgr ? 0u : kEighth);
     p.qm = make_qim(a.delta, &p.qp) == QM_POW2 ? QM_POW2 : QM_F32;
     const float t = a.tie_scale;
@@ -152,7 +160,7 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     // the FAST kernels with two and more rows round c / delta by adding 1.5 * 2^23, which needs |c / delta| < 2^22.  With one
     // row the pocketfft-identical forward costs 0.2-3 % (the kernel stays HBM-bound; profiles/history/r01_ab_quant_exact.txt),
     // so FAST mode uses it too; with more rows it costs ~17 % and stays opt-in.
-    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected) exact = true;
+    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected || p.dithered) exact = true;
     p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
     p.keyed = a.keyed;
     return p;

@@ -20,6 +20,7 @@ from config_and_setup import (bitstream_ke_bytes, buat_pasangan_kunci_ecc, buat_
                               serialisasi_kunci_publik_ecc_compressed, setup_kunci_ecc)  # noqa: F401
 from svsdct import batch as _batch
 from svsdct import coeffs as _coeffs
+from svsdct import dither as _dither
 from svsdct import framing as _framing
 from svsdct import order as _order
 from svsdct.pipeline import FramePipeline, SlotFeeder, read_ahead
@@ -66,12 +67,19 @@ MINMOVE = os.environ.get("SVS_MINMOVE", "0") == "1"
 # the reference's row-major coefficients 1..num_ac_coeffs, today's bytes.  The receiver must set the same value.  The gray path
 # only (with SVS_FUSED_COLOUR the host-conversion gray path runs); refused together with SVS_KEEP_COLOUR, SVS_READBACK and
 # SVS_READBACK_COLOUR (a selection has no colour and no read-back form).  Allowed with SVS_BLOCK_KEY and SVS_NEAREST.
+# SVS_DITHER_KEY=<integer, int(x, 0)> (read per call, opt-in): keyed dither modulation (svsdct/dither.py, include/svsdct.h) - the
+# quantiser lattice of every payload coefficient of video frame k is shifted by an offset derived from the key, k, the block and
+# the coefficient: no comb in the coefficient histogram, no bits for a receiver without the key, no distortion cost.  Unset:
+# no dither, today's bytes and routes.  The receiver must set the same value.  The gray path only (with SVS_FUSED_COLOUR the
+# host-conversion gray path runs); refused together with SVS_KEEP_COLOUR, SVS_READBACK and SVS_READBACK_COLOUR (a dithered call
+# has no colour and no read-back form).  Allowed with SVS_BLOCK_KEY, SVS_COEFFS, SVS_NEAREST and
+# SVS_MINMOVE.
 
 
-def _keyed(block_key=None, **kw):
-    """keyword arguments of a keyed call (block order): none at all without a key, so the unkeyed loop makes exactly the calls it
-    made before the order existed"""
-    if block_key is None:
+def _keyed(block_key=None, dither_key=None, **kw):
+    """keyword arguments of a keyed call (block order, dither): none at all without a key, so the unkeyed loop makes exactly the
+    calls it made before the order and the dither existed"""
+    if block_key is None and dither_key is None:
         return {}
     return kw if kw else {"block_key": block_key}
 
@@ -143,6 +151,14 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     except (TypeError, ValueError) as exc:
         print(f"    Error: SVS_COEFFS tidak valid ({exc}).")
         return False, None, None
+    try:
+        kunci_dither = _dither.key_from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"    Error: SVS_DITHER_KEY tidak valid ({exc}).")
+        return False, None, None
+    if kunci_dither is not None and (KEEP_COLOUR or READBACK or READBACK_COLOUR):
+        print("    Error: SVS_DITHER_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK atau SVS_READBACK_COLOUR.")
+        return False, None, None
     if pilihan is not None and (KEEP_COLOUR or READBACK or READBACK_COLOUR):
         print("    Error: SVS_COEFFS tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK atau SVS_READBACK_COLOUR.")
         return False, None, None
@@ -184,7 +200,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     print(f"    Video output akan disimpan sebagai '{path_out}' (Codec: FFV1).")
 
     tabel_warna = None
-    if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None and pilihan is None:   # keyed order, selection: the host-conversion gray path
+    if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None and pilihan is None and kunci_dither is None:   # keyed order, selection, dither: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -209,6 +225,9 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if pilihan is not None:
         print(f"    Info: koefisien pembawa payload dipilih (SVS_COEFFS): {list(pilihan)}")
         terdekat = dict(terdekat, coeffs=pilihan)                  # the gray pipeline's keywords (the colour path is off)
+    if kunci_dither is not None:
+        print("    Info: kisi kuantisasi digeser dengan dither berkunci (SVS_DITHER_KEY).")
+        terdekat = dict(terdekat, dither_key=kunci_dither)         # likewise
     readback_abu = READBACK or (READBACK_COLOUR and not tabel_warna)   # the gray pipeline's read-back
 
     def lapor_readback(diperbaiki, tersisa):
@@ -300,7 +319,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
             def kirim(slot, k, n):
                 offset = k * per_batch * usable
                 used = pipe.submit_embed(slot, n, bit_offset=min(offset, total_bits),
-                                         **_keyed(first_frame=k * per_batch, block_key=kunci_blok))
+                                         **_keyed(kunci_blok, kunci_dither, first_frame=k * per_batch))
                 return used, min(n * usable, max(0, total_bits - offset))
 
             with SlotFeeder(pipe, isi, kirim) as feeder:

@@ -18,6 +18,7 @@ from config_and_setup import (bytes_ke_bitstream, buat_shared_secret_ecdh, dekri
                               hitung_sha3_256, setup_kunci_ecc)  # noqa: F401
 from svsdct import batch as _batch
 from svsdct import coeffs as _coeffs
+from svsdct import dither as _dither
 from svsdct import framing as _framing
 from svsdct import order as _order
 from svsdct.pipeline import FramePipeline, SlotFeeder
@@ -31,6 +32,8 @@ FUSED_COLOUR = os.environ.get("SVS_FUSED_COLOUR", "0") == "1"
 # SVS_BLOCK_KEY (read per call): the sender's keyed block order (embed_process.py); frame k of the video is clip frame k.
 # With SVS_FUSED_COLOUR the host-conversion gray path runs.
 # SVS_COEFFS (read per call): the sender's payload coefficient selection (embed_process.py); likewise the gray path.
+# SVS_DITHER_KEY (read per call): the sender's dither key (embed_process.py); frame k of the video is clip frame k; likewise
+# the gray path.  Unset: the loops take exactly the routes they take without it.
 
 
 def _cv2():
@@ -45,13 +48,15 @@ def _gagal(pesan, cap=None):
     return False
 
 
-def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0, coeffs=None):
+def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0, coeffs=None, dither_key=None):
     if tabel_warna:                                            # frames are colour: convert + extract in one kernel
         packed, n_bits = _batch.extract_bgr_frames(np.stack(frames), delta, n_ac, weights=tabel_warna)
     else:
         keyed = {} if block_key is None else {"block_key": block_key, "first_frame": first_frame}
         if coeffs is not None:
             keyed["coeffs"] = coeffs
+        if dither_key is not None:
+            keyed.update(dither_key=dither_key, first_frame=first_frame)
         packed, n_bits = _batch.extract_frames(np.stack(frames), delta, n_ac, **keyed)
     return np.unpackbits(packed, count=n_bits)
 
@@ -74,6 +79,11 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
     except (TypeError, ValueError) as exc:
         print(f"  Error: SVS_COEFFS tidak valid ({exc}).")
         return False
+    try:
+        kunci_dither = _dither.key_from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"  Error: SVS_DITHER_KEY tidak valid ({exc}).")
+        return False
     cv2 = _cv2()
     cap = cv2.VideoCapture(path_stego_video)
     if not cap.isOpened():
@@ -87,7 +97,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
         return False
     per_frame = _batch.capacity_bits(1, h, w, num_ac_coeffs)
     tabel_warna = None
-    if FUSED_COLOUR and kunci_blok is None and pilihan is None:   # keyed order, selection: the host-conversion gray path
+    if FUSED_COLOUR and kunci_blok is None and pilihan is None and kunci_dither is None:   # keyed order, selection, dither: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -111,7 +121,8 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
             cap.release()
             return False
         print(f"    Mengekstrak bit dari frame video ke-{frame_num}...")
-        bits = _extract_frames([gray], delta_kuantisasi, num_ac_coeffs, tabel_warna, kunci_blok, frame_num - 1, pilihan)
+        bits = _extract_frames([gray], delta_kuantisasi, num_ac_coeffs, tabel_warna, kunci_blok, frame_num - 1, pilihan,
+                               **({} if kunci_dither is None else {"dither_key": kunci_dither}))
         if bits.size == 0:
             print(f"  Error: Tidak ada bit diekstrak dari frame ke-{frame_num}.")
             cap.release()
@@ -169,7 +180,8 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
                                depth=max(1, min(PIPELINE_DEPTH, -(-lagi // per_batch))),
                                mode=_batch.host_level_mode(),
                                **({} if kunci_blok is None else {"block_key": kunci_blok}),
-                               **({} if pilihan is None else {"coeffs": pilihan})) as pipe:
+                               **({} if pilihan is None else {"coeffs": pilihan}),
+                               **({} if kunci_dither is None else {"dither_key": kunci_dither})) as pipe:
                 rencana = {"lagi": lagi}
 
                 def isi(slot):
@@ -184,7 +196,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
                     return n
 
                 def kirim(slot, k, n):
-                    if kunci_blok is None:
+                    if kunci_blok is None and kunci_dither is None:
                         return pipe.submit_extract(slot, n)
                     return pipe.submit_extract(slot, n, first_frame=awal + k * per_batch)
 

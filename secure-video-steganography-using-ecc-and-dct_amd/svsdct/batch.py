@@ -19,9 +19,10 @@ from typing import NamedTuple
 import numpy as np
 
 from . import coeffs as _coeffs
+from . import dither as _dither
 from . import native
 from .hostmem import pinned_empty
-from .native import BlockOrder, Planes
+from .native import BlockOrder, Dither, Planes
 from .order import check_key
 
 MAX_AC = 63
@@ -148,9 +149,33 @@ def _coeffs_arg(coeffs, n_ac, readback=False):
     return _coeffs.native_coeffs(sel)
 
 
+def _coeffs_ref(sel):
+    return None if sel is None else C.byref(sel)
+
+
 def _no_coeffs(coeffs):
     if coeffs is not None:
         raise ValueError("a coefficient selection has no colour form: convert to gray and use the gray calls")
+
+
+def dither_arg(dither_key, first_frame: int = 0, readback: bool = False) -> Dither | None:
+    """the C ABI's svs_dither for a dither key (None: no dither); raises unless 0 <= key < 2**64 and 0 <= first_frame < 2**32,
+    and with readback (a dithered call has no read-back form)"""
+    if dither_key is None:
+        return None
+    key = _dither.check_key(dither_key)
+    if readback:
+        raise ValueError("a keyed dither has no read-back form (readback=True)")
+    first_frame = int(first_frame)
+    if not 0 <= first_frame < (1 << 32):
+        raise ValueError(f"first_frame {first_frame} outside 0 .. 2**32 - 1")
+    return Dither(key, first_frame, 0)
+
+
+def no_dither(dither_key, what: str) -> None:
+    """the colour and _str calls: a dither key is refused before the library is loaded"""
+    if dither_key is not None:
+        raise ValueError(f"a keyed dither has no {what} form: use the gray calls with packed bits")
 
 
 class ReadbackCounts(NamedTuple):
@@ -161,7 +186,7 @@ class ReadbackCounts(NamedTuple):
 
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
-                 nearest: bool = False, coeffs=None, minmove: bool = False):
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
@@ -182,9 +207,15 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     "zigzag", "zigzag:<first>", "rowmajor" or a list of n_ac distinct flat indices in 1..63): stream bit i of a block goes
     to coefficient index[i].  It combines with block_key, first_frame, nearest and mode (any selection but the prefix runs
     the exact kernels in every mode); ValueError with readback.  The receiver must use the same selection.
+    dither_key : None or an integer key 0 <= key < 2**64 (opt-in, svsdct/dither.py, include/svsdct.h): the quantiser lattice
+    of every payload coefficient is shifted by a key-derived offset - no comb in the coefficient histogram, no bits for a
+    receiver without the key, no distortion cost.  It shares first_frame with block_key and combines with block_key, coeffs,
+    nearest, minmove and mode (a dithered call runs the exact kernels in every mode); ValueError with readback.  The receiver
+    must use the same key.
     Returns (stego uint8 [F,H,W], n_embedded), with readback (stego, n_embedded, ReadbackCounts)."""
     order = block_order(block_key, first_frame)
     sel = _coeffs_arg(coeffs, n_ac, readback)
+    dith = dither_arg(dither_key, first_frame, readback)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -200,6 +231,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     stego = pinned_empty(stack.shape)      # page-locked: the download lands in it by DMA, no staging copy, no page faults
     done = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
+    if dith is not None:
+        rc = lib.svs_embed_dithered(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
+                                    C.byref(dith), float(delta), int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits),
+                                    embed_flags(mode, nearest, minmove), C.byref(done))
+        native.check(rc, "svs_embed_dithered")
+        return stego, int(done.value)
     if readback:
         counts = native.ReadbackCounts()
         rc = lib.svs_embed_readback(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), float(delta),
@@ -225,12 +262,14 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
 
 
 def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
-                   first_frame: int = 0, coeffs=None):
+                   first_frame: int = 0, coeffs=None, dither_key=None):
     """Extract the packed bit stream of a stack of gray frames on the GPU.  block_key / first_frame: as embed_frames (the
-    sender's key and clip frame index).  coeffs: as embed_frames (the sender's selection).
+    sender's key and clip frame index).  coeffs: as embed_frames (the sender's selection).  dither_key: as embed_frames (the
+    sender's dither key).
     Returns (packed uint8 [ceil(n_bits/8)], n_bits)."""
     order = block_order(block_key, first_frame)
     sel = _coeffs_arg(coeffs, n_ac)
+    dith = dither_arg(dither_key, first_frame)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -239,7 +278,11 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     out = np.zeros(max(4, (cap + 7) // 8 + (-((cap + 7) // 8)) % 4), np.uint8)
     got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    if sel is not None:
+    if dith is not None:
+        rc = lib.svs_extract_dithered(stack.ctypes.data, C.byref(planes), _order_ref(order), _coeffs_ref(sel), C.byref(dith),
+                                      float(delta), int(n_ac), out.ctypes.data, out.size, mode_flags(mode), C.byref(got))
+        native.check(rc, "svs_extract_dithered")
+    elif sel is not None:
         rc = lib.svs_extract_select(stack.ctypes.data, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
                                     out.ctypes.data, out.size, mode_flags(mode), C.byref(got))
         native.check(rc, "svs_extract_select")
@@ -279,12 +322,14 @@ def _ascii_address(text: str):
 
 
 def embed_frames_str(frames: np.ndarray, delta, n_ac, payload: str | None, device: int = 0, mode: str | None = None,
-                     want_gray: bool = False):
+                     want_gray: bool = False, dither_key=None):
     """`embed_frames` in the reference operator's own types (config_and_setup.py:106-109,172): the payload is a '0'/'1'
     string (bit_payload_segment) of which at most the capacity is read from the front - the characters go to the device as
     they are and are packed there (svs_embed_str); None / "" = nothing to embed.  want_gray: also return a copy of the input
     frames as an array of its own, the operator's first return value - the library makes it while the GPU works.
+    dither_key: refused (ValueError) - a keyed dither has no _str form.
     Returns (stego uint8 [F,H,W], n_embedded) or (gray_copy, stego, n_embedded)."""
+    no_dither(dither_key, "_str")
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -300,9 +345,10 @@ def embed_frames_str(frames: np.ndarray, delta, n_ac, payload: str | None, devic
     return (gray, stego, int(done.value)) if want_gray else (stego, int(done.value))
 
 
-def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None) -> str:
+def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, dither_key=None) -> str:
     """`extract_frames` returning the reference operator's own type: the '0'/'1' string of config_and_setup.py:173-174
-    (expanded on the device, one decode on the host)."""
+    (expanded on the device, one decode on the host).  dither_key: refused (ValueError) - no _str form."""
+    no_dither(dither_key, "_str")
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -320,19 +366,33 @@ def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: s
 
 
 # ---- device-pointer level -------------------------------------------------------------------
+def _shared_first_frame(order: BlockOrder | None, first_frame: int | None) -> int:
+    """the clip frame index a dither shares with the call's block order"""
+    if first_frame is None:
+        return int(order.first_frame) if order is not None else 0
+    return int(first_frame)
+
+
 def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_packed: int,
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
-                 nearest: bool = False, coeffs=None, minmove: bool = False) -> int:
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, first_frame: int | None = None) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
     native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
     read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
     it adds {repaired, unrepaired} into.  nearest, minmove: SVS_NEAREST, SVS_MINMOVE, as embed_frames.  coeffs: a payload coefficient selection,
-    as embed_frames (svs_embed_select_dev)."""
+    as embed_frames (svs_embed_select_dev).  dither_key: a keyed dither, as embed_frames (svs_embed_dithered_dev); its clip
+    frame index is first_frame, by default the order's (0 without one) - the two must agree."""
     done = C.c_uint64(0)
     flags = embed_flags(mode, nearest, minmove)
     sel = _coeffs_arg(coeffs, n_ac, readback)
-    if sel is not None:
+    dith = dither_arg(dither_key, _shared_first_frame(order, first_frame), readback)
+    if dith is not None:
+        rc = native.load().svs_embed_dithered_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
+                                                  C.byref(dith), float(delta), int(n_ac), d_bits_packed, int(bit_offset),
+                                                  int(n_bits), flags, C.byref(done), stream or None)
+        native.check(rc, "svs_embed_dithered_dev")
+    elif sel is not None:
         rc = native.load().svs_embed_select_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
                                                 d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done),
                                                 stream or None)
@@ -356,11 +416,19 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
 
 
 def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
-                   stream: int = 0, mode: str | None = None, order: BlockOrder | None = None, coeffs=None) -> int:
-    """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order, coeffs: as embed_device."""
+                   stream: int = 0, mode: str | None = None, order: BlockOrder | None = None, coeffs=None, dither_key=None,
+                   first_frame: int | None = None) -> int:
+    """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order, coeffs, dither_key,
+    first_frame: as embed_device."""
     got = C.c_uint64(0)
     sel = _coeffs_arg(coeffs, n_ac)
-    if sel is not None:
+    dith = dither_arg(dither_key, _shared_first_frame(order, first_frame))
+    if dith is not None:
+        rc = native.load().svs_extract_dithered_dev(d_gray, C.byref(planes), _order_ref(order), _coeffs_ref(sel), C.byref(dith),
+                                                    float(delta), int(n_ac), d_bits_out, int(out_capacity_bytes),
+                                                    mode_flags(mode), C.byref(got), stream or None)
+        native.check(rc, "svs_extract_dithered_dev")
+    elif sel is not None:
         rc = native.load().svs_extract_select_dev(d_gray, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
                                                   d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got),
                                                   stream or None)
@@ -395,13 +463,15 @@ def _bgr_flags(mode, keep_colour, nearest=False, minmove=False):
 def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Planes, delta, n_ac,
                      d_bits_packed: int, bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                      weights=None, in_pitches=None, out_pitches=None, keep_colour: bool = False, readback: bool = False,
-                     d_counts: int = 0, nearest: bool = False, coeffs=None, minmove: bool = False) -> int:
+                     d_counts: int = 0, nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None) -> int:
     """Enqueue the fused BGR -> gray -> embed -> BGR kernel over packed (or pitched) interleaved BGR frames;
     `d_gray_ref` (0 to skip) receives the gray frames before embedding.  keep_colour: stego pixels keep the cover's
     colour (SVS_KEEP_COLOUR; their gray is the stego plane) instead of B = G = R.  readback: the read-back pass follows on
     the same stream, in place on the BGR output (svs_embed_bgr_readback_dev); d_counts: 0, or a device buffer of two uint64
-    that the call adds {repaired, unrepaired} into.  nearest, minmove: SVS_NEAREST, SVS_MINMOVE, as embed_frames.  Returns bits embedded."""
+    that the call adds {repaired, unrepaired} into.  nearest, minmove: SVS_NEAREST, SVS_MINMOVE, as embed_frames.
+    dither_key: refused (ValueError) - no colour form.  Returns bits embedded."""
     _no_coeffs(coeffs)
+    no_dither(dither_key, "colour")
     irp, ifp = in_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     orp, ofp = out_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     keep, wptr = _weights_arg(weights)
@@ -422,9 +492,10 @@ def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Pla
 
 
 def extract_bgr_device(d_bgr: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
-                       stream: int = 0, weights=None, pitches=None, coeffs=None) -> int:
+                       stream: int = 0, weights=None, pitches=None, coeffs=None, dither_key=None) -> int:
     """Enqueue extraction straight from interleaved BGR frames; returns the number of bits the batch yields."""
     _no_coeffs(coeffs)
+    no_dither(dither_key, "colour")
     rp, fp = pitches or (3 * planes.width, 3 * planes.width * planes.height)
     keep, wptr = _weights_arg(weights)
     got = C.c_uint64(0)
@@ -446,13 +517,14 @@ def _as_bgr_stack(frames: np.ndarray) -> np.ndarray:
 def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                      device: int = 0, mode: str | None = None, weights=None, want_gray: bool = True,
                      keep_colour: bool = False, readback: bool = False, nearest: bool = False, coeffs=None,
-                     minmove: bool = False):
+                     minmove: bool = False, dither_key=None):
     """BGR frames in, stego BGR frames out (one fused pass on the GPU).  keep_colour: see embed_bgr_device.  readback: the
     blocks whose payload bits do not read back are repaired in place on the BGR output (svs_embed_bgr_readback,
     include/svsdct.h).  nearest, minmove: SVS_NEAREST, SVS_MINMOVE, as embed_frames.
     Returns (stego_bgr uint8 [F,H,W,3], gray uint8 [F,H,W] (the cover's) or None, n_embedded), with readback
-    (stego_bgr, gray, n_embedded, ReadbackCounts)."""
+    (stego_bgr, gray, n_embedded, ReadbackCounts).  dither_key: refused (ValueError) - no colour form."""
     _no_coeffs(coeffs)
+    no_dither(dither_key, "colour")
     lib = native.load()
     native.ensure_device(device)
     stack = _as_bgr_stack(frames_bgr)
@@ -485,8 +557,9 @@ def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int 
     return out, gray, used
 
 
-def extract_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, device: int = 0, weights=None):
-    """Extract the packed bit stream straight from BGR frames.  Returns (packed uint8, n_bits)."""
+def extract_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, device: int = 0, weights=None, dither_key=None):
+    """Extract the packed bit stream straight from BGR frames.  Returns (packed uint8, n_bits).  dither_key: refused."""
+    no_dither(dither_key, "colour")
     lib = native.load()
     native.ensure_device(device)
     stack = _as_bgr_stack(frames_bgr)

@@ -58,6 +58,11 @@ class Coeffs(C.Structure):
     _fields_ = [("count", C.c_uint8), ("index", C.c_uint8 * 63)]
 
 
+class Dither(C.Structure):
+    """struct svs_dither: the keyed dither of the dithered entry points (include/svsdct.h, svsdct/dither.py)"""
+    _fields_ = [("key", C.c_uint64), ("first_frame", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 SVS_SCAN_ROW_MAJOR = 0
 SVS_SCAN_ZIGZAG = 1
 
@@ -66,6 +71,7 @@ _u64p = C.POINTER(C.c_uint64)
 _PL = C.POINTER(Planes)
 _BO = C.POINTER(BlockOrder)
 _CO = C.POINTER(Coeffs)
+_DI = C.POINTER(Dither)
 
 # name -> (restype, argtypes); every symbol include/svsdct.h declares
 SIGNATURES = {
@@ -104,6 +110,13 @@ SIGNATURES = {
     "svs_extract_select_dev": (C.c_int, [_u8p, _PL, _BO, _CO, C.c_double, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
     "svs_embed_select": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, C.c_double, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
     "svs_extract_select": (C.c_int, [_u8p, _PL, _BO, _CO, C.c_double, _u8p, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_embed_dithered_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64,
+                                          C.c_uint32, _u64p, C.c_void_p]),
+    "svs_extract_dithered_dev": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p,
+                                            C.c_void_p]),
+    "svs_embed_dithered": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64,
+                                      C.c_uint32, _u64p]),
+    "svs_extract_dithered": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                           _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,

@@ -50,17 +50,20 @@ def _device(nbytes: int):
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
-                 nearest: bool = False, coeffs=None, minmove: bool = False):
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
         towards the nearer lattice point (SVS_NEAREST, include/svsdct.h).  minmove: every embed batch moves a payload coefficient
         only as far as its decision cell asks (SVS_MINMOVE, include/svsdct.h).  coeffs: None or a payload coefficient selection
-        for every batch, as batch.embed_frames (resolved once with n_ac; ValueError with readback)."""
+        for every batch, as batch.embed_frames (resolved once with n_ac; ValueError with readback).  dither_key: None or the
+        key of a keyed dither for every batch (svsdct/dither.py; ValueError with readback); each submit's first frame index
+        feeds both the order and the dither."""
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
         self.block_key = batch.block_order(block_key).key if block_key is not None else None
         self.coeffs = _coeffs.selection(coeffs, batch.clamp_ac(n_ac))
+        self.dither_key = batch.dither_arg(dither_key, 0, readback).key if dither_key is not None else None
         if self.coeffs is not None and readback:
             raise ValueError("a coefficient selection has no read-back form (readback=True)")
         native.ensure_device(device)
@@ -121,6 +124,10 @@ class FramePipeline:
     def _order(self, first_frame: int):
         return batch.block_order(self.block_key, first_frame) if self.block_key is not None else None
 
+    def _dither(self, first_frame: int) -> dict:
+        """the keywords of a dithered submit: none at all without a key, so the other submits make the calls they made"""
+        return {} if self.dither_key is None else {"dither_key": self.dither_key, "first_frame": first_frame}
+
     def submit_embed(self, slot: int, n_frames: int, bit_offset: int, first_frame: int = 0) -> int:
         """Enqueue H2D -> embed -> D2H for the first n_frames frames of the slot; returns the bits this batch
         will carry.  Does not wait.  first_frame: clip index of the batch's first frame (keyed block order)."""
@@ -132,7 +139,7 @@ class FramePipeline:
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
                                   stream=s["stream"].value, mode=self.mode, order=self._order(first_frame),
                                   readback=self.readback, d_counts=self._d_counts.value if self._d_counts else 0,
-                                  nearest=self.nearest, coeffs=self.coeffs, minmove=self.minmove)
+                                  nearest=self.nearest, coeffs=self.coeffs, minmove=self.minmove, **self._dither(first_frame))
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
         return used
@@ -151,7 +158,7 @@ class FramePipeline:
         native.check(self.lib.svs_memcpy_h2d(s["d_frames"], s["hin_p"], nbytes, s["stream"]), "svs_memcpy_h2d")
         got = batch.extract_device(s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac, s["d_bits"].value,
                                    self._bits_bytes, stream=s["stream"].value, mode=self.mode,
-                                   order=self._order(first_frame), coeffs=self.coeffs)
+                                   order=self._order(first_frame), coeffs=self.coeffs, **self._dither(first_frame))
         native.check(self.lib.svs_memcpy_d2h(s["hbits_p"], s["d_bits"], (got + 7) // 8, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, got
         return got
