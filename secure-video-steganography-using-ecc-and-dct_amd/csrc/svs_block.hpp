@@ -1150,6 +1150,8 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
 // exact arithmetic writes verbatim (D' = D with cn_k in place), and |cn_k - c_k| <= 1.5 delta + 0.01.  Neither needs cn_k to
 // be a lattice point; a coefficient that stays (cn_k = D_k, change 0) is an unmodified one to the analysis.  So the streaming
 // bodies take the rule with the same BETA.
+// tests/test_guard_rules_cpu.py and tests/test_guard_rules_gpu.py hold this on frames whose blocks sit at the guard's boundary
+// under each rule (tests/golden/guard_rules_corpus.npz), waves of 1 to 128 replays included.
 #define SVS_GUARD_UEFF (5.9604644775390625e-8 * (1.0 + 0.0009765625))
 // delta range the guarded path is used for (outside it the caller takes the exact kernel): below, the changes are smaller
 // than BETA and every block would be flagged; above, BETA itself exceeds 1/8

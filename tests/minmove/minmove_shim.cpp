@@ -57,15 +57,18 @@ extern "C" {
 // otherwise the route of flags = SVS_EXACT_GUARDED.  force_qm: -1 = the plan's quantiser mode, else that svs::QuantMode (the
 // caller asks only for modes that are valid for the delta).  out = {blocks the guard handed to the exact replay, the plan's
 // path, its `minmove`, its `nearest`, its qm, the rule word}.  Returns the bits embedded, ~0 for an invalid selection.
-uint64_t mm_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, double delta, int n_ac, const uint8_t *index,
-                  int count, const uint8_t *bits, uint64_t bits_bytes, uint64_t bit_offset, uint64_t n_bits, int pocketfft,
-                  int nearest, int minmove, int force_qm, uint64_t *out) {
+// guard_scale: RouteArgs::guard_scale, what SVS_GUARD_SCALE is to the experiments library (1 = the product's BETA).
+// replay_map: NULL, or one byte per block of the call (raster order over the batch), set to 1 where the guard handed the
+// block to the exact replay (the caller zeroes it).
+uint64_t mm_embed_scaled(const uint8_t *gray, uint8_t *stego, int F, int H, int W, double delta, int n_ac, const uint8_t *index,
+                         int count, const uint8_t *bits, uint64_t bits_bytes, uint64_t bit_offset, uint64_t n_bits, int pocketfft,
+                         int nearest, int minmove, int force_qm, uint64_t *out, float guard_scale, uint8_t *replay_map) {
     svs::CoeffTable table{};
     if (count && !svs::make_coeff_table(index, (uint32_t)count, &table)) return ~0ull;
     const uint32_t n = count ? table.count : (uint32_t)(n_ac < 0 ? 0 : (n_ac > 63 ? 63 : n_ac));
     const uint64_t wb = (uint64_t)W / 8, bpf = wb * (uint64_t)(H / 8), total = bpf * (uint64_t)F;
     std::memcpy(stego, gray, (size_t)F * H * W);
-    svs::RouteArgs ra{delta, n, total, n_bits, bit_offset, pocketfft != 0, pocketfft == 0, false, false, 1.0f, 1.0f};
+    svs::RouteArgs ra{delta, n, total, n_bits, bit_offset, pocketfft != 0, pocketfft == 0, false, false, guard_scale, 1.0f};
     ra.nearest = nearest != 0;
     ra.minmove = minmove != 0;
     if (count) ra.coeffs = &table;
@@ -98,9 +101,18 @@ uint64_t mm_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, doub
         else if (qm == svs::QM_POW2) replayed = one_block<svs::QM_POW2>(streaming, p.rows, raw, px, (size_t)W, p.n_ac, nb, hi, lo, rule, sel);
         else replayed = one_block<svs::QM_F32>(streaming, p.rows, raw, px, (size_t)W, p.n_ac, nb, hi, lo, rule, sel);
         out[0] += replayed;
+        if (replay_map && replayed) replay_map[gb] = 1;
         raw.store(px, (size_t)W);
     }
     return p.use;
+}
+
+// the product's guard, no map: every caller from before the guard-scale argument
+uint64_t mm_embed(const uint8_t *gray, uint8_t *stego, int F, int H, int W, double delta, int n_ac, const uint8_t *index,
+                  int count, const uint8_t *bits, uint64_t bits_bytes, uint64_t bit_offset, uint64_t n_bits, int pocketfft,
+                  int nearest, int minmove, int force_qm, uint64_t *out) {
+    return mm_embed_scaled(gray, stego, F, H, W, delta, n_ac, index, count, bits, bits_bytes, bit_offset, n_bits, pocketfft, nearest,
+                           minmove, force_qm, out, 1.0f, nullptr);
 }
 
 // the plan of a gray (bgr = 0) or fused colour embed call with the flag: out = {path, minmove, use, bits of half_cell, rule word}

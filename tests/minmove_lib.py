@@ -142,6 +142,8 @@ def shim():
         lib.mm_embed.restype = C.c_uint64
         lib.mm_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        lib.mm_embed_scaled.restype = C.c_uint64
+        lib.mm_embed_scaled.argtypes = lib.mm_embed.argtypes + [C.c_float, C.c_void_p]
         lib.mm_plan.restype = None
         lib.mm_plan.argtypes = [C.c_double, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         lib.mm_margin.restype = C.c_float
@@ -153,9 +155,11 @@ def shim():
 
 
 def host_embed(frames, delta, n_ac, bits, bit_offset=0, n_bits=None, pocketfft=False, minmove=True, nearest=False, index=None,
-               qm=-1):
+               qm=-1, guard_scale=None, replay_map=False):
     """a gray embed call through the product headers on the host -> (stego, bits embedded, info dict: `replayed` blocks, `path`,
-    the plan's `minmove`, `nearest` and `qm`, the rule `word`)"""
+    the plan's `minmove`, `nearest` and `qm`, the rule `word`).  guard_scale: RouteArgs::guard_scale, as SVS_GUARD_SCALE of the
+    experiments library (None: the product's guard).  replay_map=True: info gains `replay_map`, bool per block of the call in
+    raster order - the guard handed the block to the exact replay."""
     frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
     f, h, w = frames.shape
     bits = np.asarray(bits, np.uint8)
@@ -166,12 +170,21 @@ def host_embed(frames, delta, n_ac, bits, bit_offset=0, n_bits=None, pocketfft=F
     idx = np.zeros(1, np.uint8) if index is None else np.ascontiguousarray(np.asarray(index, np.int64).astype(np.uint8))
     out = np.empty_like(frames)
     info = np.zeros(6, np.uint64)
-    used = shim().mm_embed(frames.ctypes.data, out.ctypes.data, f, h, w, float(delta), int(n_ac), idx.ctypes.data,
-                           0 if index is None else idx.size, packed.ctypes.data, packed.size, int(bit_offset), int(n_bits),
-                           int(pocketfft), int(nearest), int(minmove), int(qm), info.ctypes.data)
+    args = (frames.ctypes.data, out.ctypes.data, f, h, w, float(delta), int(n_ac), idx.ctypes.data,
+            0 if index is None else idx.size, packed.ctypes.data, packed.size, int(bit_offset), int(n_bits),
+            int(pocketfft), int(nearest), int(minmove), int(qm), info.ctypes.data)
+    rmap = np.zeros(f * (h // 8) * (w // 8), np.uint8) if replay_map else None
+    if guard_scale is None and rmap is None:
+        used = shim().mm_embed(*args)
+    else:
+        used = shim().mm_embed_scaled(*args, 1.0 if guard_scale is None else float(guard_scale),
+                                      None if rmap is None else rmap.ctypes.data)
     assert used != 2 ** 64 - 1, "the shim refused the selection"
-    return out, int(used), dict(replayed=int(info[0]), path=int(info[1]), minmove=int(info[2]), nearest=int(info[3]),
-                                qm=int(info[4]), word=int(info[5]))
+    res = dict(replayed=int(info[0]), path=int(info[1]), minmove=int(info[2]), nearest=int(info[3]), qm=int(info[4]),
+               word=int(info[5]))
+    if rmap is not None:
+        res["replay_map"] = rmap.astype(bool)
+    return out, int(used), res
 
 
 def plan(delta, n_ac, total, n_bits, pocketfft=False, bgr=False, minmove=True, nearest=False):
