@@ -108,7 +108,8 @@ extern "C" {
  * pixels (a letterbox bar is lifted off 0: visibly lighter blocks, lower PSNR), which is why the flag is opt-in.  What the
  * search leaves: blocks that clip at both ends (no shift helps) and small delta (delta = 4, n_ac = 3: a few blocks per
  * frame); at small delta it can also overshoot, and a few accepted blocks per frame decode but are visibly destroyed.  The receiver is unchanged: any extract call decodes the result.  The call needs the reference's stego as its start
- * and not the cover, so in-place calls keep working.  Only svs_embed_readback* report the counts. */
+ * and not the cover, so in-place calls keep working.  Only svs_embed_readback* report the counts.  The select and dithered
+ * calls reject the flag too: their read-back form is svs_embed_dithered_readback* below. */
 #define SVS_READBACK 0x200u
 /* SVS_NEAREST (every embed call: svs_embed_dev, svs_embed, svs_embed_str, svs_embed_ordered*, svs_embed_readback*, svs_embed_bgr*,
  * svs_embed_bgr_readback*; every extract call rejects it with SVS_ERR_INVALID_ARG before any device work): opt-in.  It combines
@@ -160,7 +161,8 @@ extern "C" {
  * delta <= 0, n_ac = 0 and empty-payload routes (the flag has no effect there), the pocketfft inverse of all 64 coefficients,
  * clip, truncate.  With SVS_READBACK the read-back pass starts from the stego this rule wrote.
  * Cost: the stego is NEITHER the reference's NOR the nearest rule's pixels.  Limit: the guarantee excludes blocks that clip at
- * 0 / 255 (their error is not bounded by the margin); SVS_READBACK is the remedy there and combines with the flag.  The
+ * 0 / 255 (their error is not bounded by the margin); SVS_READBACK is the remedy there and combines with the flag (under a
+ * selection or a dither: svs_embed_dithered_readback*).  The
  * receiver is unchanged and the default (flag clear) is byte-identical to before.
  * Measured ON THE CPU with the oracle's pieces (tests/minmove_lib.py model_embed), one 480 x 640 frame, full-capacity random
  * payload; PSNR against the cover in dB / payload bit errors, reference | SVS_NEAREST | SVS_MINMOVE:
@@ -353,7 +355,8 @@ int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs
  * same n_ac has NOT been measured on a GPU yet: tools/coeff_select_rates.py measures it at 200 x 4K (counts 3, 10, 63) and
  * writes profiles/coeff_select_rates.txt.  Both run the same quantiser steps; the selected loop adds scalar table reads and
  * covers all 63 positions with a wave-uniform test each, where the n_ac <= 15 exact kernels cover one or two rows.
- * There is no read-back, no colour and no _str form.
+ * There is no colour and no _str form; these calls refuse SVS_READBACK - the selected embed with read-back and repair is
+ * svs_embed_dithered_readback* below (dither NULL).
  *   coeffs : the selection; the unused tail of index must be 0.  NULL, an index of 0 or above 63, a duplicate, count > 63 or
  *            a non-zero tail: SVS_ERR_INVALID_ARG before any device work.
  *   order  : NULL or a keyed block order, as in the ordered calls (a keyed host embed stages whole frames).
@@ -429,7 +432,8 @@ int svs_extract_select(const uint8_t *gray, const svs_planes *planes, const svs_
  * input), behind one wave-uniform branch in their eight-row instantiations; on top of that come one integer hash and two float
  * operations per payload coefficient.  tools/dither_rates.py times it against the SVS_EXACT_POCKETFFT call at the same n_ac
  * and against the selected call, at 200 x 4K (n_ac = 3, 10, 63).
- * There is no read-back, no colour and no _str form.
+ * There is no colour and no _str form; these calls refuse SVS_READBACK - the dithered embed with read-back and repair is
+ * svs_embed_dithered_readback* below.
  *   order  : NULL or a keyed block order, as in the ordered calls.
  *   coeffs : NULL (the row-major prefix 1..n_ac) or a coefficient selection, checked as in the select calls; n_ac is then
  *            ignored and the selection's count rules.  The dither of a coefficient is that of its flat index k, whatever slot
@@ -481,6 +485,34 @@ int svs_embed_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_pl
 int svs_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order, double delta,
                        int n_ac, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                        uint64_t *n_embedded, svs_readback_counts *counts);
+
+/* Read-back and repair under a coefficient selection and a keyed dither: svs_embed_dithered_dev / svs_embed_dithered followed,
+ * on the call's stream, by a read-back pass that checks every payload block with svs_extract_select* / svs_extract_dithered*'s
+ * own verdict - for every selected coefficient k whose slot lies inside the block's budget, the parity of quant_index(c_k)
+ * (with a dither: of quant_index(c_k - d_k), d that of the block's physical position) against the payload bit of its slot,
+ * c the pocketfft-identical forward transform - and repairs a failing block with SVS_READBACK's bounded search
+ * (csrc/svs_readback.hpp, the keyed forms): the targets are the nearest lattice points of the wanted parity of the SHIFTED
+ * lattice, q' delta + d_k, everything else is the same, at most 16 iterates, accepted only when that check confirms every bit.
+ *   order, coeffs, dither : each may be NULL.  A NULL dither is the selected call with read-back; with all three NULL, or with
+ *            a prefix selection alone, the call IS svs_embed_readback*: its kernels, its bytes and its counts.  What is given
+ *            is checked as in the dithered calls (svs_coeffs, reserved, the two first_frame values).
+ *   flags  : the mode bits are accepted and change nothing; SVS_NEAREST and SVS_MINMOVE; SVS_READBACK is accepted and implied;
+ *            anything else: SVS_ERR_INVALID_ARG before any device work.
+ *   d_counts / counts : as in svs_embed_readback*.
+ * Contract: the call first writes exactly the stego of the same call without read-back (in place allowed); a block that reads
+ * back keeps its bytes; an unrepaired block keeps them too and is counted; blocks past the budget are untouched.  The host
+ * form stages whole frames under an order or a dither and sums the counts over its chunks.  The limits are SVS_READBACK's: a
+ * block that clips at both ends can stay unrepaired, and at small delta (4) an accepted iterate can be far from the stego.
+ * Cost on a GPU: not measured yet (tools/keyed_readback_rates.py writes profiles/keyed_readback_rates.txt). */
+int svs_embed_dithered_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
+                                    const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither,
+                                    double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
+                                    uint32_t flags, uint64_t *n_embedded, uint64_t *d_counts, void *stream);
+
+int svs_embed_dithered_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                                const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
+                                const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                                uint64_t *n_embedded, svs_readback_counts *counts);
 
 /* ---- colour plumbing around the operator (device resident) --------------------------------------------
  * Interleaved 8-bit BGR frames [frame][row][col][3] <-> gray planes.  bgr_row_pitch / bgr_frame_pitch in bytes,

@@ -239,25 +239,36 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
 // embed's payload arguments (the plan's rows are 1 or 2 for n <= 15, else 8: the quantiser loop's coefficient rows).
 // The colour calls pass their BGR output as `stego`, its pitches and the call's weights in `colour`, and form = SVS_RB_BGR:
 // they run the colour body of their quantiser mode, which lives in one instantiation (plain and keep-colour output alike).
+// A plan with a non-prefix selection or a dither (svs_embed_dithered_readback_dev; `coeffs`, `dith` as launch_embed takes them)
+// runs the keyed form, form = SVS_RB_SEL + its quantiser mode, in the same instantiation: the table it passes is the call's
+// selection or the prefix table of n_ac, and a call without an order adds SVS_RB_RASTER.
 int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uint8_t *stego, svs::Geometry g, const uint32_t *bits,
                     uint64_t *counts, const svs::BlockOrderArgs &ord, const svs::ColourParams &colour = svs::ColourParams{},
-                    uint32_t form = SVS_RB_GRAY) {
+                    uint32_t form = SVS_RB_GRAY, const svs::CoeffTable *coeffs = nullptr,
+                    const svs::DitherArgs &dith = svs::DitherArgs{}) {
     g.n_ac = p.n_ac;
     g.xcd_chunk = svs::kEighth;
     const uint32_t words = (uint32_t)p.n_words;
     auto *c = reinterpret_cast<unsigned long long *>(counts);
+    const svs::DitherArgs none{};
     if (form != SVS_RB_GRAY)   // the one instantiation that holds the colour bodies (svs_device.hpp SVS_RB_HOSTS_COLOUR)
         return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
-                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_BGR + p.qm), svs::BlockOrderArgs{});
+                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_BGR + p.qm), none, svs::BlockOrderArgs{});
+    if (p.selected || p.dithered) {   // ... and the keyed bodies
+        const svs::DitherArgs kd{dith.seed, dith.first_frame, p.dithered ? 1u : 0u,
+                                 p.selected && coeffs ? *coeffs : svs::make_prefix_table((uint32_t)p.n_ac)};
+        return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
+                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_SEL + p.qm + (p.keyed ? 0u : SVS_RB_RASTER)), kd, ord);
+    }
     return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
         return dispatch<1, 2, 8>(p.rows, [&](auto u) {
             constexpr int U = decltype(u)::value;
             if (p.keyed)
                 return launch(svs::readback_kernel<U, QM, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words, c, colour, form, ord);
+                              p.bit_offset, p.n_bits, words, c, colour, form, none, ord);
             return launch(svs::readback_kernel<U, QM>, grid_for(total), 0, st, stego, g, p.qp, bits, p.bit_offset, p.n_bits, words, c,
-                          colour, form);
+                          colour, form, none);
         });
     });
 }
@@ -787,7 +798,9 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
                               dither_args(dither)))
         return rc;
     if (p.readback && p.use > 0)
-        if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, d_counts, order_args(order, g))) return rc;
+        if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, d_counts, order_args(order, g),
+                                     svs::ColourParams{}, SVS_RB_GRAY, coeffs, dither_args(dither)))
+            return rc;
     if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
 }
@@ -1156,6 +1169,46 @@ int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const sv
                                &sel, &n_ac))
         return rc;
     return extract_host(gray, planes, order, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out, sel, dither);
+}
+
+// The dithered calls with the read-back pass.  order, coeffs and dither may each be NULL here: a NULL dither is the selected
+// call with read-back, all three NULL (or a prefix selection alone) svs_embed_readback* itself.  What is given is checked as
+// the dithered calls check it, before anything else; SVS_READBACK is accepted and implied.
+static int keyed_readback_args(const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither, uint32_t flags,
+                               svs::CoeffTable *table, const svs::CoeffTable **sel, int *n_ac) {
+    if (dither)
+        if (int rc = check_dither(dither, order)) return rc;
+    *sel = nullptr;
+    if (coeffs) {
+        if (int rc = check_coeffs(coeffs, table, sel)) return rc;
+        *n_ac = coeffs->count;
+    }
+    if (flags & ~(kSelectEmbedFlags | SVS_READBACK))
+        return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a dithered read-back embed takes the mode bits, SVS_NEAREST, SVS_MINMOVE and SVS_READBACK", flags);
+    return SVS_OK;
+}
+
+int svs_embed_dithered_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                                    const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
+                                    const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                                    uint64_t *n_embedded, uint64_t *d_counts, void *stream) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = keyed_readback_args(order, coeffs, dither, flags, &table, &sel, &n_ac)) return rc;
+    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK, n_embedded,
+                     stream, d_counts, sel, dither);
+}
+
+int svs_embed_dithered_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                                const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
+                                const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                                uint64_t *n_embedded, svs_readback_counts *counts) {
+    svs::CoeffTable table;
+    const svs::CoeffTable *sel = nullptr;
+    if (int rc = keyed_readback_args(order, coeffs, dither, flags, &table, &sel, &n_ac)) return rc;
+    svs_readback_counts none;
+    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags | SVS_READBACK,
+                      n_embedded, order, counts ? counts : &none, sel, dither);
 }
 
 int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, char *bits_ascii_out,

@@ -201,4 +201,135 @@ SVS_HD uint32_t readback_step(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb,
     return repair_block<U, QM>(rx, ry, nb, hi, lo, qp) ? 1u : 2u;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The keyed forms (svs_embed_dithered_readback*, include/svsdct.h): the same check and the same search under a coefficient
+// SELECTION and a keyed DITHER.  The payload coefficients are those of a CoeffTable - the call's inverse table, or
+// make_prefix_table(n_ac) - so flat index k carries window bit slot(k) when slot(k) < nb, and with a dither the receiver
+// reads the parity of the index of c_k - d_k (dithered_parity, svs_block.hpp), d_k = dither_value(s_b, k, delta) of the
+// block's physical position.  What changes against the forms above, coefficient by coefficient:
+//   check    quant_index(c - d) & 1 against window bit slot(k)             (no dither: quant_index(c), no subtraction)
+//   target   cp = c - d;  q = quant_index(cp), moved to the neighbour on cp's side when its parity is wrong;
+//            T = (float)q * delta + d                                        (no dither: cp = c and no addition)
+// The correction, the inverse, the shift, the rounding and the acceptance rule are the ones above, masked by slot(k) < nb
+// instead of k <= nb.  All eight coefficient rows always: a selection may name any of them.  `dith` is uniform over a call
+// (wave-uniform on the device): without it no operation on d is executed, so with the prefix table these forms give the
+// bytes and status of readback_step<8, QM>.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// the two words of the inverse table that hold the slots of coefficient row u (flat indices 8u .. 8u + 7)
+struct RowSlots {
+    uint32_t w0, w1;
+    SVS_HD uint32_t slot(int v) const { return ((v < 4 ? w0 : w1) >> (8 * (v & 3))) & 0xFFu; }
+};
+SVS_HD RowSlots row_slots(const CoeffTable &t, int u) { return RowSlots{t.w[2 * u], t.w[2 * u + 1]}; }
+
+// d of coefficient row u of the block with seed s_b (computed once per block: the search reads it every iterate)
+SVS_HD void keyed_dither_row(uint32_t s_b, uint32_t u, float delta_f, float (&d)[8]) {
+#pragma unroll
+    for (int v = 0; v < 8; ++v) d[v] = dither_value(s_b, 8u * u + (uint32_t)v, delta_f);
+}
+
+template <int QM>
+SVS_HD void keyed_targets_row(const float (&c)[8], const RowSlots &rs, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp,
+                              bool dith, const float (&d)[8], float (&T)[8]) {
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const uint32_t s = rs.slot(v);
+        T[v] = 0.0f;
+        if (s < nb) {
+            const int bit = (int)window_bit_at(hi, lo, s);
+            float cp = c[v];
+            if (dith) cp = c[v] - d[v];
+            int q = quant_index<QM>(cp, qp);
+            if ((q & 1) != bit) q = cp * qp.inv_delta_f >= (float)q ? q + 1 : q - 1;
+            float t = (float)q * qp.delta_f;
+            if (dith) t = t + d[v];
+            T[v] = t;
+        }
+    }
+}
+
+SVS_HD void keyed_correction_row(const float (&T)[8], const float (&c)[8], const RowSlots &rs, uint32_t nb, float scale,
+                                 float (&e)[8]) {
+#pragma unroll
+    for (int v = 0; v < 8; ++v) e[v] = rs.slot(v) < nb ? (T[v] - c[v]) * scale : 0.0f;
+}
+
+// does the coefficient row miss a payload bit?  svs_extract_select* / svs_extract_dithered*'s own verdict
+template <int QM>
+SVS_HD bool keyed_row_misses(const float (&c)[8], const RowSlots &rs, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp,
+                             bool dith, const float (&d)[8]) {
+    bool miss = false;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const uint32_t s = rs.slot(v);
+        if (s < nb) {
+            float cp = c[v];
+            if (dith) cp = c[v] - d[v];
+            miss |= ((uint32_t)quant_index<QM>(cp, qp) & 1u) != window_bit_at(hi, lo, s);
+        }
+    }
+    return miss;
+}
+
+// one-lane forms (host emulation; the device runs the rows above on eight lanes, svs_device.hpp repair8_keyed)
+template <int QM>
+SVS_HD bool keyed_block_misses(const float (&c)[8][8], const CoeffTable &sel, uint32_t nb, uint32_t hi, uint32_t lo,
+                               const QimParams &qp, bool dith, const float (&d)[8][8]) {
+    bool miss = false;
+    for (int u = 0; u < 8; ++u) miss |= keyed_row_misses<QM>(c[u], row_slots(sel, u), nb, hi, lo, qp, dith, d[u]);
+    return miss;
+}
+
+template <int QM>
+SVS_HD bool repair_block_keyed(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, uint32_t nb, uint32_t hi, uint32_t lo,
+                               const QimParams &qp, bool dith, const float (&d)[8][8]) {
+    float c[8][8], T[8][8];
+    forward_exact(rx, ry, c);
+    for (int u = 0; u < 8; ++u) keyed_targets_row<QM>(c[u], row_slots(sel, u), nb, hi, lo, qp, dith, d[u], T[u]);
+    uint32_t px[8], py[8];
+    for (int r = 0; r < 8; ++r) { px[r] = rx[r]; py[r] = ry[r]; }
+    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
+        const float scale = 1.0f + 0.5f * (float)it;   // exact
+        float e[8][8], P[8][8], Y[8][8];
+        for (int u = 0; u < 8; ++u) keyed_correction_row(T[u], c[u], row_slots(sel, u), nb, scale, e[u]);
+        for (int x = 0; x < 8; ++x) {
+            float col[8], out[8];
+            for (int u = 0; u < 8; ++u) col[u] = e[u][x];
+            pf::dct3_8(col, out);
+            for (int y = 0; y < 8; ++y) P[y][x] = out[y];
+        }
+        float mn = 1e30f, mx = -1e30f;
+        for (int y = 0; y < 8; ++y) {
+            float row[8];
+            pf::dct3_8(P[y], row);
+            repair_add_row(px[y], py[y], row, Y[y], mn, mx);
+        }
+        const float s = repair_shift(mn, mx);
+        for (int y = 0; y < 8; ++y) repair_store_row(Y[y], s, px[y], py[y]);
+        forward_exact(px, py, c);
+        if (!keyed_block_misses<QM>(c, sel, nb, hi, lo, qp, dith, d)) {
+            for (int r = 0; r < 8; ++r) { rx[r] = px[r]; ry[r] = py[r]; }
+            return true;
+        }
+    }
+    return false;
+}
+
+// the per-block step under a selection and a dither (s_b: dither_block_seed of the block's physical position, read only
+// with dith): 0 = reads back (untouched), 1 = repaired in place, 2 = could not be repaired (untouched)
+template <int QM>
+SVS_HD uint32_t readback_step_keyed(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, uint32_t nb, uint32_t hi,
+                                    uint32_t lo, const QimParams &qp, bool dith, uint32_t s_b) {
+    float d[8][8];
+    for (int u = 0; u < 8; ++u) {
+        if (dith) keyed_dither_row(s_b, (uint32_t)u, qp.delta_f, d[u]);
+        else for (int v = 0; v < 8; ++v) d[u][v] = 0.0f;
+    }
+    float c[8][8];
+    forward_exact(rx, ry, c);
+    if (!keyed_block_misses<QM>(c, sel, nb, hi, lo, qp, dith, d)) return 0;
+    return repair_block_keyed<QM>(rx, ry, sel, nb, hi, lo, qp, dith, d) ? 1u : 2u;
+}
+
 }  // namespace svs

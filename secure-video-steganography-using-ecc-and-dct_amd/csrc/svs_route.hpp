@@ -23,7 +23,7 @@ struct RouteArgs {
     bool guarded_off;         // reaches the gray calls only
     float guard_scale, tie_scale;
     bool keyed = false;       // a keyed block order (svs_embed_ordered_dev / svs_extract_ordered_dev; gray calls only)
-    bool readback = false;    // SVS_READBACK (the gray embed calls; svs_embed_bgr_readback*)
+    bool readback = false;    // SVS_READBACK (the gray embed calls; svs_embed_bgr_readback*; svs_embed_dithered_readback*)
     bool nearest = false;     // SVS_NEAREST (every embed call)
     bool minmove = false;     // SVS_MINMOVE (every embed call)
     // a coefficient selection (svs_embed_select* / svs_extract_select*; gray calls only): NULL for none, else its table with

@@ -52,6 +52,12 @@ READBACK = os.environ.get("SVS_READBACK", "0") == "1"
 # output is the plain colour form's, byte for byte).  Refused together with SVS_BLOCK_KEY (no keyed colour form) and with
 # SVS_READBACK (one switch per path).
 READBACK_COLOUR = os.environ.get("SVS_READBACK_COLOUR", "0") == "1"
+# SVS_READBACK_KEYED=1 (opt-in): the read-back and repair under SVS_COEFFS and / or SVS_DITHER_KEY (svs_embed_dithered_readback,
+# include/svsdct.h): every payload block is read back as the receiver's selected / dithered extraction will read it, and
+# repaired where clipping or truncation lost a bit.  The gray path, with SVS_BLOCK_KEY, SVS_NEAREST and SVS_MINMOVE; with
+# neither a selection nor a dither it is SVS_READBACK's pass.  Refused together with SVS_READBACK and SVS_READBACK_COLOUR (one
+# switch per path) and with SVS_KEEP_COLOUR; with SVS_FUSED_COLOUR the host-conversion gray path runs.  The same one-line report.
+READBACK_KEYED = os.environ.get("SVS_READBACK_KEYED", "0") == "1"
 # SVS_NEAREST=1 (opt-in): a coefficient whose parity has to change moves to the nearer of its two neighbouring lattice points
 # instead of the reference's fixed direction (SVS_NEAREST, include/svsdct.h): about 2 dB more PSNR at the same delta.  The stego
 # frames are no longer the reference's pixels; the receiver does not change.  Allowed with every other switch.
@@ -66,13 +72,14 @@ MINMOVE = os.environ.get("SVS_MINMOVE", "0") == "1"
 # "zigzag:<first scan position>", "rowmajor" or a comma-separated list of num_ac_coeffs distinct flat indices in 1..63.  Unset:
 # the reference's row-major coefficients 1..num_ac_coeffs, today's bytes.  The receiver must set the same value.  The gray path
 # only (with SVS_FUSED_COLOUR the host-conversion gray path runs); refused together with SVS_KEEP_COLOUR, SVS_READBACK and
-# SVS_READBACK_COLOUR (a selection has no colour and no read-back form).  Allowed with SVS_BLOCK_KEY and SVS_NEAREST.
+# SVS_READBACK_COLOUR (a selection has no colour form; its read-back is SVS_READBACK_KEYED=1).  Allowed with SVS_BLOCK_KEY and
+# SVS_NEAREST.
 # SVS_DITHER_KEY=<integer, int(x, 0)> (read per call, opt-in): keyed dither modulation (svsdct/dither.py, include/svsdct.h) - the
 # quantiser lattice of every payload coefficient of video frame k is shifted by an offset derived from the key, k, the block and
 # the coefficient: no comb in the coefficient histogram, no bits for a receiver without the key, no distortion cost.  Unset:
 # no dither, today's bytes and routes.  The receiver must set the same value.  The gray path only (with SVS_FUSED_COLOUR the
 # host-conversion gray path runs); refused together with SVS_KEEP_COLOUR, SVS_READBACK and SVS_READBACK_COLOUR (a dithered call
-# has no colour and no read-back form).  Allowed with SVS_BLOCK_KEY, SVS_COEFFS, SVS_NEAREST and
+# has no colour form; its read-back is SVS_READBACK_KEYED=1).  Allowed with SVS_BLOCK_KEY, SVS_COEFFS, SVS_NEAREST and
 # SVS_MINMOVE.
 
 
@@ -165,6 +172,10 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if kunci_blok is not None and KEEP_COLOUR:
         print("    Error: SVS_BLOCK_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR.")
         return False, None, None
+    if READBACK_KEYED and (READBACK or READBACK_COLOUR):
+        raise ValueError("SVS_READBACK_KEYED=1 cannot be combined with SVS_READBACK=1 / SVS_READBACK_COLOUR=1: one switch per path")
+    if READBACK_KEYED and KEEP_COLOUR:
+        raise ValueError("SVS_READBACK_KEYED=1 cannot be combined with SVS_KEEP_COLOUR: the keyed read-back is the gray path's")
     if READBACK_COLOUR and READBACK:
         raise ValueError("SVS_READBACK_COLOUR=1 cannot be combined with SVS_READBACK=1: one switch per path")
     if READBACK_COLOUR and kunci_blok is not None:
@@ -200,7 +211,8 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     print(f"    Video output akan disimpan sebagai '{path_out}' (Codec: FFV1).")
 
     tabel_warna = None
-    if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None and pilihan is None and kunci_dither is None:   # keyed order, selection, dither: the host-conversion gray path
+    if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None and pilihan is None and kunci_dither is None \
+            and not READBACK_KEYED:   # keyed order, selection, dither, keyed read-back: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -229,6 +241,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         print("    Info: kisi kuantisasi digeser dengan dither berkunci (SVS_DITHER_KEY).")
         terdekat = dict(terdekat, dither_key=kunci_dither)         # likewise
     readback_abu = READBACK or (READBACK_COLOUR and not tabel_warna)   # the gray pipeline's read-back
+    rb_pipa = {"readback_keyed": True} if READBACK_KEYED else ({"readback": True} if readback_abu else {})
 
     def lapor_readback(diperbaiki, tersisa):
         print(f"    Read-back: {diperbaiki} blok diperbaiki, {tersisa} blok tidak dapat diperbaiki.")
@@ -297,7 +310,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         n_batches = PIPELINE_DEPTH if carrying is None else -(-carrying // per_batch)
         with FramePipeline(out_h, out_w, per_batch, delta_kuantisasi, num_ac_coeffs,
                            depth=max(1, min(PIPELINE_DEPTH, n_batches)), mode=_batch.host_level_mode(),
-                           **_keyed(block_key=kunci_blok), **({"readback": True} if readback_abu else {}),
+                           **_keyed(block_key=kunci_blok), **rb_pipa,
                            **terdekat) as pipe:
             pipe.set_payload(payload)
             rencana = {"sisa": carrying}
@@ -328,7 +341,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
                         raise RuntimeError(f"embed kernel consumed {used} bits, expected {expect}")
                     tulis(pipe.input(slot)[:n], pipe.embed_result(slot))
                     feeder.release(slot)
-            if readback_abu:
+            if rb_pipa:
                 rb = pipe.readback_counts()
                 lapor_readback(rb.repaired, rb.unrepaired)
     disisipkan = state["disisipkan"]

@@ -134,7 +134,8 @@ def block_order(key, first_frame: int = 0) -> BlockOrder | None:
     return BlockOrder(check_key(key), first_frame, 0)
 
 
-def _order_ref(order: BlockOrder | None):
+def _order_ref(order):
+    """a pointer to an optional struct argument (svs_block_order, svs_dither), NULL for None"""
     return C.byref(order) if order is not None else None
 
 
@@ -145,7 +146,7 @@ def _coeffs_arg(coeffs, n_ac, readback=False):
     if sel is None:
         return None
     if readback:
-        raise ValueError("a coefficient selection has no read-back form (readback=True)")
+        raise ValueError("a coefficient selection has no read-back form under readback=True: use readback_keyed=True")
     return _coeffs.native_coeffs(sel)
 
 
@@ -160,12 +161,12 @@ def _no_coeffs(coeffs):
 
 def dither_arg(dither_key, first_frame: int = 0, readback: bool = False) -> Dither | None:
     """the C ABI's svs_dither for a dither key (None: no dither); raises unless 0 <= key < 2**64 and 0 <= first_frame < 2**32,
-    and with readback (a dithered call has no read-back form)"""
+    and with readback (the dithered call with read-back is readback_keyed's)"""
     if dither_key is None:
         return None
     key = _dither.check_key(dither_key)
     if readback:
-        raise ValueError("a keyed dither has no read-back form (readback=True)")
+        raise ValueError("a keyed dither has no read-back form under readback=True: use readback_keyed=True")
     first_frame = int(first_frame)
     if not 0 <= first_frame < (1 << 32):
         raise ValueError(f"first_frame {first_frame} outside 0 .. 2**32 - 1")
@@ -178,6 +179,12 @@ def no_dither(dither_key, what: str) -> None:
         raise ValueError(f"a keyed dither has no {what} form: use the gray calls with packed bits")
 
 
+def _one_readback(readback, readback_keyed):
+    """one switch per path: readback is SVS_READBACK's, readback_keyed svs_embed_dithered_readback*'s"""
+    if readback and readback_keyed:
+        raise ValueError("readback and readback_keyed are two paths: set one of them")
+
+
 class ReadbackCounts(NamedTuple):
     """what an SVS_READBACK embed did: blocks that did not read back and were repaired / kept the reference's bytes"""
     repaired: int
@@ -186,7 +193,7 @@ class ReadbackCounts(NamedTuple):
 
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
-                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None):
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
@@ -212,10 +219,16 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     receiver without the key, no distortion cost.  It shares first_frame with block_key and combines with block_key, coeffs,
     nearest, minmove and mode (a dithered call runs the exact kernels in every mode); ValueError with readback.  The receiver
     must use the same key.
-    Returns (stego uint8 [F,H,W], n_embedded), with readback (stego, n_embedded, ReadbackCounts)."""
+    readback_keyed : opt-in (svs_embed_dithered_readback, include/svsdct.h): the read-back and repair under coeffs and / or
+    dither_key - every payload block is read back with the selected / dithered extraction's own verdict and repaired where it
+    fails.  With neither it makes the readback call.  ValueError together with readback.
+    Returns (stego uint8 [F,H,W], n_embedded), with readback or readback_keyed (stego, n_embedded, ReadbackCounts)."""
+    _one_readback(readback, readback_keyed)
     order = block_order(block_key, first_frame)
     sel = _coeffs_arg(coeffs, n_ac, readback)
     dith = dither_arg(dither_key, first_frame, readback)
+    if readback_keyed and sel is None and dith is None:
+        readback = True
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -231,6 +244,14 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     stego = pinned_empty(stack.shape)      # page-locked: the download lands in it by DMA, no staging copy, no page faults
     done = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
+    if readback_keyed and not readback:
+        counts = native.ReadbackCounts()
+        rc = lib.svs_embed_dithered_readback(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order),
+                                             _coeffs_ref(sel), _order_ref(dith), float(delta), int(n_ac), packed.ctypes.data,
+                                             int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done),
+                                             C.byref(counts))
+        native.check(rc, "svs_embed_dithered_readback")
+        return stego, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
     if dith is not None:
         rc = lib.svs_embed_dithered(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
                                     C.byref(dith), float(delta), int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits),
@@ -376,18 +397,30 @@ def _shared_first_frame(order: BlockOrder | None, first_frame: int | None) -> in
 def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_packed: int,
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
-                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, first_frame: int | None = None) -> int:
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, first_frame: int | None = None,
+                 readback_keyed: bool = False) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
     native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
     read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
     it adds {repaired, unrepaired} into.  nearest, minmove: SVS_NEAREST, SVS_MINMOVE, as embed_frames.  coeffs: a payload coefficient selection,
     as embed_frames (svs_embed_select_dev).  dither_key: a keyed dither, as embed_frames (svs_embed_dithered_dev); its clip
-    frame index is first_frame, by default the order's (0 without one) - the two must agree."""
+    frame index is first_frame, by default the order's (0 without one) - the two must agree.  readback_keyed: the read-back
+    pass under coeffs and / or dither_key (svs_embed_dithered_readback_dev; d_counts as with readback); with neither it makes
+    the readback call; ValueError together with readback."""
+    _one_readback(readback, readback_keyed)
     done = C.c_uint64(0)
     flags = embed_flags(mode, nearest, minmove)
     sel = _coeffs_arg(coeffs, n_ac, readback)
     dith = dither_arg(dither_key, _shared_first_frame(order, first_frame), readback)
-    if dith is not None:
+    if readback_keyed and sel is None and dith is None:
+        readback = True
+    if readback_keyed and not readback:
+        rc = native.load().svs_embed_dithered_readback_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
+                                                           _order_ref(dith), float(delta), int(n_ac), d_bits_packed,
+                                                           int(bit_offset), int(n_bits), flags, C.byref(done),
+                                                           d_counts or None, stream or None)
+        native.check(rc, "svs_embed_dithered_readback_dev")
+    elif dith is not None:
         rc = native.load().svs_embed_dithered_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
                                                   C.byref(dith), float(delta), int(n_ac), d_bits_packed, int(bit_offset),
                                                   int(n_bits), flags, C.byref(done), stream or None)

@@ -4,7 +4,7 @@ Without a selection the payload of a block goes into flat row-major coefficients
 n = 3 only the horizontal frequencies (0,1), (0,2), (0,3) carry bits.  A selection is an ordered list of distinct flat
 row-major indices in 1..63 (index 8*u + v: vertical frequency u, horizontal v; DC is never selectable): stream bit i of a block
 goes to coefficient index[i].  Sender and receiver must agree on it.  A selection that is the prefix 1..n is the call without
-one; any other runs the lane-per-block exact kernels, and has no read-back and no colour form.
+one; any other runs the lane-per-block exact kernels, has no colour form, and is read back and repaired by readback_keyed (svs_embed_dithered_readback*).
 """
 from __future__ import annotations
 

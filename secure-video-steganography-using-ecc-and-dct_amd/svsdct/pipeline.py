@@ -50,7 +50,7 @@ def _device(nbytes: int):
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
-                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None):
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
@@ -58,14 +58,17 @@ class FramePipeline:
         only as far as its decision cell asks (SVS_MINMOVE, include/svsdct.h).  coeffs: None or a payload coefficient selection
         for every batch, as batch.embed_frames (resolved once with n_ac; ValueError with readback).  dither_key: None or the
         key of a keyed dither for every batch (svsdct/dither.py; ValueError with readback); each submit's first frame index
-        feeds both the order and the dither."""
+        feeds both the order and the dither.  readback_keyed: every embed batch is read back and repaired under coeffs and / or
+        dither_key (svs_embed_dithered_readback_dev, include/svsdct.h; with neither: the readback call); readback_counts()
+        gives the totals; ValueError together with readback."""
+        batch._one_readback(readback, readback_keyed)
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
         self.block_key = batch.block_order(block_key).key if block_key is not None else None
         self.coeffs = _coeffs.selection(coeffs, batch.clamp_ac(n_ac))
         self.dither_key = batch.dither_arg(dither_key, 0, readback).key if dither_key is not None else None
         if self.coeffs is not None and readback:
-            raise ValueError("a coefficient selection has no read-back form (readback=True)")
+            raise ValueError("a coefficient selection has no read-back form under readback=True: use readback_keyed=True")
         native.ensure_device(device)
         self.lib = native.load()
         self.device = device
@@ -89,10 +92,11 @@ class FramePipeline:
         self._d_payload = None
         self._payload_bits = 0
         self.readback = bool(readback)
+        self.readback_keyed = bool(readback_keyed)
         self.nearest = bool(nearest)
         self.minmove = bool(minmove)
         self._d_counts = None
-        if self.readback:   # {repaired, unrepaired} of every batch, added to on the device
+        if self.readback or self.readback_keyed:   # {repaired, unrepaired} of every batch, added to on the device
             self._d_counts = _device(16)
             native.check(self.lib.svs_memset(self._d_counts, 0, 16, None), "svs_memset")
             native.check(self.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
@@ -128,6 +132,10 @@ class FramePipeline:
         """the keywords of a dithered submit: none at all without a key, so the other submits make the calls they made"""
         return {} if self.dither_key is None else {"dither_key": self.dither_key, "first_frame": first_frame}
 
+    def _readback(self) -> dict:
+        """the read-back keyword of an embed submit: one switch per path, and only the one that is on"""
+        return {"readback_keyed": True} if self.readback_keyed else {"readback": self.readback}
+
     def submit_embed(self, slot: int, n_frames: int, bit_offset: int, first_frame: int = 0) -> int:
         """Enqueue H2D -> embed -> D2H for the first n_frames frames of the slot; returns the bits this batch
         will carry.  Does not wait.  first_frame: clip index of the batch's first frame (keyed block order)."""
@@ -138,7 +146,7 @@ class FramePipeline:
         used = batch.embed_device(s["d_frames"].value, s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac,
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
                                   stream=s["stream"].value, mode=self.mode, order=self._order(first_frame),
-                                  readback=self.readback, d_counts=self._d_counts.value if self._d_counts else 0,
+                                  **self._readback(), d_counts=self._d_counts.value if self._d_counts else 0,
                                   nearest=self.nearest, coeffs=self.coeffs, minmove=self.minmove, **self._dither(first_frame))
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
@@ -171,7 +179,7 @@ class FramePipeline:
 
     def readback_counts(self) -> "batch.ReadbackCounts":
         """(repaired, unrepaired) blocks over every embed batch submitted so far (waits for all slots)"""
-        if not self.readback:
+        if not (self.readback or self.readback_keyed):
             raise RuntimeError("the pipeline was created without readback")
         for s in self._slots:
             native.check(self.lib.svs_stream_synchronize(s["stream"]), "svs_stream_synchronize")
