@@ -1,17 +1,12 @@
 """Helpers of the coefficient-selection tests (tests/test_coeff_select_cpu.py, tests/test_coeff_select_gpu.py): the restatement -
 oracle.frame_embed / frame_extract_bits with ONE lookup changed (stream bit i of a block goes to coefficient index[i] instead
 of 1 + i) and an optional nearest rule, built from the oracle's own pieces -, a literal per-block loop form, the zig-zag table
-written out (not derived by the code under test), and the host build of the block bodies (tests/coeffs/coeffs_shim.cpp)."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
+written out (not derived by the code under test), and the host build of the block bodies (tests/hostemu)."""
 import numpy as np
 from scipy.fftpack import dct, idct
 
 from oracle.qim_dct_oracle import (BLOCK, _blocks_view, _check_plane, _fwd, _inv, _quant_index, _requantised, bits_from_any)
-from testlib import CSRC, REPO
+from testlib import host_embed_call, host_extract_call, hostemu
 
 # JPEG zig-zag scan of an 8 x 8 block, flat row-major indices, position 0 = DC (ITU-T T.81 figure A.6)
 ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10,
@@ -181,70 +176,29 @@ def payload(n_bits, seed=3):
     return np.random.default_rng(seed).integers(0, 2, n_bits).astype(np.uint8)
 
 
-# ---- host build of the block bodies ----------------------------------------------------------------------------------
-_SHIM = None
-
-
-def shim():
-    global _SHIM
-    if _SHIM is None:
-        src = os.path.join(REPO, "tests", "coeffs", "coeffs_shim.cpp")
-        out = os.path.join(tempfile.mkdtemp(prefix="svs_coeffs_"), "libcs.so")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src,
-                               "-o", out])
-        lib = C.CDLL(out)
-        lib.cs_embed.restype = C.c_int64
-        lib.cs_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_void_p,
-                                 C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
-        lib.cs_extract.restype = C.c_int64
-        lib.cs_extract.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                   C.c_void_p]
-        lib.cs_table.restype = C.c_int
-        lib.cs_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        _SHIM = lib
-    return _SHIM
-
-
-def _index_arg(index):
-    return np.ascontiguousarray(np.asarray(index, np.int64).reshape(-1).astype(np.uint8))
+# ---- the block bodies on the host (tests/hostemu) ---------------------------------------------------------------------
+def _plan(res):
+    return dict(path=int(res.path), rows=int(res.rows), selected=int(res.selected), qm=int(res.qm))
 
 
 def host_embed(frames, delta, index, bits, bit_offset=0, n_bits=None, flags=0, nearest=False):
     """a select embed call through the product headers on the host (svs_route.hpp's plan, svs_block.hpp's bodies)
-    -> (stego, bits embedded, plan dict)"""
-    frames = np.ascontiguousarray(frames)
-    f, h, w = frames.shape
-    bits = np.asarray(bits, np.uint8)
-    if n_bits is None:
-        n_bits = bits.size - bit_offset
-    packed = np.packbits(bits)
-    packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
-    idx = _index_arg(index)
-    out = np.empty_like(frames)
-    info = np.zeros(4, np.int64)
-    used = shim().cs_embed(frames.ctypes.data, out.ctypes.data, f, h, w, float(delta), idx.ctypes.data, idx.size,
-                           packed.ctypes.data, packed.size, int(bit_offset), int(n_bits), int(flags), int(nearest),
-                           info.ctypes.data)
-    assert used >= 0, "the shim refused the selection"
-    return out, int(used), dict(path=int(info[0]), rows=int(info[1]), selected=int(info[2]), qm=int(info[3]))
+    -> (stego, bits embedded, plan dict).  Always with the exact arithmetic: a plan without the table (a prefix selection)
+    streams, and the streaming bodies give the same bytes and have tests of their own."""
+    out, res, _ = host_embed_call(frames, delta, 0, bits, bit_offset=bit_offset, n_bits=n_bits, index=index, pocketfft=flags & 1,
+                                  guarded=flags & 2, nearest=int(nearest), streaming_bodies=0)
+    return out, int(res.used), _plan(res)
 
 
 def host_extract(frames, delta, index, flags=0):
     """a select extract call on the host -> (0/1 bits, plan dict)"""
-    frames = np.ascontiguousarray(frames)
-    f, h, w = frames.shape
-    idx = _index_arg(index)
-    out = np.zeros(f * (h // 8) * (w // 8) * max(idx.size, 1), np.uint8)
-    info = np.zeros(4, np.int64)
-    n = shim().cs_extract(frames.ctypes.data, f, h, w, float(delta), idx.ctypes.data, idx.size, int(flags), out.ctypes.data,
-                          info.ctypes.data)
-    assert n >= 0, "the shim refused the selection"
-    return out[:n], dict(path=int(info[0]), rows=int(info[1]), selected=int(info[2]), qm=int(info[3]))
+    out, res, _ = host_extract_call(frames, delta, 0, index=index, pocketfft=flags & 1, guarded=flags & 2, streaming_bodies=0)
+    return out, _plan(res)
 
 
 def host_table(index):
     """svs::make_coeff_table -> (valid, slot[64], count)"""
-    idx = _index_arg(index) if len(index) else np.zeros(1, np.uint8)
+    idx = np.ascontiguousarray(np.asarray(index, np.int64).reshape(-1).astype(np.uint8)) if len(index) else np.zeros(1, np.uint8)
     out = np.zeros(65, np.int32)
-    ok = shim().cs_table(idx.ctypes.data, len(index), out.ctypes.data)
+    ok = hostemu().cs_table(idx.ctypes.data, len(index), out.ctypes.data)
     return bool(ok), out[:64].copy(), int(out[64])

@@ -2,18 +2,13 @@
 extract of coeff_select_lib / minmove_lib with the three changes of the rule (include/svsdct.h) written out: the quantiser sees
 c - d, the written value is moved back by d unless the rule left c - d alone, and the receiver reads the parity of the index of
 c - d -, the hash restated here (svsdct/dither.py is code under test and is imported for nothing), and the host build of the
-dithered block bodies of csrc/svs_block.hpp (tests/dither/dither_shim.cpp)."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
+dithered block bodies of csrc/svs_block.hpp (tests/hostemu)."""
 import numpy as np
 
 from minmove_lib import band
 from oracle.qim_dct_oracle import (BLOCK, MAX_AC, _blocks_view, _check_plane, _fwd, _inv, _quant_index, _requantised,
                                    bits_from_any)
-from testlib import CSRC, REPO
+from testlib import host_embed_call, host_extract_call, hostemu
 
 RULES = ("reference", "nearest", "minmove")
 M32 = 0xFFFFFFFF
@@ -198,76 +193,28 @@ def psnr(a, b):
     return float("inf") if e == 0 else 10 * np.log10(255.0 ** 2 * a.size / e)
 
 
-# ---- host build of the dithered block bodies ---------------------------------------------------------------------------
-_SHIM = None
-
-
-def shim():
-    global _SHIM
-    if _SHIM is None:
-        src = os.path.join(REPO, "tests", "dither", "dither_shim.cpp")
-        out = os.path.join(tempfile.mkdtemp(prefix="svs_dither_"), "libdt.so")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src,
-                               "-o", out])
-        lib = C.CDLL(out)
-        lib.dt_hash.restype = C.c_float
-        lib.dt_hash.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
-        lib.dt_embed.restype = C.c_uint64
-        lib.dt_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_int,
-                                 C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int,
-                                 C.c_void_p]
-        lib.dt_extract.restype = C.c_int64
-        lib.dt_extract.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_uint64,
-                                   C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-        _SHIM = lib
-    return _SHIM
-
-
+# ---- the dithered block bodies on the host (tests/hostemu) -------------------------------------------------------------
 def host_hash(key, t, i, k, delta=1.0):
     """-> (seed, s_b, h, d) of the product header"""
     out = np.zeros(3, np.uint32)
-    d = shim().dt_hash(int(key), int(t), int(i), int(k), float(delta), out.ctypes.data)
+    d = hostemu().dt_hash(int(key), int(t), int(i), int(k), float(delta), out.ctypes.data)
     return int(out[0]), int(out[1]), int(out[2]), np.float32(d)
 
 
-def _index_arg(index):
-    return np.zeros(1, np.uint8) if index is None else np.ascontiguousarray(np.asarray(index, np.int64).astype(np.uint8))
-
-
-def _info(info):
-    return dict(path=int(info[0]), rows=int(info[1]), selected=int(info[2]), qm=int(info[3]), dithered=int(info[4]))
+def _plan(res):
+    return dict(path=int(res.path), rows=int(res.rows), selected=int(res.selected), qm=int(res.qm), dithered=int(res.dithered))
 
 
 def host_embed(frames, delta, n_ac, bits, key, first_frame=0, rule="reference", index=None, bit_offset=0, n_bits=None, flags=0):
     """a dithered gray embed call through the product headers on the host -> (stego, bits embedded, plan dict)"""
-    frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
-    f, h, w = frames.shape
-    bits = np.asarray(bits, np.uint8)
-    if n_bits is None:
-        n_bits = bits.size - bit_offset
-    packed = np.packbits(bits)
-    packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
-    idx = _index_arg(index)
-    out = np.empty_like(frames)
-    info = np.zeros(5, np.int64)
-    used = shim().dt_embed(frames.ctypes.data, out.ctypes.data, f, h, w, float(delta), int(n_ac), idx.ctypes.data,
-                           0 if index is None else idx.size, int(key), int(first_frame), packed.ctypes.data, packed.size,
-                           int(bit_offset), int(n_bits), int(flags), int(rule == "nearest"), int(rule == "minmove"),
-                           info.ctypes.data)
-    assert used != 2 ** 64 - 1, "the shim refused the selection"
-    return out, int(used), _info(info)
+    out, res, _ = host_embed_call(frames, delta, n_ac, bits, bit_offset=bit_offset, n_bits=n_bits, index=index,
+                                  pocketfft=flags & 1, guarded=flags & 2, nearest=int(rule == "nearest"),
+                                  minmove=int(rule == "minmove"), dither_key=int(key), first_frame=int(first_frame))
+    return out, int(res.used), _plan(res)
 
 
 def host_extract(frames, delta, n_ac, key, first_frame=0, index=None, flags=0):
     """a dithered gray extract call on the host -> (0/1 bits, plan dict)"""
-    frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
-    f, h, w = frames.shape
-    idx = _index_arg(index)
-    n = idx.size if index is not None else max(0, min(int(n_ac), 63))
-    out = np.zeros(f * (h // 8) * (w // 8) * max(n, 1), np.uint8)
-    info = np.zeros(5, np.int64)
-    got = shim().dt_extract(frames.ctypes.data, f, h, w, float(delta), int(n_ac), idx.ctypes.data,
-                            0 if index is None else idx.size, int(key), int(first_frame), int(flags), out.ctypes.data,
-                            info.ctypes.data)
-    assert got >= 0, "the shim refused the selection"
-    return out[:got], _info(info)
+    out, res, _ = host_extract_call(frames, delta, n_ac, index=index, pocketfft=flags & 1, guarded=flags & 2, dither_key=int(key),
+                                    first_frame=int(first_frame))
+    return out, _plan(res)

@@ -4,7 +4,7 @@
 For one block under a setting (n, delta, its payload window), s* is the largest guard scale at which the cheap path keeps
 the block and its pixels differ from the exact (pocketfft-identical) arithmetic; 0 for a block whose cheap result is right
 at any scale.  t* is the same for extraction and the tie margin.  Both are found by bisection over float32 scales on
-hostemu (tests/hostemu: emu_set_guard_scale / emu_set_tie_scale), so that "differs at scale x" is exactly "x <= s*".
+hostemu (tests/hostemu: testlib.emu_scales), so that "differs at scale x" is exactly "x <= s*".
 
 Search: random blocks of several content classes and the blocks of testlib.structured_covers, then a hill-climb on +-1
 pixel moves that keeps every move not lowering s* (t*).  The best blocks per setting are placed into 544 x 960 frames so

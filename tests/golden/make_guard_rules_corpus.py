@@ -3,7 +3,7 @@ the streaming embed kernels under SVS_NEAREST and SVS_MINMOVE (their own copies 
 
 Per setting (kernel family x rule) ONE frame of 128 rows, built from two kinds of blocks:
 
-* dense-replay blocks: sampled blocks that the host build of the bodies (tests/minmove/minmove_shim.cpp, the library's route and
+* dense-replay blocks: sampled blocks that the host build of the bodies (tests/hostemu through minmove_lib.host_embed, the library's route and
   rule word, RouteArgs::guard_scale) leaves undecided at guard scale 1.  No search.  Wave k of 64 blocks (128 in the
   two-blocks-per-lane form) holds 1, 8, 31, 32, 33, 64 (128) of them at random lanes, every further wave one: the wave
   worklist and the pooled 8-lane replay run with one entry, full, half full and across the 32 / 33 split under a rule.

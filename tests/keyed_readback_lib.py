@@ -1,17 +1,12 @@
 """Helpers of the keyed read-back tests (tests/test_keyed_readback_cpu.py, tests/test_keyed_readback_gpu.py): the host build of
-the keyed forms of csrc/svs_readback.hpp (tests/keyed_readback/keyed_readback_shim.cpp) and a NumPy model of the same check and
+the keyed forms of csrc/svs_readback.hpp (tests/hostemu) and a NumPy model of the same check and
 repair under a coefficient selection and a keyed dither, restated with the oracle's transforms and dither_lib's hash."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
 import numpy as np
 
 import dither_lib
 from oracle.qim_dct_oracle import _blocks_view, _fwd, _inv, _quant_index
 from readback_lib import ITERS, content
-from testlib import CSRC, REPO
+from testlib import host_readback_call
 
 ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
@@ -59,48 +54,15 @@ def table_case(kind, delta, index, dither, rule):
     return bits, stego, key
 
 
-# ---- host build of the keyed forms -------------------------------------------------------------------------------------
-_SHIM = None
-
-
-def shim():
-    global _SHIM
-    if _SHIM is None:
-        src = os.path.join(REPO, "tests", "keyed_readback", "keyed_readback_shim.cpp")
-        out = os.path.join(tempfile.mkdtemp(prefix="svs_keyed_readback_"), "libkrb.so")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src,
-                               "-o", out])
-        lib = C.CDLL(out)
-        lib.krb_readback.restype = C.c_uint64
-        lib.krb_readback.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                     C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
-                                     C.c_void_p, C.c_void_p]
-        _SHIM = lib
-    return _SHIM
-
-
+# ---- the keyed forms on the host (tests/hostemu) ---------------------------------------------------------------------
 def host_readback(stego, delta, n_ac, bits, index=None, dither_key=None, block_key=None, first_frame=0, bit_offset=0,
                   n_bits=None):
     """the keyed read-back pass on the host over the stego of the same call without read-back -> (stego after the pass,
     (repaired, unrepaired), status per physical block: 0 reads back, 1 repaired, 2 left, 3 carries no payload).  index None:
-    the row-major prefix 1..n_ac."""
-    frames = np.array(stego if stego.ndim == 3 else stego[None], np.uint8, order="C")
-    f, h, w = frames.shape
-    bits = np.asarray(bits, np.uint8)
-    if n_bits is None:
-        n_bits = bits.size - bit_offset
-    packed = np.packbits(bits)
-    packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
-    idx = np.zeros(1, np.uint8) if index is None else np.ascontiguousarray(np.asarray(index, np.int64).astype(np.uint8))
-    counts = np.zeros(2, np.uint64)
-    status = np.zeros(f * (h // 8) * (w // 8), np.uint8)
-    used = shim().krb_readback(frames.ctypes.data, f, h, w, float(delta), int(n_ac), idx.ctypes.data,
-                               0 if index is None else idx.size, int(dither_key is not None), int(dither_key or 0),
-                               int(block_key is not None), int(block_key or 0), int(first_frame), packed.ctypes.data,
-                               packed.size, int(bit_offset), int(n_bits), counts.ctypes.data, status.ctypes.data)
-    assert used != 2 ** 64 - 1, "the shim refused the selection"
-    out = frames if stego.ndim == 3 else frames[0]
-    return out, (int(counts[0]), int(counts[1])), status
+    the row-major prefix 1..n_ac.  Always the keyed forms (readback_step_keyed), also for a prefix without a dither, so that
+    the tests can hold them to readback_step there."""
+    return host_readback_call(stego, delta, n_ac, bits, index=index, dither_key=dither_key, block_key=block_key,
+                              first_frame=int(first_frame), bit_offset=bit_offset, n_bits=n_bits, keyed_form=1)
 
 
 # ---- NumPy model ---------------------------------------------------------------------------------------------------------

@@ -1,18 +1,13 @@
 """Helpers of the SVS_MINMOVE tests (tests/test_minmove_cpu.py, tests/test_minmove_gpu.py): the NumPy model of the minimum-move
 embed - nearest_lib.model_embed with the one assignment changed to the clamp of include/svsdct.h, and the coefficient lookup of
 coeff_select_lib.select_embed so that one model serves the prefix and a selection -, the margin table recomputed from its
-definition, and the host build of the embed bodies of csrc/svs_block.hpp with the flag (tests/minmove/minmove_shim.cpp)."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
+definition, and the host build of the embed bodies of csrc/svs_block.hpp with the flag (tests/hostemu)."""
 import numpy as np
 
 from nearest_lib import content, payload, sse  # noqa: F401  (the content classes and seeds the feature was measured on)
 from oracle.qim_dct_oracle import (BLOCK, MAX_AC, _blocks_view, _check_plane, _fwd, _inv, _quant_index, _requantised,
                                    bits_from_any)
-from testlib import CSRC, REPO
+from testlib import host_embed_call, hostemu
 
 DELTAS = (8, 20, 40, 7.3, 12.5, 5000.3)       # QM_POW2, QM_F32, QM_F32, QM_DOUBLE, QM_F32, and a QM_DOUBLE step on the exact route
 N_ACS = (1, 3, 7, 8, 10, 15, 16, 63)
@@ -127,69 +122,28 @@ def psnr(a, b):
     return float("inf") if e == 0 else 10 * np.log10(255.0 ** 2 * a.size / e)
 
 
-# ---- host build of the embed bodies ------------------------------------------------------------------------------------
-_SHIM = None
-
-
-def shim():
-    global _SHIM
-    if _SHIM is None:
-        src = os.path.join(REPO, "tests", "minmove", "minmove_shim.cpp")
-        out = os.path.join(tempfile.mkdtemp(prefix="svs_minmove_"), "libmm.so")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src,
-                               "-o", out])
-        lib = C.CDLL(out)
-        lib.mm_embed.restype = C.c_uint64
-        lib.mm_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_int,
-                                 C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        lib.mm_embed_scaled.restype = C.c_uint64
-        lib.mm_embed_scaled.argtypes = lib.mm_embed.argtypes + [C.c_float, C.c_void_p]
-        lib.mm_plan.restype = None
-        lib.mm_plan.argtypes = [C.c_double, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        lib.mm_margin.restype = C.c_float
-        lib.mm_margin.argtypes = [C.c_int]
-        lib.mm_coefficient.restype = None
-        lib.mm_coefficient.argtypes = [C.c_float, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
-        _SHIM = lib
-    return _SHIM
-
-
+# ---- the embed bodies on the host (tests/hostemu) ---------------------------------------------------------------------
 def host_embed(frames, delta, n_ac, bits, bit_offset=0, n_bits=None, pocketfft=False, minmove=True, nearest=False, index=None,
                qm=-1, guard_scale=None, replay_map=False):
     """a gray embed call through the product headers on the host -> (stego, bits embedded, info dict: `replayed` blocks, `path`,
-    the plan's `minmove`, `nearest` and `qm`, the rule `word`).  guard_scale: RouteArgs::guard_scale, as SVS_GUARD_SCALE of the
-    experiments library (None: the product's guard).  replay_map=True: info gains `replay_map`, bool per block of the call in
-    raster order - the guard handed the block to the exact replay."""
-    frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
-    f, h, w = frames.shape
-    bits = np.asarray(bits, np.uint8)
-    if n_bits is None:
-        n_bits = bits.size - bit_offset
-    packed = np.packbits(bits)
-    packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
-    idx = np.zeros(1, np.uint8) if index is None else np.ascontiguousarray(np.asarray(index, np.int64).astype(np.uint8))
-    out = np.empty_like(frames)
-    info = np.zeros(6, np.uint64)
-    args = (frames.ctypes.data, out.ctypes.data, f, h, w, float(delta), int(n_ac), idx.ctypes.data,
-            0 if index is None else idx.size, packed.ctypes.data, packed.size, int(bit_offset), int(n_bits),
-            int(pocketfft), int(nearest), int(minmove), int(qm), info.ctypes.data)
-    rmap = np.zeros(f * (h // 8) * (w // 8), np.uint8) if replay_map else None
-    if guard_scale is None and rmap is None:
-        used = shim().mm_embed(*args)
-    else:
-        used = shim().mm_embed_scaled(*args, 1.0 if guard_scale is None else float(guard_scale),
-                                      None if rmap is None else rmap.ctypes.data)
-    assert used != 2 ** 64 - 1, "the shim refused the selection"
-    res = dict(replayed=int(info[0]), path=int(info[1]), minmove=int(info[2]), nearest=int(info[3]), qm=int(info[4]),
-               word=int(info[5]))
-    if rmap is not None:
-        res["replay_map"] = rmap.astype(bool)
-    return out, int(used), res
+    the plan's `minmove`, `nearest` and `qm`, the rule `word`).  The exact body is the instantiation the plan names (1, 2 or 8
+    coefficient rows).  guard_scale: RouteArgs::guard_scale, as SVS_GUARD_SCALE of the experiments library (None: the product's
+    guard).  replay_map=True: info gains `replay_map`, bool per block of the call in raster order - the guard handed the block
+    to the exact replay."""
+    out, res, rmap = host_embed_call(frames, delta, n_ac, bits, bit_offset=bit_offset, n_bits=n_bits, index=index,
+                                     pocketfft=pocketfft, guarded=not pocketfft, nearest=int(nearest), minmove=int(minmove),
+                                     force_qm=int(qm), exact_rows=0, guard_scale=1.0 if guard_scale is None else float(guard_scale))
+    info = dict(replayed=int(res.replayed), path=int(res.path), minmove=int(res.minmove), nearest=int(res.nearest), qm=int(res.qm),
+                word=int(res.word))
+    if replay_map:
+        info["replay_map"] = rmap
+    return out, int(res.used), info
 
 
 def plan(delta, n_ac, total, n_bits, pocketfft=False, bgr=False, minmove=True, nearest=False):
     """-> (path, minmove, use, half_cell as float32, rule word) of csrc/svs_route.hpp plan_embed"""
-    out = np.zeros(5, np.int64)
-    shim().mm_plan(float(delta), int(n_ac), int(total), int(n_bits), int(pocketfft), int(bgr), int(nearest), int(minmove),
-                   out.ctypes.data)
-    return int(out[0]), int(out[1]), int(out[2]), np.array([out[3]], np.uint32).view(np.float32)[0], int(out[4])
+    out = np.zeros(6, np.int64)
+    hostemu().emu_plan_rule(float(delta), int(n_ac), int(total), int(n_bits), int(pocketfft), int(bgr), int(nearest), int(minmove),
+                            out.ctypes.data)
+    return int(out[0]), int(out[2]), int(out[3]), np.array([out[4]], np.uint32).view(np.float32)[0], int(out[5])
+

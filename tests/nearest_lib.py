@@ -1,16 +1,11 @@
 """Helpers of the SVS_NEAREST tests (tests/test_nearest_cpu.py, tests/test_nearest_gpu.py): the NumPy model of the nearest-parity
 embed, built from the oracle's own pieces, the content classes the feature was measured on, and the host build of the embed
-bodies of csrc/svs_block.hpp with the flag (tests/nearest/nearest_shim.cpp)."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
+bodies of csrc/svs_block.hpp with the flag (tests/hostemu)."""
 import numpy as np
 
 from oracle.qim_dct_oracle import (BLOCK, MAX_AC, _blocks_view, _check_plane, _fwd, _inv, _quant_index, _requantised,
                                    bits_from_any)
-from testlib import CSRC, REPO
+from testlib import host_embed_call, hostemu
 
 DELTAS = (8, 20, 7.3, 0.1, 5000.3)            # QM_POW2, QM_F32, QM_DOUBLE, and two QM_DOUBLE steps on the exact route
 N_ACS = (1, 3, 7, 8, 10, 15, 16, 20, 63)
@@ -115,45 +110,17 @@ def sse(a, b):
     return int((d * d).sum())
 
 
-# ---- host build of the embed bodies ------------------------------------------------------------------------------------
-_SHIM = None
-
-
-def shim():
-    global _SHIM
-    if _SHIM is None:
-        src = os.path.join(REPO, "tests", "nearest", "nearest_shim.cpp")
-        out = os.path.join(tempfile.mkdtemp(prefix="svs_nearest_"), "libnr.so")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src,
-                               "-o", out])
-        lib = C.CDLL(out)
-        lib.nr_embed.restype = C.c_uint64
-        lib.nr_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_uint64,
-                                 C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p]
-        lib.nr_plan.restype = None
-        lib.nr_plan.argtypes = [C.c_double, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        _SHIM = lib
-    return _SHIM
-
-
+# ---- the embed bodies on the host (tests/hostemu) ---------------------------------------------------------------------
 def host_embed(frames, delta, n_ac, bits, bit_offset=0, n_bits=None, pocketfft=False, nearest=True):
     """a gray embed call through the product headers on the host -> (stego, bits embedded, blocks replayed exactly, path)"""
-    frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
-    f, h, w = frames.shape
-    bits = np.asarray(bits, np.uint8)
-    if n_bits is None:
-        n_bits = bits.size - bit_offset
-    packed = np.packbits(bits)
-    packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
-    out = np.empty_like(frames)
-    info = np.zeros(3, np.uint64)
-    used = shim().nr_embed(frames.ctypes.data, out.ctypes.data, f, h, w, float(delta), int(n_ac), packed.ctypes.data, packed.size,
-                           int(bit_offset), int(n_bits), int(pocketfft), int(nearest), info.ctypes.data)
-    return out, int(used), int(info[0]), int(info[1])
+    out, res, _ = host_embed_call(frames, delta, n_ac, bits, bit_offset=bit_offset, n_bits=n_bits, pocketfft=pocketfft,
+                                  guarded=not pocketfft, nearest=int(nearest))
+    return out, int(res.used), int(res.replayed), int(res.path)
 
 
 def plan(delta, n_ac, total, n_bits, pocketfft=False, bgr=False, nearest=True):
     """-> (path, nearest, use) of csrc/svs_route.hpp plan_embed"""
-    out = np.zeros(3, np.int64)
-    shim().nr_plan(float(delta), int(n_ac), int(total), int(n_bits), int(pocketfft), int(bgr), int(nearest), out.ctypes.data)
-    return int(out[0]), int(out[1]), int(out[2])
+    out = np.zeros(6, np.int64)
+    hostemu().emu_plan_rule(float(delta), int(n_ac), int(total), int(n_bits), int(pocketfft), int(bgr), int(nearest), 0,
+                            out.ctypes.data)
+    return int(out[0]), int(out[1]), int(out[3])

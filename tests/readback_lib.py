@@ -1,15 +1,10 @@
 """Helpers of the SVS_READBACK tests (tests/test_readback_cpu.py, tests/test_readback_gpu.py): the content classes on which the
 reference's own stego fails to read back, the oracle read-back, the host build of csrc/svs_readback.hpp
-(tests/readback/readback_shim.cpp) and a NumPy model of the repair."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
+(tests/hostemu) and a NumPy model of the repair."""
 import numpy as np
 
 from oracle.qim_dct_oracle import _blocks_view, _fwd, _inv, _quant_index, frame_embed, frame_extract_bits
-from testlib import CSRC, REPO
+from testlib import host_readback_call
 
 KINDS = ("noise", "natural", "letterbox", "bright", "flat0")
 CLIPPING = ("letterbox", "bright", "flat0")
@@ -53,42 +48,12 @@ def failing_blocks(stego, bits, delta, n_ac):
     return bad
 
 
-# ---- host build of csrc/svs_readback.hpp -----------------------------------------------------------------------------
-_SHIM = None
-
-
-def shim():
-    global _SHIM
-    if _SHIM is None:
-        src = os.path.join(REPO, "tests", "readback", "readback_shim.cpp")
-        out = os.path.join(tempfile.mkdtemp(prefix="svs_readback_"), "librb.so")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src,
-                               "-o", out])
-        lib = C.CDLL(out)
-        lib.rb_readback.restype = C.c_uint64
-        lib.rb_readback.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_uint64,
-                                    C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
-        _SHIM = lib
-    return _SHIM
-
-
+# ---- csrc/svs_readback.hpp on the host (tests/hostemu) ---------------------------------------------------------------
 def host_readback(stego, delta, n_ac, bits, bit_offset=0, n_bits=None, block_key=None, first_frame=0):
     """the read-back pass of csrc/svs_readback.hpp on the host over the reference's stego of a call -> (stego after the pass,
     (repaired, unrepaired), status per block: 0 reads back, 1 repaired, 2 left, 3 carries no payload)"""
-    frames = np.array(stego if stego.ndim == 3 else stego[None], np.uint8, order="C")
-    f, h, w = frames.shape
-    bits = np.asarray(bits, np.uint8)
-    if n_bits is None:
-        n_bits = bits.size - bit_offset
-    packed = np.packbits(bits)
-    packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
-    counts = np.zeros(2, np.uint64)
-    status = np.zeros(f * (h // 8) * (w // 8), np.uint8)
-    shim().rb_readback(frames.ctypes.data, f, h, w, float(delta), int(n_ac), packed.ctypes.data, packed.size, int(bit_offset),
-                       int(n_bits), int(block_key is not None), int(block_key or 0), int(first_frame), counts.ctypes.data,
-                       status.ctypes.data)
-    out = frames if stego.ndim == 3 else frames[0]
-    return out, (int(counts[0]), int(counts[1])), status
+    return host_readback_call(stego, delta, n_ac, bits, bit_offset=bit_offset, n_bits=n_bits, block_key=block_key,
+                              first_frame=int(first_frame))
 
 
 # ---- NumPy model of the repair -----------------------------------------------------------------------------------------

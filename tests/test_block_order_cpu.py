@@ -1,15 +1,13 @@
-"""Keyed block order, CPU tier: csrc/svs_order.hpp built for the host by tests/block_order/block_order_shim.cpp against the NumPy
+"""Keyed block order, CPU tier: csrc/svs_order.hpp built for the host by tests/hostemu against the NumPy
 restatement svsdct/order.py (both directions, bijections), pinned known-answer values (the order is a format sender and
 receiver share), the block permutation helpers, and the Python / ctypes surface of the ordered entry points."""
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from testlib import CSRC, REPO
+from testlib import hostemu
 from svsdct import batch, native, order, synth
 from svsdct.pipeline import FramePipeline
 
@@ -18,15 +16,8 @@ KEYS = (0, 1, 0x0123456789ABCDEF, 0xFFFFFFFF00000000, (1 << 64) - 1)
 
 
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    src = os.path.join(REPO, "tests", "block_order", "block_order_shim.cpp")
-    out = str(tmp_path_factory.mktemp("block_order") / "libbo.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-I" + CSRC, src, "-o", out])
-    lib = C.CDLL(out)
-    lib.bo_map.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
-    lib.bo_lowbias32.restype = C.c_uint32
-    lib.bo_lowbias32.argtypes = [C.c_uint32]
-    return lib
+def shim():
+    return hostemu()
 
 
 def _compiled(lib, key, t, n, inverse, first_frame=0):

@@ -1,5 +1,5 @@
 """SVS_NEAREST and SVS_MINMOVE on guard-boundary frames - CPU tier, on the host build of the streaming and exact bodies
-(tests/minmove/minmove_shim.cpp: the library's route, rule word and RouteArgs::guard_scale) against the NumPy models of
+(tests/hostemu through minmove_lib.host_embed: the library's route, rule word and RouteArgs::guard_scale) against the NumPy models of
 nearest_lib / minmove_lib.
 
 tests/golden/guard_rules_corpus.npz (tests/golden/make_guard_rules_corpus.py) holds one frame per kernel family and rule.  Its

@@ -1,7 +1,7 @@
 """GPU tier of the guard checks under SVS_NEAREST and SVS_MINMOVE (CPU tier: test_guard_rules_cpu.py): on the frames of
 tests/golden/guard_rules_corpus.npz - waves with 1, 8, 31, 32, 33, 64 (128) undecided blocks and one in every further wave,
 boundary blocks with s* > 0 under the rule among them - the streaming kernels' rule bodies and their pooled replay make the
-decisions of the host build of the bodies (tests/minmove/minmove_shim.cpp).
+decisions of the host build of the bodies (tests/hostemu through minmove_lib.host_embed).
 
 * product library, gray call with the flag in guarded, default and exact mode, and in place at the device-pointer level: the
   NumPy model's pixels;

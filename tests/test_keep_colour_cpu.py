@@ -1,17 +1,15 @@
 """SVS_KEEP_COLOUR, CPU tier: the per-pixel rule of csrc/svs_colour.hpp (the one the fused colour kernel applies), built for
-the host by tests/keep_colour/keep_colour_shim.cpp, checked exhaustively; a NumPy restatement of the rule (used by the GPU
+the host by tests/hostemu, checked exhaustively; a NumPy restatement of the rule (used by the GPU
 tests as their expected output) against it; the flag and the Python parameters that expose it."""
-import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 import threading
 
 import numpy as np
 import pytest
 
-from testlib import CSRC, REPO
+from testlib import REPO, hostemu
 from svsdct import batch, native
 
 TABLES = {"15-bit": (3735, 19235, 9798, 15), "14-bit": (1868, 9617, 4899, 14)}
@@ -49,15 +47,8 @@ def gray_of(bgr, weights):
 
 
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    src = os.path.join(REPO, "tests", "keep_colour", "keep_colour_shim.cpp")
-    out = str(tmp_path_factory.mktemp("keep_colour") / "libkc.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src, "-o", out])
-    lib = C.CDLL(out)
-    lib.kc_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.kc_check.restype = C.c_uint64
-    lib.kc_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-    return lib
+def shim():
+    return hostemu()
 
 
 def _check(lib, first, count, stride, radius, weights):

@@ -1,5 +1,5 @@
 """Read-back and repair under a coefficient selection and a keyed dither (svs_embed_dithered_readback*), CPU tier: the keyed
-forms of csrc/svs_readback.hpp built for the host (tests/keyed_readback) are today's read-back with the prefix table and no
+forms of csrc/svs_readback.hpp built for the host (tests/hostemu) are today's read-back with the prefix table and no
 dither, equal a NumPy model bit for bit on the content / delta / selection rows that motivated them, keep SVS_READBACK's
 contract, pair the dither with a block's physical position and the bits with its slot, and are routed by new calls only: the
 select and dithered calls keep refusing SVS_READBACK."""

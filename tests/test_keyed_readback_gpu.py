@@ -1,5 +1,5 @@
 """Read-back and repair under a coefficient selection and a keyed dither on the GPU (svs_embed_dithered_readback*): the
-keyed body of readback_kernel equals the host build of the same arithmetic (csrc/svs_readback.hpp via tests/keyed_readback)
+keyed body of readback_kernel equals the host build of the same arithmetic (csrc/svs_readback.hpp via tests/hostemu)
 byte for byte with the same counts, starting from the bytes of the same call without read-back - dither off and on, raster and
 keyed order, both embed rules, every quantiser mode, on frames whose waves straddle frames and end ragged - in place, on
 pitched planes and over several staging chunks; without a selection and a dither the calls are svs_embed_readback*; and a

@@ -18,7 +18,7 @@ import coeff_select_lib as cs
 import minmove_lib as ml
 import nearest_lib as nl
 from oracle import qim_dct_oracle as orc
-from testlib import CSRC
+from testlib import CSRC, hostemu
 from test_pipeline import _install
 from svsdct import batch, coeffs, native
 from svsdct.pipeline import FramePipeline
@@ -39,7 +39,7 @@ def test_margin_table_is_the_recomputed_bound():
     want = ml.margin_table()
     got = _source_table()
     assert got.size == 64 and np.array_equal(got[1:], want[1:])
-    assert np.array_equal(np.array([ml.shim().mm_margin(k) for k in range(1, 64)], np.float32), want[1:])
+    assert np.array_equal(np.array([hostemu().mm_margin(k) for k in range(1, 64)], np.float32), want[1:])
     bound = want[1:].astype(np.float64) - 0.0625
     assert 3.284 < bound.min() < 3.285 and abs(bound.max() - 4.0) < 1e-6
     # every r_k is 0 up to delta = 6.69 and some r_k is positive above
@@ -149,7 +149,7 @@ def test_one_coefficient_through_both_forms(qm, delta):
     c_all = np.concatenate([base, grid, grid + ml.half_cell(delta), np.float32(grid + 0.25 * d32), [np.float32(0.0)]]).astype(np.float32)
     r_all = ml.band(delta)
     out = np.zeros(2, np.float32)
-    lib = ml.shim()
+    lib = hostemu()
     for i, c in enumerate(c_all):
         k = 1 + i % 63
         bit = (i // 63) & 1

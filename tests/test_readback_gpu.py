@@ -1,5 +1,5 @@
 """SVS_READBACK on the GPU: readback_kernel's output equals the host build of the same arithmetic (csrc/svs_readback.hpp via
-tests/readback) byte for byte with the same counts - raster and keyed order, the device call in place, the host-pointer
+tests/hostemu) byte for byte with the same counts - raster and keyed order, the device call in place, the host-pointer
 call over several staging chunks - content without failures comes out byte-identical to the call without the flag,
 letterboxed 1080p frames that the reference's stego cannot deliver decode exactly, and a framed payload survives the drop-in
 video loop."""

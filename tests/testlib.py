@@ -1,5 +1,6 @@
 """Helpers shared by the CPU and GPU test tiers."""
 import ctypes
+import glob
 import hashlib
 import os
 import subprocess
@@ -200,18 +201,69 @@ def exact_tie_mask(gray, delta, n_ac):
     return mask
 
 
-# ---- test-only CPU emulation of the per-block kernel arithmetic (tests/hostemu) ---------------
+# ---- test-only CPU build of the csrc/ headers (tests/hostemu): the only host C++ the tests build or load -----------------
 _EMU = None
+_C = ctypes
+_PTR = ctypes.c_void_p
+
+
+class EmuCall(ctypes.Structure):
+    """tests/hostemu/emu_call.h, field for field"""
+    _fields_ = [("size", _C.c_uint64), ("frames_in", _PTR), ("frames_out", _PTR), ("F", _C.c_int32), ("H", _C.c_int32),
+                ("W", _C.c_int32), ("n_ac", _C.c_int32), ("delta", _C.c_double), ("index", _PTR), ("count", _C.c_int32),
+                ("pocketfft", _C.c_int32), ("guarded", _C.c_int32), ("bits", _PTR), ("bits_bytes", _C.c_uint64),
+                ("bit_offset", _C.c_uint64), ("n_bits", _C.c_uint64), ("nearest", _C.c_int32), ("minmove", _C.c_int32),
+                ("dither", _C.c_int32), ("order", _C.c_int32), ("dither_key", _C.c_uint64), ("order_key", _C.c_uint64),
+                ("first_frame", _C.c_uint32), ("guard_scale", _C.c_float), ("tie_scale", _C.c_float), ("force_qm", _C.c_int32),
+                ("exact_rows", _C.c_int32), ("streaming_bodies", _C.c_int32), ("variant", _C.c_int32),
+                ("extract_wave", _C.c_int32), ("keyed_form", _C.c_int32), ("replay_map", _PTR), ("candidate_map", _PTR),
+                ("status", _PTR), ("bits_out", _PTR)]
+
+
+class EmuResult(ctypes.Structure):
+    _fields_ = [("size", _C.c_uint64), ("used", _C.c_uint64), ("replayed", _C.c_uint64), ("repaired", _C.c_uint64),
+                ("unrepaired", _C.c_uint64), ("path", _C.c_int32), ("rows", _C.c_int32), ("qm", _C.c_int32),
+                ("selected", _C.c_int32), ("dithered", _C.c_int32), ("nearest", _C.c_int32), ("minmove", _C.c_int32),
+                ("word", _C.c_uint32)]
+
+
+_PROTOTYPES = {
+    "emu_embed_call": (_C.c_int, [_C.POINTER(EmuCall), _C.POINTER(EmuResult)]),
+    "emu_extract_call": (_C.c_int, [_C.POINTER(EmuCall), _C.POINTER(EmuResult)]),
+    "emu_readback_call": (_C.c_int, [_C.POINTER(EmuCall), _C.POINTER(EmuResult)]),
+    "emu_exact_mode": (None, [_C.POINTER(EmuCall), _C.c_int]),
+    "emu_embed": (_C.c_uint64, [_PTR, _PTR, _C.c_int, _C.c_int, _C.c_int, _C.c_double, _C.c_int, _PTR, _C.c_uint64, _C.c_uint64,
+                                _C.c_uint64, _C.c_int, _C.POINTER(_C.c_uint64)]),
+    "emu_extract": (_C.c_uint64, [_PTR, _C.c_int, _C.c_int, _C.c_int, _C.c_double, _C.c_int, _PTR, _C.c_int,
+                                  _C.POINTER(_C.c_uint64)]),
+    "emu_pf_dct2": (None, [_PTR, _PTR]),
+    "emu_pf_dct3": (None, [_PTR, _PTR]),
+    "emu_forward_block": (None, [_PTR, _PTR]),
+    "emu_idct8": (None, [_PTR, _PTR]),
+    "emu_vertical_pf01": (None, [_PTR, _PTR]),
+    "emu_qim_change_mismatches": (_C.c_uint64, [_PTR, _PTR, _C.c_uint64, _C.c_double]),
+    "emu_quant_mismatches": (_C.c_uint64, [_PTR, _C.c_uint64, _C.c_double]),
+    "emu_plan_chunks": (_C.c_uint64, [_C.c_int32, _C.c_int32, _C.c_uint64, _C.c_uint64, _C.c_uint64, _PTR, _C.c_uint64]),
+    "emu_chunk_budget": (_C.c_uint64, [_C.c_uint64, _C.c_uint64, _C.c_uint64, _C.c_uint32]),
+    "emu_plan_rule": (None, [_C.c_double, _C.c_int, _C.c_uint64, _C.c_uint64, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _PTR]),
+    "mm_margin": (_C.c_float, [_C.c_int]),
+    "mm_coefficient": (None, [_C.c_float, _C.c_int, _C.c_double, _C.c_int, _C.c_int, _PTR]),
+    "cs_table": (_C.c_int, [_PTR, _C.c_int, _PTR]),
+    "dt_hash": (_C.c_float, [_C.c_uint64, _C.c_uint32, _C.c_uint32, _C.c_uint32, _C.c_float, _PTR]),
+    "bo_map": (None, [_C.c_uint64, _C.c_uint32, _C.c_uint32, _C.c_uint32, _C.c_int, _PTR]),
+    "bo_lowbias32": (_C.c_uint32, [_C.c_uint32]),
+    "kc_apply": (None, [_PTR, _PTR, _PTR, _C.c_uint64, _PTR]),
+    "kc_check": (_C.c_uint64, [_C.c_uint32, _C.c_uint32, _C.c_uint32, _C.c_int, _PTR, _PTR]),
+}
 
 
 def hostemu():
     global _EMU
     if _EMU is not None:
         return _EMU
-    src = os.path.join(REPO, "tests", "hostemu", "hostemu.cpp")
-    out = os.path.join(REPO, "tests", "hostemu", "libsvs_hostemu.so")
-    deps = [src, os.path.join(CSRC, "svs_block.hpp"), os.path.join(CSRC, "svs_stage.hpp"),
-            os.path.join(CSRC, "svs_route.hpp"), os.path.join(CSRC, "svs_index.hpp"), os.path.join(CSRC, "svs_order.hpp")]
+    here = os.path.join(REPO, "tests", "hostemu")
+    src, out = os.path.join(here, "hostemu.cpp"), os.path.join(here, "libsvs_hostemu.so")
+    deps = glob.glob(os.path.join(CSRC, "*.hpp")) + [d for d in glob.glob(os.path.join(here, "*")) if d != out]
     stale = not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
     if stale and os.path.exists(out) and os.path.exists("/dev/kfd"):
         stale = False      # on a GPU box use the library built by build(): no compiler child processes there
@@ -219,32 +271,9 @@ def hostemu():
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w",
                                "-I" + CSRC, src, "-o", out])
     lib = ctypes.CDLL(out)
-    lib.emu_embed.restype = ctypes.c_uint64
-    lib.emu_embed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                              ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
-                              ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-    lib.emu_extract.restype = ctypes.c_uint64
-    lib.emu_extract.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
-    lib.emu_pf_dct2.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.emu_pf_dct3.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.emu_forward_block.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.emu_idct8.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.emu_vertical_pf01.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.emu_qim_change_mismatches.restype = ctypes.c_uint64
-    lib.emu_qim_change_mismatches.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double]
-    lib.emu_quant_mismatches.restype = ctypes.c_uint64
-    lib.emu_quant_mismatches.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double]
-    lib.emu_plan_chunks.restype = ctypes.c_uint64
-    lib.emu_plan_chunks.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                                    ctypes.c_uint64]
-    lib.emu_chunk_budget.restype = ctypes.c_uint64
-    lib.emu_chunk_budget.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
-    lib.emu_set_guard_scale.argtypes = [ctypes.c_float]
-    lib.emu_set_tie_scale.argtypes = [ctypes.c_float]
-    lib.emu_set_replay_map.argtypes = [ctypes.c_void_p]
-    lib.emu_set_extract_wave.argtypes = [ctypes.c_int]
-    lib.emu_set_candidate_map.argtypes = [ctypes.c_void_p]
+    for name, (res, args) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
     _EMU = lib
     return lib
 
@@ -259,88 +288,129 @@ def plan_chunks(n_frames, height, row_bytes, total_bytes=None, target_bytes=0):
     return [tuple(int(v) for v in row) for row in out[:n]]
 
 
-def emu_embed(frames, delta, n_ac, bits, bit_offset=0, exact=False, replayed=None):
-    """`replayed`: optional list; receives the number of blocks FAST mode handed to the exact replay."""
+def _emu_call(entry, frames, delta, n_ac, bits=None, bit_offset=0, n_bits=None, index=None, exact=None, pocketfft=False,
+              guarded=False, dither_key=None, block_key=None, **fields):
+    """One gray call through the host library: fills an EmuCall from NumPy arguments, runs `entry` (emu_embed_call,
+    emu_extract_call or emu_readback_call) and -> the EmuResult.  bits: 0/1 per bit, packed here MSB-first and padded to
+    whole dwords plus one; n_bits None: all of them from bit_offset on.  index: None, or the flat indices of a coefficient
+    selection.  exact: hostemu's mode number (emu_exact_mode) instead of the two mode bits.  dither_key / block_key: None, or
+    the key of the dither / the block order.  fields: the remaining members of EmuCall by name (arrays by their address)."""
     lib = hostemu()
-    frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
     f, h, w = frames.shape
-    packed = np.packbits(np.asarray(bits, np.uint8))
-    packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
-    out = np.empty_like(frames)
-    count = ctypes.c_uint64(0)
-    used = lib.emu_embed(frames.ctypes.data, out.ctypes.data, f, h, w, float(delta), int(n_ac),
-                         packed.ctypes.data, packed.size, int(bit_offset), int(len(bits) - bit_offset), int(exact),
-                         ctypes.byref(count))
-    if replayed is not None:
-        replayed.append(int(count.value))
-    return out, int(used)
+    keep = []          # the arrays made here that the call points into
+    call = EmuCall(size=ctypes.sizeof(EmuCall), F=f, H=h, W=w, delta=float(delta), n_ac=int(n_ac), pocketfft=int(pocketfft),
+                   guarded=int(guarded), guard_scale=1.0, tie_scale=1.0, force_qm=-1, exact_rows=8, streaming_bodies=1,
+                   dither=int(dither_key is not None), dither_key=int(dither_key or 0), order=int(block_key is not None),
+                   order_key=int(block_key or 0))
+    if exact is not None:
+        lib.emu_exact_mode(ctypes.byref(call), int(exact))
+    if bits is not None:
+        bits = np.asarray(bits, np.uint8)
+        packed = np.packbits(bits)
+        packed = np.concatenate([packed, np.zeros((-packed.size) % 4 + 4, np.uint8)])
+        keep.append(packed)
+        call.bits, call.bits_bytes, call.bit_offset = packed.ctypes.data, packed.size, int(bit_offset)
+        call.n_bits = int(bits.size - bit_offset if n_bits is None else n_bits)
+    if index is not None:
+        idx = np.ascontiguousarray(np.asarray(index, np.int64).reshape(-1).astype(np.uint8))
+        keep.append(idx)
+        call.index, call.count = idx.ctypes.data, idx.size
+    for name, value in fields.items():
+        if isinstance(value, np.ndarray):
+            keep.append(value)
+            value = value.ctypes.data
+        setattr(call, name, value)
+    res = EmuResult(size=ctypes.sizeof(EmuResult))
+    if getattr(lib, entry)(ctypes.byref(call), ctypes.byref(res)) != 0:
+        raise RuntimeError("EmuCall / EmuResult differ from tests/hostemu/emu_call.h: rebuild tests/hostemu or mend the mirror")
+    assert res.used != 2 ** 64 - 1, "the host library refused the selection"
+    return res
+
+
+def _frames3(frames, copy=False):
+    frames = frames if frames.ndim == 3 else frames[None]
+    return np.array(frames, np.uint8, order="C") if copy else np.ascontiguousarray(frames)
+
+
+def _block_map(frames):
+    f, h, w = frames.shape
+    return np.zeros(f * (h // 8) * (w // 8), np.uint8)
+
+
+def host_embed_call(frames, delta, n_ac, bits, **call):
+    """a gray embed call on the host -> (stego, EmuResult, replay map: bool per block in raster order over the batch - the
+    guard handed the block to the exact replay).  call: see _emu_call."""
+    frames = _frames3(frames)
+    out, rmap = np.empty_like(frames), _block_map(frames)
+    res = _emu_call("emu_embed_call", frames, delta, n_ac, bits=bits, frames_in=frames, frames_out=out, replay_map=rmap, **call)
+    return out, res, rmap.astype(bool)
+
+
+def host_extract_call(frames, delta, n_ac, **call):
+    """a gray extract call on the host -> (0/1 per bit, EmuResult, candidate map: bool per block - with extract_wave set, step
+    one of FAST extraction flags the block)"""
+    frames = _frames3(frames)
+    index = call.get("index")
+    n = max(0, min(int(n_ac), 63)) if index is None else len(index)
+    cmap = _block_map(frames)
+    out = np.zeros(cmap.size * max(n, 1), np.uint8)
+    res = _emu_call("emu_extract_call", frames, delta, n_ac, frames_in=frames, bits_out=out, candidate_map=cmap, **call)
+    return out[:res.used], res, cmap.astype(bool)
+
+
+def host_readback_call(stego, delta, n_ac, bits, **call):
+    """the read-back pass on the host over a copy of `stego` (one frame or a batch) -> (stego after the pass, (repaired,
+    unrepaired), status per physical block: 0 reads back, 1 repaired, 2 left, 3 carries no payload)"""
+    frames = _frames3(stego, copy=True)
+    status = _block_map(frames)
+    res = _emu_call("emu_readback_call", frames, delta, n_ac, bits=bits, guarded=True, frames_out=frames, status=status, **call)
+    return (frames if stego.ndim == 3 else frames[0]), (int(res.repaired), int(res.unrepaired)), status
+
+
+_SCALES = {"guard_scale": 1.0, "tie_scale": 1.0}
 
 
 class emu_scales:
-    """`with emu_scales(guard=s, tie=t):` - hostemu's BETA / tie margin multiplied by s / t inside the block, as the
-    experiments library's SVS_GUARD_SCALE / SVS_TIE_SCALE do (1 = the product's bounds)"""
+    """`with emu_scales(guard=s, tie=t):` - BETA / the tie margin of emu_embed / emu_extract (and the two maps) multiplied by
+    s / t inside the block, as the experiments library's SVS_GUARD_SCALE / SVS_TIE_SCALE do (1 = the product's bounds)"""
 
     def __init__(self, guard=1.0, tie=1.0):
         self.guard, self.tie = float(guard), float(tie)
 
     def __enter__(self):
-        lib = hostemu()
-        lib.emu_set_guard_scale(self.guard)
-        lib.emu_set_tie_scale(self.tie)
+        _SCALES.update(guard_scale=self.guard, tie_scale=self.tie)
         return self
 
     def __exit__(self, *exc):
-        lib = hostemu()
-        lib.emu_set_guard_scale(1.0)
-        lib.emu_set_tie_scale(1.0)
+        _SCALES.update(guard_scale=1.0, tie_scale=1.0)
         return False
+
+
+def emu_embed(frames, delta, n_ac, bits, bit_offset=0, exact=False, replayed=None):
+    """`replayed`: optional list; receives the number of blocks FAST mode handed to the exact replay."""
+    out, res, _ = host_embed_call(frames, delta, n_ac, bits, bit_offset=bit_offset, exact=int(exact), **_SCALES)
+    if replayed is not None:
+        replayed.append(int(res.replayed))
+    return out, int(res.used)
 
 
 def emu_replay_map(frames, delta, n_ac, bits):
     """-> bool per block (raster order over the batch): hostemu's guarded embed handed the block to the exact replay"""
-    lib = hostemu()
-    frames = frames if frames.ndim == 3 else frames[None]
-    f, h, w = frames.shape
-    out = np.zeros(f * (h // 8) * (w // 8), np.uint8)
-    lib.emu_set_replay_map(out.ctypes.data)
-    try:
-        emu_embed(frames, delta, n_ac, bits)
-    finally:
-        lib.emu_set_replay_map(None)
-    return out.astype(bool)
-
-
-def emu_tie_candidates(frames, delta, n_ac):
-    """-> bool per block: step one of FAST extraction (n >= 8) flags the block as a candidate (wave mode of emu_extract)"""
-    lib = hostemu()
-    frames = frames if frames.ndim == 3 else frames[None]
-    f, h, w = frames.shape
-    out = np.zeros(f * (h // 8) * (w // 8), np.uint8)
-    lib.emu_set_candidate_map(out.ctypes.data)
-    try:
-        emu_extract(frames, delta, n_ac, wave=64)
-    finally:
-        lib.emu_set_candidate_map(None)
-    return out.astype(bool)
+    return host_embed_call(frames, delta, n_ac, bits, exact=0, **_SCALES)[2]
 
 
 def emu_extract(frames, delta, n_ac, exact=False, redone=None, wave=0):
     """`redone`: optional list; receives the number of blocks FAST mode recomputed with the exact transform.  `wave` = 64:
     FAST extraction's step two for every block of a wave with a candidate, as the kernels do it (0: per block)."""
-    lib = hostemu()
-    lib.emu_set_extract_wave(int(wave))
-    frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
-    f, h, w = frames.shape
-    n = max(0, min(int(n_ac), 63))
-    out = np.zeros(f * (h // 8) * (w // 8) * n, np.uint8)
-    count = ctypes.c_uint64(0)
-    try:
-        lib.emu_extract(frames.ctypes.data, f, h, w, float(delta), int(n_ac), out.ctypes.data, int(exact), ctypes.byref(count))
-    finally:
-        lib.emu_set_extract_wave(0)
+    out, res, _ = host_extract_call(frames, delta, n_ac, pocketfft=bool(exact), extract_wave=int(wave), **_SCALES)
     if redone is not None:
-        redone.append(int(count.value))
+        redone.append(int(res.replayed))
     return out
+
+
+def emu_tie_candidates(frames, delta, n_ac):
+    """-> bool per block: step one of FAST extraction (n >= 8) flags the block as a candidate (wave mode of emu_extract)"""
+    return host_extract_call(frames, delta, n_ac, extract_wave=64, **_SCALES)[2]
 
 
 def guard_corpus_case(arrays, meta, name):
