@@ -187,15 +187,12 @@ using svs::ExtractPath;
 
 // svs_embed_dev's plan: embed_row1_kernel (one coefficient row, and the copy), embed_kernel<2> (two rows) or embed_exact_kernel.
 // `two`: two blocks per lane, where the plan and the buffers allow it.  A keyed plan (p.keyed, `ord` its order) launches the
-// KEYED instantiation of the same kernel family, with the order as the last argument.
+// KEYED instantiation of the same kernel family, with the order as the last argument.  `k`: the call's options in the kernels'
+// forms (svs_route.hpp, which also says which tables the exact kernel gets).
 int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
-                 svs::Geometry g, const uint32_t *bits, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{},
-                 const svs::CoeffTable *coeffs = nullptr, const svs::DitherArgs &dith = svs::DitherArgs{}) {
-    const svs::CoeffTable sel = p.selected && coeffs ? *coeffs : svs::CoeffTable{};   // count 0: the row-major prefix
-    // on only where the plan says so (EXACT, rows = 8); the dithered side runs the selected loop alone, with the prefix table of
-    // n_ac where the call has no selection
-    const svs::DitherArgs dth{dith.seed, dith.first_frame, p.dithered ? 1u : 0u,
-                              !p.dithered ? svs::CoeffTable{} : sel.count ? sel : svs::make_prefix_table((uint32_t)p.n_ac)};
+                 svs::Geometry g, const uint32_t *bits, const svs::KernelOptions &k) {
+    const svs::LaunchTables t = svs::embed_tables(p, k);
+    const svs::BlockOrderArgs &ord = k.ord;
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
     g.pad = svs::rule_word(p.nearest, p.minmove, p.half_cell);
@@ -209,9 +206,9 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
                 constexpr int U = decltype(u)::value;
                 if (p.keyed)
                     return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g,
-                                  p.qp, bits, p.bit_offset, p.n_bits, words, sel, dth, ord);
+                                  p.qp, bits, p.bit_offset, p.n_bits, words, t.sel, t.dith, ord);
                 return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words, sel, dth);
+                              p.bit_offset, p.n_bits, words, t.sel, t.dith);
             });
         if (p.rows == 2) {   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
             if (p.keyed)
@@ -239,13 +236,12 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
 // embed's payload arguments (the plan's rows are 1 or 2 for n <= 15, else 8: the quantiser loop's coefficient rows).
 // The colour calls pass their BGR output as `stego`, its pitches and the call's weights in `colour`, and form = SVS_RB_BGR:
 // they run the colour body of their quantiser mode, which lives in one instantiation (plain and keep-colour output alike).
-// A plan with a non-prefix selection or a dither (svs_embed_dithered_readback_dev; `coeffs`, `dith` as launch_embed takes them)
-// runs the keyed form, form = SVS_RB_SEL + its quantiser mode, in the same instantiation: the table it passes is the call's
-// selection or the prefix table of n_ac, and a call without an order adds SVS_RB_RASTER.
+// A plan with a non-prefix selection or a dither (svs_embed_dithered_readback_dev; `k` as launch_embed takes it) runs the keyed
+// form, form = SVS_RB_SEL + its quantiser mode, in the same instantiation, with svs_route.hpp's readback_tables; a call
+// without an order adds SVS_RB_RASTER.
 int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uint8_t *stego, svs::Geometry g, const uint32_t *bits,
-                    uint64_t *counts, const svs::BlockOrderArgs &ord, const svs::ColourParams &colour = svs::ColourParams{},
-                    uint32_t form = SVS_RB_GRAY, const svs::CoeffTable *coeffs = nullptr,
-                    const svs::DitherArgs &dith = svs::DitherArgs{}) {
+                    uint64_t *counts, const svs::KernelOptions &k, const svs::ColourParams &colour, uint32_t form) {
+    const svs::BlockOrderArgs &ord = k.ord;
     g.n_ac = p.n_ac;
     g.xcd_chunk = svs::kEighth;
     const uint32_t words = (uint32_t)p.n_words;
@@ -254,12 +250,10 @@ int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uin
     if (form != SVS_RB_GRAY)   // the one instantiation that holds the colour bodies (svs_device.hpp SVS_RB_HOSTS_COLOUR)
         return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
                       p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_BGR + p.qm), none, svs::BlockOrderArgs{});
-    if (p.selected || p.dithered) {   // ... and the keyed bodies
-        const svs::DitherArgs kd{dith.seed, dith.first_frame, p.dithered ? 1u : 0u,
-                                 p.selected && coeffs ? *coeffs : svs::make_prefix_table((uint32_t)p.n_ac)};
+    if (p.selected || p.dithered)   // ... and the keyed bodies
         return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
-                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_SEL + p.qm + (p.keyed ? 0u : SVS_RB_RASTER)), kd, ord);
-    }
+                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_SEL + p.qm + (p.keyed ? 0u : SVS_RB_RASTER)),
+                      svs::readback_tables(p, k), ord);
     return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
         return dispatch<1, 2, 8>(p.rows, [&](auto u) {
@@ -277,7 +271,7 @@ int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uin
 // A plan with the read-back bit (svs_embed_bgr_readback_dev) is followed by readback_kernel in its colour form, in place on
 // `out` (counts: device, added to; NULL for none).
 int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStream_t st, const uint8_t *in, uint8_t *out,
-                     uint8_t *ref, svs::Geometry g, const svs::ColourParams &c, const uint32_t *bits, uint64_t *counts = nullptr) {
+                     uint8_t *ref, svs::Geometry g, const svs::ColourParams &c, const uint32_t *bits, uint64_t *counts) {
     const svs::Geometry planes = g;
     g.n_ac = p.n_ac;
     g.xcd_chunk = p.xcd_chunk;
@@ -302,17 +296,15 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
     svs::ColourParams in_place = c;   // the pass reads and writes the output
     in_place.in_row_pitch = c.out_row_pitch;
     in_place.in_frame_pitch = c.out_frame_pitch;
-    return launch_readback(p, total, st, out, planes, bits, counts, svs::BlockOrderArgs{}, in_place, SVS_RB_BGR);
+    return launch_readback(p, total, st, out, planes, bits, counts, svs::KernelOptions{}, in_place, SVS_RB_BGR);
 }
 
 // svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>.  A keyed plan ORs every block's bits into its
 // slot with global atomics (svs_device.hpp, or_bits_global): the output is cleared first, on the same stream.
 int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
-                   uint64_t out_bytes, const svs::BlockOrderArgs &ord = svs::BlockOrderArgs{}, const svs::CoeffTable *coeffs = nullptr,
-                   const svs::DitherArgs &dith = svs::DitherArgs{}) {
-    const svs::CoeffTable sel = p.selected && coeffs ? *coeffs : svs::CoeffTable{};   // count 0: the row-major prefix
-    // on only where the plan says so (EXACT, rows = 8); the extract kernel reads the selection from `sel` on either side
-    const svs::DitherArgs dth{dith.seed, dith.first_frame, p.dithered ? 1u : 0u, svs::CoeffTable{}};
+                   uint64_t out_bytes, const svs::KernelOptions &k) {
+    const svs::LaunchTables t = svs::extract_tables(p, k);
+    const svs::BlockOrderArgs &ord = k.ord;
     if (p.path == ExtractPath::ZEROS || p.keyed) SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
     if (p.path == ExtractPath::ZEROS) return SVS_OK;
     g.xcd_chunk = p.xcd_chunk;
@@ -323,8 +315,8 @@ int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, co
                 constexpr int U = decltype(r)::value;
                 if (p.keyed)
                     return launch(svs::extract_exact_kernel<U, QM, 1, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, g, p.qp,
-                                  out, out_bytes, sel, dth, ord);
-                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes, sel, dth);
+                                  out, out_bytes, t.sel, t.dith, ord);
+                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes, t.sel, t.dith);
             });
         if (p.keyed)
             return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
@@ -719,19 +711,41 @@ uint64_t svs_packed_bytes(uint64_t n_bits) { return (n_bits + 7) / 8; }
 
 namespace {
 
+// What a gray call adds to the plain call (svs_embed_dev / svs_extract_dev); every member is optional.  The public entry points
+// fill one - those with a selection or a dither through with_options - and the internal functions below take it.
+struct GrayOptions {
+    const svs_block_order *order = nullptr;    // the ordered calls: a keyed block order
+    const svs::CoeffTable *coeffs = nullptr;   // the select calls: the table of a selection that is not the prefix 1..n_ac
+    const svs_dither *dither = nullptr;        // the dithered calls
+    uint64_t *d_counts = nullptr;              // the read-back calls, device: {repaired, unrepaired}, added to
+    svs_readback_counts *counts = nullptr;     // the read-back calls, host: the counts of the whole call
+
+    // the kernels' forms, for a batch of g's blocks per frame (derived once per call)
+    svs::KernelOptions kernel_forms(const svs::Geometry &g) const {
+        return {order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{}, coeffs,
+                dither ? svs::DitherArgs{svs::dither_seed(dither->key), dither->first_frame, 1u, svs::CoeffTable{}} : svs::DitherArgs{}};
+    }
+
+    // The options of a staging chunk of whole frames that starts at frame f0 of the call: its first frame is clip frame
+    // first_frame + f0 for the order and the dither alike (rebased into *o and *d), and its counts are added to `chunk_counts`.
+    GrayOptions chunk(uint32_t f0, uint64_t *chunk_counts, svs_block_order *o, svs_dither *d) const {
+        GrayOptions c = *this;
+        if (order) c.order = &(*o = svs_block_order{order->key, order->first_frame + f0, 0u});
+        if (dither) c.dither = &(*d = svs_dither{dither->key, dither->first_frame + f0, 0u});
+        c.d_counts = chunk_counts;
+        c.counts = nullptr;
+        return c;
+    }
+};
+
 // the order argument of the ordered entry points: NULL (no order) or a valid one
 int check_order(const svs_block_order *order) {
     if (order && order->reserved != 0) return fail(SVS_ERR_INVALID_ARG, "svs_block_order.reserved must be 0");
     return SVS_OK;
 }
 
-// the kernels' form of an order for a batch of `bpf` blocks per frame
-svs::BlockOrderArgs order_args(const svs_block_order *order, const svs::Geometry &g) {
-    return order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{};
-}
-
-// the dither argument of the dithered entry points: required; its first_frame must be the order's when both are given (a
-// caller must not desynchronise them silently)
+// the dither argument of the dithered entry points; its first_frame must be the order's when both are given (a caller must
+// not desynchronise them silently)
 int check_dither(const svs_dither *dither, const svs_block_order *order) {
     if (!dither) return fail(SVS_ERR_INVALID_ARG, "dither is NULL");
     if (dither->reserved != 0) return fail(SVS_ERR_INVALID_ARG, "svs_dither.reserved must be 0");
@@ -739,10 +753,6 @@ int check_dither(const svs_dither *dither, const svs_block_order *order) {
         return fail(SVS_ERR_INVALID_ARG, "svs_dither.first_frame %u differs from svs_block_order.first_frame %u",
                     (unsigned)dither->first_frame, (unsigned)order->first_frame);
     return SVS_OK;
-}
-
-svs::DitherArgs dither_args(const svs_dither *dither) {
-    return dither ? svs::DitherArgs{svs::dither_seed(dither->key), dither->first_frame, 1u, svs::CoeffTable{}} : svs::DitherArgs{};
 }
 
 // The selection of the select entry points -> the kernels' table.  *coeffs = NULL when the selection is the prefix 1..count:
@@ -758,30 +768,68 @@ int check_coeffs(const svs_coeffs *c, svs::CoeffTable *table, const svs::CoeffTa
     return SVS_OK;
 }
 
-constexpr uint32_t kSelectEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_NEAREST | SVS_MINMOVE;
+constexpr uint32_t kModeFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED;
+constexpr uint32_t kSelectEmbedFlags = kModeFlags | SVS_NEAREST | SVS_MINMOVE;
+constexpr uint32_t kGrayEmbedFlags = kSelectEmbedFlags | SVS_READBACK;
 
-constexpr uint32_t kGrayEmbedFlags = SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED | SVS_READBACK | SVS_NEAREST | SVS_MINMOVE;
+// What an entry point with a selection or a dither checks before anything else: a NULL dither or selection is refused where
+// the policy requires one and means "none" elsewhere; flags outside `allowed` are refused with `what`.
+struct OptionsPolicy {
+    bool dither_required, coeffs_required;
+    uint32_t allowed;
+    const char *what;
+};
+constexpr OptionsPolicy kSelectEmbed{false, true, kSelectEmbedFlags, "a select embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE"};
+constexpr OptionsPolicy kSelectExtract{false, true, kModeFlags, "a select extract takes the mode bits only"};
+constexpr OptionsPolicy kDitheredEmbed{true, false, kSelectEmbedFlags, "a dithered embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE"};
+constexpr OptionsPolicy kDitheredExtract{true, false, kModeFlags, "a dithered extract takes the mode bits only"};
+// order, coeffs and dither may each be NULL: a NULL dither is the selected call with read-back, all three NULL (or a prefix
+// selection alone) svs_embed_readback* itself; SVS_READBACK is accepted and implied
+constexpr OptionsPolicy kKeyedReadback{false, false, kGrayEmbedFlags,
+                                       "a dithered read-back embed takes the mode bits, SVS_NEAREST, SVS_MINMOVE and SVS_READBACK"};
 
-// svs_embed_dev, svs_embed_ordered_dev (order NULL: the call without an order) and svs_embed_readback_dev (d_counts: the
-// read-back counts, device, added to; NULL for none)
-int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order, double delta,
-              int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-              uint64_t *n_embedded, void *stream, uint64_t *d_counts = nullptr, const svs::CoeffTable *coeffs = nullptr,
-              const svs_dither *dither = nullptr) {
+// Such an entry point: its public arguments are checked in this order - the dither, the selection, the flags - and then
+// call(n_ac, options) runs.  With a selection n_ac is ignored and the selection's count rules (options.coeffs stays NULL for a
+// prefix selection: the call without one at n_ac = count).
+template <class Call>
+int with_options(const OptionsPolicy &pol, const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither,
+                 uint32_t flags, int n_ac, Call &&call) {
+    svs::CoeffTable table;
+    GrayOptions o{order, nullptr, dither};
+    if (dither || pol.dither_required)
+        if (int rc = check_dither(dither, order)) return rc;
+    if (coeffs || pol.coeffs_required) {
+        if (int rc = check_coeffs(coeffs, &table, &o.coeffs)) return rc;
+        n_ac = coeffs->count;
+    }
+    if (flags & ~pol.allowed) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: %s", flags, pol.what);
+    return call(n_ac, o);
+}
+
+int check_extract_flags(uint32_t flags) {
+    if (flags & (SVS_READBACK | SVS_NEAREST | SVS_MINMOVE))
+        return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK, SVS_NEAREST and SVS_MINMOVE are embed flags");
+    return SVS_OK;
+}
+
+// every gray device embed call: `o` says what it adds to svs_embed_dev
+int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, double delta, int n_ac,
+              const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded,
+              void *stream, const GrayOptions &o) {
     svs::Geometry g;
     uint64_t total = 0;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
-    if (int rc = check_order(order)) return rc;
+    if (int rc = check_order(o.order)) return rc;
     if (total == 0) return SVS_OK;
     if (!d_gray || !d_stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
     if (((uintptr_t)d_gray % 8) || ((uintptr_t)d_stego % 8))
         return fail(SVS_ERR_INVALID_ARG, "plane pointers must be 8-byte aligned");
     svs::RouteArgs ra = route_args(delta, g, total, n_bits, bit_offset, flags, false);
-    ra.keyed = order != nullptr;
+    ra.keyed = o.order != nullptr;
     ra.readback = (flags & SVS_READBACK) != 0;
-    ra.coeffs = coeffs;   // the select calls: n_ac == coeffs->count
-    ra.dithered = dither != nullptr;
+    ra.coeffs = o.coeffs;   // the select calls: n_ac == coeffs->count
+    ra.dithered = o.dither != nullptr;
     const svs::EmbedPlan p = svs::plan_embed(ra);
     if (p.use > 0) {
         if (!d_bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
@@ -789,31 +837,28 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
         if (bit_offset + p.use < bit_offset) return fail(SVS_ERR_INVALID_ARG, "bit_offset + n_bits overflows");
     }
     if (flags & ~kGrayEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    if (d_counts && ((uintptr_t)d_counts % 8)) return fail(SVS_ERR_INVALID_ARG, "counts pointer must be 8-byte aligned");
+    if (o.d_counts && ((uintptr_t)o.d_counts % 8)) return fail(SVS_ERR_INVALID_ARG, "counts pointer must be 8-byte aligned");
     if (p.n_words >= (1ull << 32)) return fail(SVS_ERR_INVALID_ARG, "payload too large for one call");
     if (p.path == EmbedPath::COPY && d_gray == d_stego) return SVS_OK;
     const bool two = p.two_blocks && rows_allow_two_blocks(planes, d_gray, d_stego);
     const uint32_t *bits = p.use ? reinterpret_cast<const uint32_t *>(d_bits_packed) : nullptr;
-    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g, bits, order_args(order, g), coeffs,
-                              dither_args(dither)))
-        return rc;
+    const svs::KernelOptions k = o.kernel_forms(g);
+    if (int rc = launch_embed(p, two, total, (hipStream_t)stream, d_gray, d_stego, g, bits, k)) return rc;
     if (p.readback && p.use > 0)
-        if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, d_counts, order_args(order, g),
-                                     svs::ColourParams{}, SVS_RB_GRAY, coeffs, dither_args(dither)))
+        if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, o.d_counts, k, svs::ColourParams{}, SVS_RB_GRAY))
             return rc;
     if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
 }
 
-// svs_extract_dev and svs_extract_ordered_dev
-int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
-                uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream,
-                const svs::CoeffTable *coeffs = nullptr, const svs_dither *dither = nullptr) {
+// every gray device extract call
+int extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, int n_ac, uint8_t *d_bits_packed_out,
+                uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream, const GrayOptions &o) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
-    if (int rc = check_order(order)) return rc;
-    if (flags & (SVS_READBACK | SVS_NEAREST | SVS_MINMOVE)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK, SVS_NEAREST and SVS_MINMOVE are embed flags");
+    if (int rc = check_order(o.order)) return rc;
+    if (int rc = check_extract_flags(flags)) return rc;
     if (cap == 0) return SVS_OK;
     if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
@@ -821,16 +866,13 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block
     const uint64_t bytes = (cap + 7) / 8;
     if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
     svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
-    ra.keyed = order != nullptr;
-    ra.coeffs = coeffs;   // the select calls: n_ac == coeffs->count
-    ra.dithered = dither != nullptr;
+    ra.keyed = o.order != nullptr;
+    ra.coeffs = o.coeffs;   // the select calls: n_ac == coeffs->count
+    ra.dithered = o.dither != nullptr;
     const svs::ExtractPlan p = svs::plan_extract(ra);
     // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
-    if (p.path != ExtractPath::ZEROS && (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED)))
-        return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, order_args(order, g), coeffs,
-                                dither_args(dither)))
-        return rc;
+    if (p.path != ExtractPath::ZEROS && (flags & ~kModeFlags)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, o.kernel_forms(g))) return rc;
     if (n_bits_out) *n_bits_out = cap;
     return SVS_OK;
 }
@@ -842,25 +884,25 @@ extern "C" {
 int svs_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, double delta, int n_ac,
                   const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                   uint64_t *n_embedded, void *stream) {
-    return embed_dev(d_gray, d_stego, planes, nullptr, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream);
+    return embed_dev(d_gray, d_stego, planes, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream, GrayOptions{});
 }
 
 int svs_embed_ordered_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
                           double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
                           uint32_t flags, uint64_t *n_embedded, void *stream) {
-    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream);
+    return embed_dev(d_gray, d_stego, planes, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream, GrayOptions{order});
 }
 
 int svs_extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, int n_ac,
                     uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
                     void *stream) {
-    return extract_dev(d_gray, planes, nullptr, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream);
+    return extract_dev(d_gray, planes, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, GrayOptions{});
 }
 
 int svs_extract_ordered_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, double delta,
                             int n_ac, uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
                             uint64_t *n_bits_out, void *stream) {
-    return extract_dev(d_gray, planes, order, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream);
+    return extract_dev(d_gray, planes, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, GrayOptions{order});
 }
 
 static bool ranges_overlap(const void *a, const void *b, uint64_t span) {
@@ -882,18 +924,17 @@ static void copy_gray_reference(uint8_t *dst, const uint8_t *gray, const svs_pla
 
 // svs_embed (payload = packed MSB-first bits, indexed by bit_offset) and svs_embed_str (payload = n_bits '0' / '1' characters,
 // bit_offset = 0) share everything but the way the payload reaches the device
-// (svs_embed_ordered: a packed payload and an order)
-// (svs_embed_readback: counts receives the read-back counts; the other calls pass NULL)
+// (`o`: what the call adds to svs_embed, with a packed payload; o.counts receives the read-back counts)
 static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out, const svs_planes *planes, double delta, int n_ac,
                       const uint8_t *bits_packed, const char *bits_ascii, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
-                      uint64_t *n_embedded, const svs_block_order *order = nullptr, svs_readback_counts *counts = nullptr,
-                      const svs::CoeffTable *coeffs = nullptr, const svs_dither *dither = nullptr) {
+                      uint64_t *n_embedded, const GrayOptions &o) {
     svs::Geometry g;
     uint64_t total = 0;
+    svs_readback_counts *const counts = o.counts;
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
     if (counts) *counts = svs_readback_counts{0, 0};
-    if (int rc = check_order(order)) return rc;
+    if (int rc = check_order(o.order)) return rc;
     if (total == 0) return SVS_OK;
     if (!gray || !stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
     if (flags & ~kGrayEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
@@ -926,12 +967,11 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
             const int rc = embed_chunks(
                 c, planes, 1, gray, g.n_ac, use, n_bits, rebased,
                 [&](const svs_planes &sub, int64_t off, int32_t f0, uint64_t chunk_offset, uint64_t budget, uint64_t *done, hipStream_t up) {
-                    // keyed: whole frames - the chunk's first frame is clip frame order->first_frame + f0
-                    const svs_block_order o{order ? order->key : 0u, order ? order->first_frame + (uint32_t)f0 : 0u, 0u};
-                    // dithered: whole frames too, so that a chunk boundary never changes a block's (t, i)
-                    const svs_dither di{dither ? dither->key : 0u, dither ? dither->first_frame + (uint32_t)f0 : 0u, 0u};
-                    return embed_dev(d + off, d + off, &sub, order ? &o : nullptr, delta, n_ac, static_cast<const uint8_t *>(c.bits.p),
-                                     chunk_offset, budget, flags, done, up, d_counts, coeffs, dither ? &di : nullptr);
+                    // keyed or dithered: whole frames, so that a chunk boundary never changes a block's (t, i)
+                    svs_block_order order;
+                    svs_dither dither;
+                    return embed_dev(d + off, d + off, &sub, delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset, budget,
+                                     flags, done, up, o.chunk((uint32_t)f0, d_counts, &order, &dither));
                 },
                 [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {
                     // back: pixel bytes only (padding in the caller's stego buffer is left alone)
@@ -948,7 +988,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                     }
                     return (int)SVS_OK;
                 },
-                &done_total, order != nullptr || dither != nullptr);
+                &done_total, o.order != nullptr || o.dither != nullptr);
             if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, 16, hipMemcpyDeviceToHost, c.st[0]));
             // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
             // thread would only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first.)
@@ -963,20 +1003,22 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
 
 int svs_embed(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, double delta, int n_ac,
               const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
-    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded);
+    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded,
+                      GrayOptions{});
 }
 
 int svs_embed_ordered(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order, double delta,
                       int n_ac, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                       uint64_t *n_embedded) {
-    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded, order);
+    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded,
+                      GrayOptions{order});
 }
 
 int svs_embed_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
                            double delta, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits,
                            uint32_t flags, uint64_t *n_embedded, uint64_t *d_counts, void *stream) {
-    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK, n_embedded,
-                     stream, d_counts);
+    return embed_dev(d_gray, d_stego, planes, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK, n_embedded, stream,
+                     GrayOptions{order, nullptr, nullptr, d_counts});
 }
 
 int svs_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order, double delta,
@@ -984,7 +1026,7 @@ int svs_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *pl
                        uint64_t *n_embedded, svs_readback_counts *counts) {
     svs_readback_counts none;
     return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags | SVS_READBACK,
-                      n_embedded, order, counts ? counts : &none);
+                      n_embedded, GrayOptions{order, nullptr, nullptr, nullptr, counts ? counts : &none});
 }
 
 // every character '0' or '1'?  One OR-reduction over the bytes (vectorised: about 0.05 ms per million characters)
@@ -1011,7 +1053,8 @@ int svs_embed_str(const uint8_t *gray, uint8_t *gray_ref_out, uint8_t *stego, co
         if (gray_ref_out != gray && ranges_overlap(gray_ref_out, gray, span))
             return fail(SVS_ERR_INVALID_ARG, "gray_ref_out must be the gray buffer itself or not overlap it");
     }
-    return embed_host(gray, stego, gray_ref_out, planes, delta, n_ac, nullptr, bits_ascii ? bits_ascii : "", 0, n_chars, flags, n_embedded);
+    return embed_host(gray, stego, gray_ref_out, planes, delta, n_ac, nullptr, bits_ascii ? bits_ascii : "", 0, n_chars, flags, n_embedded,
+                      GrayOptions{});
 }
 
 int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, uint8_t *bits_packed_out,
@@ -1019,15 +1062,14 @@ int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int
     return svs_extract_ordered(gray, planes, nullptr, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out);
 }
 
-// svs_extract_ordered (order NULL: svs_extract) and svs_extract_select
-static int extract_host(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
-                        uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
-                        const svs::CoeffTable *coeffs = nullptr, const svs_dither *dither = nullptr) {
+// every gray host extract call
+static int extract_host(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, uint8_t *bits_packed_out,
+                        uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, const GrayOptions &o) {
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
-    if (int rc = check_order(order)) return rc;
-    if (flags & (SVS_READBACK | SVS_NEAREST | SVS_MINMOVE)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK, SVS_NEAREST and SVS_MINMOVE are embed flags");
+    if (int rc = check_order(o.order)) return rc;
+    if (int rc = check_extract_flags(flags)) return rc;
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     const uint64_t bytes = (cap + 7) / 8;
@@ -1035,14 +1077,14 @@ static int extract_host(const uint8_t *gray, const svs_planes *planes, const svs
     return extract_staged(
         gray, span_bytes(planes), bytes, 0, n_bits_out,
         [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
-            return extract_dev(d_in, planes, order, delta, n_ac, d_bits, d_bytes, flags, got, st, coeffs, dither);
+            return extract_dev(d_in, planes, delta, n_ac, d_bits, d_bytes, flags, got, st, o);
         },
         [&](HostStage &c, hipStream_t st) { return stage_d2h(st, bits_packed_out, c.bits.p, bytes); });
 }
 
 int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
                         uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
-    return extract_host(gray, planes, order, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out);
+    return extract_host(gray, planes, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out, GrayOptions{order});
 }
 
 // ---- coefficient selection ------------------------------------------------------------------------------------------
@@ -1063,152 +1105,94 @@ int svs_coeffs_scan(svs_coeffs *out, int scan, int first, int count) {
 }
 
 // The select calls are the ordered calls at n_ac = coeffs->count with the selection's table; the prefix 1..count passes no
-// table and is the ordered call itself.  The selection and the flags are checked before anything else.
+// table and is the ordered call itself.  The dithered calls are the ordered calls (with a selection: the select calls) with the
+// dither handed down to the plan; coeffs NULL: the row-major prefix 1..n_ac.  The dithered calls with the read-back pass take
+// each of order, coeffs and dither or NULL.  with_options: what is given is checked before anything else.
 int svs_embed_select_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
                          const svs_coeffs *coeffs, double delta, const uint8_t *d_bits_packed, uint64_t bit_offset,
                          uint64_t n_bits, uint32_t flags, uint64_t *n_embedded, void *stream) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
-    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE", flags);
-    return embed_dev(d_gray, d_stego, planes, order, delta, coeffs->count, d_bits_packed, bit_offset, n_bits, flags, n_embedded,
-                     stream, nullptr, sel);
+    return with_options(kSelectEmbed, order, coeffs, nullptr, flags, 0, [&](int n, const GrayOptions &o) {
+        return embed_dev(d_gray, d_stego, planes, delta, n, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream, o);
+    });
 }
 
 int svs_embed_select(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
                      const svs_coeffs *coeffs, double delta, const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits,
                      uint32_t flags, uint64_t *n_embedded) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
-    if (flags & ~kSelectEmbedFlags) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE", flags);
-    return embed_host(gray, stego, nullptr, planes, delta, coeffs->count, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded,
-                      order, nullptr, sel);
+    return with_options(kSelectEmbed, order, coeffs, nullptr, flags, 0, [&](int n, const GrayOptions &o) {
+        return embed_host(gray, stego, nullptr, planes, delta, n, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded, o);
+    });
 }
 
 int svs_extract_select_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                            double delta, uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags,
                            uint64_t *n_bits_out, void *stream) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED))
-        return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select extract takes the mode bits only", flags);
-    return extract_dev(d_gray, planes, order, delta, coeffs->count, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream,
-                       sel);
+    return with_options(kSelectExtract, order, coeffs, nullptr, flags, 0, [&](int n, const GrayOptions &o) {
+        return extract_dev(d_gray, planes, delta, n, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, o);
+    });
 }
 
 int svs_extract_select(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                        double delta, uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = check_coeffs(coeffs, &table, &sel)) return rc;
-    if (flags & ~(SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED))
-        return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a select extract takes the mode bits only", flags);
-    return extract_host(gray, planes, order, delta, coeffs->count, bits_packed_out, out_capacity_bytes, flags, n_bits_out, sel);
+    return with_options(kSelectExtract, order, coeffs, nullptr, flags, 0, [&](int n, const GrayOptions &o) {
+        return extract_host(gray, planes, delta, n, bits_packed_out, out_capacity_bytes, flags, n_bits_out, o);
+    });
 }
-
-// ---- keyed dither modulation ----------------------------------------------------------------------------------------
-// The dithered calls are the ordered calls (with a selection: the select calls) with the dither handed down to the plan.  The
-// dither, the selection and the flags are checked before anything else.  coeffs NULL: the row-major prefix 1..n_ac; else n_ac
-// is ignored and the selection's count rules (*sel = NULL for a prefix selection: the call without one at n_ac = count).
-static int dithered_args(const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither, uint32_t flags,
-                         uint32_t allowed, const char *what, svs::CoeffTable *table, const svs::CoeffTable **sel, int *n_ac) {
-    if (int rc = check_dither(dither, order)) return rc;
-    *sel = nullptr;
-    if (coeffs) {
-        if (int rc = check_coeffs(coeffs, table, sel)) return rc;
-        *n_ac = coeffs->count;
-    }
-    if (flags & ~allowed) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: %s", flags, what);
-    return SVS_OK;
-}
-static const char kDitheredEmbedFlags[] = "a dithered embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE";
-static const char kDitheredExtractFlags[] = "a dithered extract takes the mode bits only";
 
 int svs_embed_dithered_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
                            const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
                            const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                            uint64_t *n_embedded, void *stream) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = dithered_args(order, coeffs, dither, flags, kSelectEmbedFlags, kDitheredEmbedFlags, &table, &sel, &n_ac)) return rc;
-    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream,
-                     nullptr, sel, dither);
+    return with_options(kDitheredEmbed, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return embed_dev(d_gray, d_stego, planes, delta, n, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream, o);
+    });
 }
 
 int svs_embed_dithered(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
                        const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac, const uint8_t *bits_packed,
                        uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = dithered_args(order, coeffs, dither, flags, kSelectEmbedFlags, kDitheredEmbedFlags, &table, &sel, &n_ac)) return rc;
-    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded, order,
-                      nullptr, sel, dither);
+    return with_options(kDitheredEmbed, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return embed_host(gray, stego, nullptr, planes, delta, n, bits_packed, nullptr, bit_offset, n_bits, flags, n_embedded, o);
+    });
 }
 
 int svs_extract_dithered_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order,
                              const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
                              uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out,
                              void *stream) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = dithered_args(order, coeffs, dither, flags, SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED, kDitheredExtractFlags, &table,
-                               &sel, &n_ac))
-        return rc;
-    return extract_dev(d_gray, planes, order, delta, n_ac, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, sel,
-                       dither);
+    return with_options(kDitheredExtract, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return extract_dev(d_gray, planes, delta, n, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, o);
+    });
 }
 
 int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                          const svs_dither *dither, double delta, int n_ac, uint8_t *bits_packed_out, uint64_t out_capacity_bytes,
                          uint32_t flags, uint64_t *n_bits_out) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = dithered_args(order, coeffs, dither, flags, SVS_EXACT_POCKETFFT | SVS_EXACT_GUARDED, kDitheredExtractFlags, &table,
-                               &sel, &n_ac))
-        return rc;
-    return extract_host(gray, planes, order, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out, sel, dither);
-}
-
-// The dithered calls with the read-back pass.  order, coeffs and dither may each be NULL here: a NULL dither is the selected
-// call with read-back, all three NULL (or a prefix selection alone) svs_embed_readback* itself.  What is given is checked as
-// the dithered calls check it, before anything else; SVS_READBACK is accepted and implied.
-static int keyed_readback_args(const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither, uint32_t flags,
-                               svs::CoeffTable *table, const svs::CoeffTable **sel, int *n_ac) {
-    if (dither)
-        if (int rc = check_dither(dither, order)) return rc;
-    *sel = nullptr;
-    if (coeffs) {
-        if (int rc = check_coeffs(coeffs, table, sel)) return rc;
-        *n_ac = coeffs->count;
-    }
-    if (flags & ~(kSelectEmbedFlags | SVS_READBACK))
-        return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: a dithered read-back embed takes the mode bits, SVS_NEAREST, SVS_MINMOVE and SVS_READBACK", flags);
-    return SVS_OK;
+    return with_options(kDitheredExtract, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return extract_host(gray, planes, delta, n, bits_packed_out, out_capacity_bytes, flags, n_bits_out, o);
+    });
 }
 
 int svs_embed_dithered_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
                                     const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
                                     const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                                     uint64_t *n_embedded, uint64_t *d_counts, void *stream) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = keyed_readback_args(order, coeffs, dither, flags, &table, &sel, &n_ac)) return rc;
-    return embed_dev(d_gray, d_stego, planes, order, delta, n_ac, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK, n_embedded,
-                     stream, d_counts, sel, dither);
+    return with_options(kKeyedReadback, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.d_counts = d_counts;
+        return embed_dev(d_gray, d_stego, planes, delta, n, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK, n_embedded, stream, o);
+    });
 }
 
 int svs_embed_dithered_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
                                 const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
                                 const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                                 uint64_t *n_embedded, svs_readback_counts *counts) {
-    svs::CoeffTable table;
-    const svs::CoeffTable *sel = nullptr;
-    if (int rc = keyed_readback_args(order, coeffs, dither, flags, &table, &sel, &n_ac)) return rc;
-    svs_readback_counts none;
-    return embed_host(gray, stego, nullptr, planes, delta, n_ac, bits_packed, nullptr, bit_offset, n_bits, flags | SVS_READBACK,
-                      n_embedded, order, counts ? counts : &none, sel, dither);
+    return with_options(kKeyedReadback, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        svs_readback_counts none;
+        o.counts = counts ? counts : &none;
+        return embed_host(gray, stego, nullptr, planes, delta, n, bits_packed, nullptr, bit_offset, n_bits, flags | SVS_READBACK,
+                          n_embedded, o);
+    });
 }
 
 int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, char *bits_ascii_out,
@@ -1216,7 +1200,7 @@ int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta,
     svs::Geometry g;
     uint64_t total = 0, cap = 0;
     if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
-    if (flags & (SVS_READBACK | SVS_NEAREST | SVS_MINMOVE)) return fail(SVS_ERR_INVALID_ARG, "SVS_READBACK, SVS_NEAREST and SVS_MINMOVE are embed flags");
+    if (int rc = check_extract_flags(flags)) return rc;
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_ascii_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if (int rc = check_capacity(cap, out_capacity_chars, "characters")) return rc;

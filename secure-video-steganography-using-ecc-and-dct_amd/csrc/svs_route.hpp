@@ -6,6 +6,7 @@
 
 #include "svs_block.hpp"
 #include "svs_index.hpp"   // kEighth, the tile map the plans name
+#include "svs_order.hpp"   // BlockOrderArgs
 
 namespace svs {
 
@@ -164,6 +165,40 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
     p.keyed = a.keyed;
     return p;
+}
+
+// ---- what a launch passes for the call's order, selection and dither ----------------------------------------------------------
+// A gray call's options in the kernels' forms (csrc/svs_capi.hip derives them once per call).  ord: the order of a keyed call;
+// coeffs: the table of a non-prefix selection, NULL for none; dith: seed and first_frame of the call's dither - `on` and `sel`
+// are set by the rules below.  All zero: the plain call.
+struct KernelOptions {
+    BlockOrderArgs ord;
+    const CoeffTable *coeffs;
+    DitherArgs dith;
+};
+
+struct LaunchTables {   // the `sel` and `dith` arguments of the two exact kernels
+    CoeffTable sel;
+    DitherArgs dith;
+};
+
+// embed_exact_kernel: `sel` is the call's selection where the plan is selected, else empty (count 0: the row-major prefix).  The
+// dither is on only where the plan says so (EXACT, rows = 8); the dithered side runs the selected loop alone, with the prefix
+// table of n_ac where the call has no selection.
+inline LaunchTables embed_tables(const EmbedPlan &p, const KernelOptions &k) {
+    const CoeffTable sel = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
+    return {sel, {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u,
+                  !p.dithered ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)}};
+}
+
+// readback_kernel's keyed form (a selected or dithered plan): one table, the call's selection or the prefix table of n_ac
+inline DitherArgs readback_tables(const EmbedPlan &p, const KernelOptions &k) {
+    return {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, p.selected && k.coeffs ? *k.coeffs : make_prefix_table(p.n_ac)};
+}
+
+// extract_exact_kernel reads the selection from `sel` on either side: its dither carries no table
+inline LaunchTables extract_tables(const ExtractPlan &p, const KernelOptions &k) {
+    return {p.selected && k.coeffs ? *k.coeffs : CoeffTable{}, {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, CoeffTable{}}};
 }
 
 }  // namespace svs

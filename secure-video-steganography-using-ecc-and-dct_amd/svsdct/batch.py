@@ -134,24 +134,9 @@ def block_order(key, first_frame: int = 0) -> BlockOrder | None:
     return BlockOrder(check_key(key), first_frame, 0)
 
 
-def _order_ref(order):
-    """a pointer to an optional struct argument (svs_block_order, svs_dither), NULL for None"""
-    return C.byref(order) if order is not None else None
-
-
-def _coeffs_arg(coeffs, n_ac, readback=False):
-    """`coeffs` of a gray call -> None (no selection) or the C ABI's svs_coeffs.  A spec string ("zigzag", "zigzag:6",
-    "rowmajor") resolves with the call's n_ac; an explicit list must have len == n_ac (svsdct/coeffs.py)."""
-    sel = _coeffs.selection(coeffs, clamp_ac(n_ac))
-    if sel is None:
-        return None
-    if readback:
-        raise ValueError("a coefficient selection has no read-back form under readback=True: use readback_keyed=True")
-    return _coeffs.native_coeffs(sel)
-
-
-def _coeffs_ref(sel):
-    return None if sel is None else C.byref(sel)
+def _ref(struct):
+    """a pointer to an optional struct argument (svs_block_order, svs_coeffs, svs_dither), NULL for None"""
+    return C.byref(struct) if struct is not None else None
 
 
 def _no_coeffs(coeffs):
@@ -191,6 +176,66 @@ class ReadbackCounts(NamedTuple):
     unrepaired: int
 
 
+class _GrayCall(NamedTuple):
+    """the gray keywords of a call, resolved: the structs it adds to the plain call and the entry points that take them"""
+    order: BlockOrder | None
+    sel: native.Coeffs | None
+    dith: Dither | None
+    stem: str               # key of _GRAY_CALLS
+
+
+# C symbol stem (svs_embed<stem>[_dev], svs_extract<stem>[_dev]) -> (the struct pointers that lead its argument list behind
+# the planes, takes n_ac, takes counts)
+_GRAY_CALLS = {
+    "": ((), True, False),
+    "_ordered": (("order",), True, False),
+    "_select": (("order", "sel"), False, False),
+    "_dithered": (("order", "sel", "dith"), True, False),
+    "_readback": (("order",), True, True),
+    "_dithered_readback": (("order", "sel", "dith"), True, True),
+}
+
+
+def _resolve(n_ac, order=None, block_key=None, first_frame=None, coeffs=None, dither_key=None, readback=False,
+             readback_keyed=False) -> _GrayCall:
+    """The gray keywords -> the call they make; every ValueError they can cause is raised here, before the library is loaded.
+    order: a BlockOrder, or block_key and first_frame to make one of.  coeffs: a spec string ("zigzag", "zigzag:6",
+    "rowmajor") resolves with the call's n_ac, an explicit list must have len == n_ac (svsdct/coeffs.py).  The dither shares
+    first_frame, by default the order's (0 without one).  readback_keyed with neither a selection nor a dither is readback."""
+    _one_readback(readback, readback_keyed)
+    if block_key is not None:
+        order = block_order(block_key, first_frame)
+    sel = _coeffs.selection(coeffs, clamp_ac(n_ac))
+    if sel is not None:
+        if readback:
+            raise ValueError("a coefficient selection has no read-back form under readback=True: use readback_keyed=True")
+        sel = _coeffs.native_coeffs(sel)
+    if first_frame is None:
+        first_frame = int(order.first_frame) if order is not None else 0
+    dith = dither_arg(dither_key, first_frame, readback)
+    if readback_keyed and (sel is not None or dith is not None):
+        stem = "_dithered_readback"
+    elif dith is not None:
+        stem = "_dithered"
+    elif readback or readback_keyed:
+        stem = "_readback"
+    elif sel is not None:
+        stem = "_select"
+    else:
+        stem = "_ordered" if order is not None else ""
+    return _GrayCall(order, sel, dith, stem)
+
+
+def _gray_call(lib, verb, call: _GrayCall, front, delta, n_ac, back, counts=None, stream=()) -> None:
+    """svs_<verb><stem>(*front, <the stem's struct pointers>, delta, [n_ac], *back, [counts]), or with stream = (handle,) its
+    _dev form with the stream last; raises unless it returns SVS_OK"""
+    structs, takes_n_ac, takes_counts = _GRAY_CALLS[call.stem]
+    name = f"svs_{verb}{call.stem}" + ("_dev" if stream else "")
+    args = [*front, *(_ref(getattr(call, s)) for s in structs), float(delta), *([int(n_ac)] if takes_n_ac else ()), *back,
+            *([counts] if takes_counts else ()), *stream]
+    native.check(getattr(lib, name)(*args), name)
+
+
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False):
@@ -223,12 +268,7 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     dither_key - every payload block is read back with the selected / dithered extraction's own verdict and repaired where it
     fails.  With neither it makes the readback call.  ValueError together with readback.
     Returns (stego uint8 [F,H,W], n_embedded), with readback or readback_keyed (stego, n_embedded, ReadbackCounts)."""
-    _one_readback(readback, readback_keyed)
-    order = block_order(block_key, first_frame)
-    sel = _coeffs_arg(coeffs, n_ac, readback)
-    dith = dither_arg(dither_key, first_frame, readback)
-    if readback_keyed and sel is None and dith is None:
-        readback = True
+    call = _resolve(n_ac, None, block_key, first_frame, coeffs, dither_key, readback, readback_keyed)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -244,41 +284,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     stego = pinned_empty(stack.shape)      # page-locked: the download lands in it by DMA, no staging copy, no page faults
     done = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    if readback_keyed and not readback:
-        counts = native.ReadbackCounts()
-        rc = lib.svs_embed_dithered_readback(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order),
-                                             _coeffs_ref(sel), _order_ref(dith), float(delta), int(n_ac), packed.ctypes.data,
-                                             int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done),
-                                             C.byref(counts))
-        native.check(rc, "svs_embed_dithered_readback")
+    counts = native.ReadbackCounts()
+    _gray_call(lib, "embed", call, [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], delta, n_ac,
+               [packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done)],
+               C.byref(counts))
+    if _GRAY_CALLS[call.stem][2]:
         return stego, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
-    if dith is not None:
-        rc = lib.svs_embed_dithered(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
-                                    C.byref(dith), float(delta), int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits),
-                                    embed_flags(mode, nearest, minmove), C.byref(done))
-        native.check(rc, "svs_embed_dithered")
-        return stego, int(done.value)
-    if readback:
-        counts = native.ReadbackCounts()
-        rc = lib.svs_embed_readback(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), float(delta),
-                                    int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove),
-                                    C.byref(done), C.byref(counts))
-        native.check(rc, "svs_embed_readback")
-        return stego, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
-    if sel is not None:
-        rc = lib.svs_embed_select(stack.ctypes.data, stego.ctypes.data, C.byref(planes), _order_ref(order), C.byref(sel),
-                                  float(delta), packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove),
-                                  C.byref(done))
-        native.check(rc, "svs_embed_select")
-    elif order is None:
-        rc = lib.svs_embed(stack.ctypes.data, stego.ctypes.data, C.byref(planes), float(delta), int(n_ac),
-                           packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done))
-        native.check(rc, "svs_embed")
-    else:
-        rc = lib.svs_embed_ordered(stack.ctypes.data, stego.ctypes.data, C.byref(planes), C.byref(order), float(delta),
-                                   int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove),
-                                   C.byref(done))
-        native.check(rc, "svs_embed_ordered")
     return stego, int(done.value)
 
 
@@ -288,9 +299,7 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     sender's key and clip frame index).  coeffs: as embed_frames (the sender's selection).  dither_key: as embed_frames (the
     sender's dither key).
     Returns (packed uint8 [ceil(n_bits/8)], n_bits)."""
-    order = block_order(block_key, first_frame)
-    sel = _coeffs_arg(coeffs, n_ac)
-    dith = dither_arg(dither_key, first_frame)
+    call = _resolve(n_ac, None, block_key, first_frame, coeffs, dither_key)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
@@ -299,22 +308,8 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     out = np.zeros(max(4, (cap + 7) // 8 + (-((cap + 7) // 8)) % 4), np.uint8)
     got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    if dith is not None:
-        rc = lib.svs_extract_dithered(stack.ctypes.data, C.byref(planes), _order_ref(order), _coeffs_ref(sel), C.byref(dith),
-                                      float(delta), int(n_ac), out.ctypes.data, out.size, mode_flags(mode), C.byref(got))
-        native.check(rc, "svs_extract_dithered")
-    elif sel is not None:
-        rc = lib.svs_extract_select(stack.ctypes.data, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
-                                    out.ctypes.data, out.size, mode_flags(mode), C.byref(got))
-        native.check(rc, "svs_extract_select")
-    elif order is None:
-        rc = lib.svs_extract(stack.ctypes.data, C.byref(planes), float(delta), int(n_ac), out.ctypes.data,
-                             out.size, mode_flags(mode), C.byref(got))
-        native.check(rc, "svs_extract")
-    else:
-        rc = lib.svs_extract_ordered(stack.ctypes.data, C.byref(planes), C.byref(order), float(delta), int(n_ac),
-                                     out.ctypes.data, out.size, mode_flags(mode), C.byref(got))
-        native.check(rc, "svs_extract_ordered")
+    _gray_call(lib, "extract", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac,
+               [out.ctypes.data, out.size, mode_flags(mode), C.byref(got)])
     n = int(got.value)
     return out[: (n + 7) // 8], n
 
@@ -387,13 +382,6 @@ def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: s
 
 
 # ---- device-pointer level -------------------------------------------------------------------
-def _shared_first_frame(order: BlockOrder | None, first_frame: int | None) -> int:
-    """the clip frame index a dither shares with the call's block order"""
-    if first_frame is None:
-        return int(order.first_frame) if order is not None else 0
-    return int(first_frame)
-
-
 def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_packed: int,
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
@@ -407,44 +395,12 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
     frame index is first_frame, by default the order's (0 without one) - the two must agree.  readback_keyed: the read-back
     pass under coeffs and / or dither_key (svs_embed_dithered_readback_dev; d_counts as with readback); with neither it makes
     the readback call; ValueError together with readback."""
-    _one_readback(readback, readback_keyed)
+    _one_readback(readback, readback_keyed)      # ahead of the mode's ValueError
     done = C.c_uint64(0)
     flags = embed_flags(mode, nearest, minmove)
-    sel = _coeffs_arg(coeffs, n_ac, readback)
-    dith = dither_arg(dither_key, _shared_first_frame(order, first_frame), readback)
-    if readback_keyed and sel is None and dith is None:
-        readback = True
-    if readback_keyed and not readback:
-        rc = native.load().svs_embed_dithered_readback_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
-                                                           _order_ref(dith), float(delta), int(n_ac), d_bits_packed,
-                                                           int(bit_offset), int(n_bits), flags, C.byref(done),
-                                                           d_counts or None, stream or None)
-        native.check(rc, "svs_embed_dithered_readback_dev")
-    elif dith is not None:
-        rc = native.load().svs_embed_dithered_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), _coeffs_ref(sel),
-                                                  C.byref(dith), float(delta), int(n_ac), d_bits_packed, int(bit_offset),
-                                                  int(n_bits), flags, C.byref(done), stream or None)
-        native.check(rc, "svs_embed_dithered_dev")
-    elif sel is not None:
-        rc = native.load().svs_embed_select_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
-                                                d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done),
-                                                stream or None)
-        native.check(rc, "svs_embed_select_dev")
-    elif readback:
-        rc = native.load().svs_embed_readback_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), float(delta),
-                                                  int(n_ac), d_bits_packed, int(bit_offset), int(n_bits), flags,
-                                                  C.byref(done), d_counts or None, stream or None)
-        native.check(rc, "svs_embed_readback_dev")
-    elif order is None:
-        rc = native.load().svs_embed_dev(d_gray, d_stego, C.byref(planes), float(delta), int(n_ac), d_bits_packed,
-                                         int(bit_offset), int(n_bits), flags, C.byref(done),
-                                         stream or None)
-        native.check(rc, "svs_embed_dev")
-    else:
-        rc = native.load().svs_embed_ordered_dev(d_gray, d_stego, C.byref(planes), _order_ref(order), float(delta),
-                                                 int(n_ac), d_bits_packed, int(bit_offset), int(n_bits), flags,
-                                                 C.byref(done), stream or None)
-        native.check(rc, "svs_embed_ordered_dev")
+    call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key, readback, readback_keyed)
+    _gray_call(native.load(), "embed", call, [d_gray, d_stego, C.byref(planes)], delta, n_ac,
+               [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], d_counts or None, (stream or None,))
     return int(done.value)
 
 
@@ -454,28 +410,9 @@ def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, ou
     """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order, coeffs, dither_key,
     first_frame: as embed_device."""
     got = C.c_uint64(0)
-    sel = _coeffs_arg(coeffs, n_ac)
-    dith = dither_arg(dither_key, _shared_first_frame(order, first_frame))
-    if dith is not None:
-        rc = native.load().svs_extract_dithered_dev(d_gray, C.byref(planes), _order_ref(order), _coeffs_ref(sel), C.byref(dith),
-                                                    float(delta), int(n_ac), d_bits_out, int(out_capacity_bytes),
-                                                    mode_flags(mode), C.byref(got), stream or None)
-        native.check(rc, "svs_extract_dithered_dev")
-    elif sel is not None:
-        rc = native.load().svs_extract_select_dev(d_gray, C.byref(planes), _order_ref(order), C.byref(sel), float(delta),
-                                                  d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got),
-                                                  stream or None)
-        native.check(rc, "svs_extract_select_dev")
-    elif order is None:
-        rc = native.load().svs_extract_dev(d_gray, C.byref(planes), float(delta), int(n_ac), d_bits_out,
-                                           int(out_capacity_bytes), mode_flags(mode), C.byref(got),
-                                           stream or None)
-        native.check(rc, "svs_extract_dev")
-    else:
-        rc = native.load().svs_extract_ordered_dev(d_gray, C.byref(planes), _order_ref(order), float(delta), int(n_ac),
-                                                   d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got),
-                                                   stream or None)
-        native.check(rc, "svs_extract_ordered_dev")
+    call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
+    _gray_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac,
+               [d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)], None, (stream or None,))
     return int(got.value)
 
 
@@ -509,18 +446,12 @@ def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Pla
     orp, ofp = out_pitches or (3 * planes.width, 3 * planes.width * planes.height)
     keep, wptr = _weights_arg(weights)
     done = C.c_uint64(0)
-    if readback:
-        rc = native.load().svs_embed_bgr_readback_dev(d_bgr_in, irp, ifp, d_bgr_out, orp, ofp, d_gray_ref or None,
-                                                      C.byref(planes), wptr, float(delta), int(n_ac), d_bits_packed,
-                                                      int(bit_offset), int(n_bits), _bgr_flags(mode, keep_colour, nearest, minmove),
-                                                      C.byref(done), d_counts or None, stream or None)
-        native.check(rc, "svs_embed_bgr_readback_dev")
-        return int(done.value)
-    rc = native.load().svs_embed_bgr_dev(d_bgr_in, irp, ifp, d_bgr_out, orp, ofp, d_gray_ref or None,
-                                         C.byref(planes), wptr, float(delta), int(n_ac), d_bits_packed,
-                                         int(bit_offset), int(n_bits), _bgr_flags(mode, keep_colour, nearest, minmove), C.byref(done),
-                                         stream or None)
-    native.check(rc, "svs_embed_bgr_dev")
+    name = "svs_embed_bgr" + ("_readback" if readback else "") + "_dev"
+    rc = getattr(native.load(), name)(d_bgr_in, irp, ifp, d_bgr_out, orp, ofp, d_gray_ref or None, C.byref(planes), wptr,
+                                      float(delta), int(n_ac), d_bits_packed, int(bit_offset), int(n_bits),
+                                      _bgr_flags(mode, keep_colour, nearest, minmove), C.byref(done),
+                                      *([d_counts or None] if readback else ()), stream or None)
+    native.check(rc, name)
     return int(done.value)
 
 
@@ -575,19 +506,16 @@ def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int 
     gray = pinned_empty((f, h, w)) if want_gray else None
     keep, wptr = _weights_arg(weights)
     done = C.c_uint64(0)
+    counts = native.ReadbackCounts()
+    name = "svs_embed_bgr" + ("_readback" if readback else "")
+    rc = getattr(lib, name)(stack.ctypes.data, out.ctypes.data, gray.ctypes.data if want_gray else None, C.byref(planes), wptr,
+                            float(delta), int(n_ac), packed.ctypes.data, int(bit_offset), int(n_bits),
+                            _bgr_flags(mode, keep_colour, nearest, minmove), C.byref(done),
+                            *([C.byref(counts)] if readback else ()))
+    native.check(rc, name)
     if readback:
-        counts = native.ReadbackCounts()
-        rc = lib.svs_embed_bgr_readback(stack.ctypes.data, out.ctypes.data, gray.ctypes.data if want_gray else None,
-                                        C.byref(planes), wptr, float(delta), int(n_ac), packed.ctypes.data, int(bit_offset),
-                                        int(n_bits), _bgr_flags(mode, keep_colour, nearest, minmove), C.byref(done), C.byref(counts))
-        native.check(rc, "svs_embed_bgr_readback")
         return out, gray, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
-    rc = lib.svs_embed_bgr(stack.ctypes.data, out.ctypes.data, gray.ctypes.data if want_gray else None,
-                           C.byref(planes), wptr, float(delta), int(n_ac), packed.ctypes.data, int(bit_offset),
-                           int(n_bits), _bgr_flags(mode, keep_colour, nearest, minmove), C.byref(done))
-    native.check(rc, "svs_embed_bgr")
-    used = int(done.value)
-    return out, gray, used
+    return out, gray, int(done.value)
 
 
 def extract_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, device: int = 0, weights=None, dither_key=None):

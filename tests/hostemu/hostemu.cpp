@@ -102,7 +102,7 @@ bool sizes_match(const EmuCall *c, EmuResult *r) {
 
 // ---- embed ---------------------------------------------------------------------------------------------------------------
 
-// The streaming body as the KERNELS launch it (csrc/svs_capi.hip launch_embed; edit the two together): one coefficient row -
+// The streaming body as the KERNELS launch it (csrc/svs_capi.hip launch_embed): one coefficient row -
 // embed_block_guarded; two rows - compile-time n for the GUI's default 10, and for every quantiser but the power-of-two one
 // the in-place form (truncated inverse, stego bytes written over the row dwords, an undecided block left half-written: the
 // kernel rebuilds it from the rows it parked in LDS, the caller here from the frame).  EMU_GENERIC_GUARDED2 forces
@@ -145,8 +145,9 @@ void embed_call(const EmuCall &c, EmuResult &r) {
     r.used = p.use;
     if (p.path == svs::EmbedPath::COPY) return;
     const svs::QimRule rule = svs::rule_from_word(p.qp, r.word);   // what the kernels build from Geometry::pad
-    // the dithered side runs the selected loop alone: the selection, or the prefix table of n_ac (launch_embed, svs_capi.hip)
-    const svs::CoeffTable *sel = p.selected || p.dithered ? &s.table : nullptr;
+    // the table the exact kernel reads, as it picks it from its launch arguments (svs_route.hpp embed_tables)
+    const svs::LaunchTables t = svs::embed_tables(p, svs::KernelOptions{{}, s.given ? &s.table : nullptr, {}});
+    const svs::CoeffTable *sel = t.dith.on ? &t.dith.sel : t.sel.count ? &t.sel : nullptr;
     const bool streaming = p.path == svs::EmbedPath::STREAMING && c.streaming_bodies;
     const int rows = c.exact_rows ? c.exact_rows : p.rows;
     const int variant = p.use ? c.variant : EMU_AS_LAUNCHED;   // the test-only forms are forms of a block with payload
