@@ -468,6 +468,54 @@ int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const sv
                          const svs_dither *dither, double delta, int n_ac, uint8_t *bits_packed_out, uint64_t out_capacity_bytes,
                          uint32_t flags, uint64_t *n_bits_out);
 
+/* ---- soft-decision extraction: a reliability byte per payload bit ----------------------------------------
+ * The extract calls above return hard bits, q mod 2 per payload coefficient.  These return, per capacity bit, the hard bit
+ * AND how far the coefficient sits from the nearest decision boundary of its quantiser cell - the quantity SVS_NEAREST,
+ * SVS_MINMOVE, read-back, the selection and the dither all work on at the sending end.  A sender reads from it how much
+ * disturbance a stego clip survives; a receiver sees which frames sit on the lattice; a caller that embedded the payload more
+ * than once (by tiling it: there is no repeat option) combines the copies by their reliabilities (svsdct/soft.py, combine).
+ * The byte is a FORMAT, a contract between builds as the dither's rule is.  Layout: one byte per capacity bit in stream order;
+ * byte i belongs to stream bit i of the hard extract call with the same order, coeffs, dither, delta and n_ac.  For the
+ * payload coefficient with quantiser input x - x = c for a call without a dither, x = c - d under one, c the
+ * pocketfft-identical forward transform and d exactly the dither's d above:
+ *     q    = quant_index(x)                                  (the extract call's own index: int(round(x / (float)delta)))
+ *     x0   = (float)q * (float)delta                         (one float32 multiply, whatever delta is)
+ *     a    = fabsf(x - x0)
+ *     h    = 0.5f * (float)delta
+ *     s    = (float)(254.0 / (double)(float)delta)           (rounded once, on the host)
+ *     m    = clamp((int)((h - a) * s), 0, 127)               (one subtract, one multiply, truncation toward zero)
+ *     byte = ((q & 1) << 7) | m
+ * Every float step is a single IEEE float32 operation with no contraction, in the same order on the host build of the block
+ * bodies and on the device.  byte >> 7 is the hard bit; byte & 127 is the distance from the nearest decision boundary in units
+ * of delta / 254: 127 on the lattice point, 0 on (or, through the roundings of x / delta and q * delta, just past) the boundary.
+ * It is a DISTANCE, not a probability: what it says about the chance of a bit error depends on the disturbance, which the
+ * library does not know.  delta <= 0: every byte is 0.  n_ac clamps to [0, 63]; a capacity of 0 writes nothing.
+ * Limits: the dither is lowbias32's, no cryptographic generator, and a selection says which coefficients are read, nothing
+ * more - a reader without the dither's key sees reliabilities uniform on 0..127 (the comb is gone), one with the wrong
+ * selection reads other coefficients.  Measured on the CPU model only (tests/test_soft_extract_cpu.py; README.md has the
+ * table): at delta = 20, n_ac = 10 on noise in [64, 192) undisturbed reference-rule stego has no reliability below 113 and a
+ * never-embedded frame a mean of 63.5; three tiled copies under uniform pixel noise of +-8 decode with 3 bit errors by soft
+ * vote, 10 by hard majority, 87 - 96 alone.  NOT measured: the call's time on the device (tools/soft_extract_rates.py is
+ * there for it) and any real transcode.
+ * Cost: a soft call always runs the lane-per-block SVS_EXACT_POCKETFFT extract kernel with all eight coefficient rows, whatever
+ * the mode bits say, behind one wave-uniform branch of its eight-row instantiations; every wave assembles its blocks' bytes in
+ * LDS that only this launch requests and copies them out coalesced, each byte written once (no clearing, no atomics).
+ * There is no colour and no _str form.
+ *   order, coeffs, dither : each NULL or as in the dithered calls, and checked as there (svs_coeffs, the reserved fields, equal
+ *            first_frame values when order and dither are both given); with coeffs n_ac is ignored and the count rules.
+ *   d_soft_out / soft_out : at least capacity bytes (else SVS_ERR_CAPACITY); the device pointer 4-byte aligned.  Exactly
+ *            capacity bytes are written.
+ *   flags  : as the extract calls - the mode bits are accepted and change nothing, embed flags and anything else are refused.
+ *   n_bits_out : receives the capacity, the number of bytes written.
+ * Every refusal comes before any device work.  The host form stages as svs_extract does. */
+int svs_soft_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                         const svs_dither *dither, double delta, int n_ac, uint8_t *d_soft_out, uint64_t out_capacity_bytes,
+                         uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+int svs_soft_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                     const svs_dither *dither, double delta, int n_ac, uint8_t *soft_out, uint64_t out_capacity_bytes, uint32_t flags,
+                     uint64_t *n_bits_out);
+
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:
  *   d_counts : NULL, or a device buffer of two uint64 (8-byte aligned) that the call ADDS {blocks repaired, blocks left

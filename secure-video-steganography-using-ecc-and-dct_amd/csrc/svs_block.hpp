@@ -586,6 +586,7 @@ struct DitherArgs {          // by-value argument of the two exact kernels (read
     uint32_t on;             // 0: no dither - the kernel's side that was there before the dither
     CoeffTable sel;          // on: the call's selection, or the prefix table of n_ac (make_prefix_table) - never empty.  The
                              // dithered side's own copy: read from the kernel's `sel` as well, that table went to scratch.
+                             // extract_exact_kernel: empty on its hard sides; the table of its soft side, on or off (SoftArgs)
 };
 
 // host side: the table of `count` indices; false unless they are distinct and in 1..63 (count <= 63)
@@ -1705,6 +1706,70 @@ SVS_HD void extract_block_exact_selected(const uint32_t (&rx)[8], const uint32_t
             if (s < 32u) hi |= bit;
             else lo |= bit;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// SOFT extraction (svs_soft_extract*, include/svsdct.h): one byte per payload coefficient - the hard bit in bit 7 and, in
+// bits 0..6, how far the quantiser input x sits from the nearest decision boundary of its cell, in units of delta / 254.
+// A format, as the dither's rule: x = c, or c - d under a dither (the hard side's own subtract), and
+//   q = quant_index<QM>(x);  x0 = (float)q * (float)delta   (one multiply in every quantiser mode);  a = fabsf(x - x0)
+//   h = 0.5f * (float)delta;  s = (float)(254.0 / (double)(float)delta)                       (both rounded once, host side)
+//   m = clamp((int)((h - a) * s), 0, 127)  (one subtract, one multiply, truncation toward zero);  byte = ((q & 1) << 7) | m
+// Every float step is one IEEE float32 operation (build with -ffp-contract=off), in the same order on host and device.
+// ---------------------------------------------------------------------------------------------------------------------
+// (device only) the 64 coefficients are computed HERE: each is used under one wave-uniform test of its own, and left alone
+// the compiler sinks its share of the horizontal pass into that branch, which keeps the whole vertical pass and its partial
+// sums alive through the loop - 45 to 50 registers over the 80 of the eight-row extract kernels, spilled to scratch
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SVS_PIN_COEFFICIENTS(D)                                                  \
+    _Pragma("unroll") for (int pin_k = 0; pin_k < 64; ++pin_k) asm volatile("" : "+v"((D)[pin_k >> 3][pin_k & 7]))
+#else
+#define SVS_PIN_COEFFICIENTS(D) ((void)0)
+#endif
+
+struct SoftArgs {            // by-value argument of extract_exact_kernel (read by its U = 8 instantiations only)
+    uint32_t on;             // 0: a hard call - the kernel's sides that were there before
+    float half;              // h
+    float scale;             // s
+    uint32_t recip;          // ceil(2^20 / n): t / n == (t * recip) >> 20 for every byte index t < 64 n of a wave's run
+};
+
+inline SoftArgs make_soft_args(float delta_f, uint32_t n) {
+    return {1u, 0.5f * delta_f, (float)(254.0 / (double)delta_f), n ? ((1u << 20) + n - 1u) / n : 0u};
+}
+
+// the byte of quantiser input x.  The clamp is taken on the float so that no conversion leaves the range of int: for
+// every v that converts, min(max((int)v, 0), 127) is the same value ((int)v == 0 on (-1, 0]).
+template <int QM>
+SVS_HD uint32_t soft_byte(float x, const QimParams &qp, const SoftArgs &sa) {
+    const int q = quant_index<QM>(x, qp);
+    const float x0 = (float)q * qp.delta_f;
+    const float a = fabsf(x - x0);
+    const float v = (sa.half - a) * sa.scale;
+    const uint32_t m = v >= 127.0f ? 127u : (v > 0.0f ? (uint32_t)(int)v : 0u);
+    return (((uint32_t)q & 1u) << 7) | m;
+}
+
+// SOFT extract of one block: put(s, byte) for every payload coefficient, s = sel.slot(k) its block-local stream slot.  `sel`
+// is the call's selection or the prefix table of n_ac (make_prefix_table), so the selected loop of the hard sides serves
+// every form; `dith` (wave-uniform) switches the hard dithered side's subtract on.  Each byte leaves as it is computed:
+// nothing is gathered in registers.
+template <int QM, class Put>
+SVS_HD void extract_block_soft(const uint32_t (&rx)[8], const uint32_t (&ry)[8], const CoeffTable &sel, const QimParams &qp,
+                               const SoftArgs &sa, bool dith, uint32_t s_b, Put &&put) {
+    float D[8][8];
+    forward_exact(rx, ry, D);
+    SVS_PIN_COEFFICIENTS(D);
+#pragma unroll
+    for (int k = 1; k < 64; ++k) {
+        const uint32_t s = sel.slot(k);
+        if (s < sel.count) {  // wave-uniform
+            float x = D[k >> 3][k & 7];
+            if (dith) x = x - dither_value(s_b, (uint32_t)k, qp.delta_f);
+            put(s, soft_byte<QM>(x, qp, sa));
+        }
+        SVS_SCHED_FENCE();   // coefficient by coefficient: the bytes are independent, and scheduled together they spill
     }
 }
 

@@ -300,12 +300,16 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
 }
 
 // svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>.  A keyed plan ORs every block's bits into its
-// slot with global atomics (svs_device.hpp, or_bits_global): the output is cleared first, on the same stream.
+// slot with global atomics (svs_device.hpp, or_bits_global): the output is cleared first, on the same stream.  A soft plan
+// (EXACT, rows = 8) switches the kernel's soft side on and is the only launch with dynamic LDS: a tile of 64 n bytes per wave;
+// every byte of its output has one writer, so nothing is cleared (ZEROS: out_bytes, the capacity, of zero bytes).
+uint32_t soft_lds_bytes(const svs::ExtractPlan &p) { return p.soft ? (uint32_t)(SVS_WG / 64) * 64u * p.n_ac : 0u; }
+
 int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
                    uint64_t out_bytes, const svs::KernelOptions &k) {
     const svs::LaunchTables t = svs::extract_tables(p, k);
     const svs::BlockOrderArgs &ord = k.ord;
-    if (p.path == ExtractPath::ZEROS || p.keyed) SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
+    if (p.path == ExtractPath::ZEROS || (p.keyed && !p.soft)) SVS_HIP(hipMemsetAsync(out, 0, out_bytes, st));
     if (p.path == ExtractPath::ZEROS) return SVS_OK;
     g.xcd_chunk = p.xcd_chunk;
     return dispatch<svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
@@ -314,9 +318,10 @@ int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, co
             return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
                 constexpr int U = decltype(r)::value;
                 if (p.keyed)
-                    return launch(svs::extract_exact_kernel<U, QM, 1, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, g, p.qp,
-                                  out, out_bytes, t.sel, t.dith, ord);
-                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), 0, st, gray, g, p.qp, out, out_bytes, t.sel, t.dith);
+                    return launch(svs::extract_exact_kernel<U, QM, 1, true, svs::BlockOrderArgs>, grid_for(total), soft_lds_bytes(p), st,
+                                  gray, g, p.qp, out, out_bytes, t.sel, t.dith, t.soft, ord);
+                return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), soft_lds_bytes(p), st, gray, g, p.qp, out, out_bytes,
+                              t.sel, t.dith, t.soft);
             });
         if (p.keyed)
             return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
@@ -719,6 +724,7 @@ struct GrayOptions {
     const svs_dither *dither = nullptr;        // the dithered calls
     uint64_t *d_counts = nullptr;              // the read-back calls, device: {repaired, unrepaired}, added to
     svs_readback_counts *counts = nullptr;     // the read-back calls, host: the counts of the whole call
+    bool soft = false;                         // the soft extract calls: one byte per capacity bit instead of packed bits
 
     // the kernels' forms, for a batch of g's blocks per frame (derived once per call)
     svs::KernelOptions kernel_forms(const svs::Geometry &g) const {
@@ -783,6 +789,8 @@ constexpr OptionsPolicy kSelectEmbed{false, true, kSelectEmbedFlags, "a select e
 constexpr OptionsPolicy kSelectExtract{false, true, kModeFlags, "a select extract takes the mode bits only"};
 constexpr OptionsPolicy kDitheredEmbed{true, false, kSelectEmbedFlags, "a dithered embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE"};
 constexpr OptionsPolicy kDitheredExtract{true, false, kModeFlags, "a dithered extract takes the mode bits only"};
+// order, coeffs and dither may each be NULL
+constexpr OptionsPolicy kSoftExtract{false, false, kModeFlags, "a soft extract takes the mode bits only"};
 // order, coeffs and dither may each be NULL: a NULL dither is the selected call with read-back, all three NULL (or a prefix
 // selection alone) svs_embed_readback* itself; SVS_READBACK is accepted and implied
 constexpr OptionsPolicy kKeyedReadback{false, false, kGrayEmbedFlags,
@@ -863,12 +871,13 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, i
     if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
     if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
     if ((uintptr_t)d_bits_packed_out % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
-    const uint64_t bytes = (cap + 7) / 8;
+    const uint64_t bytes = o.soft ? cap : (cap + 7) / 8;   // a soft call: one byte per capacity bit
     if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
     svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
     ra.keyed = o.order != nullptr;
     ra.coeffs = o.coeffs;   // the select calls: n_ac == coeffs->count
     ra.dithered = o.dither != nullptr;
+    ra.soft = o.soft;
     const svs::ExtractPlan p = svs::plan_extract(ra);
     // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
     if (p.path != ExtractPath::ZEROS && (flags & ~kModeFlags)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
@@ -1072,7 +1081,7 @@ static int extract_host(const uint8_t *gray, const svs_planes *planes, double de
     if (int rc = check_extract_flags(flags)) return rc;
     if (cap == 0) return SVS_OK;
     if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
-    const uint64_t bytes = (cap + 7) / 8;
+    const uint64_t bytes = o.soft ? cap : (cap + 7) / 8;
     if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
     return extract_staged(
         gray, span_bytes(planes), bytes, 0, n_bits_out,
@@ -1170,6 +1179,26 @@ int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const sv
                          uint32_t flags, uint64_t *n_bits_out) {
     return with_options(kDitheredExtract, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
         return extract_host(gray, planes, delta, n, bits_packed_out, out_capacity_bytes, flags, n_bits_out, o);
+    });
+}
+
+// The soft calls are the dithered extract calls with each of order, coeffs and dither optional, and one byte per capacity bit
+// for an output (include/svsdct.h): the same checks in the same order, the same staging.
+int svs_soft_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                         const svs_dither *dither, double delta, int n_ac, uint8_t *d_soft_out, uint64_t out_capacity_bytes,
+                         uint32_t flags, uint64_t *n_bits_out, void *stream) {
+    return with_options(kSoftExtract, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.soft = true;
+        return extract_dev(d_gray, planes, delta, n, d_soft_out, out_capacity_bytes, flags, n_bits_out, stream, o);
+    });
+}
+
+int svs_soft_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                     const svs_dither *dither, double delta, int n_ac, uint8_t *soft_out, uint64_t out_capacity_bytes, uint32_t flags,
+                     uint64_t *n_bits_out) {
+    return with_options(kSoftExtract, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.soft = true;
+        return extract_host(gray, planes, delta, n, soft_out, out_capacity_bytes, flags, n_bits_out, o);
     });
 }
 

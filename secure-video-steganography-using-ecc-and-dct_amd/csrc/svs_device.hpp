@@ -851,6 +851,36 @@ __global__ __launch_bounds__(SVS_WG) void embed_row1_kernel(const uint8_t *gray,
 // every placement, 1.77 - 1.95 ms per 600 x 4K against 1.58 - 1.62, even with the arithmetic skipped: profiles/r06_stream_pipeline.txt.
 // What the one-shot launch has and the loop has not is the hardware's own pacing: a workgroup starts when another one ends.)
 
+// Tail of the soft side of extract_exact_kernel: a wave's tile holds the n bytes of each of its `blocks` live blocks, block j
+// (lane j) at byte j n.  Without an order they are one run of blocks * n bytes of the output at `run0` (a multiple of
+// 64: the output is dword aligned), copied as dwords with a byte tail; with one, block j owns the n bytes at its own
+// first_j, copied bytewise - byte t of the tile belongs to block t / n ((t * recip) >> 20, SoftArgs) and goes to
+// first_j + t % n.  Every byte of the output has one writer; nothing at or past out_bytes (the call's capacity) is written.
+template <bool KEYED>
+__device__ __forceinline__ void copy_soft_run(const uint8_t *tile, uint32_t lane, uint32_t n, uint32_t blocks, uint64_t run0,
+                                              uint64_t first, uint32_t recip, uint8_t *__restrict__ out, uint64_t out_bytes) {
+    const uint32_t bytes = blocks * n;
+    if constexpr (!KEYED) {
+        const uint32_t *words = reinterpret_cast<const uint32_t *>(tile);
+        for (uint32_t w = lane; 4u * w < bytes; w += 64u) {
+            const uint64_t at = run0 + 4ull * w;
+            if (4u * w + 4u <= bytes && at + 4u <= out_bytes) {
+                *reinterpret_cast<uint32_t *>(out + at) = words[w];
+            } else {
+                for (uint32_t j = 4u * w; j < bytes && run0 + j < out_bytes; ++j) out[run0 + j] = tile[j];
+            }
+        }
+    } else {
+        const uint32_t f_lo = (uint32_t)first, f_hi = (uint32_t)(first >> 32);
+        for (uint32_t t0 = 0; t0 < bytes; t0 += 64u) {   // wave-uniform trip count: the shuffles run with every lane on
+            const uint32_t t = t0 + lane;
+            const uint32_t j = min((t * recip) >> 20, 63u);
+            const uint64_t at = (((uint64_t)(uint32_t)__shfl((int)f_hi, (int)j) << 32) | (uint32_t)__shfl((int)f_lo, (int)j)) + (t - j * n);
+            if (t < bytes && at < out_bytes) out[at] = tile[t];
+        }
+    }
+}
+
 // The eight-row instantiations are register-allocated for the six waves per SIMD they ran at before the dithered side joined
 // them (75 - 80 VGPRs; each side fits on its own, left alone the allocator takes 81 - 85 for the pair); a minimum of 1 is the
 // default of the others.
@@ -858,10 +888,40 @@ template <int U, int QM, int BPL = 1, bool KEYED = false, class... Order>   // B
 __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                             const QimParams qp, uint8_t *__restrict__ out,
                                                             const uint64_t out_bytes, const CoeffTable sel,
-                                                            const DitherArgs dith, const Order... order) {
+                                                            const DitherArgs dith, const SoftArgs soft, const Order... order) {
     static_assert(BPL == 1, "one block per lane");
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
+    // A soft call (soft.on; the U = 8 instantiations only - svs_route.hpp plans no other for one) is a third side behind the
+    // same kind of branch: one byte per payload coefficient instead of one bit (svs_block.hpp, SoftArgs).  It takes its wave
+    // tiles from dynamic LDS, which only the soft launch requests (soft_lds_bytes), and touches neither `flags` nor `sel`.
+    if constexpr (U == 8) {
+        if (soft.on) {     // wave-uniform
+            extern __shared__ uint32_t soft_tiles[];
+            const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+            const uint32_t n = g.n_ac;   // == dith.sel.count
+            const uint32_t wave_first = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + wave * 64u;
+            const uint32_t gblock = wave_first + lane;
+            uint8_t *tile = reinterpret_cast<uint8_t *>(soft_tiles) + wave * 64u * n;   // 64 n bytes: dword aligned
+            const bool live = gblock < g.total_blocks;
+            uint64_t first = 0;
+            if (live) {
+                u32x2 v[8];
+                load_rows<1>(gray + block_offset(gblock, g), g.row_pitch, v);
+                uint32_t ax[8], ay[8];
+#pragma unroll
+                for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
+                uint8_t *mine = tile + lane * n;
+                extract_block_soft<QM>(ax, ay, dith.sel, qp, soft, dith.on != 0u, dith.on ? dither_seed_of(gblock, g, dith) : 0u,
+                                       [&](uint32_t s, uint32_t byte) { mine[s] = (uint8_t)byte; });
+                if constexpr (KEYED) first = stream_first<true>(gblock, n, g, order_arg(order...));
+            }
+            wave_lds_fence();
+            copy_soft_run<KEYED>(tile, lane, n, wave_first < g.total_blocks ? min(64u, g.total_blocks - wave_first) : 0u,
+                                 (uint64_t)wave_first * n, first, soft.recip, out, out_bytes);
+            return;
+        }
+    }
     // A keyed dither (dith.on; the U = 8 instantiations only - svs_route.hpp plans no other for one): ONE wave-uniform branch
     // around the whole body, as in embed_exact_kernel; `dithered` is a compile-time false on the side that was there before.
     // (The dithered forms as two more alternatives beside the selection's branch, sharing the loads and the tail, took 136

@@ -36,6 +36,9 @@ struct RouteArgs {
     // eight coefficient rows in every mode, as a non-prefix selection - the streaming guard and the FAST extract tie margins
     // are derived for an undithered quantiser input
     bool dithered = false;
+    // a soft call (svs_soft_extract*; gray extract only): the eight-row pocketfft-identical extract kernel in every mode, with a
+    // prefix, a selection, a dither or an order - the reliability is a distance of the reference's own quantiser input
+    bool soft = false;
 };
 
 inline bool route_selected(const RouteArgs &a) {
@@ -135,6 +138,8 @@ struct ExtractPlan {
     bool keyed;               // the KEYED instantiation of the family (not ZEROS: all bits 0 in any order)
     bool selected;            // the launch passes the call's CoeffTable (EXACT with rows = 8 only), else an empty one
     bool dithered;            // the launch switches the exact kernel's dithered side on (EXACT with rows = 8; not ZEROS)
+    bool soft;                // the launch switches the exact kernel's soft side on (EXACT with rows = 8; ZEROS: every byte 0)
+    uint32_t n_ac;            // soft: bytes per block, the count of the table the soft side reads
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -142,13 +147,15 @@ struct ExtractPlan {
 // contiguous eighth); more rows - VALU-bound, the map does not matter.
 inline ExtractPlan plan_extract(const RouteArgs &a) {
     ExtractPlan p{};
+    p.soft = a.soft;
+    p.n_ac = a.n_ac;
     if (!(a.delta > 0.0)) {
         p.path = ExtractPath::ZEROS;
         return p;
     }
     p.selected = route_selected(a);
     p.dithered = a.dithered;
-    p.rows = p.selected || p.dithered ? 8 : rows_for((int)a.n_ac);
+    p.rows = p.selected || p.dithered || p.soft ? 8 : rows_for((int)a.n_ac);
     p.xcd_chunk = p.rows == 1 ? 32u : (p.rows == 2 && !a.bgr ? 0u : kEighth);
     p.qm = make_qim(a.delta, &p.qp) == QM_POW2 ? QM_POW2 : QM_F32;
     const float t = a.tie_scale;
@@ -161,7 +168,7 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     // the FAST kernels with two and more rows round c / delta by adding 1.5 * 2^23, which needs |c / delta| < 2^22.  With one
     // row the pocketfft-identical forward costs 0.2-3 % (the kernel stays HBM-bound; profiles/history/r01_ab_quant_exact.txt),
     // so FAST mode uses it too; with more rows it costs ~17 % and stays opt-in.
-    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected || p.dithered) exact = true;
+    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected || p.dithered || p.soft) exact = true;
     p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
     p.keyed = a.keyed;
     return p;
@@ -177,9 +184,10 @@ struct KernelOptions {
     DitherArgs dith;
 };
 
-struct LaunchTables {   // the `sel` and `dith` arguments of the two exact kernels
+struct LaunchTables {   // the `sel` and `dith` arguments of the two exact kernels, and extract_exact_kernel's `soft`
     CoeffTable sel;
     DitherArgs dith;
+    SoftArgs soft;
 };
 
 // embed_exact_kernel: `sel` is the call's selection where the plan is selected, else empty (count 0: the row-major prefix).  The
@@ -196,9 +204,14 @@ inline DitherArgs readback_tables(const EmbedPlan &p, const KernelOptions &k) {
     return {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, p.selected && k.coeffs ? *k.coeffs : make_prefix_table(p.n_ac)};
 }
 
-// extract_exact_kernel reads the selection from `sel` on either side: its dither carries no table
+// extract_exact_kernel reads the selection from `sel` on either hard side: their dither carries no table.  The soft side runs
+// the selected loop alone and reads its own copy from the dither's table, never empty: the call's selection, or the prefix
+// table of n_ac (as embed_exact_kernel's dithered side)
 inline LaunchTables extract_tables(const ExtractPlan &p, const KernelOptions &k) {
-    return {p.selected && k.coeffs ? *k.coeffs : CoeffTable{}, {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, CoeffTable{}}};
+    const CoeffTable sel = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
+    return {sel,
+            {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, !p.soft ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)},
+            p.soft ? make_soft_args(p.qp.delta_f, p.n_ac) : SoftArgs{}};
 }
 
 }  // namespace svs

@@ -7,6 +7,7 @@ Two levels:
   * `embed_frames` / `extract_frames`      NumPy in, NumPy out (host entry points of the C ABI).
   * `embed_device` / `extract_device`      raw device pointers + stream (what bench.py and a
                                            device-resident pipeline use); nothing is copied.
+  * `extract_soft_frames` / `extract_soft_device`   the same two levels of the soft-decision extraction: a byte per bit.
 Bits travel packed MSB-first (numpy.packbits order), so `unpack_to_str` of the extract output is
 the reference operator's '0'/'1' string.
 """
@@ -314,6 +315,35 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     return out[: (n + 7) // 8], n
 
 
+def _soft_call(lib, call: _GrayCall, front, delta, n_ac, back, stream=()) -> None:
+    """svs_soft_extract(*front, order, coeffs, dither, delta, n_ac, *back), or with stream = (handle,) its _dev form: the one
+    soft entry point takes each of the three structs or NULL, so every stem of _resolve makes the same call"""
+    name = "svs_soft_extract" + ("_dev" if stream else "")
+    native.check(getattr(lib, name)(*front, _ref(call.order), _ref(call.sel), _ref(call.dith), float(delta), int(n_ac), *back,
+                                    *stream), name)
+
+
+def extract_soft_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
+                        first_frame=None, coeffs=None, dither_key=None):
+    """Soft-decision extraction of a stack of gray frames on the GPU (svs_soft_extract, include/svsdct.h): one byte per
+    capacity bit in stream order - bit 7 the hard bit extract_frames returns, bits 0..6 the distance of the coefficient from
+    the nearest decision boundary in units of delta / 254 (svsdct/soft.py reads and combines them).  block_key, first_frame,
+    coeffs, dither_key: as extract_frames; mode is accepted and changes nothing (a soft call always runs the exact kernel).
+    Returns (soft uint8 [capacity], n_bits)."""
+    call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
+    lib = native.load()
+    native.ensure_device(device)
+    stack = _as_stack(frames)
+    f, h, w = stack.shape
+    cap = capacity_bits(f, h, w, n_ac)
+    out = pinned_empty(max(4, cap))
+    got = C.c_uint64(0)
+    planes = Planes.contiguous(f, h, w)
+    _soft_call(lib, call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [out.ctypes.data, cap, mode_flags(mode), C.byref(got)])
+    n = int(got.value)
+    return out[:n], n
+
+
 # ---- the reference operator's own payload types: '0' / '1' strings ------------------------------------------
 _utf8_and_size = None
 
@@ -413,6 +443,19 @@ def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, ou
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     _gray_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac,
                [d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)], None, (stream or None,))
+    return int(got.value)
+
+
+def extract_soft_device(d_gray: int, planes: Planes, delta, n_ac, d_soft_out: int, out_capacity_bytes: int, stream: int = 0,
+                        mode: str | None = None, order: BlockOrder | None = None, coeffs=None, dither_key=None,
+                        first_frame: int | None = None) -> int:
+    """Enqueue the soft-decision extraction on `stream` (svs_soft_extract_dev): one byte per capacity bit into d_soft_out
+    (4-byte aligned, at least the capacity in bytes); returns the number of bytes the batch yields.  order, coeffs, dither_key,
+    first_frame: as extract_device."""
+    got = C.c_uint64(0)
+    call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
+    _soft_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac,
+               [d_soft_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)], (stream or None,))
     return int(got.value)
 
 

@@ -1,0 +1,64 @@
+"""Reading and combining the bytes of the soft-decision extraction (svs_soft_extract, include/svsdct.h;
+batch.extract_soft_frames).  NumPy only: nothing here loads the library or touches the GPU.
+
+One byte per capacity bit, in stream order: bit 7 is the hard bit, bits 0..6 are m, the distance of the payload coefficient
+from the nearest decision boundary of its quantiser cell in units of delta / 254 - 127 on the lattice point, 0 on the
+boundary.  m is a DISTANCE, not a probability: what it says about the chance of a bit error depends on the disturbance
+between sender and receiver, which nobody here knows.
+
+A sender that wants a payload to survive a lost bit tiles it - copy after copy through the stream, the last one cut where the
+capacity ends - and embeds the tiled stream as any other; the receiver extracts soft bytes and folds them with combine().
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def _soft(soft) -> np.ndarray:
+    a = np.asarray(soft)
+    if a.dtype != np.uint8 or a.ndim != 1:
+        raise TypeError("soft must be a one-dimensional uint8 array (one byte per capacity bit)")
+    return a
+
+
+def hard_bits(soft) -> np.ndarray:
+    """the hard bits, uint8 0 / 1 per byte: numpy.packbits of them is what the matching extract call returns"""
+    return _soft(soft) >> 7
+
+
+def reliability(soft) -> np.ndarray:
+    """m per byte, uint8 in 0..127"""
+    return _soft(soft) & np.uint8(127)
+
+
+def combine(soft, period: int):
+    """Soft vote over the copies of a tiled payload of `period` bits: byte j, j + period, j + 2 period, .. are copies of
+    payload bit j, a last partial copy counting where it reaches.  Every copy votes (2 b - 1) (2 m + 1) - its hard bit, weighted
+    by an odd number so that no single byte abstains - and
+        score[j] = sum of the votes,    bit[j] = score[j] > 0,    a zero score takes copy 0's bit.
+    Returns (bits uint8 [period], score int32 [period]).  period must be in 1 .. len(soft)."""
+    a = _soft(soft)
+    period = int(period)
+    if not 1 <= period <= a.size:
+        raise ValueError(f"period {period} outside 1 .. {a.size}")
+    votes = (2 * (a >> 7).astype(np.int32) - 1) * (2 * (a & 127).astype(np.int32) + 1)
+    copies = -(-a.size // period)
+    padded = np.zeros(copies * period, np.int32)
+    padded[: a.size] = votes
+    score = padded.reshape(copies, period).sum(axis=0, dtype=np.int32)
+    bits = np.where(score != 0, score > 0, a[:period] >> 7).astype(np.uint8)
+    return bits, score
+
+
+def margin_histogram(soft, n_frames: int) -> np.ndarray:
+    """int64 [n_frames, 128]: how many bytes of each frame have each m.  The stream is the frames' bytes in order, equally many
+    per frame.  A frame whose payload coefficients sit on the lattice - stego read with the right dither, or without one -
+    has its mass near 127; a never-embedded frame, or dithered stego read without the key, is flat."""
+    a = _soft(soft)
+    n_frames = int(n_frames)
+    if n_frames < 1 or a.size % n_frames:
+        raise ValueError(f"{a.size} bytes are not {n_frames} frames of equal capacity")
+    m = (a & 127).reshape(n_frames, -1).astype(np.int64)
+    hist = np.zeros((n_frames, 128), np.int64)
+    np.add.at(hist, (np.repeat(np.arange(n_frames), m.shape[1]), m.ravel()), 1)
+    return hist
