@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Repetition by tiling, combined with the soft-decision extraction: a framed payload (svsdct.framing) is written three times
-through the stream of a clip of synthetic noise, the stego is disturbed with uniform pixel noise, and the receiver folds the three copies
-by their reliabilities (svsdct.soft.combine) before it parses the header.  There is no repeat option in the library: the sender
-tiles the bits, the receiver knows the period.
+"""Repetition by tiling, decoded by the fused soft vote: a framed payload (svsdct.framing) is written copy after copy through the
+stream of a clip of synthetic noise (batch.embed_repeated_frames), the stego is disturbed with uniform pixel noise, and the
+receiver has the device fold the copies by their reliabilities (batch.extract_vote_frames: `period` integers come back, no
+soft byte is written) before it parses the header.  The same vote on the soft bytes (batch.extract_soft_frames,
+svsdct.soft.combine) is run beside it: the bits are the same.  The sender tiles the bits, the receiver knows the period.
+The clip is sized for --copies copies and then filled to its capacity (copies=None), the last copy cut: the fused vote reads
+every capacity bit of the frames it is given, so bits the sender left unembedded would vote as noise.
 
     python examples/soft_vote_roundtrip.py [--noise 5] [--copies 3] [--n-ac 10] [--delta 20]
 
@@ -22,7 +25,7 @@ from svsdct import batch, framing, soft  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--noise", type=int, default=5, help="amplitude a of the uniform integer pixel noise in [-a, a]")
-ap.add_argument("--copies", type=int, default=3)
+ap.add_argument("--copies", type=int, default=3, help="the clip is sized to hold at least this many copies, and then filled")
 ap.add_argument("--n-ac", type=int, default=10)
 ap.add_argument("--delta", type=float, default=20)
 a = ap.parse_args()
@@ -35,16 +38,17 @@ per_frame = batch.capacity_bits(1, h, w, a.n_ac)
 frames = -(-a.copies * payload.size // per_frame)
 rng = np.random.default_rng(2)
 clip = rng.integers(64, 192, (frames, h, w)).astype(np.uint8)
-tiled = np.tile(payload, a.copies)                                                       # the sender's whole repetition
-print(f"payload {payload.size} bits x {a.copies} copies; {frames} frames of {per_frame} bits")
-
-stego, used = batch.embed_frames(clip, a.delta, a.n_ac, tiled)
+stego, used, period = batch.embed_repeated_frames(clip, a.delta, a.n_ac, payload)            # soft.tile + embed_frames
+print(f"payload {period} bits, {frames} frames of {per_frame} bits: {used / period:.2f} copies")
 disturbed = np.clip(stego.astype(np.int64) + rng.integers(-a.noise, a.noise + 1, stego.shape), 0, 255).astype(np.uint8)
 bytes_, n = batch.extract_soft_frames(disturbed, a.delta, a.n_ac)
-bytes_ = bytes_[:used]                                                                   # the receiver knows period and copies
+assert used == n                                                                         # the clip is full
 hard = soft.hard_bits(bytes_)
-voted, score = soft.combine(bytes_, payload.size)
-print("bit errors of each copy alone:", [int((hard[k * payload.size:(k + 1) * payload.size] != payload).sum()) for k in range(a.copies)],
+voted, score = soft.combine(bytes_, period)
+fused, tally = batch.extract_vote_frames(disturbed, a.delta, a.n_ac, period)             # the same vote, folded on the device
+print("the fused vote's bits equal soft.combine's:", bool(np.array_equal(fused, voted)),
+      "| its tally is soft.tally of the soft bytes:", bool(np.array_equal(tally, soft.tally(bytes_, period))))
+print("bit errors of each whole copy alone:", [int((hard[k * period:(k + 1) * period] != payload).sum()) for k in range(used // period)],
       "| after the soft vote:", int((voted != payload).sum()), "| smallest |score|:", int(np.abs(score).min()))
 try:
     hdr = framing.parse_header(voted)

@@ -473,7 +473,7 @@ int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const sv
  * AND how far the coefficient sits from the nearest decision boundary of its quantiser cell - the quantity SVS_NEAREST,
  * SVS_MINMOVE, read-back, the selection and the dither all work on at the sending end.  A sender reads from it how much
  * disturbance a stego clip survives; a receiver sees which frames sit on the lattice; a caller that embedded the payload more
- * than once (by tiling it: there is no repeat option) combines the copies by their reliabilities (svsdct/soft.py, combine).
+ * than once (by tiling it) combines the copies by their reliabilities (svsdct/soft.py, combine; on the device: svs_soft_vote*).
  * The byte is a FORMAT, a contract between builds as the dither's rule is.  Layout: one byte per capacity bit in stream order;
  * byte i belongs to stream bit i of the hard extract call with the same order, coeffs, dither, delta and n_ac.  For the
  * payload coefficient with quantiser input x - x = c for a call without a dither, x = c - d under one, c the
@@ -515,6 +515,51 @@ int svs_soft_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const 
 int svs_soft_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                      const svs_dither *dither, double delta, int n_ac, uint8_t *soft_out, uint64_t out_capacity_bytes, uint32_t flags,
                      uint64_t *n_bits_out);
+
+/* ---- fused soft vote: the copies of a tiled payload folded on the device ----------------------------------
+ * A payload of `period` bits embedded copy after copy through the stream (the sender tiles the stream itself and embeds it as any
+ * other, the last copy cut where the capacity ends; svsdct/soft.py, tile) is decoded by a vote of the soft bytes of its copies.
+ * These calls run the soft extraction and vote in the same launch: the soft bytes are never written, each is added into a tally
+ * of `period` int32 values, and the tally's 4 * period bytes are all that leaves the device.  The tally is a FORMAT, as the soft
+ * byte is.  With i the index of a capacity bit within the call, in exactly the order and layout of svs_soft_extract with the
+ * same order, coeffs, dither, delta and n_ac, p = stream_bit0 + i its stream position, j = p mod period, `byte` its soft byte,
+ * b = byte >> 7 and m = byte & 127:
+ *     tally[j] += 2 * (2b - 1) * (2m + 1)        for every capacity bit of the call
+ *     tally[j] += (2b - 1)                       additionally, where p < period   (copy 0 breaks ties)
+ *     bit[j]    = tally[j] > 0
+ * An entry is odd once copy 0 has been counted and then never zero; its sign is svsdct/soft.py combine's bit, the rule that a
+ * zero score takes copy 0's bit included, and (tally[j] - (2 b0[j] - 1)) / 2, b0 copy 0's hard bit, is combine's score.  All
+ * arithmetic is integer: the result does not depend on the order of the additions, so the calls are deterministic though the
+ * device adds with atomics.
+ * Overflow: one copy contributes at most 511 in magnitude.  A call whose capacity exceeds period * 2^22 is refused, so the at
+ * most 2^22 + 1 copies of one call stay below 2.14e9 < 2^31.  Across several calls into one tally the caller owns the bound.
+ *   period      : the payload's length in bits, 1 .. 2^61 - 1; both sides agree on it (nothing in the stream says it).
+ *   stream_bit0 : the stream position of the call's first capacity bit - for a clip processed in batches the capacity of the
+ *            frames before the batch; under an order or a dither first_frame advances as in every other call.
+ *   d_tally  : period int32 values in device memory, 4-byte aligned.  The call ADDS into it, as the read-back calls add into
+ *            d_counts: zero it before the first call.  It keeps no state and allocates nothing.
+ *   tally_out : period int32 values in host memory.  The host form stages as svs_extract does, votes into a zeroed tally of its
+ *            per-thread staging context and WRITES exactly period values; a caller with several calls adds the arrays.
+ *   order, coeffs, dither, planes, flags : as svs_soft_extract*, checked as there; the mode bits are accepted and change nothing.
+ *   n_bits_out : receives the capacity, the number of bits that voted.
+ * SVS_ERR_INVALID_ARG: embed flags or unknown ones; period 0 or above 2^61 - 1; delta <= 0 (every soft byte is 0 there and a
+ * vote over them says nothing); with a capacity above 0, a NULL tally, a device tally that is not 4-byte aligned, or a capacity
+ * above period * 2^22.  Every refusal comes before any device work and leaves the tally and *n_bits_out as they were.  A capacity
+ * of 0 is SVS_OK with *n_bits_out = 0: the device form leaves the tally untouched, the host form fills it with zeros.
+ * Cost: the soft call's launch (above) with another tail - a wave adds its run's bytes with global int32 atomics that return
+ * nothing, and where many of them share an entry (period below the 64 n bytes of a wave's run; under an order: period <= 64) it
+ * sums them per entry first.  Measured (profiles/soft_vote_rates.txt; MI355X, 200 x 4K, n_ac = 10, delta = 20): 0.89 ms at
+ * period = 10^6 against 0.80 ms of the soft call; 2.08 ms at period = 2400 and 5.37 ms there under an order - every add of the
+ * launch lands in the same 9.6 KB and the atomics set the time.
+ * Limits: there is no colour and no _str form, no FramePipeline or drop-in form (a receiver would have to know period before it
+ * can parse the header), and no repeat option of the embed calls - the sender tiles. */
+int svs_soft_vote_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                      const svs_dither *dither, double delta, int n_ac, uint64_t period, uint64_t stream_bit0, int32_t *d_tally,
+                      uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+int svs_soft_vote(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                  const svs_dither *dither, double delta, int n_ac, uint64_t period, uint64_t stream_bit0, int32_t *tally_out,
+                  uint32_t flags, uint64_t *n_bits_out);
 
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:

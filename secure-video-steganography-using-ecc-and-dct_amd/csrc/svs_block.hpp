@@ -1733,10 +1733,47 @@ struct SoftArgs {            // by-value argument of extract_exact_kernel (read 
     float half;              // h
     float scale;             // s
     uint32_t recip;          // ceil(2^20 / n): t / n == (t * recip) >> 20 for every byte index t < 64 n of a wave's run
+    // the vote (svs_soft_vote*, make_vote_args): the bytes are not written - each is added into a tally of `period` int32
+    uint32_t vote = 0;       // 0: a soft extract call - the bytes are copied out
+    uint32_t pad = 0;
+    uint64_t period = 0;     // 1 .. 2^61 - 1
+    uint64_t base = 0;       // stream_bit0 mod period: call-local bit i has residue (base + i) mod period
+    uint64_t head = 0;       // call-local bits i < head lie in copy 0 (stream position below period) and break ties
+    double inv = 0.0;        // 1.0 / period where period <= 2^38, else 0 (no quotient: base + i < 2 period, vote_residue)
 };
 
 inline SoftArgs make_soft_args(float delta_f, uint32_t n) {
     return {1u, 0.5f * delta_f, (float)(254.0 / (double)delta_f), n ? ((1u << 20) + n - 1u) / n : 0u};
+}
+
+// ---- the vote: a soft byte's place and weight in the tally (include/svsdct.h states the format) ----------------------------
+constexpr uint64_t kVotePeriodMax = (1ull << 61) - 1u;    // 4 * period, the tally's bytes, fits 63 bits
+constexpr uint64_t kVoteCopiesShift = 22;                 // a call is refused when capacity > period << 22 (the int32 bound)
+
+inline SoftArgs make_vote_args(SoftArgs sa, uint64_t period, uint64_t stream_bit0) {
+    sa.vote = 1u;
+    sa.period = period;
+    sa.base = stream_bit0 % period;
+    sa.head = stream_bit0 < period ? period - stream_bit0 : 0u;
+    sa.inv = period <= (1ull << 38) ? 1.0 / (double)period : 0.0;
+    return sa;
+}
+
+// (base + i) mod period for a call-local bit index i < 2^38 (a call has fewer than 2^31 blocks of at most 63 bits).
+// period <= 2^38: x = base + i < 2^39 is exact as a double, x * inv is within 2^-13 of x / period, so the truncated quotient is
+// the true one or off by one either way - one conditional correction.  Larger periods: inv = 0, the quotient is 0 and
+// base + i < 2 period needs the same single correction.  No 64-bit division on the device.
+SVS_HD uint64_t vote_residue(uint64_t i, const SoftArgs &sa) {
+    const uint64_t x = sa.base + i;
+    const uint64_t q = (uint64_t)((double)x * sa.inv);
+    const int64_t r = (int64_t)(x - q * sa.period), p = (int64_t)sa.period;
+    return (uint64_t)(r < 0 ? r + p : (r >= p ? r - p : r));
+}
+
+// what the byte adds to its tally entry: 2 (2b - 1)(2m + 1), and (2b - 1) more where the bit lies in copy 0
+SVS_HD int32_t vote_of(uint32_t byte, bool in_head) {
+    const int32_t w = 4 * (int32_t)(byte & 127u) + 2 + (in_head ? 1 : 0);
+    return (byte & 128u) ? w : -w;
 }
 
 // the byte of quantiser input x.  The clamp is taken on the float so that no conversion leaves the range of int: for

@@ -302,7 +302,8 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
 // svs_extract_dev's plan: extract_exact_kernel<1..8> or extract_kernel<2..8>.  A keyed plan ORs every block's bits into its
 // slot with global atomics (svs_device.hpp, or_bits_global): the output is cleared first, on the same stream.  A soft plan
 // (EXACT, rows = 8) switches the kernel's soft side on and is the only launch with dynamic LDS: a tile of 64 n bytes per wave;
-// every byte of its output has one writer, so nothing is cleared (ZEROS: out_bytes, the capacity, of zero bytes).
+// every byte of its output has one writer, so nothing is cleared (ZEROS: out_bytes, the capacity, of zero bytes).  A vote plan
+// is a soft plan whose `out` is the caller's tally of out_bytes = 4 period bytes, added to and never cleared (never ZEROS).
 uint32_t soft_lds_bytes(const svs::ExtractPlan &p) { return p.soft ? (uint32_t)(SVS_WG / 64) * 64u * p.n_ac : 0u; }
 
 int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
@@ -725,11 +726,13 @@ struct GrayOptions {
     uint64_t *d_counts = nullptr;              // the read-back calls, device: {repaired, unrepaired}, added to
     svs_readback_counts *counts = nullptr;     // the read-back calls, host: the counts of the whole call
     bool soft = false;                         // the soft extract calls: one byte per capacity bit instead of packed bits
+    uint64_t vote_period = 0, vote_bit0 = 0;   // the vote calls (vote_period != 0): the payload's bits, the call's stream position
 
     // the kernels' forms, for a batch of g's blocks per frame (derived once per call)
     svs::KernelOptions kernel_forms(const svs::Geometry &g) const {
         return {order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{}, coeffs,
-                dither ? svs::DitherArgs{svs::dither_seed(dither->key), dither->first_frame, 1u, svs::CoeffTable{}} : svs::DitherArgs{}};
+                dither ? svs::DitherArgs{svs::dither_seed(dither->key), dither->first_frame, 1u, svs::CoeffTable{}} : svs::DitherArgs{},
+                vote_period, vote_bit0};
     }
 
     // The options of a staging chunk of whole frames that starts at frame f0 of the call: its first frame is clip frame
@@ -791,6 +794,7 @@ constexpr OptionsPolicy kDitheredEmbed{true, false, kSelectEmbedFlags, "a dither
 constexpr OptionsPolicy kDitheredExtract{true, false, kModeFlags, "a dithered extract takes the mode bits only"};
 // order, coeffs and dither may each be NULL
 constexpr OptionsPolicy kSoftExtract{false, false, kModeFlags, "a soft extract takes the mode bits only"};
+constexpr OptionsPolicy kSoftVote{false, false, kModeFlags, "a soft vote takes the mode bits only"};
 // order, coeffs and dither may each be NULL: a NULL dither is the selected call with read-back, all three NULL (or a prefix
 // selection alone) svs_embed_readback* itself; SVS_READBACK is accepted and implied
 constexpr OptionsPolicy kKeyedReadback{false, false, kGrayEmbedFlags,
@@ -884,6 +888,41 @@ int extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, i
     if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, o.kernel_forms(g))) return rc;
     if (n_bits_out) *n_bits_out = cap;
     return SVS_OK;
+}
+
+// What the two vote calls check, in the order of the soft extract calls with the vote's own arguments where the output's stood;
+// nothing is written before the last check has passed (*n_bits_out and the tally are untouched by a refusal).  *cap = 0: an
+// empty call, nothing else was looked at.
+int vote_checks(const void *gray, const svs_planes *planes, double delta, int n_ac, uint64_t period, const void *tally, bool device,
+                uint32_t flags, const GrayOptions &o, svs::Geometry *g, uint64_t *total, uint64_t *cap) {
+    if (int rc = make_geometry(planes, n_ac, g, total)) return rc;
+    *cap = *total * (uint64_t)g->n_ac;
+    if (int rc = check_order(o.order)) return rc;
+    if (int rc = check_extract_flags(flags)) return rc;
+    if (period == 0) return fail(SVS_ERR_INVALID_ARG, "period is 0");
+    if (period > svs::kVotePeriodMax) return fail(SVS_ERR_INVALID_ARG, "period %llu exceeds 2^61 - 1", (unsigned long long)period);
+    if (!(delta > 0.0)) return fail(SVS_ERR_INVALID_ARG, "a vote needs delta > 0 (every soft byte is 0 otherwise)");
+    if (*cap == 0) return SVS_OK;
+    if (!gray || !tally) return fail(SVS_ERR_INVALID_ARG, "gray/tally pointer is NULL");
+    if (device && ((uintptr_t)gray % 8)) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
+    if (device && ((uintptr_t)tally % 4)) return fail(SVS_ERR_INVALID_ARG, "tally pointer must be 4-byte aligned");
+    if (period < (1ull << (64 - svs::kVoteCopiesShift)) && *cap > (period << svs::kVoteCopiesShift))
+        return fail(SVS_ERR_INVALID_ARG, "capacity %llu exceeds period * 2^22: an int32 tally entry could overflow in one call",
+                    (unsigned long long)*cap);
+    return SVS_OK;
+}
+
+// the launch of a vote call whose arguments have passed vote_checks (cap != 0)
+int vote_launch(const uint8_t *d_gray, const svs::Geometry &g, uint64_t total, double delta, uint64_t period, uint64_t stream_bit0,
+                int32_t *d_tally, uint32_t flags, hipStream_t st, GrayOptions o) {
+    svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
+    ra.keyed = o.order != nullptr;
+    ra.coeffs = o.coeffs;
+    ra.dithered = o.dither != nullptr;
+    ra.vote = true;
+    o.vote_period = period;
+    o.vote_bit0 = stream_bit0;
+    return launch_extract(svs::plan_extract(ra), total, st, d_gray, g, reinterpret_cast<uint8_t *>(d_tally), 4u * period, o.kernel_forms(g));
 }
 
 }  // namespace
@@ -1199,6 +1238,49 @@ int svs_soft_extract(const uint8_t *gray, const svs_planes *planes, const svs_bl
     return with_options(kSoftExtract, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
         o.soft = true;
         return extract_host(gray, planes, delta, n, soft_out, out_capacity_bytes, flags, n_bits_out, o);
+    });
+}
+
+// The vote calls are the soft calls with a tally for an output (include/svsdct.h): the kernel's soft side adds each byte's vote
+// into tally[stream position mod period] instead of writing it.  The device form adds into the caller's tally; the host form
+// stages the frames as svs_extract does, votes into a zeroed tally in the staging context and downloads its 4 period bytes.
+int svs_soft_vote_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                      const svs_dither *dither, double delta, int n_ac, uint64_t period, uint64_t stream_bit0, int32_t *d_tally,
+                      uint32_t flags, uint64_t *n_bits_out, void *stream) {
+    return with_options(kSoftVote, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        svs::Geometry g;
+        uint64_t total = 0, cap = 0;
+        if (int rc = vote_checks(d_gray, planes, delta, n, period, d_tally, true, flags, o, &g, &total, &cap)) return rc;
+        if (cap != 0)
+            if (int rc = vote_launch(d_gray, g, total, delta, period, stream_bit0, d_tally, flags, (hipStream_t)stream, o)) return rc;
+        if (n_bits_out) *n_bits_out = cap;
+        return (int)SVS_OK;
+    });
+}
+
+int svs_soft_vote(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                  const svs_dither *dither, double delta, int n_ac, uint64_t period, uint64_t stream_bit0, int32_t *tally_out,
+                  uint32_t flags, uint64_t *n_bits_out) {
+    return with_options(kSoftVote, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        svs::Geometry g;
+        uint64_t total = 0, cap = 0;
+        if (int rc = vote_checks(gray, planes, delta, n, period, tally_out, false, flags, o, &g, &total, &cap)) return rc;
+        if (cap == 0) {   // nothing votes: the tally of an empty call is all zero
+            if (tally_out) memset(tally_out, 0, 4u * period);
+            if (n_bits_out) *n_bits_out = 0;
+            return (int)SVS_OK;
+        }
+        const uint64_t bytes = 4u * period;
+        return extract_staged(
+            gray, span_bytes(planes), bytes, 0, n_bits_out,
+            [&](const uint8_t *d_in, uint8_t *d_tally, uint64_t, uint64_t *got, hipStream_t st) {
+                SVS_HIP(hipMemsetAsync(d_tally, 0, bytes, st));
+                if (int rc = vote_launch(d_in, g, total, delta, period, stream_bit0, reinterpret_cast<int32_t *>(d_tally), flags, st, o))
+                    return rc;
+                *got = cap;
+                return (int)SVS_OK;
+            },
+            [&](HostStage &c, hipStream_t st) { return stage_d2h(st, tally_out, c.bits.p, bytes); });
     });
 }
 

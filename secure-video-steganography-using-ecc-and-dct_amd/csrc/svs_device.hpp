@@ -881,6 +881,63 @@ __device__ __forceinline__ void copy_soft_run(const uint8_t *tile, uint32_t lane
     }
 }
 
+// The vote tail of the soft side (SoftArgs::vote; svs_soft_vote*): the tile as copy_soft_run finds it, but no byte is written -
+// byte t, call-local stream bit i (run0 + t without an order, first_j + t % n with one), adds vote_of(byte, i < head) to
+// tally[(base + i) mod period] with a global int32 atomic whose result nobody reads.  Integer sums: the order of the adds
+// does not matter.  The residue of the run's (the block's) first byte is taken once in 64 bits (vote_residue); from there a
+// byte is one conditional subtract away.  Where one wave would hit an entry many times it sums first: without an order and
+// period < the run's bytes, lane j walks the tile bytes of residues j, j + 64, .. (stride period) and issues one add each;
+// with an order and period <= 64, lane j < period sums residue j over every block.  The tile is wave-private: no barrier
+// beyond the caller's wave_lds_fence.  Nothing outside the tally's out_bytes = 4 period bytes is touched.
+template <bool KEYED>
+__device__ __forceinline__ void vote_soft_run(const uint8_t *tile, uint32_t lane, uint32_t n, uint32_t blocks, uint64_t run0,
+                                              uint64_t first, const SoftArgs &sa, int32_t *__restrict__ tally, uint64_t out_bytes) {
+    const uint32_t bytes = blocks * n;
+    const uint64_t period = sa.period;
+    if (bytes == 0u) return;   // wave-uniform
+    if constexpr (!KEYED) {
+        const uint64_t r0 = vote_residue(run0, sa);   // wave-uniform
+        if (period < bytes) {                         // wave-uniform; period < 64 n <= 4032
+            const uint32_t p = (uint32_t)period, r = (uint32_t)r0;
+            for (uint32_t j = lane; j < p; j += 64u) {
+                int32_t sum = 0;
+                for (uint32_t t = j >= r ? j - r : j + p - r; t < bytes; t += p) sum += vote_of(tile[t], run0 + t < sa.head);
+                if (4ull * j + 4u <= out_bytes) (void)atomicAdd(tally + j, sum);
+            }
+        } else {
+            for (uint32_t t = lane; t < bytes; t += 64u) {
+                uint64_t j = r0 + t;                  // t < bytes <= period
+                if (j >= period) j -= period;
+                if (4u * j + 4u <= out_bytes) (void)atomicAdd(tally + j, vote_of(tile[t], run0 + t < sa.head));
+            }
+        }
+    } else {
+        // per lane, of its own block: the residue of the first byte and how many of its leading bytes lie in copy 0
+        const uint64_t res = vote_residue(first, sa);
+        const uint32_t r_lo = (uint32_t)res, r_hi = (uint32_t)(res >> 32);
+        const uint32_t lead = first < sa.head ? (sa.head - first < n ? (uint32_t)(sa.head - first) : n) : 0u;
+        if (period <= 64u) {                          // wave-uniform
+            const uint32_t p = (uint32_t)period;
+            int32_t sum = 0;
+            for (uint32_t j = 0; j < blocks; ++j) {   // wave-uniform trip count: the shuffles run with every lane on
+                const uint32_t r = (uint32_t)__shfl((int)r_lo, (int)j), lead_j = (uint32_t)__shfl((int)lead, (int)j);
+                // lanes at or past the period sum bytes of the tile too and drop the sum
+                for (uint32_t s = lane >= r ? lane - r : lane + p - r; s < n; s += p) sum += vote_of(tile[j * n + s], s < lead_j);
+            }
+            if (lane < p && 4u * lane + 4u <= out_bytes) (void)atomicAdd(tally + lane, sum);
+        } else {
+            for (uint32_t t0 = 0; t0 < bytes; t0 += 64u) {   // wave-uniform trip count, as copy_soft_run
+                const uint32_t t = t0 + lane;
+                const uint32_t j = min((t * sa.recip) >> 20, 63u), s = t - j * n;
+                uint64_t at = (((uint64_t)(uint32_t)__shfl((int)r_hi, (int)j) << 32) | (uint32_t)__shfl((int)r_lo, (int)j)) + s;
+                const uint32_t lead_j = (uint32_t)__shfl((int)lead, (int)j);
+                if (at >= period) at -= period;       // s < n <= 63 < period
+                if (t < bytes && 4u * at + 4u <= out_bytes) (void)atomicAdd(tally + at, vote_of(tile[t], s < lead_j));
+            }
+        }
+    }
+}
+
 // The eight-row instantiations are register-allocated for the six waves per SIMD they ran at before the dithered side joined
 // them (75 - 80 VGPRs; each side fits on its own, left alone the allocator takes 81 - 85 for the pair); a minimum of 1 is the
 // default of the others.
@@ -898,7 +955,9 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
     if constexpr (U == 8) {
         if (soft.on) {     // wave-uniform
             extern __shared__ uint32_t soft_tiles[];
-            const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+            // the wave index as a scalar: with it in a vector register the keyed instantiations, at their bound of 80, spilled
+            // the thread index across the block body once the vote tail joined (profiles/soft_vote_resources.txt)
+            const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
             const uint32_t n = g.n_ac;   // == dith.sel.count
             const uint32_t wave_first = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + wave * 64u;
             const uint32_t gblock = wave_first + lane;
@@ -917,8 +976,12 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
                 if constexpr (KEYED) first = stream_first<true>(gblock, n, g, order_arg(order...));
             }
             wave_lds_fence();
-            copy_soft_run<KEYED>(tile, lane, n, wave_first < g.total_blocks ? min(64u, g.total_blocks - wave_first) : 0u,
-                                 (uint64_t)wave_first * n, first, soft.recip, out, out_bytes);
+            const uint32_t blocks = wave_first < g.total_blocks ? min(64u, g.total_blocks - wave_first) : 0u;
+            if (soft.vote)     // wave-uniform: `out` is the tally of a vote call, out_bytes its 4 period bytes
+                vote_soft_run<KEYED>(tile, lane, n, blocks, (uint64_t)wave_first * n, first, soft, reinterpret_cast<int32_t *>(out),
+                                     out_bytes);
+            else
+                copy_soft_run<KEYED>(tile, lane, n, blocks, (uint64_t)wave_first * n, first, soft.recip, out, out_bytes);
             return;
         }
     }

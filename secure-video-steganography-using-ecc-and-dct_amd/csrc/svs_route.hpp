@@ -39,6 +39,8 @@ struct RouteArgs {
     // a soft call (svs_soft_extract*; gray extract only): the eight-row pocketfft-identical extract kernel in every mode, with a
     // prefix, a selection, a dither or an order - the reliability is a distance of the reference's own quantiser input
     bool soft = false;
+    // a vote call (svs_soft_vote*): a soft call whose bytes are added into a tally instead of written (SoftArgs::vote)
+    bool vote = false;
 };
 
 inline bool route_selected(const RouteArgs &a) {
@@ -140,6 +142,7 @@ struct ExtractPlan {
     bool dithered;            // the launch switches the exact kernel's dithered side on (EXACT with rows = 8; not ZEROS)
     bool soft;                // the launch switches the exact kernel's soft side on (EXACT with rows = 8; ZEROS: every byte 0)
     uint32_t n_ac;            // soft: bytes per block, the count of the table the soft side reads
+    bool vote = false;        // soft, and the launch switches the soft side's vote tail on: `out` is the tally (never ZEROS)
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -147,7 +150,8 @@ struct ExtractPlan {
 // contiguous eighth); more rows - VALU-bound, the map does not matter.
 inline ExtractPlan plan_extract(const RouteArgs &a) {
     ExtractPlan p{};
-    p.soft = a.soft;
+    p.soft = a.soft || a.vote;
+    p.vote = a.vote;
     p.n_ac = a.n_ac;
     if (!(a.delta > 0.0)) {
         p.path = ExtractPath::ZEROS;
@@ -182,6 +186,7 @@ struct KernelOptions {
     BlockOrderArgs ord;
     const CoeffTable *coeffs;
     DitherArgs dith;
+    uint64_t vote_period = 0, vote_bit0 = 0;   // a vote call: the payload length in bits and the call's first stream position
 };
 
 struct LaunchTables {   // the `sel` and `dith` arguments of the two exact kernels, and extract_exact_kernel's `soft`
@@ -211,7 +216,9 @@ inline LaunchTables extract_tables(const ExtractPlan &p, const KernelOptions &k)
     const CoeffTable sel = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
     return {sel,
             {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, !p.soft ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)},
-            p.soft ? make_soft_args(p.qp.delta_f, p.n_ac) : SoftArgs{}};
+            !p.soft   ? SoftArgs{}
+            : !p.vote ? make_soft_args(p.qp.delta_f, p.n_ac)
+                      : make_vote_args(make_soft_args(p.qp.delta_f, p.n_ac), k.vote_period, k.vote_bit0)};
 }
 
 }  // namespace svs

@@ -8,6 +8,8 @@ Two levels:
   * `embed_device` / `extract_device`      raw device pointers + stream (what bench.py and a
                                            device-resident pipeline use); nothing is copied.
   * `extract_soft_frames` / `extract_soft_device`   the same two levels of the soft-decision extraction: a byte per bit.
+  * `embed_repeated_frames`, `extract_vote_frames` / `extract_vote_device`   a payload tiled through the stream, and the
+                                           fused soft vote that folds its copies on the device: `period` integers come back.
 Bits travel packed MSB-first (numpy.packbits order), so `unpack_to_str` of the extract output is
 the reference operator's '0'/'1' string.
 """
@@ -22,6 +24,7 @@ import numpy as np
 from . import coeffs as _coeffs
 from . import dither as _dither
 from . import native
+from . import soft as _soft
 from .hostmem import pinned_empty
 from .native import BlockOrder, Dither, Planes
 from .order import check_key
@@ -344,6 +347,63 @@ def extract_soft_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: 
     return out[:n], n
 
 
+def _period(period) -> int:
+    period = int(period)
+    if not 1 <= period < 1 << 61:
+        raise ValueError(f"period {period} outside 1 .. 2**61 - 1")
+    return period
+
+
+def _vote_call(lib, call: _GrayCall, front, delta, n_ac, period, stream_bit0, tally, flags, got, stream=()) -> None:
+    """svs_soft_vote(*front, order, coeffs, dither, delta, n_ac, period, stream_bit0, tally, flags, n_bits_out), or with
+    stream = (handle,) its _dev form"""
+    name = "svs_soft_vote" + ("_dev" if stream else "")
+    native.check(getattr(lib, name)(*front, _ref(call.order), _ref(call.sel), _ref(call.dith), float(delta), int(n_ac), int(period),
+                                    int(stream_bit0), tally, flags, C.byref(got), *stream), name)
+
+
+def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: int = 0, device: int = 0, mode: str | None = None,
+                        block_key=None, first_frame=None, coeffs=None, dither_key=None):
+    """Fused soft vote over a stack of gray frames on the GPU (svs_soft_vote, include/svsdct.h): the soft bytes of
+    extract_soft_frames are never written - the kernel adds each into a tally of `period` int32 values at its stream position
+    (stream_bit0 + its index) mod period, and only the tally comes back.  period: the payload's length in bits, as the sender
+    tiled it (embed_repeated_frames).  stream_bit0: the capacity of the frames before this stack when a clip is read in
+    batches - add the tallies of the batches and read the bits with soft.tally_bits.  The other keywords: as
+    extract_soft_frames.  Returns (bits uint8 [period], tally int32 [period]); the bits are soft.combine's."""
+    period = _period(period)
+    call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
+    lib = native.load()
+    native.ensure_device(device)
+    stack = _as_stack(frames)
+    f, h, w = stack.shape
+    tally = pinned_empty(4 * period).view(np.int32)
+    got = C.c_uint64(0)
+    planes = Planes.contiguous(f, h, w)
+    _vote_call(lib, call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, period, stream_bit0, tally.ctypes.data, mode_flags(mode),
+               got)
+    return _soft.tally_bits(tally), tally
+
+
+def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | None = None, **embed_kw):
+    """Embed a payload more than once: soft.tile(bits, copies * len(bits)) - copy after copy, copies=None: as many as the
+    stack's capacity holds, the last one cut where it ends - through embed_frames, which takes every other keyword.  There is
+    no embed kernel path of its own: the tiled stream is an eighth of a byte per capacity bit.
+    Returns (stego, used, period), and the ReadbackCounts behind them where embed_frames returns them; period = len(bits) is
+    what the receiver passes to extract_vote_frames."""
+    if isinstance(bits, str):
+        bits = str_to_bits(bits)
+    bits = np.asarray(bits, np.uint8)
+    if "bit_offset" in embed_kw or "n_bits" in embed_kw:
+        raise ValueError("embed_repeated_frames embeds the whole tiled stream: bit_offset and n_bits are not its keywords")
+    f, h, w = _as_stack(frames).shape
+    cap = capacity_bits(f, h, w, n_ac)      # a selection lists n_ac coefficients
+    if copies is not None and int(copies) < 1:
+        raise ValueError("copies must be at least 1")
+    stream = _soft.tile(bits, cap if copies is None else min(cap, int(copies) * bits.size))
+    stego, used, *counts = embed_frames(frames, delta, n_ac, stream, **embed_kw)
+    return (stego, used, int(bits.size), *counts)
+
+
 # ---- the reference operator's own payload types: '0' / '1' strings ------------------------------------------
 _utf8_and_size = None
 
@@ -456,6 +516,19 @@ def extract_soft_device(d_gray: int, planes: Planes, delta, n_ac, d_soft_out: in
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     _soft_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac,
                [d_soft_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)], (stream or None,))
+    return int(got.value)
+
+
+def extract_vote_device(d_gray: int, planes: Planes, delta, n_ac, d_tally: int, period, stream_bit0: int = 0, stream: int = 0,
+                        order: BlockOrder | None = None, first_frame: int | None = None, coeffs=None, dither_key=None) -> int:
+    """Enqueue the fused soft vote on `stream` (svs_soft_vote_dev): the batch's votes are ADDED into d_tally, `period` int32
+    values in device memory (4-byte aligned) that the caller zeroes before the first batch; stream_bit0 is the capacity of the
+    frames before the batch.  Returns the number of bits that voted.  order, coeffs, dither_key, first_frame: as
+    extract_soft_device."""
+    got = C.c_uint64(0)
+    call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
+    _vote_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac, _period(period), stream_bit0, d_tally, 0, got,
+               (stream or None,))
     return int(got.value)
 
 

@@ -6,8 +6,10 @@ from the nearest decision boundary of its quantiser cell in units of delta / 254
 boundary.  m is a DISTANCE, not a probability: what it says about the chance of a bit error depends on the disturbance
 between sender and receiver, which nobody here knows.
 
-A sender that wants a payload to survive a lost bit tiles it - copy after copy through the stream, the last one cut where the
-capacity ends - and embeds the tiled stream as any other; the receiver extracts soft bytes and folds them with combine().
+A sender that wants a payload to survive a lost bit tiles it - tile(): copy after copy through the stream, the last one cut
+where the capacity ends - and embeds the tiled stream as any other (batch.embed_repeated_frames); the receiver extracts soft
+bytes and folds them with combine(), or has the device fold them in the extract launch (svs_soft_vote, batch.extract_vote_frames)
+and gets the tally of tally() back: `period` integers whose signs are combine()'s bits.
 """
 from __future__ import annotations
 
@@ -48,6 +50,44 @@ def combine(soft, period: int):
     score = padded.reshape(copies, period).sum(axis=0, dtype=np.int32)
     bits = np.where(score != 0, score > 0, a[:period] >> 7).astype(np.uint8)
     return bits, score
+
+
+def tile(bits, n_bits: int) -> np.ndarray:
+    """the payload repeated to n_bits stream bits, the last copy cut: uint8 0 / 1.  ValueError for an empty payload"""
+    b = np.asarray(bits, np.uint8).reshape(-1)
+    n_bits = int(n_bits)
+    if b.size == 0:
+        raise ValueError("an empty payload cannot be tiled")
+    if n_bits < 0:
+        raise ValueError("n_bits is negative")
+    return np.resize(b, n_bits)
+
+
+def tally(soft, period: int, stream_bit0: int = 0) -> np.ndarray:
+    """The tally of the fused vote (svs_soft_vote, include/svsdct.h) on soft bytes: byte i has stream position
+    p = stream_bit0 + i and adds 2 (2 b - 1) (2 m + 1) to entry p mod period, and (2 b - 1) more where p < period - copy 0
+    breaks ties, so an entry that copy 0 has reached is odd and never 0.  Tallies of consecutive pieces of a stream, each at its
+    own stream_bit0, add up to the tally of the whole.  period may exceed len(soft).  int32 [period]."""
+    a = _soft(soft)
+    period, stream_bit0 = int(period), int(stream_bit0)
+    if period < 1 or stream_bit0 < 0:
+        raise ValueError("period must be at least 1 and stream_bit0 at least 0")
+    sign = 2 * (a >> 7).astype(np.int64) - 1
+    head = np.arange(a.size, dtype=np.int64) < max(period - stream_bit0, 0)             # p < period: the bits of copy 0
+    votes = 2 * sign * (2 * (a & 127).astype(np.int64) + 1) + sign * head
+    base = stream_bit0 % period                                                         # byte i sits at residue (base + i) mod period
+    rows = -(-(base + a.size) // period)
+    padded = np.zeros(max(rows, 1) * period, np.int64)
+    padded[base: base + a.size] = votes
+    out = padded.reshape(-1, period).sum(axis=0)
+    if np.abs(out).max() >= 1 << 31:
+        raise OverflowError("a tally entry leaves int32")
+    return out.astype(np.int32)
+
+
+def tally_bits(tally) -> np.ndarray:
+    """the decoded payload bits of a tally, uint8 0 / 1: entry > 0"""
+    return (np.asarray(tally) > 0).astype(np.uint8)
 
 
 def margin_histogram(soft, n_frames: int) -> np.ndarray:
