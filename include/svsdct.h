@@ -473,7 +473,7 @@ int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const sv
  * AND how far the coefficient sits from the nearest decision boundary of its quantiser cell - the quantity SVS_NEAREST,
  * SVS_MINMOVE, read-back, the selection and the dither all work on at the sending end.  A sender reads from it how much
  * disturbance a stego clip survives; a receiver sees which frames sit on the lattice; a caller that embedded the payload more
- * than once (by tiling it) combines the copies by their reliabilities (svsdct/soft.py, combine; on the device: svs_soft_vote*).
+ * than once (by tiling it) combines the copies by their reliabilities (svsdct/soft.py, combine; on the device: svs_soft_vote*).  The per-frame view of the first two uses: svs_soft_histogram*.
  * The byte is a FORMAT, a contract between builds as the dither's rule is.  Layout: one byte per capacity bit in stream order;
  * byte i belongs to stream bit i of the hard extract call with the same order, coeffs, dither, delta and n_ac.  For the
  * payload coefficient with quantiser input x - x = c for a call without a dither, x = c - d under one, c the
@@ -560,6 +560,47 @@ int svs_soft_vote_dev(const uint8_t *d_gray, const svs_planes *planes, const svs
 int svs_soft_vote(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                   const svs_dither *dither, double delta, int n_ac, uint64_t period, uint64_t stream_bit0, int32_t *tally_out,
                   uint32_t flags, uint64_t *n_bits_out);
+
+/* ---- fused per-frame soft histograms: 256 counts a frame, no soft bytes --------------------------------------
+ * Two of the soft byte's three uses - how much disturbance a clip survives, which frames sit on the lattice - want a few hundred
+ * numbers per frame, not a byte per capacity bit.  These calls run the soft extraction and count in the same launch: the soft
+ * bytes are never written, each is counted into a row of 256 uint32 values of its frame, and the rows' 1 KB per frame are all
+ * that leaves the device.  The rows are a FORMAT, as the soft byte and the tally are.  For a call on n_frames planes, with i the
+ * index of a capacity bit within the call and `byte` its soft byte exactly as svs_soft_extract writes it for the same coeffs,
+ * dither, delta and n_ac (and no order):
+ *     f = i / (N * count)              N = (height / 8) * (width / 8), count = clamp(n_ac, 0, 63) or the selection's count
+ *     hist[f * 256 + byte] += 1        for every capacity bit of the call
+ * Row f sums to N * count; hist[f][v] + hist[f][v + 128] is entry v of svsdct/soft.py margin_histogram; the sum of
+ * hist[f][128 .. 255] is the frame's number of hard ones.  All arithmetic is integer counting: the result does not depend on the
+ * order of the additions, so the calls are deterministic though the device adds with atomics.
+ * There is NO svs_block_order argument and none is needed: the dither is keyed to a block's physical position and an order
+ * only permutes the blocks inside a frame, so the multiset of a frame's bytes is the same under every order - a frame embedded
+ * under an order is read with this same call (its dither's first_frame as in every other call).
+ *   d_hist   : n_frames * 256 uint32 values in device memory, 4-byte aligned.  The call ADDS into them, as svs_soft_vote_dev adds
+ *            into d_tally: zero them before the first call.  It keeps no state and allocates nothing.  A clip read in batches
+ *            passes d_hist + 256 * (frames before the batch), and first_frame advanced under a dither.
+ *   hist_out : n_frames * 256 uint32 values in host memory.  The host form stages whole frames in one piece as svs_extract does
+ *            (no chunk boundary falls inside a frame), counts into zeroed rows of its per-thread staging context and WRITES
+ *            exactly n_frames * 256 values.
+ *   coeffs, dither, planes, flags : as svs_soft_extract*, checked as there; the mode bits are accepted and change nothing.
+ *   n_bits_out : receives the capacity, the number of bytes counted.
+ * SVS_ERR_INVALID_ARG: embed flags or unknown ones; delta <= 0 (every soft byte is 0 there and a histogram of them says
+ * nothing); a faulty coeffs, dither or planes; with a capacity above 0, a NULL gray or hist pointer, a device hist that is not
+ * 4-byte aligned, or N * count above 2^32 - 1 (one call must not be able to wrap an entry: 1 x 66080 x 66080 at n_ac = 63 is
+ * refused; across several calls into the same rows the caller owns the bound).  Every refusal comes before any device work and
+ * leaves hist and *n_bits_out as they were.  A capacity of 0 is SVS_OK with *n_bits_out = 0: the device form leaves d_hist
+ * untouched, the host form fills hist_out with zeros.
+ * Cost: the soft call's launch (above) with a third tail, compiled into the instantiations without an order only.  No soft byte
+ * and no per-byte global atomic leaves the CU: a workgroup counts into one table of 256 counters in LDS that only this launch
+ * requests, frame by frame (the frame of a block is the division by blocks per frame that its address already takes), and
+ * flushes each non-zero entry once per workgroup and frame with a global atomic that returns nothing.  Times: README.md.
+ * Limits: a distance histogram, not a detector; all blocks of a frame are counted, payload or not, so a partly filled frame
+ * shows a mixture; there is no colour and no _str form, no FramePipeline or drop-in form. */
+int svs_soft_histogram_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                           double delta, int n_ac, uint32_t *d_hist, uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+int svs_soft_histogram(const uint8_t *gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                       double delta, int n_ac, uint32_t *hist_out, uint32_t flags, uint64_t *n_bits_out);
 
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:

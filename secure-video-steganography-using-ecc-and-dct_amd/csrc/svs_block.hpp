@@ -1735,7 +1735,8 @@ struct SoftArgs {            // by-value argument of extract_exact_kernel (read 
     uint32_t recip;          // ceil(2^20 / n): t / n == (t * recip) >> 20 for every byte index t < 64 n of a wave's run
     // the vote (svs_soft_vote*, make_vote_args): the bytes are not written - each is added into a tally of `period` int32
     uint32_t vote = 0;       // 0: a soft extract call - the bytes are copied out
-    uint32_t pad = 0;
+    // the histogram (svs_soft_histogram*, make_hist_args): the bytes are not written - each is counted into its frame's row
+    uint32_t hist = 0;       // 0: a soft extract or a vote call
     uint64_t period = 0;     // 1 .. 2^61 - 1
     uint64_t base = 0;       // stream_bit0 mod period: call-local bit i has residue (base + i) mod period
     uint64_t head = 0;       // call-local bits i < head lie in copy 0 (stream position below period) and break ties
@@ -1756,6 +1757,14 @@ inline SoftArgs make_vote_args(SoftArgs sa, uint64_t period, uint64_t stream_bit
     sa.base = stream_bit0 % period;
     sa.head = stream_bit0 < period ? period - stream_bit0 : 0u;
     sa.inv = period <= (1ull << 38) ? 1.0 / (double)period : 0.0;
+    return sa;
+}
+
+// ---- the histogram: 256 counts a frame (include/svsdct.h states the format) -------------------------------------------------
+constexpr uint32_t kHistBins = 256;                       // one per value of the soft byte; hist[frame * 256 + byte] += 1
+
+inline SoftArgs make_hist_args(SoftArgs sa) {
+    sa.hist = 1u;
     return sa;
 }
 

@@ -304,7 +304,11 @@ int launch_embed_bgr(const svs::EmbedPlan &p, bool keep, uint64_t total, hipStre
 // (EXACT, rows = 8) switches the kernel's soft side on and is the only launch with dynamic LDS: a tile of 64 n bytes per wave;
 // every byte of its output has one writer, so nothing is cleared (ZEROS: out_bytes, the capacity, of zero bytes).  A vote plan
 // is a soft plan whose `out` is the caller's tally of out_bytes = 4 period bytes, added to and never cleared (never ZEROS).
-uint32_t soft_lds_bytes(const svs::ExtractPlan &p) { return p.soft ? (uint32_t)(SVS_WG / 64) * 64u * p.n_ac : 0u; }
+// A histogram plan is a soft plan whose `out` is the caller's n_frames * 256 uint32 counts, added to and never cleared; it alone
+// requests 256 dwords more, the workgroup's table of counters behind the tiles.
+uint32_t soft_lds_bytes(const svs::ExtractPlan &p) {
+    return p.soft ? (uint32_t)(SVS_WG / 64) * 64u * p.n_ac + (p.hist ? 4u * svs::kHistBins : 0u) : 0u;
+}
 
 int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, const uint8_t *gray, svs::Geometry g, uint8_t *out,
                    uint64_t out_bytes, const svs::KernelOptions &k) {
@@ -795,6 +799,7 @@ constexpr OptionsPolicy kDitheredExtract{true, false, kModeFlags, "a dithered ex
 // order, coeffs and dither may each be NULL
 constexpr OptionsPolicy kSoftExtract{false, false, kModeFlags, "a soft extract takes the mode bits only"};
 constexpr OptionsPolicy kSoftVote{false, false, kModeFlags, "a soft vote takes the mode bits only"};
+constexpr OptionsPolicy kSoftHistogram{false, false, kModeFlags, "a soft histogram takes the mode bits only"};
 // order, coeffs and dither may each be NULL: a NULL dither is the selected call with read-back, all three NULL (or a prefix
 // selection alone) svs_embed_readback* itself; SVS_READBACK is accepted and implied
 constexpr OptionsPolicy kKeyedReadback{false, false, kGrayEmbedFlags,
@@ -923,6 +928,36 @@ int vote_launch(const uint8_t *d_gray, const svs::Geometry &g, uint64_t total, d
     o.vote_period = period;
     o.vote_bit0 = stream_bit0;
     return launch_extract(svs::plan_extract(ra), total, st, d_gray, g, reinterpret_cast<uint8_t *>(d_tally), 4u * period, o.kernel_forms(g));
+}
+
+// What the two histogram calls check, in the order of the vote calls with the counts where the tally stood; nothing is written
+// before the last check has passed (*n_bits_out and the counts are untouched by a refusal).  *cap = 0: an empty call.
+int hist_checks(const void *gray, const svs_planes *planes, double delta, int n_ac, const void *hist, bool device, uint32_t flags,
+                svs::Geometry *g, uint64_t *total, uint64_t *cap) {
+    if (int rc = make_geometry(planes, n_ac, g, total)) return rc;
+    *cap = *total * (uint64_t)g->n_ac;
+    if (int rc = check_extract_flags(flags)) return rc;
+    if (!(delta > 0.0)) return fail(SVS_ERR_INVALID_ARG, "a histogram needs delta > 0 (every soft byte is 0 otherwise)");
+    if (*cap == 0) return SVS_OK;
+    if (!gray || !hist) return fail(SVS_ERR_INVALID_ARG, "gray/hist pointer is NULL");
+    if (device && ((uintptr_t)gray % 8)) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
+    if (device && ((uintptr_t)hist % 4)) return fail(SVS_ERR_INVALID_ARG, "hist pointer must be 4-byte aligned");
+    const uint64_t per_frame = (uint64_t)g->by_bpf.div * g->n_ac;
+    if (per_frame > 0xFFFFFFFFull)
+        return fail(SVS_ERR_INVALID_ARG, "planes hold %llu bytes a frame, above 2^32 - 1: a uint32 hist entry could wrap in one call",
+                    (unsigned long long)per_frame);
+    return SVS_OK;
+}
+
+// the launch of a histogram call whose arguments have passed hist_checks (cap != 0): d_hist = n_frames rows of 256 uint32
+int hist_launch(const uint8_t *d_gray, const svs::Geometry &g, uint64_t total, double delta, uint32_t n_frames, uint32_t *d_hist,
+                uint32_t flags, hipStream_t st, const GrayOptions &o) {
+    svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
+    ra.coeffs = o.coeffs;
+    ra.dithered = o.dither != nullptr;
+    ra.hist = true;
+    return launch_extract(svs::plan_extract(ra), total, st, d_gray, g, reinterpret_cast<uint8_t *>(d_hist),
+                          4ull * svs::kHistBins * n_frames, o.kernel_forms(g));
 }
 
 }  // namespace
@@ -1281,6 +1316,48 @@ int svs_soft_vote(const uint8_t *gray, const svs_planes *planes, const svs_block
                 return (int)SVS_OK;
             },
             [&](HostStage &c, hipStream_t st) { return stage_d2h(st, tally_out, c.bits.p, bytes); });
+    });
+}
+
+// The histogram calls are the soft calls without an order and with 256 counts a frame for an output (include/svsdct.h): the
+// kernel's soft side counts each byte into hist[frame * 256 + byte] instead of writing it.  The device form adds into the
+// caller's counts; the host form stages the frames as svs_extract does (whole frames, one piece), counts into zeroed rows in the
+// staging context and downloads their 1024 n_frames bytes.
+int svs_soft_histogram_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                           double delta, int n_ac, uint32_t *d_hist, uint32_t flags, uint64_t *n_bits_out, void *stream) {
+    return with_options(kSoftHistogram, nullptr, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        svs::Geometry g;
+        uint64_t total = 0, cap = 0;
+        if (int rc = hist_checks(d_gray, planes, delta, n, d_hist, true, flags, &g, &total, &cap)) return rc;
+        if (cap != 0)
+            if (int rc = hist_launch(d_gray, g, total, delta, (uint32_t)planes->n_frames, d_hist, flags, (hipStream_t)stream, o)) return rc;
+        if (n_bits_out) *n_bits_out = cap;
+        return (int)SVS_OK;
+    });
+}
+
+int svs_soft_histogram(const uint8_t *gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                       double delta, int n_ac, uint32_t *hist_out, uint32_t flags, uint64_t *n_bits_out) {
+    return with_options(kSoftHistogram, nullptr, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
+        svs::Geometry g;
+        uint64_t total = 0, cap = 0;
+        if (int rc = hist_checks(gray, planes, delta, n, hist_out, false, flags, &g, &total, &cap)) return rc;
+        const uint64_t bytes = 4ull * svs::kHistBins * (uint64_t)planes->n_frames;
+        if (cap == 0) {   // nothing is counted: the rows of an empty call are all zero
+            if (hist_out) memset(hist_out, 0, bytes);
+            if (n_bits_out) *n_bits_out = 0;
+            return (int)SVS_OK;
+        }
+        return extract_staged(
+            gray, span_bytes(planes), bytes, 0, n_bits_out,
+            [&](const uint8_t *d_in, uint8_t *d_hist, uint64_t, uint64_t *got, hipStream_t st) {
+                SVS_HIP(hipMemsetAsync(d_hist, 0, bytes, st));
+                if (int rc = hist_launch(d_in, g, total, delta, (uint32_t)planes->n_frames, reinterpret_cast<uint32_t *>(d_hist), flags, st, o))
+                    return rc;
+                *got = cap;
+                return (int)SVS_OK;
+            },
+            [&](HostStage &c, hipStream_t st) { return stage_d2h(st, hist_out, c.bits.p, bytes); });
     });
 }
 

@@ -938,6 +938,40 @@ __device__ __forceinline__ void vote_soft_run(const uint8_t *tile, uint32_t lane
     }
 }
 
+// The histogram tail of the soft side (SoftArgs::hist; svs_soft_histogram*; the instantiations without an order only): the tiles
+// as copy_soft_run finds them, but no byte is written - each is counted into hist[frame * 256 + byte], a row of 256 uint32 per
+// frame.  The workgroup shares ONE table of 256 LDS counters (`table`: behind the tiles, requested by this launch only) and
+// walks the frames its SVS_WG blocks touch - fast_div by blocks per frame, as block_offset: one frame at 4K, 256 at one block a
+// frame - with a workgroup-uniform trip count.  Per frame: every wave adds the bytes of its own part of the frame (frame_run,
+// svs_index.hpp) with one LDS atomic each - the tile is wave-private, the table is not: barriers -, then thread v flushes
+// entry v with ONE global atomic whose result nobody reads, skipped where the entry is 0, and clears it for the next frame.
+// (Counting the bytes equal to the first pending lane's by a ballot before the atomics, to spare the LDS the serialised adds to
+// a hot entry, measured slower on noise and on stego alike, and a table per wave - fences instead of barriers, four times the
+// flushes - 25 to 31 % slower on noise at n <= 10: profiles/soft_histogram_variants.txt.)  Integer counting: the order of the
+// adds does not matter.  Nothing outside the out_bytes = 1024 n_frames bytes of `hist` is touched.
+__device__ __forceinline__ void hist_soft_run(const uint8_t *tile, uint32_t *table, uint32_t lane, uint32_t n, uint32_t blocks,
+                                              uint32_t wave_first, uint32_t wg_first, const Geometry &g,
+                                              uint32_t *__restrict__ hist, uint64_t out_bytes) {
+    static_assert(SVS_WG == (int)kHistBins, "thread v of the workgroup owns entry v of the table");
+    const uint32_t wg_blocks = wg_first < g.total_blocks ? min((uint32_t)SVS_WG, g.total_blocks - wg_first) : 0u;
+    if (wg_blocks == 0u) return;   // workgroup-uniform: no barrier is left waiting
+    const uint32_t bpf = g.by_bpf.div;
+    const uint32_t f_first = fast_div(wg_first, g.by_bpf), f_last = fast_div(wg_first + wg_blocks - 1u, g.by_bpf);
+    table[threadIdx.x] = 0u;
+    for (uint32_t f = f_first; f <= f_last; ++f) {   // workgroup-uniform
+        __syncthreads();                             // the table is clear
+        uint32_t begin, end;
+        frame_run(wave_first, blocks, f, bpf, &begin, &end);
+        const uint32_t t_end = end * n;
+        for (uint32_t t = begin * n + lane; t < t_end; t += 64u) (void)atomicAdd(&table[tile[t]], 1u);
+        __syncthreads();                             // every wave's counts of frame f are in
+        const uint32_t c = table[threadIdx.x];
+        table[threadIdx.x] = 0u;
+        const uint64_t at = (uint64_t)f * kHistBins + threadIdx.x;
+        if (c != 0u && 4u * at + 4u <= out_bytes) (void)atomicAdd(hist + at, c);
+    }
+}
+
 // The eight-row instantiations are register-allocated for the six waves per SIMD they ran at before the dithered side joined
 // them (75 - 80 VGPRs; each side fits on its own, left alone the allocator takes 81 - 85 for the pair); a minimum of 1 is the
 // default of the others.
@@ -977,6 +1011,13 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
             }
             wave_lds_fence();
             const uint32_t blocks = wave_first < g.total_blocks ? min(64u, g.total_blocks - wave_first) : 0u;
+            if constexpr (!KEYED) {
+                if (soft.hist) {   // wave-uniform: `out` is the rows of a histogram call, out_bytes their 1024 n_frames bytes
+                    hist_soft_run(tile, soft_tiles + (SVS_WG / 64) * 16u * n, lane, n, blocks, wave_first, wave_first - wave * 64u, g,
+                                  reinterpret_cast<uint32_t *>(out), out_bytes);
+                    return;
+                }
+            }
             if (soft.vote)     // wave-uniform: `out` is the tally of a vote call, out_bytes its 4 period bytes
                 vote_soft_run<KEYED>(tile, lane, n, blocks, (uint64_t)wave_first * n, first, soft, reinterpret_cast<int32_t *>(out),
                                      out_bytes);

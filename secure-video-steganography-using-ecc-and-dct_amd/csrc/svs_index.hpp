@@ -76,6 +76,19 @@ SVS_HD int64_t block_offset_bgr(uint32_t gblock, const Geometry &g, int64_t row_
     return block_offset_at(gblock, g.by_wb, g.by_bpf, row_pitch, frame_pitch, 24u);
 }
 
+// The part of a run of `count` consecutive global blocks that starts at block `first` which lies in frame f, as positions
+// [*begin, *end) within the run (empty: *begin == *end).  bpf = blocks per frame; (f + 1) * bpf and first + count stay below
+// 2^32 (a call has fewer than 2^31 blocks, a grid at most one workgroup more).  The frames a run touches are
+// fast_div(first, by_bpf) .. fast_div(first + count - 1, by_bpf), the division block_offset performs; walking them with this
+// function cuts the run into its per-frame runs (the histogram tail of the soft side, svs_device.hpp hist_soft_run).
+SVS_HD void frame_run(uint32_t first, uint32_t count, uint32_t f, uint32_t bpf, uint32_t *begin, uint32_t *end) {
+    const uint32_t lo = f * bpf, hi = lo + bpf, last = first + count;
+    // both frame edges clamped into [first, last]: a frame before or behind the run gives an empty part at that end
+    const uint32_t b = lo < first ? first : (lo > last ? last : lo), e = hi < first ? first : (hi > last ? last : hi);
+    *begin = b - first;
+    *end = e - first;
+}
+
 constexpr uint32_t kEighth = 0xFFFFFFFFu;   // tile_of() chunk: one contiguous eighth of the grid per XCD-group
 
 // Workgroup -> tile mapping.  Workgroups are dealt round-robin over the 8 XCDs (i % 8 names the

@@ -41,6 +41,9 @@ struct RouteArgs {
     bool soft = false;
     // a vote call (svs_soft_vote*): a soft call whose bytes are added into a tally instead of written (SoftArgs::vote)
     bool vote = false;
+    // a histogram call (svs_soft_histogram*): a soft call whose bytes are counted per frame instead of written (SoftArgs::hist);
+    // never keyed - the counts of a frame do not depend on an order
+    bool hist = false;
 };
 
 inline bool route_selected(const RouteArgs &a) {
@@ -143,6 +146,8 @@ struct ExtractPlan {
     bool soft;                // the launch switches the exact kernel's soft side on (EXACT with rows = 8; ZEROS: every byte 0)
     uint32_t n_ac;            // soft: bytes per block, the count of the table the soft side reads
     bool vote = false;        // soft, and the launch switches the soft side's vote tail on: `out` is the tally (never ZEROS)
+    bool hist = false;        // soft, and the launch switches the soft side's histogram tail on: `out` is n_frames * 256 uint32
+                              // counts, added to; the launch requests 256 more dwords of dynamic LDS (never ZEROS, never keyed)
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -150,8 +155,9 @@ struct ExtractPlan {
 // contiguous eighth); more rows - VALU-bound, the map does not matter.
 inline ExtractPlan plan_extract(const RouteArgs &a) {
     ExtractPlan p{};
-    p.soft = a.soft || a.vote;
+    p.soft = a.soft || a.vote || a.hist;
     p.vote = a.vote;
+    p.hist = a.hist;
     p.n_ac = a.n_ac;
     if (!(a.delta > 0.0)) {
         p.path = ExtractPath::ZEROS;
@@ -174,7 +180,7 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     // so FAST mode uses it too; with more rows it costs ~17 % and stays opt-in.
     if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected || p.dithered || p.soft) exact = true;
     p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
-    p.keyed = a.keyed;
+    p.keyed = a.keyed && !a.hist;
     return p;
 }
 
@@ -216,9 +222,10 @@ inline LaunchTables extract_tables(const ExtractPlan &p, const KernelOptions &k)
     const CoeffTable sel = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
     return {sel,
             {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, !p.soft ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)},
-            !p.soft   ? SoftArgs{}
-            : !p.vote ? make_soft_args(p.qp.delta_f, p.n_ac)
-                      : make_vote_args(make_soft_args(p.qp.delta_f, p.n_ac), k.vote_period, k.vote_bit0)};
+            !p.soft  ? SoftArgs{}
+            : p.vote ? make_vote_args(make_soft_args(p.qp.delta_f, p.n_ac), k.vote_period, k.vote_bit0)
+            : p.hist ? make_hist_args(make_soft_args(p.qp.delta_f, p.n_ac))
+                     : make_soft_args(p.qp.delta_f, p.n_ac)};
 }
 
 }  // namespace svs

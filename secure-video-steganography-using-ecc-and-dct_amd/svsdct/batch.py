@@ -10,6 +10,7 @@ Two levels:
   * `extract_soft_frames` / `extract_soft_device`   the same two levels of the soft-decision extraction: a byte per bit.
   * `embed_repeated_frames`, `extract_vote_frames` / `extract_vote_device`   a payload tiled through the stream, and the
                                            fused soft vote that folds its copies on the device: `period` integers come back.
+  * `extract_histogram_frames` / `extract_histogram_device`   the fused per-frame soft histograms: 256 counts a frame come back.
 Bits travel packed MSB-first (numpy.packbits order), so `unpack_to_str` of the extract output is
 the reference operator's '0'/'1' string.
 """
@@ -384,6 +385,34 @@ def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: in
     return _soft.tally_bits(tally), tally
 
 
+def _histogram_call(lib, call: _GrayCall, front, delta, n_ac, hist, flags, got, stream=()) -> None:
+    """svs_soft_histogram(*front, coeffs, dither, delta, n_ac, hist, flags, n_bits_out), or with stream = (handle,) its _dev form"""
+    name = "svs_soft_histogram" + ("_dev" if stream else "")
+    native.check(getattr(lib, name)(*front, _ref(call.sel), _ref(call.dith), float(delta), int(n_ac), hist, flags, C.byref(got),
+                                    *stream), name)
+
+
+def extract_histogram_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, first_frame=None,
+                             coeffs=None, dither_key=None):
+    """Fused per-frame soft histograms of a stack of gray frames on the GPU (svs_soft_histogram, include/svsdct.h): the soft
+    bytes of extract_soft_frames are never written - the kernel counts each into row `frame`, column `byte` of 256 counts a
+    frame, and only the rows come back (soft.byte_histogram is the model; soft.margins and soft.lattice_share read them).
+    There is no block_key keyword and none is needed: the dither is keyed to a block's physical position and an order only
+    permutes the blocks inside a frame, so a frame's counts are the same under every order - frames embedded under a block_key
+    are read with this same call.  first_frame, coeffs, dither_key: as extract_soft_frames; mode is accepted and changes
+    nothing.  Returns (hist uint32 [n_frames, 256], n_bits)."""
+    call = _resolve(n_ac, None, None, 0 if first_frame is None else first_frame, coeffs, dither_key)
+    lib = native.load()
+    native.ensure_device(device)
+    stack = _as_stack(frames)
+    f, h, w = stack.shape
+    hist = pinned_empty(max(4, 1024 * f))[: 1024 * f].view(np.uint32).reshape(f, 256)
+    got = C.c_uint64(0)
+    planes = Planes.contiguous(f, h, w)
+    _histogram_call(lib, call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, hist.ctypes.data, mode_flags(mode), got)
+    return hist, int(got.value)
+
+
 def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | None = None, **embed_kw):
     """Embed a payload more than once: soft.tile(bits, copies * len(bits)) - copy after copy, copies=None: as many as the
     stack's capacity holds, the last one cut where it ends - through embed_frames, which takes every other keyword.  There is
@@ -529,6 +558,19 @@ def extract_vote_device(d_gray: int, planes: Planes, delta, n_ac, d_tally: int, 
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     _vote_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac, _period(period), stream_bit0, d_tally, 0, got,
                (stream or None,))
+    return int(got.value)
+
+
+def extract_histogram_device(d_gray: int, planes: Planes, delta, n_ac, d_hist: int, stream: int = 0, first_frame: int | None = None,
+                             coeffs=None, dither_key=None) -> int:
+    """Enqueue the fused per-frame soft histograms on `stream` (svs_soft_histogram_dev): the batch's bytes are ADDED into d_hist,
+    planes.n_frames rows of 256 uint32 in device memory (4-byte aligned) that the caller zeroes before the first call; a clip
+    read in batches passes d_hist + 1024 * (frames before the batch) and, under a dither, first_frame advanced by as many.
+    Returns the number of bytes counted.  No order and no block_key: a frame's counts do not depend on one (see
+    extract_histogram_frames).  coeffs, dither_key, first_frame: as extract_soft_device."""
+    got = C.c_uint64(0)
+    call = _resolve(n_ac, None, None, first_frame, coeffs, dither_key)
+    _histogram_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac, d_hist, 0, got, (stream or None,))
     return int(got.value)
 
 

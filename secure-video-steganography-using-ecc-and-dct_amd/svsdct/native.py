@@ -124,6 +124,8 @@ SIGNATURES = {
                                      _u64p, C.c_void_p]),
     "svs_soft_vote": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, C.c_double, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
                                  _u64p]),
+    "svs_soft_histogram_dev": (C.c_int, [_u8p, _PL, _CO, _DI, C.c_double, C.c_int, C.c_void_p, C.c_uint32, _u64p, C.c_void_p]),
+    "svs_soft_histogram": (C.c_int, [_u8p, _PL, _CO, _DI, C.c_double, C.c_int, C.c_void_p, C.c_uint32, _u64p]),
     "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                           _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,

@@ -10,6 +10,10 @@ A sender that wants a payload to survive a lost bit tiles it - tile(): copy afte
 where the capacity ends - and embeds the tiled stream as any other (batch.embed_repeated_frames); the receiver extracts soft
 bytes and folds them with combine(), or has the device fold them in the extract launch (svs_soft_vote, batch.extract_vote_frames)
 and gets the tally of tally() back: `period` integers whose signs are combine()'s bits.
+
+A receiver that only asks which frames sit on the lattice, or a sender that asks for the lowest reliability of each frame, needs
+no byte at all: svs_soft_histogram (batch.extract_histogram_frames) returns 256 counts a frame, the array of byte_histogram();
+margins() and lattice_share() read it.
 """
 from __future__ import annotations
 
@@ -102,3 +106,42 @@ def margin_histogram(soft, n_frames: int) -> np.ndarray:
     hist = np.zeros((n_frames, 128), np.int64)
     np.add.at(hist, (np.repeat(np.arange(n_frames), m.shape[1]), m.ravel()), 1)
     return hist
+
+
+def byte_histogram(soft, n_frames: int) -> np.ndarray:
+    """int64 [n_frames, 256]: how many bytes of each frame have each value - the format of svs_soft_histogram
+    (include/svsdct.h) on soft bytes.  The stream is the frames' bytes in order, equally many per frame; row f sums to that
+    number, row[128:] counts the frame's hard ones."""
+    a = _soft(soft)
+    n_frames = int(n_frames)
+    if n_frames < 1 or a.size % n_frames:
+        raise ValueError(f"{a.size} bytes are not {n_frames} frames of equal capacity")
+    per = a.size // n_frames
+    at = np.repeat(np.arange(n_frames, dtype=np.int64), per) * 256 + a
+    return np.bincount(at, minlength=256 * n_frames).astype(np.int64).reshape(n_frames, 256)
+
+
+def _hist(hist) -> np.ndarray:
+    h = np.asarray(hist)
+    if h.ndim != 2 or h.shape[1] != 256 or h.dtype.kind not in "iu":
+        raise TypeError("hist must be an integer array [n_frames, 256] (byte_histogram, svs_soft_histogram)")
+    return h.astype(np.int64)
+
+
+def margins(hist) -> np.ndarray:
+    """int64 [n_frames, 128]: the counts per m of a byte histogram, both hard bits together - margin_histogram of the bytes"""
+    h = _hist(hist)
+    return h[:, :128] + h[:, 128:]
+
+
+def lattice_share(hist, m_min: int = 64) -> np.ndarray:
+    """float64 per frame: the share of a frame's bytes with m >= m_min.  1.0 for stego read without a dither or with its key,
+    about a half for a never-embedded frame and for dithered stego read without the key; a frame without a byte gives nan.
+    A distance statistic, not a detector: every block of the frame is counted, payload or not."""
+    m_min = int(m_min)
+    if not 0 <= m_min <= 128:
+        raise ValueError("m_min outside 0 .. 128")
+    m = margins(hist)
+    total = m.sum(axis=1).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return m[:, m_min:].sum(axis=1) / total
