@@ -721,6 +721,23 @@ uint64_t svs_packed_bytes(uint64_t n_bits) { return (n_bits + 7) / 8; }
 
 namespace {
 
+// What an extract call writes.  BITS: the packed bits.  SOFT: one byte per capacity bit.  VOTE: the bytes' votes, added into
+// a tally of `period` int32 at (stream_bit0 + the bit's index) mod period.  HIST: the bytes counted into 256 uint32 a frame.
+// Everything in which the four kinds differ hangs on this value (extract_checks, extract_dev, extract_host).
+struct ExtractOutput {
+    enum Kind { BITS, SOFT, VOTE, HIST } kind = BITS;
+    uint64_t period = 0, stream_bit0 = 0;   // VOTE
+
+    // a tally or a histogram: the device form adds into the caller's buffer, the host form zeroes its own first (and the caller's
+    // on an empty call); no capacity argument; delta <= 0 is refused; a refusal leaves *n_bits_out alone
+    bool adds() const { return kind == VOTE || kind == HIST; }
+    const char *call() const { return kind == VOTE ? "vote" : "histogram"; }                       // adds() only
+    const char *noun() const { return kind == VOTE ? "tally" : kind == HIST ? "hist" : "bits"; }   // in the messages
+    uint64_t bytes(uint64_t cap, int32_t n_frames) const {
+        return kind == BITS ? (cap + 7) / 8 : kind == SOFT ? cap : kind == VOTE ? 4u * period : 4ull * svs::kHistBins * (uint64_t)n_frames;
+    }
+};
+
 // What a gray call adds to the plain call (svs_embed_dev / svs_extract_dev); every member is optional.  The public entry points
 // fill one - those with a selection or a dither through with_options - and the internal functions below take it.
 struct GrayOptions {
@@ -729,14 +746,26 @@ struct GrayOptions {
     const svs_dither *dither = nullptr;        // the dithered calls
     uint64_t *d_counts = nullptr;              // the read-back calls, device: {repaired, unrepaired}, added to
     svs_readback_counts *counts = nullptr;     // the read-back calls, host: the counts of the whole call
-    bool soft = false;                         // the soft extract calls: one byte per capacity bit instead of packed bits
-    uint64_t vote_period = 0, vote_bit0 = 0;   // the vote calls (vote_period != 0): the payload's bits, the call's stream position
+    ExtractOutput out;                         // the extract calls: what the call writes (the soft calls: not the packed bits)
 
     // the kernels' forms, for a batch of g's blocks per frame (derived once per call)
     svs::KernelOptions kernel_forms(const svs::Geometry &g) const {
         return {order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{}, coeffs,
                 dither ? svs::DitherArgs{svs::dither_seed(dither->key), dither->first_frame, 1u, svs::CoeffTable{}} : svs::DitherArgs{},
-                vote_period, vote_bit0};
+                out.period, out.stream_bit0};
+    }
+
+    // the routing arguments of the call (the one place that fills them from the options)
+    svs::RouteArgs route(double delta, const svs::Geometry &g, uint64_t total, uint64_t n_bits, uint64_t bit_offset, uint32_t flags) const {
+        svs::RouteArgs ra = route_args(delta, g, total, n_bits, bit_offset, flags, false);
+        ra.keyed = order != nullptr;
+        ra.readback = (flags & SVS_READBACK) != 0;   // an embed flag: the extract calls have refused it
+        ra.coeffs = coeffs;                          // the select calls: n_ac == coeffs->count
+        ra.dithered = dither != nullptr;
+        ra.soft = out.kind == ExtractOutput::SOFT;
+        ra.vote = out.kind == ExtractOutput::VOTE;
+        ra.hist = out.kind == ExtractOutput::HIST;
+        return ra;
     }
 
     // The options of a staging chunk of whole frames that starts at frame f0 of the call: its first frame is clip frame
@@ -842,12 +871,7 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
     if (!d_gray || !d_stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
     if (((uintptr_t)d_gray % 8) || ((uintptr_t)d_stego % 8))
         return fail(SVS_ERR_INVALID_ARG, "plane pointers must be 8-byte aligned");
-    svs::RouteArgs ra = route_args(delta, g, total, n_bits, bit_offset, flags, false);
-    ra.keyed = o.order != nullptr;
-    ra.readback = (flags & SVS_READBACK) != 0;
-    ra.coeffs = o.coeffs;   // the select calls: n_ac == coeffs->count
-    ra.dithered = o.dither != nullptr;
-    const svs::EmbedPlan p = svs::plan_embed(ra);
+    const svs::EmbedPlan p = svs::plan_embed(o.route(delta, g, total, n_bits, bit_offset, flags));
     if (p.use > 0) {
         if (!d_bits_packed) return fail(SVS_ERR_INVALID_ARG, "bits pointer is NULL");
         if ((uintptr_t)d_bits_packed % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
@@ -868,96 +892,55 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
     return SVS_OK;
 }
 
-// every gray device extract call
-int extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, int n_ac, uint8_t *d_bits_packed_out,
-                uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream, const GrayOptions &o) {
-    svs::Geometry g;
-    uint64_t total = 0, cap = 0;
-    if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
+// What every gray extract call checks before any device work, in this order, for the output `o.out` describes; the host forms
+// (device = false) leave the alignment to their staged buffers.  -> *bytes of output; *cap = 0: an empty call, whose pointers and
+// bounds were not looked at.  A tally or a histogram: nothing is written before the last check has passed.
+int extract_checks(const void *gray, const void *out, bool device, const svs_planes *planes, double delta, int n_ac,
+                   uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, const GrayOptions &o, svs::Geometry *g,
+                   uint64_t *total, uint64_t *cap, uint64_t *bytes) {
+    const ExtractOutput &w = o.out;
+    if (w.adds()) n_bits_out = nullptr;
+    if (int rc = extract_geometry(planes, n_ac, g, total, cap, n_bits_out)) return rc;
     if (int rc = check_order(o.order)) return rc;
     if (int rc = check_extract_flags(flags)) return rc;
-    if (cap == 0) return SVS_OK;
-    if (!d_gray || !d_bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
-    if ((uintptr_t)d_gray % 8) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
-    if ((uintptr_t)d_bits_packed_out % 4) return fail(SVS_ERR_INVALID_ARG, "bits pointer must be 4-byte aligned");
-    const uint64_t bytes = o.soft ? cap : (cap + 7) / 8;   // a soft call: one byte per capacity bit
-    if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
-    svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
-    ra.keyed = o.order != nullptr;
-    ra.coeffs = o.coeffs;   // the select calls: n_ac == coeffs->count
-    ra.dithered = o.dither != nullptr;
-    ra.soft = o.soft;
-    const svs::ExtractPlan p = svs::plan_extract(ra);
-    // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
-    if (p.path != ExtractPath::ZEROS && (flags & ~kModeFlags)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
-    if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_bits_packed_out, bytes, o.kernel_forms(g))) return rc;
-    if (n_bits_out) *n_bits_out = cap;
-    return SVS_OK;
-}
-
-// What the two vote calls check, in the order of the soft extract calls with the vote's own arguments where the output's stood;
-// nothing is written before the last check has passed (*n_bits_out and the tally are untouched by a refusal).  *cap = 0: an
-// empty call, nothing else was looked at.
-int vote_checks(const void *gray, const svs_planes *planes, double delta, int n_ac, uint64_t period, const void *tally, bool device,
-                uint32_t flags, const GrayOptions &o, svs::Geometry *g, uint64_t *total, uint64_t *cap) {
-    if (int rc = make_geometry(planes, n_ac, g, total)) return rc;
-    *cap = *total * (uint64_t)g->n_ac;
-    if (int rc = check_order(o.order)) return rc;
-    if (int rc = check_extract_flags(flags)) return rc;
-    if (period == 0) return fail(SVS_ERR_INVALID_ARG, "period is 0");
-    if (period > svs::kVotePeriodMax) return fail(SVS_ERR_INVALID_ARG, "period %llu exceeds 2^61 - 1", (unsigned long long)period);
-    if (!(delta > 0.0)) return fail(SVS_ERR_INVALID_ARG, "a vote needs delta > 0 (every soft byte is 0 otherwise)");
+    if (w.kind == ExtractOutput::VOTE) {
+        if (w.period == 0) return fail(SVS_ERR_INVALID_ARG, "period is 0");
+        if (w.period > svs::kVotePeriodMax) return fail(SVS_ERR_INVALID_ARG, "period %llu exceeds 2^61 - 1", (unsigned long long)w.period);
+    }
+    if (w.adds() && !(delta > 0.0))
+        return fail(SVS_ERR_INVALID_ARG, "a %s needs delta > 0 (every soft byte is 0 otherwise)", w.call());
+    *bytes = w.bytes(*cap, planes->n_frames);
     if (*cap == 0) return SVS_OK;
-    if (!gray || !tally) return fail(SVS_ERR_INVALID_ARG, "gray/tally pointer is NULL");
+    if (!gray || !out) return fail(SVS_ERR_INVALID_ARG, "gray/%s pointer is NULL", w.noun());
     if (device && ((uintptr_t)gray % 8)) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
-    if (device && ((uintptr_t)tally % 4)) return fail(SVS_ERR_INVALID_ARG, "tally pointer must be 4-byte aligned");
-    if (period < (1ull << (64 - svs::kVoteCopiesShift)) && *cap > (period << svs::kVoteCopiesShift))
+    if (device && ((uintptr_t)out % 4)) return fail(SVS_ERR_INVALID_ARG, "%s pointer must be 4-byte aligned", w.noun());
+    if (!w.adds()) return check_capacity(*bytes, out_capacity_bytes, "bytes");
+    // no capacity argument: the caller sized the output by the call's own arguments; what is bounded is one entry's growth
+    if (w.kind == ExtractOutput::VOTE && w.period < (1ull << (64 - svs::kVoteCopiesShift)) && *cap > (w.period << svs::kVoteCopiesShift))
         return fail(SVS_ERR_INVALID_ARG, "capacity %llu exceeds period * 2^22: an int32 tally entry could overflow in one call",
                     (unsigned long long)*cap);
-    return SVS_OK;
-}
-
-// the launch of a vote call whose arguments have passed vote_checks (cap != 0)
-int vote_launch(const uint8_t *d_gray, const svs::Geometry &g, uint64_t total, double delta, uint64_t period, uint64_t stream_bit0,
-                int32_t *d_tally, uint32_t flags, hipStream_t st, GrayOptions o) {
-    svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
-    ra.keyed = o.order != nullptr;
-    ra.coeffs = o.coeffs;
-    ra.dithered = o.dither != nullptr;
-    ra.vote = true;
-    o.vote_period = period;
-    o.vote_bit0 = stream_bit0;
-    return launch_extract(svs::plan_extract(ra), total, st, d_gray, g, reinterpret_cast<uint8_t *>(d_tally), 4u * period, o.kernel_forms(g));
-}
-
-// What the two histogram calls check, in the order of the vote calls with the counts where the tally stood; nothing is written
-// before the last check has passed (*n_bits_out and the counts are untouched by a refusal).  *cap = 0: an empty call.
-int hist_checks(const void *gray, const svs_planes *planes, double delta, int n_ac, const void *hist, bool device, uint32_t flags,
-                svs::Geometry *g, uint64_t *total, uint64_t *cap) {
-    if (int rc = make_geometry(planes, n_ac, g, total)) return rc;
-    *cap = *total * (uint64_t)g->n_ac;
-    if (int rc = check_extract_flags(flags)) return rc;
-    if (!(delta > 0.0)) return fail(SVS_ERR_INVALID_ARG, "a histogram needs delta > 0 (every soft byte is 0 otherwise)");
-    if (*cap == 0) return SVS_OK;
-    if (!gray || !hist) return fail(SVS_ERR_INVALID_ARG, "gray/hist pointer is NULL");
-    if (device && ((uintptr_t)gray % 8)) return fail(SVS_ERR_INVALID_ARG, "plane pointer must be 8-byte aligned");
-    if (device && ((uintptr_t)hist % 4)) return fail(SVS_ERR_INVALID_ARG, "hist pointer must be 4-byte aligned");
     const uint64_t per_frame = (uint64_t)g->by_bpf.div * g->n_ac;
-    if (per_frame > 0xFFFFFFFFull)
+    if (w.kind == ExtractOutput::HIST && per_frame > 0xFFFFFFFFull)
         return fail(SVS_ERR_INVALID_ARG, "planes hold %llu bytes a frame, above 2^32 - 1: a uint32 hist entry could wrap in one call",
                     (unsigned long long)per_frame);
     return SVS_OK;
 }
 
-// the launch of a histogram call whose arguments have passed hist_checks (cap != 0): d_hist = n_frames rows of 256 uint32
-int hist_launch(const uint8_t *d_gray, const svs::Geometry &g, uint64_t total, double delta, uint32_t n_frames, uint32_t *d_hist,
-                uint32_t flags, hipStream_t st, const GrayOptions &o) {
-    svs::RouteArgs ra = route_args(delta, g, total, 0, 0, flags, false);
-    ra.coeffs = o.coeffs;
-    ra.dithered = o.dither != nullptr;
-    ra.hist = true;
-    return launch_extract(svs::plan_extract(ra), total, st, d_gray, g, reinterpret_cast<uint8_t *>(d_hist),
-                          4ull * svs::kHistBins * n_frames, o.kernel_forms(g));
+// every gray device extract call; d_out: the packed bits, the soft bytes, the tally or the counts (ExtractOutput)
+int extract_dev(const uint8_t *d_gray, const svs_planes *planes, double delta, int n_ac, uint8_t *d_out, uint64_t out_capacity_bytes,
+                uint32_t flags, uint64_t *n_bits_out, void *stream, const GrayOptions &o) {
+    svs::Geometry g;
+    uint64_t total = 0, cap = 0, bytes = 0;
+    if (int rc = extract_checks(d_gray, d_out, true, planes, delta, n_ac, out_capacity_bytes, flags, n_bits_out, o, &g, &total, &cap, &bytes))
+        return rc;
+    if (cap != 0) {
+        const svs::ExtractPlan p = svs::plan_extract(o.route(delta, g, total, 0, 0, flags));
+        // the flags are checked only when there is something to extract: delta <= 0 gives zeros whatever they say
+        if (p.path != ExtractPath::ZEROS && (flags & ~kModeFlags)) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x", flags);
+        if (int rc = launch_extract(p, total, (hipStream_t)stream, d_gray, g, d_out, bytes, o.kernel_forms(g))) return rc;
+    }
+    if (n_bits_out) *n_bits_out = cap;
+    return SVS_OK;
 }
 
 }  // namespace
@@ -1145,24 +1128,26 @@ int svs_extract(const uint8_t *gray, const svs_planes *planes, double delta, int
     return svs_extract_ordered(gray, planes, nullptr, delta, n_ac, bits_packed_out, out_capacity_bytes, flags, n_bits_out);
 }
 
-// every gray host extract call
-static int extract_host(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, uint8_t *bits_packed_out,
-                        uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, const GrayOptions &o) {
+// every gray host extract call: the frames staged whole, in one piece.  A tally or a histogram is added into a zeroed buffer of
+// the staging context and downloaded; an empty call zero-fills the caller's.
+static int extract_host(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, uint8_t *out, uint64_t out_capacity_bytes,
+                        uint32_t flags, uint64_t *n_bits_out, const GrayOptions &o) {
     svs::Geometry g;
-    uint64_t total = 0, cap = 0;
-    if (int rc = extract_geometry(planes, n_ac, &g, &total, &cap, n_bits_out)) return rc;
-    if (int rc = check_order(o.order)) return rc;
-    if (int rc = check_extract_flags(flags)) return rc;
-    if (cap == 0) return SVS_OK;
-    if (!gray || !bits_packed_out) return fail(SVS_ERR_INVALID_ARG, "gray/bits pointer is NULL");
-    const uint64_t bytes = o.soft ? cap : (cap + 7) / 8;
-    if (int rc = check_capacity(bytes, out_capacity_bytes, "bytes")) return rc;
+    uint64_t total = 0, cap = 0, bytes = 0;
+    if (int rc = extract_checks(gray, out, false, planes, delta, n_ac, out_capacity_bytes, flags, n_bits_out, o, &g, &total, &cap, &bytes))
+        return rc;
+    if (cap == 0) {
+        if (o.out.adds() && out) memset(out, 0, bytes);
+        if (n_bits_out) *n_bits_out = 0;
+        return SVS_OK;
+    }
     return extract_staged(
         gray, span_bytes(planes), bytes, 0, n_bits_out,
-        [&](const uint8_t *d_in, uint8_t *d_bits, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
-            return extract_dev(d_in, planes, delta, n_ac, d_bits, d_bytes, flags, got, st, o);
+        [&](const uint8_t *d_in, uint8_t *d_out, uint64_t d_bytes, uint64_t *got, hipStream_t st) {
+            if (o.out.adds()) SVS_HIP(hipMemsetAsync(d_out, 0, bytes, st));
+            return extract_dev(d_in, planes, delta, n_ac, d_out, d_bytes, flags, got, st, o);
         },
-        [&](HostStage &c, hipStream_t st) { return stage_d2h(st, bits_packed_out, c.bits.p, bytes); });
+        [&](HostStage &c, hipStream_t st) { return stage_d2h(st, out, c.bits.p, bytes); });
 }
 
 int svs_extract_ordered(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, double delta, int n_ac,
@@ -1256,13 +1241,15 @@ int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const sv
     });
 }
 
-// The soft calls are the dithered extract calls with each of order, coeffs and dither optional, and one byte per capacity bit
-// for an output (include/svsdct.h): the same checks in the same order, the same staging.
+// The soft calls are the dithered extract calls with each of order, coeffs and dither optional and an output of their own
+// (include/svsdct.h, ExtractOutput): the same checks in the same order, the same staging.  svs_soft_extract*: one byte per
+// capacity bit.  svs_soft_vote*: the kernel's soft side adds each byte's vote into tally[stream position mod period] instead of
+// writing it.  svs_soft_histogram*: no order, and it counts each byte into hist[frame * 256 + byte].
 int svs_soft_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                          const svs_dither *dither, double delta, int n_ac, uint8_t *d_soft_out, uint64_t out_capacity_bytes,
                          uint32_t flags, uint64_t *n_bits_out, void *stream) {
     return with_options(kSoftExtract, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
-        o.soft = true;
+        o.out = {ExtractOutput::SOFT};
         return extract_dev(d_gray, planes, delta, n, d_soft_out, out_capacity_bytes, flags, n_bits_out, stream, o);
     });
 }
@@ -1271,93 +1258,42 @@ int svs_soft_extract(const uint8_t *gray, const svs_planes *planes, const svs_bl
                      const svs_dither *dither, double delta, int n_ac, uint8_t *soft_out, uint64_t out_capacity_bytes, uint32_t flags,
                      uint64_t *n_bits_out) {
     return with_options(kSoftExtract, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
-        o.soft = true;
+        o.out = {ExtractOutput::SOFT};
         return extract_host(gray, planes, delta, n, soft_out, out_capacity_bytes, flags, n_bits_out, o);
     });
 }
 
-// The vote calls are the soft calls with a tally for an output (include/svsdct.h): the kernel's soft side adds each byte's vote
-// into tally[stream position mod period] instead of writing it.  The device form adds into the caller's tally; the host form
-// stages the frames as svs_extract does, votes into a zeroed tally in the staging context and downloads its 4 period bytes.
 int svs_soft_vote_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                       const svs_dither *dither, double delta, int n_ac, uint64_t period, uint64_t stream_bit0, int32_t *d_tally,
                       uint32_t flags, uint64_t *n_bits_out, void *stream) {
-    return with_options(kSoftVote, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
-        svs::Geometry g;
-        uint64_t total = 0, cap = 0;
-        if (int rc = vote_checks(d_gray, planes, delta, n, period, d_tally, true, flags, o, &g, &total, &cap)) return rc;
-        if (cap != 0)
-            if (int rc = vote_launch(d_gray, g, total, delta, period, stream_bit0, d_tally, flags, (hipStream_t)stream, o)) return rc;
-        if (n_bits_out) *n_bits_out = cap;
-        return (int)SVS_OK;
+    return with_options(kSoftVote, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::VOTE, period, stream_bit0};
+        return extract_dev(d_gray, planes, delta, n, reinterpret_cast<uint8_t *>(d_tally), 0, flags, n_bits_out, stream, o);
     });
 }
 
 int svs_soft_vote(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                   const svs_dither *dither, double delta, int n_ac, uint64_t period, uint64_t stream_bit0, int32_t *tally_out,
                   uint32_t flags, uint64_t *n_bits_out) {
-    return with_options(kSoftVote, order, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
-        svs::Geometry g;
-        uint64_t total = 0, cap = 0;
-        if (int rc = vote_checks(gray, planes, delta, n, period, tally_out, false, flags, o, &g, &total, &cap)) return rc;
-        if (cap == 0) {   // nothing votes: the tally of an empty call is all zero
-            if (tally_out) memset(tally_out, 0, 4u * period);
-            if (n_bits_out) *n_bits_out = 0;
-            return (int)SVS_OK;
-        }
-        const uint64_t bytes = 4u * period;
-        return extract_staged(
-            gray, span_bytes(planes), bytes, 0, n_bits_out,
-            [&](const uint8_t *d_in, uint8_t *d_tally, uint64_t, uint64_t *got, hipStream_t st) {
-                SVS_HIP(hipMemsetAsync(d_tally, 0, bytes, st));
-                if (int rc = vote_launch(d_in, g, total, delta, period, stream_bit0, reinterpret_cast<int32_t *>(d_tally), flags, st, o))
-                    return rc;
-                *got = cap;
-                return (int)SVS_OK;
-            },
-            [&](HostStage &c, hipStream_t st) { return stage_d2h(st, tally_out, c.bits.p, bytes); });
+    return with_options(kSoftVote, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::VOTE, period, stream_bit0};
+        return extract_host(gray, planes, delta, n, reinterpret_cast<uint8_t *>(tally_out), 0, flags, n_bits_out, o);
     });
 }
 
-// The histogram calls are the soft calls without an order and with 256 counts a frame for an output (include/svsdct.h): the
-// kernel's soft side counts each byte into hist[frame * 256 + byte] instead of writing it.  The device form adds into the
-// caller's counts; the host form stages the frames as svs_extract does (whole frames, one piece), counts into zeroed rows in the
-// staging context and downloads their 1024 n_frames bytes.
 int svs_soft_histogram_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
                            double delta, int n_ac, uint32_t *d_hist, uint32_t flags, uint64_t *n_bits_out, void *stream) {
-    return with_options(kSoftHistogram, nullptr, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
-        svs::Geometry g;
-        uint64_t total = 0, cap = 0;
-        if (int rc = hist_checks(d_gray, planes, delta, n, d_hist, true, flags, &g, &total, &cap)) return rc;
-        if (cap != 0)
-            if (int rc = hist_launch(d_gray, g, total, delta, (uint32_t)planes->n_frames, d_hist, flags, (hipStream_t)stream, o)) return rc;
-        if (n_bits_out) *n_bits_out = cap;
-        return (int)SVS_OK;
+    return with_options(kSoftHistogram, nullptr, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::HIST};
+        return extract_dev(d_gray, planes, delta, n, reinterpret_cast<uint8_t *>(d_hist), 0, flags, n_bits_out, stream, o);
     });
 }
 
 int svs_soft_histogram(const uint8_t *gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
                        double delta, int n_ac, uint32_t *hist_out, uint32_t flags, uint64_t *n_bits_out) {
-    return with_options(kSoftHistogram, nullptr, coeffs, dither, flags, n_ac, [&](int n, const GrayOptions &o) {
-        svs::Geometry g;
-        uint64_t total = 0, cap = 0;
-        if (int rc = hist_checks(gray, planes, delta, n, hist_out, false, flags, &g, &total, &cap)) return rc;
-        const uint64_t bytes = 4ull * svs::kHistBins * (uint64_t)planes->n_frames;
-        if (cap == 0) {   // nothing is counted: the rows of an empty call are all zero
-            if (hist_out) memset(hist_out, 0, bytes);
-            if (n_bits_out) *n_bits_out = 0;
-            return (int)SVS_OK;
-        }
-        return extract_staged(
-            gray, span_bytes(planes), bytes, 0, n_bits_out,
-            [&](const uint8_t *d_in, uint8_t *d_hist, uint64_t, uint64_t *got, hipStream_t st) {
-                SVS_HIP(hipMemsetAsync(d_hist, 0, bytes, st));
-                if (int rc = hist_launch(d_in, g, total, delta, (uint32_t)planes->n_frames, reinterpret_cast<uint32_t *>(d_hist), flags, st, o))
-                    return rc;
-                *got = cap;
-                return (int)SVS_OK;
-            },
-            [&](HostStage &c, hipStream_t st) { return stage_d2h(st, hist_out, c.bits.p, bytes); });
+    return with_options(kSoftHistogram, nullptr, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::HIST};
+        return extract_host(gray, planes, delta, n, reinterpret_cast<uint8_t *>(hist_out), 0, flags, n_bits_out, o);
     });
 }
 

@@ -319,12 +319,25 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     return out[: (n + 7) // 8], n
 
 
-def _soft_call(lib, call: _GrayCall, front, delta, n_ac, back, stream=()) -> None:
-    """svs_soft_extract(*front, order, coeffs, dither, delta, n_ac, *back), or with stream = (handle,) its _dev form: the one
-    soft entry point takes each of the three structs or NULL, so every stem of _resolve makes the same call"""
-    name = "svs_soft_extract" + ("_dev" if stream else "")
-    native.check(getattr(lib, name)(*front, _ref(call.order), _ref(call.sel), _ref(call.dith), float(delta), int(n_ac), *back,
-                                    *stream), name)
+# svs_soft_<name>[_dev] -> (takes an order, its arguments between n_ac and flags)
+_SOFT_CALLS = {
+    "extract": (True, ("out", "out_capacity_bytes")),
+    "vote": (True, ("period", "stream_bit0", "tally")),
+    "histogram": (False, ("hist",)),
+}
+
+
+def _soft_call(lib, name, call: _GrayCall, front, delta, n_ac, middle, flags, stream=()) -> int:
+    """svs_soft_<name>(*front, [order], coeffs, dither, delta, n_ac, *middle, flags, n_bits_out), or with stream = (handle,) its
+    _dev form; -> n_bits_out.  A soft entry point takes each of its structs or NULL, so every stem of _resolve makes the same
+    call; raises unless it returns SVS_OK"""
+    takes_order, names = _SOFT_CALLS[name]
+    assert len(middle) == len(names), names
+    symbol = f"svs_soft_{name}" + ("_dev" if stream else "")
+    got = C.c_uint64(0)
+    native.check(getattr(lib, symbol)(*front, *([_ref(call.order)] if takes_order else ()), _ref(call.sel), _ref(call.dith),
+                                      float(delta), int(n_ac), *middle, flags, C.byref(got), *stream), symbol)
+    return int(got.value)
 
 
 def extract_soft_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
@@ -341,10 +354,8 @@ def extract_soft_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: 
     f, h, w = stack.shape
     cap = capacity_bits(f, h, w, n_ac)
     out = pinned_empty(max(4, cap))
-    got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    _soft_call(lib, call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [out.ctypes.data, cap, mode_flags(mode), C.byref(got)])
-    n = int(got.value)
+    n = _soft_call(lib, "extract", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [out.ctypes.data, cap], mode_flags(mode))
     return out[:n], n
 
 
@@ -353,14 +364,6 @@ def _period(period) -> int:
     if not 1 <= period < 1 << 61:
         raise ValueError(f"period {period} outside 1 .. 2**61 - 1")
     return period
-
-
-def _vote_call(lib, call: _GrayCall, front, delta, n_ac, period, stream_bit0, tally, flags, got, stream=()) -> None:
-    """svs_soft_vote(*front, order, coeffs, dither, delta, n_ac, period, stream_bit0, tally, flags, n_bits_out), or with
-    stream = (handle,) its _dev form"""
-    name = "svs_soft_vote" + ("_dev" if stream else "")
-    native.check(getattr(lib, name)(*front, _ref(call.order), _ref(call.sel), _ref(call.dith), float(delta), int(n_ac), int(period),
-                                    int(stream_bit0), tally, flags, C.byref(got), *stream), name)
 
 
 def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: int = 0, device: int = 0, mode: str | None = None,
@@ -378,18 +381,10 @@ def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: in
     stack = _as_stack(frames)
     f, h, w = stack.shape
     tally = pinned_empty(4 * period).view(np.int32)
-    got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    _vote_call(lib, call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, period, stream_bit0, tally.ctypes.data, mode_flags(mode),
-               got)
+    _soft_call(lib, "vote", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [period, int(stream_bit0), tally.ctypes.data],
+               mode_flags(mode))
     return _soft.tally_bits(tally), tally
-
-
-def _histogram_call(lib, call: _GrayCall, front, delta, n_ac, hist, flags, got, stream=()) -> None:
-    """svs_soft_histogram(*front, coeffs, dither, delta, n_ac, hist, flags, n_bits_out), or with stream = (handle,) its _dev form"""
-    name = "svs_soft_histogram" + ("_dev" if stream else "")
-    native.check(getattr(lib, name)(*front, _ref(call.sel), _ref(call.dith), float(delta), int(n_ac), hist, flags, C.byref(got),
-                                    *stream), name)
 
 
 def extract_histogram_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, first_frame=None,
@@ -407,10 +402,8 @@ def extract_histogram_frames(frames: np.ndarray, delta, n_ac, device: int = 0, m
     stack = _as_stack(frames)
     f, h, w = stack.shape
     hist = pinned_empty(max(4, 1024 * f))[: 1024 * f].view(np.uint32).reshape(f, 256)
-    got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    _histogram_call(lib, call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, hist.ctypes.data, mode_flags(mode), got)
-    return hist, int(got.value)
+    return hist, _soft_call(lib, "histogram", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [hist.ctypes.data], mode_flags(mode))
 
 
 def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | None = None, **embed_kw):
@@ -541,11 +534,9 @@ def extract_soft_device(d_gray: int, planes: Planes, delta, n_ac, d_soft_out: in
     """Enqueue the soft-decision extraction on `stream` (svs_soft_extract_dev): one byte per capacity bit into d_soft_out
     (4-byte aligned, at least the capacity in bytes); returns the number of bytes the batch yields.  order, coeffs, dither_key,
     first_frame: as extract_device."""
-    got = C.c_uint64(0)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
-    _soft_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac,
-               [d_soft_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)], (stream or None,))
-    return int(got.value)
+    return _soft_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac, [d_soft_out, int(out_capacity_bytes)],
+                      mode_flags(mode), (stream or None,))
 
 
 def extract_vote_device(d_gray: int, planes: Planes, delta, n_ac, d_tally: int, period, stream_bit0: int = 0, stream: int = 0,
@@ -554,11 +545,9 @@ def extract_vote_device(d_gray: int, planes: Planes, delta, n_ac, d_tally: int, 
     values in device memory (4-byte aligned) that the caller zeroes before the first batch; stream_bit0 is the capacity of the
     frames before the batch.  Returns the number of bits that voted.  order, coeffs, dither_key, first_frame: as
     extract_soft_device."""
-    got = C.c_uint64(0)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
-    _vote_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac, _period(period), stream_bit0, d_tally, 0, got,
-               (stream or None,))
-    return int(got.value)
+    return _soft_call(native.load(), "vote", call, [d_gray, C.byref(planes)], delta, n_ac, [_period(period), int(stream_bit0), d_tally],
+                      0, (stream or None,))
 
 
 def extract_histogram_device(d_gray: int, planes: Planes, delta, n_ac, d_hist: int, stream: int = 0, first_frame: int | None = None,
@@ -568,10 +557,8 @@ def extract_histogram_device(d_gray: int, planes: Planes, delta, n_ac, d_hist: i
     read in batches passes d_hist + 1024 * (frames before the batch) and, under a dither, first_frame advanced by as many.
     Returns the number of bytes counted.  No order and no block_key: a frame's counts do not depend on one (see
     extract_histogram_frames).  coeffs, dither_key, first_frame: as extract_soft_device."""
-    got = C.c_uint64(0)
     call = _resolve(n_ac, None, None, first_frame, coeffs, dither_key)
-    _histogram_call(native.load(), call, [d_gray, C.byref(planes)], delta, n_ac, d_hist, 0, got, (stream or None,))
-    return int(got.value)
+    return _soft_call(native.load(), "histogram", call, [d_gray, C.byref(planes)], delta, n_ac, [d_hist], 0, (stream or None,))
 
 
 # ---- fused colour path (BGR in, BGR out; SURVEY 8(f) rank 2) ---------------------------------

@@ -10,7 +10,9 @@ faults, of svs_last_error() texts and of the values the out parameters hold afte
 A number or null is passed as it is (pointers are fake addresses: no case gets as far as reading one); what the library does
 read is built: planes, order, dither ([key, first_frame, reserved]), coeffs ([count, index...]) and counts as structs by
 reference, {"u32s": [..]} as an array of uint32 (colour weights), ascii as a character payload, n_embedded and n_bits_out as
-uint64 out parameters pre-set to the value."""
+uint64 out parameters pre-set to the value, {"filled": [n, byte]} as a real array of n bytes pre-set to `byte` that the call
+may write (the tally and the counts of the host soft calls); its contents after the call are recorded among the outs, as
+"<n>x<byte>" while all its bytes are equal and in hex otherwise."""
 import ctypes as C
 
 from svsdct import native
@@ -68,6 +70,9 @@ def _build(arg):
     elif kind == "u64":
         obj = C.c_uint64(v)
         return C.byref(obj), obj, True
+    elif kind == "filled":
+        obj = (C.c_uint8 * v[0])(*([v[1]] * v[0]))
+        return C.cast(obj, C.c_void_p), obj, True
     elif kind == "counts":
         obj = native.ReadbackCounts(*v)
         return C.byref(obj), obj, True
@@ -76,10 +81,18 @@ def _build(arg):
     return C.byref(obj), obj, False
 
 
+def _read_out(o):
+    if isinstance(o, native.ReadbackCounts):
+        return [int(o.repaired), int(o.unrepaired)]
+    if isinstance(o, C.Array):
+        b = bytes(o)
+        return f"{len(b)}x{b[0]:02x}" if b == b[:1] * len(b) else b.hex()
+    return int(o.value)
+
+
 def run_case(lib, symbol, args):
     """-> (return code, svs_last_error() text ("" for SVS_OK), the out parameters' values after the call)"""
     built = [_build(a) for a in args]
     rc = getattr(lib, symbol)(*[b[0] for b in built])
-    outs = [[int(o.repaired), int(o.unrepaired)] if isinstance(o, native.ReadbackCounts) else int(o.value)
-            for _, o, is_out in built if is_out]
+    outs = [_read_out(o) for _, o, is_out in built if is_out]
     return rc, "" if rc == native.SVS_OK else lib.svs_last_error().decode("utf-8"), outs

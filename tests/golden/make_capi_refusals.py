@@ -1,13 +1,17 @@
-"""Writes tests/golden/capi_refusals.json: what every svs_embed* / svs_extract* entry point of the C ABI answers to arguments it
+"""Writes tests/golden/capi_refusals.json: what every svs_embed* / svs_extract* / svs_soft_* entry point of the C ABI answers to arguments it
 refuses - the return code, the full svs_last_error() text and what it left in its out parameters (pre-set to a sentinel) -
 and to the empty call (n_frames = 0) it accepts.  tests/test_capi_refusals_cpu.py replays the table against the tree's
 library, so the table pins order of checks, status codes and messages of the build that wrote it: it is written from the
 build BEFORE a change to csrc/svs_capi.hip that must leave them alone
     SVSDCT_LIB=<that build>/lib/libsvsdct.so python tests/golden/make_capi_refusals.py
-and is left alone by that change.  (Committed with the refactor to one options value per gray call, from its parent's build.)
+and is left alone by that change.  (Committed with the refactor to one options value per gray call, from its parent's build;
+the svs_soft_* symbols were added, again from the parent's build, ahead of the refactor to one description of a soft call's
+output.  The earlier symbols come first, so their entries and every index they use stay as they were.)
 
 Every argument check of these calls runs before any device work, so the library answers without a GPU, and no case may
-reach the device: pointers are fake aligned addresses, and a table in which a case returns SVS_ERR_HIP, or SVS_OK for a batch
+reach the device: pointers are fake aligned addresses - but for the tally and the counts of the host vote and histogram
+calls, which an empty call zero-fills: those are real arrays pre-set to a sentinel byte, and their contents after the call are
+part of the recorded outs (a refusal leaves them untouched) - and a table in which a case returns SVS_ERR_HIP, or SVS_OK for a batch
 that is not empty, is not written.
 
 Per symbol: a call that would be accepted (never made; the table's "good" values), every fault the symbol checks before its device work applied to it
@@ -34,6 +38,7 @@ KEY = 0x0123456789ABCDEF
 
 _E, _X = "gray stego planes", "gray planes"
 _PAY, _OUT = "bits bit_offset n_bits flags n_embedded", "out cap flags n_bits_out"
+_VOTE = "period stream_bit0 tally flags n_bits_out"
 _BGR = "bgr_in in_rp in_fp bgr_out out_rp out_fp gray_ref planes weights delta n_ac " + _PAY
 PARAMS = {name: names.split() for name, names in {
     "svs_embed_dev": f"{_E} delta n_ac {_PAY} stream",
@@ -64,6 +69,12 @@ PARAMS = {name: names.split() for name, names in {
     "svs_extract_bgr": "bgr_in planes weights delta n_ac out cap n_bits_out",
     "svs_embed_bgr_readback_dev": f"{_BGR} d_counts stream",
     "svs_embed_bgr_readback": "bgr_in bgr_out gray_ref planes weights delta n_ac " + _PAY + " counts",
+    "svs_soft_extract_dev": f"{_X} order coeffs dither delta n_ac {_OUT} stream",
+    "svs_soft_extract": f"{_X} order coeffs dither delta n_ac {_OUT}",
+    "svs_soft_vote_dev": f"{_X} order coeffs dither delta n_ac {_VOTE} stream",
+    "svs_soft_vote": f"{_X} order coeffs dither delta n_ac {_VOTE}",
+    "svs_soft_histogram_dev": f"{_X} coeffs dither delta n_ac hist flags n_bits_out stream",
+    "svs_soft_histogram": f"{_X} coeffs dither delta n_ac hist flags n_bits_out",
 }.items()}
 
 # 3 frames of 16 x 24: 18 blocks, 54 bits at n_ac = 3 (7 bytes)
@@ -72,13 +83,22 @@ GOOD = {"gray": 0x10000, "stego": 0x20000, "gray_ref": None, "planes": [3, 16, 2
         "order": [9, 5, 0], "coeffs": [3, 9, 2, 17], "dither": [KEY, 5, 0], "d_counts": 0x40000, "counts": [SENTINEL, SENTINEL - 1],
         "out": 0x60000, "cap": 64, "n_bits_out": SENTINEL, "ascii": "01" * 50, "bgr_in": 0x70000, "bgr_out": 0x80000,
         "in_rp": 72, "in_fp": 1152, "out_rp": 72, "out_fp": 1152, "weights": None}
+# the soft calls' own good values (kept out of GOOD, whose line of the table stays as it was): the device forms take fake
+# addresses, the host forms real arrays of the output's size, 4 * period and 1024 * n_frames bytes of 0xA5
+SOFT_GOOD = {"period": 10, "stream_bit0": 5, "tally": 0x90000, "hist": 0xA0000}
+SOFT_HOST = {"tally": {"filled": [40, 0xA5]}, "hist": {"filled": [3072, 0xA5]}}
+# the selection of GOOD rules (3 bits a block).  1401856 blocks: 3 bits each are above 1 * 2^22;  1500012900 blocks a frame
+# (below 2^31): 3 bytes each are above 2^32 - 1
+VOTE_BOUND = {"planes": [1, 9472, 9472, 0, 9472, 9472 * 9472], "period": 1}
+HIST_BOUND = {"planes": [1, 309840, 309840, 0, 309840, 309840 * 309840]}
 FLAG_BITS = (0x4, native.SVS_KEEP_COLOUR, native.SVS_READBACK, 0x400, native.SVS_NEAREST, native.SVS_MINMOVE, 0x80000000)
 EMBED_ONLY = native.SVS_READBACK | native.SVS_NEAREST | native.SVS_MINMOVE
 MODES = native.SVS_EXACT_POCKETFFT | native.SVS_EXACT_GUARDED
 
 
 def traits(sym):
-    t = {"dev": sym.endswith("_dev"), "extract": "extract" in sym, "bgr": "_bgr" in sym, "str": sym.endswith("_str"),
+    t = {"dev": sym.endswith("_dev"), "extract": "extract" in sym or "_soft_" in sym, "soft": "_soft_" in sym,
+         "vote": "_vote" in sym, "hist": "_histogram" in sym, "bgr": "_bgr" in sym, "str": sym.endswith("_str"),
          "select": "_select" in sym, "dithered": "_dithered" in sym, "readback": "_readback" in sym}
     t["host"] = not t["dev"]
     return t
@@ -90,7 +110,7 @@ def refused_flag_bits(sym):
     if "flags" not in PARAMS[sym]:
         return ()
     if t["extract"]:
-        if t["select"] or t["dithered"] or t["dev"]:
+        if t["select"] or t["dithered"] or t["soft"] or t["dev"]:
             return FLAG_BITS                                        # the preamble's mask, or svs_extract_dev's own
         return tuple(b for b in FLAG_BITS if b & EMBED_ONLY)         # the host calls leave unknown bits to the device call
     allowed = MODES | native.SVS_NEAREST | native.SVS_MINMOVE
@@ -124,18 +144,25 @@ def faults(sym):
                 ("coeffs.index repeated", "coeffs", {"coeffs": [3, 9, 2, 9]}),
                 ("coeffs.index DC", "coeffs", {"coeffs": [3, 9, 0, 17]})]
     if has("dither"):
-        if not t["readback"]:
+        if not (t["readback"] or t["soft"]):
             out.append(("dither NULL", "dither", {"dither": None}))
-        out += [("dither.reserved", "dither", {"dither.2": 1}), ("dither.first_frame differs", "dither.first_frame", {"dither.1": 6})]
+        out.append(("dither.reserved", "dither", {"dither.2": 1}))
+        if has("order"):
+            out.append(("dither.first_frame differs", "dither.first_frame", {"dither.1": 6}))
     for bit in refused_flag_bits(sym):
-        kind = "embed flag" if t["extract"] and bit & EMBED_ONLY and not (t["select"] or t["dithered"]) else "flag"
+        kind = "embed flag" if t["extract"] and bit & EMBED_ONLY and not (t["select"] or t["dithered"] or t["soft"]) else "flag"
         out.append((f"flag 0x{bit:x}", kind, {"flags": GOOD["flags"] | bit}))
     first, second = ("bgr_in", "bgr_out") if t["bgr"] else ("gray", "stego")
-    second = "out" if t["extract"] else second
+    second = "tally" if t["vote"] else "hist" if t["hist"] else "out" if t["extract"] else second
+    good = {**GOOD, **SOFT_GOOD}
+    if t["vote"]:
+        out += [("period 0", "period", {"period": 0}), ("period 2^61", "period", {"period": 1 << 61})]
+    if t["vote"] or t["hist"]:
+        out += [("delta 0", "delta", {"delta": 0.0}), ("delta negative", "delta", {"delta": -8.0})]
     out += [(f"{first} NULL", f"{first} NULL", {first: None}), (f"{second} NULL", f"{second} NULL", {second: None})]
     if t["dev"]:
-        out += [(f"{first} misaligned", f"{first} aligned", {first: GOOD[first] + 4}),
-                (f"{second} misaligned", f"{second} aligned", {second: GOOD[second] + 2})]
+        out += [(f"{first} misaligned", f"{first} aligned", {first: good[first] + 4}),
+                (f"{second} misaligned", f"{second} aligned", {second: good[second] + 2})]
     if t["bgr"] and t["dev"]:
         out += [("BGR row pitch short", "in pitches", {"in_rp": 64}), ("BGR frame pitch % 8", "in pitches", {"in_fp": 1156}),
                 ("weights do not sum to 2^shift", "weights", {"weights": {"u32s": [1, 1, 1, 15]}}),
@@ -158,6 +185,10 @@ def faults(sym):
                         ("payload too large", "too large", {"bit_offset": 1 << 37})]
         if has("d_counts"):
             out.append(("counts misaligned", "counts aligned", {"d_counts": GOOD["d_counts"] + 4}))
+    elif t["vote"]:
+        out.append(("capacity above period * 2^22", "bound", VOTE_BOUND))
+    elif t["hist"]:
+        out.append(("a frame above 2^32 - 1 bytes", "bound", HIST_BOUND))
     else:
         out.append(("capacity", "capacity", {"cap": 3}))
     return out
@@ -191,6 +222,7 @@ def cases_of(sym):
 def main():
     lib = native.load()
     symbols = [s for s in native.SIGNATURES if s.startswith(("svs_embed", "svs_extract"))]
+    symbols += [s for s in native.SIGNATURES if s.startswith("svs_soft")]   # behind the others: their indices stay
     assert sorted(symbols) == sorted(PARAMS), sorted(set(symbols) ^ set(PARAMS))
     messages, outs_seen, fault_ids, table, n = {}, {}, {}, {}, 0
 
@@ -203,6 +235,8 @@ def main():
     for sym in symbols:
         assert len(PARAMS[sym]) == len(native.SIGNATURES[sym][1]), sym
         own = {"gray_ref": 0x50000} if traits(sym)["bgr"] and not traits(sym)["extract"] else {}
+        if traits(sym)["soft"]:
+            own = {k: v for k, v in {**SOFT_GOOD, **(SOFT_HOST if traits(sym)["host"] else {})}.items() if k in PARAMS[sym]}
         singles, pairs = cases_of(sym)
         table[sym] = {"parameters": PARAMS[sym], "good": own,
                       "cases": [[fault_ids.setdefault(json.dumps([name, ch]), len(fault_ids))] + record(sym, own, name, ch)

@@ -14,6 +14,9 @@ enum EmuVariant {
     EMU_GENERIC_GUARDED2 = 3,     // the two-row guard through its generic instantiation <QM, 0, false>
 };
 
+// what an extract call writes, named as csrc/svs_capi.hip names it (ExtractOutput::Kind)
+enum EmuOutput { EMU_BITS = 0, EMU_SOFT = 1, EMU_VOTE = 2, EMU_HIST = 3 };
+
 struct EmuCall {
     uint64_t size;                // sizeof(EmuCall)
     // frames: contiguous [F][H][W].  embed: in -> out; extract: in; read-back: out, in place
@@ -28,7 +31,7 @@ struct EmuCall {
     const uint8_t *bits;          // payload, packed MSB-first, padded by the caller to a multiple of 4 bytes
     uint64_t bits_bytes, bit_offset, n_bits;
     int32_t nearest, minmove;     // SVS_NEAREST / SVS_MINMOVE
-    int32_t dither, order;        // a keyed dither / a keyed block order (read-back only: the other walkers refuse it) is on
+    int32_t dither, order;        // a keyed dither / a keyed block order (read-back and the soft extracts: the others refuse it) is on
     uint64_t dither_key, order_key;
     uint32_t first_frame;         // frame f of the call is clip frame first_frame + f, for the dither and the order alike
     float guard_scale, tie_scale; // RouteArgs::guard_scale / tie_scale: the experiments library's SVS_GUARD_SCALE / SVS_TIE_SCALE
@@ -38,11 +41,17 @@ struct EmuCall {
     int32_t variant;              // EmuVariant
     int32_t extract_wave;         // 0: FAST extraction settles per block; 64: per wave of 64 blocks, as the kernels' ballot does
     int32_t keyed_form;           // read-back: readback_step_keyed (svs_embed_dithered_readback*) instead of readback_step<rows>
+    int32_t output;               // extract: EmuOutput
+    uint64_t vote_period, vote_bit0;   // EMU_VOTE: the payload's length in bits, the call's first stream position
     // optional outputs, one byte per block of the call in raster order over the batch; the caller zeroes them
     uint8_t *replay_map;          // embed: 1 = the streaming guard handed the block to the exact replay
     uint8_t *candidate_map;       // extract, wave mode: 1 = a candidate of step one
     uint8_t *status;              // read-back: 0 reads back, 1 repaired, 2 left unrepaired, 3 carries no payload
     uint8_t *bits_out;            // extract: one byte (0 / 1) per bit, n bits per block
+    // the outputs of the soft kinds, each optional.  frames_in NULL: no walk at all - the result holds the call's plan
+    uint8_t *soft_out;            // EMU_SOFT: one byte per capacity bit, in stream order
+    int32_t *tally;               // EMU_VOTE: vote_period values, added to
+    uint32_t *hist;               // EMU_HIST: F * 256 values, added to
 };
 
 struct EmuResult {
@@ -53,4 +62,5 @@ struct EmuResult {
     // the plan of the call (svs::EmbedPlan / svs::ExtractPlan)
     int32_t path, rows, qm, selected, dithered, nearest, minmove;
     uint32_t word;                // rule_word(nearest, minmove, half_cell): what the launchers put into Geometry::pad
+    int32_t soft, vote, hist, keyed;   // extract
 };

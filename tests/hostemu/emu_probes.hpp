@@ -280,4 +280,66 @@ uint64_t kc_check(uint32_t first, uint32_t count, uint32_t stride, int radius, c
     return pairs;
 }
 
+// ---- the soft side's launch arguments and the integer side of its vote and histogram tails (csrc/svs_block.hpp, svs_index.hpp) ----
+
+// the SoftArgs an extract call's launch passes (svs_route.hpp extract_tables, as the launch calls it): -> 0, or -1 when the call
+// is refused.  emu_soft_args: fields[7] = {on, vote, hist, period, base, head, sizeof(SoftArgs)}
+static int soft_args_of(const EmuCall *c, svs::SoftArgs *sa) {
+    Selection s;
+    const Grid g(*c);
+    svs::ExtractPlan p;
+    svs::LaunchTables t;
+    if (c->size != sizeof(EmuCall) || !plan_extract_call(*c, s, g.total, g.bpf, p, t)) return -1;
+    *sa = t.soft;
+    return 0;
+}
+
+int emu_soft_args(const EmuCall *c, uint64_t *fields) {
+    svs::SoftArgs sa;
+    if (soft_args_of(c, &sa)) return -1;
+    const uint64_t v[7] = {sa.on, sa.vote, sa.hist, sa.period, sa.base, sa.head, sizeof(svs::SoftArgs)};
+    std::memcpy(fields, v, sizeof v);
+    return 0;
+}
+
+// c: a vote call.  residues[k] = (vote_bit0 + i[k]) mod vote_period as the kernel takes it (vote_residue: a double-precision
+// quotient with one correction, no 64-bit division), in_head[k] = whether the bit lies in copy 0
+int emu_vote_residues(const EmuCall *c, const uint64_t *i, uint64_t count, uint64_t *residues, uint8_t *in_head) {
+    svs::SoftArgs sa;
+    if (soft_args_of(c, &sa) || !sa.vote) return -1;
+    for (uint64_t k = 0; k < count; ++k) {
+        residues[k] = svs::vote_residue(i[k], sa);
+        in_head[k] = i[k] < sa.head;
+    }
+    return 0;
+}
+
+int32_t emu_vote_of(uint32_t byte, int in_head) { return svs::vote_of(byte, in_head != 0); }
+
+uint64_t emu_vote_period_max(void) { return svs::kVotePeriodMax; }
+
+uint32_t emu_hist_bins(void) { return svs::kHistBins; }
+
+// The per-frame runs of the wave whose first block is wave_first, in a workgroup whose first block is wg_first, of a call of
+// `total` blocks at bpf blocks per frame - the loop of hist_soft_run: for every frame the workgroup touches, the wave's part.
+// out: triples {frame, begin, end} (positions within the wave's run), one per frame of the WORKGROUP, empty parts included;
+// returns their number (at most `room`).
+uint32_t emu_hist_runs(uint32_t wg_first, uint32_t wg_size, uint32_t wave_first, uint32_t total, uint32_t bpf, uint32_t *out,
+                       uint32_t room) {
+    const svs::FastDiv by_bpf = svs::make_div(bpf);
+    const uint32_t wg_blocks = wg_first < total ? (total - wg_first < wg_size ? total - wg_first : wg_size) : 0u;
+    if (wg_blocks == 0u) return 0u;
+    const uint32_t blocks = wave_first < total ? (total - wave_first < 64u ? total - wave_first : 64u) : 0u;
+    const uint32_t f_first = svs::fast_div(wg_first, by_bpf), f_last = svs::fast_div(wg_first + wg_blocks - 1u, by_bpf);
+    uint32_t k = 0;
+    for (uint32_t f = f_first; f <= f_last && k < room; ++f, ++k) {
+        uint32_t begin, end;
+        svs::frame_run(wave_first, blocks, f, bpf, &begin, &end);
+        out[3 * k] = f;
+        out[3 * k + 1] = begin;
+        out[3 * k + 2] = end;
+    }
+    return k;
+}
+
 }  // extern "C"

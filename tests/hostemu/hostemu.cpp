@@ -9,7 +9,7 @@
 //
 // The only translation unit of the host library (emu_call.h: the call and result structs; emu_probes.hpp: the single-purpose
 // entry points).  A gray call is described once (EmuCall) and replayed by one of three walkers - embed_call, extract_call,
-// readback_call -; nothing here keeps state between calls.
+// readback_call -, the soft calls among the extracts; nothing here keeps state between calls.
 // Build: g++ -O2 -ffp-contract=off -std=c++17 -shared -fPIC -I<csrc> hostemu.cpp -o libsvs_hostemu.so
 #include <cmath>
 #include <cstdint>
@@ -91,7 +91,25 @@ svs::RouteArgs route(const EmuCall &c, const Selection &s, uint64_t total) {
     ra.minmove = c.minmove != 0;
     ra.dithered = c.dither != 0;
     if (s.given) ra.coeffs = &s.table;
+    ra.soft = c.output == EMU_SOFT;
+    ra.vote = c.output == EMU_VOTE;
+    ra.hist = c.output == EMU_HIST;
     return ra;
+}
+
+// the options of the call in the kernels' forms, as the library derives them (csrc/svs_capi.hip GrayOptions::kernel_forms)
+svs::KernelOptions kernel_forms(const EmuCall &c, const Selection &s, uint64_t bpf) {
+    return {svs::make_block_order(c.order_key, c.first_frame, (uint32_t)bpf), s.given ? &s.table : nullptr,
+            svs::DitherArgs{svs::dither_seed(c.dither_key), c.first_frame, 1u, svs::CoeffTable{}}, c.vote_period, c.vote_bit0};
+}
+
+// -> false: the walkers refuse the call.  Else the plan of an extract call and what its launch passes (svs_route.hpp)
+bool plan_extract_call(const EmuCall &c, Selection &s, uint64_t total, uint64_t bpf, svs::ExtractPlan &p, svs::LaunchTables &t) {
+    // the hard keyed extract is not modelled; a vote with no period is refused by the library
+    if (!make_selection(c, s) || (c.order && c.output == EMU_BITS) || (c.output == EMU_VOTE && c.vote_period == 0)) return false;
+    p = svs::plan_extract(route(c, s, total));
+    t = svs::extract_tables(p, kernel_forms(c, s, bpf));
+    return true;
 }
 
 bool sizes_match(const EmuCall *c, EmuResult *r) {
@@ -230,16 +248,25 @@ void extract_exact(const Blk &b, uint32_t n, const svs::QimParams &qp, const svs
     else svs::extract_block_exact<8, QM>(b.x, b.y, n, qp, hi, lo);
 }
 
+// The only extract walker.  A soft kind runs the soft side of extract_exact_kernel block by block - extract_block_soft with the
+// tables of the launch - and sends every byte where the kernel's tail of that kind sends it: block b of frame f owns the n
+// stream positions from (f N + slot(b)) n on, slot(b) = b without an order.  The wave tile, the LDS, the pre-reductions and the
+// atomics are NOT modelled here; the -m gpu tests cover them.
 void extract_call(const EmuCall &c, EmuResult &r) {
     Selection s;
-    if (!make_selection(c, s) || c.order) { r.used = ~0ull; return; }
     const Grid g(c);
-    const svs::ExtractPlan p = svs::plan_extract(route(c, s, g.total));
+    svs::ExtractPlan p;
+    svs::LaunchTables t;
+    if (!plan_extract_call(c, s, g.total, g.bpf, p, t)) { r.used = ~0ull; return; }
     r.path = (int32_t)p.path; r.rows = p.rows; r.qm = p.qm; r.selected = p.selected; r.dithered = p.dithered;
+    r.soft = p.soft; r.vote = p.vote; r.hist = p.hist; r.keyed = p.keyed;
     const uint32_t n = s.n;
     r.used = g.total * n;
-    std::memset(c.bits_out, 0, (size_t)r.used);
-    if (n == 0 || p.path == svs::ExtractPath::ZEROS) return;
+    if (!c.frames_in) return;
+    const bool zeros = p.path == svs::ExtractPath::ZEROS;
+    if (!p.soft) std::memset(c.bits_out, 0, (size_t)r.used);
+    else if (zeros && c.output == EMU_SOFT && c.soft_out) std::memset(c.soft_out, 0, (size_t)r.used);   // nothing votes or is counted
+    if (n == 0 || zeros) return;
     const svs::CoeffTable *sel = p.selected ? &s.table : nullptr;
     const bool fast = p.path == svs::ExtractPath::FAST && c.streaming_bodies;
     const uint32_t seed = svs::dither_seed(c.dither_key);
@@ -248,6 +275,24 @@ void extract_call(const EmuCall &c, EmuResult &r) {
     };
     auto walk = [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
+        if (p.soft) {
+            const svs::BlockOrderArgs ord = kernel_forms(c, s, g.bpf).ord;
+            for (uint64_t gb = 0; gb < g.total; ++gb) {
+                const uint64_t f = gb / g.bpf, b = gb % g.bpf;
+                Blk raw;
+                raw.load(g.block(c.frames_in, gb), (size_t)g.W);
+                const uint64_t slot = p.keyed ? svs::block_to_slot((uint32_t)b, ord, svs::round_keys(ord, ord.first_frame + (uint32_t)f)) : b;
+                const uint64_t first = (f * g.bpf + slot) * n;
+                const uint32_t s_b = svs::dither_block_seed(t.dith.seed, t.dith.first_frame + (uint32_t)f, (uint32_t)b);
+                svs::extract_block_soft<QM>(raw.x, raw.y, t.dith.sel, p.qp, t.soft, t.dith.on != 0u, s_b, [&](uint32_t k, uint32_t byte) {
+                    const uint64_t i = first + k;
+                    if (p.vote) { if (c.tally) c.tally[svs::vote_residue(i, t.soft)] += svs::vote_of(byte, i < t.soft.head); }
+                    else if (p.hist) { if (c.hist) c.hist[f * svs::kHistBins + byte] += 1u; }
+                    else if (c.soft_out) c.soft_out[i] = (uint8_t)byte;
+                });
+            }
+            return;
+        }
         if (fast && c.extract_wave > 0) {
             // step two of FAST extraction for EVERY block of an aligned group of blocks in which one block is a candidate, as
             // the kernels do it (one wave ballot; extract_kernel / extract_bgr_kernel).  With the product's margin that gives

@@ -1,18 +1,12 @@
-"""Helpers of the fused soft-histogram tests (tests/test_soft_histogram_cpu.py, tests/test_soft_histogram_gpu.py): the host
-build of the histogram's integer side (tests/soft/hist_emu.cpp - the plan, the launch arguments, the split of a wave's run of
-blocks into per-frame runs), the shapes at which the frame split can go wrong, and the scenario of
+"""Helpers of the fused soft-histogram tests (tests/test_soft_histogram_cpu.py, tests/test_soft_histogram_gpu.py): the
+histogram's integer side through tests/hostemu (the plan, the launch arguments, the split of a wave's run of blocks into
+per-frame runs, a whole call's counts), the shapes at which the frame split can go wrong, and the scenario of
 examples/find_payload_frames.py."""
-import ctypes
-import glob
-import os
-import subprocess
-
 import numpy as np
 
-from testlib import CSRC, REPO
+import soft_lib as sl
+import testlib
 
-_EMU = None
-_PTR = ctypes.c_void_p
 WG = 256                # blocks of a workgroup (csrc/svs_device.hpp SVS_WG)
 
 # name -> (frames, height, width): blocks per frame 1, 1, 6, 6, 120, 64, 256, 257
@@ -20,43 +14,27 @@ SHAPES = {"one_block": (1, 8, 8), "one_block_frames": (70, 8, 8), "tight": (2, 1
           "straddle": (5, 64, 120), "wave_edge": (3, 64, 64), "workgroup_edge": (2, 128, 128), "past_workgroup_edge": (3, 8, 2056)}
 
 
-def hist_emu():
-    """builds (when stale, as soft_lib.soft_emu does) and loads tests/soft/libsvs_hist_emu.so"""
-    global _EMU
-    if _EMU is not None:
-        return _EMU
-    here = os.path.join(REPO, "tests", "soft")
-    src, out = os.path.join(here, "hist_emu.cpp"), os.path.join(here, "libsvs_hist_emu.so")
-    deps = glob.glob(os.path.join(CSRC, "*.hpp")) + [src]
-    stale = not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
-    if stale and os.path.exists(out) and os.path.exists("/dev/kfd"):
-        stale = False      # on a GPU box use the library built by build(): no compiler child processes there
-    if stale:
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src, "-o", out])
-    lib = ctypes.CDLL(out)
-    lib.hist_emu_args.restype = ctypes.c_uint64
-    lib.hist_emu_args.argtypes = [ctypes.c_double, ctypes.c_uint32, ctypes.c_int, _PTR, _PTR]
-    lib.hist_emu_runs.restype = ctypes.c_uint32
-    lib.hist_emu_runs.argtypes = [ctypes.c_uint32] * 5 + [_PTR, ctypes.c_uint32]
-    lib.hist_emu_bins.restype = ctypes.c_uint32
-    lib.hist_emu_bins.argtypes = []
-    _EMU = lib
-    return lib
-
-
 def host_hist_args(delta, n_ac, keyed=False):
     """-> (plan dict, SoftArgs dict, sizeof(SoftArgs)) of a histogram call through svs_route.hpp"""
-    plan, fields = np.zeros(6, np.int32), np.zeros(3, np.uint32)
-    size = hist_emu().hist_emu_args(float(delta), int(n_ac), int(keyed), plan.ctypes.data, fields.ctypes.data)
-    return (dict(zip(("path", "rows", "soft", "vote", "hist", "keyed"), map(int, plan))),
-            dict(zip(("on", "vote", "hist"), map(int, fields))), int(size))
+    plan = sl.host_plan(delta, n_ac, order=keyed, output=testlib.EMU_HIST)
+    args = testlib.host_soft_args((1000, 8, 8), delta, n_ac, block_key=0 if keyed else None, output=testlib.EMU_HIST)
+    return ({k: plan[k] for k in ("path", "rows", "soft", "vote", "hist", "keyed")}, {k: args[k] for k in ("on", "vote", "hist")},
+            args["size"])
 
 
 def host_runs(wg_first, wave_first, total, bpf):
     """-> [(frame, begin, end)] of the wave at wave_first in the workgroup at wg_first, as the kernel's tail walks them"""
     out = np.zeros(3 * (WG + 2), np.uint32)
-    k = hist_emu().hist_emu_runs(int(wg_first), WG, int(wave_first), int(total), int(bpf), out.ctypes.data, WG + 2)
+    k = testlib.hostemu().emu_hist_runs(int(wg_first), WG, int(wave_first), int(total), int(bpf), out.ctypes.data, WG + 2)
     return [tuple(int(v) for v in out[3 * i: 3 * i + 3]) for i in range(k)]
+
+
+def host_hist(frames, delta, n_ac, **call):
+    """a histogram call through the product headers on the host (the extract walker) -> uint32 [F, 256], from zero"""
+    frames = np.ascontiguousarray(frames)
+    hist = np.zeros((frames.shape[0], 256), np.uint32)
+    testlib._emu_call("emu_extract_call", frames, delta, n_ac, frames_in=frames, output=testlib.EMU_HIST, hist=hist, **call)
+    return hist
 
 
 def python_runs(wg_first, wave_first, total, bpf):

@@ -1,17 +1,13 @@
 """Helpers of the soft-extraction tests (tests/test_soft_extract_cpu.py, tests/test_soft_extract_gpu.py): the NumPy model of
 the format (include/svsdct.h) - the oracle's forward transform and quantiser index, the dither of dither_lib, the keyed order of
-svsdct/order.py, and the seven float32 steps of the byte written out -, the host build of the soft block body and of a soft
-call's routing (tests/soft/soft_emu.cpp), and the disturbed three-copy experiment the README's table comes from."""
-import ctypes
-import glob
-import os
-import subprocess
-
+svsdct/order.py, and the seven float32 steps of the byte written out -, the soft block body and a soft call's routing
+through the host build of the product headers (tests/hostemu), and the disturbed three-copy experiment the README's table
+comes from."""
 import numpy as np
 
 import dither_lib as dl
+import testlib
 from oracle.qim_dct_oracle import BLOCK, MAX_AC, _blocks_view, _check_plane, _fwd, _quant_index, frame_embed
-from testlib import CSRC, REPO
 
 ZIGZAG = [1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35,
           42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
@@ -67,64 +63,27 @@ def packed_hard(soft):
     return np.packbits(np.asarray(soft, np.uint8) >> 7)
 
 
-# ---- the soft block body and a soft call's plan on the host (tests/soft/soft_emu.cpp) ---------------------------------------
-_EMU = None
-_PTR = ctypes.c_void_p
+# ---- the soft block body and a soft call's plan on the host (tests/hostemu: the extract walker with a soft output) --------
 PLAN_FIELDS = ("path", "rows", "qm", "selected", "dithered", "soft", "keyed")
 PATH_EXACT = 1          # svs::ExtractPath::EXACT
 
 
-def soft_emu():
-    """builds (when stale, as testlib.hostemu does) and loads tests/soft/libsvs_soft_emu.so"""
-    global _EMU
-    if _EMU is not None:
-        return _EMU
-    here = os.path.join(REPO, "tests", "soft")
-    src, out = os.path.join(here, "soft_emu.cpp"), os.path.join(here, "libsvs_soft_emu.so")
-    deps = glob.glob(os.path.join(CSRC, "*.hpp")) + [src]
-    stale = not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
-    if stale and os.path.exists(out) and os.path.exists("/dev/kfd"):
-        stale = False      # on a GPU box use the library built by build(): no compiler child processes there
-    if stale:
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, src, "-o", out])
-    lib = ctypes.CDLL(out)
-    lib.soft_emu_plan.restype = ctypes.c_int
-    lib.soft_emu_plan.argtypes = [ctypes.c_double, ctypes.c_int, _PTR, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                  ctypes.c_int, ctypes.c_uint64, _PTR]
-    lib.soft_emu_extract.restype = ctypes.c_uint64
-    lib.soft_emu_extract.argtypes = [_PTR, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _PTR, ctypes.c_int,
-                                     ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, _PTR]
-    _EMU = lib
-    return lib
-
-
-def _index_arg(index):
-    if index is None:
-        return None, None, 0
-    idx = np.ascontiguousarray(np.asarray(index, np.int64).reshape(-1).astype(np.uint8))
-    return idx, idx.ctypes.data, idx.size
-
-
-def host_plan(delta, n_ac, index=None, dither=False, order=False, flags=0, total_blocks=1000):
-    """svs::plan_extract of a soft call -> dict of PLAN_FIELDS"""
-    keep, ptr, count = _index_arg(index)
-    out = np.zeros(len(PLAN_FIELDS), np.int32)
-    rc = soft_emu().soft_emu_plan(float(delta), int(n_ac), ptr, count, int(dither), int(order), flags & 1, (flags >> 1) & 1,
-                                  int(total_blocks), out.ctypes.data)
-    assert rc == 0, "the host library refused the selection"
-    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+def host_plan(delta, n_ac, index=None, dither=False, order=False, flags=0, total_blocks=1000, output=testlib.EMU_SOFT, **call):
+    """svs::plan_extract of a soft call -> dict of PLAN_FIELDS (no frames: the walker stops at the plan)"""
+    res = testlib._emu_call("emu_extract_call", np.empty((total_blocks, 8, 8), np.uint8), delta, n_ac, index=index,
+                            dither_key=0 if dither else None, block_key=0 if order else None, pocketfft=flags & 1,
+                            guarded=(flags >> 1) & 1, output=output, **call)
+    return {k: int(getattr(res, k)) for k in PLAN_FIELDS + ("vote", "hist")}
 
 
 def host_soft(frames, delta, n_ac, index=None, key=None, first_frame=0, order_key=None):
     """a soft call through the product headers on the host -> the soft bytes"""
     frames = np.ascontiguousarray(frames if frames.ndim == 3 else frames[None])
     f, h, w = frames.shape
-    keep, ptr, count = _index_arg(index)
-    n = count if count else max(0, min(int(n_ac), MAX_AC))
+    n = len(index) if index is not None and len(index) else max(0, min(int(n_ac), MAX_AC))
     out = np.full(f * (h // 8) * (w // 8) * n + 8, 0xA5, np.uint8)
-    cap = soft_emu().soft_emu_extract(frames.ctypes.data, f, h, w, float(delta), int(n_ac), ptr, count, int(key is not None),
-                                      int(key or 0), int(order_key is not None), int(order_key or 0), int(first_frame),
-                                      out.ctypes.data)
+    cap = testlib._emu_call("emu_extract_call", frames, delta, n_ac, index=index, dither_key=key, block_key=order_key,
+                            first_frame=int(first_frame), frames_in=frames, output=testlib.EMU_SOFT, soft_out=out).used
     assert cap == out.size - 8, (cap, out.size - 8)
     assert (out[cap:] == 0xA5).all(), "the host body wrote past the capacity"
     return out[:cap]

@@ -1,6 +1,6 @@
-"""The refusals of every svs_embed* / svs_extract* entry point, pinned against the build that wrote
+"""The refusals of every svs_embed* / svs_extract* / svs_soft_* entry point, pinned against the build that wrote
 tests/golden/capi_refusals.json (tests/golden/make_capi_refusals.py: the parent of the refactor to one options value per gray
-call): return code, the full svs_last_error() text and what the call left in its out parameters, for every argument a symbol
+call; the svs_soft_* symbols from the parent of the refactor to one description of a soft call's output): return code, the full svs_last_error() text and what the call left in its out parameters, for every argument a symbol
 checks before its device work, alone and in pairs (precedence), and for the empty call.  No case reaches the device: the
 library answers all of them without a GPU."""
 import json
@@ -20,11 +20,11 @@ def table():
 
 
 def gray_and_colour_symbols():
-    return sorted(s for s in native.SIGNATURES if s.startswith(("svs_embed", "svs_extract")))
+    return sorted(s for s in native.SIGNATURES if s.startswith(("svs_embed", "svs_extract", "svs_soft")))
 
 
 def test_every_embed_and_extract_symbol_is_in_the_table(table):
-    assert sorted(table["symbols"]) == gray_and_colour_symbols()
+    assert sorted(table["symbols"]) == gray_and_colour_symbols() and len(table["symbols"]) == 34
     for sym, entry in table["symbols"].items():
         assert len(entry["parameters"]) == len(native.SIGNATURES[sym][1]), sym
         assert len(entry["pairs"]) >= 20, sym                                        # pairs: precedence

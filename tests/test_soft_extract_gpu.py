@@ -1,5 +1,5 @@
 """Soft-decision extraction on the GPU (svs_soft_extract_dev / svs_soft_extract, include/svsdct.h): the device call on tight and
-pitched planes and the host call against the NumPy model of tests/soft_lib.py byte for byte, on the smallest shapes at which the
+pitched planes and the host call against the NumPy model of soft_lib.py byte for byte, on the smallest shapes at which the
 block -> (frame, slot) arithmetic and the wave tile of the soft side can go wrong; the identity of the hard bits with every hard
 extract call; and that a soft call leaves nothing behind that a hard call reads."""
 import ctypes as C

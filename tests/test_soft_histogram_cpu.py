@@ -1,8 +1,8 @@
 """The fused per-frame soft histograms without a GPU (include/svsdct.h, svs_soft_histogram*): the declarations, the refusals of
 the two entry points through the real library (none reaches the device), the NumPy model of the format (svsdct/soft.py:
 byte_histogram, margins, lattice_share) against numpy.bincount and soft.margin_histogram, the host build of the histogram's
-integer side (tests/soft/hist_emu.cpp: the plan and the split of a wave's run of blocks into per-frame runs) against Python
-integers, and the scenario of examples/find_payload_frames.py on the model."""
+integer side (tests/hostemu: the plan and the split of a wave's run of blocks into per-frame runs) against Python
+integers, a whole call's counts through the host walker against the model's, and the scenario of examples/find_payload_frames.py on the model."""
 import ctypes as C
 import os
 import re
@@ -15,7 +15,7 @@ import soft_histogram_lib as hl
 import soft_lib as sl
 from svsdct import native
 from svsdct import soft as sv
-from testlib import REPO
+from testlib import REPO, hostemu
 
 SYMBOLS = ("svs_soft_histogram_dev", "svs_soft_histogram")
 
@@ -205,7 +205,7 @@ def test_lattice_share_of_the_models_stego_and_cover():
         assert 0.45 <= share <= 0.55
 
 
-# ---- the integer side of the kernel's histogram tail on the host (tests/soft/hist_emu.cpp) ---------------------------------
+# ---- the integer side of the kernel's histogram tail on the host (tests/hostemu) --------------------------------------------
 def test_a_histogram_call_plans_the_soft_side_with_the_histogram_on_and_never_keyed():
     for delta in (8, 20, 12.5, 0.1):
         for n in (1, 10, 63):
@@ -214,7 +214,7 @@ def test_a_histogram_call_plans_the_soft_side_with_the_histogram_on_and_never_ke
                 assert plan == dict(path=sl.PATH_EXACT, rows=8, soft=1, vote=0, hist=1, keyed=0)
                 assert args == dict(on=1, vote=0, hist=1)
     assert size == 56                                        # SoftArgs keeps the vote's size: the field took the pad word
-    assert hl.hist_emu().hist_emu_bins() == 256
+    assert hostemu().emu_hist_bins() == 256
     # a soft call and a vote call leave the field off
     import soft_vote_lib as vl
     assert vl.host_vote_args(20, 10, 2400, 0)[0]["vote"] == 1 and sl.host_plan(20, 10)["soft"] == 1
@@ -249,6 +249,22 @@ def test_frame_run_far_into_a_large_call():
     for wg_first in (total - total % hl.WG, (16570 * bpf) // hl.WG * hl.WG):
         for wave_first in range(wg_first, wg_first + hl.WG, 64):
             assert hl.host_runs(wg_first, wave_first, total, bpf) == hl.python_runs(wg_first, wave_first, total, bpf)
+
+
+@pytest.mark.parametrize("form", ("prefix", "dither+zigzag"))
+@pytest.mark.parametrize("name", [k for k, (f, h, w) in hl.SHAPES.items() if (h // 8) * (w // 8) <= 257])
+def test_the_walkers_histogram_is_the_models(name, form):
+    """a whole histogram call through the product headers on the host - extract_block_soft with the launch's tables, every byte
+    counted into its frame's row - against soft.byte_histogram of the NumPy model's bytes, exactly"""
+    delta, n, key, first_frame = 20, 10, 0x5EED0FD17E12, 3
+    frames = dl.noise(hl.SHAPES[name], 0, 256, seed=9)
+    keyed = form != "prefix"
+    kw = dict(index=sl.zigzag(n), key=key, first_frame=first_frame) if keyed else {}
+    call = dict(index=sl.zigzag(n), dither_key=key, first_frame=first_frame) if keyed else {}
+    got = hl.host_hist(frames, delta, n, **call)
+    want = sv.byte_histogram(sl.model_batch_soft(frames, delta, n, **kw), frames.shape[0])
+    assert got.dtype == np.uint32 and np.array_equal(got, want), (name, form)
+    assert int(got.sum()) == frames.shape[0] * (frames.shape[1] // 8) * (frames.shape[2] // 8) * n
 
 
 # ---- the use: which frames carry a payload (examples/find_payload_frames.py) on the model ----------------------------------

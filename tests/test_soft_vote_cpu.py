@@ -1,7 +1,7 @@
 """The fused soft vote without a GPU (include/svsdct.h, svs_soft_vote*): the declarations, the refusals of the two entry points
 through the real library (none reaches the device), the NumPy model of the tally (svsdct/soft.py: tally, tally_bits, tile)
-against soft.combine, the host build of the vote's integer side (tests/soft/vote_emu.cpp) against Python integers, and the
-README's +-8 row decoded through the tally."""
+against soft.combine, the host build of the vote's integer side (tests/hostemu) against Python integers, a whole call's tally
+through the host walker against the model's, and the README's +-8 row decoded through the tally."""
 import ctypes as C
 import os
 import re
@@ -13,7 +13,7 @@ import soft_lib as sl
 import soft_vote_lib as vl
 from svsdct import native
 from svsdct import soft as sv
-from testlib import REPO
+from testlib import REPO, hostemu
 
 SYMBOLS = ("svs_soft_vote_dev", "svs_soft_vote")
 
@@ -203,7 +203,7 @@ def test_tile_cuts_the_last_copy():
         sv.tally(np.zeros(4, np.uint8), 0)
 
 
-# ---- the integer side of the kernel's vote tail on the host (tests/soft/vote_emu.cpp) ------------------------------------
+# ---- the integer side of the kernel's vote tail on the host (tests/hostemu) -----------------------------------------------
 def test_a_vote_call_plans_the_soft_side_with_the_vote_on():
     for delta in (8, 20, 12.5, 0.1):
         for n in (1, 10, 63):
@@ -211,7 +211,7 @@ def test_a_vote_call_plans_the_soft_side_with_the_vote_on():
             assert plan == dict(path=sl.PATH_EXACT, rows=8, soft=1, vote=1)
             assert args == dict(vote=1, period=2400, base=5, head=0)
     assert vl.host_vote_args(20, 10, 2400, 2390)[1] == dict(vote=1, period=2400, base=2390, head=10)
-    # a soft call that is no vote: the fields at the end of SoftArgs are off (tests/soft/soft_emu.cpp never sets them)
+    # a soft call that is no vote: the fields at the end of SoftArgs are off
     assert sl.host_plan(20, 10)["soft"] == 1
 
 
@@ -219,7 +219,7 @@ def test_the_residue_without_a_division_is_the_residue():
     """vote_residue: (base + i) mod period through one double-precision multiply and one correction, for every kind of period -
     small, around the 2^38 below which the quotient is taken, and up to the largest accepted - at the i a call can reach
     (below 63 * 2^31) and the stream offsets of the issue"""
-    top = int(vl.vote_emu().vote_emu_period_max())
+    top = int(hostemu().emu_vote_period_max())
     assert top == (1 << 61) - 1
     rng = np.random.default_rng(11)
     edge_i = [0, 1, 62, 63, 64, 4031, 4032, (1 << 31) - 1, 1 << 31, (1 << 32) - 1, 1 << 32, 63 * ((1 << 31) - 1) - 1, (1 << 38) - 1]
@@ -236,12 +236,33 @@ def test_the_residue_without_a_division_is_the_residue():
 
 
 def test_the_vote_of_a_byte():
-    emu = vl.vote_emu()
+    emu = hostemu()
     for byte in range(256):
         b, m = byte >> 7, byte & 127
-        assert emu.vote_emu_vote(byte, 0) == 2 * (2 * b - 1) * (2 * m + 1)
-        assert emu.vote_emu_vote(byte, 1) == 2 * (2 * b - 1) * (2 * m + 1) + (2 * b - 1)
-    assert abs(emu.vote_emu_vote(0xFF, 1)) == 511                      # the most one copy contributes
+        assert emu.emu_vote_of(byte, 0) == 2 * (2 * b - 1) * (2 * m + 1)
+        assert emu.emu_vote_of(byte, 1) == 2 * (2 * b - 1) * (2 * m + 1) + (2 * b - 1)
+    assert abs(emu.emu_vote_of(0xFF, 1)) == 511                      # the most one copy contributes
+
+
+@pytest.mark.parametrize("form", ("prefix", "dither+zigzag+order"))
+@pytest.mark.parametrize("shape", ((2, 16, 24), (5, 64, 120)))
+def test_the_walkers_tally_is_the_models(shape, form):
+    """a whole vote call through the product headers on the host - extract_block_soft with the launch's tables, vote_residue and
+    vote_of per byte - against soft.tally of the NumPy model's bytes, exactly: every landmark period of the shape, stream offsets
+    at both ends of copy 0 and far behind it, without and with an order, a selection and a dither"""
+    import dither_lib as dl
+    delta, n, key, order_key, first_frame = 20, 10, 0x5EED0FD17E12, 0xB10C0DE, 3
+    frames = dl.noise(shape, 0, 256, seed=9)
+    cap = shape[0] * (shape[1] // 8) * (shape[2] // 8) * n
+    keyed = form != "prefix"
+    kw = dict(index=sl.zigzag(n), key=key, order_key=order_key, first_frame=first_frame) if keyed else {}
+    call = dict(index=sl.zigzag(n), dither_key=key, block_key=order_key, first_frame=first_frame) if keyed else {}
+    soft = sl.model_batch_soft(frames, delta, n, **kw)
+    assert soft.size == cap
+    for period in vl.landmark_periods(*shape, n):
+        for s0 in (0, 1, cap - 1, 10**12 + 7):
+            got = vl.host_tally(frames, delta, n, period, s0, **call)
+            assert np.array_equal(got, sv.tally(soft, period, s0)), (shape, form, period, s0)
 
 
 # ---- robustness: the README's +-8 row through the tally ------------------------------------------------------------------

@@ -216,15 +216,19 @@ class EmuCall(ctypes.Structure):
                 ("dither", _C.c_int32), ("order", _C.c_int32), ("dither_key", _C.c_uint64), ("order_key", _C.c_uint64),
                 ("first_frame", _C.c_uint32), ("guard_scale", _C.c_float), ("tie_scale", _C.c_float), ("force_qm", _C.c_int32),
                 ("exact_rows", _C.c_int32), ("streaming_bodies", _C.c_int32), ("variant", _C.c_int32),
-                ("extract_wave", _C.c_int32), ("keyed_form", _C.c_int32), ("replay_map", _PTR), ("candidate_map", _PTR),
-                ("status", _PTR), ("bits_out", _PTR)]
+                ("extract_wave", _C.c_int32), ("keyed_form", _C.c_int32), ("output", _C.c_int32), ("vote_period", _C.c_uint64),
+                ("vote_bit0", _C.c_uint64), ("replay_map", _PTR), ("candidate_map", _PTR), ("status", _PTR), ("bits_out", _PTR),
+                ("soft_out", _PTR), ("tally", _PTR), ("hist", _PTR)]
 
 
 class EmuResult(ctypes.Structure):
     _fields_ = [("size", _C.c_uint64), ("used", _C.c_uint64), ("replayed", _C.c_uint64), ("repaired", _C.c_uint64),
                 ("unrepaired", _C.c_uint64), ("path", _C.c_int32), ("rows", _C.c_int32), ("qm", _C.c_int32),
                 ("selected", _C.c_int32), ("dithered", _C.c_int32), ("nearest", _C.c_int32), ("minmove", _C.c_int32),
-                ("word", _C.c_uint32)]
+                ("word", _C.c_uint32), ("soft", _C.c_int32), ("vote", _C.c_int32), ("hist", _C.c_int32), ("keyed", _C.c_int32)]
+
+
+EMU_BITS, EMU_SOFT, EMU_VOTE, EMU_HIST = range(4)      # EmuCall.output (emu_call.h EmuOutput)
 
 
 _PROTOTYPES = {
@@ -254,6 +258,12 @@ _PROTOTYPES = {
     "bo_lowbias32": (_C.c_uint32, [_C.c_uint32]),
     "kc_apply": (None, [_PTR, _PTR, _PTR, _C.c_uint64, _PTR]),
     "kc_check": (_C.c_uint64, [_C.c_uint32, _C.c_uint32, _C.c_uint32, _C.c_int, _PTR, _PTR]),
+    "emu_soft_args": (_C.c_int, [_C.POINTER(EmuCall), _PTR]),
+    "emu_vote_residues": (_C.c_int, [_C.POINTER(EmuCall), _PTR, _C.c_uint64, _PTR, _PTR]),
+    "emu_vote_of": (_C.c_int32, [_C.c_uint32, _C.c_int]),
+    "emu_vote_period_max": (_C.c_uint64, []),
+    "emu_hist_bins": (_C.c_uint32, []),
+    "emu_hist_runs": (_C.c_uint32, [_C.c_uint32] * 5 + [_PTR, _C.c_uint32]),
 }
 
 
@@ -288,15 +298,15 @@ def plan_chunks(n_frames, height, row_bytes, total_bytes=None, target_bytes=0):
     return [tuple(int(v) for v in row) for row in out[:n]]
 
 
-def _emu_call(entry, frames, delta, n_ac, bits=None, bit_offset=0, n_bits=None, index=None, exact=None, pocketfft=False,
-              guarded=False, dither_key=None, block_key=None, **fields):
-    """One gray call through the host library: fills an EmuCall from NumPy arguments, runs `entry` (emu_embed_call,
-    emu_extract_call or emu_readback_call) and -> the EmuResult.  bits: 0/1 per bit, packed here MSB-first and padded to
-    whole dwords plus one; n_bits None: all of them from bit_offset on.  index: None, or the flat indices of a coefficient
-    selection.  exact: hostemu's mode number (emu_exact_mode) instead of the two mode bits.  dither_key / block_key: None, or
-    the key of the dither / the block order.  fields: the remaining members of EmuCall by name (arrays by their address)."""
+def _fill_call(shape, delta, n_ac, bits=None, bit_offset=0, n_bits=None, index=None, exact=None, pocketfft=False,
+               guarded=False, dither_key=None, block_key=None, **fields):
+    """An EmuCall from NumPy arguments -> (the call, the arrays made here that it points into).  shape: (F, H, W) of its frames.
+    bits: 0/1 per bit, packed here MSB-first and padded to whole dwords plus one; n_bits None: all of them from bit_offset on.
+    index: None, or the flat indices of a coefficient selection.  exact: hostemu's mode number (emu_exact_mode) instead of the
+    two mode bits.  dither_key / block_key: None, or the key of the dither / the block order.  fields: the remaining members of
+    EmuCall by name (arrays by their address)."""
     lib = hostemu()
-    f, h, w = frames.shape
+    f, h, w = shape
     keep = []          # the arrays made here that the call points into
     call = EmuCall(size=ctypes.sizeof(EmuCall), F=f, H=h, W=w, delta=float(delta), n_ac=int(n_ac), pocketfft=int(pocketfft),
                    guarded=int(guarded), guard_scale=1.0, tie_scale=1.0, force_qm=-1, exact_rows=8, streaming_bodies=1,
@@ -320,6 +330,14 @@ def _emu_call(entry, frames, delta, n_ac, bits=None, bit_offset=0, n_bits=None, 
             keep.append(value)
             value = value.ctypes.data
         setattr(call, name, value)
+    return call, keep
+
+
+def _emu_call(entry, frames, delta, n_ac, **call):
+    """One gray call through the host library: fills an EmuCall (_fill_call), runs `entry` (emu_embed_call, emu_extract_call or
+    emu_readback_call) and -> the EmuResult"""
+    lib = hostemu()
+    call, keep = _fill_call(frames.shape, delta, n_ac, **call)
     res = EmuResult(size=ctypes.sizeof(EmuResult))
     if getattr(lib, entry)(ctypes.byref(call), ctypes.byref(res)) != 0:
         raise RuntimeError("EmuCall / EmuResult differ from tests/hostemu/emu_call.h: rebuild tests/hostemu or mend the mirror")
@@ -356,6 +374,14 @@ def host_extract_call(frames, delta, n_ac, **call):
     out = np.zeros(cmap.size * max(n, 1), np.uint8)
     res = _emu_call("emu_extract_call", frames, delta, n_ac, frames_in=frames, bits_out=out, candidate_map=cmap, **call)
     return out[:res.used], res, cmap.astype(bool)
+
+
+def host_soft_args(shape, delta, n_ac, **call):
+    """the SoftArgs the launch of an extract call over frames of `shape` passes -> dict(on, vote, hist, period, base, head, size)"""
+    call, keep = _fill_call(shape, delta, n_ac, **call)
+    fields = np.zeros(7, np.uint64)
+    assert hostemu().emu_soft_args(ctypes.byref(call), fields.ctypes.data) == 0, "the host library refused the call"
+    return dict(zip(("on", "vote", "hist", "period", "base", "head", "size"), map(int, fields)))
 
 
 def host_readback_call(stego, delta, n_ac, bits, **call):
