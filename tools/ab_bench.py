@@ -26,15 +26,7 @@ ap.add_argument("libs", nargs="+")
 a = ap.parse_args()
 FLAGS = {"fast": 0, "exact": 1, "guarded": 2}[a.mode]       # SVS_EXACT_POCKETFFT = 1, SVS_EXACT_GUARDED = 2
 
-def load(path):
-    lib = C.CDLL(os.path.abspath(path))
-    for name, (res, args) in native.SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:      # a library of an earlier round (lib/variants/libsvsdct_r02.so) lacks the newer entry points
-            continue
-        fn.restype = res; fn.argtypes = args
-    return lib
+from ratelib import load_build as load      # a library of an earlier round (lib/variants/libsvsdct_r02.so) lacks the newer entry points
 
 libs = [(os.path.basename(p).replace("libsvsdct", "").replace(".so", "") or "base", load(p), None) for p in a.libs]
 if a.env_sweep:
