@@ -496,7 +496,8 @@ int svs_extract_dithered(const uint8_t *gray, const svs_planes *planes, const sv
  * table): at delta = 20, n_ac = 10 on noise in [64, 192) undisturbed reference-rule stego has no reliability below 113 and a
  * never-embedded frame a mean of 63.5; three tiled copies under uniform pixel noise of +-8 decode with 3 bit errors by soft
  * vote, 10 by hard majority, 87 - 96 alone.  NOT measured: the call's time on the device (tools/soft_extract_rates.py is
- * there for it) and any real transcode.
+ * there for it).  What requantisation on the 8x8 grid does to the same three copies is measured, on the CPU model of
+ * svs_requantise* below; a real encoder (rate control, chroma, inter prediction, in-loop filters) is not.
  * Cost: a soft call always runs the lane-per-block SVS_EXACT_POCKETFFT extract kernel with all eight coefficient rows, whatever
  * the mode bits say, behind one wave-uniform branch of its eight-row instantiations; every wave assembles its blocks' bytes in
  * LDS that only this launch requests and copies them out coalesced, each byte written once (no clearing, no atomics).
@@ -601,6 +602,56 @@ int svs_soft_histogram_dev(const uint8_t *d_gray, const svs_planes *planes, cons
 
 int svs_soft_histogram(const uint8_t *gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
                        double delta, int n_ac, uint32_t *hist_out, uint32_t flags, uint64_t *n_bits_out);
+
+/* ---- requantisation channel: what an 8x8 intra codec does to stego ------------------------------------------
+ * A measuring tool, not part of the sender's or the receiver's loop: it does to gray planes what the luminance path of JPEG /
+ * MJPEG - the first-order model of any intra codec on the same 8x8 grid - does to them, so that a caller who picks delta, a
+ * rule, a selection, a repeat count or a vote can see what survives.  The channel is a FORMAT, as the dither, the soft byte and
+ * the tally are: the host model (tests/channel_lib.py, built from the CPU oracle's pieces) and the device produce the same
+ * bytes, so a table made on the CPU is the table of the GPU call.  For every 8x8 block of every frame, all arithmetic IEEE
+ * float32, one operation per step, no contraction, the same order on host and device:
+ *     c[k]  = the pocketfft-identical forward transform of the block's uint8 pixels (k = 8u + v, row-major, k = 0..63: the
+ *             transform every exact kernel computes)
+ *     c[0]  = c[0] - 1024.0f                     (JPEG's level shift of 128 per pixel, applied to DC: one subtract)
+ *     q[k]  = rintf(c[k] / (float)step[k])       (float32 division, round half to even)
+ *     c'[k] = q[k] * (float)step[k]              (one multiply; exact: |q * step| < 2^24)
+ *     c'[0] = c'[0] + 1024.0f
+ *     p     = the pocketfft-identical inverse of all 64 c' (axis 0 first, as the embed does)
+ *     out   = saturate_u8(round_half_even(p))    (a decoder ROUNDS; this is NOT the embed's truncation)
+ * A table of all ones is "decode, round, re-encode losslessly"; it is not the identity on stego, because the embed truncates
+ * and the decoder rounds.
+ * Limits: luminance only, aligned to the embed's block grid, no chroma subsampling, no motion prediction, no deblocking, no
+ * entropy coding (which is lossless).  Measured ON THE CPU with the model (tests/test_requantise_cpu.py; README.md has the
+ * table): three 96 x 160 frames of noise in [64, 192), one 2 400-bit payload copy per frame, delta = 20, n_ac = 10, reference
+ * rule: no bit error in any copy at quality 100 .. 85; at quality 75 131 - 143 errors per copy, 137 by hard majority (the copies
+ * fail at the same coefficient indices) and 51 by the soft vote.  NOT measured: a real encoder (rate control, chroma, inter
+ * prediction, in-loop filters) and a grid that is not aligned.
+ * Cost: one launch of the lane-per-block SVS_EXACT_POCKETFFT embed kernel - the same two transforms and 2 B/pixel of traffic -
+ * behind one wave-uniform branch of the single instantiation that holds the channel; per coefficient one division, one round and
+ * one multiply instead of the parity logic.
+ *   steps  : a HOST pointer, read during the call and passed to the kernel by value.  NULL, or an entry of 0 or above 255:
+ *            SVS_ERR_INVALID_ARG (the message names the entry).  1..255 is baseline JPEG's range; the uint16 leaves room to
+ *            widen it without an ABI change.
+ *   flags  : must be 0.
+ *   planes : as everywhere; one geometry for input and output.  n_frames = 0: SVS_OK, nothing is done.
+ *   d_in / d_out : device pointers, 8-byte aligned; d_out may be d_in (in place) or must not overlap it.  Padding between rows
+ *            and frames is neither read nor written.
+ * Every refusal comes before any device work and leaves the output untouched.  svs_requantise_dev enqueues and returns; it keeps
+ * no state and allocates nothing.  svs_requantise takes host pointers and stages through the per-thread context in chunks as
+ * svs_embed does (blocks are independent: a chunk is any band of block rows).  There is no colour, FramePipeline or drop-in form. */
+typedef struct svs_steps {
+    uint16_t step[64];   /* step[k] for flat row-major k = 8u + v, k = 0 is DC; each 1..255 */
+} svs_steps;
+
+/* out = the ITU-T T.81 Annex K luminance table scaled as the IJG library scales it: s = quality < 50 ? 5000 / quality :
+ * 200 - 2 * quality (integer division), step = clamp((base * s + 50) / 100, 1, 255).  quality 50 is the Annex K table, 100 all
+ * ones.  quality outside 1..100: SVS_ERR_INVALID_ARG.  Host only: needs no GPU. */
+int svs_quality_steps(svs_steps *out, int quality);
+
+int svs_requantise_dev(const uint8_t *d_in, uint8_t *d_out, const svs_planes *planes, const svs_steps *steps, uint32_t flags,
+                       void *stream);
+
+int svs_requantise(const uint8_t *in, uint8_t *out, const svs_planes *planes, const svs_steps *steps, uint32_t flags);
 
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:

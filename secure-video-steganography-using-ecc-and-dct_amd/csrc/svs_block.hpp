@@ -589,6 +589,24 @@ struct DitherArgs {          // by-value argument of the two exact kernels (read
                              // extract_exact_kernel: empty on its hard sides; the table of its soft side, on or off (SoftArgs)
 };
 
+// The requantisation channel (include/svsdct.h svs_steps) as embed_exact_kernel takes it, by value: byte k & 3 of w[k >> 2] is the
+// step of flat row-major coefficient k, 1..255.  on == 0: an embed launch - the kernel as it was.  Read by the one
+// instantiation that holds the channel body (svs_device.hpp); k is a compile-time index there, so a step is a scalar shift
+// and mask of a kernel-argument dword and one scalar conversion.
+struct ChannelArgs {
+    uint32_t on;
+    uint32_t w[16];
+    SVS_HD float step(int k) const { return (float)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu); }
+};
+
+// host side: the channel of a checked table (every entry 1..255)
+inline ChannelArgs make_channel_args(const uint16_t (&step)[64]) {
+    ChannelArgs c{};
+    c.on = 1u;
+    for (int k = 0; k < 64; ++k) c.w[k >> 2] |= ((uint32_t)step[k] & 0xFFu) << (8 * (k & 3));
+    return c;
+}
+
 // host side: the table of `count` indices; false unless they are distinct and in 1..63 (count <= 63)
 inline bool make_coeff_table(const uint8_t *index, uint32_t count, CoeffTable *t) {
     for (int i = 0; i < 16; ++i) t->w[i] = 0xFFFFFFFFu;
@@ -1065,29 +1083,12 @@ SVS_HD void qim_exact_selected_dithered(pf::f32x2 (&D2)[4][8], const CoeffTable 
     if constexpr (K < 63) qim_exact_selected_dithered<QM, RULE, K + 1>(D2, sel, nb, hi, lo, qp, s_b);
 }
 
-// `sel`: NULL (the row-major prefix 1..n) or a selection; then n is not read, nb counts slots of the selection.  The callers
-// pass a compile-time NULL or the address of a by-value kernel argument, so the test folds on either side.
-// DITH (the dithered calls; U = 8, and `sel` is never NULL: the call's selection or the prefix table of n): the selected loop
-// with the block's s_b (dither_block_seed); everything around it is the same.
-template <int U, int QM, bool DITH = false>
-SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo,
-                              const QimRule &qp, bool constant_block = false, const CoeffTable *sel = nullptr, uint32_t s_b = 0u) {
+// The pocketfft-identical inverse of all 64 coefficients (vertical first, :168) into the block's row dwords; every byte is
+// overwritten (the input rows are dead).  RNE false: np.uint8(np.clip(v, 0, 255)), clip then truncate (:171) - the embed.
+// RNE true: round half to even, then saturate - what a decoder does (the requantisation channel).
+template <bool RNE>
+SVS_HD void inverse_exact_paired(const pf::f32x2 (&D2)[4][8], uint32_t (&rx)[8], uint32_t (&ry)[8]) {
     using pf::f32x2;
-    static_assert(!DITH || U == 8, "a dithered call covers all eight coefficient rows");
-    f32x2 D2[4][8];
-    if (constant_block) forward_exact_paired_constant(ubyte_to_float<0>(rx[0]), D2);
-    else forward_exact_paired(rx, ry, D2);
-    if constexpr (DITH) {
-        if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_selected_dithered<QM, RULE_MINMOVE>(D2, *sel, nb, hi, lo, qp, s_b);
-        else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_selected_dithered<QM, RULE_NEAREST>(D2, *sel, nb, hi, lo, qp, s_b);
-        else qim_exact_selected_dithered<QM, RULE_REFERENCE>(D2, *sel, nb, hi, lo, qp, s_b);
-    } else if (sel) {
-        if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_selected<QM, RULE_MINMOVE>(D2, *sel, nb, hi, lo, qp);
-        else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_selected<QM, RULE_NEAREST>(D2, *sel, nb, hi, lo, qp);
-        else qim_exact_selected<QM, RULE_REFERENCE>(D2, *sel, nb, hi, lo, qp);
-    } else if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_paired<U, QM, RULE_MINMOVE>(D2, n, nb, hi, lo, qp);
-    else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_paired<U, QM, RULE_NEAREST>(D2, n, nb, hi, lo, qp);
-    else qim_exact_paired<U, QM, RULE_REFERENCE>(D2, n, nb, hi, lo, qp);
     f32x2 P2[4][8];  // vertical inverse of coefficient-column pairs: P2[p][y] = (P[y][2p], P[y][2p+1])
 #pragma unroll
     for (int p2 = 0; p2 < 4; ++p2) {
@@ -1112,12 +1113,65 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
             in[2 * p2 + 1] = o;
         }
         pf::dct3_8(in, px);
-        // np.uint8(np.clip(v, 0, 255)): clip, then truncate (every byte is overwritten: the input rows are dead)
 #pragma unroll
-        for (int k = 0; k < 2; ++k)
-            store_row_trunc(px[0][k], px[1][k], px[2][k], px[3][k], px[4][k], px[5][k], px[6][k], px[7][k], rx[2 * q + k],
-                            ry[2 * q + k]);
+        for (int k = 0; k < 2; ++k) {
+            if constexpr (RNE) {
+                uint32_t a = 0u, b = 0u;
+                a = put_pixel_rne<0>(px[0][k], a); a = put_pixel_rne<1>(px[1][k], a);
+                a = put_pixel_rne<2>(px[2][k], a); a = put_pixel_rne<3>(px[3][k], a);
+                b = put_pixel_rne<0>(px[4][k], b); b = put_pixel_rne<1>(px[5][k], b);
+                b = put_pixel_rne<2>(px[6][k], b); b = put_pixel_rne<3>(px[7][k], b);
+                rx[2 * q + k] = a;
+                ry[2 * q + k] = b;
+            } else {
+                store_row_trunc(px[0][k], px[1][k], px[2][k], px[3][k], px[4][k], px[5][k], px[6][k], px[7][k], rx[2 * q + k],
+                                ry[2 * q + k]);
+            }
+        }
     }
+}
+
+// `sel`: NULL (the row-major prefix 1..n) or a selection; then n is not read, nb counts slots of the selection.  The callers
+// pass a compile-time NULL or the address of a by-value kernel argument, so the test folds on either side.
+// DITH (the dithered calls; U = 8, and `sel` is never NULL: the call's selection or the prefix table of n): the selected loop
+// with the block's s_b (dither_block_seed); everything around it is the same.
+template <int U, int QM, bool DITH = false>
+SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, uint32_t nb, uint32_t hi, uint32_t lo,
+                              const QimRule &qp, bool constant_block = false, const CoeffTable *sel = nullptr, uint32_t s_b = 0u) {
+    using pf::f32x2;
+    static_assert(!DITH || U == 8, "a dithered call covers all eight coefficient rows");
+    f32x2 D2[4][8];
+    if (constant_block) forward_exact_paired_constant(ubyte_to_float<0>(rx[0]), D2);
+    else forward_exact_paired(rx, ry, D2);
+    if constexpr (DITH) {
+        if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_selected_dithered<QM, RULE_MINMOVE>(D2, *sel, nb, hi, lo, qp, s_b);
+        else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_selected_dithered<QM, RULE_NEAREST>(D2, *sel, nb, hi, lo, qp, s_b);
+        else qim_exact_selected_dithered<QM, RULE_REFERENCE>(D2, *sel, nb, hi, lo, qp, s_b);
+    } else if (sel) {
+        if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_selected<QM, RULE_MINMOVE>(D2, *sel, nb, hi, lo, qp);
+        else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_selected<QM, RULE_NEAREST>(D2, *sel, nb, hi, lo, qp);
+        else qim_exact_selected<QM, RULE_REFERENCE>(D2, *sel, nb, hi, lo, qp);
+    } else if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_paired<U, QM, RULE_MINMOVE>(D2, n, nb, hi, lo, qp);
+    else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_paired<U, QM, RULE_NEAREST>(D2, n, nb, hi, lo, qp);
+    else qim_exact_paired<U, QM, RULE_REFERENCE>(D2, n, nb, hi, lo, qp);
+    inverse_exact_paired<false>(D2, rx, ry);
+}
+
+// The requantisation channel of one block (include/svsdct.h, "requantisation channel"): the same round trip with the 64-step
+// requantiser in place of the payload loop, and a decoder's store.  Every step is one float32 operation, in the header's order.
+SVS_HD void requantise_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], const ChannelArgs &ch) {
+    using pf::f32x2;
+    f32x2 D2[4][8];
+    forward_exact_paired(rx, ry, D2);
+    D2[0][0][0] = D2[0][0][0] - 1024.0f;   // the level shift of 128 per pixel, on DC
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const float s = ch.step(k);        // wave-uniform
+        const float c = D2[k >> 4][k & 7][(k >> 3) & 1];
+        D2[k >> 4][k & 7][(k >> 3) & 1] = rintf(c / s) * s;
+    }
+    D2[0][0][0] = D2[0][0][0] + 1024.0f;
+    inverse_exact_paired<true>(D2, rx, ry);
 }
 
 // =====================================================================================================

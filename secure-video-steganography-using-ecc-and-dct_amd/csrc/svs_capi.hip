@@ -206,9 +206,9 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
                 constexpr int U = decltype(u)::value;
                 if (p.keyed)
                     return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g,
-                                  p.qp, bits, p.bit_offset, p.n_bits, words, t.sel, t.dith, ord);
+                                  p.qp, bits, p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{}, ord);
                 return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words, t.sel, t.dith);
+                              p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{});
             });
         if (p.rows == 2) {   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
             if (p.keyed)
@@ -230,6 +230,15 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
                           p.n_bits, words SVS_COUNTER_ARG);
         });
     });
+}
+
+// svs_requantise_dev: the channel side of the one exact embed instantiation that holds it (svs_device.hpp).  No payload, no
+// quantiser parameters, no tables: the kernel reads the geometry and `chan` alone.
+int launch_requantise(uint64_t total, hipStream_t st, const uint8_t *in, uint8_t *out, svs::Geometry g, const svs::ChannelArgs &chan) {
+    g.n_ac = 0;
+    g.xcd_chunk = svs::kEighth;
+    return launch(svs::embed_exact_kernel<svs::QM_DOUBLE, 8>, grid_for(total), 0, st, in, out, g, svs::QimParams{},
+                  static_cast<const uint32_t *>(nullptr), (uint64_t)0, (uint64_t)0, (uint32_t)0, svs::CoeffTable{}, svs::DitherArgs{}, chan);
 }
 
 // SVS_READBACK: readback_kernel<rows, QM> over the stego planes the embed has just written, on the same stream, with the
@@ -988,6 +997,26 @@ static void copy_gray_reference(uint8_t *dst, const uint8_t *gray, const svs_pla
                    gray + (int64_t)f * planes->frame_pitch + (int64_t)y * planes->row_pitch, (size_t)planes->width);
 }
 
+// A staged chunk of gray planes back to the caller (`d`: the staging buffer, same offsets): pixel bytes only - padding in the
+// caller's output buffer is left alone
+static int download_pixels(uint8_t *dst, const uint8_t *d, const svs_planes *planes, const svs::Chunk &ch, int64_t off, hipStream_t st) {
+    const int32_t H = planes->height, W = planes->width;
+    const int64_t rp = planes->row_pitch, fp = planes->frame_pitch;
+    const bool rows_packed = rp == W, frames_packed = rows_packed && fp == (int64_t)H * W;
+    if (frames_packed || (rows_packed && ch.nf == 1))
+        return stage_d2h(st, dst + off, d + off, ch.nf == 1 ? (size_t)ch.rows * W : (size_t)ch.nf * H * W);
+    for (int32_t f = 0; f < ch.nf; ++f) {
+        const int64_t o = off + (int64_t)f * fp;
+        if (rows_packed) {
+            if (int rc = stage_d2h(st, dst + o, d + o, (size_t)ch.rows * W)) return rc;
+        } else if (hipMemcpy2DAsync(dst + o, (size_t)rp, d + o, (size_t)rp, (size_t)W, (size_t)ch.rows, hipMemcpyDeviceToHost, st) !=
+                   hipSuccess) {
+            return fail(SVS_ERR_HIP, "hipMemcpy2DAsync failed: %s", hipGetErrorString(hipGetLastError()));
+        }
+    }
+    return SVS_OK;
+}
+
 // svs_embed (payload = packed MSB-first bits, indexed by bit_offset) and svs_embed_str (payload = n_bits '0' / '1' characters,
 // bit_offset = 0) share everything but the way the payload reaches the device
 // (`o`: what the call adds to svs_embed, with a packed payload; o.counts receives the read-back counts)
@@ -1039,21 +1068,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                     return embed_dev(d + off, d + off, &sub, delta, n_ac, static_cast<const uint8_t *>(c.bits.p), chunk_offset, budget,
                                      flags, done, up, o.chunk((uint32_t)f0, d_counts, &order, &dither));
                 },
-                [&](const svs::Chunk &ch, int64_t off, hipStream_t st) {
-                    // back: pixel bytes only (padding in the caller's stego buffer is left alone)
-                    if (frames_packed || (rows_packed && ch.nf == 1))
-                        return stage_d2h(st, stego + off, d + off, ch.nf == 1 ? (size_t)ch.rows * W : (size_t)ch.nf * H * W);
-                    for (int32_t f = 0; f < ch.nf; ++f) {
-                        const int64_t o = off + (int64_t)f * fp;
-                        if (rows_packed) {
-                            if (int rc = stage_d2h(st, stego + o, d + o, (size_t)ch.rows * W)) return rc;
-                        } else if (hipMemcpy2DAsync(stego + o, (size_t)rp, d + o, (size_t)rp, (size_t)W, (size_t)ch.rows,
-                                                    hipMemcpyDeviceToHost, st) != hipSuccess) {
-                            return fail(SVS_ERR_HIP, "hipMemcpy2DAsync failed: %s", hipGetErrorString(hipGetLastError()));
-                        }
-                    }
-                    return (int)SVS_OK;
-                },
+                [&](const svs::Chunk &ch, int64_t off, hipStream_t st) { return download_pixels(stego, d, planes, ch, off, st); },
                 &done_total, o.order != nullptr || o.dither != nullptr);
             if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, 16, hipMemcpyDeviceToHost, c.st[0]));
             // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
@@ -1170,6 +1185,77 @@ int svs_coeffs_scan(svs_coeffs *out, int scan, int first, int count) {
     out->count = (uint8_t)count;
     for (int i = 0; i < count; ++i) out->index[i] = scan == SVS_SCAN_ZIGZAG ? kZigzag[first + i] : (uint8_t)(first + i);
     return SVS_OK;
+}
+
+// ---- the requantisation channel (include/svsdct.h) ----------------------------------------------------------------------
+// ITU-T T.81 Annex K, table K.1 (luminance), in natural row-major order
+static const uint8_t kAnnexKLuma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
+                                        14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                                        18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                                        49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+
+int svs_quality_steps(svs_steps *out, int quality) {
+    if (!out) return fail(SVS_ERR_INVALID_ARG, "out is NULL");
+    if (quality < 1 || quality > 100) return fail(SVS_ERR_INVALID_ARG, "quality %d is not in 1..100", quality);
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;   // IJG's scaling
+    for (int k = 0; k < 64; ++k) {
+        const int v = (kAnnexKLuma[k] * s + 50) / 100;
+        out->step[k] = (uint16_t)(v < 1 ? 1 : (v > 255 ? 255 : v));
+    }
+    return SVS_OK;
+}
+
+// what both requantise calls check before any device work, in this order -> the kernel's channel, geometry and block count
+// (total = 0: an empty call, whose pointers were not looked at)
+static int requantise_checks(const void *in, const void *out, bool device, const svs_planes *planes, const svs_steps *steps,
+                             uint32_t flags, svs::ChannelArgs *chan, svs::Geometry *g, uint64_t *total) {
+    if (!steps) return fail(SVS_ERR_INVALID_ARG, "steps is NULL");
+    for (int k = 0; k < 64; ++k)
+        if (steps->step[k] < 1 || steps->step[k] > 255)
+            return fail(SVS_ERR_INVALID_ARG, "step[%d] = %u is not in 1..255", k, (unsigned)steps->step[k]);
+    if (flags != 0) return fail(SVS_ERR_INVALID_ARG, "unknown flags 0x%x (the requantise calls take none)", flags);
+    if (int rc = make_geometry(planes, 0, g, total)) return rc;
+    *chan = svs::make_channel_args(steps->step);
+    if (*total == 0) return SVS_OK;
+    if (!in || !out) return fail(SVS_ERR_INVALID_ARG, "in/out pointer is NULL");
+    if (device && (((uintptr_t)in % 8) || ((uintptr_t)out % 8)))
+        return fail(SVS_ERR_INVALID_ARG, "plane pointers must be 8-byte aligned");
+    if (in != out && ranges_overlap(in, out, span_bytes(planes)))
+        return fail(SVS_ERR_INVALID_ARG, "the output must be the input itself (in place) or must not overlap it");
+    return SVS_OK;
+}
+
+int svs_requantise_dev(const uint8_t *d_in, uint8_t *d_out, const svs_planes *planes, const svs_steps *steps, uint32_t flags,
+                       void *stream) {
+    svs::ChannelArgs chan;
+    svs::Geometry g;
+    uint64_t total = 0;
+    if (int rc = requantise_checks(d_in, d_out, true, planes, steps, flags, &chan, &g, &total)) return rc;
+    if (total == 0) return SVS_OK;
+    return launch_requantise(total, (hipStream_t)stream, d_in, d_out, g, chan);
+}
+
+// Host form: svs_embed's chunk pipeline without a payload - blocks are independent, so a chunk is any band of block rows
+int svs_requantise(const uint8_t *in, uint8_t *out, const svs_planes *planes, const svs_steps *steps, uint32_t flags) {
+    svs::ChannelArgs chan;
+    svs::Geometry g;
+    uint64_t total = 0;
+    if (int rc = requantise_checks(in, out, false, planes, steps, flags, &chan, &g, &total)) return rc;
+    if (total == 0) return SVS_OK;
+    return staged(span_bytes(planes), 0, 0, 0, [&](HostStage &c) {
+        uint8_t *d = static_cast<uint8_t *>(c.frames.p);
+        uint64_t done_total = 0;
+        return embed_chunks(
+            c, planes, 1, in, 0, 0, 0, 0,
+            [&](const svs_planes &sub, int64_t off, int32_t, uint64_t, uint64_t, uint64_t *, hipStream_t up) {
+                svs::Geometry sg;
+                uint64_t sub_total = 0;
+                if (int rc = make_geometry(&sub, 0, &sg, &sub_total)) return rc;
+                return launch_requantise(sub_total, up, d + off, d + off, sg, chan);
+            },
+            [&](const svs::Chunk &ch, int64_t off, hipStream_t st) { return download_pixels(out, d, planes, ch, off, st); },
+            &done_total);
+    });
 }
 
 // The select calls are the ordered calls at n_ac = coeffs->count with the selection's table; the prefix 1..count passes no

@@ -344,8 +344,32 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
                                                           const uint32_t *__restrict__ bits,
                                                           const uint64_t bit_offset, const uint64_t n_bits,
                                                           const uint32_t n_words, const CoeffTable sel,
-                                                          const DitherArgs dith, const Order... order) {
+                                                          const DitherArgs dith, const ChannelArgs chan,
+                                                          const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
+    // The requantisation channel (svs_requantise_dev; chan.on): a wave-uniform branch around everything else, compiled into ONE
+    // instantiation - the unkeyed eight-row QM_DOUBLE one, which otherwise serves only calls whose delta is no float32 value
+    // (the channel's division is the float32 one whatever QM says).  Every other instantiation ignores `chan`.  The same
+    // round trip as the body below - load eight rows, forward, touch coefficients, inverse, store - without a payload window,
+    // a budget or an early copy: every block is requantised, and the store rounds (requantise_block_exact).  A lane loads its
+    // rows before it stores them, so in place works as for the embed.
+    if constexpr (QM == QM_DOUBLE && U == 8 && !KEYED) {
+        if (chan.on) {
+            const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
+            if (gblock >= g.total_blocks) return;
+            const int64_t off = block_offset(gblock, g);
+            typename RowVec<1>::type v[8];
+            load_rows<1>(gray + off, g.row_pitch, v);
+            uint32_t ax[8], ay[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
+            requantise_block_exact(ax, ay, chan);
+#pragma unroll
+            for (int r = 0; r < 8; ++r) { v[r].x = ax[r]; v[r].y = ay[r]; }
+            store_rows<1>(stego + off, g.row_pitch, v);
+            return;
+        }
+    }
     // SVS_NEAREST, SVS_MINMOVE: ONE wave-uniform branch around the whole body, the rule a compile-time constant on every side
     // (QimRule; under SVS_MINMOVE its half_cell is the launch's, the kind is the constant: rule_from_word with a word > 1).
     // A `return` inside the body leaves the body, and nothing follows the calls.

@@ -22,6 +22,7 @@ from typing import NamedTuple
 
 import numpy as np
 
+from . import channel as _channel
 from . import coeffs as _coeffs
 from . import dither as _dither
 from . import native
@@ -426,6 +427,23 @@ def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | N
     return (stego, used, int(bits.size), *counts)
 
 
+def requantise_frames(frames: np.ndarray, steps_or_quality, device: int = 0) -> np.ndarray:
+    """The requantisation channel on a stack of gray frames on the GPU (svs_requantise, include/svsdct.h): every 8x8 block is
+    transformed, each coefficient divided by its step, rounded and multiplied back, the block inverted and ROUNDED to uint8 -
+    the luminance path of JPEG / MJPEG on the embed's grid.  A measuring tool: what of a stego clip survives an intra codec.
+    steps_or_quality: a quality 1..100 (channel.quality_steps) or a table of 64 steps in 1..255, flat row-major, entry 0 DC.
+    Returns a new uint8 array [F,H,W]; the input is not touched."""
+    steps = _channel.steps_struct(steps_or_quality)
+    lib = native.load()
+    native.ensure_device(device)
+    stack = _as_stack(frames)
+    f, h, w = stack.shape
+    out = pinned_empty(stack.shape)
+    planes = Planes.contiguous(f, h, w)
+    native.check(lib.svs_requantise(stack.ctypes.data, out.ctypes.data, C.byref(planes), C.byref(steps), 0), "svs_requantise")
+    return out
+
+
 # ---- the reference operator's own payload types: '0' / '1' strings ------------------------------------------
 _utf8_and_size = None
 
@@ -559,6 +577,14 @@ def extract_histogram_device(d_gray: int, planes: Planes, delta, n_ac, d_hist: i
     extract_histogram_frames).  coeffs, dither_key, first_frame: as extract_soft_device."""
     call = _resolve(n_ac, None, None, first_frame, coeffs, dither_key)
     return _soft_call(native.load(), "histogram", call, [d_gray, C.byref(planes)], delta, n_ac, [d_hist], 0, (stream or None,))
+
+
+def requantise_device(d_in: int, d_out: int, planes: Planes, steps_or_quality, stream: int = 0) -> None:
+    """Enqueue the requantisation channel on `stream` (svs_requantise_dev): planes at d_in -> planes of the same geometry at
+    d_out, which may be d_in (in place) or must not overlap it.  steps_or_quality: as requantise_frames."""
+    steps = _channel.steps_struct(steps_or_quality)
+    native.check(native.load().svs_requantise_dev(d_in, d_out, C.byref(planes), C.byref(steps), 0, stream or None),
+                 "svs_requantise_dev")
 
 
 # ---- fused colour path (BGR in, BGR out; SURVEY 8(f) rank 2) ---------------------------------

@@ -63,6 +63,11 @@ class Dither(C.Structure):
     _fields_ = [("key", C.c_uint64), ("first_frame", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Steps(C.Structure):
+    """struct svs_steps: the 64 quantiser steps of the requantisation channel (include/svsdct.h, svsdct/channel.py)"""
+    _fields_ = [("step", C.c_uint16 * 64)]
+
+
 SVS_SCAN_ROW_MAJOR = 0
 SVS_SCAN_ZIGZAG = 1
 
@@ -72,6 +77,7 @@ _PL = C.POINTER(Planes)
 _BO = C.POINTER(BlockOrder)
 _CO = C.POINTER(Coeffs)
 _DI = C.POINTER(Dither)
+_ST = C.POINTER(Steps)
 
 # name -> (restype, argtypes); every symbol include/svsdct.h declares
 SIGNATURES = {
@@ -126,6 +132,9 @@ SIGNATURES = {
                                  _u64p]),
     "svs_soft_histogram_dev": (C.c_int, [_u8p, _PL, _CO, _DI, C.c_double, C.c_int, C.c_void_p, C.c_uint32, _u64p, C.c_void_p]),
     "svs_soft_histogram": (C.c_int, [_u8p, _PL, _CO, _DI, C.c_double, C.c_int, C.c_void_p, C.c_uint32, _u64p]),
+    "svs_quality_steps": (C.c_int, [_ST, C.c_int]),
+    "svs_requantise_dev": (C.c_int, [_u8p, _u8p, _PL, _ST, C.c_uint32, C.c_void_p]),
+    "svs_requantise": (C.c_int, [_u8p, _u8p, _PL, _ST, C.c_uint32]),
     "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                           _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
