@@ -8,11 +8,18 @@ lattice (soft.lattice_share).
 
     python examples/recompression_survival.py [--delta 20] [--n-ac 10] [--rule reference|nearest|minmove]
                                               [--zigzag FIRST] [--qualities 100,95,90,85,75,50]
+                                              [--steps q75x2 | q95x2f16 | d1,...,d64]
 
 Everything runs on the GPU through the library.  The channel is a format, so the numbers equal those of the CPU model
 (tests/channel_lib.py) for the same seed - at the defaults the reference-rule row of README.md's table: no error down to
 quality 85, and at 75 copies that fail together, which the soft vote mends in part.  The model is luminance only, grid-aligned,
 without chroma subsampling, motion prediction or deblocking.
+
+--steps prints two rows per quality instead: the uniform delta of --delta against per-coefficient QIM steps (svsdct/steps.py;
+batch.embed_frames / extract_frames with steps=): the PSNR of each against the cover and the bit errors of each copy alone.  A
+table matched to a codec's (q75x2: twice the quality-75 steps) keeps its lattice points through that codec's requantiser, so
+the step is large only where the codec's is - README.md has the table, from the CPU model (tests/stepped_lib.py).  A stepped
+call has no soft, vote or histogram form.
 """
 import argparse
 import os
@@ -22,7 +29,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "secure-video-steganography-using-ecc-and-dct_amd"))
 import numpy as np  # noqa: E402
 
-from svsdct import batch, soft  # noqa: E402
+from svsdct import batch, soft, steps  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--delta", type=float, default=20)
@@ -31,6 +38,8 @@ ap.add_argument("--rule", choices=("reference", "nearest", "minmove"), default="
 ap.add_argument("--zigzag", type=int, default=0, metavar="FIRST",
                 help="put the payload on zig-zag scan positions FIRST .. FIRST + n_ac - 1 instead of the row-major prefix")
 ap.add_argument("--qualities", default="100,95,90,85,75,50")
+ap.add_argument("--steps", default=None, metavar="SPEC",
+                help="compare the uniform delta with per-coefficient steps: q<quality>x<multiple>[f<floor>] or 64 integers")
 a = ap.parse_args()
 
 f, h, w = 3, 96, 160
@@ -38,6 +47,31 @@ rng = np.random.default_rng(5)
 cover = rng.integers(64, 192, (f, h, w)).astype(np.uint8)                     # no pixel clips at 0 or 255 before the channel
 payload = rng.integers(0, 2, batch.capacity_bits(1, h, w, a.n_ac)).astype(np.uint8)
 kw = dict(coeffs=f"zigzag:{a.zigzag}") if a.zigzag else {}
+
+
+def psnr(x, y):
+    e = float(((x.astype(np.int64) - y.astype(np.int64)) ** 2).sum())
+    return float("inf") if e == 0 else 10 * np.log10(255.0 ** 2 * x.size / e)
+
+
+if a.steps:
+    table = steps.parse(a.steps)
+    stream = np.tile(payload, f)
+    rule = dict(nearest=a.rule == "nearest", minmove=a.rule == "minmove")
+    print(f"{f} frames of {w}x{h}, one copy of {payload.size} bits per frame, n = {a.n_ac}, {a.rule} rule"
+          + (f", zig-zag from {a.zigzag}" if a.zigzag else ""))
+    print("steps                | PSNR dB | " + " | ".join(f"Q = {q}" for q in a.qualities.split(",")))
+    for name, how in ((f"uniform {a.delta:g}", {}), (a.steps if len(a.steps) < 20 else "table", dict(steps=table))):
+        stego, used = batch.embed_frames(cover, a.delta, a.n_ac, stream, mode="exact", **rule, **kw, **how)
+        assert used == stream.size
+        cells = []
+        for quality in (int(q) for q in a.qualities.split(",")):
+            packed, n = batch.extract_frames(batch.requantise_frames(stego, quality), a.delta, a.n_ac, mode="exact", **kw, **how)
+            got = np.unpackbits(packed, count=n).reshape(f, payload.size)
+            cells.append("/".join(str(int((g != payload).sum())) for g in got))
+        print(f"{name:20s} | {psnr(stego, cover):7.2f} | " + " | ".join(cells))
+    sys.exit(0)
+
 stego, used, period = batch.embed_repeated_frames(cover, a.delta, a.n_ac, payload, mode="exact", nearest=a.rule == "nearest",
                                                   minmove=a.rule == "minmove", **kw)
 assert (used, period) == (f * payload.size, payload.size)

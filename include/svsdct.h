@@ -653,6 +653,66 @@ int svs_requantise_dev(const uint8_t *d_in, uint8_t *d_out, const svs_planes *pl
 
 int svs_requantise(const uint8_t *in, uint8_t *out, const svs_planes *planes, const svs_steps *steps, uint32_t flags);
 
+/* ---- per-coefficient QIM steps: lattices matched to a codec's table ---------------------------------------------
+ * Every other embed call quantises all payload coefficients with one delta; an 8x8 intra codec quantises coefficient k with
+ * its own step s_k.  With delta_k = m * s_k a lattice point q * delta_k is a multiple of s_k and passes the requantiser
+ * (svs_requantise*: rintf(c / s_k) * s_k) unchanged, so the step is large only where the codec's is.  Opt-in; both sides must
+ * hold the same table.  A FORMAT, as the dither and the channel are: for a payload coefficient c at flat row-major index k
+ * with bit b, dk = (float)delta[k], every step one IEEE float32 operation with no contraction, in the same order on host and
+ * device:
+ *     q = (int)rintf(c / dk)                     (float32 division, round half to even)
+ *     the value written for index t is (float)t * dk                (exact: |t * dk| < 2^24)
+ *     reference rule: t = q with its parity forced to b (as svs_embed);  SVS_NEAREST: the nearer lattice point of parity b, the
+ *     side taken from c against c0 = (float)q * dk, the reference's choice when c == c0;  SVS_MINMOVE: c clamped into
+ *     [ct - r_k, ct + r_k] around SVS_NEAREST's point ct, h_k = 0.5f * dk, r_k = fmaxf(0, h_k - MARGIN[k])
+ *     under a dither: d = r * dk with the dithered calls' hash and r, the rule on c - d, the result moved back by d, and a
+ *     coefficient the rule leaves alone keeps c exactly
+ *     the receiver reads rintf((c - d) / dk) & 1   (d = 0 without a dither)
+ * Everything else is the reference's: stream ranges, the block budget and the block it ends in, byte-identical blocks past the
+ * budget, the copy of an empty payload, the round trip of every block when nothing can be embedded but n_bits > 0, the
+ * pocketfft-identical inverse of all 64 coefficients, clip, truncate.  There is no delta <= 0 route: an entry is at least 1.
+ * A uniform table (every delta[k] = D) gives, byte for byte and bit for bit, the output of the existing call with delta = D and
+ * the same order, selection, dither and rule; the stepped side of the kernels runs all the same.
+ *   steps  : required, a HOST pointer read during the call and passed to the kernels by value.  NULL, or an entry k >= 1 that is
+ *            0 or above 4095: SVS_ERR_INVALID_ARG naming the entry, before the other options are checked and before any device
+ *            work.  delta[0] (DC) is not read.
+ *   order, coeffs, dither : each may be NULL; checked as in the dithered calls (dither, then coeffs, then flags).  With coeffs,
+ *            n_ac is ignored.
+ *   flags  : embed - the mode bits (accepted; a stepped call runs the lane-per-block exact kernels in every mode), SVS_NEAREST
+ *            and SVS_MINMOVE; extract - the mode bits only.  SVS_READBACK, SVS_KEEP_COLOUR and anything else: refused.
+ * The host forms go through the per-thread staging context: whole frames under an order or a dither, chunks otherwise.
+ * Limits: both sides must hold the table; a matched table is tuned to ONE codec table on the aligned luminance grid (README.md
+ * has the survival table, from the CPU model; a table matched to a fine codec table needs a floor, see svs_matched_steps); a
+ * real encoder is not measured.  A stepped call has no read-back, soft, vote, histogram, colour or _str form. */
+typedef struct svs_qim_steps {
+    uint16_t delta[64];   /* delta[k]: the step of flat row-major coefficient k = 8u + v; k = 1..63 each 1..4095; delta[0] (DC) is not read */
+} svs_qim_steps;
+
+/* out->delta[k] = codec->step[k] * max(multiple, ceil(floor / codec->step[k])) for k = 1..63, delta[0] = 0.  multiple 1..16,
+ * floor 0..4095.  The floor keeps a step above the embed's own truncation disturbance (up to 4.0 per coefficient): the low
+ * frequencies of the quality-95 table have steps of 1 - 2, and twice that table does not survive its own channel; with
+ * floor = 16 it does.  SVS_ERR_INVALID_ARG for a
+ * NULL pointer, a codec entry outside 1..255 or a result above 4095 (the message names the entry); *out is then left as
+ * it was.  Host only: needs no GPU. */
+int svs_matched_steps(svs_qim_steps *out, const svs_steps *codec, int multiple, int floor);
+
+int svs_stepped_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                          const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                          const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                          uint64_t *n_embedded, void *stream);
+
+int svs_stepped_embed(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                      const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                      const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded);
+
+int svs_stepped_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                            const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint8_t *d_bits_packed_out,
+                            uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+int svs_stepped_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                        const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint8_t *bits_packed_out,
+                        uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out);
+
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:
  *   d_counts : NULL, or a device buffer of two uint64 (8-byte aligned) that the call ADDS {blocks repaired, blocks left

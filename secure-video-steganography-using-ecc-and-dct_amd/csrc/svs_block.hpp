@@ -607,6 +607,34 @@ inline ChannelArgs make_channel_args(const uint16_t (&step)[64]) {
     return c;
 }
 
+// Per-coefficient QIM steps (include/svsdct.h svs_qim_steps) as the two exact kernels take them, by value: half k & 1 of
+// w[k >> 1] is delta[k] of flat row-major coefficient k, 1..4095 (entry 0, DC, is carried and never read).  on == 0: the kernel
+// as it was.  Read by the instantiations that hold the stepped side (svs_device.hpp); k is a compile-time index in their loops,
+// so a step is a scalar shift and mask of one kernel-argument dword and one scalar conversion, read where it is used.
+struct StepArgs {
+    uint32_t on;
+    uint32_t w[32];
+    SVS_HD float step(int k) const { return (float)((w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu); }
+    // The same value with the dword's index hidden from the compiler until this point, so that the dword is loaded HERE.  Left
+    // to itself the compiler loads all 32 at the kernel's entry and holds them: extract_exact_kernel then took 100 instead of
+    // 80 scalar registers.  (In embed_exact_kernel the hidden index sent a copy of the table to scratch: it reads step().)
+    SVS_HD float step_here(int k) const {
+        int i = k >> 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(i));
+#endif
+        return (float)((w[i] >> (16 * (k & 1))) & 0xFFFFu);
+    }
+};
+
+// host side: the steps of a checked table (every entry k >= 1 in 1..4095)
+inline StepArgs make_step_args(const uint16_t (&delta)[64]) {
+    StepArgs s{};
+    s.on = 1u;
+    for (int k = 1; k < 64; ++k) s.w[k >> 1] |= (uint32_t)delta[k] << (16 * (k & 1));
+    return s;
+}
+
 // host side: the table of `count` indices; false unless they are distinct and in 1..63 (count <= 63)
 inline bool make_coeff_table(const uint8_t *index, uint32_t count, CoeffTable *t) {
     for (int i = 0; i < 16; ++i) t->w[i] = 0xFFFFFFFFu;
@@ -1083,6 +1111,60 @@ SVS_HD void qim_exact_selected_dithered(pf::f32x2 (&D2)[4][8], const CoeffTable 
     if constexpr (K < 63) qim_exact_selected_dithered<QM, RULE, K + 1>(D2, sel, nb, hi, lo, qp, s_b);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-coefficient steps (svs_stepped_embed* / svs_stepped_extract*, include/svsdct.h): coefficient k is quantised with its own
+// step dk = (float)delta[k] instead of the call's delta.  A format, as the dither's: every float step is one IEEE float32
+// operation (build with -ffp-contract=off), in this order on host and device, whatever quantiser mode the holding kernel has:
+//   q = (int)rintf(c / dk)  (the division itself);  the value written for index t is (float)t * dk  (exact: |t dk| < 2^24)
+//   reference rule: force_parity;  SVS_NEAREST: nearest_parity with c0 = (float)q * dk;
+//   SVS_MINMOVE: the band of half-width r_k = max(0, 0.5f * dk - MARGIN[k]) around nearest_parity's lattice point
+//   dither: d = r * dk (dither_value with dk), the rule on c - d, moved back by d; a coefficient the rule leaves alone keeps c
+// With every delta[k] = D the values are those of the call with delta = D (quant_index's shortcut is the division's result by
+// construction, and (float)(0.5 * D) == 0.5f * D).
+// ---------------------------------------------------------------------------------------------------------------------
+template <int RULE>
+SVS_HD float stepped_target(float c, int bit, float dk, uint32_t k) {
+    const int q = quant_index_by_division(c, dk);
+    int t;
+    if constexpr (RULE == RULE_REFERENCE) {
+        t = force_parity(q, bit);
+    } else {
+        const float c0 = (float)q * dk;
+        const int dir = c > c0 ? 1 : (c < c0 ? -1 : 2 * bit - 1);
+        t = q + (((q ^ bit) & 1) ? dir : 0);
+    }
+    const float ct = (float)t * dk;
+    if constexpr (RULE == RULE_MINMOVE) return minmove_clamp(c, ct, fmaxf(0.0f, 0.5f * dk - minmove_margin(k)));
+    else return ct;
+}
+
+// ... under a dither (DITH), as dithered_target
+template <int RULE, bool DITH>
+SVS_HD float stepped_value(float c, int bit, float dk, uint32_t k, uint32_t s_b) {
+    if constexpr (DITH) {
+        const float d = dither_value(s_b, k, dk);
+        const float cp = c - d;
+        const float cn = stepped_target<RULE>(cp, bit, dk, k);
+        return __builtin_bit_cast(uint32_t, cn) == __builtin_bit_cast(uint32_t, cp) ? c : cn + d;
+    } else {
+        return stepped_target<RULE>(c, bit, dk, k);
+    }
+}
+
+// The selected loop with a step per coefficient (a recursion over K, as qim_exact_selected_dithered and for its reason).  `sel` is
+// never empty: the call's selection, or the prefix table of n_ac.  steps.step(K) is read here, behind the slot test.
+template <int RULE, bool DITH, int K = 1>
+SVS_HD void qim_stepped_selected(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb, uint32_t hi,
+                                 uint32_t lo, uint32_t s_b) {
+    const uint32_t s = sel.slot(K);
+    if (s < sel.count) {  // wave-uniform
+        const float c = D2[K >> 4][K & 7][(K >> 3) & 1];
+        const float cn = stepped_value<RULE, DITH>(c, (int)window_bit_at(hi, lo, s), steps.step(K), (uint32_t)K, s_b);
+        D2[K >> 4][K & 7][(K >> 3) & 1] = (s < nb) ? cn : c;
+    }
+    if constexpr (K < 63) qim_stepped_selected<RULE, DITH, K + 1>(D2, sel, steps, nb, hi, lo, s_b);
+}
+
 // The pocketfft-identical inverse of all 64 coefficients (vertical first, :168) into the block's row dwords; every byte is
 // overwritten (the input rows are dead).  RNE false: np.uint8(np.clip(v, 0, 255)), clip then truncate (:171) - the embed.
 // RNE true: round half to even, then saturate - what a decoder does (the requantisation channel).
@@ -1154,6 +1236,19 @@ SVS_HD void embed_block_exact(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n, 
     } else if (qp.kind == (uint32_t)RULE_MINMOVE) qim_exact_paired<U, QM, RULE_MINMOVE>(D2, n, nb, hi, lo, qp);
     else if (qp.kind == (uint32_t)RULE_NEAREST) qim_exact_paired<U, QM, RULE_NEAREST>(D2, n, nb, hi, lo, qp);
     else qim_exact_paired<U, QM, RULE_REFERENCE>(D2, n, nb, hi, lo, qp);
+    inverse_exact_paired<false>(D2, rx, ry);
+}
+
+// The same round trip with a step per coefficient (svs_stepped_embed*): the stepped loop in place of the quantiser's; `kind` is
+// a QimRuleKind, a constant on every side of the kernel's branch as QimRule::kind is.
+template <bool DITH>
+SVS_HD void embed_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb, uint32_t hi, uint32_t lo, uint32_t kind,
+                                const CoeffTable &sel, const StepArgs &steps, uint32_t s_b = 0u) {
+    pf::f32x2 D2[4][8];
+    forward_exact_paired(rx, ry, D2);
+    if (kind == (uint32_t)RULE_MINMOVE) qim_stepped_selected<RULE_MINMOVE, DITH>(D2, sel, steps, nb, hi, lo, s_b);
+    else if (kind == (uint32_t)RULE_NEAREST) qim_stepped_selected<RULE_NEAREST, DITH>(D2, sel, steps, nb, hi, lo, s_b);
+    else qim_stepped_selected<RULE_REFERENCE, DITH>(D2, sel, steps, nb, hi, lo, s_b);
     inverse_exact_paired<false>(D2, rx, ry);
 }
 
@@ -1871,6 +1966,38 @@ SVS_HD void extract_block_soft(const uint32_t (&rx)[8], const uint32_t (&ry)[8],
         }
         SVS_SCHED_FENCE();   // coefficient by coefficient: the bytes are independent, and scheduled together they spill
     }
+}
+
+// EXACT extract with a step per coefficient (svs_stepped_extract*): the parity of rintf((c - d) / dk), d = 0 without a dither.
+// `sel` is never empty (the call's selection or the prefix table of n_ac).  A recursion over K, as qim_stepped_selected.
+template <bool DITH, int K = 1>
+SVS_HD void stepped_parities(const float (&D)[8][8], const CoeffTable &sel, const StepArgs &steps, uint32_t &hi, uint32_t &lo,
+                             uint32_t s_b) {
+    const uint32_t s = sel.slot(K);
+    if (s < sel.count) {  // wave-uniform
+        const float dk = steps.step_here(K);
+        float x = D[K >> 3][K & 7];
+        if constexpr (DITH) x = x - dither_value(s_b, (uint32_t)K, dk);
+        const uint32_t bit = ((uint32_t)quant_index_by_division(x, dk) & 1u) << ((31u - s) & 31u);
+        if (s < 32u) hi |= bit;
+        else lo |= bit;
+    }
+    if constexpr (K < 63) stepped_parities<DITH, K + 1>(D, sel, steps, hi, lo, s_b);
+}
+
+template <bool DITH>
+SVS_HD void extract_block_stepped(const uint32_t (&rx)[8], const uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps,
+                                  uint32_t &hi, uint32_t &lo, uint32_t s_b = 0u) {
+    float D[8][8];
+    forward_exact(rx, ry, D);
+    // the 63 AC coefficients are computed HERE, as in extract_block_soft and for its reason (SVS_PIN_COEFFICIENTS); DC is never read
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int k = 1; k < 64; ++k) asm volatile("" : "+v"(D[k >> 3][k & 7]));
+#endif
+    hi = 0;
+    lo = 0;
+    stepped_parities<DITH>(D, sel, steps, hi, lo, s_b);
 }
 
 inline int rows_for(int n) { return (n >> 3) + 1; }  // coefficient rows holding flat indices 1..n

@@ -206,9 +206,9 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
                 constexpr int U = decltype(u)::value;
                 if (p.keyed)
                     return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g,
-                                  p.qp, bits, p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{}, ord);
+                                  p.qp, bits, p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{}, t.steps, ord);
                 return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{});
+                              p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{}, t.steps);
             });
         if (p.rows == 2) {   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
             if (p.keyed)
@@ -238,7 +238,8 @@ int launch_requantise(uint64_t total, hipStream_t st, const uint8_t *in, uint8_t
     g.n_ac = 0;
     g.xcd_chunk = svs::kEighth;
     return launch(svs::embed_exact_kernel<svs::QM_DOUBLE, 8>, grid_for(total), 0, st, in, out, g, svs::QimParams{},
-                  static_cast<const uint32_t *>(nullptr), (uint64_t)0, (uint64_t)0, (uint32_t)0, svs::CoeffTable{}, svs::DitherArgs{}, chan);
+                  static_cast<const uint32_t *>(nullptr), (uint64_t)0, (uint64_t)0, (uint32_t)0, svs::CoeffTable{}, svs::DitherArgs{}, chan,
+                  svs::StepArgs{});
 }
 
 // SVS_READBACK: readback_kernel<rows, QM> over the stego planes the embed has just written, on the same stream, with the
@@ -333,9 +334,9 @@ int launch_extract(const svs::ExtractPlan &p, uint64_t total, hipStream_t st, co
                 constexpr int U = decltype(r)::value;
                 if (p.keyed)
                     return launch(svs::extract_exact_kernel<U, QM, 1, true, svs::BlockOrderArgs>, grid_for(total), soft_lds_bytes(p), st,
-                                  gray, g, p.qp, out, out_bytes, t.sel, t.dith, t.soft, ord);
+                                  gray, g, p.qp, out, out_bytes, t.sel, t.dith, t.soft, t.steps, ord);
                 return launch(svs::extract_exact_kernel<U, QM>, grid_for(total), soft_lds_bytes(p), st, gray, g, p.qp, out, out_bytes,
-                              t.sel, t.dith, t.soft);
+                              t.sel, t.dith, t.soft, t.steps);
             });
         if (p.keyed)
             return dispatch<2, 3, 4, 5, 6, 7, 8>(p.rows, [&](auto r) {
@@ -756,12 +757,13 @@ struct GrayOptions {
     uint64_t *d_counts = nullptr;              // the read-back calls, device: {repaired, unrepaired}, added to
     svs_readback_counts *counts = nullptr;     // the read-back calls, host: the counts of the whole call
     ExtractOutput out;                         // the extract calls: what the call writes (the soft calls: not the packed bits)
+    const svs::StepArgs *steps = nullptr;      // the stepped calls: the checked table in the kernels' form
 
     // the kernels' forms, for a batch of g's blocks per frame (derived once per call)
     svs::KernelOptions kernel_forms(const svs::Geometry &g) const {
         return {order ? svs::make_block_order(order->key, order->first_frame, g.by_bpf.div) : svs::BlockOrderArgs{}, coeffs,
                 dither ? svs::DitherArgs{svs::dither_seed(dither->key), dither->first_frame, 1u, svs::CoeffTable{}} : svs::DitherArgs{},
-                out.period, out.stream_bit0};
+                out.period, out.stream_bit0, steps ? *steps : svs::StepArgs{}};
     }
 
     // the routing arguments of the call (the one place that fills them from the options)
@@ -774,6 +776,7 @@ struct GrayOptions {
         ra.soft = out.kind == ExtractOutput::SOFT;
         ra.vote = out.kind == ExtractOutput::VOTE;
         ra.hist = out.kind == ExtractOutput::HIST;
+        ra.stepped = steps != nullptr;
         return ra;
     }
 
@@ -859,6 +862,27 @@ int with_options(const OptionsPolicy &pol, const svs_block_order *order, const s
     }
     if (flags & ~pol.allowed) return fail(SVS_ERR_INVALID_ARG, "flags 0x%x: %s", flags, pol.what);
     return call(n_ac, o);
+}
+
+// The stepped calls are the dithered calls with each of order, coeffs and dither optional and the table in place of delta: the
+// table is checked first, then what with_options checks, then the call runs as every gray call does - with a positive delta
+// that routes it and that no kernel reads (svs_route.hpp RouteArgs::stepped).
+constexpr OptionsPolicy kSteppedEmbed{false, false, kSelectEmbedFlags, "a stepped embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE"};
+constexpr OptionsPolicy kSteppedExtract{false, false, kModeFlags, "a stepped extract takes the mode bits only"};
+constexpr double kSteppedRouteDelta = 1.0;
+
+template <class Call>
+int with_steps(const OptionsPolicy &pol, const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither,
+                      const svs_qim_steps *steps, uint32_t flags, int n_ac, Call &&call) {
+    if (!steps) return fail(SVS_ERR_INVALID_ARG, "steps is NULL");
+    for (int k = 1; k < 64; ++k)
+        if (steps->delta[k] < 1 || steps->delta[k] > 4095)
+            return fail(SVS_ERR_INVALID_ARG, "delta[%d] = %u is not in 1..4095", k, (unsigned)steps->delta[k]);
+    const svs::StepArgs table = svs::make_step_args(steps->delta);
+    return with_options(pol, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
+        o.steps = &table;
+        return call(n, o);
+    });
 }
 
 int check_extract_flags(uint32_t flags) {
@@ -1402,6 +1426,60 @@ int svs_embed_dithered_readback(const uint8_t *gray, uint8_t *stego, const svs_p
         o.counts = counts ? counts : &none;
         return embed_host(gray, stego, nullptr, planes, delta, n, bits_packed, nullptr, bit_offset, n_bits, flags | SVS_READBACK,
                           n_embedded, o);
+    });
+}
+
+// ---- per-coefficient QIM steps (include/svsdct.h) -------------------------------------------------------------------------
+int svs_matched_steps(svs_qim_steps *out, const svs_steps *codec, int multiple, int floor) {
+    if (!out) return fail(SVS_ERR_INVALID_ARG, "out is NULL");
+    if (!codec) return fail(SVS_ERR_INVALID_ARG, "codec is NULL");
+    if (multiple < 1 || multiple > 16) return fail(SVS_ERR_INVALID_ARG, "multiple %d is not in 1..16", multiple);
+    if (floor < 0 || floor > 4095) return fail(SVS_ERR_INVALID_ARG, "floor %d is not in 0..4095", floor);
+    svs_qim_steps t{};
+    for (int k = 0; k < 64; ++k) {   // the codec table is checked as svs_requantise checks it, DC included
+        const int s = codec->step[k];
+        if (s < 1 || s > 255) return fail(SVS_ERR_INVALID_ARG, "step[%d] = %d is not in 1..255", k, s);
+        if (k == 0) continue;
+        const int need = (floor + s - 1) / s;   // ceil(floor / s)
+        const int d = s * (multiple > need ? multiple : need);
+        if (d > 4095) return fail(SVS_ERR_INVALID_ARG, "delta[%d] = %d exceeds 4095", k, d);
+        t.delta[k] = (uint16_t)d;
+    }
+    *out = t;
+    return SVS_OK;
+}
+
+int svs_stepped_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                          const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                          const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                          uint64_t *n_embedded, void *stream) {
+    return with_steps(kSteppedEmbed, order, coeffs, dither, steps, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return embed_dev(d_gray, d_stego, planes, kSteppedRouteDelta, n, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream, o);
+    });
+}
+
+int svs_stepped_embed(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                      const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                      const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
+    return with_steps(kSteppedEmbed, order, coeffs, dither, steps, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return embed_host(gray, stego, nullptr, planes, kSteppedRouteDelta, n, bits_packed, nullptr, bit_offset, n_bits, flags,
+                          n_embedded, o);
+    });
+}
+
+int svs_stepped_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                            const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint8_t *d_bits_packed_out,
+                            uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream) {
+    return with_steps(kSteppedExtract, order, coeffs, dither, steps, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return extract_dev(d_gray, planes, kSteppedRouteDelta, n, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, o);
+    });
+}
+
+int svs_stepped_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                        const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint8_t *bits_packed_out,
+                        uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
+    return with_steps(kSteppedExtract, order, coeffs, dither, steps, flags, n_ac, [&](int n, const GrayOptions &o) {
+        return extract_host(gray, planes, kSteppedRouteDelta, n, bits_packed_out, out_capacity_bytes, flags, n_bits_out, o);
     });
 }
 

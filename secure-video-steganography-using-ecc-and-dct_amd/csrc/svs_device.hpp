@@ -345,7 +345,7 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
                                                           const uint64_t bit_offset, const uint64_t n_bits,
                                                           const uint32_t n_words, const CoeffTable sel,
                                                           const DitherArgs dith, const ChannelArgs chan,
-                                                          const Order... order) {
+                                                          const StepArgs steps, const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     // The requantisation channel (svs_requantise_dev; chan.on): a wave-uniform branch around everything else, compiled into ONE
     // instantiation - the unkeyed eight-row QM_DOUBLE one, which otherwise serves only calls whose delta is no float32 value
@@ -377,7 +377,12 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
     // second such branch: `table` is a compile-time NULL on the side without one, which is the body as it was.
     // A keyed dither (dith.on; the U = 8 instantiations only - svs_route.hpp plans no other for one) is a third: `dithered` is a
     // compile-time false on every side that was there before, which keeps its code; the dithered side has its own three copies.
-    const auto body = [&](const QimRule qp, const CoeffTable *table, auto dithered) __attribute__((always_inline)) {
+    // Per-coefficient steps (steps.on; svs_stepped_embed_dev) are a fourth, compiled into the two eight-row QM_DOUBLE
+    // instantiations alone, which otherwise serve only calls whose delta is no float32 value (the stepped arithmetic is the
+    // float32 one whatever QM says; svs_route.hpp plans no other instantiation for a stepped call).  `stepped` is a compile-time
+    // false on every side that was there before.  The stepped side reads its table from the dither's copy, on or off, as the
+    // dithered side does: the call's selection or the prefix table of n_ac.
+    const auto body = [&](const QimRule qp, const CoeffTable *table, auto dithered, auto stepped) __attribute__((always_inline)) {
         const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
         if (gblock >= g.total_blocks) return;
         const int64_t off = block_offset(gblock, g);
@@ -394,7 +399,11 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
         for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
         uint32_t hi, lo;
         payload_window(bits, n_words, bit_offset + first, hi, lo);
-        if constexpr (decltype(dithered)::value)
+        if constexpr (decltype(stepped)::value) {
+            uint32_t s_b = 0u;
+            if constexpr (decltype(dithered)::value) s_b = dither_seed_of(gblock, g, dith);
+            embed_block_stepped<decltype(dithered)::value>(ax, ay, block_budget(first, n_bits, n), hi, lo, qp.kind, *table, steps, s_b);
+        } else if constexpr (decltype(dithered)::value)
             embed_block_exact<U, QM, true>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp, false, table,
                                            dither_seed_of(gblock, g, dith));
         else
@@ -404,24 +413,40 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
         store_rows<1>(stego + off, g.row_pitch, v);
     };
     constexpr std::false_type plain{};
-    if constexpr (U == 8) {
-        if (dith.on) {     // wave-uniform; `sel` is the call's selection or the prefix table of n_ac: one selected loop serves both
-            constexpr std::true_type dithered{};
-            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &dith.sel, dithered);
-            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered);
-            else body(QimRule(qp, 0u), &dith.sel, dithered);
-            return;
-        }
-        if (sel.count) {   // Geometry::n_ac == sel.count: the stream ranges and the block budget are those of n_ac slots
-            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &sel, plain);
-            else if (g.pad) body(QimRule(qp, 1u), &sel, plain);
-            else body(QimRule(qp, 0u), &sel, plain);
+    if constexpr (QM == QM_DOUBLE && U == 8) {
+        if (steps.on) {    // wave-uniform
+            constexpr std::true_type stepped{};
+            if (dith.on) {
+                constexpr std::true_type dithered{};
+                if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, dithered, stepped);
+                else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered, stepped);
+                else body(QimRule(qp, 0u), &dith.sel, dithered, stepped);
+                return;
+            }
+            if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, plain, stepped);
+            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, plain, stepped);
+            else body(QimRule(qp, 0u), &dith.sel, plain, stepped);
             return;
         }
     }
-    if (g.pad > 1u) body(rule_from_word(qp, g.pad), nullptr, plain);
-    else if (g.pad) body(QimRule(qp, 1u), nullptr, plain);
-    else body(QimRule(qp, 0u), nullptr, plain);
+    if constexpr (U == 8) {
+        if (dith.on) {     // wave-uniform; `sel` is the call's selection or the prefix table of n_ac: one selected loop serves both
+            constexpr std::true_type dithered{};
+            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &dith.sel, dithered, plain);
+            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered, plain);
+            else body(QimRule(qp, 0u), &dith.sel, dithered, plain);
+            return;
+        }
+        if (sel.count) {   // Geometry::n_ac == sel.count: the stream ranges and the block budget are those of n_ac slots
+            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &sel, plain, plain);
+            else if (g.pad) body(QimRule(qp, 1u), &sel, plain, plain);
+            else body(QimRule(qp, 0u), &sel, plain, plain);
+            return;
+        }
+    }
+    if (g.pad > 1u) body(rule_from_word(qp, g.pad), nullptr, plain, plain);
+    else if (g.pad) body(QimRule(qp, 1u), nullptr, plain, plain);
+    else body(QimRule(qp, 0u), nullptr, plain, plain);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1003,7 +1028,8 @@ template <int U, int QM, int BPL = 1, bool KEYED = false, class... Order>   // B
 __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(const uint8_t *__restrict__ gray, const Geometry g,
                                                             const QimParams qp, uint8_t *__restrict__ out,
                                                             const uint64_t out_bytes, const CoeffTable sel,
-                                                            const DitherArgs dith, const SoftArgs soft, const Order... order) {
+                                                            const DitherArgs dith, const SoftArgs soft, const StepArgs steps,
+                                                            const Order... order) {
     static_assert(BPL == 1, "one block per lane");
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t flags[SVS_WG / 64][SVS_WAVE_BITS_DWORDS(1)];
@@ -1054,7 +1080,10 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
     // around the whole body, as in embed_exact_kernel; `dithered` is a compile-time false on the side that was there before.
     // (The dithered forms as two more alternatives beside the selection's branch, sharing the loads and the tail, took 136
     // instead of 77 VGPRs and three waves per SIMD from the calls without a dither.)
-    const auto body = [&](auto dithered) __attribute__((always_inline)) {
+    // Per-coefficient steps (steps.on; svs_stepped_extract_dev) are one more such side, compiled into the two eight-row QM_POW2
+    // instantiations alone (svs_route.hpp plans no other for a stepped call; the GUI's delta = 20 runs the QM_F32 ones).  Its
+    // table is `sel`, never empty: the call's selection or the prefix table of n_ac.
+    const auto body = [&](auto dithered, auto stepped) __attribute__((always_inline)) {
         constexpr bool DITH = decltype(dithered)::value;
         const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
         const uint32_t tile = tile_id(g.xcd_chunk);
@@ -1070,7 +1099,11 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
             // a coefficient selection (U = 8 only; n == sel.count): one wave-uniform branch around the block's arithmetic
             bool selected = false;
             if constexpr (U == 8) selected = sel.count != 0;
-            if constexpr (DITH) {
+            if constexpr (decltype(stepped)::value) {
+                uint32_t s_b = 0u;
+                if constexpr (DITH) s_b = dither_seed_of(gblock, g, dith);
+                extract_block_stepped<DITH>(ax, ay, sel, steps, hi, lo, s_b);
+            } else if constexpr (DITH) {
                 // the prefix form and the selected form, as on the side without a dither
                 const uint32_t s_b = dither_seed_of(gblock, g, dith);
                 if (selected) extract_block_exact_selected<QM, true>(ax, ay, sel, qp, hi, lo, s_b);
@@ -1084,13 +1117,20 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
         if constexpr (!KEYED)
             emit_wave_bits<U, 1>(&flags[wave][0], lane, (uint64_t)tile * (uint32_t)SVS_WG + wave * 64u, n, hi, lo, 0u, 0u, out, out_bytes);
     };
-    if constexpr (U == 8) {
-        if (dith.on) {     // wave-uniform
-            body(std::true_type{});
+    if constexpr (U == 8 && QM == QM_POW2) {
+        if (steps.on) {    // wave-uniform
+            if (dith.on) body(std::true_type{}, std::true_type{});
+            else body(std::false_type{}, std::true_type{});
             return;
         }
     }
-    body(std::false_type{});
+    if constexpr (U == 8) {
+        if (dith.on) {     // wave-uniform
+            body(std::true_type{}, std::false_type{});
+            return;
+        }
+    }
+    body(std::false_type{}, std::false_type{});
 }
 
 // ---------------------------------------------------------------------------------------

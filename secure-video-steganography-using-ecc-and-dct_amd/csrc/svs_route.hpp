@@ -44,6 +44,10 @@ struct RouteArgs {
     // a histogram call (svs_soft_histogram*): a soft call whose bytes are counted per frame instead of written (SoftArgs::hist);
     // never keyed - the counts of a frame do not depend on an order
     bool hist = false;
+    // per-coefficient steps (svs_stepped_embed* / svs_stepped_extract*; gray calls only): the lane-per-block exact kernels with
+    // all eight coefficient rows in every mode, in the instantiations that hold the stepped side (svs_device.hpp) - QM_DOUBLE
+    // for an embed, QM_POW2 for an extract - whatever `delta` says; the callers pass a positive one, and no kernel reads it
+    bool stepped = false;
 };
 
 inline bool route_selected(const RouteArgs &a) {
@@ -76,6 +80,7 @@ struct EmbedPlan {
     uint64_t bit_offset, n_bits, n_words;   // the kernel's payload arguments; n_words >= 2^32: too large for one call
     bool selected;            // the launch passes the call's CoeffTable (EXACT with rows = 8 only), else an empty one
     bool dithered;            // the launch switches the exact kernel's dithered side on (EXACT with rows = 8 only)
+    bool stepped = false;     // the launch passes the call's StepArgs (EXACT with rows = 8 and QM_DOUBLE only), else an empty one
 };
 
 // Which kernel family (include/svsdct.h `flags`).  The streaming kernels cover one and two coefficient rows (n <= 15) inside the
@@ -88,14 +93,14 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
     p.use = a.n_bits < cap ? a.n_bits : cap;
     if (!(a.delta > 0.0) || n == 0) p.use = 0;   // nothing can be embedded (config_and_setup.py:143-145)
     const bool selected = route_selected(a);
-    const int rows = selected || a.dithered ? 8 : rows_for((int)n);
+    const int rows = selected || a.dithered || a.stepped ? 8 : rows_for((int)n);
     const bool in_range = a.delta >= SVS_GUARD_DELTA_MIN && a.delta <= SVS_GUARD_DELTA_MAX;
     const bool streaming = p.use > 0 && in_range && !a.pocketfft && rows <= 2 && !(a.guarded_off && !a.bgr);   // never selected or dithered: rows = 8
     p.xcd_chunk = kEighth;
     const int qm = make_qim(p.use == 0 ? 1.0 : a.delta, &p.qp);
     if (p.use > 0) {
         p.path = streaming ? EmbedPath::STREAMING : EmbedPath::EXACT;
-        p.qm = qm;
+        p.qm = a.stepped ? (int)QM_DOUBLE : qm;   // stepped: the holder of the stepped side, whose arithmetic reads no QimParams
         p.n_ac = n;
         p.bit_offset = a.bit_offset;
         p.n_bits = p.use;
@@ -111,6 +116,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.half_cell = a.minmove ? (float)(0.5 * a.delta) : 0.0f;
         p.selected = selected;                // likewise: the other paths touch no coefficient
         p.dithered = a.dithered;              // likewise (EXACT with rows = 8)
+        p.stepped = a.stepped;                // likewise (EXACT with rows = 8, never STREAMING: rows = 8)
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;
@@ -148,6 +154,7 @@ struct ExtractPlan {
     bool vote = false;        // soft, and the launch switches the soft side's vote tail on: `out` is the tally (never ZEROS)
     bool hist = false;        // soft, and the launch switches the soft side's histogram tail on: `out` is n_frames * 256 uint32
                               // counts, added to; the launch requests 256 more dwords of dynamic LDS (never ZEROS, never keyed)
+    bool stepped = false;     // the launch passes the call's StepArgs (EXACT with rows = 8 and QM_POW2; never ZEROS, never FAST)
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -165,9 +172,10 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     }
     p.selected = route_selected(a);
     p.dithered = a.dithered;
-    p.rows = p.selected || p.dithered || p.soft ? 8 : rows_for((int)a.n_ac);
+    p.stepped = a.stepped;
+    p.rows = p.selected || p.dithered || p.soft || p.stepped ? 8 : rows_for((int)a.n_ac);
     p.xcd_chunk = p.rows == 1 ? 32u : (p.rows == 2 && !a.bgr ? 0u : kEighth);
-    p.qm = make_qim(a.delta, &p.qp) == QM_POW2 ? QM_POW2 : QM_F32;
+    p.qm = make_qim(a.delta, &p.qp) == QM_POW2 || p.stepped ? QM_POW2 : QM_F32;   // stepped: the holder of the stepped side
     const float t = a.tie_scale;
     p.qp.tie_slope *= t; p.qp.tie2_sum *= t; p.qp.tie2_resid *= t; p.qp.tie2_c00 *= t; p.qp.tie2_max *= t;
     // GUARDED = FAST inside the guard's delta range (n >= 8: 0.86 instead of 1.03 ms per 600 x 4K at n = 10), the
@@ -178,7 +186,7 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     // the FAST kernels with two and more rows round c / delta by adding 1.5 * 2^23, which needs |c / delta| < 2^22.  With one
     // row the pocketfft-identical forward costs 0.2-3 % (the kernel stays HBM-bound; profiles/history/r01_ab_quant_exact.txt),
     // so FAST mode uses it too; with more rows it costs ~17 % and stays opt-in.
-    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected || p.dithered || p.soft) exact = true;
+    if ((double)p.qp.delta_f < SVS_FAST_EXTRACT_DELTA_MIN || p.rows == 1 || p.selected || p.dithered || p.soft || p.stepped) exact = true;
     p.path = exact ? ExtractPath::EXACT : ExtractPath::FAST;
     p.keyed = a.keyed && !a.hist;
     return p;
@@ -193,21 +201,24 @@ struct KernelOptions {
     const CoeffTable *coeffs;
     DitherArgs dith;
     uint64_t vote_period = 0, vote_bit0 = 0;   // a vote call: the payload length in bits and the call's first stream position
+    StepArgs steps{};                          // a stepped call: its table (on = 1), else empty
 };
 
 struct LaunchTables {   // the `sel` and `dith` arguments of the two exact kernels, and extract_exact_kernel's `soft`
     CoeffTable sel;
     DitherArgs dith;
     SoftArgs soft;
+    StepArgs steps{};   // the `steps` argument of the two exact kernels: the call's where the plan is stepped, else empty
 };
 
 // embed_exact_kernel: `sel` is the call's selection where the plan is selected, else empty (count 0: the row-major prefix).  The
 // dither is on only where the plan says so (EXACT, rows = 8); the dithered side runs the selected loop alone, with the prefix
-// table of n_ac where the call has no selection.
+// table of n_ac where the call has no selection.  The stepped side reads that table too, with the dither on or off.
 inline LaunchTables embed_tables(const EmbedPlan &p, const KernelOptions &k) {
     const CoeffTable sel = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
     return {sel, {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u,
-                  !p.dithered ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)}};
+                  !(p.dithered || p.stepped) ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)},
+            SoftArgs{}, p.stepped ? k.steps : StepArgs{}};
 }
 
 // readback_kernel's keyed form (a selected or dithered plan): one table, the call's selection or the prefix table of n_ac
@@ -218,14 +229,17 @@ inline DitherArgs readback_tables(const EmbedPlan &p, const KernelOptions &k) {
 // extract_exact_kernel reads the selection from `sel` on either hard side: their dither carries no table.  The soft side runs
 // the selected loop alone and reads its own copy from the dither's table, never empty: the call's selection, or the prefix
 // table of n_ac (as embed_exact_kernel's dithered side)
+// The stepped side runs the selected loop alone and reads it from `sel`: the call's selection, or the prefix table of n_ac.
 inline LaunchTables extract_tables(const ExtractPlan &p, const KernelOptions &k) {
-    const CoeffTable sel = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
+    const CoeffTable own = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
+    const CoeffTable sel = p.stepped && !own.count ? make_prefix_table(p.n_ac) : own;
     return {sel,
             {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, !p.soft ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)},
             !p.soft  ? SoftArgs{}
             : p.vote ? make_vote_args(make_soft_args(p.qp.delta_f, p.n_ac), k.vote_period, k.vote_bit0)
             : p.hist ? make_hist_args(make_soft_args(p.qp.delta_f, p.n_ac))
-                     : make_soft_args(p.qp.delta_f, p.n_ac)};
+                     : make_soft_args(p.qp.delta_f, p.n_ac),
+            p.stepped ? k.steps : StepArgs{}};
 }
 
 }  // namespace svs

@@ -23,6 +23,7 @@ from svsdct import coeffs as _coeffs
 from svsdct import dither as _dither
 from svsdct import framing as _framing
 from svsdct import order as _order
+from svsdct import steps as _steps
 from svsdct.pipeline import FramePipeline, SlotFeeder, read_ahead
 
 BATCH_FRAMES = int(os.environ.get("SVS_BATCH_FRAMES", "32"))
@@ -81,6 +82,13 @@ MINMOVE = os.environ.get("SVS_MINMOVE", "0") == "1"
 # host-conversion gray path runs); refused together with SVS_KEEP_COLOUR, SVS_READBACK and SVS_READBACK_COLOUR (a dithered call
 # has no colour form; its read-back is SVS_READBACK_KEYED=1).  Allowed with SVS_BLOCK_KEY, SVS_COEFFS, SVS_NEAREST and
 # SVS_MINMOVE.
+# SVS_STEPS (read per call, opt-in): per-coefficient QIM steps (svsdct/steps.py, include/svsdct.h) - `q<quality>x<multiple>`,
+# optionally `f<floor>` (q75x2, q95x2f16: the steps of an 8x8 intra codec at that quality times the multiple, none below the
+# floor), or 64 comma-separated integers.  Coefficient k is quantised with its own step and DELTA is not used; a lattice point of
+# a matched table passes that codec's requantiser unchanged.  Unset: today's bytes and routes.  The receiver must set the same
+# value.  The gray path only (with SVS_FUSED_COLOUR the host-conversion gray path runs); refused together with SVS_KEEP_COLOUR,
+# SVS_READBACK, SVS_READBACK_COLOUR and SVS_READBACK_KEYED (a stepped call has no colour and no read-back form).  Allowed with
+# SVS_BLOCK_KEY, SVS_COEFFS, SVS_DITHER_KEY, SVS_NEAREST and SVS_MINMOVE.
 
 
 def _keyed(block_key=None, dither_key=None, **kw):
@@ -163,6 +171,15 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     except (TypeError, ValueError) as exc:
         print(f"    Error: SVS_DITHER_KEY tidak valid ({exc}).")
         return False, None, None
+    try:
+        tabel_langkah = _steps.from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"    Error: SVS_STEPS tidak valid ({exc}).")
+        return False, None, None
+    if tabel_langkah is not None and (KEEP_COLOUR or READBACK or READBACK_COLOUR or READBACK_KEYED):
+        print("    Error: SVS_STEPS tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK, SVS_READBACK_COLOUR atau "
+              "SVS_READBACK_KEYED.")
+        return False, None, None
     if kunci_dither is not None and (KEEP_COLOUR or READBACK or READBACK_COLOUR):
         print("    Error: SVS_DITHER_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK atau SVS_READBACK_COLOUR.")
         return False, None, None
@@ -212,7 +229,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
 
     tabel_warna = None
     if (FUSED_COLOUR or KEEP_COLOUR or READBACK_COLOUR) and kunci_blok is None and pilihan is None and kunci_dither is None \
-            and not READBACK_KEYED:   # keyed order, selection, dither, keyed read-back: the host-conversion gray path
+            and not READBACK_KEYED and tabel_langkah is None:   # keyed order, selection, dither, keyed read-back, steps: the host-conversion gray path
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -226,7 +243,8 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if jaga_warna:
         print("    Info: warna video sampul dipertahankan.")
     per_frame = _batch.capacity_bits(1, out_h, out_w, num_ac_coeffs)
-    usable = per_frame if delta_kuantisasi > 0 else 0              # nothing can be embedded otherwise (:143-145)
+    # nothing can be embedded at delta <= 0 (:143-145) - unless a step table replaces delta
+    usable = per_frame if delta_kuantisasi > 0 or tabel_langkah is not None else 0
     state = {"disisipkan": 0, "frame_num": 0, "first": None}
     if NEAREST:
         print("    Info: paritas koefisien dipaksa ke titik kisi terdekat (SVS_NEAREST).")
@@ -240,6 +258,9 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if kunci_dither is not None:
         print("    Info: kisi kuantisasi digeser dengan dither berkunci (SVS_DITHER_KEY).")
         terdekat = dict(terdekat, dither_key=kunci_dither)         # likewise
+    if tabel_langkah is not None:
+        print("    Info: langkah kuantisasi per koefisien dipakai (SVS_STEPS); DELTA tidak dipakai.")
+        terdekat = dict(terdekat, steps=tabel_langkah)             # likewise
     readback_abu = READBACK or (READBACK_COLOUR and not tabel_warna)   # the gray pipeline's read-back
     rb_pipa = {"readback_keyed": True} if READBACK_KEYED else ({"readback": True} if readback_abu else {})
 

@@ -21,6 +21,7 @@ from svsdct import coeffs as _coeffs
 from svsdct import dither as _dither
 from svsdct import framing as _framing
 from svsdct import order as _order
+from svsdct import steps as _steps
 from svsdct.pipeline import FramePipeline, SlotFeeder
 
 BATCH_FRAMES = int(os.environ.get("SVS_BATCH_FRAMES", "32"))
@@ -34,6 +35,8 @@ FUSED_COLOUR = os.environ.get("SVS_FUSED_COLOUR", "0") == "1"
 # SVS_COEFFS (read per call): the sender's payload coefficient selection (embed_process.py); likewise the gray path.
 # SVS_DITHER_KEY (read per call): the sender's dither key (embed_process.py); frame k of the video is clip frame k; likewise
 # the gray path.  Unset: the loops take exactly the routes they take without it.
+# SVS_STEPS (read per call): the sender's per-coefficient QIM steps (embed_process.py); DELTA is then not used; likewise the gray
+# path.
 
 
 def _cv2():
@@ -48,7 +51,7 @@ def _gagal(pesan, cap=None):
     return False
 
 
-def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0, coeffs=None, dither_key=None):
+def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0, coeffs=None, dither_key=None, steps=None):
     if tabel_warna:                                            # frames are colour: convert + extract in one kernel
         packed, n_bits = _batch.extract_bgr_frames(np.stack(frames), delta, n_ac, weights=tabel_warna)
     else:
@@ -57,6 +60,8 @@ def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first
             keyed["coeffs"] = coeffs
         if dither_key is not None:
             keyed.update(dither_key=dither_key, first_frame=first_frame)
+        if steps is not None:
+            keyed["steps"] = steps
         packed, n_bits = _batch.extract_frames(np.stack(frames), delta, n_ac, **keyed)
     return np.unpackbits(packed, count=n_bits)
 
@@ -84,6 +89,14 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
     except (TypeError, ValueError) as exc:
         print(f"  Error: SVS_DITHER_KEY tidak valid ({exc}).")
         return False
+    try:
+        tabel_langkah = _steps.from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"  Error: SVS_STEPS tidak valid ({exc}).")
+        return False
+    if tabel_langkah is not None:
+        print("  Info: langkah kuantisasi per koefisien dipakai (SVS_STEPS); DELTA tidak dipakai.")
+    langkah = {} if tabel_langkah is None else {"steps": tabel_langkah}
     cv2 = _cv2()
     cap = cv2.VideoCapture(path_stego_video)
     if not cap.isOpened():
@@ -97,7 +110,8 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
         return False
     per_frame = _batch.capacity_bits(1, h, w, num_ac_coeffs)
     tabel_warna = None
-    if FUSED_COLOUR and kunci_blok is None and pilihan is None and kunci_dither is None:   # keyed order, selection, dither: the host-conversion gray path
+    if FUSED_COLOUR and kunci_blok is None and pilihan is None and kunci_dither is None and tabel_langkah is None:
+        # (a keyed order, a selection, a dither, a step table: the host-conversion gray path)
         from svsdct import colour as _colour
         try:
             tabel_warna = _colour.weights_matching_cv2(cv2)
@@ -122,7 +136,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
             return False
         print(f"    Mengekstrak bit dari frame video ke-{frame_num}...")
         bits = _extract_frames([gray], delta_kuantisasi, num_ac_coeffs, tabel_warna, kunci_blok, frame_num - 1, pilihan,
-                               **({} if kunci_dither is None else {"dither_key": kunci_dither}))
+                               **({} if kunci_dither is None else {"dither_key": kunci_dither}), **langkah)
         if bits.size == 0:
             print(f"  Error: Tidak ada bit diekstrak dari frame ke-{frame_num}.")
             cap.release()
@@ -181,7 +195,7 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
                                mode=_batch.host_level_mode(),
                                **({} if kunci_blok is None else {"block_key": kunci_blok}),
                                **({} if pilihan is None else {"coeffs": pilihan}),
-                               **({} if kunci_dither is None else {"dither_key": kunci_dither})) as pipe:
+                               **({} if kunci_dither is None else {"dither_key": kunci_dither}), **langkah) as pipe:
                 rencana = {"lagi": lagi}
 
                 def isi(slot):

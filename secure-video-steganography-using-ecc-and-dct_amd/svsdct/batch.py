@@ -26,6 +26,7 @@ from . import channel as _channel
 from . import coeffs as _coeffs
 from . import dither as _dither
 from . import native
+from . import steps as _steps
 from . import soft as _soft
 from .hostmem import pinned_empty
 from .native import BlockOrder, Dither, Planes
@@ -242,9 +243,28 @@ def _gray_call(lib, verb, call: _GrayCall, front, delta, n_ac, back, counts=None
     native.check(getattr(lib, name)(*args), name)
 
 
+def _steps_arg(steps, readback=False, readback_keyed=False):
+    """steps= of the gray calls -> struct svs_qim_steps, None for None; every ValueError it can cause is raised here, before the
+    library is loaded (a stepped call has no read-back form)"""
+    if steps is None:
+        return None
+    if readback or readback_keyed:
+        raise ValueError("per-coefficient steps have no read-back form: drop readback / readback_keyed or steps")
+    return _steps.steps_struct(steps)
+
+
+def _stepped_call(lib, verb, call: _GrayCall, steps, front, n_ac, back, stream=()) -> None:
+    """svs_stepped_<verb>(*front, order, coeffs, dither, steps, n_ac, *back), or with stream = (handle,) its _dev form with the
+    stream last; raises unless it returns SVS_OK.  The call's delta is not an argument: the table replaces it."""
+    name = f"svs_stepped_{verb}" + ("_dev" if stream else "")
+    args = [*front, _ref(call.order), _ref(call.sel), _ref(call.dith), C.byref(steps), int(n_ac), *back, *stream]
+    native.check(getattr(lib, name)(*args), name)
+
+
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
-                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False):
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
+                 steps=None):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
@@ -273,7 +293,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     readback_keyed : opt-in (svs_embed_dithered_readback, include/svsdct.h): the read-back and repair under coeffs and / or
     dither_key - every payload block is read back with the selected / dithered extraction's own verdict and repaired where it
     fails.  With neither it makes the readback call.  ValueError together with readback.
+    steps : None, or a table of 64 per-coefficient QIM steps (opt-in, svsdct/steps.py: steps.matched(75), steps.uniform(20);
+    svs_stepped_embed, include/svsdct.h): coefficient k is quantised with steps[k] and the call's delta is not used.  It
+    combines with block_key, coeffs, dither_key, nearest and minmove and runs the exact kernels in every mode; ValueError with
+    readback or readback_keyed.  The receiver must use the same table.
     Returns (stego uint8 [F,H,W], n_embedded), with readback or readback_keyed (stego, n_embedded, ReadbackCounts)."""
+    table = _steps_arg(steps, readback, readback_keyed)
     call = _resolve(n_ac, None, block_key, first_frame, coeffs, dither_key, readback, readback_keyed)
     lib = native.load()
     native.ensure_device(device)
@@ -291,6 +316,10 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     done = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
     counts = native.ReadbackCounts()
+    if table is not None:
+        _stepped_call(lib, "embed", call, table, [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], n_ac,
+                      [packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done)])
+        return stego, int(done.value)
     _gray_call(lib, "embed", call, [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], delta, n_ac,
                [packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done)],
                C.byref(counts))
@@ -300,11 +329,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
 
 
 def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
-                   first_frame: int = 0, coeffs=None, dither_key=None):
+                   first_frame: int = 0, coeffs=None, dither_key=None, steps=None):
     """Extract the packed bit stream of a stack of gray frames on the GPU.  block_key / first_frame: as embed_frames (the
     sender's key and clip frame index).  coeffs: as embed_frames (the sender's selection).  dither_key: as embed_frames (the
-    sender's dither key).
+    sender's dither key).  steps: as embed_frames (the sender's step table; delta is then not used).
     Returns (packed uint8 [ceil(n_bits/8)], n_bits)."""
+    table = _steps_arg(steps)
     call = _resolve(n_ac, None, block_key, first_frame, coeffs, dither_key)
     lib = native.load()
     native.ensure_device(device)
@@ -314,8 +344,11 @@ def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str |
     out = np.zeros(max(4, (cap + 7) // 8 + (-((cap + 7) // 8)) % 4), np.uint8)
     got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
-    _gray_call(lib, "extract", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac,
-               [out.ctypes.data, out.size, mode_flags(mode), C.byref(got)])
+    back = [out.ctypes.data, out.size, mode_flags(mode), C.byref(got)]
+    if table is not None:
+        _stepped_call(lib, "extract", call, table, [stack.ctypes.data, C.byref(planes)], n_ac, back)
+    else:
+        _gray_call(lib, "extract", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, back)
     n = int(got.value)
     return out[: (n + 7) // 8], n
 
@@ -516,7 +549,7 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, first_frame: int | None = None,
-                 readback_keyed: bool = False) -> int:
+                 readback_keyed: bool = False, steps=None) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
     native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
     read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
@@ -524,11 +557,17 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
     as embed_frames (svs_embed_select_dev).  dither_key: a keyed dither, as embed_frames (svs_embed_dithered_dev); its clip
     frame index is first_frame, by default the order's (0 without one) - the two must agree.  readback_keyed: the read-back
     pass under coeffs and / or dither_key (svs_embed_dithered_readback_dev; d_counts as with readback); with neither it makes
-    the readback call; ValueError together with readback."""
+    the readback call; ValueError together with readback.  steps: per-coefficient QIM steps, as embed_frames
+    (svs_stepped_embed_dev; delta is then not used)."""
     _one_readback(readback, readback_keyed)      # ahead of the mode's ValueError
     done = C.c_uint64(0)
     flags = embed_flags(mode, nearest, minmove)
+    table = _steps_arg(steps, readback, readback_keyed)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key, readback, readback_keyed)
+    if table is not None:
+        _stepped_call(native.load(), "embed", call, table, [d_gray, d_stego, C.byref(planes)], n_ac,
+                      [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], (stream or None,))
+        return int(done.value)
     _gray_call(native.load(), "embed", call, [d_gray, d_stego, C.byref(planes)], delta, n_ac,
                [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], d_counts or None, (stream or None,))
     return int(done.value)
@@ -536,13 +575,17 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
 
 def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
                    stream: int = 0, mode: str | None = None, order: BlockOrder | None = None, coeffs=None, dither_key=None,
-                   first_frame: int | None = None) -> int:
+                   first_frame: int | None = None, steps=None) -> int:
     """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order, coeffs, dither_key,
-    first_frame: as embed_device."""
+    first_frame, steps: as embed_device."""
     got = C.c_uint64(0)
+    table = _steps_arg(steps)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
-    _gray_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac,
-               [d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)], None, (stream or None,))
+    back = [d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)]
+    if table is not None:
+        _stepped_call(native.load(), "extract", call, table, [d_gray, C.byref(planes)], n_ac, back, (stream or None,))
+    else:
+        _gray_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac, back, None, (stream or None,))
     return int(got.value)
 
 

@@ -68,6 +68,11 @@ class Steps(C.Structure):
     _fields_ = [("step", C.c_uint16 * 64)]
 
 
+class QimSteps(C.Structure):
+    """struct svs_qim_steps: the per-coefficient QIM steps of the stepped entry points (include/svsdct.h, svsdct/steps.py)"""
+    _fields_ = [("delta", C.c_uint16 * 64)]
+
+
 SVS_SCAN_ROW_MAJOR = 0
 SVS_SCAN_ZIGZAG = 1
 
@@ -78,6 +83,7 @@ _BO = C.POINTER(BlockOrder)
 _CO = C.POINTER(Coeffs)
 _DI = C.POINTER(Dither)
 _ST = C.POINTER(Steps)
+_QS = C.POINTER(QimSteps)
 
 # name -> (restype, argtypes); every symbol include/svsdct.h declares
 SIGNATURES = {
@@ -135,6 +141,12 @@ SIGNATURES = {
     "svs_quality_steps": (C.c_int, [_ST, C.c_int]),
     "svs_requantise_dev": (C.c_int, [_u8p, _u8p, _PL, _ST, C.c_uint32, C.c_void_p]),
     "svs_requantise": (C.c_int, [_u8p, _u8p, _PL, _ST, C.c_uint32]),
+    "svs_matched_steps": (C.c_int, [_QS, _ST, C.c_int, C.c_int]),
+    "svs_stepped_embed_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                         _u64p, C.c_void_p]),
+    "svs_stepped_embed": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_stepped_extract_dev": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
+    "svs_stepped_extract": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                           _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,

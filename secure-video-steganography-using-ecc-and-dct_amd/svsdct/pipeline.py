@@ -31,6 +31,7 @@ import numpy as np
 
 from . import batch, native
 from . import coeffs as _coeffs
+from . import steps as _steps
 from .native import Planes
 
 
@@ -50,7 +51,8 @@ def _device(nbytes: int):
 class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
-                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False):
+                 nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
+                 steps=None):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
@@ -60,8 +62,12 @@ class FramePipeline:
         key of a keyed dither for every batch (svsdct/dither.py; ValueError with readback); each submit's first frame index
         feeds both the order and the dither.  readback_keyed: every embed batch is read back and repaired under coeffs and / or
         dither_key (svs_embed_dithered_readback_dev, include/svsdct.h; with neither: the readback call); readback_counts()
-        gives the totals; ValueError together with readback."""
+        gives the totals; ValueError together with readback.  steps: None or a table of 64 per-coefficient QIM steps for every
+        batch (svsdct/steps.py; svs_stepped_embed_dev / svs_stepped_extract_dev, include/svsdct.h): delta is then not used;
+        ValueError with readback or readback_keyed."""
         batch._one_readback(readback, readback_keyed)
+        batch._steps_arg(steps, readback, readback_keyed)      # its ValueErrors, before anything is allocated
+        self.steps = None if steps is None else _steps.as_table(steps)
         if height % 8 or width % 8:
             raise ValueError("frame height and width must be multiples of 8")
         self.block_key = batch.block_order(block_key).key if block_key is not None else None
@@ -132,6 +138,10 @@ class FramePipeline:
         """the keywords of a dithered submit: none at all without a key, so the other submits make the calls they made"""
         return {} if self.dither_key is None else {"dither_key": self.dither_key, "first_frame": first_frame}
 
+    def _steps(self) -> dict:
+        """the keyword of a stepped submit: none at all without a table"""
+        return {} if self.steps is None else {"steps": self.steps}
+
     def _readback(self) -> dict:
         """the read-back keyword of an embed submit: one switch per path, and only the one that is on"""
         return {"readback_keyed": True} if self.readback_keyed else {"readback": self.readback}
@@ -147,7 +157,8 @@ class FramePipeline:
                                   self._d_payload.value if self._d_payload else 0, bit_offset, left,
                                   stream=s["stream"].value, mode=self.mode, order=self._order(first_frame),
                                   **self._readback(), d_counts=self._d_counts.value if self._d_counts else 0,
-                                  nearest=self.nearest, coeffs=self.coeffs, minmove=self.minmove, **self._dither(first_frame))
+                                  nearest=self.nearest, coeffs=self.coeffs, minmove=self.minmove, **self._dither(first_frame),
+                                  **self._steps())
         native.check(self.lib.svs_memcpy_d2h(s["hout_p"], s["d_frames"], nbytes, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, used
         return used
@@ -166,7 +177,7 @@ class FramePipeline:
         native.check(self.lib.svs_memcpy_h2d(s["d_frames"], s["hin_p"], nbytes, s["stream"]), "svs_memcpy_h2d")
         got = batch.extract_device(s["d_frames"].value, self._planes(n_frames), self.delta, self.n_ac, s["d_bits"].value,
                                    self._bits_bytes, stream=s["stream"].value, mode=self.mode,
-                                   order=self._order(first_frame), coeffs=self.coeffs, **self._dither(first_frame))
+                                   order=self._order(first_frame), coeffs=self.coeffs, **self._dither(first_frame), **self._steps())
         native.check(self.lib.svs_memcpy_d2h(s["hbits_p"], s["d_bits"], (got + 7) // 8, s["stream"]), "svs_memcpy_d2h")
         s["frames"], s["bits"] = n_frames, got
         return got
