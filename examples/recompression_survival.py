@@ -15,11 +15,12 @@ Everything runs on the GPU through the library.  The channel is a format, so the
 quality 85, and at 75 copies that fail together, which the soft vote mends in part.  The model is luminance only, grid-aligned,
 without chroma subsampling, motion prediction or deblocking.
 
---steps prints two rows per quality instead: the uniform delta of --delta against per-coefficient QIM steps (svsdct/steps.py;
-batch.embed_frames / extract_frames with steps=): the PSNR of each against the cover and the bit errors of each copy alone.  A
-table matched to a codec's (q75x2: twice the quality-75 steps) keeps its lattice points through that codec's requantiser, so
-the step is large only where the codec's is - README.md has the table, from the CPU model (tests/stepped_lib.py).  A stepped
-call has no soft, vote or histogram form.
+--steps prints two rows instead: the uniform delta of --delta against per-coefficient QIM steps (svsdct/steps.py; the batch
+calls with steps=): the PSNR of each against the cover and, per quality, the bit errors of each copy alone, those of the fused
+soft vote and the lowest lattice share of the three frames - for the stepped row through svs_stepped_soft_vote and
+svs_stepped_soft_histogram, whose bytes count the distance in units of each coefficient's own cell.  A table matched to a
+codec's (q75x2: twice the quality-75 steps) keeps its lattice points through that codec's requantiser, so the step is large
+only where the codec's is - README.md has the tables, from the CPU models (tests/stepped_lib.py, tests/stepped_soft_lib.py).
 """
 import argparse
 import os
@@ -60,15 +61,20 @@ if a.steps:
     rule = dict(nearest=a.rule == "nearest", minmove=a.rule == "minmove")
     print(f"{f} frames of {w}x{h}, one copy of {payload.size} bits per frame, n = {a.n_ac}, {a.rule} rule"
           + (f", zig-zag from {a.zigzag}" if a.zigzag else ""))
-    print("steps                | PSNR dB | " + " | ".join(f"Q = {q}" for q in a.qualities.split(",")))
+    print("steps                | PSNR dB | per quality: errors of each copy alone, fused soft vote, lowest lattice share")
+    print("                     |         | " + " | ".join(f"Q = {q}" for q in a.qualities.split(",")))
     for name, how in ((f"uniform {a.delta:g}", {}), (a.steps if len(a.steps) < 20 else "table", dict(steps=table))):
         stego, used = batch.embed_frames(cover, a.delta, a.n_ac, stream, mode="exact", **rule, **kw, **how)
         assert used == stream.size
         cells = []
         for quality in (int(q) for q in a.qualities.split(",")):
-            packed, n = batch.extract_frames(batch.requantise_frames(stego, quality), a.delta, a.n_ac, mode="exact", **kw, **how)
+            seen = batch.requantise_frames(stego, quality)
+            packed, n = batch.extract_frames(seen, a.delta, a.n_ac, mode="exact", **kw, **how)
             got = np.unpackbits(packed, count=n).reshape(f, payload.size)
-            cells.append("/".join(str(int((g != payload).sum())) for g in got))
+            voted, _ = batch.extract_vote_frames(seen, a.delta, a.n_ac, payload.size, **kw, **how)
+            hist, _ = batch.extract_histogram_frames(seen, a.delta, a.n_ac, **kw, **how)
+            cells.append("/".join(str(int((g != payload).sum())) for g in got) + f", {int((voted != payload).sum())}, "
+                         f"{soft.lattice_share(hist).min():.3f}")
         print(f"{name:20s} | {psnr(stego, cover):7.2f} | " + " | ".join(cells))
     sys.exit(0)
 

@@ -683,7 +683,8 @@ int svs_requantise(const uint8_t *in, uint8_t *out, const svs_planes *planes, co
  * The host forms go through the per-thread staging context: whole frames under an order or a dither, chunks otherwise.
  * Limits: both sides must hold the table; a matched table is tuned to ONE codec table on the aligned luminance grid (README.md
  * has the survival table, from the CPU model; a table matched to a fine codec table needs a floor, see svs_matched_steps); a
- * real encoder is not measured.  A stepped call has no read-back, soft, vote, histogram, colour or _str form. */
+ * real encoder is not measured.  A stepped call has no read-back, colour or _str form; its soft, vote and histogram forms are
+ * svs_stepped_soft_* below. */
 typedef struct svs_qim_steps {
     uint16_t delta[64];   /* delta[k]: the step of flat row-major coefficient k = 8u + v; k = 1..63 each 1..4095; delta[0] (DC) is not read */
 } svs_qim_steps;
@@ -712,6 +713,67 @@ int svs_stepped_extract_dev(const uint8_t *d_gray, const svs_planes *planes, con
 int svs_stepped_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
                         const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint8_t *bits_packed_out,
                         uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out);
+
+/* ---- soft bytes, the fused vote and the fused histograms under per-coefficient steps -------------------------------
+ * svs_soft_extract*, svs_soft_vote* and svs_soft_histogram* with a svs_qim_steps table in the place of delta, as
+ * svs_stepped_extract* is to svs_extract_dithered*; the argument order is svs_stepped_extract*'s.  The layout is that of the
+ * existing soft call with the same order, coeffs, dither and n_ac: one byte per capacity bit in stream order, byte i belonging to
+ * stream bit i of svs_stepped_extract*; the tally and the histogram rows are exactly the formats stated above, fed with these
+ * bytes.  The byte is a FORMAT.  For the payload coefficient at flat row-major index k, dk = (float)steps->delta[k], c the
+ * pocketfft-identical forward coefficient, d = r * dk the stepped calls' dither (0 without one), every step one IEEE float32
+ * operation with no contraction, in the same order on host and device:
+ *     x    = c - d
+ *     q    = (int)rintf(x / dk)          (the stepped extract's own index: float32 division, round half to even)
+ *     x0   = (float)q * dk
+ *     a    = fabsf(x - x0)
+ *     h_k  = 0.5f * dk
+ *     s_k  = 254.0f / dk                 (one float32 division; equal to (float)(254.0 / (double)dk) for every dk in 1..4095)
+ *     m    = clamp((int)((h_k - a) * s_k), 0, 127)        (truncation toward zero)
+ *     byte = ((q & 1) << 7) | m
+ * On a lattice point (a = 0) m is (int)(h_k * s_k): 127, or 126 for the steps whose float32 product falls just below 127, as
+ * in svs_soft_extract* at such a delta.
+ * So m is the distance from the nearest decision boundary in units of delta[k] / 254, the coefficient's OWN cell: under a vote
+ * a copy weighs by how deep it sits in its cell, whatever the size of that cell.  A uniform table (every delta[k] = D) gives,
+ * byte for byte, tally entry for tally entry and count for count, the output of svs_soft_extract* / svs_soft_vote* /
+ * svs_soft_histogram* at delta = D with the same options; the stepped side of the kernels runs all the same.
+ *   steps  : as svs_stepped_extract*: checked first, before the other options and before any device work; NULL, or an entry
+ *            k >= 1 that is 0 or above 4095, is SVS_ERR_INVALID_ARG naming the entry.  There is no delta <= 0 route.
+ *   order, coeffs, dither : each may be NULL; checked next (dither, then coeffs, then flags) as in svs_stepped_extract*.  The
+ *            histogram calls take no order, as svs_soft_histogram*.
+ *   flags  : the mode bits are accepted and change nothing; embed flags and unknown bits are refused.
+ *   every other argument, and every other check in its order (planes, a NULL or unaligned pointer, the capacity of d_soft_out,
+ *            period 0 or above 2^61 - 1, capacity above period * 2^22, N * count above 2^32 - 1): as the soft call of the same
+ *            name.  A capacity of 0 behaves as there: the soft call writes nothing, a device tally or hist is left untouched, a
+ *            host tally or hist is filled with zeros, *n_bits_out = 0.  A refusal leaves the outputs and *n_bits_out as they were
+ *            where the existing call does.
+ * Cost: the soft launch of the two eight-row power-of-two-delta extract instantiations, which hold the stepped side, with this
+ * byte in the place of theirs - per coefficient one more float32 division than the stepped extract; the three tails (copy, vote,
+ * histogram), the tiles in LDS, the atomics and the flush rules are the existing ones.  Times: README.md.
+ * Limits: as the stepped calls and the soft calls; a vote that weighs a copy by its ABSOLUTE distance (in coefficient units,
+ * not in units of its own cell) was not evaluated; the survival figures (README.md) come from the CPU model of the channel, not
+ * from a real encoder; there is no colour and no _str form, no FramePipeline or drop-in form. */
+int svs_stepped_soft_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order,
+                                 const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                                 uint8_t *d_soft_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+int svs_stepped_soft_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                             const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint8_t *soft_out,
+                             uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out);
+
+int svs_stepped_soft_vote_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                              const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint64_t period, uint64_t stream_bit0,
+                              int32_t *d_tally, uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+int svs_stepped_soft_vote(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                          const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint64_t period, uint64_t stream_bit0,
+                          int32_t *tally_out, uint32_t flags, uint64_t *n_bits_out);
+
+int svs_stepped_soft_histogram_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                                   const svs_qim_steps *steps, int n_ac, uint32_t *d_hist, uint32_t flags, uint64_t *n_bits_out,
+                                   void *stream);
+
+int svs_stepped_soft_histogram(const uint8_t *gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                               const svs_qim_steps *steps, int n_ac, uint32_t *hist_out, uint32_t flags, uint64_t *n_bits_out);
 
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:

@@ -625,6 +625,20 @@ struct StepArgs {
 #endif
         return (float)((w[i] >> (16 * (k & 1))) & 0xFFFFu);
     }
+    // dwords 2j and 2j + 1 - the steps of coefficients 4j .. 4j + 3 - loaded HERE in the same way, steps 4j and 4j + 1 in the low
+    // half.  One read for four coefficients: the compiler reads this kernel argument in place only while it can follow every
+    // address formed on it, up to a fixed number of them (300 in this LLVM); past that it copies the table to scratch at the
+    // kernel's entry.  The stepped soft side (stepped_soft_bytes) on top of stepped_parities' two loops stays below it with 16
+    // reads, not with 63 or 32.
+    SVS_HD uint64_t quad_here(int j) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(j));
+#endif
+        uint64_t q;
+        __builtin_memcpy(&q, &w[2 * j], sizeof q);
+        return q;
+    }
+    static SVS_HD float step_of_quad(uint64_t quad, int k) { return (float)(uint32_t)((quad >> (16 * (k & 3))) & 0xFFFFu); }
 };
 
 // host side: the steps of a checked table (every entry k >= 1 in 1..4095)
@@ -1998,6 +2012,68 @@ SVS_HD void extract_block_stepped(const uint32_t (&rx)[8], const uint32_t (&ry)[
     hi = 0;
     lo = 0;
     stepped_parities<DITH>(D, sel, steps, hi, lo, s_b);
+}
+
+// a wave-uniform float as a scalar value on the device (a vector register less for each the stepped soft side holds)
+SVS_HD float wave_uniform(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+#else
+    return v;
+#endif
+}
+
+// SOFT extraction with a step per coefficient (svs_stepped_soft_extract*, include/svsdct.h states the format): soft_byte with
+// the stepped extract's own index and the coefficient's own cell - h_k = 0.5f * dk and s_k = 254.0f / dk are computed here, one
+// float32 operation each (the division is the correctly rounded one quant_index_by_division relies on; for an integer dk in
+// 1..4095 it is make_soft_args' (float)(254.0 / (double)dk) bit for bit), so SoftArgs carries no per-coefficient value.
+SVS_HD uint32_t stepped_soft_byte(float x, float dk, float hk, float sk) {   // hk = 0.5f * dk, sk = 254.0f / dk
+    const int q = quant_index_by_division(x, dk);
+    const float x0 = (float)q * dk;
+    const float a = fabsf(x - x0);
+    const float v = (hk - a) * sk;
+    const uint32_t m = v >= 127.0f ? 127u : (v > 0.0f ? (uint32_t)(int)v : 0u);   // the clamp on the float, as soft_byte
+    return (((uint32_t)q & 1u) << 7) | m;
+}
+
+// put(s, byte) for every payload coefficient, as extract_block_soft's loop; a recursion over K, as stepped_parities and for its
+// reason (the step keeps a compile-time position).  `quad` holds the table's steps of coefficients K & ~3 .. K | 3, read at the
+// first of the four where any of them carries a slot (StepArgs::quad_here).  `dith` is wave-uniform.
+template <int K = 1, class Put>
+SVS_HD void stepped_soft_bytes(const float (&D)[8][8], const CoeffTable &sel, const StepArgs &steps, bool dith, uint32_t s_b,
+                               Put &&put, uint64_t quad = 0u) {
+    const uint32_t s = sel.slot(K);
+    if constexpr (K == 1 || (K & 3) == 0) {
+        bool any = false;   // wave-uniform
+#pragma unroll
+        for (int k = K; k <= (K | 3); ++k) any = any || sel.slot(k) < sel.count;
+        if (any) quad = steps.quad_here(K >> 2);
+    }
+    if (s < sel.count) {  // wave-uniform
+        // the cell's three values first, each a scalar: their division is over before the coefficient's own begins
+        const float dk = wave_uniform(StepArgs::step_of_quad(quad, K));
+        const float hk = wave_uniform(0.5f * dk), sk = wave_uniform(254.0f / dk);
+        SVS_SCHED_FENCE();
+        float x = D[K >> 3][K & 7];
+        if (dith) x = x - dither_value(s_b, (uint32_t)K, dk);
+        put(s, stepped_soft_byte(x, dk, hk, sk));
+    }
+    SVS_SCHED_FENCE();   // coefficient by coefficient, as extract_block_soft
+    if constexpr (K < 63) stepped_soft_bytes<K + 1>(D, sel, steps, dith, s_b, put, quad);
+}
+
+// extract_block_soft with a step per coefficient: `sel` is never empty (the call's selection or the prefix table of n_ac)
+template <class Put>
+SVS_HD void extract_block_stepped_soft(const uint32_t (&rx)[8], const uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps,
+                                       bool dith, uint32_t s_b, Put &&put) {
+    float D[8][8];
+    forward_exact(rx, ry, D);
+    // the 63 AC coefficients are computed HERE, as in extract_block_stepped: DC is never read, and pinned too it costs a register
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int k = 1; k < 64; ++k) asm volatile("" : "+v"(D[k >> 3][k & 7]));
+#endif
+    stepped_soft_bytes(D, sel, steps, dith, s_b, put);
 }
 
 inline int rows_for(int n) { return (n >> 3) + 1; }  // coefficient rows holding flat indices 1..n

@@ -1483,6 +1483,62 @@ int svs_stepped_extract(const uint8_t *gray, const svs_planes *planes, const svs
     });
 }
 
+// The stepped soft calls are the soft calls inside with_steps, under the stepped extract's policy: the table is checked first,
+// then what the soft call checks, in its order; the call routes with a positive delta that no kernel reads, so the vote's and
+// the histogram's delta <= 0 refusal cannot occur (an entry is at least 1).
+int svs_stepped_soft_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order,
+                                 const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                                 uint8_t *d_soft_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream) {
+    return with_steps(kSteppedExtract, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::SOFT};
+        return extract_dev(d_gray, planes, kSteppedRouteDelta, n, d_soft_out, out_capacity_bytes, flags, n_bits_out, stream, o);
+    });
+}
+
+int svs_stepped_soft_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                             const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint8_t *soft_out,
+                             uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
+    return with_steps(kSteppedExtract, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::SOFT};
+        return extract_host(gray, planes, kSteppedRouteDelta, n, soft_out, out_capacity_bytes, flags, n_bits_out, o);
+    });
+}
+
+int svs_stepped_soft_vote_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                              const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint64_t period, uint64_t stream_bit0,
+                              int32_t *d_tally, uint32_t flags, uint64_t *n_bits_out, void *stream) {
+    return with_steps(kSteppedExtract, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::VOTE, period, stream_bit0};
+        return extract_dev(d_gray, planes, kSteppedRouteDelta, n, reinterpret_cast<uint8_t *>(d_tally), 0, flags, n_bits_out, stream, o);
+    });
+}
+
+int svs_stepped_soft_vote(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                          const svs_dither *dither, const svs_qim_steps *steps, int n_ac, uint64_t period, uint64_t stream_bit0,
+                          int32_t *tally_out, uint32_t flags, uint64_t *n_bits_out) {
+    return with_steps(kSteppedExtract, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::VOTE, period, stream_bit0};
+        return extract_host(gray, planes, kSteppedRouteDelta, n, reinterpret_cast<uint8_t *>(tally_out), 0, flags, n_bits_out, o);
+    });
+}
+
+int svs_stepped_soft_histogram_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                                   const svs_qim_steps *steps, int n_ac, uint32_t *d_hist, uint32_t flags, uint64_t *n_bits_out,
+                                   void *stream) {
+    return with_steps(kSteppedExtract, nullptr, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::HIST};
+        return extract_dev(d_gray, planes, kSteppedRouteDelta, n, reinterpret_cast<uint8_t *>(d_hist), 0, flags, n_bits_out, stream, o);
+    });
+}
+
+int svs_stepped_soft_histogram(const uint8_t *gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
+                               const svs_qim_steps *steps, int n_ac, uint32_t *hist_out, uint32_t flags, uint64_t *n_bits_out) {
+    return with_steps(kSteppedExtract, nullptr, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.out = {ExtractOutput::HIST};
+        return extract_host(gray, planes, kSteppedRouteDelta, n, reinterpret_cast<uint8_t *>(hist_out), 0, flags, n_bits_out, o);
+    });
+}
+
 int svs_extract_str(const uint8_t *gray, const svs_planes *planes, double delta, int n_ac, char *bits_ascii_out,
                     uint64_t out_capacity_chars, uint32_t flags, uint64_t *n_bits_out) {
     svs::Geometry g;

@@ -1036,8 +1036,12 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
     // A soft call (soft.on; the U = 8 instantiations only - svs_route.hpp plans no other for one) is a third side behind the
     // same kind of branch: one byte per payload coefficient instead of one bit (svs_block.hpp, SoftArgs).  It takes its wave
     // tiles from dynamic LDS, which only the soft launch requests (soft_lds_bytes), and touches neither `flags` nor `sel`.
+    // Per-coefficient steps under a soft call (soft.on && steps.on; svs_stepped_soft_*) are the same side with the stepped byte in
+    // the bytes' places (svs_block.hpp extract_block_stepped_soft), compiled into the two QM_POW2 instantiations that hold the
+    // stepped side (below) behind ONE wave-uniform branch around the whole side, tails included: as an alternative beside
+    // extract_block_soft that shares the loads and the tails it spilled 75 VGPRs (profiles/stepped_soft_resources.txt).
     if constexpr (U == 8) {
-        if (soft.on) {     // wave-uniform
+        const auto soft_side = [&](auto stepped) __attribute__((always_inline)) {
             extern __shared__ uint32_t soft_tiles[];
             // the wave index as a scalar: with it in a vector register the keyed instantiations, at their bound of 80, spilled
             // the thread index across the block body once the vote tail joined (profiles/soft_vote_resources.txt)
@@ -1055,8 +1059,10 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
 #pragma unroll
                 for (int r = 0; r < 8; ++r) { ax[r] = v[r].x; ay[r] = v[r].y; }
                 uint8_t *mine = tile + lane * n;
-                extract_block_soft<QM>(ax, ay, dith.sel, qp, soft, dith.on != 0u, dith.on ? dither_seed_of(gblock, g, dith) : 0u,
-                                       [&](uint32_t s, uint32_t byte) { mine[s] = (uint8_t)byte; });
+                const uint32_t s_b = dith.on ? dither_seed_of(gblock, g, dith) : 0u;
+                const auto put = [&](uint32_t s, uint32_t byte) { mine[s] = (uint8_t)byte; };
+                if constexpr (decltype(stepped)::value) extract_block_stepped_soft(ax, ay, dith.sel, steps, dith.on != 0u, s_b, put);
+                else extract_block_soft<QM>(ax, ay, dith.sel, qp, soft, dith.on != 0u, s_b, put);
                 if constexpr (KEYED) first = stream_first<true>(gblock, n, g, order_arg(order...));
             }
             wave_lds_fence();
@@ -1073,6 +1079,19 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
                                      out_bytes);
             else
                 copy_soft_run<KEYED>(tile, lane, n, blocks, (uint64_t)wave_first * n, first, soft.recip, out, out_bytes);
+        };
+        if (soft.on) {     // wave-uniform
+            if constexpr (QM == QM_POW2) {
+                // the side that was there first comes first: with the stepped one ahead of it the keyed instantiation spilled
+                // two registers on the side that was there before (profiles/stepped_soft_resources.txt)
+                if (!steps.on) {   // wave-uniform
+                    soft_side(std::false_type{});
+                    return;
+                }
+                soft_side(std::true_type{});
+                return;
+            }
+            soft_side(std::false_type{});
             return;
         }
     }

@@ -44,9 +44,10 @@ struct RouteArgs {
     // a histogram call (svs_soft_histogram*): a soft call whose bytes are counted per frame instead of written (SoftArgs::hist);
     // never keyed - the counts of a frame do not depend on an order
     bool hist = false;
-    // per-coefficient steps (svs_stepped_embed* / svs_stepped_extract*; gray calls only): the lane-per-block exact kernels with
-    // all eight coefficient rows in every mode, in the instantiations that hold the stepped side (svs_device.hpp) - QM_DOUBLE
-    // for an embed, QM_POW2 for an extract - whatever `delta` says; the callers pass a positive one, and no kernel reads it
+    // per-coefficient steps (svs_stepped_embed* / svs_stepped_extract* / svs_stepped_soft_*; gray calls only): the lane-per-block
+    // exact kernels with all eight coefficient rows in every mode, in the instantiations that hold the stepped side
+    // (svs_device.hpp) - QM_DOUBLE for an embed, QM_POW2 for an extract - whatever `delta` says; the callers pass a positive
+    // one, and no kernel reads it
     bool stepped = false;
 };
 
@@ -230,6 +231,9 @@ inline DitherArgs readback_tables(const EmbedPlan &p, const KernelOptions &k) {
 // the selected loop alone and reads its own copy from the dither's table, never empty: the call's selection, or the prefix
 // table of n_ac (as embed_exact_kernel's dithered side)
 // The stepped side runs the selected loop alone and reads it from `sel`: the call's selection, or the prefix table of n_ac.
+// A stepped soft call (svs_stepped_soft_*: soft, vote or hist, and stepped) is planned EXACT with eight rows and QM_POW2 by
+// plan_extract's own rules and gets both: the soft side's table and SoftArgs as a soft call (half and scale are those of the
+// route's delta and are not read: the stepped byte takes them from its coefficient's step) and the call's StepArgs.
 inline LaunchTables extract_tables(const ExtractPlan &p, const KernelOptions &k) {
     const CoeffTable own = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
     const CoeffTable sel = p.stepped && !own.count ? make_prefix_table(p.n_ac) : own;

@@ -361,26 +361,31 @@ _SOFT_CALLS = {
 }
 
 
-def _soft_call(lib, name, call: _GrayCall, front, delta, n_ac, middle, flags, stream=()) -> int:
+def _soft_call(lib, name, call: _GrayCall, front, delta, n_ac, middle, flags, stream=(), steps=None) -> int:
     """svs_soft_<name>(*front, [order], coeffs, dither, delta, n_ac, *middle, flags, n_bits_out), or with stream = (handle,) its
     _dev form; -> n_bits_out.  A soft entry point takes each of its structs or NULL, so every stem of _resolve makes the same
-    call; raises unless it returns SVS_OK"""
+    call; raises unless it returns SVS_OK.  steps (a struct of _steps_arg): svs_stepped_soft_<name>, the same call with the
+    table in the place of delta."""
     takes_order, names = _SOFT_CALLS[name]
     assert len(middle) == len(names), names
-    symbol = f"svs_soft_{name}" + ("_dev" if stream else "")
+    symbol = ("svs_soft_" if steps is None else "svs_stepped_soft_") + name + ("_dev" if stream else "")
     got = C.c_uint64(0)
     native.check(getattr(lib, symbol)(*front, *([_ref(call.order)] if takes_order else ()), _ref(call.sel), _ref(call.dith),
-                                      float(delta), int(n_ac), *middle, flags, C.byref(got), *stream), symbol)
+                                      float(delta) if steps is None else C.byref(steps), int(n_ac), *middle, flags, C.byref(got),
+                                      *stream), symbol)
     return int(got.value)
 
 
 def extract_soft_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
-                        first_frame=None, coeffs=None, dither_key=None):
+                        first_frame=None, coeffs=None, dither_key=None, steps=None):
     """Soft-decision extraction of a stack of gray frames on the GPU (svs_soft_extract, include/svsdct.h): one byte per
     capacity bit in stream order - bit 7 the hard bit extract_frames returns, bits 0..6 the distance of the coefficient from
     the nearest decision boundary in units of delta / 254 (svsdct/soft.py reads and combines them).  block_key, first_frame,
     coeffs, dither_key: as extract_frames; mode is accepted and changes nothing (a soft call always runs the exact kernel).
+    steps: as extract_frames (svs_stepped_soft_extract: the sender's step table; delta is then not used, and the distance of
+    coefficient k is in units of steps[k] / 254, its own cell).
     Returns (soft uint8 [capacity], n_bits)."""
+    table = _steps_arg(steps)
     call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
     lib = native.load()
     native.ensure_device(device)
@@ -389,7 +394,8 @@ def extract_soft_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: 
     cap = capacity_bits(f, h, w, n_ac)
     out = pinned_empty(max(4, cap))
     planes = Planes.contiguous(f, h, w)
-    n = _soft_call(lib, "extract", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [out.ctypes.data, cap], mode_flags(mode))
+    n = _soft_call(lib, "extract", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [out.ctypes.data, cap], mode_flags(mode),
+                   steps=table)
     return out[:n], n
 
 
@@ -401,14 +407,16 @@ def _period(period) -> int:
 
 
 def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: int = 0, device: int = 0, mode: str | None = None,
-                        block_key=None, first_frame=None, coeffs=None, dither_key=None):
+                        block_key=None, first_frame=None, coeffs=None, dither_key=None, steps=None):
     """Fused soft vote over a stack of gray frames on the GPU (svs_soft_vote, include/svsdct.h): the soft bytes of
     extract_soft_frames are never written - the kernel adds each into a tally of `period` int32 values at its stream position
     (stream_bit0 + its index) mod period, and only the tally comes back.  period: the payload's length in bits, as the sender
     tiled it (embed_repeated_frames).  stream_bit0: the capacity of the frames before this stack when a clip is read in
     batches - add the tallies of the batches and read the bits with soft.tally_bits.  The other keywords: as
-    extract_soft_frames.  Returns (bits uint8 [period], tally int32 [period]); the bits are soft.combine's."""
+    extract_soft_frames (steps: svs_stepped_soft_vote).  Returns (bits uint8 [period], tally int32 [period]); the bits are
+    soft.combine's."""
     period = _period(period)
+    table = _steps_arg(steps)
     call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
     lib = native.load()
     native.ensure_device(device)
@@ -417,19 +425,20 @@ def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: in
     tally = pinned_empty(4 * period).view(np.int32)
     planes = Planes.contiguous(f, h, w)
     _soft_call(lib, "vote", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [period, int(stream_bit0), tally.ctypes.data],
-               mode_flags(mode))
+               mode_flags(mode), steps=table)
     return _soft.tally_bits(tally), tally
 
 
 def extract_histogram_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, first_frame=None,
-                             coeffs=None, dither_key=None):
+                             coeffs=None, dither_key=None, steps=None):
     """Fused per-frame soft histograms of a stack of gray frames on the GPU (svs_soft_histogram, include/svsdct.h): the soft
     bytes of extract_soft_frames are never written - the kernel counts each into row `frame`, column `byte` of 256 counts a
     frame, and only the rows come back (soft.byte_histogram is the model; soft.margins and soft.lattice_share read them).
     There is no block_key keyword and none is needed: the dither is keyed to a block's physical position and an order only
     permutes the blocks inside a frame, so a frame's counts are the same under every order - frames embedded under a block_key
-    are read with this same call.  first_frame, coeffs, dither_key: as extract_soft_frames; mode is accepted and changes
-    nothing.  Returns (hist uint32 [n_frames, 256], n_bits)."""
+    are read with this same call.  first_frame, coeffs, dither_key, steps: as extract_soft_frames (steps: svs_stepped_soft_histogram);
+    mode is accepted and changes nothing.  Returns (hist uint32 [n_frames, 256], n_bits)."""
+    table = _steps_arg(steps)
     call = _resolve(n_ac, None, None, 0 if first_frame is None else first_frame, coeffs, dither_key)
     lib = native.load()
     native.ensure_device(device)
@@ -437,7 +446,8 @@ def extract_histogram_frames(frames: np.ndarray, delta, n_ac, device: int = 0, m
     f, h, w = stack.shape
     hist = pinned_empty(max(4, 1024 * f))[: 1024 * f].view(np.uint32).reshape(f, 256)
     planes = Planes.contiguous(f, h, w)
-    return hist, _soft_call(lib, "histogram", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [hist.ctypes.data], mode_flags(mode))
+    return hist, _soft_call(lib, "histogram", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, [hist.ctypes.data], mode_flags(mode),
+                            steps=table)
 
 
 def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | None = None, **embed_kw):
@@ -591,35 +601,40 @@ def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, ou
 
 def extract_soft_device(d_gray: int, planes: Planes, delta, n_ac, d_soft_out: int, out_capacity_bytes: int, stream: int = 0,
                         mode: str | None = None, order: BlockOrder | None = None, coeffs=None, dither_key=None,
-                        first_frame: int | None = None) -> int:
+                        first_frame: int | None = None, steps=None) -> int:
     """Enqueue the soft-decision extraction on `stream` (svs_soft_extract_dev): one byte per capacity bit into d_soft_out
     (4-byte aligned, at least the capacity in bytes); returns the number of bytes the batch yields.  order, coeffs, dither_key,
-    first_frame: as extract_device."""
+    first_frame, steps: as extract_device (steps: svs_stepped_soft_extract_dev)."""
+    table = _steps_arg(steps)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     return _soft_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac, [d_soft_out, int(out_capacity_bytes)],
-                      mode_flags(mode), (stream or None,))
+                      mode_flags(mode), (stream or None,), table)
 
 
 def extract_vote_device(d_gray: int, planes: Planes, delta, n_ac, d_tally: int, period, stream_bit0: int = 0, stream: int = 0,
-                        order: BlockOrder | None = None, first_frame: int | None = None, coeffs=None, dither_key=None) -> int:
+                        order: BlockOrder | None = None, first_frame: int | None = None, coeffs=None, dither_key=None,
+                        steps=None) -> int:
     """Enqueue the fused soft vote on `stream` (svs_soft_vote_dev): the batch's votes are ADDED into d_tally, `period` int32
     values in device memory (4-byte aligned) that the caller zeroes before the first batch; stream_bit0 is the capacity of the
-    frames before the batch.  Returns the number of bits that voted.  order, coeffs, dither_key, first_frame: as
-    extract_soft_device."""
+    frames before the batch.  Returns the number of bits that voted.  order, coeffs, dither_key, first_frame, steps: as
+    extract_soft_device (steps: svs_stepped_soft_vote_dev)."""
+    table = _steps_arg(steps)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     return _soft_call(native.load(), "vote", call, [d_gray, C.byref(planes)], delta, n_ac, [_period(period), int(stream_bit0), d_tally],
-                      0, (stream or None,))
+                      0, (stream or None,), table)
 
 
 def extract_histogram_device(d_gray: int, planes: Planes, delta, n_ac, d_hist: int, stream: int = 0, first_frame: int | None = None,
-                             coeffs=None, dither_key=None) -> int:
+                             coeffs=None, dither_key=None, steps=None) -> int:
     """Enqueue the fused per-frame soft histograms on `stream` (svs_soft_histogram_dev): the batch's bytes are ADDED into d_hist,
     planes.n_frames rows of 256 uint32 in device memory (4-byte aligned) that the caller zeroes before the first call; a clip
     read in batches passes d_hist + 1024 * (frames before the batch) and, under a dither, first_frame advanced by as many.
     Returns the number of bytes counted.  No order and no block_key: a frame's counts do not depend on one (see
-    extract_histogram_frames).  coeffs, dither_key, first_frame: as extract_soft_device."""
+    extract_histogram_frames).  coeffs, dither_key, first_frame, steps: as extract_soft_device (steps:
+    svs_stepped_soft_histogram_dev)."""
+    table = _steps_arg(steps)
     call = _resolve(n_ac, None, None, first_frame, coeffs, dither_key)
-    return _soft_call(native.load(), "histogram", call, [d_gray, C.byref(planes)], delta, n_ac, [d_hist], 0, (stream or None,))
+    return _soft_call(native.load(), "histogram", call, [d_gray, C.byref(planes)], delta, n_ac, [d_hist], 0, (stream or None,), table)
 
 
 def requantise_device(d_in: int, d_out: int, planes: Planes, steps_or_quality, stream: int = 0) -> None:

@@ -147,6 +147,15 @@ SIGNATURES = {
     "svs_stepped_embed": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _u64p]),
     "svs_stepped_extract_dev": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
     "svs_stepped_extract": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_stepped_soft_extract_dev": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p,
+                                                C.c_void_p]),
+    "svs_stepped_soft_extract": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
+    "svs_stepped_soft_vote_dev": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                             _u64p, C.c_void_p]),
+    "svs_stepped_soft_vote": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                         _u64p]),
+    "svs_stepped_soft_histogram_dev": (C.c_int, [_u8p, _PL, _CO, _DI, _QS, C.c_int, C.c_void_p, C.c_uint32, _u64p, C.c_void_p]),
+    "svs_stepped_soft_histogram": (C.c_int, [_u8p, _PL, _CO, _DI, _QS, C.c_int, C.c_void_p, C.c_uint32, _u64p]),
     "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                           _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
