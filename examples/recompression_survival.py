@@ -8,7 +8,7 @@ lattice (soft.lattice_share).
 
     python examples/recompression_survival.py [--delta 20] [--n-ac 10] [--rule reference|nearest|minmove]
                                               [--zigzag FIRST] [--qualities 100,95,90,85,75,50]
-                                              [--steps q75x2 | q95x2f16 | d1,...,d64]
+                                              [--steps q75x2 | q95x2f16 | d1,...,d64 [--readback] [--letterbox]]
 
 Everything runs on the GPU through the library.  The channel is a format, so the numbers equal those of the CPU model
 (tests/channel_lib.py) for the same seed - at the defaults the reference-rule row of README.md's table: no error down to
@@ -21,6 +21,9 @@ soft vote and the lowest lattice share of the three frames - for the stepped row
 svs_stepped_soft_histogram, whose bytes count the distance in units of each coefficient's own cell.  A table matched to a
 codec's (q75x2: twice the quality-75 steps) keeps its lattice points through that codec's requantiser, so the step is large
 only where the codec's is - README.md has the tables, from the CPU models (tests/stepped_lib.py, tests/stepped_soft_lib.py).
+--readback (with --steps) adds a third row: the stepped embed with its read-back and repair (readback_stepped=True;
+svs_stepped_embed_readback), and the blocks it repaired / left.  On the default cover nothing clips and the row equals the
+second; --letterbox blacks out a sixth of the rows at the top and at the bottom, where the plain rows lose bits before any channel.
 """
 import argparse
 import os
@@ -41,11 +44,17 @@ ap.add_argument("--zigzag", type=int, default=0, metavar="FIRST",
 ap.add_argument("--qualities", default="100,95,90,85,75,50")
 ap.add_argument("--steps", default=None, metavar="SPEC",
                 help="compare the uniform delta with per-coefficient steps: q<quality>x<multiple>[f<floor>] or 64 integers")
+ap.add_argument("--readback", action="store_true", help="with --steps: a third row, the stepped embed with read-back and repair")
+ap.add_argument("--letterbox", action="store_true", help="black bars over a sixth of the rows at the top and at the bottom")
 a = ap.parse_args()
 
 f, h, w = 3, 96, 160
 rng = np.random.default_rng(5)
 cover = rng.integers(64, 192, (f, h, w)).astype(np.uint8)                     # no pixel clips at 0 or 255 before the channel
+if a.letterbox:
+    bar = (h // 6) // 8 * 8
+    cover[:, :bar] = 0
+    cover[:, h - bar:] = 0
 payload = rng.integers(0, 2, batch.capacity_bits(1, h, w, a.n_ac)).astype(np.uint8)
 kw = dict(coeffs=f"zigzag:{a.zigzag}") if a.zigzag else {}
 
@@ -63,8 +72,12 @@ if a.steps:
           + (f", zig-zag from {a.zigzag}" if a.zigzag else ""))
     print("steps                | PSNR dB | per quality: errors of each copy alone, fused soft vote, lowest lattice share")
     print("                     |         | " + " | ".join(f"Q = {q}" for q in a.qualities.split(",")))
-    for name, how in ((f"uniform {a.delta:g}", {}), (a.steps if len(a.steps) < 20 else "table", dict(steps=table))):
-        stego, used = batch.embed_frames(cover, a.delta, a.n_ac, stream, mode="exact", **rule, **kw, **how)
+    label = a.steps if len(a.steps) < 20 else "table"
+    rows = [(f"uniform {a.delta:g}", {}, {}), (label, dict(steps=table), {})]
+    if a.readback:
+        rows.append((label + " + rb", dict(steps=table), dict(readback_stepped=True)))
+    for name, how, rb in rows:
+        stego, used, *counts = batch.embed_frames(cover, a.delta, a.n_ac, stream, mode="exact", **rule, **kw, **how, **rb)
         assert used == stream.size
         cells = []
         for quality in (int(q) for q in a.qualities.split(",")):
@@ -75,7 +88,8 @@ if a.steps:
             hist, _ = batch.extract_histogram_frames(seen, a.delta, a.n_ac, **kw, **how)
             cells.append("/".join(str(int((g != payload).sum())) for g in got) + f", {int((voted != payload).sum())}, "
                          f"{soft.lattice_share(hist).min():.3f}")
-        print(f"{name:20s} | {psnr(stego, cover):7.2f} | " + " | ".join(cells))
+        print(f"{name:20s} | {psnr(stego, cover):7.2f} | " + " | ".join(cells)
+              + (f" | read-back: {counts[0].repaired} repaired, {counts[0].unrepaired} left" if counts else ""))
     sys.exit(0)
 
 stego, used, period = batch.embed_repeated_frames(cover, a.delta, a.n_ac, payload, mode="exact", nearest=a.rule == "nearest",

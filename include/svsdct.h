@@ -683,8 +683,8 @@ int svs_requantise(const uint8_t *in, uint8_t *out, const svs_planes *planes, co
  * The host forms go through the per-thread staging context: whole frames under an order or a dither, chunks otherwise.
  * Limits: both sides must hold the table; a matched table is tuned to ONE codec table on the aligned luminance grid (README.md
  * has the survival table, from the CPU model; a table matched to a fine codec table needs a floor, see svs_matched_steps); a
- * real encoder is not measured.  A stepped call has no read-back, colour or _str form; its soft, vote and histogram forms are
- * svs_stepped_soft_* below. */
+ * real encoder is not measured.  A stepped call has no colour or _str form; its soft, vote and histogram forms are
+ * svs_stepped_soft_* below, its read-back form is svs_stepped_embed_readback* further below. */
 typedef struct svs_qim_steps {
     uint16_t delta[64];   /* delta[k]: the step of flat row-major coefficient k = 8u + v; k = 1..63 each 1..4095; delta[0] (DC) is not read */
 } svs_qim_steps;
@@ -820,6 +820,49 @@ int svs_embed_dithered_readback(const uint8_t *gray, uint8_t *stego, const svs_p
                                 const svs_coeffs *coeffs, const svs_dither *dither, double delta, int n_ac,
                                 const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                                 uint64_t *n_embedded, svs_readback_counts *counts);
+
+/* Read-back and repair under per-coefficient steps: svs_stepped_embed_dev / svs_stepped_embed followed, on the call's stream, by
+ * the read-back pass with coefficient k's own step in the place of delta.  A FORMAT, as the stepped and keyed formats are: it is
+ * svs_embed_dithered_readback* with delta_k for delta.  For a payload coefficient c at flat row-major index k whose slot lies
+ * inside the block's budget, c the pocketfft-identical forward transform of the stego block, every float step one IEEE float32
+ * operation with no contraction, in the same order on host and device:
+ *     dk = (float)steps->delta[k]
+ *     d  = dither_value(s_b, k, dk): the stepped calls' d = r * dk of the block's physical position; without a dither no
+ *          operation on d is executed
+ *     check   (int)rintf((c - d) / dk) & 1 against the payload bit of the slot: svs_stepped_extract*'s own verdict
+ *     target  cp = c - d
+ *             q  = (int)rintf(cp / dk)
+ *             where the parity is wrong:  q = cp * (1.0f / dk) >= (float)q ? q + 1 : q - 1      (the neighbour on cp's side)
+ *             T  = (float)q * dk + d
+ * Everything else is SVS_READBACK's, unchanged: the over-relaxed correction (T - c) * (1 + it / 2), the inverse, the shift off
+ * 0 / 255, round-half-even and clip, at most 16 iterates, accepted only when the check confirms every bit.  The side test takes
+ * the reciprocal so that a uniform table (every delta[k] = D) gives, byte for byte and count for count, the output of
+ * svs_embed_dithered_readback* at delta = D with the same order, selection, dither and rule (1.0f / D is that call's own
+ * reciprocal) - and so, without a selection and a dither, svs_embed_readback*'s; the stepped body of the kernel runs all the
+ * same: a uniform table is not rerouted.
+ *   steps  : as svs_stepped_embed*: checked first, before the other options and before any device work.
+ *   order, coeffs, dither : each may be NULL; checked next (dither, then coeffs, then flags) as in svs_stepped_embed*.
+ *   flags  : the mode bits are accepted and change nothing; SVS_NEAREST and SVS_MINMOVE; SVS_READBACK is accepted and implied;
+ *            anything else: SVS_ERR_INVALID_ARG before any device work.  (svs_stepped_embed* itself keeps refusing SVS_READBACK.)
+ *   d_counts / counts : as in svs_embed_readback*: d_counts is added to.
+ * Contract: the call first writes exactly the stego of svs_stepped_embed* with the same arguments (in place allowed), then runs
+ * the pass on the same stream; a block that reads back keeps its bytes; an unrepaired block keeps them too and is counted;
+ * blocks past the budget are untouched.  The host form stages whole frames under an order or a dither, chunks otherwise, and
+ * sums the counts over its chunks.
+ * Limits: SVS_READBACK's - a block that clips at both ends can stay unrepaired - and the stepped calls'.  A repaired block is
+ * accepted because it decodes, not because it lies on a lattice point: through a requantising channel it may survive worse than
+ * an untouched block (README.md has the measured table; an acceptance margin on the soft byte is not built).  There is no
+ * colour and no _str form.  Cost: the stepped embed plus one launch of the read-back kernel's keyed instantiation, about 1.01 -
+ * 1.06 x svs_embed_dithered_readback_dev at the same settings (README.md, profiles/stepped_readback_rates.txt). */
+int svs_stepped_embed_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                                   const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                                   const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                                   uint64_t *n_embedded, uint64_t *d_counts, void *stream);
+
+int svs_stepped_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                               const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                               const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                               uint64_t *n_embedded, svs_readback_counts *counts);
 
 /* ---- colour plumbing around the operator (device resident) --------------------------------------------
  * Interleaved 8-bit BGR frames [frame][row][col][3] <-> gray planes.  bgr_row_pitch / bgr_frame_pitch in bytes,

@@ -248,7 +248,8 @@ int launch_requantise(uint64_t total, hipStream_t st, const uint8_t *in, uint8_t
 // they run the colour body of their quantiser mode, which lives in one instantiation (plain and keep-colour output alike).
 // A plan with a non-prefix selection or a dither (svs_embed_dithered_readback_dev; `k` as launch_embed takes it) runs the keyed
 // form, form = SVS_RB_SEL + its quantiser mode, in the same instantiation, with svs_route.hpp's readback_tables; a call
-// without an order adds SVS_RB_RASTER.
+// without an order adds SVS_RB_RASTER.  A stepped plan (svs_stepped_embed_readback_dev) runs the stepped form, form = SVS_RB_STEP,
+// there too: the same tables and the call's StepArgs, which every other launch passes empty.
 int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uint8_t *stego, svs::Geometry g, const uint32_t *bits,
                     uint64_t *counts, const svs::KernelOptions &k, const svs::ColourParams &colour, uint32_t form) {
     const svs::BlockOrderArgs &ord = k.ord;
@@ -257,22 +258,27 @@ int launch_readback(const svs::EmbedPlan &p, uint64_t total, hipStream_t st, uin
     const uint32_t words = (uint32_t)p.n_words;
     auto *c = reinterpret_cast<unsigned long long *>(counts);
     const svs::DitherArgs none{};
+    const svs::StepArgs no_steps{};
     if (form != SVS_RB_GRAY)   // the one instantiation that holds the colour bodies (svs_device.hpp SVS_RB_HOSTS_COLOUR)
         return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
-                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_BGR + p.qm), none, svs::BlockOrderArgs{});
+                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_BGR + p.qm), none, no_steps, svs::BlockOrderArgs{});
+    if (p.stepped)   // ... the stepped body
+        return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
+                      p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_STEP + (p.keyed ? 0u : SVS_RB_RASTER)),
+                      svs::readback_tables(p, k), k.steps, ord);
     if (p.selected || p.dithered)   // ... and the keyed bodies
         return launch(svs::readback_kernel<8, svs::QM_POW2, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
                       p.bit_offset, p.n_bits, words, c, colour, (uint32_t)(SVS_RB_SEL + p.qm + (p.keyed ? 0u : SVS_RB_RASTER)),
-                      svs::readback_tables(p, k), ord);
+                      svs::readback_tables(p, k), no_steps, ord);
     return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
         return dispatch<1, 2, 8>(p.rows, [&](auto u) {
             constexpr int U = decltype(u)::value;
             if (p.keyed)
                 return launch(svs::readback_kernel<U, QM, true, svs::BlockOrderArgs>, grid_for(total), 0, st, stego, g, p.qp, bits,
-                              p.bit_offset, p.n_bits, words, c, colour, form, none, ord);
+                              p.bit_offset, p.n_bits, words, c, colour, form, none, no_steps, ord);
             return launch(svs::readback_kernel<U, QM>, grid_for(total), 0, st, stego, g, p.qp, bits, p.bit_offset, p.n_bits, words, c,
-                          colour, form, none);
+                          colour, form, none, no_steps);
         });
     });
 }
@@ -869,6 +875,9 @@ int with_options(const OptionsPolicy &pol, const svs_block_order *order, const s
 // that routes it and that no kernel reads (svs_route.hpp RouteArgs::stepped).
 constexpr OptionsPolicy kSteppedEmbed{false, false, kSelectEmbedFlags, "a stepped embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE"};
 constexpr OptionsPolicy kSteppedExtract{false, false, kModeFlags, "a stepped extract takes the mode bits only"};
+// the stepped embed with read-back: SVS_READBACK is accepted and implied (svs_stepped_embed* itself keeps refusing it)
+constexpr OptionsPolicy kSteppedReadback{false, false, kGrayEmbedFlags,
+                                         "a stepped read-back embed takes the mode bits, SVS_NEAREST, SVS_MINMOVE and SVS_READBACK"};
 constexpr double kSteppedRouteDelta = 1.0;
 
 template <class Call>
@@ -1464,6 +1473,30 @@ int svs_stepped_embed(const uint8_t *gray, uint8_t *stego, const svs_planes *pla
     return with_steps(kSteppedEmbed, order, coeffs, dither, steps, flags, n_ac, [&](int n, const GrayOptions &o) {
         return embed_host(gray, stego, nullptr, planes, kSteppedRouteDelta, n, bits_packed, nullptr, bit_offset, n_bits, flags,
                           n_embedded, o);
+    });
+}
+
+// The stepped embed followed by the read-back pass in its stepped form: the keyed read-back calls inside with_steps
+int svs_stepped_embed_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                                   const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                                   const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                                   uint64_t *n_embedded, uint64_t *d_counts, void *stream) {
+    return with_steps(kSteppedReadback, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.d_counts = d_counts;
+        return embed_dev(d_gray, d_stego, planes, kSteppedRouteDelta, n, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK,
+                         n_embedded, stream, o);
+    });
+}
+
+int svs_stepped_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                               const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                               const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                               uint64_t *n_embedded, svs_readback_counts *counts) {
+    return with_steps(kSteppedReadback, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        svs_readback_counts none;
+        o.counts = counts ? counts : &none;
+        return embed_host(gray, stego, nullptr, planes, kSteppedRouteDelta, n, bits_packed, nullptr, bit_offset, n_bits,
+                          flags | SVS_READBACK, n_embedded, o);
     });
 }
 

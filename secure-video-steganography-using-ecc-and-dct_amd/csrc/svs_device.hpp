@@ -1541,6 +1541,140 @@ __device__ __forceinline__ void readback_keyed(uint32_t *wslots, u32x4 *wmeta, f
     }
 }
 
+// The stepped form (svs_stepped_embed_readback_dev): readback_keyed with a step per coefficient (svs_readback.hpp, the stepped
+// forms), behind form = SVS_RB_STEP (+ SVS_RB_RASTER).  kd as in the keyed form - its table is never empty -, `steps` the call's
+// table, by value.  The same worklist, entry layout, rounds and passes; what differs:
+//   steps   lane r of a group needs the steps of flat indices 8r .. 8r + 7, dwords 4r .. 4r + 3 of the table: selected into four
+//           registers once (twenty-eight v_cndmask, as row_slots_of_lane selects the inverse table - never indexed, a per-lane
+//           index into a kernel argument is scratch), kept packed and converted where a step is used
+//   dither  d is recomputed from the entry's s_b where it is used (svs_readback.hpp), not held in eight registers
+// No QimParams is read: the body has no quantiser mode, so it is one body, not three.
+#define SVS_RB_STEP 16u
+
+__device__ __forceinline__ RowSteps row_steps_of_lane(const StepArgs &t, uint32_t r) {
+    RowSteps st{{t.w[0], t.w[1], t.w[2], t.w[3]}};
+#pragma unroll
+    for (int u = 1; u < 8; ++u) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) st.w[j] = r == (uint32_t)u ? t.w[4 * u + j] : st.w[j];
+    }
+    return st;
+}
+
+// repair_block_stepped on eight lanes, as repair8_keyed is repair_block_keyed on eight lanes
+__device__ bool repair8_stepped(uint32_t *px, float *t, uint32_t r, const RowSlots &rs, const RowSteps &st, uint32_t nb, uint32_t hi,
+                                uint32_t lo, bool dith, uint32_t s_b) {
+    float c[8], T[8];
+    forward8<8>(px, t, r, c);
+    stepped_targets_row(c, rs, st, r, nb, hi, lo, dith, s_b, T);
+#pragma unroll 1
+    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
+        const float scale = 1.0f + 0.5f * (float)it;
+        float d[8], col[8], row[8], y[8];
+        keyed_correction_row(T, c, rs, nb, scale, d);
+#pragma unroll
+        for (int x = 0; x < 8; ++x) t[8 * r + x] = d[x];            // coefficient row r
+        wave_lds_fence();
+#pragma unroll
+        for (int u = 0; u < 8; ++u) col[u] = t[8 * u + r];          // coefficient column r
+        wave_lds_fence();
+        inverse8<8>(col, t, r, row);                                 // row r of P
+        wave_lds_fence();
+        float mn = 1e30f, mx = -1e30f;
+        repair_add_row(px[2 * r], px[2 * r + 1], row, y, mn, mx);
+        const float s = repair_shift(group8_min(mn), group8_max(mx));
+        uint32_t lo4, hi4;
+        repair_store_row(y, s, lo4, hi4);
+        px[2 * r] = lo4;
+        px[2 * r + 1] = hi4;
+        wave_lds_fence();
+        forward8<8>(px, t, r, c);
+        // s_b is hidden from the compiler HERE, once per iterate, so that d is recomputed: left to itself it computes the row's
+        // eight d ahead of the loop and holds them beside the eight float steps (133 VGPRs instead of 127)
+        uint32_t sb = s_b;
+        asm volatile("" : "+v"(sb));
+        if (group8_or(stepped_row_misses(c, rs, st, r, nb, hi, lo, dith, sb) ? 1u : 0u) == 0) return true;
+    }
+    return false;
+}
+
+__device__ __forceinline__ void readback_stepped(uint32_t *wslots, u32x4 *wmeta, float *wtiles, uint8_t *stego, const Geometry &g,
+                                                 const uint32_t *__restrict__ bits, const uint64_t bit_offset, const uint64_t n_bits,
+                                                 const uint32_t n_words, unsigned long long *counts, const DitherArgs &kd,
+                                                 const StepArgs &steps, const bool raster, const BlockOrderArgs &ord) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
+    const uint32_t n = g.n_ac;
+    const bool dith = kd.on != 0u;
+    uint32_t nb = 0;
+    uint64_t first = 0;
+    if (gblock < g.total_blocks) {
+        first = raster ? stream_first_raster(gblock, n) : stream_first<true>(gblock, n, g, ord);
+        nb = block_budget(first, n_bits, n);
+    }
+    const uint64_t mask = __ballot(nb > 0);
+    if (mask == 0) return;               // wave-uniform
+    const uint32_t total = (uint32_t)__popcll(mask);
+    const uint32_t rank = wave_rank(mask);
+    const uint32_t grp = lane >> 3, r = lane & 7u;
+    const RowSlots rs = row_slots_of_lane(kd.sel, r);
+    const RowSteps st = row_steps_of_lane(steps, r);
+    int64_t off = 0;
+    if (nb > 0) off = block_offset(gblock, g);
+    uint32_t status = 0;
+#pragma unroll 1
+    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries (at most two)
+        const bool mine = nb > 0 && rank >= base && rank < base + SVS_RB_CAP;
+        if (mine) {
+            u32x2 v[8];
+            load_rows<1>(stego + off, g.row_pitch, v);
+            uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
+#pragma unroll
+            for (int y = 0; y < 8; ++y) { e[2 * y] = v[y].x; e[2 * y + 1] = v[y].y; }
+            u32x4 m; m.z = nb; m.w = dith ? dither_seed_of(gblock, g, kd) : 0u;
+            uint32_t hi, lo;
+            payload_window(bits, n_words, bit_offset + first, hi, lo);
+            m.x = hi; m.y = lo;
+            wmeta[rank - base] = m;
+        }
+        wave_lds_fence();
+        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
+#pragma unroll 1
+        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time (at most four passes)
+            const uint32_t idx = at + grp;
+            if (idx < count) {
+                const u32x4 m = wmeta[idx];
+                uint32_t *px = wslots + idx * SVS_RB_SLOT;
+                float *t = wtiles + 64 * grp;
+                float c[8];
+                forward8<8>(px, t, r, c);
+                if (group8_or(stepped_row_misses(c, rs, st, r, m.z, m.x, m.y, dith, m.w) ? 1u : 0u) != 0) {   // uniform over the eight lanes
+                    wave_lds_fence();
+                    const bool ok = repair8_stepped(px, t, r, rs, st, m.z, m.x, m.y, dith, m.w);
+                    if (r == 0) wmeta[idx].z = m.z | (ok ? 1u : 2u) << 8;
+                }
+            }
+            wave_lds_fence();
+        }
+        if (mine) {
+            status = wmeta[rank - base].z >> 8;
+            if (status == 1) {
+                const uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
+                u32x2 v[8];
+#pragma unroll
+                for (int y = 0; y < 8; ++y) { v[y].x = e[2 * y]; v[y].y = e[2 * y + 1]; }
+                store_rows<1>(stego + off, g.row_pitch, v);
+            }
+        }
+        wave_lds_fence();
+    }
+    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
+    if (counts && lane == 0) {
+        if (rep) atomicAdd(&counts[0], (unsigned long long)__popcll(rep));
+        if (left) atomicAdd(&counts[1], (unsigned long long)__popcll(left));
+    }
+}
+
 // form = SVS_RB_GRAY: `stego` = the gray planes of g, c unused.  form = SVS_RB_BGR + the call's QuantMode: `stego` = the BGR
 // output, readback_colour - in ONE instantiation only.  The colour body depends on the quantiser mode alone (not on U, and it
 // has no order), so all three of its forms live in the instantiation whose gray body leaves the most registers free,
@@ -1552,13 +1686,16 @@ __device__ __forceinline__ void readback_keyed(uint32_t *wslots, u32x4 *wmeta, f
 // alone - all eight coefficient rows always, and raster order is a wave-uniform switch in front of the order the KEYED
 // instantiation takes - and the eight-row keyed instantiations of the two other modes sit at exactly 128 VGPRs, where any body
 // beside the gray one costs a wave per SIMD (profiles/keyed_readback_resources.txt).
+// form = SVS_RB_STEP (+ SVS_RB_RASTER): the stepped form, readback_stepped, `stego` = the gray planes, kd its table and dither,
+// `steps` the call's per-coefficient steps.  One body - it reads no QimParams - in that same instantiation, behind the sides that
+// were there first; the other seventeen carry `steps` unused, as they carry kd (profiles/stepped_readback_resources.txt).
 #define SVS_RB_HOSTS_COLOUR(U, QM, KEYED) ((U) == 8 && (QM) == QM_POW2 && (KEYED))
 template <int U, int QM, bool KEYED = false, class... Order>
 __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const Geometry g, const QimParams qp,
                                                          const uint32_t *__restrict__ bits, const uint64_t bit_offset,
                                                          const uint64_t n_bits, const uint32_t n_words,
                                                          unsigned long long *counts, const ColourParams c, const uint32_t form,
-                                                         const DitherArgs kd, const Order... order) {
+                                                         const DitherArgs kd, const StepArgs steps, const Order... order) {
     static_assert(sizeof...(Order) == (KEYED ? 1u : 0u), "KEYED instantiations take one BlockOrderArgs");
     __shared__ uint32_t slots[SVS_WG / 64][SVS_RB_CAP * SVS_RB_SLOT];
     __shared__ u32x4 meta[SVS_WG / 64][SVS_RB_CAP];
@@ -1571,6 +1708,10 @@ __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const 
             float *wt = &tiles[wave][0];
             if (form >= SVS_RB_SEL) {    // the keyed form; (form & 3) = the call's quantiser mode
                 const bool raster = (form & SVS_RB_RASTER) != 0u;
+                if (form >= SVS_RB_STEP) {   // the stepped form: after the sides that were there first; no quantiser mode
+                    readback_stepped(ws, wm, wt, stego, g, bits, bit_offset, n_bits, n_words, counts, kd, steps, raster, order...);
+                    return;
+                }
                 const uint32_t qm = form & 3u;
                 if (qm == QM_F32) readback_keyed<QM_F32>(ws, wm, wt, stego, g, qp, bits, bit_offset, n_bits, n_words, counts, kd, raster, order...);
                 else if (qm == QM_DOUBLE) readback_keyed<QM_DOUBLE>(ws, wm, wt, stego, g, qp, bits, bit_offset, n_bits, n_words, counts, kd, raster, order...);

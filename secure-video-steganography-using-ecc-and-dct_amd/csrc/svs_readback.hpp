@@ -332,4 +332,126 @@ SVS_HD uint32_t readback_step_keyed(uint32_t (&rx)[8], uint32_t (&ry)[8], const 
     return repair_block_keyed<QM>(rx, ry, sel, nb, hi, lo, qp, dith, d) ? 1u : 2u;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The stepped forms (svs_stepped_embed_readback*, include/svsdct.h): the keyed forms with coefficient k's own step
+// dk = (float)delta[k] (StepArgs) in the place of delta - a format, stated in the header.  Coefficient by coefficient:
+//   d        dither_value(s_b, k, dk) with a dither: the stepped calls' d = r * dk of the block's physical position
+//   check    (int)rintf((c - d) / dk) & 1 against window bit slot(k): svs_stepped_extract*'s own verdict
+//   target   cp = c - d;  q = (int)rintf(cp / dk), moved to the neighbour on cp's side - cp * (1.0f / dk) >= (float)q - when
+//            its parity is wrong;  T = (float)q * dk + d.  The side test takes the reciprocal so that a uniform table gives
+//            the keyed form's cp * qp.inv_delta_f >= (float)q exactly (make_qim: inv_delta_f = 1.0f / delta_f)
+// No QimParams: none of this reads the call's delta.  The correction, the inverse, the shift, the rounding and the store are
+// the keyed forms' own functions.  d is computed where it is used, from s_b - a hash and three exact float operations - not
+// held: the device's eight lanes keep the row's steps as four packed dwords and s_b, five registers instead of sixteen.
+// With every delta[k] = D the bytes, counts and status are readback_step_keyed's at delta = D.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// the four dwords of the table that hold the steps of coefficient row u (flat indices 8u .. 8u + 7), converted at use
+struct RowSteps {
+    uint32_t w[4];
+    SVS_HD float step(int v) const { return (float)((w[v >> 1] >> (16 * (v & 1))) & 0xFFFFu); }
+};
+SVS_HD RowSteps row_steps(const StepArgs &t, int u) { return RowSteps{{t.w[4 * u], t.w[4 * u + 1], t.w[4 * u + 2], t.w[4 * u + 3]}}; }
+
+// the quantiser input of coefficient v of row u: c - d under a dither, else c untouched
+SVS_HD float stepped_input(float c, bool dith, uint32_t s_b, uint32_t u, int v, float dk, float &d) {
+    d = 0.0f;
+    if (!dith) return c;
+    d = dither_value(s_b, 8u * u + (uint32_t)v, dk);
+    return c - d;
+}
+
+SVS_HD void stepped_targets_row(const float (&c)[8], const RowSlots &rs, const RowSteps &st, uint32_t u, uint32_t nb, uint32_t hi,
+                                uint32_t lo, bool dith, uint32_t s_b, float (&T)[8]) {
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const uint32_t s = rs.slot(v);
+        T[v] = 0.0f;
+        if (s < nb) {
+            const int bit = (int)window_bit_at(hi, lo, s);
+            const float dk = st.step(v);
+            float d;
+            const float cp = stepped_input(c[v], dith, s_b, u, v, dk, d);
+            int q = quant_index_by_division(cp, dk);
+            if ((q & 1) != bit) q = cp * (1.0f / dk) >= (float)q ? q + 1 : q - 1;
+            float t = (float)q * dk;
+            if (dith) t = t + d;
+            T[v] = t;
+        }
+        SVS_SCHED_FENCE();   // coefficient by coefficient: the divisions are independent, and scheduled together they cost registers
+    }
+}
+
+// does the coefficient row miss a payload bit?  svs_stepped_extract*'s own verdict
+SVS_HD bool stepped_row_misses(const float (&c)[8], const RowSlots &rs, const RowSteps &st, uint32_t u, uint32_t nb, uint32_t hi,
+                               uint32_t lo, bool dith, uint32_t s_b) {
+    bool miss = false;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const uint32_t s = rs.slot(v);
+        if (s < nb) {
+            const float dk = st.step(v);
+            float d;
+            const float cp = stepped_input(c[v], dith, s_b, u, v, dk, d);
+            miss |= ((uint32_t)quant_index_by_division(cp, dk) & 1u) != window_bit_at(hi, lo, s);
+        }
+        SVS_SCHED_FENCE();
+    }
+    return miss;
+}
+
+// one-lane forms (host emulation; the device runs the rows above on eight lanes, svs_device.hpp repair8_stepped)
+SVS_HD bool stepped_block_misses(const float (&c)[8][8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb, uint32_t hi,
+                                 uint32_t lo, bool dith, uint32_t s_b) {
+    bool miss = false;
+    for (int u = 0; u < 8; ++u)
+        miss |= stepped_row_misses(c[u], row_slots(sel, u), row_steps(steps, u), (uint32_t)u, nb, hi, lo, dith, s_b);
+    return miss;
+}
+
+SVS_HD bool repair_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
+                                 uint32_t hi, uint32_t lo, bool dith, uint32_t s_b) {
+    float c[8][8], T[8][8];
+    forward_exact(rx, ry, c);
+    for (int u = 0; u < 8; ++u)
+        stepped_targets_row(c[u], row_slots(sel, u), row_steps(steps, u), (uint32_t)u, nb, hi, lo, dith, s_b, T[u]);
+    uint32_t px[8], py[8];
+    for (int r = 0; r < 8; ++r) { px[r] = rx[r]; py[r] = ry[r]; }
+    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
+        const float scale = 1.0f + 0.5f * (float)it;   // exact
+        float e[8][8], P[8][8], Y[8][8];
+        for (int u = 0; u < 8; ++u) keyed_correction_row(T[u], c[u], row_slots(sel, u), nb, scale, e[u]);
+        for (int x = 0; x < 8; ++x) {
+            float col[8], out[8];
+            for (int u = 0; u < 8; ++u) col[u] = e[u][x];
+            pf::dct3_8(col, out);
+            for (int y = 0; y < 8; ++y) P[y][x] = out[y];
+        }
+        float mn = 1e30f, mx = -1e30f;
+        for (int y = 0; y < 8; ++y) {
+            float row[8];
+            pf::dct3_8(P[y], row);
+            repair_add_row(px[y], py[y], row, Y[y], mn, mx);
+        }
+        const float s = repair_shift(mn, mx);
+        for (int y = 0; y < 8; ++y) repair_store_row(Y[y], s, px[y], py[y]);
+        forward_exact(px, py, c);
+        if (!stepped_block_misses(c, sel, steps, nb, hi, lo, dith, s_b)) {
+            for (int r = 0; r < 8; ++r) { rx[r] = px[r]; ry[r] = py[r]; }
+            return true;
+        }
+    }
+    return false;
+}
+
+// the per-block step under per-coefficient steps (s_b: read only with dith): 0 = reads back (untouched), 1 = repaired in
+// place, 2 = could not be repaired (untouched)
+SVS_HD uint32_t readback_step_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
+                                      uint32_t hi, uint32_t lo, bool dith, uint32_t s_b) {
+    float c[8][8];
+    forward_exact(rx, ry, c);
+    if (!stepped_block_misses(c, sel, steps, nb, hi, lo, dith, s_b)) return 0;
+    return repair_block_stepped(rx, ry, sel, steps, nb, hi, lo, dith, s_b) ? 1u : 2u;
+}
+
 }  // namespace svs

@@ -59,6 +59,12 @@ READBACK_COLOUR = os.environ.get("SVS_READBACK_COLOUR", "0") == "1"
 # neither a selection nor a dither it is SVS_READBACK's pass.  Refused together with SVS_READBACK and SVS_READBACK_COLOUR (one
 # switch per path) and with SVS_KEEP_COLOUR; with SVS_FUSED_COLOUR the host-conversion gray path runs.  The same one-line report.
 READBACK_KEYED = os.environ.get("SVS_READBACK_KEYED", "0") == "1"
+# SVS_READBACK_STEPPED=1 (opt-in): the read-back and repair under SVS_STEPS (svs_stepped_embed_readback, include/svsdct.h): every
+# payload block is read back as the receiver's stepped extraction will read it, and repaired where clipping or truncation lost
+# a bit.  It needs SVS_STEPS (refused without it) and is the gray path's, with SVS_BLOCK_KEY, SVS_COEFFS, SVS_DITHER_KEY,
+# SVS_NEAREST and SVS_MINMOVE.  Refused together with SVS_READBACK, SVS_READBACK_COLOUR and SVS_READBACK_KEYED (one switch per
+# path) and with SVS_KEEP_COLOUR; with SVS_FUSED_COLOUR the host-conversion gray path runs.  The same one-line report.
+READBACK_STEPPED = os.environ.get("SVS_READBACK_STEPPED", "0") == "1"
 # SVS_NEAREST=1 (opt-in): a coefficient whose parity has to change moves to the nearer of its two neighbouring lattice points
 # instead of the reference's fixed direction (SVS_NEAREST, include/svsdct.h): about 2 dB more PSNR at the same delta.  The stego
 # frames are no longer the reference's pixels; the receiver does not change.  Allowed with every other switch.
@@ -87,7 +93,8 @@ MINMOVE = os.environ.get("SVS_MINMOVE", "0") == "1"
 # floor), or 64 comma-separated integers.  Coefficient k is quantised with its own step and DELTA is not used; a lattice point of
 # a matched table passes that codec's requantiser unchanged.  Unset: today's bytes and routes.  The receiver must set the same
 # value.  The gray path only (with SVS_FUSED_COLOUR the host-conversion gray path runs); refused together with SVS_KEEP_COLOUR,
-# SVS_READBACK, SVS_READBACK_COLOUR and SVS_READBACK_KEYED (a stepped call has no colour and no read-back form).  Allowed with
+# SVS_READBACK, SVS_READBACK_COLOUR and SVS_READBACK_KEYED (a stepped call has no colour form; its read-back is
+# SVS_READBACK_STEPPED=1).  Allowed with
 # SVS_BLOCK_KEY, SVS_COEFFS, SVS_DITHER_KEY, SVS_NEAREST and SVS_MINMOVE.
 
 
@@ -180,6 +187,13 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         print("    Error: SVS_STEPS tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK, SVS_READBACK_COLOUR atau "
               "SVS_READBACK_KEYED.")
         return False, None, None
+    if READBACK_STEPPED and tabel_langkah is None:
+        print("    Error: SVS_READBACK_STEPPED=1 memerlukan SVS_STEPS.")
+        return False, None, None
+    if READBACK_STEPPED and (KEEP_COLOUR or READBACK or READBACK_COLOUR or READBACK_KEYED):
+        print("    Error: SVS_READBACK_STEPPED tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK, SVS_READBACK_COLOUR atau "
+              "SVS_READBACK_KEYED.")
+        return False, None, None
     if kunci_dither is not None and (KEEP_COLOUR or READBACK or READBACK_COLOUR):
         print("    Error: SVS_DITHER_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK atau SVS_READBACK_COLOUR.")
         return False, None, None
@@ -263,6 +277,8 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         terdekat = dict(terdekat, steps=tabel_langkah)             # likewise
     readback_abu = READBACK or (READBACK_COLOUR and not tabel_warna)   # the gray pipeline's read-back
     rb_pipa = {"readback_keyed": True} if READBACK_KEYED else ({"readback": True} if readback_abu else {})
+    if READBACK_STEPPED:
+        rb_pipa = {"readback_stepped": True}
 
     def lapor_readback(diperbaiki, tersisa):
         print(f"    Read-back: {diperbaiki} blok diperbaiki, {tersisa} blok tidak dapat diperbaiki.")

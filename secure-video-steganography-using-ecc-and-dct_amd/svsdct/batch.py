@@ -245,7 +245,7 @@ def _gray_call(lib, verb, call: _GrayCall, front, delta, n_ac, back, counts=None
 
 def _steps_arg(steps, readback=False, readback_keyed=False):
     """steps= of the gray calls -> struct svs_qim_steps, None for None; every ValueError it can cause is raised here, before the
-    library is loaded (a stepped call has no read-back form)"""
+    library is loaded (steps with readback / readback_keyed is refused: the stepped read-back is readback_stepped's path)"""
     if steps is None:
         return None
     if readback or readback_keyed:
@@ -253,18 +253,32 @@ def _steps_arg(steps, readback=False, readback_keyed=False):
     return _steps.steps_struct(steps)
 
 
-def _stepped_call(lib, verb, call: _GrayCall, steps, front, n_ac, back, stream=()) -> None:
+def _readback_stepped_arg(readback_stepped, steps, readback=False, readback_keyed=False) -> bool:
+    """one switch per path: readback_stepped is svs_stepped_embed_readback*'s.  It needs steps and excludes the two other
+    read-back switches; raised before the library is loaded (and before _steps_arg's own refusal, which names the pair it
+    refuses: steps with readback / readback_keyed stays refused without this switch)."""
+    if not readback_stepped:
+        return False
+    if readback or readback_keyed:
+        raise ValueError("readback_stepped is a path of its own: drop readback / readback_keyed")
+    if steps is None:
+        raise ValueError("readback_stepped needs steps: the read-back of a call without them is readback / readback_keyed")
+    return True
+
+
+def _stepped_call(lib, verb, call: _GrayCall, steps, front, n_ac, back, stream=(), counts=()) -> None:
     """svs_stepped_<verb>(*front, order, coeffs, dither, steps, n_ac, *back), or with stream = (handle,) its _dev form with the
-    stream last; raises unless it returns SVS_OK.  The call's delta is not an argument: the table replaces it."""
+    stream last; raises unless it returns SVS_OK.  The call's delta is not an argument: the table replaces it.  counts =
+    (pointer,): the counts argument of the read-back form (verb "embed_readback"), behind `back`."""
     name = f"svs_stepped_{verb}" + ("_dev" if stream else "")
-    args = [*front, _ref(call.order), _ref(call.sel), _ref(call.dith), C.byref(steps), int(n_ac), *back, *stream]
+    args = [*front, _ref(call.order), _ref(call.sel), _ref(call.dith), C.byref(steps), int(n_ac), *back, *counts, *stream]
     native.check(getattr(lib, name)(*args), name)
 
 
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
-                 steps=None):
+                 steps=None, readback_stepped: bool = False):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
@@ -296,8 +310,13 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     steps : None, or a table of 64 per-coefficient QIM steps (opt-in, svsdct/steps.py: steps.matched(75), steps.uniform(20);
     svs_stepped_embed, include/svsdct.h): coefficient k is quantised with steps[k] and the call's delta is not used.  It
     combines with block_key, coeffs, dither_key, nearest and minmove and runs the exact kernels in every mode; ValueError with
-    readback or readback_keyed.  The receiver must use the same table.
-    Returns (stego uint8 [F,H,W], n_embedded), with readback or readback_keyed (stego, n_embedded, ReadbackCounts)."""
+    readback or readback_keyed: its read-back form is readback_stepped.  The receiver must use the same table.
+    readback_stepped : opt-in (svs_stepped_embed_readback, include/svsdct.h): the read-back and repair under steps - every
+    payload block is read back with the stepped extraction's own verdict and repaired where it fails.  It needs steps and
+    combines with block_key, coeffs, dither_key, nearest, minmove and first_frame; ValueError with readback or readback_keyed.
+    Returns (stego uint8 [F,H,W], n_embedded), with readback, readback_keyed or readback_stepped (stego, n_embedded,
+    ReadbackCounts)."""
+    stepped_rb = _readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
     table = _steps_arg(steps, readback, readback_keyed)
     call = _resolve(n_ac, None, block_key, first_frame, coeffs, dither_key, readback, readback_keyed)
     lib = native.load()
@@ -317,8 +336,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     planes = Planes.contiguous(f, h, w)
     counts = native.ReadbackCounts()
     if table is not None:
-        _stepped_call(lib, "embed", call, table, [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], n_ac,
-                      [packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done)])
+        _stepped_call(lib, "embed_readback" if stepped_rb else "embed", call, table,
+                      [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], n_ac,
+                      [packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done)],
+                      counts=(C.byref(counts),) if stepped_rb else ())
+        if stepped_rb:
+            return stego, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
         return stego, int(done.value)
     _gray_call(lib, "embed", call, [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], delta, n_ac,
                [packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done)],
@@ -559,7 +582,7 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, first_frame: int | None = None,
-                 readback_keyed: bool = False, steps=None) -> int:
+                 readback_keyed: bool = False, steps=None, readback_stepped: bool = False) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
     native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
     read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
@@ -568,15 +591,18 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
     frame index is first_frame, by default the order's (0 without one) - the two must agree.  readback_keyed: the read-back
     pass under coeffs and / or dither_key (svs_embed_dithered_readback_dev; d_counts as with readback); with neither it makes
     the readback call; ValueError together with readback.  steps: per-coefficient QIM steps, as embed_frames
-    (svs_stepped_embed_dev; delta is then not used)."""
+    (svs_stepped_embed_dev; delta is then not used).  readback_stepped: the read-back pass under steps
+    (svs_stepped_embed_readback_dev; d_counts as with readback); it needs steps; ValueError with readback or readback_keyed."""
     _one_readback(readback, readback_keyed)      # ahead of the mode's ValueError
+    stepped_rb = _readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
     done = C.c_uint64(0)
     flags = embed_flags(mode, nearest, minmove)
     table = _steps_arg(steps, readback, readback_keyed)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key, readback, readback_keyed)
     if table is not None:
-        _stepped_call(native.load(), "embed", call, table, [d_gray, d_stego, C.byref(planes)], n_ac,
-                      [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], (stream or None,))
+        _stepped_call(native.load(), "embed_readback" if stepped_rb else "embed", call, table, [d_gray, d_stego, C.byref(planes)],
+                      n_ac, [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], (stream or None,),
+                      counts=(d_counts or None,) if stepped_rb else ())
         return int(done.value)
     _gray_call(native.load(), "embed", call, [d_gray, d_stego, C.byref(planes)], delta, n_ac,
                [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], d_counts or None, (stream or None,))

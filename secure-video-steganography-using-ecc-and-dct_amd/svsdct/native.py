@@ -164,6 +164,10 @@ SIGNATURES = {
                                                    C.c_uint64, C.c_uint32, _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_dithered_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64,
                                                C.c_uint32, _u64p, C.POINTER(ReadbackCounts)]),
+    "svs_stepped_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64,
+                                                  C.c_uint32, _u64p, C.c_void_p, C.c_void_p]),
+    "svs_stepped_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64,
+                                              C.c_uint32, _u64p, C.POINTER(ReadbackCounts)]),
     "svs_extract_dev": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
     "svs_extract": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_bgr_to_gray_dev": (C.c_int, [_u8p, C.c_int64, C.c_int64, _u8p, _PL, C.c_void_p, C.c_void_p]),

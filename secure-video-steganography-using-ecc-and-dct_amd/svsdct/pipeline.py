@@ -52,7 +52,7 @@ class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
-                 steps=None):
+                 steps=None, readback_stepped: bool = False):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
@@ -64,8 +64,11 @@ class FramePipeline:
         dither_key (svs_embed_dithered_readback_dev, include/svsdct.h; with neither: the readback call); readback_counts()
         gives the totals; ValueError together with readback.  steps: None or a table of 64 per-coefficient QIM steps for every
         batch (svsdct/steps.py; svs_stepped_embed_dev / svs_stepped_extract_dev, include/svsdct.h): delta is then not used;
-        ValueError with readback or readback_keyed."""
+        ValueError with readback or readback_keyed.  readback_stepped: every embed batch is read back and repaired under steps
+        (svs_stepped_embed_readback_dev, include/svsdct.h); it needs steps; readback_counts() gives the totals; ValueError
+        together with readback or readback_keyed."""
         batch._one_readback(readback, readback_keyed)
+        batch._readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
         batch._steps_arg(steps, readback, readback_keyed)      # its ValueErrors, before anything is allocated
         self.steps = None if steps is None else _steps.as_table(steps)
         if height % 8 or width % 8:
@@ -99,10 +102,12 @@ class FramePipeline:
         self._payload_bits = 0
         self.readback = bool(readback)
         self.readback_keyed = bool(readback_keyed)
+        self.readback_stepped = bool(readback_stepped)
         self.nearest = bool(nearest)
         self.minmove = bool(minmove)
         self._d_counts = None
-        if self.readback or self.readback_keyed:   # {repaired, unrepaired} of every batch, added to on the device
+        if self.readback or self.readback_keyed or self.readback_stepped:
+            # {repaired, unrepaired} of every batch, added to on the device
             self._d_counts = _device(16)
             native.check(self.lib.svs_memset(self._d_counts, 0, 16, None), "svs_memset")
             native.check(self.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
@@ -144,6 +149,8 @@ class FramePipeline:
 
     def _readback(self) -> dict:
         """the read-back keyword of an embed submit: one switch per path, and only the one that is on"""
+        if self.readback_stepped:
+            return {"readback_stepped": True}
         return {"readback_keyed": True} if self.readback_keyed else {"readback": self.readback}
 
     def submit_embed(self, slot: int, n_frames: int, bit_offset: int, first_frame: int = 0) -> int:
@@ -190,7 +197,7 @@ class FramePipeline:
 
     def readback_counts(self) -> "batch.ReadbackCounts":
         """(repaired, unrepaired) blocks over every embed batch submitted so far (waits for all slots)"""
-        if not (self.readback or self.readback_keyed):
+        if not (self.readback or self.readback_keyed or self.readback_stepped):
             raise RuntimeError("the pipeline was created without readback")
         for s in self._slots:
             native.check(self.lib.svs_stream_synchronize(s["stream"]), "svs_stream_synchronize")
