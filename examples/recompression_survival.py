@@ -8,7 +8,7 @@ lattice (soft.lattice_share).
 
     python examples/recompression_survival.py [--delta 20] [--n-ac 10] [--rule reference|nearest|minmove]
                                               [--zigzag FIRST] [--qualities 100,95,90,85,75,50]
-                                              [--steps q75x2 | q95x2f16 | d1,...,d64 [--readback] [--letterbox]]
+                                              [--steps q75x2 | q95x2f16 | d1,...,d64 [--readback [--margin G]] [--letterbox]]
 
 Everything runs on the GPU through the library.  The channel is a format, so the numbers equal those of the CPU model
 (tests/channel_lib.py) for the same seed - at the defaults the reference-rule row of README.md's table: no error down to
@@ -24,6 +24,9 @@ only where the codec's is - README.md has the tables, from the CPU models (tests
 --readback (with --steps) adds a third row: the stepped embed with its read-back and repair (readback_stepped=True;
 svs_stepped_embed_readback), and the blocks it repaired / left.  On the default cover nothing clips and the row equals the
 second; --letterbox blacks out a sixth of the rows at the top and at the bottom, where the plain rows lose bits before any channel.
+--margin G (with --steps --readback; G in 1..127) adds a fourth row: the read-back followed by the soft-margin pass
+(readback_margin=G; svs_stepped_embed_readback_margin), which strengthens every block that decodes but would reach the receiver
+with a soft margin below G on some coefficient, and the blocks it strengthened / left weak.
 """
 import argparse
 import os
@@ -45,6 +48,8 @@ ap.add_argument("--qualities", default="100,95,90,85,75,50")
 ap.add_argument("--steps", default=None, metavar="SPEC",
                 help="compare the uniform delta with per-coefficient steps: q<quality>x<multiple>[f<floor>] or 64 integers")
 ap.add_argument("--readback", action="store_true", help="with --steps: a third row, the stepped embed with read-back and repair")
+ap.add_argument("--margin", type=int, default=0, metavar="G",
+                help="with --steps --readback: a fourth row, the read-back followed by the soft-margin pass at gate G (1..127)")
 ap.add_argument("--letterbox", action="store_true", help="black bars over a sixth of the rows at the top and at the bottom")
 a = ap.parse_args()
 
@@ -76,6 +81,8 @@ if a.steps:
     rows = [(f"uniform {a.delta:g}", {}, {}), (label, dict(steps=table), {})]
     if a.readback:
         rows.append((label + " + rb", dict(steps=table), dict(readback_stepped=True)))
+        if a.margin:
+            rows.append((label + f" + rb, g {a.margin}", dict(steps=table), dict(readback_margin=a.margin)))
     for name, how, rb in rows:
         stego, used, *counts = batch.embed_frames(cover, a.delta, a.n_ac, stream, mode="exact", **rule, **kw, **how, **rb)
         assert used == stream.size
@@ -89,7 +96,8 @@ if a.steps:
             cells.append("/".join(str(int((g != payload).sum())) for g in got) + f", {int((voted != payload).sum())}, "
                          f"{soft.lattice_share(hist).min():.3f}")
         print(f"{name:20s} | {psnr(stego, cover):7.2f} | " + " | ".join(cells)
-              + (f" | read-back: {counts[0].repaired} repaired, {counts[0].unrepaired} left" if counts else ""))
+              + (f" | read-back: {counts[0].repaired} repaired, {counts[0].unrepaired} left" if counts else "")
+              + (f"; margin: {counts[0].strengthened} strengthened, {counts[0].weak} weak" if "readback_margin" in rb else ""))
     sys.exit(0)
 
 stego, used, period = batch.embed_repeated_frames(cover, a.delta, a.n_ac, payload, mode="exact", nearest=a.rule == "nearest",

@@ -851,7 +851,8 @@ int svs_embed_dithered_readback(const uint8_t *gray, uint8_t *stego, const svs_p
  * sums the counts over its chunks.
  * Limits: SVS_READBACK's - a block that clips at both ends can stay unrepaired - and the stepped calls'.  A repaired block is
  * accepted because it decodes, not because it lies on a lattice point: through a requantising channel it may survive worse than
- * an untouched block (README.md has the measured table; an acceptance margin on the soft byte is not built).  There is no
+ * an untouched block (README.md has the measured table; svs_stepped_embed_readback_margin* below adds the acceptance margin on
+ * the soft byte).  There is no
  * colour and no _str form.  Cost: the stepped embed plus one launch of the read-back kernel's keyed instantiation, about 1.01 -
  * 1.06 x svs_embed_dithered_readback_dev at the same settings (README.md, profiles/stepped_readback_rates.txt). */
 int svs_stepped_embed_readback_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
@@ -863,6 +864,61 @@ int svs_stepped_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_pl
                                const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
                                const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
                                uint64_t *n_embedded, svs_readback_counts *counts);
+
+/* The soft-margin pass behind the stepped read-back (opt-in): svs_stepped_embed_readback* asks that every block decodes; these
+ * calls ask in addition that every payload coefficient reaches the receiver with a soft margin of at least min_margin - the low
+ * seven bits m of the byte svs_stepped_soft_extract* gives, the distance from the decision boundary in units of delta_k / 254.  A
+ * FORMAT, step by step:
+ *   1. Pass 1 is svs_stepped_embed_readback* with the same arguments: the same launches, the same bytes, the same `repaired` and
+ *      `unrepaired`.  With min_margin = 0 the call ends here and strengthened = weak = 0.
+ *   2. Pass 2 runs on the same stream and looks at every payload block again, on its bytes after pass 1.  For each payload
+ *      coefficient, with the check's own values - c the pocketfft-identical forward coefficient, dk and d as above -, each step
+ *      one IEEE float32 operation with no contraction, in this order (stepped_soft_byte's arithmetic):
+ *          x = c - d                            (without a dither: x = c)
+ *          q = (int)rintf(x / dk)
+ *          v = (0.5f * dk - fabsf(x - (float)q * dk)) * (254.0f / dk)
+ *      The coefficient is STRONG when q's parity is the payload bit and v >= (float)min_margin; for min_margin in 1..127 that is
+ *      exactly "the receiver's soft byte has the right bit 7 and m >= min_margin".
+ *        - a block with a wrong bit is skipped: it is pass 1's `unrepaired`;
+ *        - a block that is strong throughout is untouched;
+ *        - a block that decodes but has a weak coefficient is searched with the stepped read-back's own targets, correction,
+ *          inverse, shift, rounding and sixteen iterates; only the acceptance differs: the first iterate whose payload
+ *          coefficients are all strong is stored and counted `strengthened`.  A block that none of the sixteen makes strong
+ *          keeps its bytes - pass 1's, which decode - and is counted `weak`.
+ *   3. No fallback block is kept: a failed search stores nothing.  That is why the pass is a second launch and not fused.
+ *   min_margin : 0..127; more is SVS_ERR_INVALID_ARG, checked behind `steps` and ahead of everything else.  Every other argument
+ *                is checked as in svs_stepped_embed_readback*.
+ *   d_counts   : NULL, or four uint64 on the device, 8-byte aligned, added to: svs_margin_counts.  The host form zeroes *counts
+ *                and sums over its staging chunks.
+ * A caller with one delta passes a uniform table.  There is no delta form, no colour form and no _str form.
+ * Limits: the margin is the luminance model's (svsdct/channel.py: requantisation of the 8x8 luminance DCT, no real encoder);
+ * `weak` blocks remain and are counted - blocks that clip at both ends, and at small delta_k any gate near 127, which is
+ * unreachable there because the stored block's own rounding to uint8 moves a coefficient by up to about 2; a uniform table on
+ * row-major coefficients gains nothing at the quality where its lattice, not its margin, fails.  Measured (README.md, the CPU
+ * model on three 96 x 160 frames, 2 400 bits a frame, 10 coefficients, min_margin = 64, bit errors after requantisation at
+ * Q = 75 with the read-back alone / with the pass):
+ *     matched(75, 2), row-major 1..10, noise over 0..255 (clips)   143 / 16    108 of 720 blocks strengthened, 0 weak, -0.12 dB
+ *     matched(75, 2), zig-zag 1..10, letterboxed                    18 /  0      9 strengthened, 0 weak, -0.04 dB
+ *     matched(75, 2), row-major 1..10, letterboxed                  24 /  0      9 strengthened, 0 weak, -0.01 dB
+ *     uniform 20, row-major 1..10, noise                           431 / 430     4 strengthened, 0 weak, -0.01 dB
+ * Cost: one more launch of the read-back kernel's hosting instantiation: at g = 64 on 200 x 4K about 2.0 - 2.4 ms on top of
+ * svs_stepped_embed_readback_dev's 2.9 - 4.0 ms, 1.6 - 1.7 x that call; at g = 0 that call's cost (README.md,
+ * profiles/readback_margin_rates.txt). */
+typedef struct svs_margin_counts {
+    uint64_t repaired, unrepaired;   /* pass 1: svs_readback_counts */
+    uint64_t strengthened, weak;     /* pass 2 */
+} svs_margin_counts;
+
+int svs_stepped_embed_readback_margin_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
+                                          const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither,
+                                          const svs_qim_steps *steps, int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset,
+                                          uint64_t n_bits, uint32_t min_margin, uint32_t flags, uint64_t *n_embedded,
+                                          uint64_t *d_counts, void *stream);
+
+int svs_stepped_embed_readback_margin(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                                      const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                                      const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t min_margin,
+                                      uint32_t flags, uint64_t *n_embedded, svs_margin_counts *counts);
 
 /* ---- colour plumbing around the operator (device resident) --------------------------------------------
  * Interleaved 8-bit BGR frames [frame][row][col][3] <-> gray planes.  bgr_row_pitch / bgr_frame_pitch in bytes,

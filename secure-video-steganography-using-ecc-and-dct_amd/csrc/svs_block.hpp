@@ -611,9 +611,11 @@ inline ChannelArgs make_channel_args(const uint16_t (&step)[64]) {
 // w[k >> 1] is delta[k] of flat row-major coefficient k, 1..4095 (entry 0, DC, is carried and never read).  on == 0: the kernel
 // as it was.  Read by the instantiations that hold the stepped side (svs_device.hpp); k is a compile-time index in their loops,
 // so a step is a scalar shift and mask of one kernel-argument dword and one scalar conversion, read where it is used.
+#define SVS_STEP_GATE_SHIFT 8
 struct StepArgs {
-    uint32_t on;
+    uint32_t on;      // bit 0: a stepped call.  Bits 8..14, read by readback_kernel's stepped form alone: the margin pass's gate
     uint32_t w[32];
+    SVS_HD uint32_t margin_gate() const { return on >> SVS_STEP_GATE_SHIFT; }
     SVS_HD float step(int k) const { return (float)((w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu); }
     // The same value with the dword's index hidden from the compiler until this point, so that the dword is loaded HERE.  Left
     // to itself the compiler loads all 32 at the kernel's entry and holds them: extract_exact_kernel then took 100 instead of

@@ -764,6 +764,9 @@ struct GrayOptions {
     svs_readback_counts *counts = nullptr;     // the read-back calls, host: the counts of the whole call
     ExtractOutput out;                         // the extract calls: what the call writes (the soft calls: not the packed bits)
     const svs::StepArgs *steps = nullptr;      // the stepped calls: the checked table in the kernels' form
+    uint32_t min_margin = 0;                   // the margin calls: the gate of the pass behind the stepped read-back (0: none);
+                                               // d_counts is then four uint64, svs_margin_counts
+    svs_margin_counts *margin_counts = nullptr;   // the margin calls, host: the counts of the whole call (in the place of `counts`)
 
     // the kernels' forms, for a batch of g's blocks per frame (derived once per call)
     svs::KernelOptions kernel_forms(const svs::Geometry &g) const {
@@ -783,6 +786,7 @@ struct GrayOptions {
         ra.vote = out.kind == ExtractOutput::VOTE;
         ra.hist = out.kind == ExtractOutput::HIST;
         ra.stepped = steps != nullptr;
+        ra.min_margin = min_margin;
         return ra;
     }
 
@@ -794,6 +798,7 @@ struct GrayOptions {
         if (dither) c.dither = &(*d = svs_dither{dither->key, dither->first_frame + f0, 0u});
         c.d_counts = chunk_counts;
         c.counts = nullptr;
+        c.margin_counts = nullptr;
         return c;
     }
 };
@@ -880,16 +885,19 @@ constexpr OptionsPolicy kSteppedReadback{false, false, kGrayEmbedFlags,
                                          "a stepped read-back embed takes the mode bits, SVS_NEAREST, SVS_MINMOVE and SVS_READBACK"};
 constexpr double kSteppedRouteDelta = 1.0;
 
+// min_margin: the gate of the margin calls (svs_stepped_embed_readback_margin*), checked behind the table and ahead of the rest
 template <class Call>
 int with_steps(const OptionsPolicy &pol, const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither,
-                      const svs_qim_steps *steps, uint32_t flags, int n_ac, Call &&call) {
+                      const svs_qim_steps *steps, uint32_t flags, int n_ac, Call &&call, uint32_t min_margin = 0) {
     if (!steps) return fail(SVS_ERR_INVALID_ARG, "steps is NULL");
     for (int k = 1; k < 64; ++k)
         if (steps->delta[k] < 1 || steps->delta[k] > 4095)
             return fail(SVS_ERR_INVALID_ARG, "delta[%d] = %u is not in 1..4095", k, (unsigned)steps->delta[k]);
+    if (min_margin > 127) return fail(SVS_ERR_INVALID_ARG, "min_margin %u exceeds 127, the largest soft margin", (unsigned)min_margin);
     const svs::StepArgs table = svs::make_step_args(steps->delta);
     return with_options(pol, order, coeffs, dither, flags, n_ac, [&](int n, GrayOptions o) {
         o.steps = &table;
+        o.min_margin = min_margin;
         return call(n, o);
     });
 }
@@ -930,6 +938,12 @@ int embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes,
     if (p.readback && p.use > 0)
         if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, o.d_counts, k, svs::ColourParams{}, SVS_RB_GRAY))
             return rc;
+    if (p.min_margin > 0) {   // the margin pass: the stepped form once more, on the bytes the read-back left, with the gate
+        svs::KernelOptions km = k;
+        km.steps = svs::margin_steps(k.steps, p.min_margin);
+        if (int rc = launch_readback(p, total, (hipStream_t)stream, d_stego, g, bits, o.d_counts, km, svs::ColourParams{}, SVS_RB_GRAY))
+            return rc;
+    }
     if (n_embedded) *n_embedded = p.use;
     return SVS_OK;
 }
@@ -1059,9 +1073,11 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
     svs::Geometry g;
     uint64_t total = 0;
     svs_readback_counts *const counts = o.counts;
+    svs_margin_counts *const margin = o.margin_counts;   // a margin call: four counts in the place of two
     if (int rc = make_geometry(planes, n_ac, &g, &total)) return rc;
     if (n_embedded) *n_embedded = 0;
     if (counts) *counts = svs_readback_counts{0, 0};
+    if (margin) *margin = svs_margin_counts{0, 0, 0, 0};
     if (int rc = check_order(o.order)) return rc;
     if (total == 0) return SVS_OK;
     if (!gray || !stego) return fail(SVS_ERR_INVALID_ARG, "gray/stego pointer is NULL");
@@ -1080,16 +1096,16 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
     // download lands in the source (a pageable download blocks)
     const bool ref_first = gray_ref_out && gray_ref_out != gray && ranges_overlap(gray, stego, span);
     uint64_t done_total = 0;
-    // the read-back counts of the whole call: two u64 in c.bits behind the payload, cleared before the first chunk, added to by
-    // every chunk's readback_kernel, downloaded after the last
-    const bool readback = counts && (flags & SVS_READBACK);
-    const size_t counts_at = (payload.bits_bytes() + 7) & ~(size_t)7;
-    uint64_t got_counts[2] = {0, 0};
-    if (int rc = staged(span, 0, payload.ascii_bytes(), readback ? counts_at + 16 : payload.bits_bytes(), [&](HostStage &c) {
+    // the read-back counts of the whole call: two u64 (a margin call: four) in c.bits behind the payload, cleared before the first
+    // chunk, added to by every chunk's readback_kernel, downloaded after the last
+    const bool readback = (counts || margin) && (flags & SVS_READBACK);
+    const size_t counts_at = (payload.bits_bytes() + 7) & ~(size_t)7, counts_bytes = margin ? 32 : 16;
+    uint64_t got_counts[4] = {0, 0, 0, 0};
+    if (int rc = staged(span, 0, payload.ascii_bytes(), readback ? counts_at + counts_bytes : payload.bits_bytes(), [&](HostStage &c) {
             uint64_t rebased = 0;
             if (int rc = payload.stage(c, &rebased)) return rc;
             uint64_t *d_counts = readback ? reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(c.bits.p) + counts_at) : nullptr;
-            if (d_counts) SVS_HIP(hipMemsetAsync(d_counts, 0, 16, c.st[0]));
+            if (d_counts) SVS_HIP(hipMemsetAsync(d_counts, 0, counts_bytes, c.st[0]));
             if (ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
             uint8_t *d = static_cast<uint8_t *>(c.frames.p);
             const int rc = embed_chunks(
@@ -1103,7 +1119,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                 },
                 [&](const svs::Chunk &ch, int64_t off, hipStream_t st) { return download_pixels(stego, d, planes, ch, off, st); },
                 &done_total, o.order != nullptr || o.dither != nullptr);
-            if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, 16, hipMemcpyDeviceToHost, c.st[0]));
+            if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, counts_bytes, hipMemcpyDeviceToHost, c.st[0]));
             // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
             // thread would only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first.)
             if (!rc && gray_ref_out && gray_ref_out != gray && !ref_first) copy_gray_reference(gray_ref_out, gray, planes, frames_packed, span);
@@ -1111,7 +1127,8 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
         }))
         return rc;
     if (n_embedded) *n_embedded = done_total;
-    if (readback) *counts = svs_readback_counts{got_counts[0], got_counts[1]};
+    if (readback && margin) *margin = svs_margin_counts{got_counts[0], got_counts[1], got_counts[2], got_counts[3]};
+    else if (readback) *counts = svs_readback_counts{got_counts[0], got_counts[1]};
     return SVS_OK;
 }
 
@@ -1498,6 +1515,31 @@ int svs_stepped_embed_readback(const uint8_t *gray, uint8_t *stego, const svs_pl
         return embed_host(gray, stego, nullptr, planes, kSteppedRouteDelta, n, bits_packed, nullptr, bit_offset, n_bits,
                           flags | SVS_READBACK, n_embedded, o);
     });
+}
+
+// The stepped read-back embed followed by the margin pass (include/svsdct.h): the same calls with the gate in the options;
+// min_margin = 0 is svs_stepped_embed_readback* itself, with two more counts that stay 0
+int svs_stepped_embed_readback_margin_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                                          const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                                          const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t min_margin,
+                                          uint32_t flags, uint64_t *n_embedded, uint64_t *d_counts, void *stream) {
+    return with_steps(kSteppedReadback, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        o.d_counts = d_counts;
+        return embed_dev(d_gray, d_stego, planes, kSteppedRouteDelta, n, d_bits_packed, bit_offset, n_bits, flags | SVS_READBACK,
+                         n_embedded, stream, o);
+    }, min_margin);
+}
+
+int svs_stepped_embed_readback_margin(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                                      const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, int n_ac,
+                                      const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t min_margin,
+                                      uint32_t flags, uint64_t *n_embedded, svs_margin_counts *counts) {
+    return with_steps(kSteppedReadback, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        svs_margin_counts none;
+        o.margin_counts = counts ? counts : &none;
+        return embed_host(gray, stego, nullptr, planes, kSteppedRouteDelta, n, bits_packed, nullptr, bit_offset, n_bits,
+                          flags | SVS_READBACK, n_embedded, o);
+    }, min_margin);
 }
 
 int svs_stepped_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,

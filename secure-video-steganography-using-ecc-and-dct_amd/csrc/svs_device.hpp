@@ -1228,7 +1228,7 @@ __device__ __forceinline__ float group8_max(float v) {
 // stego; out: the last iterate), t = the group's 64-float tile.  The same operations on the same values, so the same bytes;
 // true (in all eight lanes) when an iterate read back.
 template <int QM>
-__device__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+__device__ __forceinline__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
     float c[8], T[8];
     forward8<8>(px, t, r, c);
     repair_targets_row<QM>(c, (int)r, nb, hi, lo, qp, T);
@@ -1561,9 +1561,11 @@ __device__ __forceinline__ RowSteps row_steps_of_lane(const StepArgs &t, uint32_
     return st;
 }
 
-// repair_block_stepped on eight lanes, as repair8_keyed is repair_block_keyed on eight lanes
+// repair_block_stepped on eight lanes, as repair8_keyed is repair_block_keyed on eight lanes.  gate (wave-uniform) = 0: the
+// read-back's acceptance, the iterate decodes; 1..127: the margin pass's (strengthen_block_stepped), every payload coefficient of
+// the iterate is strong - both verdicts come as two bits from one row function.
 __device__ bool repair8_stepped(uint32_t *px, float *t, uint32_t r, const RowSlots &rs, const RowSteps &st, uint32_t nb, uint32_t hi,
-                                uint32_t lo, bool dith, uint32_t s_b) {
+                                uint32_t lo, bool dith, uint32_t s_b, uint32_t gate) {
     float c[8], T[8];
     forward8<8>(px, t, r, c);
     stepped_targets_row(c, rs, st, r, nb, hi, lo, dith, s_b, T);
@@ -1593,11 +1595,20 @@ __device__ bool repair8_stepped(uint32_t *px, float *t, uint32_t r, const RowSlo
         // eight d ahead of the loop and holds them beside the eight float steps (133 VGPRs instead of 127)
         uint32_t sb = s_b;
         asm volatile("" : "+v"(sb));
-        if (group8_or(stepped_row_misses(c, rs, st, r, nb, hi, lo, dith, sb) ? 1u : 0u) == 0) return true;
+        const uint32_t bad = __builtin_expect(gate != 0u, 0) ? stepped_row_verdict(c, rs, st, r, nb, hi, lo, dith, sb, (float)gate)
+                                                             : stepped_row_misses(c, rs, st, r, nb, hi, lo, dith, sb) ? 1u : 0u;
+        if (group8_or(bad) == 0) return true;
     }
     return false;
 }
 
+// GATED false: the read-back, the body as it was - the gate is the constant 0 and every branch on it folds away.  GATED true: the
+// margin pass (svs_stepped_embed_readback_margin_dev's second launch; readback_kernel takes it when `steps` carries a gate), the
+// same body with the gate read from `steps` and a wave-uniform branch at the check, at the search's acceptance and at the counts.
+// Two bodies, so that the read-back's keeps its code; and the gated one branches at run time instead of being a third compiled
+// form, because that is what fits: with the gate known to be non-zero the compiler's margin-only body takes 131 VGPRs, with the
+// branches kept - the gate hidden from it below - the kernel stays at 128 (profiles/readback_margin_resources.txt).
+template <bool GATED>
 __device__ __forceinline__ void readback_stepped(uint32_t *wslots, u32x4 *wmeta, float *wtiles, uint8_t *stego, const Geometry &g,
                                                  const uint32_t *__restrict__ bits, const uint64_t bit_offset, const uint64_t n_bits,
                                                  const uint32_t n_words, unsigned long long *counts, const DitherArgs &kd,
@@ -1606,6 +1617,11 @@ __device__ __forceinline__ void readback_stepped(uint32_t *wslots, u32x4 *wmeta,
     const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t n = g.n_ac;
     const bool dith = kd.on != 0u;
+    uint32_t gate = 0u;   // wave-uniform, a scalar; 0: the read-back, > 0: the margin pass
+    if constexpr (GATED) {
+        gate = steps.margin_gate();
+        asm volatile("" : "+s"(gate));   // hidden: the caller has tested it, and known non-zero it folds the branches (above)
+    }
     uint32_t nb = 0;
     uint64_t first = 0;
     if (gblock < g.total_blocks) {
@@ -1648,9 +1664,15 @@ __device__ __forceinline__ void readback_stepped(uint32_t *wslots, u32x4 *wmeta,
                 float *t = wtiles + 64 * grp;
                 float c[8];
                 forward8<8>(px, t, r, c);
-                if (group8_or(stepped_row_misses(c, rs, st, r, m.z, m.x, m.y, dith, m.w) ? 1u : 0u) != 0) {   // uniform over the eight lanes
+                // searched (uniform over the eight lanes): the read-back, a block that misses a bit; the margin pass, a block that
+                // decodes and has a weak coefficient - one that misses a bit is the read-back's unrepaired block and is left
+                bool search;
+                if (__builtin_expect(gate != 0u, 0))
+                    search = group8_or(stepped_row_verdict(c, rs, st, r, m.z, m.x, m.y, dith, m.w, (float)gate)) == SVS_MARGIN_WEAK;
+                else search = group8_or(stepped_row_misses(c, rs, st, r, m.z, m.x, m.y, dith, m.w) ? 1u : 0u) != 0;
+                if (search) {
                     wave_lds_fence();
-                    const bool ok = repair8_stepped(px, t, r, rs, st, m.z, m.x, m.y, dith, m.w);
+                    const bool ok = repair8_stepped(px, t, r, rs, st, m.z, m.x, m.y, dith, m.w, gate);
                     if (r == 0) wmeta[idx].z = m.z | (ok ? 1u : 2u) << 8;
                 }
             }
@@ -1670,8 +1692,9 @@ __device__ __forceinline__ void readback_stepped(uint32_t *wslots, u32x4 *wmeta,
     }
     const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
     if (counts && lane == 0) {
-        if (rep) atomicAdd(&counts[0], (unsigned long long)__popcll(rep));
-        if (left) atomicAdd(&counts[1], (unsigned long long)__popcll(left));
+        const uint32_t at = gate != 0u ? 2u : 0u;   // svs_margin_counts: {repaired, unrepaired, strengthened, weak}
+        if (rep) atomicAdd(&counts[at], (unsigned long long)__popcll(rep));
+        if (left) atomicAdd(&counts[at + 1], (unsigned long long)__popcll(left));
     }
 }
 
@@ -1709,7 +1732,11 @@ __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const 
             if (form >= SVS_RB_SEL) {    // the keyed form; (form & 3) = the call's quantiser mode
                 const bool raster = (form & SVS_RB_RASTER) != 0u;
                 if (form >= SVS_RB_STEP) {   // the stepped form: after the sides that were there first; no quantiser mode
-                    readback_stepped(ws, wm, wt, stego, g, bits, bit_offset, n_bits, n_words, counts, kd, steps, raster, order...);
+                    // wave-uniform: a gate in `steps` makes the launch the margin pass
+                    if (steps.margin_gate() != 0u)
+                        readback_stepped<true>(ws, wm, wt, stego, g, bits, bit_offset, n_bits, n_words, counts, kd, steps, raster, order...);
+                    else
+                        readback_stepped<false>(ws, wm, wt, stego, g, bits, bit_offset, n_bits, n_words, counts, kd, steps, raster, order...);
                     return;
                 }
                 const uint32_t qm = form & 3u;

@@ -409,8 +409,11 @@ SVS_HD bool stepped_block_misses(const float (&c)[8][8], const CoeffTable &sel, 
     return miss;
 }
 
-SVS_HD bool repair_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
-                                 uint32_t hi, uint32_t lo, bool dith, uint32_t s_b) {
+// the search over the sixteen iterates; accept(c): is the iterate with these coefficients taken?  (The read-back accepts one that
+// decodes, the margin pass one that is strong throughout.)
+template <class Accept>
+SVS_HD bool search_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
+                                 uint32_t hi, uint32_t lo, bool dith, uint32_t s_b, Accept &&accept) {
     float c[8][8], T[8][8];
     forward_exact(rx, ry, c);
     for (int u = 0; u < 8; ++u)
@@ -436,12 +439,19 @@ SVS_HD bool repair_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const Coe
         const float s = repair_shift(mn, mx);
         for (int y = 0; y < 8; ++y) repair_store_row(Y[y], s, px[y], py[y]);
         forward_exact(px, py, c);
-        if (!stepped_block_misses(c, sel, steps, nb, hi, lo, dith, s_b)) {
+        if (accept(c)) {
             for (int r = 0; r < 8; ++r) { rx[r] = px[r]; ry[r] = py[r]; }
             return true;
         }
     }
     return false;
+}
+
+SVS_HD bool repair_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
+                                 uint32_t hi, uint32_t lo, bool dith, uint32_t s_b) {
+    return search_block_stepped(rx, ry, sel, steps, nb, hi, lo, dith, s_b, [&](const float (&c)[8][8]) {
+        return !stepped_block_misses(c, sel, steps, nb, hi, lo, dith, s_b);
+    });
 }
 
 // the per-block step under per-coefficient steps (s_b: read only with dith): 0 = reads back (untouched), 1 = repaired in
@@ -452,6 +462,74 @@ SVS_HD uint32_t readback_step_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], cons
     forward_exact(rx, ry, c);
     if (!stepped_block_misses(c, sel, steps, nb, hi, lo, dith, s_b)) return 0;
     return repair_block_stepped(rx, ry, sel, steps, nb, hi, lo, dith, s_b) ? 1u : 2u;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The margin forms (svs_stepped_embed_readback_margin*, include/svsdct.h states the format): a second pass over the bytes the
+// stepped pass left, which asks of every payload coefficient not only the right parity but the receiver's soft margin
+//   v = (0.5f * dk - fabsf(x - (float)q * dk)) * (254.0f / dk) >= gate,   x = c - d, q = (int)rintf(x / dk)
+// - stepped_soft_byte's arithmetic (svs_block.hpp), one float32 operation a step, so that for gate = 1..127 "strong" is exactly
+// "the byte svs_stepped_soft_extract* gives has the right bit 7 and m >= gate".  A block with a wrong bit is the stepped pass's
+// `unrepaired` and is left; a block that decodes with a weak coefficient is searched with repair_block_stepped's own targets,
+// correction, inverse, shift, rounding and iterates, and the first iterate that is strong throughout is taken.
+// ---------------------------------------------------------------------------------------------------------------------
+#define SVS_MARGIN_MISS 1u   // a payload coefficient of the row has the wrong parity
+#define SVS_MARGIN_WEAK 2u   // a payload coefficient of the row has v < gate
+
+// both verdicts of a coefficient row from one function, coefficient by coefficient: bit 0 miss, bit 1 weak
+SVS_HD uint32_t stepped_row_verdict(const float (&c)[8], const RowSlots &rs, const RowSteps &st, uint32_t u, uint32_t nb, uint32_t hi,
+                                    uint32_t lo, bool dith, uint32_t s_b, float gate) {
+    uint32_t bad = 0u;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        const uint32_t s = rs.slot(v);
+        if (s < nb) {
+            float dk = st.step(v);
+#if defined(__HIP_DEVICE_COMPILE__)
+            // the step is hidden from the compiler HERE: the search calls this once per iterate with the same row, and left to
+            // itself the compiler computes the row's eight 0.5f * dk and eight 254.0f / dk ahead of the loop and holds them
+            asm volatile("" : "+v"(dk));
+#endif
+            float d;
+            const float x = stepped_input(c[v], dith, s_b, u, v, dk, d);
+            const int q = quant_index_by_division(x, dk);
+            const float a = fabsf(x - (float)q * dk);
+            const float m = (0.5f * dk - a) * (254.0f / dk);
+            if (((uint32_t)q & 1u) != window_bit_at(hi, lo, s)) bad |= SVS_MARGIN_MISS;
+            if (!(m >= gate)) bad |= SVS_MARGIN_WEAK;
+        }
+        SVS_SCHED_FENCE();
+    }
+    return bad;
+}
+
+// one-lane forms (host emulation; the device runs the rows on eight lanes, svs_device.hpp repair8_stepped with a gate)
+SVS_HD uint32_t stepped_block_verdict(const float (&c)[8][8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb, uint32_t hi,
+                                      uint32_t lo, bool dith, uint32_t s_b, float gate) {
+    uint32_t bad = 0u;
+    for (int u = 0; u < 8; ++u)
+        bad |= stepped_row_verdict(c[u], row_slots(sel, u), row_steps(steps, u), (uint32_t)u, nb, hi, lo, dith, s_b, gate);
+    return bad;
+}
+
+// repair_block_stepped's search with the margin's acceptance: the first iterate whose payload coefficients are all strong
+SVS_HD bool strengthen_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
+                                     uint32_t hi, uint32_t lo, bool dith, uint32_t s_b, float gate) {
+    return search_block_stepped(rx, ry, sel, steps, nb, hi, lo, dith, s_b, [&](const float (&c)[8][8]) {
+        return stepped_block_verdict(c, sel, steps, nb, hi, lo, dith, s_b, gate) == 0u;
+    });
+}
+
+// the per-block step of the margin pass, gate = (float)min_margin with min_margin in 1..127: 0 = strong throughout, or a wrong
+// bit (the stepped pass's unrepaired block) - untouched either way; 1 = strengthened in place; 2 = weak, could not be
+// strengthened (untouched: the bytes the stepped pass left, which decode)
+SVS_HD uint32_t margin_step_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
+                                    uint32_t hi, uint32_t lo, bool dith, uint32_t s_b, float gate) {
+    float c[8][8];
+    forward_exact(rx, ry, c);
+    const uint32_t bad = stepped_block_verdict(c, sel, steps, nb, hi, lo, dith, s_b, gate);
+    if (bad == 0u || (bad & SVS_MARGIN_MISS)) return 0;
+    return strengthen_block_stepped(rx, ry, sel, steps, nb, hi, lo, dith, s_b, gate) ? 1u : 2u;
 }
 
 }  // namespace svs

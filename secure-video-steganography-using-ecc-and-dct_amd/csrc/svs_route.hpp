@@ -49,6 +49,9 @@ struct RouteArgs {
     // (svs_device.hpp) - QM_DOUBLE for an embed, QM_POW2 for an extract - whatever `delta` says; the callers pass a positive
     // one, and no kernel reads it
     bool stepped = false;
+    // svs_stepped_embed_readback_margin*: the gate of the soft-margin pass that follows the stepped read-back, 0..127 (0: no such
+    // pass).  Read only with stepped and readback.
+    uint32_t min_margin = 0;
 };
 
 inline bool route_selected(const RouteArgs &a) {
@@ -82,6 +85,7 @@ struct EmbedPlan {
     bool selected;            // the launch passes the call's CoeffTable (EXACT with rows = 8 only), else an empty one
     bool dithered;            // the launch switches the exact kernel's dithered side on (EXACT with rows = 8 only)
     bool stepped = false;     // the launch passes the call's StepArgs (EXACT with rows = 8 and QM_DOUBLE only), else an empty one
+    uint32_t min_margin = 0;  // stepped with readback: a second readback_kernel launch, the margin pass, follows with this gate
 };
 
 // Which kernel family (include/svsdct.h `flags`).  The streaming kernels cover one and two coefficient rows (n <= 15) inside the
@@ -118,6 +122,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.selected = selected;                // likewise: the other paths touch no coefficient
         p.dithered = a.dithered;              // likewise (EXACT with rows = 8)
         p.stepped = a.stepped;                // likewise (EXACT with rows = 8, never STREAMING: rows = 8)
+        p.min_margin = a.stepped && a.readback ? a.min_margin : 0u;
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;
@@ -225,6 +230,14 @@ inline LaunchTables embed_tables(const EmbedPlan &p, const KernelOptions &k) {
 // readback_kernel's keyed form (a selected or dithered plan): one table, the call's selection or the prefix table of n_ac
 inline DitherArgs readback_tables(const EmbedPlan &p, const KernelOptions &k) {
     return {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, p.selected && k.coeffs ? *k.coeffs : make_prefix_table(p.n_ac)};
+}
+
+// readback_kernel's stepped form as the margin pass (svs_stepped_embed_readback_margin*): the call's table with the gate in the
+// spare bits of `on` (StepArgs::margin_gate), so that no kernel signature changes.  gate 0: the table as it is, the read-back.
+inline StepArgs margin_steps(const StepArgs &steps, uint32_t gate) {
+    StepArgs s = steps;
+    s.on = 1u | (gate << SVS_STEP_GATE_SHIFT);
+    return s;
 }
 
 // extract_exact_kernel reads the selection from `sel` on either hard side: their dither carries no table.  The soft side runs

@@ -65,6 +65,11 @@ READBACK_KEYED = os.environ.get("SVS_READBACK_KEYED", "0") == "1"
 # SVS_NEAREST and SVS_MINMOVE.  Refused together with SVS_READBACK, SVS_READBACK_COLOUR and SVS_READBACK_KEYED (one switch per
 # path) and with SVS_KEEP_COLOUR; with SVS_FUSED_COLOUR the host-conversion gray path runs.  The same one-line report.
 READBACK_STEPPED = os.environ.get("SVS_READBACK_STEPPED", "0") == "1"
+# SVS_READBACK_MARGIN=g (opt-in, an integer 1..127): SVS_READBACK_STEPPED's pass followed by the soft-margin pass
+# (svs_stepped_embed_readback_margin, include/svsdct.h): a block that decodes but would reach the receiver with a soft margin
+# m < g on some payload coefficient is searched for bytes that are strong throughout.  It implies SVS_READBACK_STEPPED=1 and, as
+# that switch, needs SVS_STEPS.  The report line gains the two counts of the pass: blocks strengthened, blocks left weak.
+READBACK_MARGIN = os.environ.get("SVS_READBACK_MARGIN", "")
 # SVS_NEAREST=1 (opt-in): a coefficient whose parity has to change moves to the nearer of its two neighbouring lattice points
 # instead of the reference's fixed direction (SVS_NEAREST, include/svsdct.h): about 2 dB more PSNR at the same delta.  The stego
 # frames are no longer the reference's pixels; the receiver does not change.  Allowed with every other switch.
@@ -194,6 +199,15 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         print("    Error: SVS_READBACK_STEPPED tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK, SVS_READBACK_COLOUR atau "
               "SVS_READBACK_KEYED.")
         return False, None, None
+    gerbang = None
+    if READBACK_MARGIN:
+        if tabel_langkah is None:
+            print("    Error: SVS_READBACK_MARGIN memerlukan SVS_STEPS.")
+            return False, None, None
+        if not (READBACK_MARGIN.isdigit() and 1 <= int(READBACK_MARGIN) <= 127):
+            print(f"    Error: SVS_READBACK_MARGIN harus bilangan bulat 1..127 (bukan '{READBACK_MARGIN}').")
+            return False, None, None
+        gerbang = int(READBACK_MARGIN)
     if kunci_dither is not None and (KEEP_COLOUR or READBACK or READBACK_COLOUR):
         print("    Error: SVS_DITHER_KEY tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK atau SVS_READBACK_COLOUR.")
         return False, None, None
@@ -279,9 +293,15 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     rb_pipa = {"readback_keyed": True} if READBACK_KEYED else ({"readback": True} if readback_abu else {})
     if READBACK_STEPPED:
         rb_pipa = {"readback_stepped": True}
+    if gerbang is not None:
+        rb_pipa = {"readback_margin": gerbang}
 
-    def lapor_readback(diperbaiki, tersisa):
-        print(f"    Read-back: {diperbaiki} blok diperbaiki, {tersisa} blok tidak dapat diperbaiki.")
+    def lapor_readback(diperbaiki, tersisa, diperkuat=None, lemah=None):
+        if diperkuat is None:
+            print(f"    Read-back: {diperbaiki} blok diperbaiki, {tersisa} blok tidak dapat diperbaiki.")
+        else:
+            print(f"    Read-back: {diperbaiki} blok diperbaiki, {tersisa} blok tidak dapat diperbaiki, {diperkuat} blok diperkuat "
+                  f"(margin >= {gerbang}), {lemah} blok tetap lemah.")
         if tersisa:
             print(f"    Warning: {tersisa} blok tidak terbaca kembali dengan benar; "
                   "payload kemungkinan gagal didekripsi.")
@@ -379,8 +399,7 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
                     tulis(pipe.input(slot)[:n], pipe.embed_result(slot))
                     feeder.release(slot)
             if rb_pipa:
-                rb = pipe.readback_counts()
-                lapor_readback(rb.repaired, rb.unrepaired)
+                lapor_readback(*(pipe.margin_counts() if gerbang is not None else pipe.readback_counts()))
     disisipkan = state["disisipkan"]
     selesai = usable > 0 and disisipkan >= total_bits
     if selesai:

@@ -183,6 +183,15 @@ class ReadbackCounts(NamedTuple):
     unrepaired: int
 
 
+class MarginCounts(NamedTuple):
+    """what a readback_margin embed did: the read-back's two counts, then the margin pass's - blocks that decoded with a weak
+    coefficient and were strengthened / kept the read-back's bytes (svs_stepped_embed_readback_margin, include/svsdct.h)"""
+    repaired: int
+    unrepaired: int
+    strengthened: int
+    weak: int
+
+
 class _GrayCall(NamedTuple):
     """the gray keywords of a call, resolved: the structs it adds to the plain call and the entry points that take them"""
     order: BlockOrder | None
@@ -266,10 +275,22 @@ def _readback_stepped_arg(readback_stepped, steps, readback=False, readback_keye
     return True
 
 
+def _readback_margin_arg(readback_margin, steps, readback=False, readback_keyed=False) -> int:
+    """readback_margin=g of the gray embeds -> the gate, 0 for None.  An int 1..127; it implies readback_stepped, so it needs
+    steps and refuses readback / readback_keyed as that switch does; raised before the library is loaded."""
+    if readback_margin is None:
+        return 0
+    if isinstance(readback_margin, bool) or not isinstance(readback_margin, (int, np.integer)) or not 1 <= int(readback_margin) <= 127:
+        raise ValueError("readback_margin is an int in 1..127: the smallest soft margin m a payload coefficient may be left with")
+    _readback_stepped_arg(True, steps, readback, readback_keyed)
+    return int(readback_margin)
+
+
 def _stepped_call(lib, verb, call: _GrayCall, steps, front, n_ac, back, stream=(), counts=()) -> None:
     """svs_stepped_<verb>(*front, order, coeffs, dither, steps, n_ac, *back), or with stream = (handle,) its _dev form with the
     stream last; raises unless it returns SVS_OK.  The call's delta is not an argument: the table replaces it.  counts =
-    (pointer,): the counts argument of the read-back form (verb "embed_readback"), behind `back`."""
+    (pointer,): the counts argument of the read-back forms (verbs "embed_readback" and "embed_readback_margin", whose `back`
+    carries the gate in front of the flags), behind `back`."""
     name = f"svs_stepped_{verb}" + ("_dev" if stream else "")
     args = [*front, _ref(call.order), _ref(call.sel), _ref(call.dith), C.byref(steps), int(n_ac), *back, *counts, *stream]
     native.check(getattr(lib, name)(*args), name)
@@ -278,7 +299,7 @@ def _stepped_call(lib, verb, call: _GrayCall, steps, front, n_ac, back, stream=(
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
-                 steps=None, readback_stepped: bool = False):
+                 steps=None, readback_stepped: bool = False, readback_margin: int | None = None):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
@@ -314,8 +335,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     readback_stepped : opt-in (svs_stepped_embed_readback, include/svsdct.h): the read-back and repair under steps - every
     payload block is read back with the stepped extraction's own verdict and repaired where it fails.  It needs steps and
     combines with block_key, coeffs, dither_key, nearest, minmove and first_frame; ValueError with readback or readback_keyed.
+    readback_margin : None, or an int g in 1..127 (opt-in, svs_stepped_embed_readback_margin, include/svsdct.h): after the
+    stepped read-back a second pass strengthens every block that decodes but would reach the receiver with a soft margin m < g
+    on some payload coefficient.  It implies readback_stepped: it needs steps; ValueError with readback or readback_keyed.
     Returns (stego uint8 [F,H,W], n_embedded), with readback, readback_keyed or readback_stepped (stego, n_embedded,
-    ReadbackCounts)."""
+    ReadbackCounts), with readback_margin (stego, n_embedded, MarginCounts)."""
+    gate = _readback_margin_arg(readback_margin, steps, readback, readback_keyed)
     stepped_rb = _readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
     table = _steps_arg(steps, readback, readback_keyed)
     call = _resolve(n_ac, None, block_key, first_frame, coeffs, dither_key, readback, readback_keyed)
@@ -335,6 +360,12 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     done = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
     counts = native.ReadbackCounts()
+    if gate:
+        four = native.MarginCounts()
+        _stepped_call(lib, "embed_readback_margin", call, table, [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], n_ac,
+                      [packed.ctypes.data, int(bit_offset), int(n_bits), gate, embed_flags(mode, nearest, minmove), C.byref(done)],
+                      counts=(C.byref(four),))
+        return stego, int(done.value), MarginCounts(int(four.repaired), int(four.unrepaired), int(four.strengthened), int(four.weak))
     if table is not None:
         _stepped_call(lib, "embed_readback" if stepped_rb else "embed", call, table,
                       [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], n_ac,
@@ -477,7 +508,7 @@ def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | N
     """Embed a payload more than once: soft.tile(bits, copies * len(bits)) - copy after copy, copies=None: as many as the
     stack's capacity holds, the last one cut where it ends - through embed_frames, which takes every other keyword.  There is
     no embed kernel path of its own: the tiled stream is an eighth of a byte per capacity bit.
-    Returns (stego, used, period), and the ReadbackCounts behind them where embed_frames returns them; period = len(bits) is
+    Returns (stego, used, period), and the ReadbackCounts or MarginCounts behind them where embed_frames returns them; period = len(bits) is
     what the receiver passes to extract_vote_frames."""
     if isinstance(bits, str):
         bits = str_to_bits(bits)
@@ -582,7 +613,8 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
                  bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, first_frame: int | None = None,
-                 readback_keyed: bool = False, steps=None, readback_stepped: bool = False) -> int:
+                 readback_keyed: bool = False, steps=None, readback_stepped: bool = False,
+                 readback_margin: int | None = None) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
     native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
     read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
@@ -592,13 +624,21 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
     pass under coeffs and / or dither_key (svs_embed_dithered_readback_dev; d_counts as with readback); with neither it makes
     the readback call; ValueError together with readback.  steps: per-coefficient QIM steps, as embed_frames
     (svs_stepped_embed_dev; delta is then not used).  readback_stepped: the read-back pass under steps
-    (svs_stepped_embed_readback_dev; d_counts as with readback); it needs steps; ValueError with readback or readback_keyed."""
+    (svs_stepped_embed_readback_dev; d_counts as with readback); it needs steps; ValueError with readback or readback_keyed.
+    readback_margin: an int g in 1..127, the margin pass behind that read-back (svs_stepped_embed_readback_margin_dev; it implies
+    readback_stepped; d_counts is then FOUR uint64: repaired, unrepaired, strengthened, weak)."""
     _one_readback(readback, readback_keyed)      # ahead of the mode's ValueError
+    gate = _readback_margin_arg(readback_margin, steps, readback, readback_keyed)
     stepped_rb = _readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
     done = C.c_uint64(0)
     flags = embed_flags(mode, nearest, minmove)
     table = _steps_arg(steps, readback, readback_keyed)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key, readback, readback_keyed)
+    if gate:
+        _stepped_call(native.load(), "embed_readback_margin", call, table, [d_gray, d_stego, C.byref(planes)], n_ac,
+                      [d_bits_packed, int(bit_offset), int(n_bits), gate, flags, C.byref(done)], (stream or None,),
+                      counts=(d_counts or None,))
+        return int(done.value)
     if table is not None:
         _stepped_call(native.load(), "embed_readback" if stepped_rb else "embed", call, table, [d_gray, d_stego, C.byref(planes)],
                       n_ac, [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], (stream or None,),

@@ -48,6 +48,11 @@ class ReadbackCounts(C.Structure):
     _fields_ = [("repaired", C.c_uint64), ("unrepaired", C.c_uint64)]
 
 
+class MarginCounts(C.Structure):
+    """struct svs_margin_counts: the read-back's two counts and the margin pass's (svs_stepped_embed_readback_margin*)"""
+    _fields_ = [("repaired", C.c_uint64), ("unrepaired", C.c_uint64), ("strengthened", C.c_uint64), ("weak", C.c_uint64)]
+
+
 class BlockOrder(C.Structure):
     """struct svs_block_order: the keyed block order of the ordered entry points (include/svsdct.h, svsdct/order.py)"""
     _fields_ = [("key", C.c_uint64), ("first_frame", C.c_uint32), ("reserved", C.c_uint32)]
@@ -168,6 +173,10 @@ SIGNATURES = {
                                                   C.c_uint32, _u64p, C.c_void_p, C.c_void_p]),
     "svs_stepped_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64,
                                               C.c_uint32, _u64p, C.POINTER(ReadbackCounts)]),
+    "svs_stepped_embed_readback_margin_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64,
+                                                         C.c_uint32, C.c_uint32, _u64p, C.c_void_p, C.c_void_p]),
+    "svs_stepped_embed_readback_margin": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, C.c_int, _u8p, C.c_uint64, C.c_uint64,
+                                                     C.c_uint32, C.c_uint32, _u64p, C.POINTER(MarginCounts)]),
     "svs_extract_dev": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p, C.c_void_p]),
     "svs_extract": (C.c_int, [_u8p, _PL, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_bgr_to_gray_dev": (C.c_int, [_u8p, C.c_int64, C.c_int64, _u8p, _PL, C.c_void_p, C.c_void_p]),

@@ -52,7 +52,7 @@ class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
-                 steps=None, readback_stepped: bool = False):
+                 steps=None, readback_stepped: bool = False, readback_margin: int | None = None):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
@@ -66,8 +66,11 @@ class FramePipeline:
         batch (svsdct/steps.py; svs_stepped_embed_dev / svs_stepped_extract_dev, include/svsdct.h): delta is then not used;
         ValueError with readback or readback_keyed.  readback_stepped: every embed batch is read back and repaired under steps
         (svs_stepped_embed_readback_dev, include/svsdct.h); it needs steps; readback_counts() gives the totals; ValueError
-        together with readback or readback_keyed."""
+        together with readback or readback_keyed.  readback_margin: None or an int g in 1..127 - the margin pass behind that
+        read-back in every embed batch (svs_stepped_embed_readback_margin_dev); it implies readback_stepped; margin_counts()
+        gives the four totals, readback_counts() the first two."""
         batch._one_readback(readback, readback_keyed)
+        self.readback_margin = batch._readback_margin_arg(readback_margin, steps, readback, readback_keyed)
         batch._readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
         batch._steps_arg(steps, readback, readback_keyed)      # its ValueErrors, before anything is allocated
         self.steps = None if steps is None else _steps.as_table(steps)
@@ -102,14 +105,14 @@ class FramePipeline:
         self._payload_bits = 0
         self.readback = bool(readback)
         self.readback_keyed = bool(readback_keyed)
-        self.readback_stepped = bool(readback_stepped)
+        self.readback_stepped = bool(readback_stepped) or self.readback_margin > 0
         self.nearest = bool(nearest)
         self.minmove = bool(minmove)
         self._d_counts = None
         if self.readback or self.readback_keyed or self.readback_stepped:
-            # {repaired, unrepaired} of every batch, added to on the device
-            self._d_counts = _device(16)
-            native.check(self.lib.svs_memset(self._d_counts, 0, 16, None), "svs_memset")
+            # {repaired, unrepaired} of every batch - and behind them the margin pass's {strengthened, weak} -, added to on the device
+            self._d_counts = _device(32)
+            native.check(self.lib.svs_memset(self._d_counts, 0, 32, None), "svs_memset")
             native.check(self.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
 
     def bind_thread(self) -> None:
@@ -149,6 +152,8 @@ class FramePipeline:
 
     def _readback(self) -> dict:
         """the read-back keyword of an embed submit: one switch per path, and only the one that is on"""
+        if self.readback_margin:
+            return {"readback_margin": self.readback_margin}
         if self.readback_stepped:
             return {"readback_stepped": True}
         return {"readback_keyed": True} if self.readback_keyed else {"readback": self.readback}
@@ -205,6 +210,17 @@ class FramePipeline:
         native.check(self.lib.svs_memcpy_d2h(out.ctypes.data, self._d_counts, 16, None), "svs_memcpy_d2h")
         native.check(self.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
         return batch.ReadbackCounts(int(out[0]), int(out[1]))
+
+    def margin_counts(self) -> "batch.MarginCounts":
+        """(repaired, unrepaired, strengthened, weak) blocks over every embed batch submitted so far (waits for all slots)"""
+        if not self.readback_margin:
+            raise RuntimeError("the pipeline was created without readback_margin")
+        for s in self._slots:
+            native.check(self.lib.svs_stream_synchronize(s["stream"]), "svs_stream_synchronize")
+        out = np.zeros(4, np.uint64)
+        native.check(self.lib.svs_memcpy_d2h(out.ctypes.data, self._d_counts, 32, None), "svs_memcpy_d2h")
+        native.check(self.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+        return batch.MarginCounts(*(int(c) for c in out))
 
     def close(self) -> None:
         for s in self._slots:
