@@ -775,6 +775,69 @@ int svs_stepped_soft_histogram_dev(const uint8_t *d_gray, const svs_planes *plan
 int svs_stepped_soft_histogram(const uint8_t *gray, const svs_planes *planes, const svs_coeffs *coeffs, const svs_dither *dither,
                                const svs_qim_steps *steps, int n_ac, uint32_t *hist_out, uint32_t flags, uint64_t *n_bits_out);
 
+/* ---- matrix embedding: k bits a block for one or two parity flips ---------------------------------------------------
+ * Every other embed call writes one payload bit into the parity of one coefficient, and about half of them must be pushed into
+ * the neighbouring cell.  Matrix embedding (the (2^k - 1, k) Hamming syndrome code of F5, and its "modified" form) lets a block
+ * of n = 2^k - 1 payload coefficients carry k message bits as the syndrome of their n parities: the sender reaches any message
+ * by flipping AT MOST ONE parity (search 0), or the cheaper of one flip and a pair of flips (search 1).  The receiver needs no
+ * side information.  Opt-in, and it pays off under SVS_MINMOVE alone, where a coefficient whose parity is right mostly stays
+ * where it is (README.md has the table); under the other rules every selected coefficient is pulled to a lattice point, so more
+ * carriers cost more.  These are STEPPED calls: a caller with one delta passes a uniform table.  A FORMAT, step by step:
+ *   selection : `coeffs` when given, else the row-major prefix 1..n_ac.  It must have exactly n = 2^k - 1 entries.  Slot t in
+ *               0..n-1 of a block is entry t of the selection, as in the select calls.
+ *   stream    : a block carries k bits.  Block j of the call's stream order (raster, or keyed with an order) owns stream bits
+ *               [j k, j k + k); the capacity is blocks * k (svs_matrix_capacity_bits).  The block's budget is
+ *               nb = clamp(n_bits - j k, 0, k); nb = 0: the block's bytes are the cover's.  Its message value is
+ *               m = sum over i < nb of bit_i * 2^i; bits past the budget count as 0.
+ *   parities  : p_t = rintf(x_t / delta_k) & 1 with x_t = c_t - d_t, exactly svs_stepped_extract*'s verdict (d = 0 without a
+ *               dither); the syndrome S = XOR over the slots t with p_t = 1 of (t + 1).
+ *   extract   : bit i of the block is (S >> i) & 1, all k bits of every block; the output is the packed stream of blocks * k
+ *               bits and *n_bits_out the capacity.
+ *   embed     : j = S ^ m; the flip set F is a set of slots.  j = 0: F is empty.  search 0: F = {j - 1}.  search 1: with
+ *               stay_t = rule(x_t, p_t) and flip_t = rule(x_t, p_t ^ 1), the rule being the stepped calls' for the call's flags, in
+ *               float32 with one IEEE operation a step  a = flip_t - x_t;  b = stay_t - x_t;  e_t = a * a - b * b;  start with
+ *               best = e_{j-1}, F = {j - 1}; for a = 1, 2, .., n in this order with b = a ^ j and a < b: v = e_{a-1} + e_{b-1};
+ *               if v < best (strictly) then best = v and F = {a - 1, b - 1}.
+ *               Then EVERY one of the n selected coefficients is written by the stepped rule with the bit p_t ^ [t in F] -
+ *               reference, SVS_NEAREST or SVS_MINMOVE as the flags say, with the band, the dither and "a coefficient the rule
+ *               leaves alone keeps c exactly" as in the stepped calls.  The inverse, clip and truncate are the reference's.
+ *               *n_embedded = min(n_bits, capacity).
+ * Order, dither and first-frame rules are svs_stepped_embed*'s.  With k = 1 the embed gives, byte for byte,
+ * svs_stepped_embed* with the same one-coefficient selection, table, order, dither and rule, and the extract gives
+ * svs_stepped_extract*'s bits, for both search values; a k = 1 call runs the matrix side of the kernels all the same.
+ * Refused with SVS_ERR_INVALID_ARG before any device work: a NULL matrix or steps; k outside 1..6; search > 1; reserved != 0;
+ * search 1 with k = 6 (the embed keeps n floats per lane in a wave-private LDS tile and the pair search n more: 126 of them for
+ * 256 lanes exceed the 64 KB a launch may request); a selection or n_ac of a size other than 2^k - 1; SVS_READBACK, SVS_KEEP_COLOUR and every flag
+ * the stepped calls refuse; SVS_NEAREST or SVS_MINMOVE on extract.  The host forms stage whole frames, as the keyed calls do.
+ * Limits: a message bit depends on about n / 2 parities, so one disturbed coefficient corrupts up to k bits of its block: a
+ * quality option for channels the lattice survives.  Clipping blocks are not repaired (no read-back form), so SVS_MINMOVE's
+ * guarantee that a stego frame decodes excludes them.  No soft, vote, histogram, read-back, margin, colour or _str form. */
+typedef struct svs_matrix {
+    uint32_t k;             /* message bits a block, 1..6; the selection has 2^k - 1 coefficients */
+    uint32_t search;        /* 0: the syndrome's single flip;  1: the cheapest of a single flip or a pair (k <= 5) */
+    uint32_t reserved[2];   /* must be 0 */
+} svs_matrix;
+
+/* blocks * k; 0 for a NULL pointer, a k outside 1..6 or planes svs_capacity_bits gives 0 for */
+uint64_t svs_matrix_capacity_bits(const svs_planes *p, const svs_matrix *m);
+
+int svs_matrix_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                         const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix,
+                         int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                         uint64_t *n_embedded, void *stream);
+
+int svs_matrix_embed(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                     const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix, int n_ac,
+                     const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded);
+
+int svs_matrix_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                           const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix, int n_ac,
+                           uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream);
+
+int svs_matrix_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                       const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix, int n_ac,
+                       uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out);
+
 /* ---- the operator with read-back and repair (SVS_READBACK) ---------------------------------------------
  * svs_embed_ordered_dev / svs_embed_ordered with SVS_READBACK implied (order may be NULL), plus the counts of the read-back:
  *   d_counts : NULL, or a device buffer of two uint64 (8-byte aligned) that the call ADDS {blocks repaired, blocks left

@@ -612,10 +612,14 @@ inline ChannelArgs make_channel_args(const uint16_t (&step)[64]) {
 // as it was.  Read by the instantiations that hold the stepped side (svs_device.hpp); k is a compile-time index in their loops,
 // so a step is a scalar shift and mask of one kernel-argument dword and one scalar conversion, read where it is used.
 #define SVS_STEP_GATE_SHIFT 8
+#define SVS_STEP_MATRIX_SHIFT 16
 struct StepArgs {
-    uint32_t on;      // bit 0: a stepped call.  Bits 8..14, read by readback_kernel's stepped form alone: the margin pass's gate
+    uint32_t on;      // bit 0: a stepped call.  Bits 8..14, read by readback_kernel's stepped form alone: the margin pass's gate.
+                      // Bits 16..19, read by the two exact kernels' stepped sides alone: a matrix call (svs_matrix_*) - k in
+                      // bits 16..18, the pair search in bit 19 (make_matrix_word); a matrix call never reaches readback_kernel
     uint32_t w[32];
     SVS_HD uint32_t margin_gate() const { return on >> SVS_STEP_GATE_SHIFT; }
+    SVS_HD uint32_t matrix() const { return on >> SVS_STEP_MATRIX_SHIFT; }   // 0: no matrix call; else k | search << 3
     SVS_HD float step(int k) const { return (float)((w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu); }
     // The same value with the dword's index hidden from the compiler until this point, so that the dword is loaded HERE.  Left
     // to itself the compiler loads all 32 at the kernel's entry and holds them: extract_exact_kernel then took 100 instead of
@@ -1265,6 +1269,146 @@ SVS_HD void embed_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t n
     if (kind == (uint32_t)RULE_MINMOVE) qim_stepped_selected<RULE_MINMOVE, DITH>(D2, sel, steps, nb, hi, lo, s_b);
     else if (kind == (uint32_t)RULE_NEAREST) qim_stepped_selected<RULE_NEAREST, DITH>(D2, sel, steps, nb, hi, lo, s_b);
     else qim_stepped_selected<RULE_REFERENCE, DITH>(D2, sel, steps, nb, hi, lo, s_b);
+    inverse_exact_paired<false>(D2, rx, ry);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Matrix embedding (svs_matrix_embed* / svs_matrix_extract*, include/svsdct.h "matrix embedding"): a block's k message bits are
+// the syndrome of the parities of its n = 2^k - 1 selected coefficients under the (n, k) Hamming code, so the sender flips at
+// most one parity - or, with the pair search, the cheaper of one or two.  A stepped call: the parity is svs_stepped_extract*'s
+// verdict, and every selected coefficient is written by the stepped rule with its own parity, flipped where the code says so.
+// The parity window is the payload window's form: slot t at bit 63 - t of hi:lo.
+// ---------------------------------------------------------------------------------------------------------------------
+// bits of the window half (LOW: slots 32..62) whose slot t has bit I of t + 1 set
+constexpr uint32_t matrix_mask_bits(int i, bool low) {
+    uint32_t m = 0;
+    for (int t = low ? 32 : 0; t < (low ? 63 : 32); ++t)
+        if (((t + 1) >> i) & 1) m |= 1u << ((63 - t) & 31);
+    return m;
+}
+
+template <int I = 0>
+SVS_HD uint32_t matrix_syndrome(uint32_t hi, uint32_t lo) {   // XOR of t + 1 over the set slots t: six masked parities
+    constexpr uint32_t MH = matrix_mask_bits(I, false), ML = matrix_mask_bits(I, true);
+    const uint32_t bit = ((uint32_t)(__builtin_popcount(hi & MH) + __builtin_popcount(lo & ML)) & 1u) << I;
+    if constexpr (I < 5) return bit | matrix_syndrome<I + 1>(hi, lo);
+    else return bit;
+}
+
+// the message value of a block with a budget of nb <= 6 bits: stream bit i (bit 31 - i of the payload window) is bit i of m
+SVS_HD uint32_t matrix_message(uint32_t hi, uint32_t nb) {
+    uint32_t m = 0;
+    for (int i = 0; i < 6; ++i) m |= ((hi >> (31 - i)) & 1u) << i;
+    return m & ((1u << nb) - 1u);
+}
+
+// ... and back: the syndrome as the block's k stream bits, MSB first in hi
+SVS_HD void matrix_fold(uint32_t &hi, uint32_t &lo) {
+    const uint32_t S = matrix_syndrome(hi, lo);
+    hi = 0;
+    for (int i = 0; i < 6; ++i) hi |= ((S >> i) & 1u) << (31 - i);
+    lo = 0;
+}
+
+// One pass over the selected coefficients of a block in embed_block_exact's paired layout.  For slot s of coefficient K, with
+// x = c - d the rule's input: the parity p = rintf(x / dk) & 1 (stepped_parities' verdict) goes into the window hi:lo; the value
+// the stepped rule writes for the bit p (stepped_value's, dither and "leave c alone" included) goes into D2; the value it writes
+// for the bit p ^ 1 goes to flipped[s * stride]; and with COSTS the pair search's cost of flipping the slot goes to
+// e[s * stride]: stay = rule(x, p), flip = rule(x, p ^ 1), a = flip - x; b = stay - x; e = a a - b b, one float32 operation a step.
+// `flipped` and `e` are the lane's own columns of its wave's tile (device: dynamic LDS, stride 64 - written here at a wave-uniform
+// slot, read back at a per-lane one).  The rule is a wave-uniform run-time branch per coefficient, not three loops: every read of
+// the tables through the kernel's arguments counts against the compiler's limit for reading them in place (StepArgs::quad_here).
+template <bool DITH, bool COSTS, int K = 1>
+SVS_HD void matrix_pass(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, const StepArgs &steps, uint32_t kind, uint32_t &hi, uint32_t &lo,
+                        uint32_t s_b, float *flipped, float *e, uint32_t stride) {
+    const uint32_t s = sel.slot(K);
+    if (s < sel.count) {  // wave-uniform
+        const float dk = steps.step(K);
+        const float c = D2[K >> 4][K & 7][(K >> 3) & 1];
+        float d = 0.0f, x = c;
+        if constexpr (DITH) {
+            d = dither_value(s_b, (uint32_t)K, dk);
+            x = c - d;
+        }
+        const int p = quant_index_by_division(x, dk) & 1;
+        const uint32_t bit = (uint32_t)p << ((31u - s) & 31u);
+        if (s < 32u) hi |= bit;
+        else lo |= bit;
+        float stay, flip;
+        if (kind == (uint32_t)RULE_MINMOVE) {
+            stay = stepped_target<RULE_MINMOVE>(x, p, dk, (uint32_t)K);
+            flip = stepped_target<RULE_MINMOVE>(x, p ^ 1, dk, (uint32_t)K);
+        } else if (kind == (uint32_t)RULE_NEAREST) {
+            stay = stepped_target<RULE_NEAREST>(x, p, dk, (uint32_t)K);
+            flip = stepped_target<RULE_NEAREST>(x, p ^ 1, dk, (uint32_t)K);
+        } else {
+            stay = stepped_target<RULE_REFERENCE>(x, p, dk, (uint32_t)K);
+            flip = stepped_target<RULE_REFERENCE>(x, p ^ 1, dk, (uint32_t)K);
+        }
+        if constexpr (COSTS) {
+            const float a = flip - x, b = stay - x;
+            const float aa = a * a, bb = b * b;
+            e[s * stride] = aa - bb;
+        }
+        if constexpr (DITH) {   // as stepped_value: a coefficient the rule leaves alone keeps c exactly
+            stay = __builtin_bit_cast(uint32_t, stay) == __builtin_bit_cast(uint32_t, x) ? c : stay + d;
+            flip = __builtin_bit_cast(uint32_t, flip) == __builtin_bit_cast(uint32_t, x) ? c : flip + d;
+        }
+        D2[K >> 4][K & 7][(K >> 3) & 1] = stay;
+        flipped[s * stride] = flip;
+    }
+    if constexpr (K < 63) matrix_pass<DITH, COSTS, K + 1>(D2, sel, steps, kind, hi, lo, s_b, flipped, e, stride);
+}
+
+// The flip set of a block whose syndrome misses its message by j (1..n) under the pair search: the single slot j - 1, or the
+// first pair of slots {a - 1, (a ^ j) - 1}, a = 1..n in this order with a < a ^ j, whose summed cost is strictly below the best so
+// far.  fb = 64: no second slot.
+SVS_HD void matrix_search(uint32_t j, uint32_t n, const float *e, uint32_t stride, uint32_t &fa, uint32_t &fb) {
+    float best = e[(j - 1u) * stride];
+    fa = j - 1u;
+    fb = 64u;
+    for (uint32_t a = 1; a <= n; ++a) {
+        const uint32_t b = a ^ j;
+        if (a < b) {
+            const float v = e[(a - 1u) * stride] + e[(b - 1u) * stride];
+            if (v < best) { best = v; fa = a - 1u; fb = b - 1u; }
+        }
+    }
+}
+
+// the coefficients of the slots fa and fb (64: none) take the values va and vb
+template <int K = 1>
+SVS_HD void matrix_apply(pf::f32x2 (&D2)[4][8], const CoeffTable &sel, uint32_t fa, uint32_t fb, float va, float vb) {
+    const uint32_t s = sel.slot(K);
+    if (s < sel.count) {  // wave-uniform
+        const float c = D2[K >> 4][K & 7][(K >> 3) & 1];
+        D2[K >> 4][K & 7][(K >> 3) & 1] = s == fa ? va : (s == fb ? vb : c);
+    }
+    if constexpr (K < 63) matrix_apply<K + 1>(D2, sel, fa, fb, va, vb);
+}
+
+// The round trip of a matrix call: nb is the block's budget of its k stream bits (1..k), mword = StepArgs::matrix().  sel.count
+// == 2^k - 1 (the callers refuse anything else), so the syndrome, the message and j are below 2^k and every slot read is < count.
+// tile: the lane's column of its wave's tile - count values for the flipped forms and, with the pair search, count more for e.
+template <bool DITH>
+SVS_HD void embed_block_matrix(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb, uint32_t hi, uint32_t kind, const CoeffTable &sel,
+                               const StepArgs &steps, uint32_t mword, uint32_t s_b, float *tile, uint32_t stride) {
+    pf::f32x2 D2[4][8];
+    forward_exact_paired(rx, ry, D2);
+    const uint32_t n = sel.count;
+    float *e = tile + n * stride;
+    uint32_t ph = 0, pl = 0, fa = 64u, fb = 64u;
+    if (mword & 8u) {  // wave-uniform: the pair search
+        matrix_pass<DITH, true>(D2, sel, steps, kind, ph, pl, s_b, tile, e, stride);
+        const uint32_t j = matrix_syndrome(ph, pl) ^ matrix_message(hi, nb);
+        if (j) matrix_search(j, n, e, stride, fa, fb);
+    } else {
+        matrix_pass<DITH, false>(D2, sel, steps, kind, ph, pl, s_b, tile, e, stride);
+        const uint32_t j = matrix_syndrome(ph, pl) ^ matrix_message(hi, nb);
+        if (j) fa = j - 1u;
+    }
+    const float va = fa < 64u ? tile[fa * stride] : 0.0f, vb = fb < 64u ? tile[fb * stride] : 0.0f;
+    matrix_apply(D2, sel, fa, fb, va, vb);
     inverse_exact_paired<false>(D2, rx, ry);
 }
 

@@ -189,6 +189,12 @@ using svs::ExtractPath;
 // `two`: two blocks per lane, where the plan and the buffers allow it.  A keyed plan (p.keyed, `ord` its order) launches the
 // KEYED instantiation of the same kernel family, with the order as the last argument.  `k`: the call's options in the kernels'
 // forms (svs_route.hpp, which also says which tables the exact kernel gets).
+// A matrix plan is the only embed launch with dynamic LDS: per wave a tile of 64 floats a slot, and as many again with the pair
+// search (svs_device.hpp).  At most 63 KB: k = 6 without the search, k = 5 with it.
+uint32_t matrix_lds_bytes(const svs::EmbedPlan &p) {
+    return p.matrix ? (uint32_t)(SVS_WG / 64) * 64u * 4u * svs::matrix_slots(p.matrix) * ((p.matrix & 8u) ? 2u : 1u) : 0u;
+}
+
 int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t st, const uint8_t *gray, uint8_t *stego,
                  svs::Geometry g, const uint32_t *bits, const svs::KernelOptions &k) {
     const svs::LaunchTables t = svs::embed_tables(p, k);
@@ -197,6 +203,7 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
     g.xcd_chunk = p.xcd_chunk;
     g.pad = svs::rule_word(p.nearest, p.minmove, p.half_cell);
     const uint32_t words = (uint32_t)p.n_words;
+    const uint32_t exact_lds = matrix_lds_bytes(p);   // 0 for every launch but a matrix plan's
     return dispatch<svs::QM_DOUBLE, svs::QM_POW2, svs::QM_F32>(p.qm, [&](auto qm) {
         constexpr int QM = decltype(qm)::value;
         if (p.path == EmbedPath::EXACT || p.path == EmbedPath::ROUND_TRIP)
@@ -205,9 +212,9 @@ int launch_embed(const svs::EmbedPlan &p, bool two, uint64_t total, hipStream_t 
             return dispatch<1, 2, 8>(p.rows, [&](auto u) {
                 constexpr int U = decltype(u)::value;
                 if (p.keyed)
-                    return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), 0, st, gray, stego, g,
+                    return launch(svs::embed_exact_kernel<QM, U, true, svs::BlockOrderArgs>, grid_for(total), exact_lds, st, gray, stego, g,
                                   p.qp, bits, p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{}, t.steps, ord);
-                return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), 0, st, gray, stego, g, p.qp, bits,
+                return launch(svs::embed_exact_kernel<QM, U>, grid_for(total), exact_lds, st, gray, stego, g, p.qp, bits,
                               p.bit_offset, p.n_bits, words, t.sel, t.dith, svs::ChannelArgs{}, t.steps);
             });
         if (p.rows == 2) {   // n = 10 (the reference GUI's default, app.py:69; BASELINE configs[1]) has a compile-time-n instantiation
@@ -767,6 +774,7 @@ struct GrayOptions {
     uint32_t min_margin = 0;                   // the margin calls: the gate of the pass behind the stepped read-back (0: none);
                                                // d_counts is then four uint64, svs_margin_counts
     svs_margin_counts *margin_counts = nullptr;   // the margin calls, host: the counts of the whole call (in the place of `counts`)
+    uint32_t matrix = 0;                       // the matrix calls: svs_route.hpp's matrix word; the call's n_ac is then k
 
     // the kernels' forms, for a batch of g's blocks per frame (derived once per call)
     svs::KernelOptions kernel_forms(const svs::Geometry &g) const {
@@ -787,6 +795,7 @@ struct GrayOptions {
         ra.hist = out.kind == ExtractOutput::HIST;
         ra.stepped = steps != nullptr;
         ra.min_margin = min_margin;
+        ra.matrix = matrix;
         return ra;
     }
 
@@ -899,6 +908,36 @@ int with_steps(const OptionsPolicy &pol, const svs_block_order *order, const svs
         o.steps = &table;
         o.min_margin = min_margin;
         return call(n, o);
+    });
+}
+
+// The matrix calls are the stepped calls with k stream bits a block: the matrix struct is checked first, then what with_steps
+// checks, then the size of the selection (or n_ac) against 2^k - 1; the call then runs as a stepped call at n_ac = k whose table
+// has 2^k - 1 slots (svs_route.hpp RouteArgs::matrix).  The pair search keeps 2 (2^k - 1) floats per lane in LDS: k <= 5.
+constexpr OptionsPolicy kMatrixEmbed{false, false, kSelectEmbedFlags, "a matrix embed takes the mode bits, SVS_NEAREST and SVS_MINMOVE"};
+constexpr OptionsPolicy kMatrixExtract{false, false, kModeFlags, "a matrix extract takes the mode bits only"};
+
+int check_matrix(const svs_matrix *m) {
+    if (!m) return fail(SVS_ERR_INVALID_ARG, "matrix is NULL");
+    if (m->k < 1 || m->k > 6) return fail(SVS_ERR_INVALID_ARG, "svs_matrix.k %u is not in 1..6", (unsigned)m->k);
+    if (m->search > 1) return fail(SVS_ERR_INVALID_ARG, "svs_matrix.search %u is not 0 or 1", (unsigned)m->search);
+    if (m->reserved[0] != 0 || m->reserved[1] != 0) return fail(SVS_ERR_INVALID_ARG, "svs_matrix.reserved must be 0");
+    if (m->search == 1 && m->k > 5)
+        return fail(SVS_ERR_INVALID_ARG, "svs_matrix.search 1 takes k <= 5 (the pair search's tile of 2 * 63 floats a lane exceeds a launch's LDS)");
+    return SVS_OK;
+}
+
+template <class Call>
+int with_matrix(const OptionsPolicy &pol, const svs_block_order *order, const svs_coeffs *coeffs, const svs_dither *dither,
+                const svs_qim_steps *steps, const svs_matrix *matrix, uint32_t flags, int n_ac, Call &&call) {
+    if (int rc = check_matrix(matrix)) return rc;
+    return with_steps(pol, order, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
+        const int slots = (1 << matrix->k) - 1;
+        if (n != slots)
+            return fail(SVS_ERR_INVALID_ARG, "a matrix call with k = %u takes a selection (or n_ac) of exactly %d coefficients, not %d",
+                        (unsigned)matrix->k, slots, n);
+        o.matrix = svs::make_matrix_word(matrix->k, matrix->search);
+        return call((int)matrix->k, o);
     });
 }
 
@@ -1118,7 +1157,7 @@ static int embed_host(const uint8_t *gray, uint8_t *stego, uint8_t *gray_ref_out
                                      flags, done, up, o.chunk((uint32_t)f0, d_counts, &order, &dither));
                 },
                 [&](const svs::Chunk &ch, int64_t off, hipStream_t st) { return download_pixels(stego, d, planes, ch, off, st); },
-                &done_total, o.order != nullptr || o.dither != nullptr);
+                &done_total, o.order != nullptr || o.dither != nullptr || o.matrix != 0u);
             if (!rc && d_counts) SVS_HIP(hipMemcpyAsync(got_counts, d_counts, counts_bytes, hipMemcpyDeviceToHost, c.st[0]));
             // the gray reference is copied by the calling thread HERE, while the streams work: everything is enqueued, the
             // thread would only wait.  (Not when stego overlaps gray: the downloads would overwrite the source first.)
@@ -1611,6 +1650,46 @@ int svs_stepped_soft_histogram(const uint8_t *gray, const svs_planes *planes, co
     return with_steps(kSteppedExtract, nullptr, coeffs, dither, steps, flags, n_ac, [&](int n, GrayOptions o) {
         o.out = {ExtractOutput::HIST};
         return extract_host(gray, planes, kSteppedRouteDelta, n, reinterpret_cast<uint8_t *>(hist_out), 0, flags, n_bits_out, o);
+    });
+}
+
+// ---- matrix embedding (include/svsdct.h) -----------------------------------------------------------------------------------
+uint64_t svs_matrix_capacity_bits(const svs_planes *p, const svs_matrix *m) {
+    if (!m || m->k < 1 || m->k > 6) return 0;
+    return svs_capacity_bits(p, (int)m->k);
+}
+
+int svs_matrix_embed_dev(const uint8_t *d_gray, uint8_t *d_stego, const svs_planes *planes, const svs_block_order *order,
+                         const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix,
+                         int n_ac, const uint8_t *d_bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags,
+                         uint64_t *n_embedded, void *stream) {
+    return with_matrix(kMatrixEmbed, order, coeffs, dither, steps, matrix, flags, n_ac, [&](int k, const GrayOptions &o) {
+        return embed_dev(d_gray, d_stego, planes, kSteppedRouteDelta, k, d_bits_packed, bit_offset, n_bits, flags, n_embedded, stream, o);
+    });
+}
+
+int svs_matrix_embed(const uint8_t *gray, uint8_t *stego, const svs_planes *planes, const svs_block_order *order,
+                     const svs_coeffs *coeffs, const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix, int n_ac,
+                     const uint8_t *bits_packed, uint64_t bit_offset, uint64_t n_bits, uint32_t flags, uint64_t *n_embedded) {
+    return with_matrix(kMatrixEmbed, order, coeffs, dither, steps, matrix, flags, n_ac, [&](int k, const GrayOptions &o) {
+        return embed_host(gray, stego, nullptr, planes, kSteppedRouteDelta, k, bits_packed, nullptr, bit_offset, n_bits, flags,
+                          n_embedded, o);
+    });
+}
+
+int svs_matrix_extract_dev(const uint8_t *d_gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                           const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix, int n_ac,
+                           uint8_t *d_bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out, void *stream) {
+    return with_matrix(kMatrixExtract, order, coeffs, dither, steps, matrix, flags, n_ac, [&](int k, const GrayOptions &o) {
+        return extract_dev(d_gray, planes, kSteppedRouteDelta, k, d_bits_packed_out, out_capacity_bytes, flags, n_bits_out, stream, o);
+    });
+}
+
+int svs_matrix_extract(const uint8_t *gray, const svs_planes *planes, const svs_block_order *order, const svs_coeffs *coeffs,
+                       const svs_dither *dither, const svs_qim_steps *steps, const svs_matrix *matrix, int n_ac,
+                       uint8_t *bits_packed_out, uint64_t out_capacity_bytes, uint32_t flags, uint64_t *n_bits_out) {
+    return with_matrix(kMatrixExtract, order, coeffs, dither, steps, matrix, flags, n_ac, [&](int k, const GrayOptions &o) {
+        return extract_host(gray, planes, kSteppedRouteDelta, k, bits_packed_out, out_capacity_bytes, flags, n_bits_out, o);
     });
 }
 

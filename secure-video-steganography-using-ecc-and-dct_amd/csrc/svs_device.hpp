@@ -382,7 +382,12 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
     // float32 one whatever QM says; svs_route.hpp plans no other instantiation for a stepped call).  `stepped` is a compile-time
     // false on every side that was there before.  The stepped side reads its table from the dither's copy, on or off, as the
     // dithered side does: the call's selection or the prefix table of n_ac.
-    const auto body = [&](const QimRule qp, const CoeffTable *table, auto dithered, auto stepped) __attribute__((always_inline)) {
+    // A matrix call (steps.matrix(); svs_matrix_embed_dev) is one more side of the stepped side, behind it: the same loads, stream
+    // position, budget and store with g.n_ac = k stream bits a block and a table of 2^k - 1 slots; embed_block_matrix in the place
+    // of embed_block_stepped.  It keeps a wave-private tile of 64 count floats in dynamic LDS - the values of the flipped forms;
+    // twice that with the pair search, for its costs -, which only this launch requests (svs_capi.hip matrix_lds_bytes); a lane
+    // reads and writes its own column alone, so nothing is fenced.
+    const auto body = [&](const QimRule qp, const CoeffTable *table, auto dithered, auto stepped, auto matrix) __attribute__((always_inline)) {
         const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
         if (gblock >= g.total_blocks) return;
         const int64_t off = block_offset(gblock, g);
@@ -402,7 +407,14 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
         if constexpr (decltype(stepped)::value) {
             uint32_t s_b = 0u;
             if constexpr (decltype(dithered)::value) s_b = dither_seed_of(gblock, g, dith);
-            embed_block_stepped<decltype(dithered)::value>(ax, ay, block_budget(first, n_bits, n), hi, lo, qp.kind, *table, steps, s_b);
+            if constexpr (decltype(matrix)::value) {
+                extern __shared__ float matrix_tile[];
+                const uint32_t per_wave = 64u * table->count * ((steps.matrix() & 8u) ? 2u : 1u);   // svs_capi.hip matrix_lds_bytes
+                float *tile = matrix_tile + (threadIdx.x >> 6) * per_wave + (threadIdx.x & 63u);
+                embed_block_matrix<decltype(dithered)::value>(ax, ay, block_budget(first, n_bits, n), hi, qp.kind, *table, steps,
+                                                              steps.matrix(), s_b, tile, 64u);
+            } else
+                embed_block_stepped<decltype(dithered)::value>(ax, ay, block_budget(first, n_bits, n), hi, lo, qp.kind, *table, steps, s_b);
         } else if constexpr (decltype(dithered)::value)
             embed_block_exact<U, QM, true>(ax, ay, n, block_budget(first, n_bits, n), hi, lo, qp, false, table,
                                            dither_seed_of(gblock, g, dith));
@@ -416,37 +428,51 @@ __global__ __launch_bounds__(SVS_WG, 2) void embed_exact_kernel(const uint8_t *g
     if constexpr (QM == QM_DOUBLE && U == 8) {
         if (steps.on) {    // wave-uniform
             constexpr std::true_type stepped{};
-            if (dith.on) {
-                constexpr std::true_type dithered{};
-                if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, dithered, stepped);
-                else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered, stepped);
-                else body(QimRule(qp, 0u), &dith.sel, dithered, stepped);
+            if (steps.matrix()) {   // wave-uniform; behind the side that was there first, which returns
+                constexpr std::true_type matrix{};
+                if (dith.on) {
+                    constexpr std::true_type dithered{};
+                    if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, dithered, stepped, matrix);
+                    else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered, stepped, matrix);
+                    else body(QimRule(qp, 0u), &dith.sel, dithered, stepped, matrix);
+                    return;
+                }
+                if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, plain, stepped, matrix);
+                else if (g.pad) body(QimRule(qp, 1u), &dith.sel, plain, stepped, matrix);
+                else body(QimRule(qp, 0u), &dith.sel, plain, stepped, matrix);
                 return;
             }
-            if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, plain, stepped);
-            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, plain, stepped);
-            else body(QimRule(qp, 0u), &dith.sel, plain, stepped);
+            if (dith.on) {
+                constexpr std::true_type dithered{};
+                if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, dithered, stepped, plain);
+                else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered, stepped, plain);
+                else body(QimRule(qp, 0u), &dith.sel, dithered, stepped, plain);
+                return;
+            }
+            if (g.pad > 1u) body(QimRule(qp, (uint32_t)RULE_MINMOVE), &dith.sel, plain, stepped, plain);
+            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, plain, stepped, plain);
+            else body(QimRule(qp, 0u), &dith.sel, plain, stepped, plain);
             return;
         }
     }
     if constexpr (U == 8) {
         if (dith.on) {     // wave-uniform; `sel` is the call's selection or the prefix table of n_ac: one selected loop serves both
             constexpr std::true_type dithered{};
-            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &dith.sel, dithered, plain);
-            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered, plain);
-            else body(QimRule(qp, 0u), &dith.sel, dithered, plain);
+            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &dith.sel, dithered, plain, plain);
+            else if (g.pad) body(QimRule(qp, 1u), &dith.sel, dithered, plain, plain);
+            else body(QimRule(qp, 0u), &dith.sel, dithered, plain, plain);
             return;
         }
         if (sel.count) {   // Geometry::n_ac == sel.count: the stream ranges and the block budget are those of n_ac slots
-            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &sel, plain, plain);
-            else if (g.pad) body(QimRule(qp, 1u), &sel, plain, plain);
-            else body(QimRule(qp, 0u), &sel, plain, plain);
+            if (g.pad > 1u) body(rule_from_word(qp, g.pad), &sel, plain, plain, plain);
+            else if (g.pad) body(QimRule(qp, 1u), &sel, plain, plain, plain);
+            else body(QimRule(qp, 0u), &sel, plain, plain, plain);
             return;
         }
     }
-    if (g.pad > 1u) body(rule_from_word(qp, g.pad), nullptr, plain, plain);
-    else if (g.pad) body(QimRule(qp, 1u), nullptr, plain, plain);
-    else body(QimRule(qp, 0u), nullptr, plain, plain);
+    if (g.pad > 1u) body(rule_from_word(qp, g.pad), nullptr, plain, plain, plain);
+    else if (g.pad) body(QimRule(qp, 1u), nullptr, plain, plain, plain);
+    else body(QimRule(qp, 0u), nullptr, plain, plain, plain);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1122,6 +1148,8 @@ __global__ __launch_bounds__(SVS_WG, U == 8 ? 6 : 1) void extract_exact_kernel(c
                 uint32_t s_b = 0u;
                 if constexpr (DITH) s_b = dither_seed_of(gblock, g, dith);
                 extract_block_stepped<DITH>(ax, ay, sel, steps, hi, lo, s_b);
+                // a matrix call (svs_matrix_extract_dev): the block's n = g.n_ac stream bits are the syndrome of its parities
+                if (steps.matrix()) matrix_fold(hi, lo);   // wave-uniform
             } else if constexpr (DITH) {
                 // the prefix form and the selected form, as on the side without a dither
                 const uint32_t s_b = dither_seed_of(gblock, g, dith);

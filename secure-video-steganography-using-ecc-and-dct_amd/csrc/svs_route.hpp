@@ -52,7 +52,23 @@ struct RouteArgs {
     // svs_stepped_embed_readback_margin*: the gate of the soft-margin pass that follows the stepped read-back, 0..127 (0: no such
     // pass).  Read only with stepped and readback.
     uint32_t min_margin = 0;
+    // a matrix call (svs_matrix_embed* / svs_matrix_extract*; stepped, never with readback): StepArgs::matrix()'s word, k in bits
+    // 0..2 and the pair search in bit 3 (make_matrix_word).  n_ac is then k, the stream bits a block carries - capacity, stream
+    // positions and budgets are those of k - while the table the stepped side reads has 2^k - 1 slots: the call's selection
+    // (coeffs, whose count is NOT n_ac here) or the prefix table of 2^k - 1.
+    uint32_t matrix = 0;
 };
+
+// the word of a matrix call and the slots of its table
+inline uint32_t make_matrix_word(uint32_t k, uint32_t search) { return k | (search ? 8u : 0u); }
+inline uint32_t matrix_slots(uint32_t word) { return (1u << (word & 7u)) - 1u; }
+// the slots of the table a stepped side reads where the call has no selection: n_ac, or a matrix call's 2^k - 1
+inline uint32_t stepped_slots(uint32_t n_ac, uint32_t matrix) { return matrix ? matrix_slots(matrix) : n_ac; }
+inline StepArgs matrix_steps(const StepArgs &steps, uint32_t matrix) {
+    StepArgs s = steps;
+    s.on |= matrix << SVS_STEP_MATRIX_SHIFT;
+    return s;
+}
 
 inline bool route_selected(const RouteArgs &a) {
     return a.coeffs && a.coeffs->count != 0 && !coeff_table_is_prefix(*a.coeffs);
@@ -86,6 +102,7 @@ struct EmbedPlan {
     bool dithered;            // the launch switches the exact kernel's dithered side on (EXACT with rows = 8 only)
     bool stepped = false;     // the launch passes the call's StepArgs (EXACT with rows = 8 and QM_DOUBLE only), else an empty one
     uint32_t min_margin = 0;  // stepped with readback: a second readback_kernel launch, the margin pass, follows with this gate
+    uint32_t matrix = 0;      // stepped: the matrix word the launch puts into StepArgs::on (0: none); n_ac is then k
 };
 
 // Which kernel family (include/svsdct.h `flags`).  The streaming kernels cover one and two coefficient rows (n <= 15) inside the
@@ -123,6 +140,7 @@ inline EmbedPlan plan_embed(const RouteArgs &a) {
         p.dithered = a.dithered;              // likewise (EXACT with rows = 8)
         p.stepped = a.stepped;                // likewise (EXACT with rows = 8, never STREAMING: rows = 8)
         p.min_margin = a.stepped && a.readback ? a.min_margin : 0u;
+        p.matrix = a.stepped ? a.matrix : 0u;
         if (streaming) {
             make_guard(a.delta, rows, &p.qp);
             p.qp.g_sum *= a.guard_scale; p.qp.g_resid *= a.guard_scale; p.qp.g_delta *= a.guard_scale;
@@ -161,6 +179,7 @@ struct ExtractPlan {
     bool hist = false;        // soft, and the launch switches the soft side's histogram tail on: `out` is n_frames * 256 uint32
                               // counts, added to; the launch requests 256 more dwords of dynamic LDS (never ZEROS, never keyed)
     bool stepped = false;     // the launch passes the call's StepArgs (EXACT with rows = 8 and QM_POW2; never ZEROS, never FAST)
+    uint32_t matrix = 0;      // stepped: the matrix word the launch puts into StepArgs::on (0: none); n_ac is then k
 };
 
 // Tile maps (measured on MI355X, profiles/history/r02_ab_extract_chunk.txt): one coefficient row - runs of 32 tiles per XCD
@@ -179,6 +198,7 @@ inline ExtractPlan plan_extract(const RouteArgs &a) {
     p.selected = route_selected(a);
     p.dithered = a.dithered;
     p.stepped = a.stepped;
+    p.matrix = a.stepped ? a.matrix : 0u;
     p.rows = p.selected || p.dithered || p.soft || p.stepped ? 8 : rows_for((int)a.n_ac);
     p.xcd_chunk = p.rows == 1 ? 32u : (p.rows == 2 && !a.bgr ? 0u : kEighth);
     p.qm = make_qim(a.delta, &p.qp) == QM_POW2 || p.stepped ? QM_POW2 : QM_F32;   // stepped: the holder of the stepped side
@@ -219,12 +239,13 @@ struct LaunchTables {   // the `sel` and `dith` arguments of the two exact kerne
 
 // embed_exact_kernel: `sel` is the call's selection where the plan is selected, else empty (count 0: the row-major prefix).  The
 // dither is on only where the plan says so (EXACT, rows = 8); the dithered side runs the selected loop alone, with the prefix
-// table of n_ac where the call has no selection.  The stepped side reads that table too, with the dither on or off.
+// table of n_ac where the call has no selection.  The stepped side reads that table too, with the dither on or off; a matrix
+// call's has 2^k - 1 slots (stepped_slots) and its StepArgs carry the matrix word.
 inline LaunchTables embed_tables(const EmbedPlan &p, const KernelOptions &k) {
     const CoeffTable sel = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
     return {sel, {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u,
-                  !(p.dithered || p.stepped) ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)},
-            SoftArgs{}, p.stepped ? k.steps : StepArgs{}};
+                  !(p.dithered || p.stepped) ? CoeffTable{} : sel.count ? sel : make_prefix_table(stepped_slots(p.n_ac, p.matrix))},
+            SoftArgs{}, p.stepped ? matrix_steps(k.steps, p.matrix) : StepArgs{}};
 }
 
 // readback_kernel's keyed form (a selected or dithered plan): one table, the call's selection or the prefix table of n_ac
@@ -249,14 +270,14 @@ inline StepArgs margin_steps(const StepArgs &steps, uint32_t gate) {
 // route's delta and are not read: the stepped byte takes them from its coefficient's step) and the call's StepArgs.
 inline LaunchTables extract_tables(const ExtractPlan &p, const KernelOptions &k) {
     const CoeffTable own = p.selected && k.coeffs ? *k.coeffs : CoeffTable{};
-    const CoeffTable sel = p.stepped && !own.count ? make_prefix_table(p.n_ac) : own;
+    const CoeffTable sel = p.stepped && !own.count ? make_prefix_table(stepped_slots(p.n_ac, p.matrix)) : own;
     return {sel,
             {k.dith.seed, k.dith.first_frame, p.dithered ? 1u : 0u, !p.soft ? CoeffTable{} : sel.count ? sel : make_prefix_table(p.n_ac)},
             !p.soft  ? SoftArgs{}
             : p.vote ? make_vote_args(make_soft_args(p.qp.delta_f, p.n_ac), k.vote_period, k.vote_bit0)
             : p.hist ? make_hist_args(make_soft_args(p.qp.delta_f, p.n_ac))
                      : make_soft_args(p.qp.delta_f, p.n_ac),
-            p.stepped ? k.steps : StepArgs{}};
+            p.stepped ? matrix_steps(k.steps, p.matrix) : StepArgs{}};
 }
 
 }  // namespace svs

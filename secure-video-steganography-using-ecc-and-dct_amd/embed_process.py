@@ -23,6 +23,7 @@ from svsdct import coeffs as _coeffs
 from svsdct import dither as _dither
 from svsdct import framing as _framing
 from svsdct import order as _order
+from svsdct import matrix as _matrix
 from svsdct import steps as _steps
 from svsdct.pipeline import FramePipeline, SlotFeeder, read_ahead
 
@@ -101,6 +102,11 @@ MINMOVE = os.environ.get("SVS_MINMOVE", "0") == "1"
 # SVS_READBACK, SVS_READBACK_COLOUR and SVS_READBACK_KEYED (a stepped call has no colour form; its read-back is
 # SVS_READBACK_STEPPED=1).  Allowed with
 # SVS_BLOCK_KEY, SVS_COEFFS, SVS_DITHER_KEY, SVS_NEAREST and SVS_MINMOVE.
+# SVS_MATRIX (read per call, opt-in): matrix embedding (svsdct/matrix.py, include/svsdct.h) - `k` (1..6) or `k:pair` (k <= 5).  A
+# block carries k bits as the Hamming syndrome of the parities of its 2^k - 1 payload coefficients (the AC count or SVS_COEFFS
+# must name exactly that many), so at most one of them - with `:pair` the cheaper of one or two - changes parity; the capacity of
+# a frame becomes blocks * k.  It needs SVS_STEPS (refused without it; `20,20,..` 64 times for one delta) and pays off with
+# SVS_MINMOVE=1.  Refused with every read-back switch.  The receiver must set the same k.
 
 
 def _keyed(block_key=None, dither_key=None, **kw):
@@ -199,6 +205,17 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
         print("    Error: SVS_READBACK_STEPPED tidak dapat dipakai bersama SVS_KEEP_COLOUR, SVS_READBACK, SVS_READBACK_COLOUR atau "
               "SVS_READBACK_KEYED.")
         return False, None, None
+    try:
+        matriks = _matrix.from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"    Error: SVS_MATRIX tidak valid ({exc}).")
+        return False, None, None
+    if matriks is not None and tabel_langkah is None:
+        print("    Error: SVS_MATRIX memerlukan SVS_STEPS.")
+        return False, None, None
+    if matriks is not None and (READBACK_STEPPED or READBACK_MARGIN):
+        print("    Error: SVS_MATRIX tidak dapat dipakai bersama SVS_READBACK_STEPPED atau SVS_READBACK_MARGIN.")
+        return False, None, None
     gerbang = None
     if READBACK_MARGIN:
         if tabel_langkah is None:
@@ -270,7 +287,8 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     jaga_warna = bool(KEEP_COLOUR and tabel_warna)
     if jaga_warna:
         print("    Info: warna video sampul dipertahankan.")
-    per_frame = _batch.capacity_bits(1, out_h, out_w, num_ac_coeffs)
+    per_frame = (_batch.capacity_bits(1, out_h, out_w, num_ac_coeffs) if matriks is None
+                 else _matrix.capacity_bits(1, out_h, out_w, _matrix.as_pair(matriks)[0]))
     # nothing can be embedded at delta <= 0 (:143-145) - unless a step table replaces delta
     usable = per_frame if delta_kuantisasi > 0 or tabel_langkah is not None else 0
     state = {"disisipkan": 0, "frame_num": 0, "first": None}
@@ -289,6 +307,9 @@ def embed_gambar_ke_video_final(path_video_input, path_gambar_rahasia, path_vide
     if tabel_langkah is not None:
         print("    Info: langkah kuantisasi per koefisien dipakai (SVS_STEPS); DELTA tidak dipakai.")
         terdekat = dict(terdekat, steps=tabel_langkah)             # likewise
+    if matriks is not None:
+        print(f"    Info: penyisipan matriks dipakai (SVS_MATRIX): {_matrix.as_pair(matriks)[0]} bit per blok.")
+        terdekat = dict(terdekat, matrix=matriks)                  # likewise
     readback_abu = READBACK or (READBACK_COLOUR and not tabel_warna)   # the gray pipeline's read-back
     rb_pipa = {"readback_keyed": True} if READBACK_KEYED else ({"readback": True} if readback_abu else {})
     if READBACK_STEPPED:

@@ -21,6 +21,7 @@ from svsdct import coeffs as _coeffs
 from svsdct import dither as _dither
 from svsdct import framing as _framing
 from svsdct import order as _order
+from svsdct import matrix as _matrix
 from svsdct import steps as _steps
 from svsdct.pipeline import FramePipeline, SlotFeeder
 
@@ -37,6 +38,8 @@ FUSED_COLOUR = os.environ.get("SVS_FUSED_COLOUR", "0") == "1"
 # the gray path.  Unset: the loops take exactly the routes they take without it.
 # SVS_STEPS (read per call): the sender's per-coefficient QIM steps (embed_process.py); DELTA is then not used; likewise the gray
 # path.
+# SVS_MATRIX (read per call): the sender's matrix embedding, `k` or `k:pair` (embed_process.py); it needs SVS_STEPS; a frame then
+# yields blocks * k bits; likewise the gray path.
 
 
 def _cv2():
@@ -51,7 +54,8 @@ def _gagal(pesan, cap=None):
     return False
 
 
-def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0, coeffs=None, dither_key=None, steps=None):
+def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first_frame=0, coeffs=None, dither_key=None, steps=None,
+                    matrix=None):
     if tabel_warna:                                            # frames are colour: convert + extract in one kernel
         packed, n_bits = _batch.extract_bgr_frames(np.stack(frames), delta, n_ac, weights=tabel_warna)
     else:
@@ -62,6 +66,8 @@ def _extract_frames(frames, delta, n_ac, tabel_warna=None, block_key=None, first
             keyed.update(dither_key=dither_key, first_frame=first_frame)
         if steps is not None:
             keyed["steps"] = steps
+        if matrix is not None:
+            keyed["matrix"] = matrix
         packed, n_bits = _batch.extract_frames(np.stack(frames), delta, n_ac, **keyed)
     return np.unpackbits(packed, count=n_bits)
 
@@ -97,6 +103,17 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
     if tabel_langkah is not None:
         print("  Info: langkah kuantisasi per koefisien dipakai (SVS_STEPS); DELTA tidak dipakai.")
     langkah = {} if tabel_langkah is None else {"steps": tabel_langkah}
+    try:
+        matriks = _matrix.from_env()
+    except (TypeError, ValueError) as exc:
+        print(f"  Error: SVS_MATRIX tidak valid ({exc}).")
+        return False
+    if matriks is not None:
+        if tabel_langkah is None:
+            print("  Error: SVS_MATRIX memerlukan SVS_STEPS.")
+            return False
+        print(f"  Info: penyisipan matriks dipakai (SVS_MATRIX): {_matrix.as_pair(matriks)[0]} bit per blok.")
+        langkah["matrix"] = matriks
     cv2 = _cv2()
     cap = cv2.VideoCapture(path_stego_video)
     if not cap.isOpened():
@@ -108,7 +125,8 @@ def ekstraksi_gambar_video_final(path_stego_video, path_gambar_output,
         print("  Error: Dimensi video terlalu kecil.")
         cap.release()
         return False
-    per_frame = _batch.capacity_bits(1, h, w, num_ac_coeffs)
+    per_frame = (_batch.capacity_bits(1, h, w, num_ac_coeffs) if matriks is None
+                 else _matrix.capacity_bits(1, h, w, _matrix.as_pair(matriks)[0]))
     tabel_warna = None
     if FUSED_COLOUR and kunci_blok is None and pilihan is None and kunci_dither is None and tabel_langkah is None:
         # (a keyed order, a selection, a dither, a step table: the host-conversion gray path)

@@ -26,6 +26,7 @@ from . import channel as _channel
 from . import coeffs as _coeffs
 from . import dither as _dither
 from . import native
+from . import matrix as _matrix
 from . import steps as _steps
 from . import soft as _soft
 from .hostmem import pinned_empty
@@ -286,20 +287,40 @@ def _readback_margin_arg(readback_margin, steps, readback=False, readback_keyed=
     return int(readback_margin)
 
 
-def _stepped_call(lib, verb, call: _GrayCall, steps, front, n_ac, back, stream=(), counts=()) -> None:
+def _matrix_arg(matrix, steps, *readbacks):
+    """matrix= of the gray calls (k, or (k, "pair"): svsdct/matrix.py) -> struct svs_matrix, None for None.  It needs steps and has
+    no read-back form; every ValueError it can cause is raised here, before the library is loaded."""
+    if matrix is None:
+        return None
+    k, search = _matrix.as_pair(matrix)
+    if steps is None:
+        raise ValueError("matrix needs steps: a matrix call is a stepped call (steps.uniform(delta) for one delta)")
+    if any(readbacks):
+        raise ValueError("matrix embedding has no read-back form: drop the read-back switch or matrix")
+    return _matrix.matrix_struct(k, search)
+
+
+def _no_matrix(matrix, what: str) -> None:
+    if matrix is not None:
+        raise ValueError(f"matrix embedding has no {what} form")
+
+
+def _stepped_call(lib, verb, call: _GrayCall, steps, front, n_ac, back, stream=(), counts=(), matrix=None) -> None:
     """svs_stepped_<verb>(*front, order, coeffs, dither, steps, n_ac, *back), or with stream = (handle,) its _dev form with the
     stream last; raises unless it returns SVS_OK.  The call's delta is not an argument: the table replaces it.  counts =
     (pointer,): the counts argument of the read-back forms (verbs "embed_readback" and "embed_readback_margin", whose `back`
-    carries the gate in front of the flags), behind `back`."""
-    name = f"svs_stepped_{verb}" + ("_dev" if stream else "")
-    args = [*front, _ref(call.order), _ref(call.sel), _ref(call.dith), C.byref(steps), int(n_ac), *back, *counts, *stream]
+    carries the gate in front of the flags), behind `back`.  matrix (a struct of _matrix_arg; verbs "embed" and "extract"):
+    svs_matrix_<verb>, the same call with the struct behind the table."""
+    name = (f"svs_stepped_{verb}" if matrix is None else f"svs_matrix_{verb}") + ("_dev" if stream else "")
+    args = [*front, _ref(call.order), _ref(call.sel), _ref(call.dith), C.byref(steps), *(() if matrix is None else (C.byref(matrix),)),
+            int(n_ac), *back, *counts, *stream]
     native.check(getattr(lib, name)(*args), name)
 
 
 def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                  device: int = 0, mode: str | None = None, block_key=None, first_frame: int = 0, readback: bool = False,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
-                 steps=None, readback_stepped: bool = False, readback_margin: int | None = None):
+                 steps=None, readback_stepped: bool = False, readback_margin: int | None = None, matrix=None):
     """Embed a bit stream into a stack of gray frames on the GPU.
 
     frames : uint8 [F,H,W] (or [H,W]);  bits : 0/1 array or '0'/'1' str (the stream; bit
@@ -338,8 +359,13 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
     readback_margin : None, or an int g in 1..127 (opt-in, svs_stepped_embed_readback_margin, include/svsdct.h): after the
     stepped read-back a second pass strengthens every block that decodes but would reach the receiver with a soft margin m < g
     on some payload coefficient.  It implies readback_stepped: it needs steps; ValueError with readback or readback_keyed.
+    matrix : None, k or (k, "pair") (opt-in, svsdct/matrix.py; svs_matrix_embed, include/svsdct.h): matrix embedding - a block
+    carries k bits as the Hamming syndrome of the parities of its 2^k - 1 payload coefficients, so at most one of them (with
+    "pair": the cheaper of one or two) changes parity.  It needs steps, a selection (or n_ac) of exactly 2^k - 1 coefficients,
+    and pays off under minmove; the capacity is blocks * k.  ValueError without steps or with any read-back switch.
     Returns (stego uint8 [F,H,W], n_embedded), with readback, readback_keyed or readback_stepped (stego, n_embedded,
     ReadbackCounts), with readback_margin (stego, n_embedded, MarginCounts)."""
+    mx = _matrix_arg(matrix, steps, readback, readback_keyed, readback_stepped, readback_margin)
     gate = _readback_margin_arg(readback_margin, steps, readback, readback_keyed)
     stepped_rb = _readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
     table = _steps_arg(steps, readback, readback_keyed)
@@ -370,7 +396,7 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
         _stepped_call(lib, "embed_readback" if stepped_rb else "embed", call, table,
                       [stack.ctypes.data, stego.ctypes.data, C.byref(planes)], n_ac,
                       [packed.ctypes.data, int(bit_offset), int(n_bits), embed_flags(mode, nearest, minmove), C.byref(done)],
-                      counts=(C.byref(counts),) if stepped_rb else ())
+                      counts=(C.byref(counts),) if stepped_rb else (), matrix=mx)
         if stepped_rb:
             return stego, int(done.value), ReadbackCounts(int(counts.repaired), int(counts.unrepaired))
         return stego, int(done.value)
@@ -383,24 +409,26 @@ def embed_frames(frames: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_b
 
 
 def extract_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
-                   first_frame: int = 0, coeffs=None, dither_key=None, steps=None):
+                   first_frame: int = 0, coeffs=None, dither_key=None, steps=None, matrix=None):
     """Extract the packed bit stream of a stack of gray frames on the GPU.  block_key / first_frame: as embed_frames (the
     sender's key and clip frame index).  coeffs: as embed_frames (the sender's selection).  dither_key: as embed_frames (the
-    sender's dither key).  steps: as embed_frames (the sender's step table; delta is then not used).
+    sender's dither key).  steps: as embed_frames (the sender's step table; delta is then not used).  matrix: as embed_frames
+    (the sender's k; svs_matrix_extract: k bits a block, n_bits = blocks * k; "pair" reads as k).
     Returns (packed uint8 [ceil(n_bits/8)], n_bits)."""
+    mx = _matrix_arg(matrix, steps)
     table = _steps_arg(steps)
     call = _resolve(n_ac, None, block_key, first_frame, coeffs, dither_key)
     lib = native.load()
     native.ensure_device(device)
     stack = _as_stack(frames)
     f, h, w = stack.shape
-    cap = capacity_bits(f, h, w, n_ac)
+    cap = capacity_bits(f, h, w, n_ac) if mx is None else _matrix.capacity_bits(f, h, w, mx.k)
     out = np.zeros(max(4, (cap + 7) // 8 + (-((cap + 7) // 8)) % 4), np.uint8)
     got = C.c_uint64(0)
     planes = Planes.contiguous(f, h, w)
     back = [out.ctypes.data, out.size, mode_flags(mode), C.byref(got)]
     if table is not None:
-        _stepped_call(lib, "extract", call, table, [stack.ctypes.data, C.byref(planes)], n_ac, back)
+        _stepped_call(lib, "extract", call, table, [stack.ctypes.data, C.byref(planes)], n_ac, back, matrix=mx)
     else:
         _gray_call(lib, "extract", call, [stack.ctypes.data, C.byref(planes)], delta, n_ac, back)
     n = int(got.value)
@@ -431,14 +459,16 @@ def _soft_call(lib, name, call: _GrayCall, front, delta, n_ac, middle, flags, st
 
 
 def extract_soft_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, block_key=None,
-                        first_frame=None, coeffs=None, dither_key=None, steps=None):
+                        first_frame=None, coeffs=None, dither_key=None, steps=None, matrix=None):
     """Soft-decision extraction of a stack of gray frames on the GPU (svs_soft_extract, include/svsdct.h): one byte per
     capacity bit in stream order - bit 7 the hard bit extract_frames returns, bits 0..6 the distance of the coefficient from
     the nearest decision boundary in units of delta / 254 (svsdct/soft.py reads and combines them).  block_key, first_frame,
     coeffs, dither_key: as extract_frames; mode is accepted and changes nothing (a soft call always runs the exact kernel).
     steps: as extract_frames (svs_stepped_soft_extract: the sender's step table; delta is then not used, and the distance of
     coefficient k is in units of steps[k] / 254, its own cell).
-    Returns (soft uint8 [capacity], n_bits)."""
+    Returns (soft uint8 [capacity], n_bits).
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no soft form."""
+    _no_matrix(matrix, "soft")
     table = _steps_arg(steps)
     call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
     lib = native.load()
@@ -461,14 +491,16 @@ def _period(period) -> int:
 
 
 def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: int = 0, device: int = 0, mode: str | None = None,
-                        block_key=None, first_frame=None, coeffs=None, dither_key=None, steps=None):
+                        block_key=None, first_frame=None, coeffs=None, dither_key=None, steps=None, matrix=None):
     """Fused soft vote over a stack of gray frames on the GPU (svs_soft_vote, include/svsdct.h): the soft bytes of
     extract_soft_frames are never written - the kernel adds each into a tally of `period` int32 values at its stream position
     (stream_bit0 + its index) mod period, and only the tally comes back.  period: the payload's length in bits, as the sender
     tiled it (embed_repeated_frames).  stream_bit0: the capacity of the frames before this stack when a clip is read in
     batches - add the tallies of the batches and read the bits with soft.tally_bits.  The other keywords: as
     extract_soft_frames (steps: svs_stepped_soft_vote).  Returns (bits uint8 [period], tally int32 [period]); the bits are
-    soft.combine's."""
+    soft.combine's.
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no vote form."""
+    _no_matrix(matrix, "vote")
     period = _period(period)
     table = _steps_arg(steps)
     call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
@@ -484,14 +516,16 @@ def extract_vote_frames(frames: np.ndarray, delta, n_ac, period, stream_bit0: in
 
 
 def extract_histogram_frames(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, first_frame=None,
-                             coeffs=None, dither_key=None, steps=None):
+                             coeffs=None, dither_key=None, steps=None, matrix=None):
     """Fused per-frame soft histograms of a stack of gray frames on the GPU (svs_soft_histogram, include/svsdct.h): the soft
     bytes of extract_soft_frames are never written - the kernel counts each into row `frame`, column `byte` of 256 counts a
     frame, and only the rows come back (soft.byte_histogram is the model; soft.margins and soft.lattice_share read them).
     There is no block_key keyword and none is needed: the dither is keyed to a block's physical position and an order only
     permutes the blocks inside a frame, so a frame's counts are the same under every order - frames embedded under a block_key
     are read with this same call.  first_frame, coeffs, dither_key, steps: as extract_soft_frames (steps: svs_stepped_soft_histogram);
-    mode is accepted and changes nothing.  Returns (hist uint32 [n_frames, 256], n_bits)."""
+    mode is accepted and changes nothing.  Returns (hist uint32 [n_frames, 256], n_bits).
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no histogram form."""
+    _no_matrix(matrix, "histogram")
     table = _steps_arg(steps)
     call = _resolve(n_ac, None, None, 0 if first_frame is None else first_frame, coeffs, dither_key)
     lib = native.load()
@@ -517,6 +551,8 @@ def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | N
         raise ValueError("embed_repeated_frames embeds the whole tiled stream: bit_offset and n_bits are not its keywords")
     f, h, w = _as_stack(frames).shape
     cap = capacity_bits(f, h, w, n_ac)      # a selection lists n_ac coefficients
+    if embed_kw.get("matrix") is not None:  # a matrix call carries k bits a block
+        cap = _matrix.capacity_bits(f, h, w, _matrix.as_pair(embed_kw["matrix"])[0])
     if copies is not None and int(copies) < 1:
         raise ValueError("copies must be at least 1")
     stream = _soft.tile(bits, cap if copies is None else min(cap, int(copies) * bits.size))
@@ -565,13 +601,15 @@ def _ascii_address(text: str):
 
 
 def embed_frames_str(frames: np.ndarray, delta, n_ac, payload: str | None, device: int = 0, mode: str | None = None,
-                     want_gray: bool = False, dither_key=None):
+                     want_gray: bool = False, dither_key=None, matrix=None):
     """`embed_frames` in the reference operator's own types (config_and_setup.py:106-109,172): the payload is a '0'/'1'
     string (bit_payload_segment) of which at most the capacity is read from the front - the characters go to the device as
     they are and are packed there (svs_embed_str); None / "" = nothing to embed.  want_gray: also return a copy of the input
     frames as an array of its own, the operator's first return value - the library makes it while the GPU works.
     dither_key: refused (ValueError) - a keyed dither has no _str form.
-    Returns (stego uint8 [F,H,W], n_embedded) or (gray_copy, stego, n_embedded)."""
+    Returns (stego uint8 [F,H,W], n_embedded) or (gray_copy, stego, n_embedded).
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no _str form."""
+    _no_matrix(matrix, "_str")
     no_dither(dither_key, "_str")
     lib = native.load()
     native.ensure_device(device)
@@ -588,9 +626,11 @@ def embed_frames_str(frames: np.ndarray, delta, n_ac, payload: str | None, devic
     return (gray, stego, int(done.value)) if want_gray else (stego, int(done.value))
 
 
-def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, dither_key=None) -> str:
+def extract_frames_str(frames: np.ndarray, delta, n_ac, device: int = 0, mode: str | None = None, dither_key=None, matrix=None) -> str:
     """`extract_frames` returning the reference operator's own type: the '0'/'1' string of config_and_setup.py:173-174
-    (expanded on the device, one decode on the host).  dither_key: refused (ValueError) - no _str form."""
+    (expanded on the device, one decode on the host).  dither_key: refused (ValueError) - no _str form.
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no _str form."""
+    _no_matrix(matrix, "_str")
     no_dither(dither_key, "_str")
     lib = native.load()
     native.ensure_device(device)
@@ -614,7 +654,7 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
                  order: BlockOrder | None = None, readback: bool = False, d_counts: int = 0,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, first_frame: int | None = None,
                  readback_keyed: bool = False, steps=None, readback_stepped: bool = False,
-                 readback_margin: int | None = None) -> int:
+                 readback_margin: int | None = None, matrix=None) -> int:
     """Enqueue the embed kernel on `stream` (a hipStream_t handle as int); returns bits embedded.  order: None, or a
     native.BlockOrder (block_order(key, first_frame)) - the keyed block order of svs_embed_ordered_dev.  readback: the
     read-back pass follows on the same stream (svs_embed_readback_dev); d_counts: 0, or a device buffer of two uint64 that
@@ -626,8 +666,10 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
     (svs_stepped_embed_dev; delta is then not used).  readback_stepped: the read-back pass under steps
     (svs_stepped_embed_readback_dev; d_counts as with readback); it needs steps; ValueError with readback or readback_keyed.
     readback_margin: an int g in 1..127, the margin pass behind that read-back (svs_stepped_embed_readback_margin_dev; it implies
-    readback_stepped; d_counts is then FOUR uint64: repaired, unrepaired, strengthened, weak)."""
+    readback_stepped; d_counts is then FOUR uint64: repaired, unrepaired, strengthened, weak).  matrix: k or (k, "pair"), as
+    embed_frames (svs_matrix_embed_dev; it needs steps; ValueError with any read-back switch)."""
     _one_readback(readback, readback_keyed)      # ahead of the mode's ValueError
+    mx = _matrix_arg(matrix, steps, readback, readback_keyed, readback_stepped, readback_margin)
     gate = _readback_margin_arg(readback_margin, steps, readback, readback_keyed)
     stepped_rb = _readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
     done = C.c_uint64(0)
@@ -642,7 +684,7 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
     if table is not None:
         _stepped_call(native.load(), "embed_readback" if stepped_rb else "embed", call, table, [d_gray, d_stego, C.byref(planes)],
                       n_ac, [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], (stream or None,),
-                      counts=(d_counts or None,) if stepped_rb else ())
+                      counts=(d_counts or None,) if stepped_rb else (), matrix=mx)
         return int(done.value)
     _gray_call(native.load(), "embed", call, [d_gray, d_stego, C.byref(planes)], delta, n_ac,
                [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], d_counts or None, (stream or None,))
@@ -651,15 +693,16 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
 
 def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
                    stream: int = 0, mode: str | None = None, order: BlockOrder | None = None, coeffs=None, dither_key=None,
-                   first_frame: int | None = None, steps=None) -> int:
+                   first_frame: int | None = None, steps=None, matrix=None) -> int:
     """Enqueue the extract kernel on `stream`; returns the number of bits the batch yields.  order, coeffs, dither_key,
-    first_frame, steps: as embed_device."""
+    first_frame, steps, matrix: as embed_device (matrix: svs_matrix_extract_dev, blocks * k bits)."""
     got = C.c_uint64(0)
+    mx = _matrix_arg(matrix, steps)
     table = _steps_arg(steps)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     back = [d_bits_out, int(out_capacity_bytes), mode_flags(mode), C.byref(got)]
     if table is not None:
-        _stepped_call(native.load(), "extract", call, table, [d_gray, C.byref(planes)], n_ac, back, (stream or None,))
+        _stepped_call(native.load(), "extract", call, table, [d_gray, C.byref(planes)], n_ac, back, (stream or None,), matrix=mx)
     else:
         _gray_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac, back, None, (stream or None,))
     return int(got.value)
@@ -667,10 +710,12 @@ def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, ou
 
 def extract_soft_device(d_gray: int, planes: Planes, delta, n_ac, d_soft_out: int, out_capacity_bytes: int, stream: int = 0,
                         mode: str | None = None, order: BlockOrder | None = None, coeffs=None, dither_key=None,
-                        first_frame: int | None = None, steps=None) -> int:
+                        first_frame: int | None = None, steps=None, matrix=None) -> int:
     """Enqueue the soft-decision extraction on `stream` (svs_soft_extract_dev): one byte per capacity bit into d_soft_out
     (4-byte aligned, at least the capacity in bytes); returns the number of bytes the batch yields.  order, coeffs, dither_key,
-    first_frame, steps: as extract_device (steps: svs_stepped_soft_extract_dev)."""
+    first_frame, steps: as extract_device (steps: svs_stepped_soft_extract_dev).
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no soft form."""
+    _no_matrix(matrix, "soft")
     table = _steps_arg(steps)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     return _soft_call(native.load(), "extract", call, [d_gray, C.byref(planes)], delta, n_ac, [d_soft_out, int(out_capacity_bytes)],
@@ -679,11 +724,13 @@ def extract_soft_device(d_gray: int, planes: Planes, delta, n_ac, d_soft_out: in
 
 def extract_vote_device(d_gray: int, planes: Planes, delta, n_ac, d_tally: int, period, stream_bit0: int = 0, stream: int = 0,
                         order: BlockOrder | None = None, first_frame: int | None = None, coeffs=None, dither_key=None,
-                        steps=None) -> int:
+                        steps=None, matrix=None) -> int:
     """Enqueue the fused soft vote on `stream` (svs_soft_vote_dev): the batch's votes are ADDED into d_tally, `period` int32
     values in device memory (4-byte aligned) that the caller zeroes before the first batch; stream_bit0 is the capacity of the
     frames before the batch.  Returns the number of bits that voted.  order, coeffs, dither_key, first_frame, steps: as
-    extract_soft_device (steps: svs_stepped_soft_vote_dev)."""
+    extract_soft_device (steps: svs_stepped_soft_vote_dev).
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no vote form."""
+    _no_matrix(matrix, "vote")
     table = _steps_arg(steps)
     call = _resolve(n_ac, order, None, first_frame, coeffs, dither_key)
     return _soft_call(native.load(), "vote", call, [d_gray, C.byref(planes)], delta, n_ac, [_period(period), int(stream_bit0), d_tally],
@@ -691,13 +738,15 @@ def extract_vote_device(d_gray: int, planes: Planes, delta, n_ac, d_tally: int, 
 
 
 def extract_histogram_device(d_gray: int, planes: Planes, delta, n_ac, d_hist: int, stream: int = 0, first_frame: int | None = None,
-                             coeffs=None, dither_key=None, steps=None) -> int:
+                             coeffs=None, dither_key=None, steps=None, matrix=None) -> int:
     """Enqueue the fused per-frame soft histograms on `stream` (svs_soft_histogram_dev): the batch's bytes are ADDED into d_hist,
     planes.n_frames rows of 256 uint32 in device memory (4-byte aligned) that the caller zeroes before the first call; a clip
     read in batches passes d_hist + 1024 * (frames before the batch) and, under a dither, first_frame advanced by as many.
     Returns the number of bytes counted.  No order and no block_key: a frame's counts do not depend on one (see
     extract_histogram_frames).  coeffs, dither_key, first_frame, steps: as extract_soft_device (steps:
-    svs_stepped_soft_histogram_dev)."""
+    svs_stepped_soft_histogram_dev).
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no histogram form."""
+    _no_matrix(matrix, "histogram")
     table = _steps_arg(steps)
     call = _resolve(n_ac, None, None, first_frame, coeffs, dither_key)
     return _soft_call(native.load(), "histogram", call, [d_gray, C.byref(planes)], delta, n_ac, [d_hist], 0, (stream or None,), table)
@@ -728,13 +777,15 @@ def _bgr_flags(mode, keep_colour, nearest=False, minmove=False):
 def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Planes, delta, n_ac,
                      d_bits_packed: int, bit_offset: int, n_bits: int, stream: int = 0, mode: str | None = None,
                      weights=None, in_pitches=None, out_pitches=None, keep_colour: bool = False, readback: bool = False,
-                     d_counts: int = 0, nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None) -> int:
+                     d_counts: int = 0, nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, matrix=None) -> int:
     """Enqueue the fused BGR -> gray -> embed -> BGR kernel over packed (or pitched) interleaved BGR frames;
     `d_gray_ref` (0 to skip) receives the gray frames before embedding.  keep_colour: stego pixels keep the cover's
     colour (SVS_KEEP_COLOUR; their gray is the stego plane) instead of B = G = R.  readback: the read-back pass follows on
     the same stream, in place on the BGR output (svs_embed_bgr_readback_dev); d_counts: 0, or a device buffer of two uint64
     that the call adds {repaired, unrepaired} into.  nearest, minmove: SVS_NEAREST, SVS_MINMOVE, as embed_frames.
-    dither_key: refused (ValueError) - no colour form.  Returns bits embedded."""
+    dither_key: refused (ValueError) - no colour form.  Returns bits embedded.
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no colour form."""
+    _no_matrix(matrix, "colour")
     _no_coeffs(coeffs)
     no_dither(dither_key, "colour")
     irp, ifp = in_pitches or (3 * planes.width, 3 * planes.width * planes.height)
@@ -751,8 +802,10 @@ def embed_bgr_device(d_bgr_in: int, d_bgr_out: int, d_gray_ref: int, planes: Pla
 
 
 def extract_bgr_device(d_bgr: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
-                       stream: int = 0, weights=None, pitches=None, coeffs=None, dither_key=None) -> int:
-    """Enqueue extraction straight from interleaved BGR frames; returns the number of bits the batch yields."""
+                       stream: int = 0, weights=None, pitches=None, coeffs=None, dither_key=None, matrix=None) -> int:
+    """Enqueue extraction straight from interleaved BGR frames; returns the number of bits the batch yields.
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no colour form."""
+    _no_matrix(matrix, "colour")
     _no_coeffs(coeffs)
     no_dither(dither_key, "colour")
     rp, fp = pitches or (3 * planes.width, 3 * planes.width * planes.height)
@@ -776,12 +829,14 @@ def _as_bgr_stack(frames: np.ndarray) -> np.ndarray:
 def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int = 0, n_bits: int | None = None,
                      device: int = 0, mode: str | None = None, weights=None, want_gray: bool = True,
                      keep_colour: bool = False, readback: bool = False, nearest: bool = False, coeffs=None,
-                     minmove: bool = False, dither_key=None):
+                     minmove: bool = False, dither_key=None, matrix=None):
     """BGR frames in, stego BGR frames out (one fused pass on the GPU).  keep_colour: see embed_bgr_device.  readback: the
     blocks whose payload bits do not read back are repaired in place on the BGR output (svs_embed_bgr_readback,
     include/svsdct.h).  nearest, minmove: SVS_NEAREST, SVS_MINMOVE, as embed_frames.
     Returns (stego_bgr uint8 [F,H,W,3], gray uint8 [F,H,W] (the cover's) or None, n_embedded), with readback
-    (stego_bgr, gray, n_embedded, ReadbackCounts).  dither_key: refused (ValueError) - no colour form."""
+    (stego_bgr, gray, n_embedded, ReadbackCounts).  dither_key: refused (ValueError) - no colour form.
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no colour form."""
+    _no_matrix(matrix, "colour")
     _no_coeffs(coeffs)
     no_dither(dither_key, "colour")
     lib = native.load()
@@ -813,8 +868,10 @@ def embed_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, bits, bit_offset: int 
     return out, gray, int(done.value)
 
 
-def extract_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, device: int = 0, weights=None, dither_key=None):
-    """Extract the packed bit stream straight from BGR frames.  Returns (packed uint8, n_bits).  dither_key: refused."""
+def extract_bgr_frames(frames_bgr: np.ndarray, delta, n_ac, device: int = 0, weights=None, dither_key=None, matrix=None):
+    """Extract the packed bit stream straight from BGR frames.  Returns (packed uint8, n_bits).  dither_key: refused.
+    matrix: refused (ValueError): matrix embedding (svsdct/matrix.py) has no colour form."""
+    _no_matrix(matrix, "colour")
     no_dither(dither_key, "colour")
     lib = native.load()
     native.ensure_device(device)

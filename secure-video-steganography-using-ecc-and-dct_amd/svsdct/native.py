@@ -78,6 +78,11 @@ class QimSteps(C.Structure):
     _fields_ = [("delta", C.c_uint16 * 64)]
 
 
+class Matrix(C.Structure):
+    """struct svs_matrix: k bits a block and the flip search of the matrix entry points (include/svsdct.h, svsdct/matrix.py)"""
+    _fields_ = [("k", C.c_uint32), ("search", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 SVS_SCAN_ROW_MAJOR = 0
 SVS_SCAN_ZIGZAG = 1
 
@@ -89,6 +94,7 @@ _CO = C.POINTER(Coeffs)
 _DI = C.POINTER(Dither)
 _ST = C.POINTER(Steps)
 _QS = C.POINTER(QimSteps)
+_MX = C.POINTER(Matrix)
 
 # name -> (restype, argtypes); every symbol include/svsdct.h declares
 SIGNATURES = {
@@ -161,6 +167,14 @@ SIGNATURES = {
                                          _u64p]),
     "svs_stepped_soft_histogram_dev": (C.c_int, [_u8p, _PL, _CO, _DI, _QS, C.c_int, C.c_void_p, C.c_uint32, _u64p, C.c_void_p]),
     "svs_stepped_soft_histogram": (C.c_int, [_u8p, _PL, _CO, _DI, _QS, C.c_int, C.c_void_p, C.c_uint32, _u64p]),
+    "svs_matrix_capacity_bits": (C.c_uint64, [_PL, _MX]),
+    "svs_matrix_embed_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, _MX, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                        _u64p, C.c_void_p]),
+    "svs_matrix_embed": (C.c_int, [_u8p, _u8p, _PL, _BO, _CO, _DI, _QS, _MX, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                    _u64p]),
+    "svs_matrix_extract_dev": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, _MX, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p,
+                                          C.c_void_p]),
+    "svs_matrix_extract": (C.c_int, [_u8p, _PL, _BO, _CO, _DI, _QS, _MX, C.c_int, _u8p, C.c_uint64, C.c_uint32, _u64p]),
     "svs_embed_readback_dev": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,
                                           _u64p, C.c_void_p, C.c_void_p]),
     "svs_embed_readback": (C.c_int, [_u8p, _u8p, _PL, _BO, C.c_double, C.c_int, _u8p, C.c_uint64, C.c_uint64, C.c_uint32,

@@ -31,6 +31,7 @@ import numpy as np
 
 from . import batch, native
 from . import coeffs as _coeffs
+from . import matrix as _matrix
 from . import steps as _steps
 from .native import Planes
 
@@ -52,7 +53,7 @@ class FramePipeline:
     def __init__(self, height: int, width: int, batch_frames: int, delta, n_ac, depth: int = 3,
                  mode: str | None = None, device: int = 0, block_key=None, readback: bool = False,
                  nearest: bool = False, coeffs=None, minmove: bool = False, dither_key=None, readback_keyed: bool = False,
-                 steps=None, readback_stepped: bool = False, readback_margin: int | None = None):
+                 steps=None, readback_stepped: bool = False, readback_margin: int | None = None, matrix=None):
         """block_key: None (raster order) or the key of a keyed block order (svsdct/order.py); each submit then names the
         clip index of its batch's first frame.  readback: every embed batch is read back and its failing blocks repaired
         (SVS_READBACK, include/svsdct.h); readback_counts() gives the totals.  nearest: every embed batch forces a wrong parity
@@ -68,8 +69,13 @@ class FramePipeline:
         (svs_stepped_embed_readback_dev, include/svsdct.h); it needs steps; readback_counts() gives the totals; ValueError
         together with readback or readback_keyed.  readback_margin: None or an int g in 1..127 - the margin pass behind that
         read-back in every embed batch (svs_stepped_embed_readback_margin_dev); it implies readback_stepped; margin_counts()
-        gives the four totals, readback_counts() the first two."""
+        gives the four totals, readback_counts() the first two.  matrix: None, k or (k, "pair") - matrix embedding in every
+        batch (svsdct/matrix.py; svs_matrix_embed_dev / svs_matrix_extract_dev, include/svsdct.h): k bits a block over a
+        selection (or n_ac) of 2^k - 1 coefficients, so frame_capacity is blocks * k; it needs steps; ValueError with any
+        read-back switch."""
         batch._one_readback(readback, readback_keyed)
+        batch._matrix_arg(matrix, steps, readback, readback_keyed, readback_stepped, readback_margin)
+        self.matrix = matrix
         self.readback_margin = batch._readback_margin_arg(readback_margin, steps, readback, readback_keyed)
         batch._readback_stepped_arg(readback_stepped, steps, readback, readback_keyed)
         batch._steps_arg(steps, readback, readback_keyed)      # its ValueErrors, before anything is allocated
@@ -86,7 +92,8 @@ class FramePipeline:
         self.device = device
         self.h, self.w, self.batch, self.depth = height, width, batch_frames, depth
         self.delta, self.n_ac, self.mode = delta, n_ac, batch.resolve_mode(mode)
-        self.frame_capacity = batch.capacity_bits(1, height, width, n_ac)
+        self.frame_capacity = (batch.capacity_bits(1, height, width, n_ac) if matrix is None
+                               else _matrix.capacity_bits(1, height, width, _matrix.as_pair(matrix)[0]))
         self.batch_capacity = self.frame_capacity * batch_frames
         self._bits_bytes = (self.batch_capacity + 7) // 8 + 8
         nbytes = batch_frames * height * width
@@ -147,8 +154,10 @@ class FramePipeline:
         return {} if self.dither_key is None else {"dither_key": self.dither_key, "first_frame": first_frame}
 
     def _steps(self) -> dict:
-        """the keyword of a stepped submit: none at all without a table"""
-        return {} if self.steps is None else {"steps": self.steps}
+        """the keywords of a stepped submit: none at all without a table; a matrix submit is a stepped one"""
+        if self.steps is None:
+            return {}
+        return {"steps": self.steps} if self.matrix is None else {"steps": self.steps, "matrix": self.matrix}
 
     def _readback(self) -> dict:
         """the read-back keyword of an embed submit: one switch per path, and only the one that is on"""
