@@ -1,0 +1,217 @@
+// svs_fec.hip - the C ABI declared in include/svsfec.h: the host encoder and the windowed Viterbi decoder for gfx950.
+// Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC  (see csrc/Makefile)
+//
+// The decoder kernel: one wave decodes one segment, lane s owns trellis state s.
+//   1. the window's weights are loaded coalesced, converted (soft byte or int32 -> int16) and kept in a run of LDS private to
+//      the wave; every lane then reads a step's weights from the same address (a broadcast).
+//   2. add-compare-select: two cross-lane reads of the predecessors' metrics (ds_bpermute), one add, one subtract, a compare
+//      and a select.  The signs of a lane's branch metric are lane constants.  The 64 decisions of a step are one ballot word;
+//      lane i of the wave collects the word of step 64 c + i, and every 64 steps the words go to the wave's run of LDS in one
+//      store.
+//   3. traceback: the state is wave-uniform; the words come back 64 at a time, one per lane, and are read lane by lane.  The
+//      512 bits of the segment leave as 64 bytes, one per lane, in one coalesced store: a segment starts on a byte boundary,
+//      so no two waves write the same byte and no atomics are needed.  The last, partial segment masks its tail.
+// LDS per wave: 640 words of 8 bytes and 640 * RATE int16.  No global atomics, no scratch (profiles/fec_resources.txt).
+#include "svsfec.h"
+#include "svs_fec.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <string>
+
+namespace {
+
+thread_local std::string g_last_error;
+
+int fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_last_error = buf;
+    return code;
+}
+
+bool rate_ok(int rate) { return rate == 2 || rate == 3; }
+
+constexpr int kWavesPerGroup = 4;
+constexpr int kThreads = 64 * kWavesPerGroup;
+
+}  // namespace
+
+namespace svsfec {
+
+template <int RATE, typename In>
+__global__ __launch_bounds__(kThreads) void decode_kernel(const In *__restrict__ in, uint64_t n_info, uint64_t n_segments,
+                                                           uint8_t *__restrict__ out, uint64_t out_bytes) {
+    __shared__ uint64_t s_dec[kWavesPerGroup][kWindow];
+    __shared__ int16_t s_w[kWavesPerGroup][kWindow * RATE];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t seg = (uint64_t)blockIdx.x * kWavesPerGroup + wave;
+    const bool live = seg < n_segments;                  // wave-uniform; a wave without a segment only meets the barriers
+    const uint64_t n = n_info + kTail;
+    const uint64_t a = seg * kSegment;
+    const uint64_t ws = window_start(a), we = live ? window_end(a, n) : ws;
+    const int len = (int)(we - ws);                      // 1 .. 640 for a live wave
+    int16_t *w = s_w[wave];
+    uint64_t *dec = s_dec[wave];
+
+    if (live) {
+        const In *src = in + (uint64_t)RATE * ws;        // the last window ends at coded bit RATE * n - 1
+        for (int i = lane; i < RATE * len; i += 64) w[i] = (int16_t)weight_of(src[i]);
+    }
+    __syncthreads();
+
+    int32_t m = start_metric(ws, (uint32_t)lane);
+    if (live) {
+        const int from0 = 4 * (int)pred0((uint32_t)lane);           // ds_bpermute addresses a lane by 4 * its number
+        const int sign[3] = {branch_sign(lane, 0), branch_sign(lane, 1), branch_sign(lane, 2)};
+        for (int base = 0; base < len; base += 64) {
+            const int count = len - base < 64 ? len - base : 64;
+            uint64_t keep = 0;                                       // lane i: the decisions of step base + i
+            for (int i = 0; i < count; ++i) {
+                const int16_t *wt = w + RATE * (base + i);
+                const int32_t ww[3] = {wt[0], wt[1], RATE == 3 ? wt[2] : 0};
+                const int32_t bm = branch_metric<RATE>(sign, ww);
+                const int32_t m0 = __builtin_amdgcn_ds_bpermute(from0, m);
+                const int32_t m1 = __builtin_amdgcn_ds_bpermute(from0 + 4, m);
+                uint32_t d;
+                m = acs(m0, m1, bm, &d);
+                const uint64_t word = __ballot(d);
+                keep = lane == i ? word : keep;
+            }
+            if (lane < count) dec[base + lane] = keep;
+        }
+    }
+    __syncthreads();
+
+    if (!live) return;
+    uint32_t s = 0;
+    if (we != n) {                                       // the lowest-numbered state with the largest metric
+        int32_t best = m;
+        for (int o = 32; o; o >>= 1) {
+            const int32_t other = __shfl_xor(best, o);
+            best = other > best ? other : best;
+        }
+        s = (uint32_t)(__ffsll((unsigned long long)__ballot(m == best)) - 1);
+    }
+    s = (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+    const int lead = a > 0 ? 1 : 0;                      // a - ws is 0 or 64: whole words of the window lie before the segment
+    uint64_t mine = 0;                                   // lane i: the word that holds byte i of the segment
+    for (int base = ((len - 1) >> 6) << 6; base >= 64 * lead; base -= 64) {
+        const int count = len - base < 64 ? len - base : 64;
+        const uint64_t word = lane < count ? dec[base + lane] : 0;
+        const int lo = (int)(uint32_t)word, hi = (int)(uint32_t)(word >> 32);
+        uint64_t bits = 0;
+        for (int i = count - 1; i >= 0; --i) {
+            const uint64_t d = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(hi, i) << 32) | (uint32_t)__builtin_amdgcn_readlane(lo, i);
+            bits |= (uint64_t)trace_step(d, &s) << i;
+        }
+        if ((lane >> 3) == (base >> 6) - lead) mine = bits;
+    }
+    // bit k of the word is step 8 (lane & ~7) + k; the byte wants its first step in bit 7
+    uint32_t byte = __brev((uint32_t)(mine >> (8 * (lane & 7))) & 0xFFu) >> 24;
+    const uint64_t at = seg * (kSegment / 8) + (uint64_t)lane;
+    if (at < out_bytes) {
+        if (at == out_bytes - 1 && (n_info & 7)) byte &= 0xFF00u >> (n_info & 7);   // the pad bits of the last byte are 0
+        out[at] = (uint8_t)byte;
+    }
+}
+
+}  // namespace svsfec
+
+namespace {
+
+template <typename In>
+int decode(const In *d_in, uint64_t n_info, int rate, uint8_t *d_out, uint64_t out_capacity_bytes, void *stream, const char *what) {
+    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "%s: rate %d is neither 2 nor 3", what, rate);
+    if (n_info == 0) return SVS_OK;
+    if (n_info > SVS_FEC_MAX_INFO_BITS)
+        return fail(SVS_ERR_INVALID_ARG, "%s: n_info %llu exceeds SVS_FEC_MAX_INFO_BITS", what, (unsigned long long)n_info);
+    if (!d_in || !d_out) return fail(SVS_ERR_INVALID_ARG, "%s: NULL pointer", what);
+    if (sizeof(In) == 4 && ((uintptr_t)d_in & 3u)) return fail(SVS_ERR_INVALID_ARG, "%s: weights are not 4-byte aligned", what);
+    const uint64_t out_bytes = (n_info + 7) / 8;
+    if (out_capacity_bytes < out_bytes)
+        return fail(SVS_ERR_CAPACITY, "%s: the output holds %llu bytes, the call writes %llu", what,
+                    (unsigned long long)out_capacity_bytes, (unsigned long long)out_bytes);
+    const uint64_t n_segments = (n_info + svsfec::kSegment - 1) / svsfec::kSegment;   // segments behind n_info hold tail steps only
+    const uint64_t groups = (n_segments + kWavesPerGroup - 1) / kWavesPerGroup;       // at most 2^29 at SVS_FEC_MAX_INFO_BITS
+    hipStream_t st = (hipStream_t)stream;
+    if (rate == 2)
+        hipLaunchKernelGGL((svsfec::decode_kernel<2, In>), dim3((uint32_t)groups), dim3(kThreads), 0, st, d_in, n_info, n_segments, d_out,
+                           out_bytes);
+    else
+        hipLaunchKernelGGL((svsfec::decode_kernel<3, In>), dim3((uint32_t)groups), dim3(kThreads), 0, st, d_in, n_info, n_segments, d_out,
+                           out_bytes);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SVS_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    return SVS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svs_fec_abi_version(void) { return SVS_FEC_ABI_VERSION; }
+
+const char *svs_fec_last_error(void) { return g_last_error.c_str(); }
+
+uint64_t svs_fec_coded_bits(uint64_t n_info, int rate) {
+    if (!rate_ok(rate) || n_info > SVS_FEC_MAX_INFO_BITS) return 0;
+    return (uint64_t)rate * (n_info + SVS_FEC_TAIL);
+}
+
+uint64_t svs_fec_info_bits(uint64_t capacity_bits, int rate) {
+    if (!rate_ok(rate)) return 0;
+    const uint64_t steps = capacity_bits / (uint64_t)rate;
+    return steps > SVS_FEC_TAIL ? steps - SVS_FEC_TAIL : 0;
+}
+
+int svs_fec_encode(const uint8_t *info_packed, uint64_t n_info, int rate, uint8_t *coded_packed_out, uint64_t capacity_bytes,
+                   uint64_t *n_coded_out) {
+    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: rate %d is neither 2 nor 3", rate);
+    if (n_info == 0) {
+        if (n_coded_out) *n_coded_out = 0;
+        return SVS_OK;
+    }
+    if (n_info > SVS_FEC_MAX_INFO_BITS)
+        return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: n_info %llu exceeds SVS_FEC_MAX_INFO_BITS", (unsigned long long)n_info);
+    if (!info_packed || !coded_packed_out) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: NULL pointer");
+    const uint64_t n = n_info + SVS_FEC_TAIL, n_coded = (uint64_t)rate * n, bytes = (n_coded + 7) / 8;
+    if (capacity_bytes < bytes)
+        return fail(SVS_ERR_CAPACITY, "svs_fec_encode: the output holds %llu bytes, the call writes %llu",
+                    (unsigned long long)capacity_bytes, (unsigned long long)bytes);
+    uint32_t s = 0, acc = 0;
+    uint64_t at = 0;                                     // coded bits written so far
+    for (uint64_t t = 0; t < n; ++t) {
+        const uint32_t x = t < n_info ? (info_packed[t >> 3] >> (7 - (t & 7))) & 1u : 0u;
+        for (int j = 0; j < rate; ++j) {
+            acc = (acc << 1) | svsfec::output_bit(s, x, j);
+            if ((++at & 7) == 0) {
+                coded_packed_out[(at >> 3) - 1] = (uint8_t)acc;
+                acc = 0;
+            }
+        }
+        s = svsfec::next_state(s, x);
+    }
+    if (at & 7) coded_packed_out[at >> 3] = (uint8_t)(acc << (8 - (at & 7)));
+    if (n_coded_out) *n_coded_out = n_coded;
+    return SVS_OK;
+}
+
+int svs_fec_decode_soft_dev(const uint8_t *d_soft, uint64_t n_info, int rate, uint8_t *d_info_packed_out, uint64_t out_capacity_bytes,
+                            void *stream) {
+    return decode<uint8_t>(d_soft, n_info, rate, d_info_packed_out, out_capacity_bytes, stream, "svs_fec_decode_soft_dev");
+}
+
+int svs_fec_decode_weights_dev(const int32_t *d_weights, uint64_t n_info, int rate, uint8_t *d_info_packed_out,
+                               uint64_t out_capacity_bytes, void *stream) {
+    return decode<int32_t>(d_weights, n_info, rate, d_info_packed_out, out_capacity_bytes, stream, "svs_fec_decode_weights_dev");
+}
+
+}  // extern "C"

@@ -11,6 +11,8 @@ Two levels:
   * `embed_repeated_frames`, `extract_vote_frames` / `extract_vote_device`   a payload tiled through the stream, and the
                                            fused soft vote that folds its copies on the device: `period` integers come back.
   * `extract_histogram_frames` / `extract_histogram_device`   the fused per-frame soft histograms: 256 counts a frame come back.
+  * `embed_coded_frames` / `extract_coded_frames`   a payload under the convolutional code of svsdct/fec.py: the soft bytes (or the
+                                           tally of its copies) stay on the device and feed the Viterbi decoder; the payload comes back.
 Bits travel packed MSB-first (numpy.packbits order), so `unpack_to_str` of the extract output is
 the reference operator's '0'/'1' string.
 """
@@ -25,6 +27,7 @@ import numpy as np
 from . import channel as _channel
 from . import coeffs as _coeffs
 from . import dither as _dither
+from . import fec as _fec
 from . import native
 from . import matrix as _matrix
 from . import steps as _steps
@@ -558,6 +561,82 @@ def embed_repeated_frames(frames: np.ndarray, delta, n_ac, bits, copies: int | N
     stream = _soft.tile(bits, cap if copies is None else min(cap, int(copies) * bits.size))
     stego, used, *counts = embed_frames(frames, delta, n_ac, stream, **embed_kw)
     return (stego, used, int(bits.size), *counts)
+
+
+def _coded_copies(copies):
+    if copies is not None and (isinstance(copies, bool) or int(copies) < 1):
+        raise ValueError("copies must be at least 1 (None: as many as the capacity holds)")
+    return None if copies is None else int(copies)
+
+
+def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2, copies: int | None = 1, **embed_kw):
+    """Embed a payload under the convolutional code (svsdct/fec.py, include/svsfec.h): fec.encode(info_bits, rate) - rate 2 or 3
+    coded bits a payload bit, six tail bits -, then soft.tile when copies > 1 (copies=None: as many as the stack's capacity
+    holds, the last one cut), then embed_frames, which takes every other keyword (coeffs, dither_key, block_key, steps, the
+    rules and read-backs).  The coded stream must fit: fec.info_bits(capacity, rate) is the largest payload of one copy.
+    Returns (stego, used, n_info), and the counts behind them where embed_frames returns them; the receiver passes n_info, rate
+    and copies to extract_coded_frames.
+    matrix: refused (ValueError): a syndrome bit has no margin, so a matrix call has no soft form to decode."""
+    _no_matrix(embed_kw.get("matrix"), "coded")
+    if "bit_offset" in embed_kw or "n_bits" in embed_kw:
+        raise ValueError("embed_coded_frames embeds the whole coded stream: bit_offset and n_bits are not its keywords")
+    copies = _coded_copies(copies)
+    info = np.asarray(str_to_bits(info_bits) if isinstance(info_bits, str) else info_bits, np.uint8).reshape(-1)
+    if info.size == 0:
+        raise ValueError("an empty payload cannot be coded")
+    f, h, w = _as_stack(frames).shape
+    cap = capacity_bits(f, h, w, n_ac)
+    coded = _fec.encode(info, rate)
+    if coded.size > cap:
+        raise ValueError(f"{coded.size} coded bits exceed the capacity of {cap}: at rate {rate} it holds {_fec.info_bits(cap, rate)} payload bits")
+    stream = coded if copies == 1 else _soft.tile(coded, cap if copies is None else min(cap, copies * coded.size))
+    stego, used, *counts = embed_frames(frames, delta, n_ac, stream, **embed_kw)
+    return (stego, used, int(info.size), *counts)
+
+
+def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int = 2, copies: int | None = 1, device: int = 0,
+                         mode: str | None = None, block_key=None, first_frame=None, coeffs=None, dither_key=None, steps=None,
+                         matrix=None) -> np.ndarray:
+    """Read a payload embedded by embed_coded_frames: the frames go to the device once, the soft bytes never leave it, and only
+    ceil(n_info / 8) bytes come back.
+      copies = 1:  svs_soft_extract_dev into device memory, then svs_fec_decode_soft_dev on its first fec.coded_bits(n_info, rate)
+                   bytes, on the same stream.
+      otherwise:   svs_soft_vote_dev with period = n_coded into a zeroed tally, then svs_fec_decode_weights_dev on the tally.
+                   Every capacity bit of the stack votes, so bits behind the last copy vote as noise: let the copies fill the
+                   capacity (copies=None on both sides does).
+    coeffs, dither_key, block_key, first_frame, steps: as extract_soft_frames (the sender's).  Returns uint8 0/1 [n_info].
+    matrix: refused (ValueError): a syndrome bit has no margin."""
+    _no_matrix(matrix, "coded")
+    copies = _coded_copies(copies)
+    n_coded = _fec.coded_bits(n_info, rate)
+    n_info = int(n_info)
+    if n_info == 0:
+        raise ValueError("an empty payload cannot be decoded")
+    table = _steps_arg(steps)
+    call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
+    stack = _as_stack(frames)
+    f, h, w = stack.shape
+    cap = capacity_bits(f, h, w, n_ac)
+    if n_coded > cap:
+        raise ValueError(f"{n_coded} coded bits exceed the capacity of {cap}")
+    lib = native.load()
+    _fec.load()
+    native.ensure_device(device)
+    planes = Planes.contiguous(f, h, w)
+    out_bytes = (n_info + 7) // 8
+    with _fec._Staged() as dev:
+        d_gray, d_out = dev.alloc(stack.nbytes), dev.alloc(out_bytes)
+        native.check(lib.svs_memcpy_h2d(d_gray, stack.ctypes.data, stack.nbytes, None), "svs_memcpy_h2d")
+        if copies == 1:
+            d_soft = dev.alloc(cap)
+            _soft_call(lib, "extract", call, [d_gray, C.byref(planes)], delta, n_ac, [d_soft, cap], mode_flags(mode), (None,), table)
+            _fec.decode_soft_device(d_soft, n_info, rate, d_out, out_bytes)
+        else:
+            d_tally = dev.alloc(4 * n_coded)
+            native.check(lib.svs_memset(d_tally, 0, 4 * n_coded, None), "svs_memset")
+            _soft_call(lib, "vote", call, [d_gray, C.byref(planes)], delta, n_ac, [n_coded, 0, d_tally], 0, (None,), table)
+            _fec.decode_weights_device(d_tally, n_info, rate, d_out, out_bytes)
+        return _fec.download_info(d_out, n_info)
 
 
 def requantise_frames(frames: np.ndarray, steps_or_quality, device: int = 0) -> np.ndarray:

@@ -1,0 +1,188 @@
+"""The convolutional code and its soft-decision Viterbi decoder (libsvsfec.so, include/svsfec.h): a constraint-length-7 code
+at rate 1/2 (generators 133, 171) or 1/3 (133, 171, 165), six zero tail bits, decoded on the device by a windowed Viterbi from
+one soft byte (svs_soft_extract) or one int32 (an entry of svs_soft_vote's tally) per coded bit.
+
+    coded = encode(info_bits, rate)                          host: 0/1 per coded bit
+    ... embed `coded`, let the channel do its worst, soft-extract ...
+    info = decode_soft(soft_bytes, n_info, rate)             device: 0/1 per payload bit
+
+batch.embed_coded_frames / batch.extract_coded_frames wrap both ends around the frame calls and keep the soft bytes on the device.
+The library is loaded on first use; SVSFEC_LIB overrides its path.  There is no CPU fallback for the decoder.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import native
+from .native import SvsNativeError
+
+LIB_PATH = os.environ.get("SVSFEC_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsfec.so"))
+ABI_VERSION = 1
+RATES = (2, 3)
+SEGMENT, OVERLAP, TAIL = 512, 64, 6
+MAX_INFO_BITS = 1 << 40
+
+_u8p = C.c_void_p
+# name -> (restype, argtypes); every symbol include/svsfec.h declares
+SIGNATURES = {
+    "svs_fec_abi_version": (C.c_int, []),
+    "svs_fec_last_error": (C.c_char_p, []),
+    "svs_fec_coded_bits": (C.c_uint64, [C.c_uint64, C.c_int]),
+    "svs_fec_info_bits": (C.c_uint64, [C.c_uint64, C.c_int]),
+    "svs_fec_encode": (C.c_int, [_u8p, C.c_uint64, C.c_int, _u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "svs_fec_decode_soft_dev": (C.c_int, [_u8p, C.c_uint64, C.c_int, _u8p, C.c_uint64, C.c_void_p]),
+    "svs_fec_decode_weights_dev": (C.c_int, [_u8p, C.c_uint64, C.c_int, _u8p, C.c_uint64, C.c_void_p]),
+}
+
+_lib = None
+
+
+def load() -> C.CDLL:
+    """Load libsvsfec.so once and attach prototypes.  Loading does not touch the GPU."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise SvsNativeError(f"libsvsfec.so not found at {LIB_PATH}; build it with `python __graft_entry__.py` "
+                             f"(or `make -C <package>/csrc`). There is no CPU fallback.")
+    try:
+        lib = C.CDLL(LIB_PATH)
+    except OSError as exc:
+        raise SvsNativeError(f"cannot load {LIB_PATH}: {exc}") from exc
+    for name, (res, args) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise SvsNativeError(f"{LIB_PATH} does not export {name}; rebuild it") from exc
+        fn.restype, fn.argtypes = res, args
+    if lib.svs_fec_abi_version() != ABI_VERSION:
+        raise SvsNativeError(f"ABI version mismatch: {LIB_PATH} reports {lib.svs_fec_abi_version()}, the binding expects "
+                             f"{ABI_VERSION}; rebuild libsvsfec.so")
+    _lib = lib
+    return lib
+
+
+def check(rc: int, what: str) -> None:
+    if rc != native.SVS_OK:
+        raise SvsNativeError(f"{what} failed ({rc}): {load().svs_fec_last_error().decode('utf-8', 'replace')}", rc)
+
+
+def _rate(rate) -> int:
+    if isinstance(rate, bool) or rate not in RATES:
+        raise ValueError(f"rate {rate!r}: 2 (rate 1/2) or 3 (rate 1/3)")
+    return int(rate)
+
+
+def _n_info(n_info) -> int:
+    n_info = int(n_info)
+    if not 0 <= n_info <= MAX_INFO_BITS:
+        raise ValueError(f"n_info {n_info} outside 0 .. 2**40")
+    return n_info
+
+
+def coded_bits(n_info: int, rate: int = 2) -> int:
+    """rate * (n_info + 6): the coded bits of n_info payload bits"""
+    return _rate(rate) * (_n_info(n_info) + TAIL)
+
+
+def info_bits(capacity_bits: int, rate: int = 2) -> int:
+    """capacity // rate - 6, at least 0: the largest payload whose coded stream fits capacity_bits"""
+    return max(int(capacity_bits) // _rate(rate) - TAIL, 0)
+
+
+def encode(bits, rate: int = 2) -> np.ndarray:
+    """Payload bits (0/1 per entry) -> the coded stream, uint8 0/1 per coded bit (svs_fec_encode; host code, no GPU)."""
+    rate = _rate(rate)
+    b = np.asarray(bits, np.uint8).reshape(-1)
+    if b.size == 0:
+        return np.zeros(0, np.uint8)
+    packed = np.packbits(b)
+    n_coded = coded_bits(b.size, rate)
+    out = np.empty((n_coded + 7) // 8, np.uint8)
+    got = C.c_uint64(0)
+    check(load().svs_fec_encode(packed.ctypes.data, b.size, rate, out.ctypes.data, out.size, C.byref(got)), "svs_fec_encode")
+    assert got.value == n_coded
+    return np.unpackbits(out, count=n_coded)
+
+
+def decode_soft_device(d_soft: int, n_info: int, rate: int, d_info_packed_out: int, out_capacity_bytes: int, stream: int = 0) -> None:
+    """Enqueue the decoder on `stream` (svs_fec_decode_soft_dev): rate * (n_info + 6) soft bytes at d_soft, coded bit i in
+    byte i, -> ceil(n_info / 8) packed bytes at d_info_packed_out."""
+    check(load().svs_fec_decode_soft_dev(d_soft, _n_info(n_info), _rate(rate), d_info_packed_out, int(out_capacity_bytes),
+                                         stream or None), "svs_fec_decode_soft_dev")
+
+
+def decode_weights_device(d_weights: int, n_info: int, rate: int, d_info_packed_out: int, out_capacity_bytes: int,
+                          stream: int = 0) -> None:
+    """Enqueue the decoder on `stream` (svs_fec_decode_weights_dev): rate * (n_info + 6) int32 weights (4-byte aligned, each
+    clamped to +-32767; the tally of svs_soft_vote_dev at period = n_coded) -> ceil(n_info / 8) packed bytes."""
+    check(load().svs_fec_decode_weights_dev(d_weights, _n_info(n_info), _rate(rate), d_info_packed_out, int(out_capacity_bytes),
+                                            stream or None), "svs_fec_decode_weights_dev")
+
+
+class _Staged:
+    """device buffers of one staged call (svs_malloc), freed when the call is over"""
+
+    def __init__(self):
+        self.lib, self.ptrs = native.load(), []
+
+    def alloc(self, nbytes: int) -> int:
+        p = C.c_void_p()
+        native.check(self.lib.svs_malloc(C.byref(p), max(int(nbytes), 4)), "svs_malloc")
+        self.ptrs.append(p)
+        return p.value
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.ptrs:
+            self.lib.svs_free(p)
+        return False
+
+
+def download_info(d_packed: int, n_info: int) -> np.ndarray:
+    """ceil(n_info / 8) bytes from the device (null stream, synchronised) -> 0/1 per payload bit"""
+    lib = native.load()
+    out = np.empty((n_info + 7) // 8, np.uint8)
+    if out.size:
+        native.check(lib.svs_memcpy_d2h(out.ctypes.data, d_packed, out.size, None), "svs_memcpy_d2h")
+    native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+    return np.unpackbits(out, count=n_info)
+
+
+def _decode_staged(values: np.ndarray, n_info: int, rate: int, device: int, call) -> np.ndarray:
+    n_info, rate = _n_info(n_info), _rate(rate)
+    if values.ndim != 1 or values.size != coded_bits(n_info, rate):
+        raise ValueError(f"{values.size} values are not the {coded_bits(n_info, rate)} coded bits of n_info = {n_info} at rate {rate}")
+    if n_info == 0:
+        return np.zeros(0, np.uint8)
+    load()
+    native.ensure_device(device)
+    values = np.ascontiguousarray(values)
+    with _Staged() as dev:
+        d_in, d_out = dev.alloc(values.nbytes), dev.alloc((n_info + 7) // 8)
+        native.check(dev.lib.svs_memcpy_h2d(d_in, values.ctypes.data, values.nbytes, None), "svs_memcpy_h2d")
+        call(d_in, n_info, rate, d_out, (n_info + 7) // 8)
+        return download_info(d_out, n_info)
+
+
+def decode_soft(soft_bytes, n_info: int, rate: int = 2, device: int = 0) -> np.ndarray:
+    """Decode soft bytes held on the host: staged through svs_malloc / svs_memcpy_*, decoded by svs_fec_decode_soft_dev.
+    soft_bytes: uint8 [coded_bits(n_info, rate)].  Returns uint8 0/1 [n_info]."""
+    a = np.asarray(soft_bytes)
+    if a.dtype != np.uint8:
+        raise TypeError("soft_bytes must be uint8: one byte per coded bit (svs_soft_extract)")
+    return _decode_staged(a, n_info, rate, device, decode_soft_device)
+
+
+def decode_weights(weights, n_info: int, rate: int = 2, device: int = 0) -> np.ndarray:
+    """decode_soft for int32 weights held on the host (svs_fec_decode_weights_dev): a tally of svs_soft_vote, or any integers
+    whose sign is the bit and whose size is the confidence."""
+    a = np.asarray(weights)
+    if a.dtype != np.int32:
+        raise TypeError("weights must be int32: one value per coded bit (soft.tally)")
+    return _decode_staged(a, n_info, rate, device, decode_weights_device)
