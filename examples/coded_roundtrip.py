@@ -8,7 +8,8 @@ back), the tiled one by the fused soft vote (batch.extract_vote_frames).
 
     python examples/coded_roundtrip.py [--quality 75] [--rate 2] [--delta 20] [--n-ac 10]
 
-At the defaults the code delivers all 3 594 bits and three copies leave 51 of 2 400 wrong (README.md has the table).
+At the defaults the code delivers all 3 594 bits and three copies leave 51 of 2 400 wrong; --rate 34, the rate-1/2 code punctured
+to rate 3/4, delivers 5 394 (README.md has the tables).
 """
 import argparse
 import os
@@ -22,7 +23,8 @@ from svsdct import batch, fec  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--quality", type=int, default=75, help="quality of the requantisation channel, 1..100")
-ap.add_argument("--rate", type=int, default=2, choices=fec.RATES, help="coded bits a payload bit")
+ap.add_argument("--rate", type=int, default=2, choices=fec.RATES + fec.PUNCTURED,
+                help="coded bits a payload bit (2, 3), or a punctured code: 23, 34, 56, 78 for rate 2/3, 3/4, 5/6, 7/8")
 ap.add_argument("--delta", type=float, default=20)
 ap.add_argument("--n-ac", type=int, default=10)
 a = ap.parse_args()
@@ -37,7 +39,8 @@ received = batch.requantise_frames(stego, a.quality)
 decoded = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate)
 soft, _ = batch.extract_soft_frames(received, a.delta, a.n_ac)
 coded_wrong = int(((soft[:used] >> 7) != fec.encode(info, a.rate)).sum())
-print(f"rate 1/{a.rate}: {n_info} payload bits in {used} of {cap} capacity bits; after the channel at Q = {a.quality} "
+name = f"1/{a.rate}" if a.rate in fec.RATES else f"{a.rate // 10}/{a.rate % 10}"
+print(f"rate {name}: {n_info} payload bits in {used} of {cap} capacity bits; after the channel at Q = {a.quality} "
       f"{coded_wrong} coded bits are wrong, {int((decoded != info).sum())} payload bits after the decoder")
 
 rng = np.random.default_rng(5)                      # the README's experiment: the copy is drawn right behind the cover

@@ -15,7 +15,7 @@
  * THE FORMAT, step by step.  Host and device compute it in integers, so the result is the same bits everywhere.
  *
  * Code
- *   constraint length 7: a state s is the last six input bits, the newest in bit 5.  rate = r is 2 or 3.
+ *   constraint length 7: a state s is the last six input bits, the newest in bit 5.  rate = r is 2 or 3 (or a punctured code, below).
  *   generators (octal)   g_0 = 133, g_1 = 171          at rate 2 (rate 1/2),
  *                        g_0 = 133, g_1 = 171, g_2 = 165 at rate 3 (rate 1/3).
  *   one step, state s and input bit x:
@@ -26,6 +26,27 @@
  *       n = n_info + 6 steps,   n_coded = r * n coded bits,   coded bit r * t + j is out_j of step t.
  *   svs_fec_info_bits(capacity, r) = capacity / r - 6 (integer division; 0 when that is not positive) is the largest n_info
  *   whose coded stream fits `capacity` bits.
+ *
+ * Punctured codes
+ *   the `rate` argument of every function is a code: 2 and 3 are the two rates above, and four more values name a punctured
+ *   stream - the rate-2 code (generators 133, 171) with some coded bits not sent.  Period P; step t is step i = t mod P of its
+ *   period and sends out_0 and out_1 where the row has a 1; K bits are sent a period:
+ *       code                    P   out_0 (133) sent   out_1 (171) sent   K
+ *       23  SVS_FEC_RATE_2_3    2   1 1                1 0                3
+ *       34  SVS_FEC_RATE_3_4    3   1 1 0              1 0 1              4
+ *       56  SVS_FEC_RATE_5_6    5   1 1 0 1 0          1 0 1 0 1          6
+ *       78  SVS_FEC_RATE_7_8    7   1 1 1 1 0 1 0      1 0 0 0 1 0 1      8
+ *   Every step sends at least one bit.
+ *       pre[i] = the sent bits of the steps 0 .. i - 1 of a period (pre[0] = 0)
+ *       S(t)   = (t div P) * K + pre[t mod P]        the sent bits before step t; strictly increasing
+ *   the encoder runs the rate-2 encoder over its n = n_info + 6 steps and sends the kept bits of step t, out_0 before out_1, at
+ *   the positions S(t) and following.  The last period is simply cut: n_sent = S(n) is what svs_fec_coded_bits(n_info, code)
+ *   returns, and wherever this header says r * (n_info + 6) a punctured code has n_sent.
+ *   svs_fec_info_bits(capacity, code) = (the largest n with S(n) <= capacity) - 6, 0 when that is not positive.
+ *   the decoders take n_sent soft bytes or int32 values, one per sent bit, and turn each into its weight as below.  Mother bit
+ *   2 t + j (out_j of step t) has the weight of its sent bit when it was sent and the weight 0 when not.  From there the decoder is
+ *   the rate-2 decoder below, word for word: windows, start metrics, ties, traceback.  Zeros only make |bm| smaller, so the
+ *   bound on the metrics holds unchanged.
  *
  * Weights
  *   the decoder sees one integer w per coded bit, positive for 1, |w| the confidence:
@@ -55,7 +76,7 @@
  *   The windowed decoder IS the format: with enough noise it differs from an untruncated Viterbi in a few bits.
  *
  * Refusals of svs_fec_encode and the two decoders, in this order and before any device work:
- *   1. rate other than 2 or 3                                             SVS_ERR_INVALID_ARG
+ *   1. rate other than 2, 3, 23, 34, 56, 78                               SVS_ERR_INVALID_ARG
  *   2. n_info = 0                                                          SVS_OK: nothing is done, no pointer is looked at
  *                                                                          (svs_fec_encode still reports *n_coded_out)
  *   3. n_info above SVS_FEC_MAX_INFO_BITS (2^40: the coded length of a larger one leaves what any device holds long before
@@ -90,28 +111,38 @@ extern "C" {
 #define SVS_FEC_TAIL 6            /* zero bits behind the payload */
 #define SVS_FEC_MAX_INFO_BITS (1ull << 40)
 
+/* values of `rate` beside 2 (rate 1/2) and 3 (rate 1/3): the punctured codes of "Punctured codes" above */
+#define SVS_FEC_RATE_2_3 23
+#define SVS_FEC_RATE_3_4 34
+#define SVS_FEC_RATE_5_6 56
+#define SVS_FEC_RATE_7_8 78
+
 int svs_fec_abi_version(void);
 const char *svs_fec_last_error(void);
 
-/* r * (n_info + 6); 0 for a rate other than 2 or 3 or an n_info above SVS_FEC_MAX_INFO_BITS */
+/* r * (n_info + 6), under a punctured code S(n_info + 6); 0 for a rate that is none of the six or an n_info above
+ * SVS_FEC_MAX_INFO_BITS */
 uint64_t svs_fec_coded_bits(uint64_t n_info, int rate);
-/* capacity / r - 6, 0 when that is not positive or the rate is neither 2 nor 3 */
+/* capacity / r - 6, under a punctured code (the largest n with S(n) <= capacity) - 6; 0 when that is not positive or the rate
+ * is none of the six */
 uint64_t svs_fec_info_bits(uint64_t capacity_bits, int rate);
 
-/* Host only.  Encodes the first n_info bits of info_packed into coded_packed_out: ceil(n_coded / 8) bytes are written, the
+/* Host only.  Encodes the first n_info bits of info_packed into coded_packed_out at `rate` (2, 3 or a punctured code, whose
+ * unsent bits are left out: n_coded = n_sent): ceil(n_coded / 8) bytes are written, the
  * pad bits of the last one 0, no byte behind it; capacity_bytes is the size of the output buffer.  The input is not written;
  * the buffers must not overlap. */
 int svs_fec_encode(const uint8_t *info_packed, uint64_t n_info, int rate, uint8_t *coded_packed_out, uint64_t capacity_bytes,
                    uint64_t *n_coded_out);
 
-/* Decodes r * (n_info + 6) soft bytes at d_soft - coded bit i is byte i; a caller whose coded stream starts inside a buffer
+/* Decodes r * (n_info + 6) soft bytes at d_soft (under a punctured code its n_sent soft bytes, one per sent bit, and no more
+ * are read) - coded bit i is byte i; a caller whose coded stream starts inside a buffer
  * offsets the pointer, any alignment - into ceil(n_info / 8) bytes at d_info_packed_out: the pad bits of the last byte are 0,
  * no byte behind it is written, the input is not written.  The buffers must not overlap.  One launch on `stream`. */
 int svs_fec_decode_soft_dev(const uint8_t *d_soft, uint64_t n_info, int rate, uint8_t *d_info_packed_out,
                             uint64_t out_capacity_bytes, void *stream);
 
-/* The same call on r * (n_info + 6) int32 weights (4-byte aligned), each clamped to -32767 .. 32767: the tally of
- * svs_soft_vote_dev at period = n_coded is such an array. */
+/* The same call on r * (n_info + 6) int32 weights (n_sent under a punctured code; 4-byte aligned), each clamped to
+ * -32767 .. 32767: the tally of svs_soft_vote_dev at period = n_coded is such an array. */
 int svs_fec_decode_weights_dev(const int32_t *d_weights, uint64_t n_info, int rate, uint8_t *d_info_packed_out,
                                uint64_t out_capacity_bytes, void *stream);
 

@@ -3,7 +3,9 @@
 //
 // The decoder kernel: one wave decodes one segment, lane s owns trellis state s.
 //   1. the window's weights are loaded coalesced, converted (soft byte or int32 -> int16) and kept in a run of LDS private to
-//      the wave; every lane then reads a step's weights from the same address (a broadcast).
+//      the wave; every lane then reads a step's weights from the same address (a broadcast).  Under a punctured code the
+//      window's run of sent values [S(ws), S(we)) is loaded and spread over the rate-2 run, zeros at the unsent bits
+//      (decode_punctured_kernel; profiles/fec_punctured_resources.txt); nothing behind the load knows of it.
 //   2. add-compare-select: two cross-lane reads of the predecessors' metrics (ds_bpermute), one add, one subtract, a compare
 //      and a select.  The signs of a lane's branch metric are lane constants.  The 64 decisions of a step are one ballot word;
 //      lane i of the wave collects the word of step 64 c + i, and every 64 steps the words go to the wave's run of LDS in one
@@ -35,7 +37,14 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-bool rate_ok(int rate) { return rate == 2 || rate == 3; }
+bool punctured(int rate) { return svsfec::puncture(rate).period != 0; }
+bool rate_ok(int rate) { return rate == 2 || rate == 3 || punctured(rate); }
+const char *const kRates = "none of 2, 3, 23, 34, 56, 78";
+
+// the values a stream of n steps holds: rate * n, or S(n) of a punctured code
+uint64_t stream_bits(uint64_t n, int rate) {
+    return punctured(rate) ? svsfec::sent_before(svsfec::puncture(rate), n) : (uint64_t)rate * n;
+}
 
 constexpr int kWavesPerGroup = 4;
 constexpr int kThreads = 64 * kWavesPerGroup;
@@ -44,9 +53,11 @@ constexpr int kThreads = 64 * kWavesPerGroup;
 
 namespace svsfec {
 
-template <int RATE, typename In>
-__global__ __launch_bounds__(kThreads) void decode_kernel(const In *__restrict__ in, uint64_t n_info, uint64_t n_segments,
-                                                           uint8_t *__restrict__ out, uint64_t out_bytes) {
+// CODE = 0: the RATE coded bits of every step are there.  CODE = a punctured code (RATE is 2): the window's run of sent values is
+// spread over the wave's weights on the way in, zeros where a bit was not sent; everything behind the load is the same code.
+template <int RATE, int CODE, typename In>
+__device__ __forceinline__ void decode_segment(const In *__restrict__ in, uint64_t n_info, uint64_t n_segments,
+                                               uint8_t *__restrict__ out, uint64_t out_bytes) {
     __shared__ uint64_t s_dec[kWavesPerGroup][kWindow];
     __shared__ int16_t s_w[kWavesPerGroup][kWindow * RATE];
 
@@ -61,9 +72,31 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(const In *__restrict__
     int16_t *w = s_w[wave];
     uint64_t *dec = s_dec[wave];
 
-    if (live) {
-        const In *src = in + (uint64_t)RATE * ws;        // the last window ends at coded bit RATE * n - 1
-        for (int i = lane; i < RATE * len; i += 64) w[i] = (int16_t)weight_of(src[i]);
+    if constexpr (CODE == 0) {
+        if (live) {
+            const In *src = in + (uint64_t)RATE * ws;    // the last window ends at coded bit RATE * n - 1
+            for (int i = lane; i < RATE * len; i += 64) w[i] = (int16_t)weight_of(src[i]);
+        }
+    } else {
+        static_assert(RATE == kMotherRate, "a punctured code is the rate-2 code");
+        if (live) {
+            // the window reads the sent values [S(ws), S(we)): the last window ends at sent value S(n) - 1.  ws is wave-uniform,
+            // so S(ws) and ws mod P are two divisions by a constant a wave; a lane owns out_(lane & 1) of the steps
+            // (lane >> 1) + 32 k and walks the period 32 steps at a time.  The lanes of sent bits read neighbouring values.
+            constexpr Puncture pc = puncture(CODE);
+            const int phase = (int)(ws % (uint64_t)pc.period);
+            const In *src = in + sent_before(pc, ws);
+            PunctStep at = punct_step(pc, phase + (lane >> 1));
+#pragma unroll 4
+            for (int i = lane; i < RATE * len; i += 64) {
+                // no branch around the load: the lane of an unsent bit reads the run's first value (a step sends at least one
+                // bit, so the run is not empty) and keeps 0, and the loads of several rounds can be in flight together
+                const int k = sent_place(pc, phase, at, lane & 1);
+                const int32_t v = weight_of(src[k < 0 ? 0 : k]);
+                w[i] = (int16_t)(k < 0 ? 0 : v);
+                at = punct_advance(pc, at, 32);
+            }
+        }
     }
     __syncthreads();
 
@@ -123,13 +156,26 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(const In *__restrict__
     }
 }
 
+template <int RATE, typename In>
+__global__ __launch_bounds__(kThreads) void decode_kernel(const In *__restrict__ in, uint64_t n_info, uint64_t n_segments,
+                                                           uint8_t *__restrict__ out, uint64_t out_bytes) {
+    decode_segment<RATE, 0, In>(in, n_info, n_segments, out, out_bytes);
+}
+
+// `in` holds S(n) values, one per sent bit of punctured code CODE
+template <int CODE, typename In>
+__global__ __launch_bounds__(kThreads) void decode_punctured_kernel(const In *__restrict__ in, uint64_t n_info, uint64_t n_segments,
+                                                                     uint8_t *__restrict__ out, uint64_t out_bytes) {
+    decode_segment<kMotherRate, CODE, In>(in, n_info, n_segments, out, out_bytes);
+}
+
 }  // namespace svsfec
 
 namespace {
 
 template <typename In>
 int decode(const In *d_in, uint64_t n_info, int rate, uint8_t *d_out, uint64_t out_capacity_bytes, void *stream, const char *what) {
-    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "%s: rate %d is neither 2 nor 3", what, rate);
+    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "%s: rate %d is %s", what, rate, kRates);
     if (n_info == 0) return SVS_OK;
     if (n_info > SVS_FEC_MAX_INFO_BITS)
         return fail(SVS_ERR_INVALID_ARG, "%s: n_info %llu exceeds SVS_FEC_MAX_INFO_BITS", what, (unsigned long long)n_info);
@@ -142,12 +188,17 @@ int decode(const In *d_in, uint64_t n_info, int rate, uint8_t *d_out, uint64_t o
     const uint64_t n_segments = (n_info + svsfec::kSegment - 1) / svsfec::kSegment;   // segments behind n_info hold tail steps only
     const uint64_t groups = (n_segments + kWavesPerGroup - 1) / kWavesPerGroup;       // at most 2^29 at SVS_FEC_MAX_INFO_BITS
     hipStream_t st = (hipStream_t)stream;
-    if (rate == 2)
-        hipLaunchKernelGGL((svsfec::decode_kernel<2, In>), dim3((uint32_t)groups), dim3(kThreads), 0, st, d_in, n_info, n_segments, d_out,
-                           out_bytes);
-    else
-        hipLaunchKernelGGL((svsfec::decode_kernel<3, In>), dim3((uint32_t)groups), dim3(kThreads), 0, st, d_in, n_info, n_segments, d_out,
-                           out_bytes);
+    const auto launch = [&](void (*kernel)(const In *, uint64_t, uint64_t, uint8_t *, uint64_t)) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)groups), dim3(kThreads), 0, st, d_in, n_info, n_segments, d_out, out_bytes);
+    };
+    switch (rate) {
+        case 2: launch(svsfec::decode_kernel<2, In>); break;
+        case 3: launch(svsfec::decode_kernel<3, In>); break;
+        case SVS_FEC_RATE_2_3: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_2_3, In>); break;
+        case SVS_FEC_RATE_3_4: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_3_4, In>); break;
+        case SVS_FEC_RATE_5_6: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_5_6, In>); break;
+        default: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_7_8, In>); break;
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SVS_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     return SVS_OK;
@@ -163,18 +214,18 @@ const char *svs_fec_last_error(void) { return g_last_error.c_str(); }
 
 uint64_t svs_fec_coded_bits(uint64_t n_info, int rate) {
     if (!rate_ok(rate) || n_info > SVS_FEC_MAX_INFO_BITS) return 0;
-    return (uint64_t)rate * (n_info + SVS_FEC_TAIL);
+    return stream_bits(n_info + SVS_FEC_TAIL, rate);
 }
 
 uint64_t svs_fec_info_bits(uint64_t capacity_bits, int rate) {
     if (!rate_ok(rate)) return 0;
-    const uint64_t steps = capacity_bits / (uint64_t)rate;
+    const uint64_t steps = punctured(rate) ? svsfec::steps_that_fit(svsfec::puncture(rate), capacity_bits) : capacity_bits / (uint64_t)rate;
     return steps > SVS_FEC_TAIL ? steps - SVS_FEC_TAIL : 0;
 }
 
 int svs_fec_encode(const uint8_t *info_packed, uint64_t n_info, int rate, uint8_t *coded_packed_out, uint64_t capacity_bytes,
                    uint64_t *n_coded_out) {
-    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: rate %d is neither 2 nor 3", rate);
+    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: rate %d is %s", rate, kRates);
     if (n_info == 0) {
         if (n_coded_out) *n_coded_out = 0;
         return SVS_OK;
@@ -182,15 +233,19 @@ int svs_fec_encode(const uint8_t *info_packed, uint64_t n_info, int rate, uint8_
     if (n_info > SVS_FEC_MAX_INFO_BITS)
         return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: n_info %llu exceeds SVS_FEC_MAX_INFO_BITS", (unsigned long long)n_info);
     if (!info_packed || !coded_packed_out) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: NULL pointer");
-    const uint64_t n = n_info + SVS_FEC_TAIL, n_coded = (uint64_t)rate * n, bytes = (n_coded + 7) / 8;
+    const uint64_t n = n_info + SVS_FEC_TAIL, n_coded = stream_bits(n, rate), bytes = (n_coded + 7) / 8;
     if (capacity_bytes < bytes)
         return fail(SVS_ERR_CAPACITY, "svs_fec_encode: the output holds %llu bytes, the call writes %llu",
                     (unsigned long long)capacity_bytes, (unsigned long long)bytes);
     uint32_t s = 0, acc = 0;
     uint64_t at = 0;                                     // coded bits written so far
+    const svsfec::Puncture pc = svsfec::puncture(rate);  // period 0: every bit of a step is sent
+    const int outputs = pc.period ? svsfec::kMotherRate : rate;
+    int step = 0;                                        // t mod P
     for (uint64_t t = 0; t < n; ++t) {
         const uint32_t x = t < n_info ? (info_packed[t >> 3] >> (7 - (t & 7))) & 1u : 0u;
-        for (int j = 0; j < rate; ++j) {
+        for (int j = 0; j < outputs; ++j) {
+            if (pc.period && !svsfec::punct_kept(pc, step, j)) continue;
             acc = (acc << 1) | svsfec::output_bit(s, x, j);
             if ((++at & 7) == 0) {
                 coded_packed_out[(at >> 3) - 1] = (uint8_t)acc;
@@ -198,6 +253,7 @@ int svs_fec_encode(const uint8_t *info_packed, uint64_t n_info, int rate, uint8_
             }
         }
         s = svsfec::next_state(s, x);
+        if (pc.period && ++step == pc.period) step = 0;
     }
     if (at & 7) coded_packed_out[at >> 3] = (uint8_t)(acc << (8 - (at & 7)));
     if (n_coded_out) *n_coded_out = n_coded;

@@ -75,4 +75,58 @@ SVS_FEC_HD uint32_t trace_step(uint64_t word, uint32_t *s) {
     return bit;
 }
 
+// ---- punctured codes ("Punctured codes" in the header): the rate-2 code with some coded bits not sent ----------------------
+// period P, K kept bits a period; bit 2 i + j of `pattern` is set when out_j of step i of a period is sent.  period = 0: `code`
+// is no punctured code
+struct Puncture {
+    int period, kept;
+    uint32_t pattern;
+};
+SVS_FEC_HD constexpr Puncture puncture(int code) {
+    return code == 23   ? Puncture{2, 3, 0x7u}         // out_0 1 1            out_1 1 0
+           : code == 34 ? Puncture{3, 4, 0x27u}        //       1 1 0                1 0 1
+           : code == 56 ? Puncture{5, 6, 0x267u}       //       1 1 0 1 0            1 0 1 0 1
+           : code == 78 ? Puncture{7, 8, 0x2657u}      //       1 1 1 1 0 1 0        1 0 0 0 1 0 1
+                        : Puncture{0, 0, 0u};
+}
+constexpr int kMotherRate = 2;
+
+SVS_FEC_HD uint32_t punct_kept(const Puncture &pc, int i, int j) { return (pc.pattern >> (2 * i + j)) & 1u; }
+// the kept bits of a period before out_j of its step i; j = 0: pre[i]
+SVS_FEC_HD int punct_before(const Puncture &pc, int i, int j = 0) {
+    return __builtin_popcount(pc.pattern & ((1u << (2 * i + j)) - 1u));
+}
+// S(t): the sent bits before step t.  64-bit: t reaches 2^40 + 6
+SVS_FEC_HD uint64_t sent_before(const Puncture &pc, uint64_t t) {
+    return t / (uint64_t)pc.period * (uint64_t)pc.kept + (uint64_t)punct_before(pc, (int)(t % (uint64_t)pc.period));
+}
+// the largest n with S(n) <= capacity.  S is strictly increasing (every step keeps a bit); period < kept, so n <= capacity
+SVS_FEC_HD uint64_t steps_that_fit(const Puncture &pc, uint64_t capacity) {
+    const int left = (int)(capacity % (uint64_t)pc.kept);
+    int i = pc.period - 1;
+    while (punct_before(pc, i) > left) --i;             // pre[0] = 0 ends it
+    return capacity / (uint64_t)pc.kept * (uint64_t)pc.period + (uint64_t)i;
+}
+
+// Where a window finds its mother bits.  A window that starts at step ws = wq P + phase reads the run of sent values from
+// S(ws) on; its step ws + k is step r of period wq + q, with phase + k = q P + r, and small numbers do from there.
+struct PunctStep {
+    int q, r;
+};
+SVS_FEC_HD PunctStep punct_step(const Puncture &pc, int u) { return PunctStep{u / pc.period, u % pc.period}; }
+SVS_FEC_HD PunctStep punct_advance(const Puncture &pc, PunctStep s, int steps) {
+    s.q += steps / pc.period;
+    s.r += steps % pc.period;
+    if (s.r >= pc.period) {
+        s.r -= pc.period;
+        ++s.q;
+    }
+    return s;
+}
+// the place of out_j of that step in the window's run (0 = the value at S(ws)), -1 when it is not sent
+SVS_FEC_HD int sent_place(const Puncture &pc, int phase, PunctStep s, int j) {
+    if (!punct_kept(pc, s.r, j)) return -1;
+    return s.q * pc.kept + punct_before(pc, s.r, j) - punct_before(pc, phase);
+}
+
 }  // namespace svsfec

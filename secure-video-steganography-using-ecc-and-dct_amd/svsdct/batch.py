@@ -571,7 +571,8 @@ def _coded_copies(copies):
 
 def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2, copies: int | None = 1, **embed_kw):
     """Embed a payload under the convolutional code (svsdct/fec.py, include/svsfec.h): fec.encode(info_bits, rate) - rate 2 or 3
-    coded bits a payload bit, six tail bits -, then soft.tile when copies > 1 (copies=None: as many as the stack's capacity
+    coded bits a payload bit, or a punctured code of fec.PUNCTURED (23, 34, 56, 78: rate 2/3 .. 7/8, the unsent bits are not
+    embedded), six tail bits -, then soft.tile when copies > 1 (copies=None: as many as the stack's capacity
     holds, the last one cut), then embed_frames, which takes every other keyword (coeffs, dither_key, block_key, steps, the
     rules and read-backs).  The coded stream must fit: fec.info_bits(capacity, rate) is the largest payload of one copy.
     Returns (stego, used, n_info), and the counts behind them where embed_frames returns them; the receiver passes n_info, rate
@@ -588,7 +589,8 @@ def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2
     cap = capacity_bits(f, h, w, n_ac)
     coded = _fec.encode(info, rate)
     if coded.size > cap:
-        raise ValueError(f"{coded.size} coded bits exceed the capacity of {cap}: at rate {rate} it holds {_fec.info_bits(cap, rate)} payload bits")
+        raise ValueError(f"{coded.size} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
+                         f"{_fec.info_bits(cap, rate)} payload bits")
     stream = coded if copies == 1 else _soft.tile(coded, cap if copies is None else min(cap, copies * coded.size))
     stego, used, *counts = embed_frames(frames, delta, n_ac, stream, **embed_kw)
     return (stego, used, int(info.size), *counts)
@@ -604,6 +606,8 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
       otherwise:   svs_soft_vote_dev with period = n_coded into a zeroed tally, then svs_fec_decode_weights_dev on the tally.
                    Every capacity bit of the stack votes, so bits behind the last copy vote as noise: let the copies fill the
                    capacity (copies=None on both sides does).
+    rate: the sender's, 2, 3 or a punctured code of fec.PUNCTURED; n_coded = fec.coded_bits(n_info, rate) is then the number of
+    SENT bits, the period of the tally included, and the decoder gives the unsent bits the weight 0.
     coeffs, dither_key, block_key, first_frame, steps: as extract_soft_frames (the sender's).  Returns uint8 0/1 [n_info].
     matrix: refused (ValueError): a syndrome bit has no margin."""
     _no_matrix(matrix, "coded")
@@ -618,7 +622,8 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
     f, h, w = stack.shape
     cap = capacity_bits(f, h, w, n_ac)
     if n_coded > cap:
-        raise ValueError(f"{n_coded} coded bits exceed the capacity of {cap}")
+        raise ValueError(f"{n_coded} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
+                         f"{_fec.info_bits(cap, rate)} payload bits")
     lib = native.load()
     _fec.load()
     native.ensure_device(device)

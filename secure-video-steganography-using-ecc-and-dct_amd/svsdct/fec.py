@@ -1,6 +1,8 @@
 """The convolutional code and its soft-decision Viterbi decoder (libsvsfec.so, include/svsfec.h): a constraint-length-7 code
 at rate 1/2 (generators 133, 171) or 1/3 (133, 171, 165), six zero tail bits, decoded on the device by a windowed Viterbi from
-one soft byte (svs_soft_extract) or one int32 (an entry of svs_soft_vote's tally) per coded bit.
+one soft byte (svs_soft_extract) or one int32 (an entry of svs_soft_vote's tally) per coded bit.  `rate` is a code: 2, 3, or
+one of PUNCTURED = (23, 34, 56, 78) - the rate-1/2 code at rate 2/3, 3/4, 5/6 or 7/8, some coded bits not sent (PATTERNS); the
+decoder then takes one value per SENT bit and gives the unsent ones the weight 0.
 
     coded = encode(info_bits, rate)                          host: 0/1 per coded bit
     ... embed `coded`, let the channel do its worst, soft-extract ...
@@ -22,6 +24,14 @@ from .native import SvsNativeError
 LIB_PATH = os.environ.get("SVSFEC_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsfec.so"))
 ABI_VERSION = 1
 RATES = (2, 3)
+RATE_2_3, RATE_3_4, RATE_5_6, RATE_7_8 = PUNCTURED = (23, 34, 56, 78)
+# code -> (out_0 sent, out_1 sent) for the steps of a period (include/svsfec.h, "Punctured codes")
+PATTERNS = {
+    RATE_2_3: ((1, 1), (1, 0)),
+    RATE_3_4: ((1, 1, 0), (1, 0, 1)),
+    RATE_5_6: ((1, 1, 0, 1, 0), (1, 0, 1, 0, 1)),
+    RATE_7_8: ((1, 1, 1, 1, 0, 1, 0), (1, 0, 0, 0, 1, 0, 1)),
+}
 SEGMENT, OVERLAP, TAIL = 512, 64, 6
 MAX_INFO_BITS = 1 << 40
 
@@ -71,9 +81,24 @@ def check(rc: int, what: str) -> None:
 
 
 def _rate(rate) -> int:
-    if isinstance(rate, bool) or rate not in RATES:
-        raise ValueError(f"rate {rate!r}: 2 (rate 1/2) or 3 (rate 1/3)")
+    if isinstance(rate, bool) or rate not in RATES + PUNCTURED:
+        raise ValueError(f"rate {rate!r}: 2 (rate 1/2), 3 (rate 1/3) or a punctured code 23, 34, 56, 78 (rate 2/3 .. 7/8)")
     return int(rate)
+
+
+def _period(rate: int):
+    """(P, K, pre): the period of a punctured code, its sent bits, and pre[i], those of its steps 0 .. i - 1"""
+    out0, out1 = PATTERNS[rate]
+    pre = [0]
+    for a, b in zip(out0, out1):
+        pre.append(pre[-1] + a + b)
+    return len(out0), pre[-1], pre[:-1]
+
+
+def sent_before(t: int, rate: int) -> int:
+    """S(t): the bits a punctured code sends before step t"""
+    p, k, pre = _period(_rate(rate))
+    return t // p * k + pre[t % p]
 
 
 def _n_info(n_info) -> int:
@@ -84,13 +109,19 @@ def _n_info(n_info) -> int:
 
 
 def coded_bits(n_info: int, rate: int = 2) -> int:
-    """rate * (n_info + 6): the coded bits of n_info payload bits"""
-    return _rate(rate) * (_n_info(n_info) + TAIL)
+    """rate * (n_info + 6), under a punctured code S(n_info + 6): the coded bits sent for n_info payload bits"""
+    rate, n = _rate(rate), _n_info(n_info) + TAIL
+    return sent_before(n, rate) if rate in PUNCTURED else rate * n
 
 
 def info_bits(capacity_bits: int, rate: int = 2) -> int:
-    """capacity // rate - 6, at least 0: the largest payload whose coded stream fits capacity_bits"""
-    return max(int(capacity_bits) // _rate(rate) - TAIL, 0)
+    """capacity // rate - 6, under a punctured code (the largest n with S(n) <= capacity) - 6; at least 0: the largest payload
+    whose coded stream fits capacity_bits"""
+    rate, cap = _rate(rate), int(capacity_bits)
+    if rate not in PUNCTURED:
+        return max(cap // rate - TAIL, 0)
+    p, k, pre = _period(rate)
+    return max(cap // k * p + max(i for i in range(p) if pre[i] <= cap % k) - TAIL, 0)
 
 
 def encode(bits, rate: int = 2) -> np.ndarray:
@@ -109,15 +140,15 @@ def encode(bits, rate: int = 2) -> np.ndarray:
 
 
 def decode_soft_device(d_soft: int, n_info: int, rate: int, d_info_packed_out: int, out_capacity_bytes: int, stream: int = 0) -> None:
-    """Enqueue the decoder on `stream` (svs_fec_decode_soft_dev): rate * (n_info + 6) soft bytes at d_soft, coded bit i in
-    byte i, -> ceil(n_info / 8) packed bytes at d_info_packed_out."""
+    """Enqueue the decoder on `stream` (svs_fec_decode_soft_dev): coded_bits(n_info, rate) soft bytes at d_soft, coded bit i
+    (under a punctured code: sent bit i) in byte i, -> ceil(n_info / 8) packed bytes at d_info_packed_out."""
     check(load().svs_fec_decode_soft_dev(d_soft, _n_info(n_info), _rate(rate), d_info_packed_out, int(out_capacity_bytes),
                                          stream or None), "svs_fec_decode_soft_dev")
 
 
 def decode_weights_device(d_weights: int, n_info: int, rate: int, d_info_packed_out: int, out_capacity_bytes: int,
                           stream: int = 0) -> None:
-    """Enqueue the decoder on `stream` (svs_fec_decode_weights_dev): rate * (n_info + 6) int32 weights (4-byte aligned, each
+    """Enqueue the decoder on `stream` (svs_fec_decode_weights_dev): coded_bits(n_info, rate) int32 weights (4-byte aligned, each
     clamped to +-32767; the tally of svs_soft_vote_dev at period = n_coded) -> ceil(n_info / 8) packed bytes."""
     check(load().svs_fec_decode_weights_dev(d_weights, _n_info(n_info), _rate(rate), d_info_packed_out, int(out_capacity_bytes),
                                             stream or None), "svs_fec_decode_weights_dev")
