@@ -6,10 +6,13 @@ Both stego clips go through the requantisation channel (batch.requantise_frames)
 device by the soft-decision Viterbi decoder (batch.extract_coded_frames: the soft bytes stay on the device, the payload comes
 back), the tiled one by the fused soft vote (batch.extract_vote_frames).
 
-    python examples/coded_roundtrip.py [--quality 75] [--rate 2] [--delta 20] [--n-ac 10]
+    python examples/coded_roundtrip.py [--quality 75] [--rate 2] [--delta 20] [--n-ac 10] [--outer]
 
 At the defaults the code delivers all 3 594 bits and three copies leave 51 of 2 400 wrong; --rate 34, the rate-1/2 code punctured
-to rate 3/4, delivers 5 394 (README.md has the tables).
+to rate 3/4, delivers 5 394 (README.md has the tables).  --outer puts the Reed-Solomon outer code (svsdct.rs, RS(255, 223),
+byte-interleaved) in front of the convolutional code: the payload shrinks to rs.payload_bits(capacity, rate), the Viterbi
+decoder's output is decoded on the device, and a status byte a codeword says how many bytes were corrected, or 255: not
+decodable.  --outer --rate 3 --quality 60: the Viterbi decoder leaves 5 wrong bits, the outer code none.
 """
 import argparse
 import os
@@ -19,7 +22,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "secure-video-steganography-using-ecc-and-dct_amd"))
 import numpy as np  # noqa: E402
 
-from svsdct import batch, fec  # noqa: E402
+from svsdct import batch, fec, rs  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--quality", type=int, default=75, help="quality of the requantisation channel, 1..100")
@@ -27,21 +30,33 @@ ap.add_argument("--rate", type=int, default=2, choices=fec.RATES + fec.PUNCTURED
                 help="coded bits a payload bit (2, 3), or a punctured code: 23, 34, 56, 78 for rate 2/3, 3/4, 5/6, 7/8")
 ap.add_argument("--delta", type=float, default=20)
 ap.add_argument("--n-ac", type=int, default=10)
+ap.add_argument("--outer", action="store_true", help="Reed-Solomon (255, 223) outer code in front of the convolutional code")
 a = ap.parse_args()
 
 rng = np.random.default_rng(5)
 clip = rng.integers(64, 192, (3, 96, 160)).astype(np.uint8)
 cap = batch.capacity_bits(*clip.shape, a.n_ac)
-info = rng.integers(0, 2, fec.info_bits(cap, a.rate)).astype(np.uint8)
-
-stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate)
-received = batch.requantise_frames(stego, a.quality)
-decoded = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate)
-soft, _ = batch.extract_soft_frames(received, a.delta, a.n_ac)
-coded_wrong = int(((soft[:used] >> 7) != fec.encode(info, a.rate)).sum())
 name = f"1/{a.rate}" if a.rate in fec.RATES else f"{a.rate // 10}/{a.rate % 10}"
-print(f"rate {name}: {n_info} payload bits in {used} of {cap} capacity bits; after the channel at Q = {a.quality} "
-      f"{coded_wrong} coded bits are wrong, {int((decoded != info).sum())} payload bits after the decoder")
+if a.outer:
+    data = rng.integers(0, 256, rs.payload_bits(cap, a.rate) // 8).astype(np.uint8)
+    info = np.unpackbits(data)
+    stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate, outer=True)
+    received = batch.requantise_frames(stego, a.quality)
+    inner = batch.extract_coded_frames(received, a.delta, a.n_ac, 8 * rs.coded_bytes(data.size), rate=a.rate)
+    decoded, status = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate, outer=True)
+    print(f"rate {name} under RS(255, 223): {n_info} payload bits ({data.size} bytes in {status.size} codewords) in {used} of {cap} "
+          f"capacity bits; after the channel at Q = {a.quality} the Viterbi decoder leaves {int((inner[:n_info] != info).sum())} wrong "
+          f"payload bits, the outer code {int((decoded != info).sum())}; status bytes {status.tolist()}"
+          + (" - not every codeword decoded: the stream is reported as failed" if (status == rs.UNCORRECTABLE).any() else ""))
+else:
+    info = rng.integers(0, 2, fec.info_bits(cap, a.rate)).astype(np.uint8)
+    stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate)
+    received = batch.requantise_frames(stego, a.quality)
+    decoded = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate)
+    soft, _ = batch.extract_soft_frames(received, a.delta, a.n_ac)
+    coded_wrong = int(((soft[:used] >> 7) != fec.encode(info, a.rate)).sum())
+    print(f"rate {name}: {n_info} payload bits in {used} of {cap} capacity bits; after the channel at Q = {a.quality} "
+          f"{coded_wrong} coded bits are wrong, {int((decoded != info).sum())} payload bits after the decoder")
 
 rng = np.random.default_rng(5)                      # the README's experiment: the copy is drawn right behind the cover
 rng.integers(64, 192, clip.shape)

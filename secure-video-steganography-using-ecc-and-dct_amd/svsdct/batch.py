@@ -30,6 +30,7 @@ from . import dither as _dither
 from . import fec as _fec
 from . import native
 from . import matrix as _matrix
+from . import rs as _rs
 from . import steps as _steps
 from . import soft as _soft
 from .hostmem import pinned_empty
@@ -569,7 +570,14 @@ def _coded_copies(copies):
     return None if copies is None else int(copies)
 
 
-def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2, copies: int | None = 1, **embed_kw):
+def _outer_bytes(n_bits: int) -> int:
+    if n_bits % 8:
+        raise ValueError(f"outer=True: the outer code takes whole bytes, {n_bits} payload bits are not")
+    return n_bits // 8
+
+
+def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2, copies: int | None = 1, outer: bool = False,
+                       **embed_kw):
     """Embed a payload under the convolutional code (svsdct/fec.py, include/svsfec.h): fec.encode(info_bits, rate) - rate 2 or 3
     coded bits a payload bit, or a punctured code of fec.PUNCTURED (23, 34, 56, 78: rate 2/3 .. 7/8, the unsent bits are not
     embedded), six tail bits -, then soft.tile when copies > 1 (copies=None: as many as the stack's capacity
@@ -577,6 +585,9 @@ def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2
     rules and read-backs).  The coded stream must fit: fec.info_bits(capacity, rate) is the largest payload of one copy.
     Returns (stego, used, n_info), and the counts behind them where embed_frames returns them; the receiver passes n_info, rate
     and copies to extract_coded_frames.
+    outer=True: the payload, whole bytes (ValueError otherwise), first goes through the Reed-Solomon outer code (svsdct/rs.py,
+    include/svsrs.h): bytes -> rs.encode -> fec.encode -> embed; rs.payload_bits(capacity, rate) is then the largest payload.
+    n_info stays the PAYLOAD's bit count, and the receiver passes outer=True as well.
     matrix: refused (ValueError): a syndrome bit has no margin, so a matrix call has no soft form to decode."""
     _no_matrix(embed_kw.get("matrix"), "coded")
     if "bit_offset" in embed_kw or "n_bits" in embed_kw:
@@ -587,10 +598,11 @@ def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2
         raise ValueError("an empty payload cannot be coded")
     f, h, w = _as_stack(frames).shape
     cap = capacity_bits(f, h, w, n_ac)
-    coded = _fec.encode(info, rate)
+    inner = np.unpackbits(_rs.encode_array(np.packbits(info[: 8 * _outer_bytes(info.size)]))) if outer else info
+    coded = _fec.encode(inner, rate)
     if coded.size > cap:
         raise ValueError(f"{coded.size} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
-                         f"{_fec.info_bits(cap, rate)} payload bits")
+                         f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
     stream = coded if copies == 1 else _soft.tile(coded, cap if copies is None else min(cap, copies * coded.size))
     stego, used, *counts = embed_frames(frames, delta, n_ac, stream, **embed_kw)
     return (stego, used, int(info.size), *counts)
@@ -598,7 +610,7 @@ def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2
 
 def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int = 2, copies: int | None = 1, device: int = 0,
                          mode: str | None = None, block_key=None, first_frame=None, coeffs=None, dither_key=None, steps=None,
-                         matrix=None) -> np.ndarray:
+                         matrix=None, outer: bool = False):
     """Read a payload embedded by embed_coded_frames: the frames go to the device once, the soft bytes never leave it, and only
     ceil(n_info / 8) bytes come back.
       copies = 1:  svs_soft_extract_dev into device memory, then svs_fec_decode_soft_dev on its first fec.coded_bits(n_info, rate)
@@ -609,9 +621,17 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
     rate: the sender's, 2, 3 or a punctured code of fec.PUNCTURED; n_coded = fec.coded_bits(n_info, rate) is then the number of
     SENT bits, the period of the tally included, and the decoder gives the unsent bits the weight 0.
     coeffs, dither_key, block_key, first_frame, steps: as extract_soft_frames (the sender's).  Returns uint8 0/1 [n_info].
+    outer=True (the sender's): n_info is the payload's bit count, whole bytes (ValueError otherwise).  The Viterbi decoder
+    writes the 8 rs.coded_bytes(n_info / 8) bits of the Reed-Solomon stream as packed bytes, svs_rs_decode_dev decodes them in
+    place on the same stream, and nothing leaves the device in between.  Returns (bits uint8 0/1 [n_info], status uint8
+    [rs.codewords(n_info / 8)]: the bytes corrected in each codeword, or 255 - that codeword did not decode and is as the Viterbi
+    decoder left it).
     matrix: refused (ValueError): a syndrome bit has no margin."""
     _no_matrix(matrix, "coded")
     copies = _coded_copies(copies)
+    n_payload = int(n_info)
+    if outer:
+        n_info = 8 * _rs.coded_bytes(_outer_bytes(n_payload))
     n_coded = _fec.coded_bits(n_info, rate)
     n_info = int(n_info)
     if n_info == 0:
@@ -623,9 +643,11 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
     cap = capacity_bits(f, h, w, n_ac)
     if n_coded > cap:
         raise ValueError(f"{n_coded} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
-                         f"{_fec.info_bits(cap, rate)} payload bits")
+                         f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
     lib = native.load()
     _fec.load()
+    if outer:
+        _rs.load()
     native.ensure_device(device)
     planes = Planes.contiguous(f, h, w)
     out_bytes = (n_info + 7) // 8
@@ -641,7 +663,14 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
             native.check(lib.svs_memset(d_tally, 0, 4 * n_coded, None), "svs_memset")
             _soft_call(lib, "vote", call, [d_gray, C.byref(planes)], delta, n_ac, [n_coded, 0, d_tally], 0, (None,), table)
             _fec.decode_weights_device(d_tally, n_info, rate, d_out, out_bytes)
-        return _fec.download_info(d_out, n_info)
+        if not outer:
+            return _fec.download_info(d_out, n_info)
+        k, n_cw = n_payload // 8, _rs.codewords(n_payload // 8)
+        d_status = dev.alloc(n_cw)
+        _rs.decode_device(d_out, k, d_status, n_cw)          # the null stream, as the launches before it
+        status = np.empty(n_cw, np.uint8)
+        native.check(lib.svs_memcpy_d2h(status.ctypes.data, d_status, n_cw, None), "svs_memcpy_d2h")
+        return _fec.download_info(d_out, n_payload), status
 
 
 def requantise_frames(frames: np.ndarray, steps_or_quality, device: int = 0) -> np.ndarray:

@@ -1,0 +1,160 @@
+"""The Reed-Solomon outer code (libsvsrs.so, include/svsrs.h): RS(255, 223) over GF(2^8), shortened, byte-interleaved over all
+its codewords, decoded on the device in place - up to 16 wrong bytes a codeword corrected, and a status byte a codeword that
+says how many were, or 255: not decodable, left as received.  It sits behind the Viterbi decoder of svsdct/fec.py, whose packed
+output bytes are its input.
+
+    stream = encode(data)                                    host: data + 32 parity bytes per 223 data bytes
+    ... fec.encode, embed, the channel, soft extract, Viterbi ...
+    data, status = decode(stream, len(data))                 device
+
+batch.embed_coded_frames / batch.extract_coded_frames take outer=True and keep everything between the soft extract and the
+status bytes on the device.  The library is loaded on first use; SVSRS_LIB overrides its path.  There is no CPU decoder.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import fec as _fec
+from . import native
+from .native import SvsNativeError
+
+LIB_PATH = os.environ.get("SVSRS_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsrs.so"))
+ABI_VERSION = 1
+CODEWORD, DATA, PARITY, T = 255, 223, 32, 16
+UNCORRECTABLE = 255
+MAX_DATA_BYTES = 1 << 37
+
+_p = C.c_void_p
+# name -> (restype, argtypes); every symbol include/svsrs.h declares
+SIGNATURES = {
+    "svs_rs_abi_version": (C.c_int, []),
+    "svs_rs_last_error": (C.c_char_p, []),
+    "svs_rs_codewords": (C.c_uint64, [C.c_uint64]),
+    "svs_rs_coded_bytes": (C.c_uint64, [C.c_uint64]),
+    "svs_rs_data_bytes": (C.c_uint64, [C.c_uint64]),
+    "svs_rs_encode": (C.c_int, [_p, C.c_uint64, _p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "svs_rs_decode_dev": (C.c_int, [_p, C.c_uint64, _p, C.c_uint64, _p, C.c_void_p]),
+}
+
+_lib = None
+
+
+def load() -> C.CDLL:
+    """Load libsvsrs.so once and attach prototypes.  Loading does not touch the GPU."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise SvsNativeError(f"libsvsrs.so not found at {LIB_PATH}; build it with `python __graft_entry__.py` "
+                             f"(or `make -C <package>/csrc`). There is no CPU fallback.")
+    try:
+        lib = C.CDLL(LIB_PATH)
+    except OSError as exc:
+        raise SvsNativeError(f"cannot load {LIB_PATH}: {exc}") from exc
+    for name, (res, args) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise SvsNativeError(f"{LIB_PATH} does not export {name}; rebuild it") from exc
+        fn.restype, fn.argtypes = res, args
+    if lib.svs_rs_abi_version() != ABI_VERSION:
+        raise SvsNativeError(f"ABI version mismatch: {LIB_PATH} reports {lib.svs_rs_abi_version()}, the binding expects "
+                             f"{ABI_VERSION}; rebuild libsvsrs.so")
+    _lib = lib
+    return lib
+
+
+def check(rc: int, what: str) -> None:
+    if rc != native.SVS_OK:
+        raise SvsNativeError(f"{what} failed ({rc}): {load().svs_rs_last_error().decode('utf-8', 'replace')}", rc)
+
+
+def _k(k) -> int:
+    k = int(k)
+    if not 0 <= k <= MAX_DATA_BYTES:
+        raise ValueError(f"k {k} outside 0 .. 2**37")
+    return k
+
+
+def codewords(k: int) -> int:
+    """C = ceil(k / 223): the codewords that k data bytes are interleaved over"""
+    return -(-_k(k) // DATA)
+
+
+def coded_bytes(k: int) -> int:
+    """k + 32 C: the bytes of the stream of k data bytes"""
+    return _k(k) + PARITY * codewords(k)
+
+
+def data_bytes(total_bytes: int) -> int:
+    """the largest k whose stream fits total_bytes; 0 when there is none"""
+    total = int(total_bytes)
+    if total < 0:
+        raise ValueError("total_bytes is negative")
+    return min(total // CODEWORD * DATA + max(total % CODEWORD - PARITY, 0), MAX_DATA_BYTES)
+
+
+def payload_bits(capacity_bits: int, rate: int = 2) -> int:
+    """the payload bits that `capacity_bits` carry under both codes: 8 data_bytes(fec.info_bits(capacity_bits, rate) // 8)"""
+    return 8 * data_bytes(_fec.info_bits(capacity_bits, rate) // 8)
+
+
+def _bytes(data) -> np.ndarray:
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(bytes(data), np.uint8)
+    a = np.asarray(data)
+    if a.dtype != np.uint8:
+        raise TypeError("the outer code takes bytes: a bytes object or a uint8 array")
+    return np.ascontiguousarray(a.reshape(-1))
+
+
+def encode_array(data) -> np.ndarray:
+    """encode on a uint8 array -> uint8 [coded_bytes(k)] (svs_rs_encode; host code, no GPU)"""
+    d = _bytes(data)
+    k = _k(d.size)
+    out = np.empty(coded_bytes(k), np.uint8)
+    if k == 0:
+        return out
+    got = C.c_uint64(0)
+    check(load().svs_rs_encode(d.ctypes.data, k, out.ctypes.data, out.size, C.byref(got)), "svs_rs_encode")
+    assert got.value == out.size
+    return out
+
+
+def encode(data) -> bytes:
+    """k data bytes -> the stream: the data itself, then 32 C interleaved parity bytes"""
+    return encode_array(data).tobytes()
+
+
+def decode_device(d_stream: int, k: int, d_status: int, status_capacity: int, d_counts: int = 0, stream: int = 0) -> None:
+    """Enqueue the decoder on `stream` (svs_rs_decode_dev): coded_bytes(k) bytes at d_stream, any alignment, decoded in place;
+    codewords(k) status bytes to d_status; d_counts: 0 or a 4-byte aligned uint32[2] that the call adds to."""
+    check(load().svs_rs_decode_dev(d_stream, _k(k), d_status, int(status_capacity), d_counts or None, stream or None), "svs_rs_decode_dev")
+
+
+def decode(stream, k: int, device: int = 0):
+    """Decode a stream held on the host: staged through svs_malloc / svs_memcpy_*, decoded by svs_rs_decode_dev.
+    stream: coded_bytes(k) bytes.  Returns (data: bytes [k], status: uint8 [codewords(k)] - bytes corrected, or 255)."""
+    s = _bytes(stream)
+    k = _k(k)
+    if s.size != coded_bytes(k):
+        raise ValueError(f"{s.size} bytes are not the {coded_bytes(k)} of a stream of k = {k}")
+    if k == 0:
+        return b"", np.zeros(0, np.uint8)
+    load()
+    lib = native.load()
+    native.ensure_device(device)
+    n_cw = codewords(k)
+    status = np.empty(n_cw, np.uint8)
+    data = np.empty(k, np.uint8)
+    with _fec._Staged() as dev:
+        d_stream, d_status = dev.alloc(s.size), dev.alloc(n_cw)
+        native.check(lib.svs_memcpy_h2d(d_stream, s.ctypes.data, s.size, None), "svs_memcpy_h2d")
+        decode_device(d_stream, k, d_status, n_cw)
+        native.check(lib.svs_memcpy_d2h(data.ctypes.data, d_stream, k, None), "svs_memcpy_d2h")
+        native.check(lib.svs_memcpy_d2h(status.ctypes.data, d_status, n_cw, None), "svs_memcpy_d2h")
+        native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+    return data.tobytes(), status
