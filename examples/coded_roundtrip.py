@@ -6,13 +6,18 @@ Both stego clips go through the requantisation channel (batch.requantise_frames)
 device by the soft-decision Viterbi decoder (batch.extract_coded_frames: the soft bytes stay on the device, the payload comes
 back), the tiled one by the fused soft vote (batch.extract_vote_frames).
 
-    python examples/coded_roundtrip.py [--quality 75] [--rate 2] [--delta 20] [--n-ac 10] [--outer]
+    python examples/coded_roundtrip.py [--quality 75] [--rate 2] [--delta 20] [--n-ac 10] [--outer [--lose-frame J]]
 
 At the defaults the code delivers all 3 594 bits and three copies leave 51 of 2 400 wrong; --rate 34, the rate-1/2 code punctured
 to rate 3/4, delivers 5 394 (README.md has the tables).  --outer puts the Reed-Solomon outer code (svsdct.rs, RS(255, 223),
 byte-interleaved) in front of the convolutional code: the payload shrinks to rs.payload_bits(capacity, rate), the Viterbi
 decoder's output is decoded on the device, and a status byte a codeword says how many bytes were corrected, or 255: not
 decodable.  --outer --rate 3 --quality 60: the Viterbi decoder leaves 5 wrong bits, the outer code none.
+--outer --lose-frame J overwrites frame J of the received clip with noise - a replaced frame - and passes it to
+extract_coded_frames as lost (lost_frames=[J]): its soft bytes are zeroed and the bytes it maps to are erased for the
+errors-and-erasures decoder (svsdct.rse).  One frame of three is a third of the stream, past any 32 parity bytes; the clip is
+then twelve frames (--frames), of which one is a twelfth: --outer --lose-frame 5 --quality 95 returns the payload where the
+call without lost_frames returns 255 for every codeword.
 """
 import argparse
 import os
@@ -31,10 +36,17 @@ ap.add_argument("--rate", type=int, default=2, choices=fec.RATES + fec.PUNCTURED
 ap.add_argument("--delta", type=float, default=20)
 ap.add_argument("--n-ac", type=int, default=10)
 ap.add_argument("--outer", action="store_true", help="Reed-Solomon (255, 223) outer code in front of the convolutional code")
+ap.add_argument("--lose-frame", type=int, default=None, metavar="J", help="with --outer: overwrite frame J with noise and pass it as lost")
+ap.add_argument("--frames", type=int, default=None, help="frames of the clip: 3, or 12 with --lose-frame")
 a = ap.parse_args()
+if a.lose_frame is not None and not a.outer:
+    ap.error("--lose-frame needs --outer: it is the Reed-Solomon decoder that takes erasures")
+n_frames = a.frames or (3 if a.lose_frame is None else 12)
+if a.lose_frame is not None and not 0 <= a.lose_frame < n_frames:
+    ap.error(f"--lose-frame {a.lose_frame}: the clip has the frames 0 .. {n_frames - 1}")
 
 rng = np.random.default_rng(5)
-clip = rng.integers(64, 192, (3, 96, 160)).astype(np.uint8)
+clip = rng.integers(64, 192, (n_frames, 96, 160)).astype(np.uint8)
 cap = batch.capacity_bits(*clip.shape, a.n_ac)
 name = f"1/{a.rate}" if a.rate in fec.RATES else f"{a.rate // 10}/{a.rate % 10}"
 if a.outer:
@@ -42,8 +54,14 @@ if a.outer:
     info = np.unpackbits(data)
     stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate, outer=True)
     received = batch.requantise_frames(stego, a.quality)
+    if a.lose_frame is not None:
+        received[a.lose_frame] = rng.integers(64, 192, received.shape[1:]).astype(np.uint8)
+        blind, status = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate, outer=True)
+        print(f"frame {a.lose_frame} of {n_frames} replaced by noise; not told so, the outer code leaves {int((blind != info).sum())} wrong "
+              f"payload bits, status bytes {status.tolist()}")
+    lost = [] if a.lose_frame is None else [a.lose_frame]
     inner = batch.extract_coded_frames(received, a.delta, a.n_ac, 8 * rs.coded_bytes(data.size), rate=a.rate)
-    decoded, status = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate, outer=True)
+    decoded, status = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate, outer=True, lost_frames=lost)
     print(f"rate {name} under RS(255, 223): {n_info} payload bits ({data.size} bytes in {status.size} codewords) in {used} of {cap} "
           f"capacity bits; after the channel at Q = {a.quality} the Viterbi decoder leaves {int((inner[:n_info] != info).sum())} wrong "
           f"payload bits, the outer code {int((decoded != info).sum())}; status bytes {status.tolist()}"
@@ -60,7 +78,7 @@ else:
 
 rng = np.random.default_rng(5)                      # the README's experiment: the copy is drawn right behind the cover
 rng.integers(64, 192, clip.shape)
-copy = rng.integers(0, 2, cap // 3).astype(np.uint8)
+copy = rng.integers(0, 2, cap // 3).astype(np.uint8)             # three copies, whatever the clip's length
 stego, used, period = batch.embed_repeated_frames(clip, a.delta, a.n_ac, copy)
 voted, _ = batch.extract_vote_frames(batch.requantise_frames(stego, a.quality), a.delta, a.n_ac, period)
 print(f"repetition: {period} payload bits in three copies; {int((voted != copy).sum())} payload bits are wrong after the soft vote")

@@ -61,8 +61,8 @@
  *   svs_rs_encode: the same 1 (it still reports *n_out = 0), 2 and 3 (data or output NULL), then capacity_bytes below
  *   k + 32 C is SVS_ERR_CAPACITY.  n_out may be NULL.
  *
- * Not here: a host decoder (the product has no CPU path; the model lives in the tests), a device encoder, erasure decoding,
- * and any interleaving depth other than "all codewords".
+ * Not here: a host decoder (the product has no CPU path; the model lives in the tests), a device encoder, and any interleaving
+ * depth other than "all codewords".  Errors-and-erasures decoding of this code is libsvsrse.so, include/svsrse.h.
  */
 #ifndef SVSRS_H
 #define SVSRS_H

@@ -158,4 +158,38 @@ SVS_RS_HD uint64_t stream_offset(uint64_t k, uint64_t C, uint64_t c, uint32_t k_
     return i < k_c ? (uint64_t)i * C + c : k + (uint64_t)(i - k_c) * C + c;
 }
 
+// ---- the steps that errors-and-erasures decoding adds (include/svsrse.h; csrc/svs_rse.hip, tests/hostemu/rse_emu.cpp).  f erased
+// bytes of a codeword, f <= 32, at the positions p_0 .. p_(f - 1); X_t = alpha^(p_t) -----------------------------------------------
+// the erasure locator Gamma(x) = prod (1 - X_t x), lane i holds Gamma_i.  Start: Gamma = 1.  One step per erased position:
+// Gamma <- Gamma (1 - X x); `below` is Gamma_(i - 1) before the step, 0 on lane 0
+SVS_RS_HD uint32_t gamma_step(uint32_t gamma, uint32_t below, int p, const Gf &gf) { return gamma ^ gf.mul(gf.exp2[p], below); }
+
+// Berlekamp-Massey then starts from Lambda = Gamma, x^m B = x Gamma, L = f, b = 1 and runs the steps n = f .. 31 with bm_term and
+// bm_update as they are.  What changes is when the locator gets longer, its new length, and when the codeword is given up:
+SVS_RS_HD bool bm_longer(uint32_t d, int L, int n, int f) { return d != 0 && 2 * L <= n + f; }
+SVS_RS_HD int bm_length(int L, int n, int f) { return n + 1 - L + f; }
+// L - f errors and f erasures are past the code's reach
+SVS_RS_HD bool bm_beyond(int L, int f) { return 2 * L - f > kParity; }
+// Omega = S Lambda mod x^32 has 32 coefficients: omega_coefficient on the lanes j = 0 .. 31 with degree = L <= 32.
+
+// the map of a codeword's erased positions, 256 bits in eight words
+SVS_RS_HD uint32_t erased_word(int p) { return (uint32_t)p >> 5; }
+SVS_RS_HD uint32_t erased_bit(int p) { return 1u << (p & 31); }
+SVS_RS_HD bool is_erased(const uint32_t *map, int p) { return (map[erased_word(p)] & erased_bit(p)) != 0; }
+
+// root_value with erasures, degree = L <= 32.  Returns 0: no root at a position that is not erased; 1 .. 255: the value to xor
+// into the byte; kRightErasure: a root at an erased position whose value is 0, the byte was right; kBadRoot: an erased position
+// that is no root, a zero derivative at a root, or a zero value at a root that is not erased.
+constexpr uint32_t kRightErasure = 257;
+SVS_RS_HD uint32_t errata_value(int p, int degree, const uint8_t *lambda, const uint8_t *omega, bool erased, const Gf &gf) {
+    const int zlog = p ? 255 - p : 0;
+    if (evaluate(lambda, 0, degree, 1, zlog, gf) != 0) return erased ? kBadRoot : 0u;
+    const int z2 = 2 * zlog >= 255 ? 2 * zlog - 255 : 2 * zlog;
+    const uint32_t slope = evaluate(lambda, 1, degree, 2, z2, gf);
+    if (slope == 0) return kBadRoot;
+    const uint32_t top = evaluate(omega, 0, degree - 1, 1, zlog, gf);
+    if (top == 0) return erased ? kRightErasure : kBadRoot;
+    return gf.mul(gf.exp2[p], gf.div(top, slope));
+}
+
 }  // namespace svsrs

@@ -31,6 +31,7 @@ from . import fec as _fec
 from . import native
 from . import matrix as _matrix
 from . import rs as _rs
+from . import rse as _rse
 from . import steps as _steps
 from . import soft as _soft
 from .hostmem import pinned_empty
@@ -576,6 +577,33 @@ def _outer_bytes(n_bits: int) -> int:
     return n_bits // 8
 
 
+def _lost_frames_arg(lost_frames, erase_margin, outer, copies):
+    """(sorted frame indices, margin) of extract_coded_frames' lost_frames; the upper bound is checked where the stack is known"""
+    lost = []
+    for i in lost_frames:
+        if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)):
+            raise ValueError(f"lost_frames: {i!r} is no frame index")
+        if i < 0:
+            raise ValueError(f"lost_frames: frame {i} is outside the stack")
+        lost.append(int(i))
+    if isinstance(erase_margin, (bool, np.bool_)) or not isinstance(erase_margin, (int, np.integer)) or erase_margin < 0:
+        raise ValueError("erase_margin is a number of bytes, 0 or more")
+    if lost and not outer:
+        raise ValueError("lost_frames needs outer=True: it is the Reed-Solomon decoder that takes erasures")
+    if lost and copies != 1:
+        raise ValueError("lost_frames needs copies = 1: a tally of copies has no stream range per frame")
+    return sorted(set(lost)), int(erase_margin)
+
+
+def lost_span(lo: int, hi: int, rate: int, k: int, erase_margin: int = 1):
+    """[lo, hi) in sent bits of the coded stream -> the [lo, hi) byte range of the Reed-Solomon stream of k data bytes that they
+    bear on: the trellis steps (fec.steps_of_sent_bits; payload bit t of the inner code is step t, and its payload IS the
+    Reed-Solomon stream) divided by 8, clipped to the stream - the six tail steps fall away - and widened by erase_margin bytes"""
+    total = _rs.coded_bytes(k)
+    t0, t1 = _fec.steps_of_sent_bits(lo, hi, rate)
+    return max(min(t0 // 8, total) - erase_margin, 0), min(min(-(-t1 // 8), total) + erase_margin, total)
+
+
 def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2, copies: int | None = 1, outer: bool = False,
                        **embed_kw):
     """Embed a payload under the convolutional code (svsdct/fec.py, include/svsfec.h): fec.encode(info_bits, rate) - rate 2 or 3
@@ -610,7 +638,7 @@ def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2
 
 def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int = 2, copies: int | None = 1, device: int = 0,
                          mode: str | None = None, block_key=None, first_frame=None, coeffs=None, dither_key=None, steps=None,
-                         matrix=None, outer: bool = False):
+                         matrix=None, outer: bool = False, lost_frames=(), erase_margin: int = 1):
     """Read a payload embedded by embed_coded_frames: the frames go to the device once, the soft bytes never leave it, and only
     ceil(n_info / 8) bytes come back.
       copies = 1:  svs_soft_extract_dev into device memory, then svs_fec_decode_soft_dev on its first fec.coded_bits(n_info, rate)
@@ -626,9 +654,19 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
     place on the same stream, and nothing leaves the device in between.  Returns (bits uint8 0/1 [n_info], status uint8
     [rs.codewords(n_info / 8)]: the bytes corrected in each codeword, or 255 - that codeword did not decode and is as the Viterbi
     decoder left it).
+    lost_frames: indices within the stack of frames that the receiver gave up on - a replaced frame, an overlaid logo
+    (extract_histogram_frames tells such frames apart).  Needs outer=True and copies = 1 (ValueError otherwise, as for an index
+    that is no integer or out of range, before any device work).  Frame i owns the capacity bits [i cap / f, (i + 1) cap / f) of
+    the stream, under a block key, a selection or a dither as well.  For each lost frame its soft bytes are set to 0x00 behind
+    the soft extract (svs_memset on the same stream; 0x00 is the weight -1, the smallest the format has, where noise would vote
+    with full margins), its sent bits are mapped to the bytes of the Reed-Solomon stream they bear on
+    (fec.steps_of_sent_bits, divided by 8), the span is widened by erase_margin bytes on each side, and the codewords are decoded
+    by svs_rse_decode_dev (svsdct/rse.py, include/svsrse.h) with those bytes erased: 2 e + f <= 32 a codeword, where blind decoding
+    stops at 16 wrong bytes.  The status is then the bytes changed, 0 .. 32, or 255.  Without lost_frames nothing changes.
     matrix: refused (ValueError): a syndrome bit has no margin."""
     _no_matrix(matrix, "coded")
     copies = _coded_copies(copies)
+    lost, erase_margin = _lost_frames_arg(lost_frames, erase_margin, outer, copies)
     n_payload = int(n_info)
     if outer:
         n_info = 8 * _rs.coded_bytes(_outer_bytes(n_payload))
@@ -644,10 +682,13 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
     if n_coded > cap:
         raise ValueError(f"{n_coded} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
                          f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
+    if lost and not lost[-1] < f:
+        raise ValueError(f"lost_frames: frame {lost[-1]} is outside the stack's 0 .. {f - 1}")
+    lost_bits = [(i * (cap // f), min((i + 1) * (cap // f), n_coded)) for i in lost if i * (cap // f) < n_coded]
     lib = native.load()
     _fec.load()
     if outer:
-        _rs.load()
+        (_rse if lost else _rs).load()
     native.ensure_device(device)
     planes = Planes.contiguous(f, h, w)
     out_bytes = (n_info + 7) // 8
@@ -657,6 +698,8 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
         if copies == 1:
             d_soft = dev.alloc(cap)
             _soft_call(lib, "extract", call, [d_gray, C.byref(planes)], delta, n_ac, [d_soft, cap], mode_flags(mode), (None,), table)
+            for lo, hi in lost_bits:
+                native.check(lib.svs_memset(d_soft + lo, 0, hi - lo, None), "svs_memset")
             _fec.decode_soft_device(d_soft, n_info, rate, d_out, out_bytes)
         else:
             d_tally = dev.alloc(4 * n_coded)
@@ -667,7 +710,13 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
             return _fec.download_info(d_out, n_info)
         k, n_cw = n_payload // 8, _rs.codewords(n_payload // 8)
         d_status = dev.alloc(n_cw)
-        _rs.decode_device(d_out, k, d_status, n_cw)          # the null stream, as the launches before it
+        if lost:
+            erased = _rse.mask(k, [lost_span(lo, hi, rate, k, erase_margin) for lo, hi in lost_bits])
+            d_erased = dev.alloc(erased.size)
+            native.check(lib.svs_memcpy_h2d(d_erased, erased.ctypes.data, erased.size, None), "svs_memcpy_h2d")
+            _rse.decode_device(d_out, k, d_erased, d_status, n_cw)
+        else:
+            _rs.decode_device(d_out, k, d_status, n_cw)      # the null stream, as the launches before it
         status = np.empty(n_cw, np.uint8)
         native.check(lib.svs_memcpy_d2h(status.ctypes.data, d_status, n_cw, None), "svs_memcpy_d2h")
         return _fec.download_info(d_out, n_payload), status

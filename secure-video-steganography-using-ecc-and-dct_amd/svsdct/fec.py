@@ -124,6 +124,25 @@ def info_bits(capacity_bits: int, rate: int = 2) -> int:
     return max(cap // k * p + max(i for i in range(p) if pre[i] <= cap % k) - TAIL, 0)
 
 
+def _step_holding(x: int, rate: int) -> int:
+    """the largest t with S(t) <= x: the step that sends bit x"""
+    if rate not in PUNCTURED:
+        return x // rate
+    p, k, pre = _period(rate)
+    return x // k * p + max(i for i in range(p) if pre[i] <= x % k)
+
+
+def steps_of_sent_bits(lo: int, hi: int, rate: int = 2):
+    """(t0, t1): the trellis steps t0 .. t1 - 1 whose sent bits touch the range [lo, hi) of the coded stream, lo < hi.  Rates 2 and
+    3: t0 = lo // rate, t1 = ceil(hi / rate); a punctured code: S(t) of include/svsfec.h inverted.  Payload bit t is the input
+    of step t, so these are also the payload bits that a damaged stretch of the coded stream bears on most directly (the six
+    tail steps lie behind the payload)."""
+    rate, lo, hi = _rate(rate), int(lo), int(hi)
+    if not 0 <= lo < hi:
+        raise ValueError(f"[{lo}, {hi}) is no range of sent bits")
+    return _step_holding(lo, rate), _step_holding(hi - 1, rate) + 1
+
+
 def encode(bits, rate: int = 2) -> np.ndarray:
     """Payload bits (0/1 per entry) -> the coded stream, uint8 0/1 per coded bit (svs_fec_encode; host code, no GPU)."""
     rate = _rate(rate)
