@@ -1,8 +1,9 @@
-// svs_rs.hpp - the per-step arithmetic of the Reed-Solomon outer code (include/svsrs.h, "THE FORMAT"): the field, the
-// generator, the encoder's LFSR, and a bounded-distance decoder's steps - syndromes, Berlekamp-Massey, root search, Forney - each
-// as what ONE LANE does, in a form that compiles for the device (csrc/svs_rs.hip: a wave runs the lanes side by side) and for the
-// host (svs_rs_encode; tests/hostemu/rs_emu.cpp runs the lanes one after the other).  What crosses lanes - the xor of the 64
-// discrepancy terms, the shift of B by one coefficient, the count of roots - is the caller's.  Integers only.
+// svs_rs.hpp - the per-step arithmetic of the Reed-Solomon outer code (include/svsrs.h and include/svsrse.h, "THE FORMAT"): the
+// field, the generator, the encoder's LFSR, and the steps of an errors-and-erasures decoder - syndromes, the erasure locator,
+// Berlekamp-Massey, root search, Forney - each as what ONE LANE does, in a form that compiles for the device
+// (csrc/svs_rs_decode.hpp: a wave runs the lanes side by side) and for the host (svs_rs_encode; tests/hostemu/rs_emu.cpp runs the
+// lanes one after the other).  What crosses lanes - the xor of the 64 discrepancy terms, the shift of B by one coefficient, the
+// count of roots - is the caller's.  f is the number of a codeword's erased bytes; f = 0 is errors-only decoding.  Integers only.
 #pragma once
 
 #include <stdint.h>
@@ -91,7 +92,9 @@ SVS_RS_HD void lfsr_step(uint32_t *w, uint32_t byte, const uint32_t *table) {
     w[7] = (w[7] >> 8) ^ row[7];
 }
 
-// ---- the decoder's steps.  r: the 32 bytes of r(x) = c(x) mod g(x), r[j] the coefficient of x^(31 - j) ---------------------------
+// ---- the decoder's steps.  r: the 32 bytes of r(x) = c(x) mod g(x), r[j] the coefficient of x^(31 - j).  f <= 32 bytes of the
+// codeword are erased, at the positions p_0 .. p_(f - 1) (position p: the byte that multiplies x^p), X_t = alpha^(p_t); f = 0: errors
+// only, and every step below is that of a bounded-distance decoder for up to kT errors ----------------------------------------------
 // lane j = 0 .. 31: S_j = r(alpha^j)
 SVS_RS_HD uint32_t syndrome(int j, const uint8_t *r, const Gf &gf) {
     uint32_t s = 0;
@@ -105,12 +108,21 @@ SVS_RS_HD uint32_t syndrome(int j, const uint8_t *r, const Gf &gf) {
     return s;
 }
 
-// Berlekamp-Massey, lane i holds Lambda_i and coefficient i of x^m B(x).  Step n = 0 .. 31:
+// the erasure locator Gamma(x) = prod (1 - X_t x), lane i holds Gamma_i.  Start: Gamma = 1.  One step per erased position:
+// Gamma <- Gamma (1 - X x); `below` is Gamma_(i - 1) before the step, 0 on lane 0
+SVS_RS_HD uint32_t gamma_step(uint32_t gamma, uint32_t below, int p, const Gf &gf) { return gamma ^ gf.mul(gf.exp2[p], below); }
+
+// Berlekamp-Massey, lane i holds Lambda_i and coefficient i of x^m B(x).  Step n = f .. 31:
 //   d = the xor over the lanes of bm_term;  d = 0: nothing but the shift of B.
-//   d != 0: Lambda <- Lambda - (d / b) x^m B;  when 2 L <= n also B <- the Lambda before, b <- d, L <- n + 1 - L.
+//   d != 0: Lambda <- Lambda - (d / b) x^m B;  when bm_longer (2 L <= n + f) also B <- the Lambda before, b <- d,
+//   L <- bm_length (n + 1 - L + f), and the codeword is given up when bm_beyond: L - f errors and f erasures, 2 (L - f) + f > 32.
 //   Then B is shifted up by one coefficient: lane i takes `pass` of lane i - 1, lane 0 takes 0.
-// Start: Lambda = 1, x^m B = x, L = 0, b = 1.
+// Start: Lambda = Gamma, x^m B = x Gamma, L = f, b = 1.  f = 0: Lambda = 1, x^m B = x, L = 0; longer when 2 L <= n, L <- n + 1 - L,
+// given up when L > kT.
 SVS_RS_HD uint32_t bm_term(int i, int n, uint32_t lambda, const uint8_t *syn, const Gf &gf) { return i <= n ? gf.mul(lambda, syn[n - i]) : 0u; }
+SVS_RS_HD bool bm_longer(uint32_t d, int L, int n, int f) { return d != 0 && 2 * L <= n + f; }
+SVS_RS_HD int bm_length(int L, int n, int f) { return n + 1 - L + f; }
+SVS_RS_HD bool bm_beyond(int L, int f) { return 2 * L - f > kParity; }
 struct BmLane {
     uint32_t lambda, pass;
 };
@@ -119,7 +131,7 @@ SVS_RS_HD BmLane bm_update(uint32_t lambda, uint32_t shifted_b, uint32_t d, uint
     return BmLane{lambda ^ gf.mul(gf.div(d, b), shifted_b), longer ? lambda : shifted_b};
 }
 
-// lane j = 0 .. 15: Omega_j = sum over i <= j of Lambda_i S_(j - i): Omega = S Lambda mod x^32, and its degree is below L
+// lane j = 0 .. 31: Omega_j = sum over i <= j of Lambda_i S_(j - i): Omega = S Lambda mod x^32, with degree = L <= 32
 SVS_RS_HD uint32_t omega_coefficient(int j, int degree, const uint8_t *lambda, const uint8_t *syn, const Gf &gf) {
     uint32_t o = 0;
     for (int i = 0; i <= j && i <= degree; ++i) o ^= gf.mul(lambda[i], syn[j - i]);
@@ -138,48 +150,18 @@ SVS_RS_HD uint32_t evaluate(const uint8_t *coef, int from, int to, int stride, i
     return acc;
 }
 
-// the lane of position p (the byte that multiplies x^p, X = alpha^p): is X^-1 a root of Lambda, and if so the error value
-//   e = X Omega(X^-1) / Lambda'(X^-1),   Lambda'(z) = sum over odd i of Lambda_i z^(i - 1).
-// Returns 0: no root; 1 .. 255: the value to xor into the byte; kBadRoot: a root whose derivative or value is zero.
-constexpr uint32_t kBadRoot = 256;
-SVS_RS_HD uint32_t root_value(int p, int degree, const uint8_t *lambda, const uint8_t *omega, const Gf &gf) {
-    const int zlog = p ? 255 - p : 0;
-    if (evaluate(lambda, 0, degree, 1, zlog, gf) != 0) return 0;
-    const int z2 = 2 * zlog >= 255 ? 2 * zlog - 255 : 2 * zlog;
-    const uint32_t slope = evaluate(lambda, 1, degree, 2, z2, gf);
-    const uint32_t top = evaluate(omega, 0, degree - 1, 1, zlog, gf);
-    if (slope == 0 || top == 0) return kBadRoot;
-    return gf.mul(gf.exp2[p], gf.div(top, slope));
-}
-
-// where byte i of codeword c (i < k_c: data byte d_i, otherwise parity byte p_(i - k_c)) lies in a stream of k data bytes
-// interleaved over C codewords
-SVS_RS_HD uint64_t stream_offset(uint64_t k, uint64_t C, uint64_t c, uint32_t k_c, uint32_t i) {
-    return i < k_c ? (uint64_t)i * C + c : k + (uint64_t)(i - k_c) * C + c;
-}
-
-// ---- the steps that errors-and-erasures decoding adds (include/svsrse.h; csrc/svs_rse.hip, tests/hostemu/rse_emu.cpp).  f erased
-// bytes of a codeword, f <= 32, at the positions p_0 .. p_(f - 1); X_t = alpha^(p_t) -----------------------------------------------
-// the erasure locator Gamma(x) = prod (1 - X_t x), lane i holds Gamma_i.  Start: Gamma = 1.  One step per erased position:
-// Gamma <- Gamma (1 - X x); `below` is Gamma_(i - 1) before the step, 0 on lane 0
-SVS_RS_HD uint32_t gamma_step(uint32_t gamma, uint32_t below, int p, const Gf &gf) { return gamma ^ gf.mul(gf.exp2[p], below); }
-
-// Berlekamp-Massey then starts from Lambda = Gamma, x^m B = x Gamma, L = f, b = 1 and runs the steps n = f .. 31 with bm_term and
-// bm_update as they are.  What changes is when the locator gets longer, its new length, and when the codeword is given up:
-SVS_RS_HD bool bm_longer(uint32_t d, int L, int n, int f) { return d != 0 && 2 * L <= n + f; }
-SVS_RS_HD int bm_length(int L, int n, int f) { return n + 1 - L + f; }
-// L - f errors and f erasures are past the code's reach
-SVS_RS_HD bool bm_beyond(int L, int f) { return 2 * L - f > kParity; }
-// Omega = S Lambda mod x^32 has 32 coefficients: omega_coefficient on the lanes j = 0 .. 31 with degree = L <= 32.
-
 // the map of a codeword's erased positions, 256 bits in eight words
 SVS_RS_HD uint32_t erased_word(int p) { return (uint32_t)p >> 5; }
 SVS_RS_HD uint32_t erased_bit(int p) { return 1u << (p & 31); }
 SVS_RS_HD bool is_erased(const uint32_t *map, int p) { return (map[erased_word(p)] & erased_bit(p)) != 0; }
 
-// root_value with erasures, degree = L <= 32.  Returns 0: no root at a position that is not erased; 1 .. 255: the value to xor
-// into the byte; kRightErasure: a root at an erased position whose value is 0, the byte was right; kBadRoot: an erased position
-// that is no root, a zero derivative at a root, or a zero value at a root that is not erased.
+// the lane of position p (X = alpha^p), degree = L <= 32: is X^-1 a root of Lambda, and if so the value
+//   e = X Omega(X^-1) / Lambda'(X^-1),   Lambda'(z) = sum over odd i of Lambda_i z^(i - 1).
+// Returns 0: no root at a position that is not erased; 1 .. 255: the value to xor into the byte; kRightErasure: a root at an
+// erased position whose value is 0, the byte was right; kBadRoot: an erased position that is no root, a zero derivative at a
+// root, or a zero value at a root that is not erased.  With no erased position the number of non-zero returns of a codeword that
+// decodes is L.
+constexpr uint32_t kBadRoot = 256;
 constexpr uint32_t kRightErasure = 257;
 SVS_RS_HD uint32_t errata_value(int p, int degree, const uint8_t *lambda, const uint8_t *omega, bool erased, const Gf &gf) {
     const int zlog = p ? 255 - p : 0;
@@ -190,6 +172,16 @@ SVS_RS_HD uint32_t errata_value(int p, int degree, const uint8_t *lambda, const 
     const uint32_t top = evaluate(omega, 0, degree - 1, 1, zlog, gf);
     if (top == 0) return erased ? kRightErasure : kBadRoot;
     return gf.mul(gf.exp2[p], gf.div(top, slope));
+}
+// f = 0 under the name host emulations written before the mask call it by: the same steps, no second set of them
+SVS_RS_HD uint32_t root_value(int p, int degree, const uint8_t *lambda, const uint8_t *omega, const Gf &gf) {
+    return errata_value(p, degree, lambda, omega, false, gf);
+}
+
+// where byte i of codeword c (i < k_c: data byte d_i, otherwise parity byte p_(i - k_c)) lies in a stream of k data bytes
+// interleaved over C codewords
+SVS_RS_HD uint64_t stream_offset(uint64_t k, uint64_t C, uint64_t c, uint32_t k_c, uint32_t i) {
+    return i < k_c ? (uint64_t)i * C + c : k + (uint64_t)(i - k_c) * C + c;
 }
 
 }  // namespace svsrs

@@ -53,26 +53,9 @@ _lib = None
 def load() -> C.CDLL:
     """Load libsvsfec.so once and attach prototypes.  Loading does not touch the GPU."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise SvsNativeError(f"libsvsfec.so not found at {LIB_PATH}; build it with `python __graft_entry__.py` "
-                             f"(or `make -C <package>/csrc`). There is no CPU fallback.")
-    try:
-        lib = C.CDLL(LIB_PATH)
-    except OSError as exc:
-        raise SvsNativeError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise SvsNativeError(f"{LIB_PATH} does not export {name}; rebuild it") from exc
-        fn.restype, fn.argtypes = res, args
-    if lib.svs_fec_abi_version() != ABI_VERSION:
-        raise SvsNativeError(f"ABI version mismatch: {LIB_PATH} reports {lib.svs_fec_abi_version()}, the binding expects "
-                             f"{ABI_VERSION}; rebuild libsvsfec.so")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = native.load_library(LIB_PATH, SIGNATURES, "svs_fec_abi_version", ABI_VERSION)
+    return _lib
 
 
 def check(rc: int, what: str) -> None:

@@ -245,6 +245,29 @@ def load() -> C.CDLL:
     return lib
 
 
+def load_library(path: str, signatures: dict, abi_symbol: str, version: int) -> C.CDLL:
+    """One of the smaller libraries (svsdct/fec.py, rs.py, rse.py), with the prototype of every name in `signatures` attached and
+    its ABI version checked.  Loading does not touch the GPU."""
+    so = "lib" + abi_symbol[: -len("_abi_version")].replace("_", "") + ".so"          # svs_rs_abi_version: libsvsrs.so
+    if not os.path.exists(path):
+        raise SvsNativeError(f"{so} not found at {path}; build it with `python __graft_entry__.py` "
+                             f"(or `make -C <package>/csrc`). There is no CPU fallback.")
+    try:
+        lib = C.CDLL(path)
+    except OSError as exc:
+        raise SvsNativeError(f"cannot load {path}: {exc}") from exc
+    for name, (res, args) in signatures.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as exc:
+            raise SvsNativeError(f"{path} does not export {name}; rebuild it") from exc
+        fn.restype, fn.argtypes = res, args
+    got = getattr(lib, abi_symbol)()
+    if got != version:
+        raise SvsNativeError(f"ABI version mismatch: {path} reports {got}, the binding expects {version}; rebuild {so}")
+    return lib
+
+
 def check(rc: int, what: str) -> None:
     if rc != SVS_OK:
         msg = load().svs_last_error().decode("utf-8", "replace")

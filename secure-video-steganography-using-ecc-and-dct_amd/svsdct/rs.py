@@ -45,26 +45,9 @@ _lib = None
 def load() -> C.CDLL:
     """Load libsvsrs.so once and attach prototypes.  Loading does not touch the GPU."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise SvsNativeError(f"libsvsrs.so not found at {LIB_PATH}; build it with `python __graft_entry__.py` "
-                             f"(or `make -C <package>/csrc`). There is no CPU fallback.")
-    try:
-        lib = C.CDLL(LIB_PATH)
-    except OSError as exc:
-        raise SvsNativeError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise SvsNativeError(f"{LIB_PATH} does not export {name}; rebuild it") from exc
-        fn.restype, fn.argtypes = res, args
-    if lib.svs_rs_abi_version() != ABI_VERSION:
-        raise SvsNativeError(f"ABI version mismatch: {LIB_PATH} reports {lib.svs_rs_abi_version()}, the binding expects "
-                             f"{ABI_VERSION}; rebuild libsvsrs.so")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = native.load_library(LIB_PATH, SIGNATURES, "svs_rs_abi_version", ABI_VERSION)
+    return _lib
 
 
 def check(rc: int, what: str) -> None:
@@ -135,16 +118,19 @@ def decode_device(d_stream: int, k: int, d_status: int, status_capacity: int, d_
     check(load().svs_rs_decode_dev(d_stream, _k(k), d_status, int(status_capacity), d_counts or None, stream or None), "svs_rs_decode_dev")
 
 
-def decode(stream, k: int, device: int = 0):
-    """Decode a stream held on the host: staged through svs_malloc / svs_memcpy_*, decoded by svs_rs_decode_dev.
-    stream: coded_bytes(k) bytes.  Returns (data: bytes [k], status: uint8 [codewords(k)] - bytes corrected, or 255)."""
+def _decode_staged(stream, k: int, erased, device: int, load_lib, launch):
+    """The staged call that decode and rse.decode share: the stream (and the mask, if there is one) up through svs_malloc /
+    svs_memcpy_*, launch(d_stream, k, d_erased or 0, d_status, codewords(k)), the data bytes and the status bytes down."""
     s = _bytes(stream)
     k = _k(k)
     if s.size != coded_bytes(k):
         raise ValueError(f"{s.size} bytes are not the {coded_bytes(k)} of a stream of k = {k}")
+    m = None if erased is None else _bytes(erased)
+    if m is not None and m.size != s.size:
+        raise ValueError(f"{m.size} mask bytes are not the {s.size} of the stream")
     if k == 0:
         return b"", np.zeros(0, np.uint8)
-    load()
+    load_lib()
     lib = native.load()
     native.ensure_device(device)
     n_cw = codewords(k)
@@ -153,8 +139,19 @@ def decode(stream, k: int, device: int = 0):
     with _fec._Staged() as dev:
         d_stream, d_status = dev.alloc(s.size), dev.alloc(n_cw)
         native.check(lib.svs_memcpy_h2d(d_stream, s.ctypes.data, s.size, None), "svs_memcpy_h2d")
-        decode_device(d_stream, k, d_status, n_cw)
+        d_erased = 0
+        if m is not None:
+            d_erased = dev.alloc(m.size)
+            native.check(lib.svs_memcpy_h2d(d_erased, m.ctypes.data, m.size, None), "svs_memcpy_h2d")
+        launch(d_stream, k, d_erased, d_status, n_cw)
         native.check(lib.svs_memcpy_d2h(data.ctypes.data, d_stream, k, None), "svs_memcpy_d2h")
         native.check(lib.svs_memcpy_d2h(status.ctypes.data, d_status, n_cw, None), "svs_memcpy_d2h")
         native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
     return data.tobytes(), status
+
+
+def decode(stream, k: int, device: int = 0):
+    """Decode a stream held on the host: staged through svs_malloc / svs_memcpy_*, decoded by svs_rs_decode_dev.
+    stream: coded_bytes(k) bytes.  Returns (data: bytes [k], status: uint8 [codewords(k)] - bytes corrected, or 255)."""
+    return _decode_staged(stream, k, None, device, load,
+                          lambda d_stream, k, d_erased, d_status, n_cw: decode_device(d_stream, k, d_status, n_cw))

@@ -18,10 +18,9 @@ import os
 
 import numpy as np
 
-from . import fec as _fec
 from . import native
 from .native import SvsNativeError
-from .rs import MAX_DATA_BYTES, PARITY, UNCORRECTABLE, _bytes, _k, codewords, coded_bytes  # noqa: F401
+from .rs import MAX_DATA_BYTES, PARITY, UNCORRECTABLE, _bytes, _decode_staged, _k, codewords, coded_bytes  # noqa: F401
 
 LIB_PATH = os.environ.get("SVSRSE_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsrse.so"))
 ABI_VERSION = 1
@@ -41,26 +40,9 @@ _lib = None
 def load() -> C.CDLL:
     """Load libsvsrse.so once and attach prototypes.  Loading does not touch the GPU."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise SvsNativeError(f"libsvsrse.so not found at {LIB_PATH}; build it with `python __graft_entry__.py` "
-                             f"(or `make -C <package>/csrc`). There is no CPU fallback.")
-    try:
-        lib = C.CDLL(LIB_PATH)
-    except OSError as exc:
-        raise SvsNativeError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise SvsNativeError(f"{LIB_PATH} does not export {name}; rebuild it") from exc
-        fn.restype, fn.argtypes = res, args
-    if lib.svs_rse_abi_version() != ABI_VERSION:
-        raise SvsNativeError(f"ABI version mismatch: {LIB_PATH} reports {lib.svs_rse_abi_version()}, the binding expects "
-                             f"{ABI_VERSION}; rebuild libsvsrse.so")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = native.load_library(LIB_PATH, SIGNATURES, "svs_rse_abi_version", ABI_VERSION)
+    return _lib
 
 
 def check(rc: int, what: str) -> None:
@@ -92,30 +74,4 @@ def decode(stream, k: int, erased=None, device: int = 0):
     """Decode a stream held on the host: staged through svs_malloc / svs_memcpy_*, decoded by svs_rse_decode_dev.
     stream: coded_bytes(k) bytes; erased: None or as many mask bytes (non-zero: that byte is erased).
     Returns (data: bytes [k], status: uint8 [codewords(k)] - bytes changed, or 255)."""
-    s = _bytes(stream)
-    k = _k(k)
-    if s.size != coded_bytes(k):
-        raise ValueError(f"{s.size} bytes are not the {coded_bytes(k)} of a stream of k = {k}")
-    m = None if erased is None else _bytes(erased)
-    if m is not None and m.size != s.size:
-        raise ValueError(f"{m.size} mask bytes are not the {s.size} of the stream")
-    if k == 0:
-        return b"", np.zeros(0, np.uint8)
-    load()
-    lib = native.load()
-    native.ensure_device(device)
-    n_cw = codewords(k)
-    status = np.empty(n_cw, np.uint8)
-    data = np.empty(k, np.uint8)
-    with _fec._Staged() as dev:
-        d_stream, d_status = dev.alloc(s.size), dev.alloc(n_cw)
-        native.check(lib.svs_memcpy_h2d(d_stream, s.ctypes.data, s.size, None), "svs_memcpy_h2d")
-        d_erased = 0
-        if m is not None:
-            d_erased = dev.alloc(m.size)
-            native.check(lib.svs_memcpy_h2d(d_erased, m.ctypes.data, m.size, None), "svs_memcpy_h2d")
-        decode_device(d_stream, k, d_erased, d_status, n_cw)
-        native.check(lib.svs_memcpy_d2h(data.ctypes.data, d_stream, k, None), "svs_memcpy_d2h")
-        native.check(lib.svs_memcpy_d2h(status.ctypes.data, d_status, n_cw, None), "svs_memcpy_d2h")
-        native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
-    return data.tobytes(), status
+    return _decode_staged(stream, k, erased, device, load, decode_device)

@@ -286,7 +286,7 @@ def emu(build_dir=None):
         out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="rs_emu_"), "libsvs_rs_emu.so")
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, EMU_SRC, "-o", out])
         lib = C.CDLL(out)
-        lib.rs_emu_decode.restype, lib.rs_emu_decode.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.rs_emu_decode.restype, lib.rs_emu_decode.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rs_emu_encode.restype, lib.rs_emu_encode.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]
         lib.rs_emu_data_bytes.restype, lib.rs_emu_data_bytes.argtypes = C.c_uint64, [C.c_uint64]
         lib.rs_emu_coded_bytes.restype, lib.rs_emu_coded_bytes.argtypes = C.c_uint64, [C.c_uint64]
@@ -294,12 +294,13 @@ def emu(build_dir=None):
     return _EMU
 
 
-def emu_decode(received, k, counts=(0, 0), build_dir=None):
-    """the host build's decoder -> (stream, status, counts)"""
+def emu_decode(received, k, counts=(0, 0), build_dir=None, mask=None):
+    """the host build's decoder (mask: the erased bytes, tests/rse_lib.py; here none) -> (stream, status, counts)"""
     stream = np.array(received, np.uint8)
     status = np.full(codewords(k), 0xEE, np.uint8)
     cnt = np.array(counts, np.uint32)
-    assert emu(build_dir).rs_emu_decode(stream.ctypes.data, k, status.ctypes.data, cnt.ctypes.data) == 0
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+    assert emu(build_dir).rs_emu_decode(stream.ctypes.data, k, None if m is None else m.ctypes.data, status.ctypes.data, cnt.ctypes.data) == 0
     return stream, status, (int(cnt[0]), int(cnt[1]))
 
 

@@ -2,14 +2,9 @@
 ("THE FORMAT") and not from csrc/svs_rs.hpp: the field, the layout and the syndromes are tests/rs_lib.py's; here are the erasure
 locator, Berlekamp-Massey started from it on all dirty codewords at once, the roots by evaluating the locator at every position,
 Forney, and `check_definition`, which holds a decoder's output against the format's definition; the inputs of
-tests/test_rse_gpu.py, so that the CPU tier runs the host build of svs_rs.hpp (tests/hostemu/rse_emu.cpp) on the same ones; and
+tests/test_rse_gpu.py, so that the CPU tier runs the host build of svs_rs.hpp (tests/hostemu/rs_emu.cpp) on the same ones; and
 the lost-frame experiment of the README's table (tests/channel_lib.py's model of the embed, tests/soft_lib.py's soft bytes,
 tests/fec_lib.py's inner code)."""
-import ctypes as C
-import os
-import subprocess
-import tempfile
-
 import numpy as np
 
 import rs_lib as rl
@@ -202,33 +197,13 @@ def case(kind, k):
     return _CASES[key]
 
 
-# ---- the host build of the new steps of csrc/svs_rs.hpp (tests/hostemu/rse_emu.cpp) ----------------------------------------------
-_EMU = None
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = rl.CSRC
-EMU_SRC = os.path.join(HERE, "hostemu", "rse_emu.cpp")
-
-
-def emu(build_dir=None):
-    """tests/hostemu/rse_emu.cpp, compiled once per process with g++ as the other host emulations are"""
-    global _EMU
-    if _EMU is None:
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="rse_emu_"), "libsvs_rse_emu.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, EMU_SRC, "-o", out])
-        lib = C.CDLL(out)
-        lib.rse_emu_decode.restype, lib.rse_emu_decode.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        _EMU = lib
-    return _EMU
+# ---- the host build of csrc/svs_rs.hpp: rs_lib's (tests/hostemu/rs_emu.cpp), called with a mask ------------------------------------
+CSRC, EMU_SRC, emu = rl.CSRC, rl.EMU_SRC, rl.emu
 
 
 def emu_decode(received, k, mask=None, counts=(0, 0), build_dir=None):
     """the host build's decoder -> (stream, status, counts)"""
-    stream = np.array(received, np.uint8)
-    status = np.full(codewords(k), 0xEE, np.uint8)
-    cnt = np.array(counts, np.uint32)
-    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-    assert emu(build_dir).rse_emu_decode(stream.ctypes.data, k, None if m is None else m.ctypes.data, status.ctypes.data, cnt.ctypes.data) == 0
-    return stream, status, (int(cnt[0]), int(cnt[1]))
+    return rl.emu_decode(received, k, counts, build_dir, mask)
 
 
 # ---- the README's table: a lost frame -------------------------------------------------------------------------------------------------

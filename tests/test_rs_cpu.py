@@ -35,6 +35,9 @@ def test_the_library_exports_exactly_the_header():
     out = subprocess.run(["nm", "-D", "--defined-only", rs.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("svs_"))
     assert exported == _declared() == sorted(rs.SIGNATURES) and len(exported) == 7
+    # both Reed-Solomon libraries hold the kernel and the tables of csrc/svs_rs_decode.hpp and are loaded into one process: a
+    # dynamic symbol of either would be interposed by the other's
+    assert not [line for line in out.splitlines() if any(name in line for name in ("decode_kernel", "d_field", "d_lfsr"))], out
     assert rs.load().svs_rs_abi_version() == rs.ABI_VERSION == 1
     undefined = subprocess.run(["nm", "-D", "--undefined-only", rs.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "hipLaunchKernel" in undefined or "__hipPushCallConfiguration" in undefined       # nm really listed imports

@@ -29,6 +29,9 @@ def test_the_library_exports_exactly_the_header():
     out = subprocess.run(["nm", "-D", "--defined-only", rse.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("svs_"))
     assert exported == _declared() == sorted(rse.SIGNATURES) and len(exported) == 3
+    # both Reed-Solomon libraries hold the kernel and the tables of csrc/svs_rs_decode.hpp and are loaded into one process: a
+    # dynamic symbol of either would be interposed by the other's
+    assert not [line for line in out.splitlines() if any(name in line for name in ("decode_kernel", "d_field", "d_lfsr"))], out
     assert rse.load().svs_rse_abi_version() == rse.ABI_VERSION == 1
     undefined = subprocess.run(["nm", "-D", "--undefined-only", rse.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "hipLaunchKernel" in undefined or "__hipPushCallConfiguration" in undefined       # nm really listed imports
@@ -170,8 +173,8 @@ def test_the_host_build_without_erasures_is_the_parents_model(kind, emu_dir):
 
 
 def test_the_sanitized_stand_alone_program(tmp_path):
-    """the host build's screening with a mask, erasure locator, Berlekamp-Massey, root search and Forney, driven by rse_emu.cpp's
-    own main, under the address and undefined-behaviour sanitizers: a stand-alone program, run once; nothing is loaded into python"""
+    """the host build's screening with a mask, erasure locator, Berlekamp-Massey, root search and Forney, driven by rs_emu.cpp's
+    -DRSE_EMU_MAIN main, under the address and undefined-behaviour sanitizers: a stand-alone program, run once; nothing is loaded into python"""
     exe = str(tmp_path / "rse_emu_main")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DRSE_EMU_MAIN",
                            "-I" + el.CSRC, el.EMU_SRC, "-o", exe])

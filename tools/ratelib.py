@@ -39,7 +39,7 @@ def parser(out, frames=200, reps=5, rounds=False, baseline=None):
     ap.add_argument("--fixed-order", action="store_true", help="the same order of the calls in every repetition (no rotation)")
     if baseline:
         ap.add_argument("--baseline-lib", required=baseline == "required", default=None,
-                        help="libsvsdct.so of the parent commit, timed alternately with this build")
+                        help="the library of the parent commit, timed alternately with this build")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", out))
     return ap
 
@@ -71,8 +71,9 @@ _torch = None      # imported by the session, which a script makes before it tim
 
 def timed(fn):
     """ms of one call between a pair of HIP events on the null stream (torch.cuda.Event; the library's calls with stream NULL
-    are enqueued on the same stream)"""
+    are enqueued on the same stream).  A call that works in place carries its own `prepare`, run before the first event"""
     a, b = _torch.cuda.Event(enable_timing=True), _torch.cuda.Event(enable_timing=True)
+    getattr(fn, "prepare", lambda: None)()
     sync()
     a.record()
     fn()

@@ -11,10 +11,15 @@ pair of HIP events.  The calls are alternated inside every repetition and the or
 Before the timing each case is decoded once into zeroed counters, which the report shows.  The Viterbi call reads soft bytes
 of the same length extracted from noise frames: its work does not depend on its data (tools/fec_rates.py).  No ratio is
 asserted: the file reports the four times, their ratios to the Viterbi call and the clean pass's bytes per second.
+With --baseline-lib (libsvsrs.so of the parent commit: `make -C <package>/csrc rs-baseline REV=<commit>`), each of the four cases
+is also timed against that library's svs_rs_decode_dev, each pair alternated and judged by the baseline's own spread
+(ratelib.verdict).
 Output: profiles/rs_rates.txt.
 
-    python tools/rs_rates.py
+    python tools/rs_rates.py [--baseline-lib <package>/lib/variants/libsvsrs_parent.so]
 """
+import ctypes as C
+import os
 import statistics
 
 import numpy as np
@@ -44,8 +49,16 @@ def received(sent, k, rng, share, lo, hi):
     return out
 
 
+def load_rs_build(path):
+    lib = C.CDLL(os.path.abspath(path))
+    for name, (res, args) in rs.SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
+    return lib
+
+
 def main():
-    args = ratelib.parser("rs_rates.txt", reps=15).parse_args()
+    args = ratelib.parser("rs_rates.txt", reps=15, baseline="optional").parse_args()
     s = ratelib.Session(args)
     torch = ratelib._torch
     lib, flib, rlib = s.lib, fec.load(), rs.load()
@@ -73,8 +86,8 @@ def main():
     s.soft(lib, DELTA, N, d_soft)()                        # the soft bytes the Viterbi decoder reads
     ratelib.sync()
 
-    def decode(name, d_counts=None):
-        fn = lambda: rs.check(rlib.svs_rs_decode_dev(work.data_ptr(), k, status.data_ptr(), n_cw, d_counts, None), "svs_rs_decode_dev")  # noqa: E731
+    def decode(name, d_counts=None, build=rlib):
+        fn = lambda: rs.check(build.svs_rs_decode_dev(work.data_ptr(), k, status.data_ptr(), n_cw, d_counts, None), "svs_rs_decode_dev")  # noqa: E731
         fn.prepare = lambda: work.copy_(master[name])
         return fn
 
@@ -88,20 +101,22 @@ def main():
         got = counts.cpu().numpy().view(np.uint32)
         s.say(f"    {name:42s} {int(got[0]):9d} {int(got[1]):7d} {int((status == 0).sum().item()):7d}")
 
-    def timed(fn):
-        getattr(fn, "prepare", lambda: None)()
-        return ratelib.timed(fn)
-
     viterbi = "svs_fec_decode_soft_dev, rate 2, same payload"
     todo = {viterbi: lambda: fec.check(flib.svs_fec_decode_soft_dev(d_soft, n_info, 2, d_out, (n_info + 7) // 8, None),
                                        "svs_fec_decode_soft_dev")}
     todo.update({name: decode(name) for name in cases})
-    t = ratelib.alternate(todo, args.reps, not args.fixed_order, timed)
+    t = s.measure(todo)
     base = statistics.median(t[viterbi])
     for name, v in t.items():
         s.say(ratelib.row(name, v, 46) + f"  spread {ratelib.spread(v):.1f} %" + ("" if name == viterbi else f"  {statistics.median(v) / base:.3f} x the Viterbi call"))
     clean = statistics.median(t["clean"])
     s.say(f"    the clean pass reads {total} bytes in {clean:.3f} ms: {total / clean / 1e6:.1f} GB/s")
+    if not args.baseline_lib:
+        s.say("  no --baseline-lib: the four cases were not timed against the parent commit's library")
+    else:
+        old = load_rs_build(args.baseline_lib)
+        s.say(f"  against {os.path.basename(args.baseline_lib)} (the parent commit's libsvsrs.so), each pair alternated")
+        s.against_baseline([(name, decode(name, build=old), decode(name)) for name in cases])
     s.close()
 
 

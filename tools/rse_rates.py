@@ -1,16 +1,16 @@
-"""Cost of the errors-and-erasures decoder (include/svsrse.h svs_rse_decode_dev) beside the decoder it extends
-(include/svsrs.h svs_rs_decode_dev, the same library file as before this decoder existed) and beside the call in front of both,
-the Viterbi decoder (svs_fec_decode_soft_dev at rate 2) on the same payload, all in one process.  The workload is that of
+"""Cost of the errors-and-erasures decoder (include/svsrse.h svs_rse_decode_dev) beside the call in front of it, the Viterbi
+decoder (svs_fec_decode_soft_dev at rate 2) on the same payload, all in one process.  svs_rs_decode_dev (include/svsrs.h) runs
+the same kernel without a mask; tools/rs_rates.py --baseline-lib times that against an earlier build.  The workload is that of
 tools/rs_rates.py: the RS stream that fills svs_fec_info_bits of the frames' capacity at n_ac = 10, rate 1/2.  Cases:
-  clean, NULL mask             the screening pass without the mask load            (old call: the same bytes)
+  clean, NULL mask             the screening pass without the mask load
   clean, mask of zeros         what the second byte load costs the clean pass
   clean, a run of 32 C erased  every codeword has f = 32 and a zero remainder: status 0 from the screening pass
   that run randomised          every codeword repairs at f = 32: 32 locator steps, no Berlekamp-Massey step, degree 32
-  16 errors, NULL mask         every codeword repaired at the blind limit          (old call: the same bytes)
+  16 errors, NULL mask         every codeword repaired at the blind limit
 The decoders work in place, so before every timed call the received stream is copied back over the working buffer, outside the
 pair of HIP events.  The calls are alternated inside every repetition and the order rotated from one repetition to the next.
 Before the timing each case is decoded once into zeroed counters, which the report shows.  No ratio is asserted: the file
-reports the times, their ratios to the old call on the same bytes where it takes them, and to the Viterbi call.
+reports the times and their ratios to the Viterbi call.
 Output: profiles/rse_rates.txt.
 
     python tools/rse_rates.py
@@ -45,14 +45,14 @@ def main():
     randomised[n_cw: 33 * n_cw] ^= rng.integers(1, 256, 32 * n_cw).astype(np.uint8)
     sixteen = received(sent, k, rng, 1, 16, 16)
     zeros = np.zeros(total, np.uint8)
-    # name -> (received stream, mask or None, does the old call take it)
-    cases = {"clean, NULL mask": (sent, None, True),
-             "clean, mask of zeros": (sent, zeros, False),
-             "clean, a run of 32 C bytes erased": (sent, run, False),
-             "that run randomised: every codeword f = 32": (randomised, run, False),
-             "every codeword with 16 errors, NULL mask": (sixteen, None, True)}
-    master = {name: torch.from_numpy(a).cuda() for name, (a, _, _) in cases.items()}
-    masks = {name: None if m is None else torch.from_numpy(np.concatenate([[0], m]).astype(np.uint8)).cuda()[1:] for name, (_, m, _) in cases.items()}
+    # name -> (received stream, mask or None)
+    cases = {"clean, NULL mask": (sent, None),
+             "clean, mask of zeros": (sent, zeros),
+             "clean, a run of 32 C bytes erased": (sent, run),
+             "that run randomised: every codeword f = 32": (randomised, run),
+             "every codeword with 16 errors, NULL mask": (sixteen, None)}
+    master = {name: torch.from_numpy(a).cuda() for name, (a, _) in cases.items()}
+    masks = {name: None if m is None else torch.from_numpy(np.concatenate([[0], m]).astype(np.uint8)).cuda()[1:] for name, (_, m) in cases.items()}
     work = torch.empty(total + 1, dtype=torch.uint8, device="cuda")[1:]                 # an odd address: any alignment
     status = torch.empty(n_cw, dtype=torch.uint8, device="cuda")
     counts = torch.zeros(2, dtype=torch.int32, device="cuda")
@@ -72,11 +72,6 @@ def main():
         fn.prepare = lambda: work.copy_(master[name])
         return fn
 
-    def old(name):
-        fn = lambda: rs.check(rlib.svs_rs_decode_dev(work.data_ptr(), k, status.data_ptr(), n_cw, None, None), "svs_rs_decode_dev")  # noqa: E731
-        fn.prepare = lambda: work.copy_(master[name])
-        return fn
-
     s.say("  one decode of each case into zeroed counters: bytes changed, codewords with status 255, codewords with status 0")
     for name in cases:
         counts.zero_()
@@ -87,27 +82,14 @@ def main():
         got = counts.cpu().numpy().view(np.uint32)
         s.say(f"    {name:46s} {int(got[0]):9d} {int(got[1]):7d} {int((status == 0).sum().item()):7d}")
 
-    def timed(fn):
-        getattr(fn, "prepare", lambda: None)()
-        return ratelib.timed(fn)
-
     viterbi = "svs_fec_decode_soft_dev, rate 2, same payload"
     todo = {viterbi: lambda: fec.check(flib.svs_fec_decode_soft_dev(d_soft, n_info, 2, d_out, (n_info + 7) // 8, None),
                                        "svs_fec_decode_soft_dev")}
-    for name, (_, _, takes) in cases.items():
-        todo[name] = new(name)
-        if takes:
-            todo["svs_rs_decode_dev: " + name.split(",")[0]] = old(name)
-    t = ratelib.alternate(todo, args.reps, not args.fixed_order, timed)
+    todo.update({name: new(name) for name in cases})
+    t = s.measure(todo)
     base = statistics.median(t[viterbi])
     for name, v in t.items():
-        line = ratelib.row(name, v, 50) + f"  spread {ratelib.spread(v):.1f} %"
-        if name != viterbi:
-            line += f"  {statistics.median(v) / base:.3f} x the Viterbi call"
-        before = "svs_rs_decode_dev: " + name.split(",")[0]
-        if name in cases and before in t:
-            line += f"  {statistics.median(v) / statistics.median(t[before]):.3f} x the old call"
-        s.say(line)
+        s.say(ratelib.row(name, v, 50) + f"  spread {ratelib.spread(v):.1f} %" + ("" if name == viterbi else f"  {statistics.median(v) / base:.3f} x the Viterbi call"))
     clean, masked = statistics.median(t["clean, NULL mask"]), statistics.median(t["clean, mask of zeros"])
     s.say(f"    the clean pass reads {total} bytes in {clean:.3f} ms: {total / clean / 1e6:.1f} GB/s; with the mask beside them "
           f"{2 * total} bytes in {masked:.3f} ms: {2 * total / masked / 1e6:.1f} GB/s")
