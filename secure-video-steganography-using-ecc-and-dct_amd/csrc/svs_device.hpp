@@ -1228,7 +1228,7 @@ __device__ __forceinline__ void bgr8_to_gray(const u32x2 &q0, const u32x2 &q1, c
 //           payload words the embed used (svs_readback.hpp readback_block_ok: extract_exact_kernel's forward transform on
 //           the payload rows).  A block that reads back is not written.  Waves without a failing block end after a ballot.
 //   repair  the wave's failing blocks are compacted into a wave-private LDS worklist (ballot + mbcnt: their rows and
-//           payload window, SVS_RB_CAP per round); the whole wave then repairs them eight lanes per block (repair8: lane r
+//           payload window, SVS_RB_CAP per round); the whole wave then repairs them eight lanes per block (search8: lane r
 //           transforms column r and row r, the block's lines meet in an LDS tile) - eight blocks at a time.  Owners of repaired blocks read
 //           the accepted rows back and store them; an unrepaired block is not written (the reference's bytes stay).
 // Counts: one 64-bit atomic per wave and kind into counts[0] (repaired) / counts[1] (left unrepaired), NULL for none.
@@ -1252,19 +1252,25 @@ __device__ __forceinline__ float group8_max(float v) {
     return fmaxf(v, __shfl_xor(v, 4, 64));
 }
 
-// svs_readback.hpp repair_block on eight lanes (r = 0..7) of one worklist entry: px = its rows in LDS (in: the reference's
+// svs_readback.hpp search_block on eight lanes (r = 0..7) of one worklist entry: px = its rows in LDS (in: the reference's
 // stego; out: the last iterate), t = the group's 64-float tile.  The same operations on the same values, so the same bytes;
-// true (in all eight lanes) when an iterate read back.
-template <int QM>
-__device__ __forceinline__ bool repair8(uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+// true (in all eight lanes) when an iterate was accepted.  The one copy of the loop on the device: `rows` is what a form of
+// the pass differs in, lane r's coefficient row of each (svs_readback.hpp's row functions) -
+//   targets(c, T)               the row's targets from the block's coefficients
+//   correction(T, c, scale, d)  its over-relaxed correction
+//   rejects(c)                  non-zero while the row keeps these coefficients from being accepted: the lane's own verdict,
+//                               ORed over the group here
+// - a small value type (PlainRows, KeyedRows, SteppedRows below), everything inlined.
+template <class Rows>
+__device__ __forceinline__ bool search8(uint32_t *px, float *t, uint32_t r, const Rows &rows) {
     float c[8], T[8];
     forward8<8>(px, t, r, c);
-    repair_targets_row<QM>(c, (int)r, nb, hi, lo, qp, T);
+    rows.targets(c, T);
 #pragma unroll 1
     for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
         const float scale = 1.0f + 0.5f * (float)it;
         float d[8], col[8], row[8], y[8];
-        repair_correction_row(T, c, (int)r, nb, scale, d);
+        rows.correction(T, c, scale, d);
 #pragma unroll
         for (int x = 0; x < 8; ++x) t[8 * r + x] = d[x];            // coefficient row r
         wave_lds_fence();
@@ -1282,15 +1288,124 @@ __device__ __forceinline__ bool repair8(uint32_t *px, float *t, uint32_t r, uint
         px[2 * r + 1] = hi4;
         wave_lds_fence();
         forward8<8>(px, t, r, c);
-        if (group8_or(row_misses<QM>(c, (int)r, nb, hi, lo, qp) ? 1u : 0u) == 0) return true;
+        if (group8_or(rows.rejects(c)) == 0) return true;
     }
     return false;
+}
+
+// does the worklist entry px read back?  Eight lanes: the forward transform and acceptance test of search8, so the verdict is
+// readback_block_ok's (the exact read-back) for every number of coefficient rows
+template <class Rows>
+__device__ __forceinline__ bool reads_back8(const uint32_t *px, float *t, uint32_t r, const Rows &rows) {
+    float c[8];
+    forward8<8>(px, t, r, c);
+    return !group8_or(rows.rejects(c));
+}
+
+// an entry that is checked on eight lanes before it is searched: left alone when it reads back, else settled as 1 = repaired or
+// 2 = could not be repaired (settle: readback_worklist's)
+template <class Rows, class Settle>
+__device__ __forceinline__ void check_and_search8(uint32_t *px, float *t, uint32_t r, const Rows &rows, Settle &&settle) {
+    if (reads_back8(px, t, r, rows)) return;   // uniform over the entry's eight lanes
+    wave_lds_fence();
+    settle(search8(px, t, r, rows) ? 1u : 2u);
+}
+
+// the gray and the colour form: flat indices 1 .. nb under the call's quantiser
+template <int QM>
+struct PlainRows {
+    uint32_t r, nb, hi, lo;
+    const QimParams &qp;
+    __device__ __forceinline__ void targets(const float (&c)[8], float (&T)[8]) const { repair_targets_row<QM>(c, (int)r, nb, hi, lo, qp, T); }
+    __device__ __forceinline__ void correction(const float (&T)[8], const float (&c)[8], float scale, float (&d)[8]) const {
+        repair_correction_row(T, c, (int)r, nb, scale, d);
+    }
+    __device__ __forceinline__ uint32_t rejects(const float (&c)[8]) const { return row_misses<QM>(c, (int)r, nb, hi, lo, qp) ? 1u : 0u; }
+};
+
+// The wave's worklist, every form: wslots / wmeta / wtiles = the wave's part of readback_kernel's three LDS arrays, `wanted` =
+// this lane's block enters the worklist, as number `rank` of the wave's `total`.  Rounds of SVS_RB_CAP entries, each in passes
+// of eight entries on eight lanes each:
+//   deposit(e, m)          the owner fills its entry: e = its SVS_RB_SLOT dwords of rows, m = its meta - x / y = the payload
+//                          window, z = nb, w = s_b (0 without a dither)
+//   examine(px, t, r, m, settle)   lanes 8 grp .. 8 grp + 7, r = lane & 7, on the entry's rows px with the group's tile t.  An
+//                          entry it leaves as it is keeps status 0; one it searched it settles, in all eight lanes, with
+//                          settle(1) = px holds the accepted block or settle(2) = searched in vain, kept in the entry as z = nb |
+//                          status << 8 - written there, inside the branch that searched, not behind examine
+//   store(e)               the owner of an entry with status 1 writes its rows out (wtiles is free between the passes)
+// Returns the lane's status (0 for a lane without an entry).
+template <class Deposit, class Examine, class Store>
+__device__ __forceinline__ uint32_t readback_worklist(uint32_t *wslots, u32x4 *wmeta, float *wtiles, const bool wanted,
+                                                      const uint32_t rank, const uint32_t total, Deposit &&deposit,
+                                                      Examine &&examine, Store &&store) {
+    const uint32_t lane = threadIdx.x & 63u, grp = lane >> 3, r = lane & 7u;
+    uint32_t status = 0;
+#pragma unroll 1
+    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries (at most two)
+        const bool mine = wanted && rank >= base && rank < base + SVS_RB_CAP;
+        if (mine) {
+            u32x4 m;
+            deposit(wslots + (rank - base) * SVS_RB_SLOT, m);
+            wmeta[rank - base] = m;
+        }
+        wave_lds_fence();
+        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
+#pragma unroll 1
+        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time (at most four passes)
+            const uint32_t idx = at + grp;
+            if (idx < count) {
+                const u32x4 m = wmeta[idx];
+                examine(wslots + idx * SVS_RB_SLOT, wtiles + 64 * grp, r, m, [&](uint32_t found) {
+                    if (r == 0) wmeta[idx].z = m.z | found << 8;
+                });
+            }
+            wave_lds_fence();
+        }
+        if (mine) {
+            status = wmeta[rank - base].z >> 8;
+            if (status == 1) store(wslots + (rank - base) * SVS_RB_SLOT);
+        }
+        wave_lds_fence();
+    }
+    return status;
+}
+
+// one 64-bit atomic per wave and kind: counts[at] += the wave's lanes with status 1, counts[at + 1] += those with status 2
+__device__ __forceinline__ void add_counts(unsigned long long *counts, uint32_t at, uint32_t status) {
+    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
+    if (counts && (threadIdx.x & 63u) == 0) {
+        if (rep) atomicAdd(&counts[at], (unsigned long long)__popcll(rep));
+        if (left) atomicAdd(&counts[at + 1], (unsigned long long)__popcll(left));
+    }
+}
+
+// an entry's meta as its owner deposits it: the payload window that starts at stream bit `at`, nb and s_b
+__device__ __forceinline__ u32x4 entry_meta(const uint32_t *__restrict__ bits, uint32_t n_words, uint64_t at, uint32_t nb, uint32_t s_b) {
+    u32x4 m; m.z = nb; m.w = s_b;
+    uint32_t hi, lo;
+    payload_window(bits, n_words, at, hi, lo);
+    m.x = hi; m.y = lo;
+    return m;
+}
+
+// a gray block's rows into its entry, and an accepted entry's rows back over the block
+__device__ __forceinline__ void deposit_rows(const uint8_t *src, int64_t row_pitch, uint32_t *e) {
+    u32x2 v[8];
+    load_rows<1>(src, row_pitch, v);
+#pragma unroll
+    for (int y = 0; y < 8; ++y) { e[2 * y] = v[y].x; e[2 * y + 1] = v[y].y; }
+}
+__device__ __forceinline__ void store_entry_rows(const uint32_t *e, uint8_t *dst, int64_t row_pitch) {
+    u32x2 v[8];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) { v[y].x = e[2 * y]; v[y].y = e[2 * y + 1]; }
+    store_rows<1>(dst, row_pitch, v);
 }
 
 // The colour form (svs_embed_bgr_readback_dev): the same pass in place on the fused colour embed's interleaved BGR output
 // (c: its pitches in out_*, the call's weights).  Check and repair work on gray(BGR), the call's fixed-point gray, so they
 // are the gray pass's; only the way a block's rows come in and leave differs.  A body of its own behind the kernel's
-// wave-uniform `form` argument - no instantiation of its own, and the gray body above it stays as it was.  Raster order
+// wave-uniform `form` argument - no instantiation of its own, and the gray body stays as it was.  Raster order
 // only: the colour calls have no keyed order.
 //   check   every block that carries payload is deposited in the worklist - its gray rows computed from its 24-byte rows -
 //           and read back on eight lanes (reads_back8)
@@ -1302,7 +1417,7 @@ __device__ __forceinline__ bool repair8(uint32_t *px, float *t, uint32_t r, uint
 #define SVS_RB_BGR 1u
 static_assert(64 * 6 <= 8 * 64, "one 24-byte row per lane fits the wave's tiles");
 
-// gray rows of one block from its BGR rows into a worklist entry, a row at a time (only failing blocks come here)
+// gray rows of one block from its BGR rows into a worklist entry, a row at a time
 __device__ __forceinline__ void deposit_bgr_as_gray(const uint8_t *src, int64_t row_pitch, const ColourParams &c, uint32_t *e) {
 #pragma unroll 1
     for (int y = 0; y < 8; ++y) {
@@ -1349,20 +1464,10 @@ __device__ __forceinline__ void store_entry_as_bgr(const uint32_t *e, uint8_t *d
     }
 }
 
-// does the worklist entry px read back?  Eight lanes: the forward transform and acceptance test of repair8, so the verdict is
-// readback_block_ok's (the exact read-back) for every number of coefficient rows
-template <int QM>
-__device__ __forceinline__ bool reads_back8(const uint32_t *px, float *t, uint32_t r, uint32_t nb, uint32_t hi, uint32_t lo,
-                                            const QimParams &qp) {
-    float c[8];
-    forward8<8>(px, t, r, c);
-    return group8_or(row_misses<QM>(c, (int)r, nb, hi, lo, qp) ? 1u : 0u) == 0;
-}
-
-// wslots / wmeta / wtiles: the wave's part of readback_kernel's three LDS arrays.  Every block that carries payload goes
-// through the worklist and is CHECKED on eight lanes too (reads_back8): the lane-per-block check of the gray form, fed from BGR,
-// took up to 132 VGPRs with eight coefficient rows - a wave per SIMD of the gray form's - while this body stays within the
-// repair's registers; the arithmetic per block is the same sixteen 8-point transforms, spread over eight lanes.
+// Every block that carries payload goes through the worklist and is CHECKED on eight lanes too (reads_back8): the
+// lane-per-block check of the gray form, fed from BGR, took up to 132 VGPRs with eight coefficient rows - a wave per SIMD of
+// the gray form's - while this body stays within the search's registers; the arithmetic per block is the same sixteen 8-point
+// transforms, spread over eight lanes.
 template <int QM>
 __device__ __forceinline__ void readback_colour(uint32_t *wslots, u32x4 *wmeta, float *wtiles, uint8_t *bgr, const Geometry &g,
                                                 const QimParams &qp, const uint32_t *__restrict__ bits, const uint64_t bit_offset,
@@ -1381,64 +1486,33 @@ __device__ __forceinline__ void readback_colour(uint32_t *wslots, u32x4 *wmeta, 
     if (mask == 0) return;               // wave-uniform
     const uint32_t total = (uint32_t)__popcll(mask);
     const uint32_t rank = wave_rank(mask);
-    const uint32_t grp = lane >> 3, r = lane & 7u;
     int64_t off = 0;
     if (nb > 0) off = block_offset_bgr(gblock, g, c.out_row_pitch, c.out_frame_pitch);
-    uint32_t status = 0;
-#pragma unroll 1
-    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries
-        const bool mine = nb > 0 && rank >= base && rank < base + SVS_RB_CAP;
-        if (mine) {
-            deposit_bgr_as_gray(bgr + off, c.out_row_pitch, c, wslots + (rank - base) * SVS_RB_SLOT);
-            u32x4 m; m.z = nb; m.w = 0u;
-            uint32_t hi, lo;
-            payload_window(bits, n_words, bit_offset + first, hi, lo);
-            m.x = hi; m.y = lo;
-            wmeta[rank - base] = m;
-        }
-        wave_lds_fence();
-        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
-#pragma unroll 1
-        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time
-            const uint32_t idx = at + grp;
-            if (idx < count) {
-                const u32x4 m = wmeta[idx];
-                uint32_t *px = wslots + idx * SVS_RB_SLOT;
-                float *t = wtiles + 64 * grp;
-                if (!reads_back8<QM>(px, t, r, m.z, m.x, m.y, qp)) {   // uniform over the entry's eight lanes
-                    wave_lds_fence();
-                    const bool ok = repair8<QM>(px, t, r, m.z, m.x, m.y, qp);
-                    if (r == 0) wmeta[idx].w = ok ? 1u : 2u;
-                }
-            }
-            wave_lds_fence();
-        }
-        if (mine) {
-            status = wmeta[rank - base].w;
-            if (status == 1)   // the tiles are free between the passes: 24 bytes of them per lane
-                store_entry_as_bgr(wslots + (rank - base) * SVS_RB_SLOT, bgr + off, c.out_row_pitch, c,
-                                   reinterpret_cast<u32x2 *>(wtiles) + 3 * lane);
-        }
-        wave_lds_fence();
-    }
-    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
-    if (counts && lane == 0) {
-        if (rep) atomicAdd(&counts[0], (unsigned long long)__popcll(rep));
-        if (left) atomicAdd(&counts[1], (unsigned long long)__popcll(left));
-    }
+    const uint32_t status = readback_worklist(
+        wslots, wmeta, wtiles, nb > 0, rank, total,
+        [&](uint32_t *e, u32x4 &m) {
+            deposit_bgr_as_gray(bgr + off, c.out_row_pitch, c, e);
+            m = entry_meta(bits, n_words, bit_offset + first, nb, 0u);
+        },
+        [&](uint32_t *px, float *t, uint32_t r, const u32x4 &m, auto settle) {
+            check_and_search8(px, t, r, PlainRows<QM>{r, m.z, m.x, m.y, qp}, settle);
+        },
+        [&](const uint32_t *e) {   // 24 bytes of the tiles per lane
+            store_entry_as_bgr(e, bgr + off, c.out_row_pitch, c, reinterpret_cast<u32x2 *>(wtiles) + 3 * lane);
+        });
+    add_counts(counts, 0u, status);
 }
 
 // The keyed form (svs_embed_dithered_readback_dev): the gray pass under a coefficient SELECTION and a keyed DITHER
 // (svs_readback.hpp, the keyed forms).  kd.sel = the call's inverse table or the prefix table of n_ac (never empty here), kd.on
-// = the dither's switch, a kernel argument and so wave-uniform.  Structured as readback_colour: every block that carries
-// payload goes into the worklist - its rows, payload window, nb and s_b - is checked on eight lanes and repaired on eight
-// lanes when it fails; the owner stores an accepted block, every other block is never written.
+// = the dither's switch, a kernel argument and so wave-uniform.  Every block that carries payload goes into the worklist - its
+// rows, payload window, nb and s_b - is checked on eight lanes and searched on eight lanes when it fails; the owner stores an
+// accepted block, every other block is never written.
 //   table   lane r of a group handles flat indices 8r .. 8r + 7 and needs words 2r and 2r + 1 of the inverse table: selected
 //           into two registers once (fourteen v_cndmask), never indexed - a per-lane index into a kernel argument is scratch
 //   dither  s_b is that of the block's PHYSICAL position (dither_seed_of), per owner lane - a wave can straddle two frames -
 //           and travels in the entry; the eight lanes each derive the d of their coefficient row from it once per entry
 //   window  that of the block's SLOT: stream_first<true> under an order, gblock * n in raster order (`raster`, wave-uniform)
-// Entry meta: x / y = the payload window, z = nb | status << 8, w = s_b.
 #define SVS_RB_SEL 4u      // form = SVS_RB_SEL + the call's QuantMode (+ SVS_RB_RASTER: no block order)
 #define SVS_RB_RASTER 8u
 
@@ -1452,46 +1526,25 @@ __device__ __forceinline__ RowSlots row_slots_of_lane(const CoeffTable &t, uint3
     return rs;
 }
 
-// repair_block_keyed on eight lanes, as repair8 is repair_block on eight lanes
 template <int QM>
-__device__ bool repair8_keyed(uint32_t *px, float *t, uint32_t r, const RowSlots &rs, uint32_t nb, uint32_t hi, uint32_t lo,
-                              const QimParams &qp, bool dith, const float (&dv)[8]) {
-    float c[8], T[8];
-    forward8<8>(px, t, r, c);
-    keyed_targets_row<QM>(c, rs, nb, hi, lo, qp, dith, dv, T);
-#pragma unroll 1
-    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
-        const float scale = 1.0f + 0.5f * (float)it;
-        float d[8], col[8], row[8], y[8];
+struct KeyedRows {
+    const RowSlots &rs;
+    uint32_t nb, hi, lo;
+    const QimParams &qp;
+    bool dith;
+    const float (&dv)[8];   // the row's d, all 0 without a dither
+    __device__ __forceinline__ void targets(const float (&c)[8], float (&T)[8]) const { keyed_targets_row<QM>(c, rs, nb, hi, lo, qp, dith, dv, T); }
+    __device__ __forceinline__ void correction(const float (&T)[8], const float (&c)[8], float scale, float (&d)[8]) const {
         keyed_correction_row(T, c, rs, nb, scale, d);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) t[8 * r + x] = d[x];            // coefficient row r
-        wave_lds_fence();
-#pragma unroll
-        for (int u = 0; u < 8; ++u) col[u] = t[8 * u + r];          // coefficient column r
-        wave_lds_fence();
-        inverse8<8>(col, t, r, row);                                 // row r of P
-        wave_lds_fence();
-        float mn = 1e30f, mx = -1e30f;
-        repair_add_row(px[2 * r], px[2 * r + 1], row, y, mn, mx);
-        const float s = repair_shift(group8_min(mn), group8_max(mx));
-        uint32_t lo4, hi4;
-        repair_store_row(y, s, lo4, hi4);
-        px[2 * r] = lo4;
-        px[2 * r + 1] = hi4;
-        wave_lds_fence();
-        forward8<8>(px, t, r, c);
-        if (group8_or(keyed_row_misses<QM>(c, rs, nb, hi, lo, qp, dith, dv) ? 1u : 0u) == 0) return true;
     }
-    return false;
-}
+    __device__ __forceinline__ uint32_t rejects(const float (&c)[8]) const { return keyed_row_misses<QM>(c, rs, nb, hi, lo, qp, dith, dv) ? 1u : 0u; }
+};
 
 template <int QM>
 __device__ __forceinline__ void readback_keyed(uint32_t *wslots, u32x4 *wmeta, float *wtiles, uint8_t *stego, const Geometry &g,
                                                const QimParams &qp, const uint32_t *__restrict__ bits, const uint64_t bit_offset,
                                                const uint64_t n_bits, const uint32_t n_words, unsigned long long *counts,
                                                const DitherArgs &kd, const bool raster, const BlockOrderArgs &ord) {
-    const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t n = g.n_ac;
     const bool dith = kd.on != 0u;
@@ -1505,76 +1558,34 @@ __device__ __forceinline__ void readback_keyed(uint32_t *wslots, u32x4 *wmeta, f
     if (mask == 0) return;               // wave-uniform
     const uint32_t total = (uint32_t)__popcll(mask);
     const uint32_t rank = wave_rank(mask);
-    const uint32_t grp = lane >> 3, r = lane & 7u;
-    const RowSlots rs = row_slots_of_lane(kd.sel, r);
+    const RowSlots rs = row_slots_of_lane(kd.sel, threadIdx.x & 7u);
     int64_t off = 0;
     if (nb > 0) off = block_offset(gblock, g);
-    uint32_t status = 0;
-#pragma unroll 1
-    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries (at most two)
-        const bool mine = nb > 0 && rank >= base && rank < base + SVS_RB_CAP;
-        if (mine) {
-            u32x2 v[8];
-            load_rows<1>(stego + off, g.row_pitch, v);
-            uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
+    const uint32_t status = readback_worklist(
+        wslots, wmeta, wtiles, nb > 0, rank, total,
+        [&](uint32_t *e, u32x4 &m) {
+            deposit_rows(stego + off, g.row_pitch, e);
+            m = entry_meta(bits, n_words, bit_offset + first, nb, dith ? dither_seed_of(gblock, g, kd) : 0u);
+        },
+        [&](uint32_t *px, float *t, uint32_t r, const u32x4 &m, auto settle) {
+            float dv[8];
+            if (dith) keyed_dither_row(m.w, r, qp.delta_f, dv);
+            else {
 #pragma unroll
-            for (int y = 0; y < 8; ++y) { e[2 * y] = v[y].x; e[2 * y + 1] = v[y].y; }
-            u32x4 m; m.z = nb; m.w = dith ? dither_seed_of(gblock, g, kd) : 0u;
-            uint32_t hi, lo;
-            payload_window(bits, n_words, bit_offset + first, hi, lo);
-            m.x = hi; m.y = lo;
-            wmeta[rank - base] = m;
-        }
-        wave_lds_fence();
-        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
-#pragma unroll 1
-        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time (at most four passes)
-            const uint32_t idx = at + grp;
-            if (idx < count) {
-                const u32x4 m = wmeta[idx];
-                uint32_t *px = wslots + idx * SVS_RB_SLOT;
-                float *t = wtiles + 64 * grp;
-                float dv[8];
-                if (dith) keyed_dither_row(m.w, r, qp.delta_f, dv);
-                else {
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) dv[v] = 0.0f;
-                }
-                float c[8];
-                forward8<8>(px, t, r, c);
-                if (group8_or(keyed_row_misses<QM>(c, rs, m.z, m.x, m.y, qp, dith, dv) ? 1u : 0u) != 0) {   // uniform over the eight lanes
-                    wave_lds_fence();
-                    const bool ok = repair8_keyed<QM>(px, t, r, rs, m.z, m.x, m.y, qp, dith, dv);
-                    if (r == 0) wmeta[idx].z = m.z | (ok ? 1u : 2u) << 8;
-                }
+                for (int v = 0; v < 8; ++v) dv[v] = 0.0f;
             }
-            wave_lds_fence();
-        }
-        if (mine) {
-            status = wmeta[rank - base].z >> 8;
-            if (status == 1) {
-                const uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
-                u32x2 v[8];
-#pragma unroll
-                for (int y = 0; y < 8; ++y) { v[y].x = e[2 * y]; v[y].y = e[2 * y + 1]; }
-                store_rows<1>(stego + off, g.row_pitch, v);
-            }
-        }
-        wave_lds_fence();
-    }
-    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
-    if (counts && lane == 0) {
-        if (rep) atomicAdd(&counts[0], (unsigned long long)__popcll(rep));
-        if (left) atomicAdd(&counts[1], (unsigned long long)__popcll(left));
-    }
+            check_and_search8(px, t, r, KeyedRows<QM>{rs, m.z, m.x, m.y, qp, dith, dv}, settle);
+        },
+        [&](const uint32_t *e) { store_entry_rows(e, stego + off, g.row_pitch); });
+    add_counts(counts, 0u, status);
 }
 
 // The stepped form (svs_stepped_embed_readback_dev): readback_keyed with a step per coefficient (svs_readback.hpp, the stepped
 // forms), behind form = SVS_RB_STEP (+ SVS_RB_RASTER).  kd as in the keyed form - its table is never empty -, `steps` the call's
-// table, by value.  The same worklist, entry layout, rounds and passes; what differs:
+// table, by value.  What differs:
 //   steps   lane r of a group needs the steps of flat indices 8r .. 8r + 7, dwords 4r .. 4r + 3 of the table: selected into four
-//           registers once (twenty-eight v_cndmask, as row_slots_of_lane selects the inverse table - never indexed, a per-lane
-//           index into a kernel argument is scratch), kept packed and converted where a step is used
+//           registers once (twenty-eight v_cndmask, as row_slots_of_lane selects the inverse table), kept packed and converted
+//           where a step is used
 //   dither  d is recomputed from the entry's s_b where it is used (svs_readback.hpp), not held in eight registers
 // No QimParams is read: the body has no quantiser mode, so it is one body, not three.
 #define SVS_RB_STEP 16u
@@ -1589,48 +1600,29 @@ __device__ __forceinline__ RowSteps row_steps_of_lane(const StepArgs &t, uint32_
     return st;
 }
 
-// repair_block_stepped on eight lanes, as repair8_keyed is repair_block_keyed on eight lanes.  gate (wave-uniform) = 0: the
-// read-back's acceptance, the iterate decodes; 1..127: the margin pass's (strengthen_block_stepped), every payload coefficient of
-// the iterate is strong - both verdicts come as two bits from one row function.
-__device__ bool repair8_stepped(uint32_t *px, float *t, uint32_t r, const RowSlots &rs, const RowSteps &st, uint32_t nb, uint32_t hi,
-                                uint32_t lo, bool dith, uint32_t s_b, uint32_t gate) {
-    float c[8], T[8];
-    forward8<8>(px, t, r, c);
-    stepped_targets_row(c, rs, st, r, nb, hi, lo, dith, s_b, T);
-#pragma unroll 1
-    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
-        const float scale = 1.0f + 0.5f * (float)it;
-        float d[8], col[8], row[8], y[8];
+// gate (wave-uniform) = 0: the read-back's verdict, bit 0 = the row misses a bit; 1..127: the margin pass's
+// (strengthen_block_stepped), SVS_MARGIN_MISS | SVS_MARGIN_WEAK - both as two bits from one row function.
+struct SteppedRows {
+    const RowSlots &rs;
+    const RowSteps &st;
+    uint32_t r, nb, hi, lo;
+    bool dith;
+    uint32_t s_b, gate;
+    __device__ __forceinline__ void targets(const float (&c)[8], float (&T)[8]) const { stepped_targets_row(c, rs, st, r, nb, hi, lo, dith, s_b, T); }
+    __device__ __forceinline__ void correction(const float (&T)[8], const float (&c)[8], float scale, float (&d)[8]) const {
         keyed_correction_row(T, c, rs, nb, scale, d);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) t[8 * r + x] = d[x];            // coefficient row r
-        wave_lds_fence();
-#pragma unroll
-        for (int u = 0; u < 8; ++u) col[u] = t[8 * u + r];          // coefficient column r
-        wave_lds_fence();
-        inverse8<8>(col, t, r, row);                                 // row r of P
-        wave_lds_fence();
-        float mn = 1e30f, mx = -1e30f;
-        repair_add_row(px[2 * r], px[2 * r + 1], row, y, mn, mx);
-        const float s = repair_shift(group8_min(mn), group8_max(mx));
-        uint32_t lo4, hi4;
-        repair_store_row(y, s, lo4, hi4);
-        px[2 * r] = lo4;
-        px[2 * r + 1] = hi4;
-        wave_lds_fence();
-        forward8<8>(px, t, r, c);
+    }
+    __device__ __forceinline__ uint32_t rejects(const float (&c)[8]) const {
         // s_b is hidden from the compiler HERE, once per iterate, so that d is recomputed: left to itself it computes the row's
         // eight d ahead of the loop and holds them beside the eight float steps (133 VGPRs instead of 127)
         uint32_t sb = s_b;
         asm volatile("" : "+v"(sb));
-        const uint32_t bad = __builtin_expect(gate != 0u, 0) ? stepped_row_verdict(c, rs, st, r, nb, hi, lo, dith, sb, (float)gate)
-                                                             : stepped_row_misses(c, rs, st, r, nb, hi, lo, dith, sb) ? 1u : 0u;
-        if (group8_or(bad) == 0) return true;
+        return __builtin_expect(gate != 0u, 0) ? stepped_row_verdict(c, rs, st, r, nb, hi, lo, dith, sb, (float)gate)
+                                               : stepped_row_misses(c, rs, st, r, nb, hi, lo, dith, sb) ? 1u : 0u;
     }
-    return false;
-}
+};
 
-// GATED false: the read-back, the body as it was - the gate is the constant 0 and every branch on it folds away.  GATED true: the
+// GATED false: the read-back - the gate is the constant 0 and every branch on it folds away.  GATED true: the
 // margin pass (svs_stepped_embed_readback_margin_dev's second launch; readback_kernel takes it when `steps` carries a gate), the
 // same body with the gate read from `steps` and a wave-uniform branch at the check, at the search's acceptance and at the counts.
 // Two bodies, so that the read-back's keeps its code; and the gated one branches at run time instead of being a third compiled
@@ -1641,7 +1633,6 @@ __device__ __forceinline__ void readback_stepped(uint32_t *wslots, u32x4 *wmeta,
                                                  const uint32_t *__restrict__ bits, const uint64_t bit_offset, const uint64_t n_bits,
                                                  const uint32_t n_words, unsigned long long *counts, const DitherArgs &kd,
                                                  const StepArgs &steps, const bool raster, const BlockOrderArgs &ord) {
-    const uint32_t lane = threadIdx.x & 63u;
     const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t n = g.n_ac;
     const bool dith = kd.on != 0u;
@@ -1660,76 +1651,39 @@ __device__ __forceinline__ void readback_stepped(uint32_t *wslots, u32x4 *wmeta,
     if (mask == 0) return;               // wave-uniform
     const uint32_t total = (uint32_t)__popcll(mask);
     const uint32_t rank = wave_rank(mask);
-    const uint32_t grp = lane >> 3, r = lane & 7u;
-    const RowSlots rs = row_slots_of_lane(kd.sel, r);
-    const RowSteps st = row_steps_of_lane(steps, r);
+    const RowSlots rs = row_slots_of_lane(kd.sel, threadIdx.x & 7u);
+    const RowSteps st = row_steps_of_lane(steps, threadIdx.x & 7u);
     int64_t off = 0;
     if (nb > 0) off = block_offset(gblock, g);
-    uint32_t status = 0;
-#pragma unroll 1
-    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries (at most two)
-        const bool mine = nb > 0 && rank >= base && rank < base + SVS_RB_CAP;
-        if (mine) {
-            u32x2 v[8];
-            load_rows<1>(stego + off, g.row_pitch, v);
-            uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
-#pragma unroll
-            for (int y = 0; y < 8; ++y) { e[2 * y] = v[y].x; e[2 * y + 1] = v[y].y; }
-            u32x4 m; m.z = nb; m.w = dith ? dither_seed_of(gblock, g, kd) : 0u;
-            uint32_t hi, lo;
-            payload_window(bits, n_words, bit_offset + first, hi, lo);
-            m.x = hi; m.y = lo;
-            wmeta[rank - base] = m;
-        }
-        wave_lds_fence();
-        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
-#pragma unroll 1
-        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time (at most four passes)
-            const uint32_t idx = at + grp;
-            if (idx < count) {
-                const u32x4 m = wmeta[idx];
-                uint32_t *px = wslots + idx * SVS_RB_SLOT;
-                float *t = wtiles + 64 * grp;
-                float c[8];
-                forward8<8>(px, t, r, c);
-                // searched (uniform over the eight lanes): the read-back, a block that misses a bit; the margin pass, a block that
-                // decodes and has a weak coefficient - one that misses a bit is the read-back's unrepaired block and is left
-                bool search;
-                if (__builtin_expect(gate != 0u, 0))
-                    search = group8_or(stepped_row_verdict(c, rs, st, r, m.z, m.x, m.y, dith, m.w, (float)gate)) == SVS_MARGIN_WEAK;
-                else search = group8_or(stepped_row_misses(c, rs, st, r, m.z, m.x, m.y, dith, m.w) ? 1u : 0u) != 0;
-                if (search) {
-                    wave_lds_fence();
-                    const bool ok = repair8_stepped(px, t, r, rs, st, m.z, m.x, m.y, dith, m.w, gate);
-                    if (r == 0) wmeta[idx].z = m.z | (ok ? 1u : 2u) << 8;
-                }
-            }
+    const uint32_t status = readback_worklist(
+        wslots, wmeta, wtiles, nb > 0, rank, total,
+        [&](uint32_t *e, u32x4 &m) {
+            deposit_rows(stego + off, g.row_pitch, e);
+            m = entry_meta(bits, n_words, bit_offset + first, nb, dith ? dither_seed_of(gblock, g, kd) : 0u);
+        },
+        [&](uint32_t *px, float *t, uint32_t r, const u32x4 &m, auto settle) {
+            const SteppedRows rows{rs, st, r, m.z, m.x, m.y, dith, m.w, gate};
+            float c[8];
+            forward8<8>(px, t, r, c);
+            // searched (uniform over the eight lanes): the read-back, a block that misses a bit; the margin pass, a block that
+            // decodes and has a weak coefficient - one that misses a bit is the read-back's unrepaired block and is left.  (The
+            // row functions called here, not rows.rejects: the check needs no hidden s_b.)
+            bool search;
+            if (__builtin_expect(gate != 0u, 0))
+                search = group8_or(stepped_row_verdict(c, rs, st, r, m.z, m.x, m.y, dith, m.w, (float)gate)) == SVS_MARGIN_WEAK;
+            else search = group8_or(stepped_row_misses(c, rs, st, r, m.z, m.x, m.y, dith, m.w) ? 1u : 0u) != 0;
+            if (!search) return;
             wave_lds_fence();
-        }
-        if (mine) {
-            status = wmeta[rank - base].z >> 8;
-            if (status == 1) {
-                const uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
-                u32x2 v[8];
-#pragma unroll
-                for (int y = 0; y < 8; ++y) { v[y].x = e[2 * y]; v[y].y = e[2 * y + 1]; }
-                store_rows<1>(stego + off, g.row_pitch, v);
-            }
-        }
-        wave_lds_fence();
-    }
-    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
-    if (counts && lane == 0) {
-        const uint32_t at = gate != 0u ? 2u : 0u;   // svs_margin_counts: {repaired, unrepaired, strengthened, weak}
-        if (rep) atomicAdd(&counts[at], (unsigned long long)__popcll(rep));
-        if (left) atomicAdd(&counts[at + 1], (unsigned long long)__popcll(left));
-    }
+            settle(search8(px, t, r, rows) ? 1u : 2u);
+        },
+        [&](const uint32_t *e) { store_entry_rows(e, stego + off, g.row_pitch); });
+    add_counts(counts, gate != 0u ? 2u : 0u, status);   // svs_margin_counts: {repaired, unrepaired, strengthened, weak}
 }
 
 // form = SVS_RB_GRAY: `stego` = the gray planes of g, c unused.  form = SVS_RB_BGR + the call's QuantMode: `stego` = the BGR
 // output, readback_colour - in ONE instantiation only.  The colour body depends on the quantiser mode alone (not on U, and it
 // has no order), so all three of its forms live in the instantiation whose gray body leaves the most registers free,
-// readback_kernel<8, QM_POW2, true, BlockOrderArgs> (118 VGPRs), and every colour call launches that one: the other seventeen
+// readback_kernel<8, QM_POW2, true, BlockOrderArgs>, and every colour call launches that one: the other seventeen
 // are the gray pass's code as it was.  (The colour body next to the gray one cost every instantiation that held both 2 - 9
 // VGPRs, and the eight-row ones with a step that is no power of two a wave per SIMD.)
 // form = SVS_RB_SEL + the call's QuantMode (+ SVS_RB_RASTER): the keyed form, readback_keyed, `stego` = the gray planes, kd its
@@ -1751,12 +1705,12 @@ __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const 
     __shared__ uint32_t slots[SVS_WG / 64][SVS_RB_CAP * SVS_RB_SLOT];
     __shared__ u32x4 meta[SVS_WG / 64][SVS_RB_CAP];
     __shared__ float tiles[SVS_WG / 64][8 * 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t *ws = &slots[wave][0];
+    u32x4 *wm = &meta[wave][0];
+    float *wt = &tiles[wave][0];
     if constexpr (SVS_RB_HOSTS_COLOUR(U, QM, KEYED)) {
         if (form != SVS_RB_GRAY) {   // a kernel argument: wave-uniform; form - SVS_RB_BGR = the call's quantiser mode
-            uint32_t *ws = &slots[wave][0];
-            u32x4 *wm = &meta[wave][0];
-            float *wt = &tiles[wave][0];
             if (form >= SVS_RB_SEL) {    // the keyed form; (form & 3) = the call's quantiser mode
                 const bool raster = (form & SVS_RB_RASTER) != 0u;
                 if (form >= SVS_RB_STEP) {   // the stepped form: after the sides that were there first; no quantiser mode
@@ -1779,6 +1733,8 @@ __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const 
             return;
         }
     }
+    // The gray form: one lane per block checks it with the lane-per-block arithmetic (readback_block_ok<U, QM>), and only the
+    // failing blocks enter the worklist, where they are searched without another check.
     const uint32_t gblock = tile_id(g.xcd_chunk) * (uint32_t)SVS_WG + threadIdx.x;
     const uint32_t n = g.n_ac;
     uint32_t nb = 0;
@@ -1790,10 +1746,10 @@ __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const 
     if (__ballot(nb > 0) == 0) return;   // wave-uniform
     bool bad = false;
     int64_t off = 0;
-    u32x2 v[8];
     uint32_t hi = 0, lo = 0;
     if (nb > 0) {
         off = block_offset(gblock, g);
+        u32x2 v[8];
         load_rows<1>(stego + off, g.row_pitch, v);
         uint32_t ax[8], ay[8];
 #pragma unroll
@@ -1803,53 +1759,17 @@ __global__ __launch_bounds__(SVS_WG) void readback_kernel(uint8_t *stego, const 
     }
     const uint64_t mask = __ballot(bad);
     if (mask == 0) return;               // wave-uniform: content without failures
-    const uint32_t total = (uint32_t)__popcll(mask);
-    const uint32_t rank = wave_rank(mask);
-    // The worklist written out rather than through wave_worklist: the rounds and passes stay loops (#pragma unroll 1) with a
-    // fence after every pass, and through the driver readback_kernel<8, 2, true> took 125 instead of 118 VGPRs.
-    uint32_t *wslots = &slots[wave][0];
-    u32x4 *wmeta = &meta[wave][0];
-    const uint32_t grp = lane >> 3, r = lane & 7u;
-    uint32_t status = 0;
-#pragma unroll 1
-    for (uint32_t base = 0; base < total; base += SVS_RB_CAP) {   // wave-uniform: rounds of SVS_RB_CAP entries
-        const bool mine = bad && rank >= base && rank < base + SVS_RB_CAP;
-        if (mine) {   // the rows are read again (the block's own bytes, still unwritten): no registers held across rounds
-            load_rows<1>(stego + off, g.row_pitch, v);
-            uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
-#pragma unroll
-            for (int y = 0; y < 8; ++y) { e[2 * y] = v[y].x; e[2 * y + 1] = v[y].y; }
-            u32x4 m; m.x = hi; m.y = lo; m.z = nb; m.w = 0u;
-            wmeta[rank - base] = m;
-        }
-        wave_lds_fence();
-        const uint32_t count = total - base < SVS_RB_CAP ? total - base : SVS_RB_CAP;
-#pragma unroll 1
-        for (uint32_t at = 0; at < count; at += 8u) {   // wave-uniform: eight entries at a time
-            const uint32_t idx = at + grp;
-            if (idx < count) {
-                const u32x4 m = wmeta[idx];
-                const bool ok = repair8<QM>(wslots + idx * SVS_RB_SLOT, &tiles[wave][64 * grp], r, m.z, m.x, m.y, qp);
-                if (r == 0) wmeta[idx].w = ok ? 1u : 2u;
-            }
-            wave_lds_fence();
-        }
-        if (mine) {
-            status = wmeta[rank - base].w;
-            if (status == 1) {
-                const uint32_t *e = wslots + (rank - base) * SVS_RB_SLOT;
-#pragma unroll
-                for (int y = 0; y < 8; ++y) { v[y].x = e[2 * y]; v[y].y = e[2 * y + 1]; }
-                store_rows<1>(stego + off, g.row_pitch, v);
-            }
-        }
-        wave_lds_fence();
-    }
-    const uint64_t rep = __ballot(status == 1), left = __ballot(status == 2);
-    if (counts && lane == 0) {
-        if (rep) atomicAdd(&counts[0], (unsigned long long)__popcll(rep));
-        if (left) atomicAdd(&counts[1], (unsigned long long)__popcll(left));
-    }
+    const uint32_t status = readback_worklist(
+        ws, wm, wt, bad, wave_rank(mask), (uint32_t)__popcll(mask),
+        [&](uint32_t *e, u32x4 &m) {   // the rows are read again (the block's own bytes, still unwritten): no registers held across rounds
+            deposit_rows(stego + off, g.row_pitch, e);
+            m.x = hi; m.y = lo; m.z = nb; m.w = 0u;
+        },
+        [&](uint32_t *px, float *t, uint32_t r, const u32x4 &m, auto settle) {
+            settle(search8(px, t, r, PlainRows<QM>{r, m.z, m.x, m.y, qp}) ? 1u : 2u);
+        },
+        [&](const uint32_t *e) { store_entry_rows(e, stego + off, g.row_pitch); });
+    add_counts(counts, 0u, status);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -2,8 +2,8 @@
 // back with the reference's extraction arithmetic and, where its payload bits do not come back, search for a block whose
 // bits do.  Plain C++ on register values, like svs_block.hpp: csrc/svs_device.hpp checks one block per lane and repairs
 // one block on eight lanes with the per-line steps below and the embed kernels' eight-lane forward / inverse passes
-// (readback_kernel, repair8: forward8 / inverse8 on 64-float tiles); tests/readback builds the one-lane
-// form with g++ for the CPU tier.  Both builds use -ffp-contract=off; the repair
+// (readback_kernel, search8: forward8 / inverse8 on 64-float tiles); tests/hostemu builds the one-lane
+// form (search_block) with g++ for the CPU tier.  Both builds use -ffp-contract=off; the repair
 // rounds to nearest after float arithmetic, so host and device must execute the same operations in the same order: the
 // transforms are svs_block.hpp's pocketfft replays (their fmaf only where it is exact), every other operation below is one
 // IEEE float32 operation (no FMA), and min / max and the final rounding are exact.
@@ -81,8 +81,9 @@ SVS_HD bool readback_block_ok(const uint32_t (&rx)[8], const uint32_t (&ry)[8], 
 // at n = 63 on high-contrast blocks an accepted iterate can be far from the reference's block.  Those blocks do decode;
 // tests/test_readback_cpu.py measures how many there are.
 // The search is written per LINE of the block (coefficient row u, pixel row y) so that the device can run one block on
-// eight lanes (csrc/svs_device.hpp repair8) with exactly these operations: the transforms between the steps are
-// pocketfft's per line, the min / max over the block and the shift are exact.  repair_block below is the one-lane form.
+// eight lanes (csrc/svs_device.hpp search8) with exactly these operations: the transforms between the steps are
+// pocketfft's per line, the min / max over the block and the shift are exact.  search_block below is the one-lane form, the
+// only copy of the loop on this side: every form further down gives it its row functions and its acceptance.
 
 // targets of coefficient row u (flat indices 8u .. 8u + 7; only 1 .. nb are used)
 template <int QM>
@@ -155,19 +156,22 @@ SVS_HD void repair_store_row(const float (&y)[8], float s, uint32_t &lo4, uint32
     hi4 = b;
 }
 
-// the one-lane form (host emulation; the device repairs with eight lanes per block)
-template <int U, int QM>
-SVS_HD bool repair_block(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+// the one-lane form (host emulation; the device searches with eight lanes per block).  What a form of the pass differs in:
+//   targets_row(c_u, u, T_u)                  the targets of coefficient row u from the block's coefficients
+//   correction_row(T_u, c_u, u, scale, d_u)   the row's over-relaxed correction
+//   accept(c)                                 is the iterate with these 8 x 8 coefficients taken?
+template <class Targets, class Correction, class Accept>
+SVS_HD bool search_block(uint32_t (&rx)[8], uint32_t (&ry)[8], Targets &&targets_row, Correction &&correction_row, Accept &&accept) {
     float c[8][8], T[8][8];
     forward_exact(rx, ry, c);
-    for (int u = 0; u < 8; ++u) repair_targets_row<QM>(c[u], u, nb, hi, lo, qp, T[u]);
+    for (int u = 0; u < 8; ++u) targets_row(c[u], u, T[u]);
     uint32_t px[8], py[8];
     for (int r = 0; r < 8; ++r) { px[r] = rx[r]; py[r] = ry[r]; }
     for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
         const float scale = 1.0f + 0.5f * (float)it;   // exact
         // the correction's inverse transform: columns (axis 0) first, then rows, as the reference inverts
         float d[8][8], P[8][8], Y[8][8];
-        for (int u = 0; u < 8; ++u) repair_correction_row(T[u], c[u], u, nb, scale, d[u]);
+        for (int u = 0; u < 8; ++u) correction_row(T[u], c[u], u, scale, d[u]);
         for (int x = 0; x < 8; ++x) {
             float col[8], out[8];
             for (int u = 0; u < 8; ++u) col[u] = d[u][x];
@@ -183,14 +187,25 @@ SVS_HD bool repair_block(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb, uint
         const float s = repair_shift(mn, mx);
         for (int y = 0; y < 8; ++y) repair_store_row(Y[y], s, px[y], py[y]);
         forward_exact(px, py, c);
-        bool miss = false;
-        for (int u = 0; u < U; ++u) miss |= row_misses<QM>(c[u], u, nb, hi, lo, qp);
-        if (!miss) {
+        if (accept(c)) {
             for (int r = 0; r < 8; ++r) { rx[r] = px[r]; ry[r] = py[r]; }
             return true;
         }
     }
     return false;
+}
+
+// the plain form: flat indices 1 .. nb; the acceptance looks at the U coefficient rows the payload can reach
+template <int U, int QM>
+SVS_HD bool repair_block(uint32_t (&rx)[8], uint32_t (&ry)[8], uint32_t nb, uint32_t hi, uint32_t lo, const QimParams &qp) {
+    return search_block(
+        rx, ry, [&](const float (&c)[8], int u, float (&T)[8]) { repair_targets_row<QM>(c, u, nb, hi, lo, qp, T); },
+        [&](const float (&T)[8], const float (&c)[8], int u, float scale, float (&d)[8]) { repair_correction_row(T, c, u, nb, scale, d); },
+        [&](const float (&c)[8][8]) {
+            bool miss = false;
+            for (int u = 0; u < U; ++u) miss |= row_misses<QM>(c[u], u, nb, hi, lo, qp);
+            return !miss;
+        });
 }
 
 // The whole per-block step of the read-back pass: 0 = the block reads back (untouched), 1 = repaired in place, 2 = could not
@@ -272,7 +287,7 @@ SVS_HD bool keyed_row_misses(const float (&c)[8], const RowSlots &rs, uint32_t n
     return miss;
 }
 
-// one-lane forms (host emulation; the device runs the rows above on eight lanes, svs_device.hpp repair8_keyed)
+// one-lane forms (host emulation; the device runs the rows above on eight lanes, svs_device.hpp KeyedRows)
 template <int QM>
 SVS_HD bool keyed_block_misses(const float (&c)[8][8], const CoeffTable &sel, uint32_t nb, uint32_t hi, uint32_t lo,
                                const QimParams &qp, bool dith, const float (&d)[8][8]) {
@@ -284,36 +299,13 @@ SVS_HD bool keyed_block_misses(const float (&c)[8][8], const CoeffTable &sel, ui
 template <int QM>
 SVS_HD bool repair_block_keyed(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, uint32_t nb, uint32_t hi, uint32_t lo,
                                const QimParams &qp, bool dith, const float (&d)[8][8]) {
-    float c[8][8], T[8][8];
-    forward_exact(rx, ry, c);
-    for (int u = 0; u < 8; ++u) keyed_targets_row<QM>(c[u], row_slots(sel, u), nb, hi, lo, qp, dith, d[u], T[u]);
-    uint32_t px[8], py[8];
-    for (int r = 0; r < 8; ++r) { px[r] = rx[r]; py[r] = ry[r]; }
-    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
-        const float scale = 1.0f + 0.5f * (float)it;   // exact
-        float e[8][8], P[8][8], Y[8][8];
-        for (int u = 0; u < 8; ++u) keyed_correction_row(T[u], c[u], row_slots(sel, u), nb, scale, e[u]);
-        for (int x = 0; x < 8; ++x) {
-            float col[8], out[8];
-            for (int u = 0; u < 8; ++u) col[u] = e[u][x];
-            pf::dct3_8(col, out);
-            for (int y = 0; y < 8; ++y) P[y][x] = out[y];
-        }
-        float mn = 1e30f, mx = -1e30f;
-        for (int y = 0; y < 8; ++y) {
-            float row[8];
-            pf::dct3_8(P[y], row);
-            repair_add_row(px[y], py[y], row, Y[y], mn, mx);
-        }
-        const float s = repair_shift(mn, mx);
-        for (int y = 0; y < 8; ++y) repair_store_row(Y[y], s, px[y], py[y]);
-        forward_exact(px, py, c);
-        if (!keyed_block_misses<QM>(c, sel, nb, hi, lo, qp, dith, d)) {
-            for (int r = 0; r < 8; ++r) { rx[r] = px[r]; ry[r] = py[r]; }
-            return true;
-        }
-    }
-    return false;
+    return search_block(
+        rx, ry,
+        [&](const float (&c)[8], int u, float (&T)[8]) { keyed_targets_row<QM>(c, row_slots(sel, u), nb, hi, lo, qp, dith, d[u], T); },
+        [&](const float (&T)[8], const float (&c)[8], int u, float scale, float (&e)[8]) {
+            keyed_correction_row(T, c, row_slots(sel, u), nb, scale, e);
+        },
+        [&](const float (&c)[8][8]) { return !keyed_block_misses<QM>(c, sel, nb, hi, lo, qp, dith, d); });
 }
 
 // the per-block step under a selection and a dither (s_b: dither_block_seed of the block's physical position, read only
@@ -400,7 +392,7 @@ SVS_HD bool stepped_row_misses(const float (&c)[8], const RowSlots &rs, const Ro
     return miss;
 }
 
-// one-lane forms (host emulation; the device runs the rows above on eight lanes, svs_device.hpp repair8_stepped)
+// one-lane forms (host emulation; the device runs the rows above on eight lanes, svs_device.hpp SteppedRows)
 SVS_HD bool stepped_block_misses(const float (&c)[8][8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb, uint32_t hi,
                                  uint32_t lo, bool dith, uint32_t s_b) {
     bool miss = false;
@@ -409,42 +401,20 @@ SVS_HD bool stepped_block_misses(const float (&c)[8][8], const CoeffTable &sel, 
     return miss;
 }
 
-// the search over the sixteen iterates; accept(c): is the iterate with these coefficients taken?  (The read-back accepts one that
-// decodes, the margin pass one that is strong throughout.)
+// search_block with the stepped targets and the keyed correction; accept(c): is the iterate with these coefficients taken?  (The
+// read-back accepts one that decodes, the margin pass one that is strong throughout.)
 template <class Accept>
 SVS_HD bool search_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
                                  uint32_t hi, uint32_t lo, bool dith, uint32_t s_b, Accept &&accept) {
-    float c[8][8], T[8][8];
-    forward_exact(rx, ry, c);
-    for (int u = 0; u < 8; ++u)
-        stepped_targets_row(c[u], row_slots(sel, u), row_steps(steps, u), (uint32_t)u, nb, hi, lo, dith, s_b, T[u]);
-    uint32_t px[8], py[8];
-    for (int r = 0; r < 8; ++r) { px[r] = rx[r]; py[r] = ry[r]; }
-    for (int it = 0; it < SVS_READBACK_ITERS; ++it) {
-        const float scale = 1.0f + 0.5f * (float)it;   // exact
-        float e[8][8], P[8][8], Y[8][8];
-        for (int u = 0; u < 8; ++u) keyed_correction_row(T[u], c[u], row_slots(sel, u), nb, scale, e[u]);
-        for (int x = 0; x < 8; ++x) {
-            float col[8], out[8];
-            for (int u = 0; u < 8; ++u) col[u] = e[u][x];
-            pf::dct3_8(col, out);
-            for (int y = 0; y < 8; ++y) P[y][x] = out[y];
-        }
-        float mn = 1e30f, mx = -1e30f;
-        for (int y = 0; y < 8; ++y) {
-            float row[8];
-            pf::dct3_8(P[y], row);
-            repair_add_row(px[y], py[y], row, Y[y], mn, mx);
-        }
-        const float s = repair_shift(mn, mx);
-        for (int y = 0; y < 8; ++y) repair_store_row(Y[y], s, px[y], py[y]);
-        forward_exact(px, py, c);
-        if (accept(c)) {
-            for (int r = 0; r < 8; ++r) { rx[r] = px[r]; ry[r] = py[r]; }
-            return true;
-        }
-    }
-    return false;
+    return search_block(
+        rx, ry,
+        [&](const float (&c)[8], int u, float (&T)[8]) {
+            stepped_targets_row(c, row_slots(sel, u), row_steps(steps, u), (uint32_t)u, nb, hi, lo, dith, s_b, T);
+        },
+        [&](const float (&T)[8], const float (&c)[8], int u, float scale, float (&e)[8]) {
+            keyed_correction_row(T, c, row_slots(sel, u), nb, scale, e);
+        },
+        accept);
 }
 
 SVS_HD bool repair_block_stepped(uint32_t (&rx)[8], uint32_t (&ry)[8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb,
@@ -503,7 +473,7 @@ SVS_HD uint32_t stepped_row_verdict(const float (&c)[8], const RowSlots &rs, con
     return bad;
 }
 
-// one-lane forms (host emulation; the device runs the rows on eight lanes, svs_device.hpp repair8_stepped with a gate)
+// one-lane forms (host emulation; the device runs the rows on eight lanes, svs_device.hpp SteppedRows with a gate)
 SVS_HD uint32_t stepped_block_verdict(const float (&c)[8][8], const CoeffTable &sel, const StepArgs &steps, uint32_t nb, uint32_t hi,
                                       uint32_t lo, bool dith, uint32_t s_b, float gate) {
     uint32_t bad = 0u;

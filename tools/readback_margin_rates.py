@@ -7,7 +7,9 @@ alternated in the same rounds of one process, each call timed with a pair of HIP
   (ii)  the calls that launch the hosting instantiation, this build against --baseline-lib (the parent commit's library: `make -C
         csrc pre_readback_margin`), each judged against the parent's own spread (ratelib.verdict): svs_embed_readback_dev with an
         order at delta = 16, n = 63; svs_embed_bgr_readback_dev plain and keep-colour; svs_embed_dithered_readback_dev;
-        svs_stepped_embed_readback_dev
+        svs_stepped_embed_readback_dev; and, so that every body of the pass is covered, the gray pass in raster order in a two-row
+        instantiation (delta = 20, n = 10) and an eight-row one at 128 VGPRs (delta = 7.5, n = 20), and
+        svs_stepped_embed_readback_margin_dev at g = --gate where the baseline has it
 Output: profiles/readback_margin_rates.txt (--out).
 
     python tools/readback_margin_rates.py [--frames 200 --h 2160 --w 3840 --reps 15 --gate 64 --baseline-lib PATH]
@@ -42,8 +44,8 @@ def main():
             s.gray, s.stego, s.P, None, C.byref(sel), C.byref(dith), C.byref(table), n_ac, s.bits, 0, cap, G, C.byref(s.done),
             s.small, None), "svs_stepped_embed_readback_dev")
 
-    def margin(g):
-        return lambda: native.check(lib.svs_stepped_embed_readback_margin_dev(
+    def margin(g, so=lib):
+        return lambda: native.check(so.svs_stepped_embed_readback_margin_dev(
             s.gray, s.stego, s.P, None, C.byref(sel), C.byref(dith), C.byref(table), n_ac, s.bits, 0, cap, g, G, C.byref(s.done),
             four, None), "svs_stepped_embed_readback_margin_dev")
 
@@ -87,13 +89,18 @@ def main():
               f"{four_counts(margin(0))}, {m['stepped_embed_readback_margin, g = 0'] / alone:.3f} x")
         if old is not None:
             s.say("  (ii) the calls that launch the hosting instantiation, against the parent commit's library")
-            s.against_baseline([
+            cases = [
                 ("embed_readback, keyed order, delta 16, n 63", ordered_readback(old), ordered_readback(lib)),
                 ("embed_bgr_readback, plain", bgr_readback(old, False), bgr_readback(lib, False)),
                 ("embed_bgr_readback, keep-colour", bgr_readback(old, True), bgr_readback(lib, True)),
                 ("embed_dithered_readback, zig-zag 10, dither", keyed_readback(old), keyed_readback(lib)),
                 ("stepped_embed_readback, zig-zag 10, dither, uniform 20", stepped_readback(old), stepped_readback(lib)),
-            ])
+                ("embed_readback, raster, delta 20, n 10", s.embed_readback(old, 20.0, 10, G), s.embed_readback(lib, 20.0, 10, G)),
+                ("embed_readback, raster, delta 7.5, n 20", s.embed_readback(old, 7.5, 20, G), s.embed_readback(lib, 7.5, 20, G)),
+            ]
+            if hasattr(old, "svs_stepped_embed_readback_margin_dev"):      # a baseline from before the margin pass has none
+                cases.append((f"stepped_embed_readback_margin, g = {gate}", margin(gate, old), margin(gate, lib)))
+            s.against_baseline(cases)
     s.close()
 
 
