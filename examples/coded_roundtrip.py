@@ -6,7 +6,7 @@ Both stego clips go through the requantisation channel (batch.requantise_frames)
 device by the soft-decision Viterbi decoder (batch.extract_coded_frames: the soft bytes stay on the device, the payload comes
 back), the tiled one by the fused soft vote (batch.extract_vote_frames).
 
-    python examples/coded_roundtrip.py [--quality 75] [--rate 2] [--delta 20] [--n-ac 10] [--outer [--lose-frame J]]
+    python examples/coded_roundtrip.py [--quality 75] [--rate 2] [--delta 20] [--n-ac 10] [--outer [--lose-frame J]] [--device-encode]
 
 At the defaults the code delivers all 3 594 bits and three copies leave 51 of 2 400 wrong; --rate 34, the rate-1/2 code punctured
 to rate 3/4, delivers 5 394 (README.md has the tables).  --outer puts the Reed-Solomon outer code (svsdct.rs, RS(255, 223),
@@ -18,6 +18,7 @@ extract_coded_frames as lost (lost_frames=[J]): its soft bytes are zeroed and th
 errors-and-erasures decoder (svsdct.rse).  One frame of three is a third of the stream, past any 32 parity bytes; the clip is
 then twelve frames (--frames), of which one is a twelfth: --outer --lose-frame 5 --quality 95 returns the payload where the
 call without lost_frames returns 255 for every codeword.
+--device-encode runs the sender's codes on the GPU (svsdct.enc, batch.embed_coded_frames(encoder="device")): the same stego bytes.
 """
 import argparse
 import os
@@ -37,8 +38,10 @@ ap.add_argument("--delta", type=float, default=20)
 ap.add_argument("--n-ac", type=int, default=10)
 ap.add_argument("--outer", action="store_true", help="Reed-Solomon (255, 223) outer code in front of the convolutional code")
 ap.add_argument("--lose-frame", type=int, default=None, metavar="J", help="with --outer: overwrite frame J with noise and pass it as lost")
+ap.add_argument("--device-encode", action="store_true", help="encode on the GPU: embed_coded_frames(encoder=\"device\")")
 ap.add_argument("--frames", type=int, default=None, help="frames of the clip: 3, or 12 with --lose-frame")
 a = ap.parse_args()
+encoder = "device" if a.device_encode else "host"
 if a.lose_frame is not None and not a.outer:
     ap.error("--lose-frame needs --outer: it is the Reed-Solomon decoder that takes erasures")
 n_frames = a.frames or (3 if a.lose_frame is None else 12)
@@ -52,7 +55,7 @@ name = f"1/{a.rate}" if a.rate in fec.RATES else f"{a.rate // 10}/{a.rate % 10}"
 if a.outer:
     data = rng.integers(0, 256, rs.payload_bits(cap, a.rate) // 8).astype(np.uint8)
     info = np.unpackbits(data)
-    stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate, outer=True)
+    stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate, outer=True, encoder=encoder)
     received = batch.requantise_frames(stego, a.quality)
     if a.lose_frame is not None:
         received[a.lose_frame] = rng.integers(64, 192, received.shape[1:]).astype(np.uint8)
@@ -68,7 +71,7 @@ if a.outer:
           + (" - not every codeword decoded: the stream is reported as failed" if (status == rs.UNCORRECTABLE).any() else ""))
 else:
     info = rng.integers(0, 2, fec.info_bits(cap, a.rate)).astype(np.uint8)
-    stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate)
+    stego, used, n_info = batch.embed_coded_frames(clip, a.delta, a.n_ac, info, rate=a.rate, encoder=encoder)
     received = batch.requantise_frames(stego, a.quality)
     decoded = batch.extract_coded_frames(received, a.delta, a.n_ac, n_info, rate=a.rate)
     soft, _ = batch.extract_soft_frames(received, a.delta, a.n_ac)

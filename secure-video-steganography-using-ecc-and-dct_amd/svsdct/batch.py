@@ -27,6 +27,7 @@ import numpy as np
 from . import channel as _channel
 from . import coeffs as _coeffs
 from . import dither as _dither
+from . import enc as _enc
 from . import fec as _fec
 from . import native
 from . import matrix as _matrix
@@ -604,8 +605,69 @@ def lost_span(lo: int, hi: int, rate: int, k: int, erase_margin: int = 1):
     return max(min(t0 // 8, total) - erase_margin, 0), min(min(-(-t1 // 8), total) + erase_margin, total)
 
 
+def _round4(nbytes: int) -> int:
+    return (int(nbytes) + 3) // 4 * 4
+
+
+def _coded_plan(n_info: int, rate: int, copies, outer: bool, cap: int):
+    """The lengths of the sender's chain, and embed_coded_frames' ValueErrors about them: (k data bytes of the outer code or 0,
+    the inner code's info bits, its coded bits, the bits of the stream that is embedded)"""
+    k = _outer_bytes(n_info) if outer else 0
+    inner = 8 * _rs.coded_bytes(k) if outer else int(n_info)
+    coded = _fec.coded_bits(inner, rate)
+    if coded > cap:
+        raise ValueError(f"{coded} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
+                         f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
+    return k, inner, coded, coded if copies == 1 else cap if copies is None else min(cap, copies * coded)
+
+
+def coded_workspace_bytes(n_info: int, rate: int = 2, copies: int | None = 1, outer: bool = False, capacity: int = 0) -> int:
+    """The bytes of d_work that embed_coded_device needs for a payload of n_info bits in a stack of `capacity` bits
+    (capacity_bits): the Reed-Solomon stream under outer, the coded stream, and the tiled stream unless copies is 1 - each
+    rounded up to 4 bytes.  Raises embed_coded_frames' ValueErrors."""
+    copies = _coded_copies(copies)
+    k, _, coded, stream = _coded_plan(int(n_info), rate, copies, outer, int(capacity))
+    return ((_round4(_rs.coded_bytes(k)) if outer else 0) + _round4((coded + 7) // 8)
+            + (0 if copies == 1 else _round4((stream + 7) // 8)))
+
+
+def _embed_coded_on_device(frames, delta, n_ac, info, rate, copies, outer, embed_kw):
+    """embed_coded_frames(encoder="device"): the packed payload and the frames go up, embed_coded_device runs, the stego comes
+    back; what embed_frames' keywords say is said to embed_device"""
+    kw = dict(embed_kw)
+    device, block_key, first_frame = kw.pop("device", 0), kw.pop("block_key", None), kw.pop("first_frame", 0)
+    counted = 4 if kw.get("readback_margin") is not None else 2 if any(
+        kw.get(name) for name in ("readback", "readback_keyed", "readback_stepped")) else 0
+    stack = _as_stack(frames)
+    f, h, w = stack.shape
+    work_bytes = coded_workspace_bytes(info.size, rate, copies, outer, capacity_bits(f, h, w, n_ac))
+    order = block_order(block_key, first_frame)
+    lib = native.load()
+    _enc.load()
+    native.ensure_device(device)
+    packed = np.packbits(info)
+    stego = pinned_empty(stack.shape)
+    counts = np.zeros(4, np.uint64)
+    with _fec._Staged() as dev:
+        d_gray, d_stego, d_payload, d_work = (dev.alloc(n) for n in (stack.size, stack.size, packed.size, work_bytes))
+        native.check(lib.svs_memcpy_h2d(d_gray, stack.ctypes.data, stack.size, None), "svs_memcpy_h2d")
+        native.check(lib.svs_memcpy_h2d(d_payload, packed.ctypes.data, packed.size, None), "svs_memcpy_h2d")
+        d_counts = 0
+        if counted:
+            d_counts = dev.alloc(32)
+            native.check(lib.svs_memset(d_counts, 0, 32, None), "svs_memset")
+        used = embed_coded_device(d_gray, d_stego, Planes.contiguous(f, h, w), delta, n_ac, d_payload, info.size, d_work, work_bytes,
+                                  rate=rate, copies=copies, outer=outer, order=order, first_frame=first_frame, d_counts=d_counts, **kw)
+        native.check(lib.svs_memcpy_d2h(stego.ctypes.data, d_stego, stack.size, None), "svs_memcpy_d2h")
+        if counted:
+            native.check(lib.svs_memcpy_d2h(counts.ctypes.data, d_counts, 32, None), "svs_memcpy_d2h")
+        native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+    tail = () if not counted else (MarginCounts(*map(int, counts)),) if counted == 4 else (ReadbackCounts(int(counts[0]), int(counts[1])),)
+    return (stego, used, int(info.size), *tail)
+
+
 def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2, copies: int | None = 1, outer: bool = False,
-                       **embed_kw):
+                       encoder: str = "host", **embed_kw):
     """Embed a payload under the convolutional code (svsdct/fec.py, include/svsfec.h): fec.encode(info_bits, rate) - rate 2 or 3
     coded bits a payload bit, or a punctured code of fec.PUNCTURED (23, 34, 56, 78: rate 2/3 .. 7/8, the unsent bits are not
     embedded), six tail bits -, then soft.tile when copies > 1 (copies=None: as many as the stack's capacity
@@ -616,14 +678,21 @@ def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2
     outer=True: the payload, whole bytes (ValueError otherwise), first goes through the Reed-Solomon outer code (svsdct/rs.py,
     include/svsrs.h): bytes -> rs.encode -> fec.encode -> embed; rs.payload_bits(capacity, rate) is then the largest payload.
     n_info stays the PAYLOAD's bit count, and the receiver passes outer=True as well.
-    matrix: refused (ValueError): a syndrome bit has no margin, so a matrix call has no soft form to decode."""
+    matrix: refused (ValueError): a syndrome bit has no margin, so a matrix call has no soft form to decode.
+    encoder: "host" (svs_rs_encode, svs_fec_encode and soft.tile on the CPU, the coded stream uploaded) or "device" (the packed
+    payload uploaded, then embed_coded_device: libsvsenc.so's encoders and the embed on the GPU).  The same stego and counts
+    either way, byte for byte."""
     _no_matrix(embed_kw.get("matrix"), "coded")
     if "bit_offset" in embed_kw or "n_bits" in embed_kw:
         raise ValueError("embed_coded_frames embeds the whole coded stream: bit_offset and n_bits are not its keywords")
+    if encoder not in ("host", "device"):
+        raise ValueError(f'encoder {encoder!r}: "host" or "device"')
     copies = _coded_copies(copies)
     info = np.asarray(str_to_bits(info_bits) if isinstance(info_bits, str) else info_bits, np.uint8).reshape(-1)
     if info.size == 0:
         raise ValueError("an empty payload cannot be coded")
+    if encoder == "device":
+        return _embed_coded_on_device(frames, delta, n_ac, info, rate, copies, outer, embed_kw)
     f, h, w = _as_stack(frames).shape
     cap = capacity_bits(f, h, w, n_ac)
     inner = np.unpackbits(_rs.encode_array(np.packbits(info[: 8 * _outer_bytes(info.size)]))) if outer else info
@@ -851,6 +920,41 @@ def embed_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_bits_
     _gray_call(native.load(), "embed", call, [d_gray, d_stego, C.byref(planes)], delta, n_ac,
                [d_bits_packed, int(bit_offset), int(n_bits), flags, C.byref(done)], d_counts or None, (stream or None,))
     return int(done.value)
+
+
+def embed_coded_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d_payload_packed: int, n_info: int, d_work: int,
+                       work_bytes: int, rate: int = 2, copies: int | None = 1, outer: bool = False, stream: int = 0, **embed_kw) -> int:
+    """embed_coded_frames for a payload that lies on the device: everything is enqueued on `stream`, nothing leaves the device and
+    nothing is synchronised.  d_payload_packed: the n_info payload bits, packed MSB first, any alignment (under outer whole
+    bytes, the data of the outer code).  d_work: 4-byte aligned scratch of coded_workspace_bytes(n_info, rate, copies, outer,
+    capacity) bytes, work_bytes its size.  The chain: with outer svs_rs_encode_dev (out of place, into d_work), then
+    svs_fec_encode_dev, with copies != 1 svs_bits_tile_dev, then embed_device on the result, which takes every other keyword
+    (mode, order, first_frame, coeffs, dither_key, steps, the rules, the read-backs and d_counts).  Returns the bits embedded.
+    ValueError, before any device work: matrix; a payload that is not whole bytes under outer; a coded stream above the
+    capacity; a workspace that is misaligned or too small."""
+    _no_matrix(embed_kw.get("matrix"), "coded")
+    if "bit_offset" in embed_kw or "n_bits" in embed_kw:
+        raise ValueError("embed_coded_device embeds the whole coded stream: bit_offset and n_bits are not its keywords")
+    copies, n_info = _coded_copies(copies), int(n_info)
+    if n_info < 1:
+        raise ValueError("an empty payload cannot be coded")
+    cap = capacity_bits(planes.n_frames, planes.height, planes.width, n_ac)
+    k, inner, coded, n_stream = _coded_plan(n_info, rate, copies, outer, cap)
+    need = coded_workspace_bytes(n_info, rate, copies, outer, cap)
+    if int(d_work) % 4 or int(work_bytes) < need:
+        raise ValueError(f"the workspace must be 4-byte aligned and hold {need} bytes (coded_workspace_bytes)")
+    d_inner, at = int(d_payload_packed), int(d_work)
+    if outer:
+        total = _rs.coded_bytes(k)
+        _enc.rs_encode_device(d_inner, k, at, total, stream)
+        d_inner, at = at, at + _round4(total)
+    coded_bytes = (coded + 7) // 8
+    _enc.fec_encode_device(d_inner, inner, rate, at, coded_bytes, stream)
+    d_bits = at
+    if copies != 1:
+        d_bits = at + _round4(coded_bytes)
+        _enc.tile_device(at, coded, d_bits, n_stream, (n_stream + 7) // 8, stream)
+    return embed_device(d_gray, d_stego, planes, delta, n_ac, d_bits, 0, n_stream, stream=stream, **embed_kw)
 
 
 def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,
