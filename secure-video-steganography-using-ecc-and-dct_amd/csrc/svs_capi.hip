@@ -1,31 +1,17 @@
 // svs_capi.hip - the C ABI declared in include/svsdct.h (host side + kernel launches).
 // Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC  (see csrc/Makefile)
 #include "svsdct.h"
+#include "svs_abi.hpp"
 #include "svs_device.hpp"
 #include "svs_route.hpp"
 #include "svs_stage.hpp"
 
-#include <cstdarg>
-#include <cstdio>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <type_traits>
 
 namespace {
-
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
 
 #define SVS_HIP(expr)                                                                          \
     do {                                                                                       \

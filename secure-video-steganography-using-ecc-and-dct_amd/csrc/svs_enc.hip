@@ -18,42 +18,12 @@
 //       shifted into place - two at most when the period is 32 bits or more, one per copy when it is shorter.
 // No atomics, no scratch (profiles/enc_resources.txt).
 #include "svsenc.h"
-#include "svsfec.h"
-#include "svsrs.h"
+#include "svs_enc_args.hpp"   // and svs_abi.hpp: fail(), launched(), overlap()
 #include "svs_enc.hpp"
-
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 
 namespace {
 
 using namespace svsenc;
-
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SVS_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return SVS_OK;
-}
-
-bool overlap(const uint8_t *a, uint64_t na, const uint8_t *b, uint64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
 
 constexpr int kThreads = 256;
 constexpr int kRsThreads = 64;                    // a workgroup is one wave: 64 codewords, as the decoder's screening wave
@@ -108,9 +78,6 @@ __global__ __launch_bounds__(kThreads) void tile_kernel(const uint8_t *__restric
     store_dword(out, d * 4u, out_bytes, tile_dword(Bytes{in}, period, tile_residue(d, period), d, n_out));
 }
 
-bool punctured(int rate) { return svsfec::puncture(rate).period != 0; }
-bool rate_ok(int rate) { return rate == 2 || rate == 3 || punctured(rate); }
-
 template <int CODE>
 void launch_fec(const uint8_t *d_info, uint64_t n_info, uint64_t n_coded, uint8_t *d_out, uint64_t bytes, hipStream_t st) {
     const uint64_t units = fec_units<CODE>(n_coded);                      // at most 2^38 at SVS_FEC_MAX_INFO_BITS: 2^30 workgroups
@@ -127,13 +94,9 @@ int svs_enc_abi_version(void) { return SVS_ENC_ABI_VERSION; }
 const char *svs_enc_last_error(void) { return g_last_error.c_str(); }
 
 int svs_rs_encode_dev(const uint8_t *d_data, uint64_t k, uint8_t *d_stream_out, uint64_t capacity_bytes, void *stream) {
-    if (k == 0) return SVS_OK;
-    if (k > SVS_RS_MAX_DATA_BYTES) return fail(SVS_ERR_INVALID_ARG, "svs_rs_encode_dev: k %llu exceeds SVS_RS_MAX_DATA_BYTES", (unsigned long long)k);
-    if (!d_data || !d_stream_out) return fail(SVS_ERR_INVALID_ARG, "svs_rs_encode_dev: NULL pointer");
-    const uint64_t C = svsrs::codewords(k), total = k + svsrs::kParity * C;
-    if (capacity_bytes < total)
-        return fail(SVS_ERR_CAPACITY, "svs_rs_encode_dev: the output holds %llu bytes, the call writes %llu", (unsigned long long)capacity_bytes,
-                    (unsigned long long)total);
+    uint64_t C = 0, total = 0;
+    const int rc = rs_encode_args("svs_rs_encode_dev", d_data, k, d_stream_out, capacity_bytes, &C, &total);
+    if (rc != kEncode) return rc;
     const bool in_place = d_stream_out == d_data;
     if (!in_place && overlap(d_data, k, d_stream_out, total))
         return fail(SVS_ERR_INVALID_ARG, "svs_rs_encode_dev: the data and the stream overlap without being the same buffer");
@@ -145,27 +108,12 @@ int svs_rs_encode_dev(const uint8_t *d_data, uint64_t k, uint8_t *d_stream_out, 
 
 int svs_fec_encode_dev(const uint8_t *d_info_packed, uint64_t n_info, int rate, uint8_t *d_coded_packed_out, uint64_t capacity_bytes,
                        void *stream) {
-    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode_dev: rate %d is none of 2, 3, 23, 34, 56, 78", rate);
-    if (n_info == 0) return SVS_OK;
-    if (n_info > SVS_FEC_MAX_INFO_BITS)
-        return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode_dev: n_info %llu exceeds SVS_FEC_MAX_INFO_BITS", (unsigned long long)n_info);
-    if (!d_info_packed || !d_coded_packed_out) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode_dev: NULL pointer");
-    if ((uintptr_t)d_coded_packed_out & 3u) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode_dev: the output is not 4-byte aligned");
-    const uint64_t n = n_info + SVS_FEC_TAIL;
-    const uint64_t n_coded = punctured(rate) ? svsfec::sent_before(svsfec::puncture(rate), n) : (uint64_t)rate * n;
-    const uint64_t bytes = (n_coded + 7) / 8;
-    if (capacity_bytes < bytes)
-        return fail(SVS_ERR_CAPACITY, "svs_fec_encode_dev: the output holds %llu bytes, the call writes %llu",
-                    (unsigned long long)capacity_bytes, (unsigned long long)bytes);
-    hipStream_t st = (hipStream_t)stream;
-    switch (rate) {
-        case 2: launch_fec<2>(d_info_packed, n_info, n_coded, d_coded_packed_out, bytes, st); break;
-        case 3: launch_fec<3>(d_info_packed, n_info, n_coded, d_coded_packed_out, bytes, st); break;
-        case SVS_FEC_RATE_2_3: launch_fec<SVS_FEC_RATE_2_3>(d_info_packed, n_info, n_coded, d_coded_packed_out, bytes, st); break;
-        case SVS_FEC_RATE_3_4: launch_fec<SVS_FEC_RATE_3_4>(d_info_packed, n_info, n_coded, d_coded_packed_out, bytes, st); break;
-        case SVS_FEC_RATE_5_6: launch_fec<SVS_FEC_RATE_5_6>(d_info_packed, n_info, n_coded, d_coded_packed_out, bytes, st); break;
-        default: launch_fec<SVS_FEC_RATE_7_8>(d_info_packed, n_info, n_coded, d_coded_packed_out, bytes, st); break;
-    }
+    uint64_t n_coded = 0;
+    const int rc = fec_encode_args("svs_fec_encode_dev", d_info_packed, n_info, rate, d_coded_packed_out, capacity_bytes, true, &n_coded);
+    if (rc != kEncode) return rc;
+    svsfec::with_rate(rate, [&](auto code) {
+        launch_fec<decltype(code)::value>(d_info_packed, n_info, n_coded, d_coded_packed_out, (n_coded + 7) / 8, (hipStream_t)stream);
+    });
     return launched("svs_fec_encode_dev");
 }
 

@@ -15,36 +15,15 @@
 //      so no two waves write the same byte and no atomics are needed.  The last, partial segment masks its tail.
 // LDS per wave: 640 words of 8 bytes and 640 * RATE int16.  No global atomics, no scratch (profiles/fec_resources.txt).
 #include "svsfec.h"
+#include "svs_enc_args.hpp"   // and svs_abi.hpp: fail(), launched()
 #include "svs_fec.hpp"
-
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 
 namespace {
 
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-bool punctured(int rate) { return svsfec::puncture(rate).period != 0; }
-bool rate_ok(int rate) { return rate == 2 || rate == 3 || punctured(rate); }
-const char *const kRates = "none of 2, 3, 23, 34, 56, 78";
-
-// the values a stream of n steps holds: rate * n, or S(n) of a punctured code
-uint64_t stream_bits(uint64_t n, int rate) {
-    return punctured(rate) ? svsfec::sent_before(svsfec::puncture(rate), n) : (uint64_t)rate * n;
-}
+using svsfec::kRates;
+using svsfec::punctured;
+using svsfec::rate_ok;
+using svsfec::stream_bits;
 
 constexpr int kWavesPerGroup = 4;
 constexpr int kThreads = 64 * kWavesPerGroup;
@@ -188,20 +167,14 @@ int decode(const In *d_in, uint64_t n_info, int rate, uint8_t *d_out, uint64_t o
     const uint64_t n_segments = (n_info + svsfec::kSegment - 1) / svsfec::kSegment;   // segments behind n_info hold tail steps only
     const uint64_t groups = (n_segments + kWavesPerGroup - 1) / kWavesPerGroup;       // at most 2^29 at SVS_FEC_MAX_INFO_BITS
     hipStream_t st = (hipStream_t)stream;
-    const auto launch = [&](void (*kernel)(const In *, uint64_t, uint64_t, uint8_t *, uint64_t)) {
+    svsfec::with_rate(rate, [&](auto code) {
+        constexpr int kCode = decltype(code)::value;
+        void (*kernel)(const In *, uint64_t, uint64_t, uint8_t *, uint64_t);
+        if constexpr (kCode <= 3) kernel = svsfec::decode_kernel<kCode, In>;
+        else kernel = svsfec::decode_punctured_kernel<kCode, In>;
         hipLaunchKernelGGL(kernel, dim3((uint32_t)groups), dim3(kThreads), 0, st, d_in, n_info, n_segments, d_out, out_bytes);
-    };
-    switch (rate) {
-        case 2: launch(svsfec::decode_kernel<2, In>); break;
-        case 3: launch(svsfec::decode_kernel<3, In>); break;
-        case SVS_FEC_RATE_2_3: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_2_3, In>); break;
-        case SVS_FEC_RATE_3_4: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_3_4, In>); break;
-        case SVS_FEC_RATE_5_6: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_5_6, In>); break;
-        default: launch(svsfec::decode_punctured_kernel<SVS_FEC_RATE_7_8, In>); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SVS_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return SVS_OK;
+    });
+    return launched(what);
 }
 
 }  // namespace
@@ -225,18 +198,13 @@ uint64_t svs_fec_info_bits(uint64_t capacity_bits, int rate) {
 
 int svs_fec_encode(const uint8_t *info_packed, uint64_t n_info, int rate, uint8_t *coded_packed_out, uint64_t capacity_bytes,
                    uint64_t *n_coded_out) {
-    if (!rate_ok(rate)) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: rate %d is %s", rate, kRates);
-    if (n_info == 0) {
-        if (n_coded_out) *n_coded_out = 0;
-        return SVS_OK;
+    uint64_t n_coded = 0;
+    const int rc = fec_encode_args("svs_fec_encode", info_packed, n_info, rate, coded_packed_out, capacity_bytes, false, &n_coded);
+    if (rc != kEncode) {
+        if (rc == SVS_OK && n_coded_out) *n_coded_out = 0;
+        return rc;
     }
-    if (n_info > SVS_FEC_MAX_INFO_BITS)
-        return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: n_info %llu exceeds SVS_FEC_MAX_INFO_BITS", (unsigned long long)n_info);
-    if (!info_packed || !coded_packed_out) return fail(SVS_ERR_INVALID_ARG, "svs_fec_encode: NULL pointer");
-    const uint64_t n = n_info + SVS_FEC_TAIL, n_coded = stream_bits(n, rate), bytes = (n_coded + 7) / 8;
-    if (capacity_bytes < bytes)
-        return fail(SVS_ERR_CAPACITY, "svs_fec_encode: the output holds %llu bytes, the call writes %llu",
-                    (unsigned long long)capacity_bytes, (unsigned long long)bytes);
+    const uint64_t n = n_info + SVS_FEC_TAIL;
     uint32_t s = 0, acc = 0;
     uint64_t at = 0;                                     // coded bits written so far
     const svsfec::Puncture pc = svsfec::puncture(rate);  // period 0: every bit of a step is sent

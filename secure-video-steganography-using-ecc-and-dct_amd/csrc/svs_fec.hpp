@@ -5,6 +5,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 #if defined(__HIPCC__)
 #define SVS_FEC_HD __host__ __device__ inline
 #else
@@ -127,6 +129,27 @@ SVS_FEC_HD PunctStep punct_advance(const Puncture &pc, PunctStep s, int steps) {
 SVS_FEC_HD int sent_place(const Puncture &pc, int phase, PunctStep s, int j) {
     if (!punct_kept(pc, s.r, j)) return -1;
     return s.q * pc.kept + punct_before(pc, s.r, j) - punct_before(pc, phase);
+}
+
+// ---- the host side's rules about a rate code: 2, 3 or a punctured code -------------------------------------------------------
+inline bool punctured(int rate) { return puncture(rate).period != 0; }
+inline bool rate_ok(int rate) { return rate == 2 || rate == 3 || punctured(rate); }
+constexpr const char *kRates = "none of 2, 3, 23, 34, 56, 78";
+
+// the values a stream of n steps holds: rate * n, or S(n) of a punctured code
+inline uint64_t stream_bits(uint64_t n, int rate) { return punctured(rate) ? sent_before(puncture(rate), n) : (uint64_t)rate * n; }
+
+// f(std::integral_constant<int, rate>) of a rate that rate_ok() let through: the one place a runtime rate picks an instantiation
+template <typename F>
+inline void with_rate(int rate, F &&f) {
+    switch (rate) {
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 23: f(std::integral_constant<int, 23>{}); break;
+        case 34: f(std::integral_constant<int, 34>{}); break;
+        case 56: f(std::integral_constant<int, 56>{}); break;
+        default: f(std::integral_constant<int, 78>{}); break;
+    }
 }
 
 }  // namespace svsfec

@@ -2,6 +2,7 @@
 // which launches the decoder kernel of csrc/svs_rs_decode.hpp in its instantiation without a mask - the only one this library
 // holds.  The kernel, and why it has the shape it has, is described there.
 // Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC  (see csrc/Makefile)
+#include "svs_enc_args.hpp"
 #include "svs_rs_decode.hpp"
 
 namespace {
@@ -29,16 +30,12 @@ uint64_t svs_rs_data_bytes(uint64_t total_bytes) {
 }
 
 int svs_rs_encode(const uint8_t *data, uint64_t k, uint8_t *out, uint64_t capacity_bytes, uint64_t *n_out) {
-    if (k == 0) {
-        if (n_out) *n_out = 0;
-        return SVS_OK;
+    uint64_t C = 0, total = 0;
+    const int rc = rs_encode_args("svs_rs_encode", data, k, out, capacity_bytes, &C, &total);
+    if (rc != kEncode) {
+        if (rc == SVS_OK && n_out) *n_out = 0;
+        return rc;
     }
-    if (k > SVS_RS_MAX_DATA_BYTES) return fail(SVS_ERR_INVALID_ARG, "svs_rs_encode: k %llu exceeds SVS_RS_MAX_DATA_BYTES", (unsigned long long)k);
-    if (!data || !out) return fail(SVS_ERR_INVALID_ARG, "svs_rs_encode: NULL pointer");
-    const uint64_t C = svsrs::codewords(k), total = k + svsrs::kParity * C;
-    if (capacity_bytes < total)
-        return fail(SVS_ERR_CAPACITY, "svs_rs_encode: the output holds %llu bytes, the call writes %llu", (unsigned long long)capacity_bytes,
-                    (unsigned long long)total);
     for (uint64_t i = 0; i < k; ++i) out[i] = data[i];
     for (uint64_t c = 0; c < C; ++c) {
         uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};

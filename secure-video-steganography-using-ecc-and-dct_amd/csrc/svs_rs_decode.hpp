@@ -1,8 +1,8 @@
 // svs_rs_decode.hpp - the one Reed-Solomon decoder kernel for gfx950 and the host side of a *_decode_dev call.  Two libraries are
 // built from it: libsvsrs.so (csrc/svs_rs.hip, svs_rs_decode_dev: errors only, the instantiation without a mask) and libsvsrse.so
 // (csrc/svs_rse.hip, svs_rse_decode_dev: with a mask of erased bytes, both instantiations).  Both are loaded into one process, so
-// EVERYTHING HERE HAS INTERNAL LINKAGE - one anonymous namespace around the kernel, the device tables, the last-error string and the
-// host functions: the same named kernel stub or __device__ variable defined in two shared objects would be interposed by the dynamic
+// EVERYTHING HERE HAS INTERNAL LINKAGE - one anonymous namespace around the kernel, the device tables, the last-error string (csrc/svs_abi.hpp)
+// and the host functions: the same named kernel stub or __device__ variable defined in two shared objects would be interposed by the dynamic
 // linker, and each library keeps a last-error string of its own.
 //
 // The kernel, one launch; a workgroup is four waves and owns 64 codewords:
@@ -43,29 +43,12 @@
 #pragma once
 
 #include "svsrs.h"
+#include "svs_abi.hpp"
 #include "svs_rs.hpp"
-
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 
 namespace {
 
 using namespace svsrs;
-
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
 
 constexpr int kWavesPerGroup = 4;
 constexpr int kThreads = 64 * kWavesPerGroup;
@@ -295,9 +278,7 @@ int decode_dev(const char *name, uint8_t *d_stream, uint64_t k, const uint8_t *d
         if (d_erased) kernel = rse_decode_kernel<true>;
     hipLaunchKernelGGL(kernel, dim3((uint32_t)groups), dim3(kThreads), 0, (hipStream_t)stream, d_stream, k, C, (uint32_t)(k / C), k % C,
                        d_erased, d_status, d_counts);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SVS_ERR_HIP, "%s: launch failed: %s", name, hipGetErrorString(e));
-    return SVS_OK;
+    return launched(name);
 }
 
 }  // namespace

@@ -38,6 +38,7 @@ from . import soft as _soft
 from .hostmem import pinned_empty
 from .native import BlockOrder, Dither, Planes
 from .order import check_key
+from .staging import Staged
 
 MAX_AC = 63
 
@@ -609,26 +610,40 @@ def _round4(nbytes: int) -> int:
     return (int(nbytes) + 3) // 4 * 4
 
 
-def _coded_plan(n_info: int, rate: int, copies, outer: bool, cap: int):
-    """The lengths of the sender's chain, and embed_coded_frames' ValueErrors about them: (k data bytes of the outer code or 0,
-    the inner code's info bits, its coded bits, the bits of the stream that is embedded)"""
-    k = _outer_bytes(n_info) if outer else 0
-    inner = 8 * _rs.coded_bytes(k) if outer else int(n_info)
-    coded = _fec.coded_bits(inner, rate)
-    if coded > cap:
-        raise ValueError(f"{coded} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
-                         f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
-    return k, inner, coded, coded if copies == 1 else cap if copies is None else min(cap, copies * coded)
+class _CodedPlan(NamedTuple):
+    """The lengths of a coded stream in a stack of `capacity` bits, and where embed_coded_device puts each stage in its workspace
+    (byte offsets, each stage rounded up to 4 bytes): the one place that knows them, for both ends of the chain."""
+    capacity: int
+    k: int            # the data bytes of the outer code, 0 without it
+    inner: int        # the info bits of the inner code: the payload, or the bits of the Reed-Solomon stream
+    coded: int        # its coded (sent) bits
+    stream: int       # the bits that are embedded: one copy, or the copies cut at the capacity
+    at_coded: int     # the Reed-Solomon stream, if there is one, lies at 0
+    at_stream: int    # = at_coded when copies is 1: the coded stream is what is embedded
+    work_bytes: int
+
+    @classmethod
+    def of(cls, n_info: int, rate: int, copies, outer: bool, capacity: int) -> "_CodedPlan":
+        """copies: as _coded_copies returns it.  Raises the ValueErrors about a payload that is not whole bytes under outer, a
+        rate that is none, and a coded stream above the capacity - in that order."""
+        n_info, cap = int(n_info), int(capacity)
+        k = _outer_bytes(n_info) if outer else 0
+        inner = 8 * _rs.coded_bytes(k) if outer else n_info
+        coded = _fec.coded_bits(inner, rate)
+        if coded > cap:
+            raise ValueError(f"{coded} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
+                             f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
+        stream = coded if copies == 1 else cap if copies is None else min(cap, copies * coded)
+        at_coded = _round4(_rs.coded_bytes(k)) if outer else 0
+        at_stream = at_coded if copies == 1 else at_coded + _round4((coded + 7) // 8)
+        return cls(cap, k, inner, coded, stream, at_coded, at_stream, at_stream + _round4((stream + 7) // 8))
 
 
 def coded_workspace_bytes(n_info: int, rate: int = 2, copies: int | None = 1, outer: bool = False, capacity: int = 0) -> int:
     """The bytes of d_work that embed_coded_device needs for a payload of n_info bits in a stack of `capacity` bits
     (capacity_bits): the Reed-Solomon stream under outer, the coded stream, and the tiled stream unless copies is 1 - each
     rounded up to 4 bytes.  Raises embed_coded_frames' ValueErrors."""
-    copies = _coded_copies(copies)
-    k, _, coded, stream = _coded_plan(int(n_info), rate, copies, outer, int(capacity))
-    return ((_round4(_rs.coded_bytes(k)) if outer else 0) + _round4((coded + 7) // 8)
-            + (0 if copies == 1 else _round4((stream + 7) // 8)))
+    return _CodedPlan.of(n_info, rate, _coded_copies(copies), outer, capacity).work_bytes
 
 
 def _embed_coded_on_device(frames, delta, n_ac, info, rate, copies, outer, embed_kw):
@@ -642,26 +657,20 @@ def _embed_coded_on_device(frames, delta, n_ac, info, rate, copies, outer, embed
     f, h, w = stack.shape
     work_bytes = coded_workspace_bytes(info.size, rate, copies, outer, capacity_bits(f, h, w, n_ac))
     order = block_order(block_key, first_frame)
-    lib = native.load()
     _enc.load()
-    native.ensure_device(device)
-    packed = np.packbits(info)
-    stego = pinned_empty(stack.shape)
     counts = np.zeros(4, np.uint64)
-    with _fec._Staged() as dev:
-        d_gray, d_stego, d_payload, d_work = (dev.alloc(n) for n in (stack.size, stack.size, packed.size, work_bytes))
-        native.check(lib.svs_memcpy_h2d(d_gray, stack.ctypes.data, stack.size, None), "svs_memcpy_h2d")
-        native.check(lib.svs_memcpy_h2d(d_payload, packed.ctypes.data, packed.size, None), "svs_memcpy_h2d")
-        d_counts = 0
+    with Staged(device) as dev:
+        d_gray, d_payload = dev.upload(stack), dev.upload(np.packbits(info))
+        d_stego, d_work, d_counts = dev.alloc(stack.size), dev.alloc(work_bytes), 0
         if counted:
             d_counts = dev.alloc(32)
-            native.check(lib.svs_memset(d_counts, 0, 32, None), "svs_memset")
+            dev.zero(d_counts, 32)
         used = embed_coded_device(d_gray, d_stego, Planes.contiguous(f, h, w), delta, n_ac, d_payload, info.size, d_work, work_bytes,
                                   rate=rate, copies=copies, outer=outer, order=order, first_frame=first_frame, d_counts=d_counts, **kw)
-        native.check(lib.svs_memcpy_d2h(stego.ctypes.data, d_stego, stack.size, None), "svs_memcpy_d2h")
+        stego = dev.download(d_stego, pinned_empty(stack.shape))
         if counted:
-            native.check(lib.svs_memcpy_d2h(counts.ctypes.data, d_counts, 32, None), "svs_memcpy_d2h")
-        native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+            dev.download(d_counts, counts)
+        dev.synchronise()
     tail = () if not counted else (MarginCounts(*map(int, counts)),) if counted == 4 else (ReadbackCounts(int(counts[0]), int(counts[1])),)
     return (stego, used, int(info.size), *tail)
 
@@ -694,13 +703,9 @@ def embed_coded_frames(frames: np.ndarray, delta, n_ac, info_bits, rate: int = 2
     if encoder == "device":
         return _embed_coded_on_device(frames, delta, n_ac, info, rate, copies, outer, embed_kw)
     f, h, w = _as_stack(frames).shape
-    cap = capacity_bits(f, h, w, n_ac)
-    inner = np.unpackbits(_rs.encode_array(np.packbits(info[: 8 * _outer_bytes(info.size)]))) if outer else info
-    coded = _fec.encode(inner, rate)
-    if coded.size > cap:
-        raise ValueError(f"{coded.size} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
-                         f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
-    stream = coded if copies == 1 else _soft.tile(coded, cap if copies is None else min(cap, copies * coded.size))
+    plan = _CodedPlan.of(info.size, rate, copies, outer, capacity_bits(f, h, w, n_ac))      # refuses before anything is encoded
+    coded = _fec.encode(np.unpackbits(_rs.encode_array(np.packbits(info))) if outer else info, rate)
+    stream = coded if copies == 1 else _soft.tile(coded, plan.stream)
     stego, used, *counts = embed_frames(frames, delta, n_ac, stream, **embed_kw)
     return (stego, used, int(info.size), *counts)
 
@@ -736,59 +741,36 @@ def extract_coded_frames(frames: np.ndarray, delta, n_ac, n_info: int, rate: int
     _no_matrix(matrix, "coded")
     copies = _coded_copies(copies)
     lost, erase_margin = _lost_frames_arg(lost_frames, erase_margin, outer, copies)
-    n_payload = int(n_info)
-    if outer:
-        n_info = 8 * _rs.coded_bytes(_outer_bytes(n_payload))
-    n_coded = _fec.coded_bits(n_info, rate)
     n_info = int(n_info)
-    if n_info == 0:
+    stack = _as_stack(frames)
+    f, h, w = stack.shape
+    plan = _CodedPlan.of(n_info, rate, copies, outer, capacity_bits(f, h, w, n_ac))
+    if plan.inner == 0:
         raise ValueError("an empty payload cannot be decoded")
     table = _steps_arg(steps)
     call = _resolve(n_ac, None, block_key, 0 if first_frame is None else first_frame, coeffs, dither_key)
-    stack = _as_stack(frames)
-    f, h, w = stack.shape
-    cap = capacity_bits(f, h, w, n_ac)
-    if n_coded > cap:
-        raise ValueError(f"{n_coded} coded bits exceed the capacity of {cap}: at rate code {rate} it holds "
-                         f"{_rs.payload_bits(cap, rate) if outer else _fec.info_bits(cap, rate)} payload bits")
     if lost and not lost[-1] < f:
         raise ValueError(f"lost_frames: frame {lost[-1]} is outside the stack's 0 .. {f - 1}")
-    lost_bits = [(i * (cap // f), min((i + 1) * (cap // f), n_coded)) for i in lost if i * (cap // f) < n_coded]
-    lib = native.load()
+    per_frame = plan.capacity // f
+    lost_bits = [(i * per_frame, min((i + 1) * per_frame, plan.coded)) for i in lost if i * per_frame < plan.coded]
     _fec.load()
     if outer:
         (_rse if lost else _rs).load()
-    native.ensure_device(device)
-    planes = Planes.contiguous(f, h, w)
-    out_bytes = (n_info + 7) // 8
-    with _fec._Staged() as dev:
-        d_gray, d_out = dev.alloc(stack.nbytes), dev.alloc(out_bytes)
-        native.check(lib.svs_memcpy_h2d(d_gray, stack.ctypes.data, stack.nbytes, None), "svs_memcpy_h2d")
-        if copies == 1:
-            d_soft = dev.alloc(cap)
-            _soft_call(lib, "extract", call, [d_gray, C.byref(planes)], delta, n_ac, [d_soft, cap], mode_flags(mode), (None,), table)
-            for lo, hi in lost_bits:
-                native.check(lib.svs_memset(d_soft + lo, 0, hi - lo, None), "svs_memset")
-            _fec.decode_soft_device(d_soft, n_info, rate, d_out, out_bytes)
-        else:
-            d_tally = dev.alloc(4 * n_coded)
-            native.check(lib.svs_memset(d_tally, 0, 4 * n_coded, None), "svs_memset")
-            _soft_call(lib, "vote", call, [d_gray, C.byref(planes)], delta, n_ac, [n_coded, 0, d_tally], 0, (None,), table)
-            _fec.decode_weights_device(d_tally, n_info, rate, d_out, out_bytes)
-        if not outer:
-            return _fec.download_info(d_out, n_info)
-        k, n_cw = n_payload // 8, _rs.codewords(n_payload // 8)
-        d_status = dev.alloc(n_cw)
+    n_cw = _rs.codewords(plan.k)
+    with Staged(device) as dev:
+        d_gray, d_out = dev.upload(stack), dev.alloc((plan.inner + 7) // 8)
+        d_work = dev.alloc(plan.capacity if copies == 1 else 4 * plan.coded)
+        d_status = dev.alloc(n_cw) if outer else 0
+        d_erased = 0
         if lost:
-            erased = _rse.mask(k, [lost_span(lo, hi, rate, k, erase_margin) for lo, hi in lost_bits])
-            d_erased = dev.alloc(erased.size)
-            native.check(lib.svs_memcpy_h2d(d_erased, erased.ctypes.data, erased.size, None), "svs_memcpy_h2d")
-            _rse.decode_device(d_out, k, d_erased, d_status, n_cw)
-        else:
-            _rs.decode_device(d_out, k, d_status, n_cw)      # the null stream, as the launches before it
-        status = np.empty(n_cw, np.uint8)
-        native.check(lib.svs_memcpy_d2h(status.ctypes.data, d_status, n_cw, None), "svs_memcpy_d2h")
-        return _fec.download_info(d_out, n_payload), status
+            d_erased = dev.upload(_rse.mask(plan.k, [lost_span(lo, hi, rate, plan.k, erase_margin) for lo, hi in lost_bits]))
+        _extract_coded_device(d_gray, Planes.contiguous(f, h, w), delta, n_ac, plan, rate, copies, d_work, d_out, d_status, d_erased,
+                              lost_bits, call, table, mode)
+        status = dev.download(d_status, n_cw) if outer else None
+        packed = dev.download(d_out, (n_info + 7) // 8)      # under outer the data bytes lead the Reed-Solomon stream
+        dev.synchronise()
+    bits = np.unpackbits(packed, count=n_info)
+    return (bits, status) if outer else bits
 
 
 def requantise_frames(frames: np.ndarray, steps_or_quality, device: int = 0) -> np.ndarray:
@@ -938,23 +920,42 @@ def embed_coded_device(d_gray: int, d_stego: int, planes: Planes, delta, n_ac, d
     copies, n_info = _coded_copies(copies), int(n_info)
     if n_info < 1:
         raise ValueError("an empty payload cannot be coded")
-    cap = capacity_bits(planes.n_frames, planes.height, planes.width, n_ac)
-    k, inner, coded, n_stream = _coded_plan(n_info, rate, copies, outer, cap)
-    need = coded_workspace_bytes(n_info, rate, copies, outer, cap)
-    if int(d_work) % 4 or int(work_bytes) < need:
-        raise ValueError(f"the workspace must be 4-byte aligned and hold {need} bytes (coded_workspace_bytes)")
-    d_inner, at = int(d_payload_packed), int(d_work)
+    plan = _CodedPlan.of(n_info, rate, copies, outer, capacity_bits(planes.n_frames, planes.height, planes.width, n_ac))
+    if int(d_work) % 4 or int(work_bytes) < plan.work_bytes:
+        raise ValueError(f"the workspace must be 4-byte aligned and hold {plan.work_bytes} bytes (coded_workspace_bytes)")
+    d_inner, d_coded, d_bits = int(d_payload_packed), int(d_work) + plan.at_coded, int(d_work) + plan.at_stream
     if outer:
-        total = _rs.coded_bytes(k)
-        _enc.rs_encode_device(d_inner, k, at, total, stream)
-        d_inner, at = at, at + _round4(total)
-    coded_bytes = (coded + 7) // 8
-    _enc.fec_encode_device(d_inner, inner, rate, at, coded_bytes, stream)
-    d_bits = at
+        d_inner = int(d_work)
+        _enc.rs_encode_device(int(d_payload_packed), plan.k, d_inner, _rs.coded_bytes(plan.k), stream)
+    _enc.fec_encode_device(d_inner, plan.inner, rate, d_coded, (plan.coded + 7) // 8, stream)
     if copies != 1:
-        d_bits = at + _round4(coded_bytes)
-        _enc.tile_device(at, coded, d_bits, n_stream, (n_stream + 7) // 8, stream)
-    return embed_device(d_gray, d_stego, planes, delta, n_ac, d_bits, 0, n_stream, stream=stream, **embed_kw)
+        _enc.tile_device(d_coded, plan.coded, d_bits, plan.stream, (plan.stream + 7) // 8, stream)
+    return embed_device(d_gray, d_stego, planes, delta, n_ac, d_bits, 0, plan.stream, stream=stream, **embed_kw)
+
+
+def _extract_coded_device(d_gray: int, planes: Planes, delta, n_ac, plan: _CodedPlan, rate: int, copies, d_work: int, d_out: int,
+                          d_status: int, d_erased: int, lost_bits, call: _GrayCall, table, mode, stream: int = 0) -> None:
+    """The receiving chain, the mirror image of embed_coded_device: everything is enqueued on `stream`, nothing leaves the device
+    and nothing is synchronised.  copies = 1: the soft extract into d_work (plan.capacity bytes), the soft bytes of the sent-bit
+    ranges lost_bits set to 0x00, the Viterbi decoder on the soft bytes; otherwise d_work (4 plan.coded bytes, 4-byte aligned)
+    is zeroed, takes the vote, and the decoder reads the tally.  d_out: ceil(plan.inner / 8) bytes.  d_status: 0, or
+    rs.codewords(plan.k) bytes - then the Reed-Solomon decoder follows in place on d_out, with the mask d_erased where it is
+    not 0 (svs_rse_decode_dev) and blind without (svs_rs_decode_dev).  call, table: the _GrayCall and the steps of the sender."""
+    lib, st = native.load(), (stream or None,)
+    front, out_bytes = [d_gray, C.byref(planes)], (plan.inner + 7) // 8
+    if copies == 1:
+        _soft_call(lib, "extract", call, front, delta, n_ac, [d_work, plan.capacity], mode_flags(mode), st, table)
+        for lo, hi in lost_bits:
+            native.check(lib.svs_memset(d_work + lo, 0, hi - lo, *st), "svs_memset")
+        _fec.decode_soft_device(d_work, plan.inner, rate, d_out, out_bytes, stream)
+    else:
+        native.check(lib.svs_memset(d_work, 0, 4 * plan.coded, *st), "svs_memset")
+        _soft_call(lib, "vote", call, front, delta, n_ac, [plan.coded, 0, d_work], 0, st, table)
+        _fec.decode_weights_device(d_work, plan.inner, rate, d_out, out_bytes, stream)
+    if d_status and d_erased:
+        _rse.decode_device(d_out, plan.k, d_erased, d_status, _rs.codewords(plan.k), stream=stream)
+    elif d_status:
+        _rs.decode_device(d_out, plan.k, d_status, _rs.codewords(plan.k), stream=stream)
 
 
 def extract_device(d_gray: int, planes: Planes, delta, n_ac, d_bits_out: int, out_capacity_bytes: int,

@@ -21,7 +21,7 @@ import numpy as np
 from . import fec as _fec
 from . import native
 from . import rs as _rs
-from .native import SvsNativeError
+from .staging import Staged
 
 LIB_PATH = os.environ.get("SVSENC_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsenc.so"))
 ABI_VERSION = 1
@@ -37,20 +37,7 @@ SIGNATURES = {
     "svs_bits_tile_dev": (C.c_int, [_p, C.c_uint64, _p, C.c_uint64, C.c_uint64, C.c_void_p]),
 }
 
-_lib = None
-
-
-def load() -> C.CDLL:
-    """Load libsvsenc.so once and attach prototypes.  Loading does not touch the GPU."""
-    global _lib
-    if _lib is None:
-        _lib = native.load_library(LIB_PATH, SIGNATURES, "svs_enc_abi_version", ABI_VERSION)
-    return _lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != native.SVS_OK:
-        raise SvsNativeError(f"{what} failed ({rc}): {load().svs_enc_last_error().decode('utf-8', 'replace')}", rc)
+load, check = native.bind(globals(), "svs_enc")
 
 
 def _tile_bits(n, what: str, least: int) -> int:
@@ -84,14 +71,11 @@ def tile_device(d_bits_packed: int, period_bits: int, d_out_packed: int, n_out_b
 def _staged(host_in: np.ndarray, out_bytes: int, device: int, call) -> np.ndarray:
     """host_in up, call(d_in, d_out), out_bytes down (null stream, synchronised)"""
     load()
-    native.ensure_device(device)
-    out = np.empty(out_bytes, np.uint8)
-    with _fec._Staged() as dev:
-        d_in, d_out = dev.alloc(host_in.size), dev.alloc(out_bytes)
-        native.check(dev.lib.svs_memcpy_h2d(d_in, host_in.ctypes.data, host_in.size, None), "svs_memcpy_h2d")
+    with Staged(device) as dev:
+        d_in, d_out = dev.upload(host_in), dev.alloc(out_bytes)
         call(d_in, d_out)
-        native.check(dev.lib.svs_memcpy_d2h(out.ctypes.data, d_out, out_bytes, None), "svs_memcpy_d2h")
-        native.check(dev.lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+        out = dev.download(d_out, out_bytes)
+        dev.synchronise()
     return out
 
 

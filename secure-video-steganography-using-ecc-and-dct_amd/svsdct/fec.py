@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import native
-from .native import SvsNativeError
+from .staging import Staged
 
 LIB_PATH = os.environ.get("SVSFEC_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsfec.so"))
 ABI_VERSION = 1
@@ -47,20 +47,7 @@ SIGNATURES = {
     "svs_fec_decode_weights_dev": (C.c_int, [_u8p, C.c_uint64, C.c_int, _u8p, C.c_uint64, C.c_void_p]),
 }
 
-_lib = None
-
-
-def load() -> C.CDLL:
-    """Load libsvsfec.so once and attach prototypes.  Loading does not touch the GPU."""
-    global _lib
-    if _lib is None:
-        _lib = native.load_library(LIB_PATH, SIGNATURES, "svs_fec_abi_version", ABI_VERSION)
-    return _lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != native.SVS_OK:
-        raise SvsNativeError(f"{what} failed ({rc}): {load().svs_fec_last_error().decode('utf-8', 'replace')}", rc)
+load, check = native.bind(globals(), "svs_fec")
 
 
 def _rate(rate) -> int:
@@ -156,37 +143,6 @@ def decode_weights_device(d_weights: int, n_info: int, rate: int, d_info_packed_
                                             stream or None), "svs_fec_decode_weights_dev")
 
 
-class _Staged:
-    """device buffers of one staged call (svs_malloc), freed when the call is over"""
-
-    def __init__(self):
-        self.lib, self.ptrs = native.load(), []
-
-    def alloc(self, nbytes: int) -> int:
-        p = C.c_void_p()
-        native.check(self.lib.svs_malloc(C.byref(p), max(int(nbytes), 4)), "svs_malloc")
-        self.ptrs.append(p)
-        return p.value
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            self.lib.svs_free(p)
-        return False
-
-
-def download_info(d_packed: int, n_info: int) -> np.ndarray:
-    """ceil(n_info / 8) bytes from the device (null stream, synchronised) -> 0/1 per payload bit"""
-    lib = native.load()
-    out = np.empty((n_info + 7) // 8, np.uint8)
-    if out.size:
-        native.check(lib.svs_memcpy_d2h(out.ctypes.data, d_packed, out.size, None), "svs_memcpy_d2h")
-    native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
-    return np.unpackbits(out, count=n_info)
-
-
 def _decode_staged(values: np.ndarray, n_info: int, rate: int, device: int, call) -> np.ndarray:
     n_info, rate = _n_info(n_info), _rate(rate)
     if values.ndim != 1 or values.size != coded_bits(n_info, rate):
@@ -194,13 +150,13 @@ def _decode_staged(values: np.ndarray, n_info: int, rate: int, device: int, call
     if n_info == 0:
         return np.zeros(0, np.uint8)
     load()
-    native.ensure_device(device)
-    values = np.ascontiguousarray(values)
-    with _Staged() as dev:
-        d_in, d_out = dev.alloc(values.nbytes), dev.alloc((n_info + 7) // 8)
-        native.check(dev.lib.svs_memcpy_h2d(d_in, values.ctypes.data, values.nbytes, None), "svs_memcpy_h2d")
-        call(d_in, n_info, rate, d_out, (n_info + 7) // 8)
-        return download_info(d_out, n_info)
+    out_bytes = (n_info + 7) // 8
+    with Staged(device) as dev:
+        d_in, d_out = dev.upload(np.ascontiguousarray(values)), dev.alloc(out_bytes)
+        call(d_in, n_info, rate, d_out, out_bytes)
+        packed = dev.download(d_out, out_bytes)
+        dev.synchronise()
+    return np.unpackbits(packed, count=n_info)
 
 
 def decode_soft(soft_bytes, n_info: int, rate: int = 2, device: int = 0) -> np.ndarray:

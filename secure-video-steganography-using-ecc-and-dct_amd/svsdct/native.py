@@ -215,46 +215,18 @@ SIGNATURES = {
     "svs_bit_errors_dev": (C.c_int, [_u8p, _u8p, C.c_uint64, C.c_void_p, C.c_void_p]),
 }
 
-_lib = None
-
-
-def load() -> C.CDLL:
-    """Load libsvsdct.so once and attach prototypes.  Loading does not touch the GPU."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise SvsNativeError(
-            f"libsvsdct.so not found at {LIB_PATH}; build it with "
-            f"`python __graft_entry__.py` (or `make -C <package>/csrc`). There is no CPU fallback.")
-    try:
-        lib = C.CDLL(LIB_PATH)
-    except OSError as exc:  # missing ROCm runtime etc.
-        raise SvsNativeError(f"cannot load {LIB_PATH}: {exc}") from exc
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as exc:
-            raise SvsNativeError(f"{LIB_PATH} does not export {name}; rebuild it") from exc
-        fn.restype = res
-        fn.argtypes = args
-    if lib.svs_abi_version() != ABI_VERSION and not os.environ.get("SVS_SKIP_ABI_CHECK"):   # (A/B runs against old builds)
-        raise SvsNativeError(f"ABI version mismatch: library reports {lib.svs_abi_version()}, binding expects "
-                             f"{ABI_VERSION}; rebuild libsvsdct.so")
-    _lib = lib
-    return lib
-
-
 def load_library(path: str, signatures: dict, abi_symbol: str, version: int) -> C.CDLL:
-    """One of the smaller libraries (svsdct/fec.py, rs.py, rse.py), with the prototype of every name in `signatures` attached and
-    its ABI version checked.  Loading does not touch the GPU."""
-    so = "lib" + abi_symbol[: -len("_abi_version")].replace("_", "") + ".so"          # svs_rs_abi_version: libsvsrs.so
+    """The one loader of the package's shared libraries: the library at `path` with the prototype of every name in `signatures`
+    attached and its ABI version (`abi_symbol`, svs_rs_abi_version: libsvsrs.so) checked against `version`; SVS_SKIP_ABI_CHECK
+    in the environment lets a mismatch through (A/B runs against old builds).  Loading does not touch the GPU."""
+    stem = abi_symbol[: -len("_abi_version")].replace("_", "")
+    so = "lib" + ("svsdct" if stem == "svs" else stem) + ".so"
     if not os.path.exists(path):
         raise SvsNativeError(f"{so} not found at {path}; build it with `python __graft_entry__.py` "
                              f"(or `make -C <package>/csrc`). There is no CPU fallback.")
     try:
         lib = C.CDLL(path)
-    except OSError as exc:
+    except OSError as exc:  # missing ROCm runtime etc.
         raise SvsNativeError(f"cannot load {path}: {exc}") from exc
     for name, (res, args) in signatures.items():
         try:
@@ -263,15 +235,33 @@ def load_library(path: str, signatures: dict, abi_symbol: str, version: int) -> 
             raise SvsNativeError(f"{path} does not export {name}; rebuild it") from exc
         fn.restype, fn.argtypes = res, args
     got = getattr(lib, abi_symbol)()
-    if got != version:
+    if got != version and not os.environ.get("SVS_SKIP_ABI_CHECK"):
         raise SvsNativeError(f"ABI version mismatch: {path} reports {got}, the binding expects {version}; rebuild {so}")
     return lib
 
 
-def check(rc: int, what: str) -> None:
-    if rc != SVS_OK:
-        msg = load().svs_last_error().decode("utf-8", "replace")
-        raise SvsNativeError(f"{what} failed ({rc}): {msg}", rc)
+def bind(module: dict, prefix: str):
+    """(load, check) of the binding module whose globals() are `module` and whose symbols start with `prefix` (svs_fec:
+    svs_fec_abi_version, svs_fec_last_error).  load() loads the module's LIB_PATH once, with its SIGNATURES and ABI_VERSION, and
+    keeps the library in the module's `_lib`, which a caller may assign to route the calls elsewhere; all four are read at the
+    call.  check(rc, what) raises SvsNativeError with the library's last error unless rc is SVS_OK."""
+    module.setdefault("_lib", None)
+
+    def load() -> C.CDLL:
+        if module["_lib"] is None:
+            module["_lib"] = load_library(module["LIB_PATH"], module["SIGNATURES"], prefix + "_abi_version", module["ABI_VERSION"])
+        return module["_lib"]
+
+    def check(rc: int, what: str) -> None:
+        if rc != SVS_OK:
+            msg = getattr(load(), prefix + "_last_error")().decode("utf-8", "replace")
+            raise SvsNativeError(f"{what} failed ({rc}): {msg}", rc)
+
+    load.__doc__ = "Load the library once and attach prototypes.  Loading does not touch the GPU."
+    return load, check
+
+
+load, check = bind(globals(), "svs")
 
 
 _current = threading.local()      # hipSetDevice is per host thread: remember what THIS thread last selected

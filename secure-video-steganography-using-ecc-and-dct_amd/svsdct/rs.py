@@ -19,7 +19,7 @@ import numpy as np
 
 from . import fec as _fec
 from . import native
-from .native import SvsNativeError
+from .staging import Staged
 
 LIB_PATH = os.environ.get("SVSRS_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsrs.so"))
 ABI_VERSION = 1
@@ -39,20 +39,7 @@ SIGNATURES = {
     "svs_rs_decode_dev": (C.c_int, [_p, C.c_uint64, _p, C.c_uint64, _p, C.c_void_p]),
 }
 
-_lib = None
-
-
-def load() -> C.CDLL:
-    """Load libsvsrs.so once and attach prototypes.  Loading does not touch the GPU."""
-    global _lib
-    if _lib is None:
-        _lib = native.load_library(LIB_PATH, SIGNATURES, "svs_rs_abi_version", ABI_VERSION)
-    return _lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != native.SVS_OK:
-        raise SvsNativeError(f"{what} failed ({rc}): {load().svs_rs_last_error().decode('utf-8', 'replace')}", rc)
+load, check = native.bind(globals(), "svs_rs")
 
 
 def _k(k) -> int:
@@ -131,22 +118,12 @@ def _decode_staged(stream, k: int, erased, device: int, load_lib, launch):
     if k == 0:
         return b"", np.zeros(0, np.uint8)
     load_lib()
-    lib = native.load()
-    native.ensure_device(device)
     n_cw = codewords(k)
-    status = np.empty(n_cw, np.uint8)
-    data = np.empty(k, np.uint8)
-    with _fec._Staged() as dev:
-        d_stream, d_status = dev.alloc(s.size), dev.alloc(n_cw)
-        native.check(lib.svs_memcpy_h2d(d_stream, s.ctypes.data, s.size, None), "svs_memcpy_h2d")
-        d_erased = 0
-        if m is not None:
-            d_erased = dev.alloc(m.size)
-            native.check(lib.svs_memcpy_h2d(d_erased, m.ctypes.data, m.size, None), "svs_memcpy_h2d")
-        launch(d_stream, k, d_erased, d_status, n_cw)
-        native.check(lib.svs_memcpy_d2h(data.ctypes.data, d_stream, k, None), "svs_memcpy_d2h")
-        native.check(lib.svs_memcpy_d2h(status.ctypes.data, d_status, n_cw, None), "svs_memcpy_d2h")
-        native.check(lib.svs_stream_synchronize(None), "svs_stream_synchronize")
+    with Staged(device) as dev:
+        d_stream, d_status = dev.upload(s), dev.alloc(n_cw)
+        launch(d_stream, k, 0 if m is None else dev.upload(m), d_status, n_cw)
+        data, status = dev.download(d_stream, k), dev.download(d_status, n_cw)
+        dev.synchronise()
     return data.tobytes(), status
 
 

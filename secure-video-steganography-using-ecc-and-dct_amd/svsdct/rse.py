@@ -19,7 +19,6 @@ import os
 import numpy as np
 
 from . import native
-from .native import SvsNativeError
 from .rs import MAX_DATA_BYTES, PARITY, UNCORRECTABLE, _bytes, _decode_staged, _k, codewords, coded_bytes  # noqa: F401
 
 LIB_PATH = os.environ.get("SVSRSE_LIB", os.path.join(native._PKG_DIR, "lib", "libsvsrse.so"))
@@ -34,20 +33,7 @@ SIGNATURES = {
     "svs_rse_decode_dev": (C.c_int, [_p, C.c_uint64, _p, _p, C.c_uint64, _p, C.c_void_p]),
 }
 
-_lib = None
-
-
-def load() -> C.CDLL:
-    """Load libsvsrse.so once and attach prototypes.  Loading does not touch the GPU."""
-    global _lib
-    if _lib is None:
-        _lib = native.load_library(LIB_PATH, SIGNATURES, "svs_rse_abi_version", ABI_VERSION)
-    return _lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != native.SVS_OK:
-        raise SvsNativeError(f"{what} failed ({rc}): {load().svs_rse_last_error().decode('utf-8', 'replace')}", rc)
+load, check = native.bind(globals(), "svs_rse")
 
 
 def mask(k: int, spans) -> np.ndarray:

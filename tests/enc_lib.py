@@ -4,15 +4,13 @@ define no format, so every expectation is something that exists and is pinned al
 CPU tier runs the host build of csrc/svs_enc.hpp (tests/hostemu/enc_emu.cpp) on the lengths the GPU tier runs the kernels on;
 and, for positions no buffer reaches, the parity formula of include/svsfec.h evaluated bit by bit on a synthetic stream."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import fec_lib as fl
 import fec_punctured_lib as fpl
 import rs_lib as rl
+from testlib import build_emu
 from svsdct import fec, rs, soft
 
 RATES = (2, 3, 23, 34, 56, 78)
@@ -133,29 +131,21 @@ def tile_word(d, period, n_out):
 
 
 # ---- the host build of csrc/svs_enc.hpp (tests/hostemu/enc_emu.cpp) -------------------------------------------------------------------
-_EMU = None
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMU_SRC = os.path.join(HERE, "hostemu", "enc_emu.cpp")
-CSRC = fl.CSRC
+_U64, _P = C.c_uint64, C.c_void_p
+PROTOTYPES = {
+    "enc_emu_fec_encode": (C.c_int, [_P, _U64, C.c_int, _P]),
+    "enc_emu_fec_unit_hashed": (C.c_int, [_U64, C.c_int, _U64, _P]),
+    "enc_emu_unit_steps": (C.c_int, [C.c_int]),
+    "enc_emu_hashed_byte": (C.c_uint32, [_U64]),
+    "enc_emu_rs_encode": (C.c_int, [_P, _U64, _P]),
+    "enc_emu_tile": (C.c_int, [_P, _U64, _P, _U64]),
+    "enc_emu_tile_dword_hashed": (C.c_uint32, [_U64, _U64, _U64]),
+}
 
 
 def emu(build_dir=None):
     """tests/hostemu/enc_emu.cpp, compiled once per process with g++ as the other host emulations are"""
-    global _EMU
-    if _EMU is None:
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="enc_emu_"), "libsvs_enc_emu.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, EMU_SRC, "-o", out])
-        lib = C.CDLL(out)
-        u64, p = C.c_uint64, C.c_void_p
-        lib.enc_emu_fec_encode.restype, lib.enc_emu_fec_encode.argtypes = C.c_int, [p, u64, C.c_int, p]
-        lib.enc_emu_fec_unit_hashed.restype, lib.enc_emu_fec_unit_hashed.argtypes = C.c_int, [u64, C.c_int, u64, p]
-        lib.enc_emu_unit_steps.restype, lib.enc_emu_unit_steps.argtypes = C.c_int, [C.c_int]
-        lib.enc_emu_hashed_byte.restype, lib.enc_emu_hashed_byte.argtypes = C.c_uint32, [u64]
-        lib.enc_emu_rs_encode.restype, lib.enc_emu_rs_encode.argtypes = C.c_int, [p, u64, p]
-        lib.enc_emu_tile.restype, lib.enc_emu_tile.argtypes = C.c_int, [p, u64, p, u64]
-        lib.enc_emu_tile_dword_hashed.restype, lib.enc_emu_tile_dword_hashed.argtypes = C.c_uint32, [u64, u64, u64]
-        _EMU = lib
-    return _EMU
+    return build_emu("enc_emu.cpp", PROTOTYPES, build_dir)
 
 
 GUARD = 16

@@ -3,11 +3,10 @@ FORMAT") and not from csrc/svs_fec.hpp: the encoder, the weights, the windowed d
 the inputs of tests/test_fec_gpu.py, so that the CPU tier runs the host build of svs_fec.hpp on the same ones; and the channel
 experiment of the README's table (tests/channel_lib.py's frames, seed and model of the channel)."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+from testlib import build_emu
 
 SEGMENT, OVERLAP, TAIL = 512, 64, 6
 GENERATORS = {2: (0o133, 0o171), 3: (0o133, 0o171, 0o165)}
@@ -203,24 +202,13 @@ def case(kind, n_info, rate):
 
 
 # ---- the host build of csrc/svs_fec.hpp (tests/hostemu/fec_emu.cpp) --------------------------------------------------------------
-_EMU = None
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "secure-video-steganography-using-ecc-and-dct_amd", "csrc")
-EMU_SRC = os.path.join(HERE, "hostemu", "fec_emu.cpp")
+_DECODE = (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p])
+PROTOTYPES = {"fec_emu_decode_soft": _DECODE, "fec_emu_decode_weights": _DECODE}
 
 
 def emu(build_dir=None):
     """tests/hostemu/fec_emu.cpp, compiled once per process with g++ as the other host emulations are"""
-    global _EMU
-    if _EMU is None:
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="fec_emu_"), "libsvs_fec_emu.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, EMU_SRC, "-o", out])
-        lib = C.CDLL(out)
-        for name in ("fec_emu_decode_soft", "fec_emu_decode_weights"):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
-        _EMU = lib
-    return _EMU
+    return build_emu("fec_emu.cpp", PROTOTYPES, build_dir)
 
 
 def emu_decode(values, n_info, rate, build_dir=None):

@@ -4,13 +4,11 @@ depuncturer (one weight per sent bit -> one per mother bit, zeros at the unsent 
 rate 2; the inputs of tests/test_fec_punctured_gpu.py, built as fec_lib's are, so that the CPU tier runs the host build
 (tests/hostemu/fec_punctured_emu.cpp) on the same ones; and the channel experiment of the README's punctured table."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import fec_lib as fl
+from testlib import build_emu
 
 CODES = (23, 34, 56, 78)
 # code -> (out_0 sent, out_1 sent) over the P steps of a period
@@ -154,26 +152,18 @@ def case(kind, n_info, code):
 
 
 # ---- the host build (tests/hostemu/fec_punctured_emu.cpp) -----------------------------------------------------------------------
-_EMU = None
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMU_SRC = os.path.join(HERE, "hostemu", "fec_punctured_emu.cpp")
+_U64 = C.c_uint64
+PROTOTYPES = {
+    "fec_punctured_emu_decode_soft": (C.c_int, [C.c_void_p, _U64, C.c_int, C.c_void_p]),
+    "fec_punctured_emu_decode_weights": (C.c_int, [C.c_void_p, _U64, C.c_int, C.c_void_p]),
+    "fec_punctured_emu_sent_before": (_U64, [_U64, C.c_int]),
+    "fec_punctured_emu_steps_that_fit": (_U64, [_U64, C.c_int]),
+}
 
 
 def emu(build_dir=None):
     """tests/hostemu/fec_punctured_emu.cpp, compiled once per process with g++ as the other host emulations are"""
-    global _EMU
-    if _EMU is None:
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="fec_punctured_emu_"),
-                           "libsvs_fec_punctured_emu.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + fl.CSRC, EMU_SRC, "-o", out])
-        lib = C.CDLL(out)
-        for name in ("fec_punctured_emu_decode_soft", "fec_punctured_emu_decode_weights"):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
-        lib.fec_punctured_emu_sent_before.restype, lib.fec_punctured_emu_sent_before.argtypes = C.c_uint64, [C.c_uint64, C.c_int]
-        lib.fec_punctured_emu_steps_that_fit.restype, lib.fec_punctured_emu_steps_that_fit.argtypes = C.c_uint64, [C.c_uint64, C.c_int]
-        _EMU = lib
-    return _EMU
+    return build_emu("fec_punctured_emu.cpp", PROTOTYPES, build_dir)
 
 
 def emu_decode(values, n_info, code, build_dir=None):

@@ -3,9 +3,6 @@ one-lane forms of the stepped read-back and the margin pass behind it (tests/hos
 verdict from stepped_soft_lib's NumPy soft bytes, the cases both tiers run, and the experiment table of the README (what the
 requantisation channel leaves of a payload embedded with svs_stepped_embed_readback_margin* at several gates)."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -14,6 +11,7 @@ import dither_lib as dl
 import stepped_lib as stl
 import stepped_readback_lib as srl
 import stepped_soft_lib as ssl
+from testlib import build_emu
 from keyed_readback_lib import DITHER_KEY
 from svsdct import channel
 
@@ -24,27 +22,16 @@ GPU_SHAPE = srl.GPU_SHAPE
 FIRST_FRAME = srl.FIRST_FRAME
 
 # ---- the one-lane forms on the host ---------------------------------------------------------------------------------------
-_EMU = None
+PROTOTYPES = {
+    "readback_margin_emu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64,
+                                      C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+}
 
 
 def emu(build_dir=None):
     """tests/hostemu/readback_margin_emu.cpp, compiled once per process with -ffp-contract=off (as stepped_readback_lib.emu)"""
-    global _EMU
-    if _EMU is None:
-        here = os.path.dirname(os.path.abspath(__file__))
-        repo = os.path.dirname(here)
-        src = os.path.join(here, "hostemu", "readback_margin_emu.cpp")
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="readback_margin_emu_"),
-                           "libsvs_readback_margin_emu.so")
-        csrc = os.path.join(repo, "secure-video-steganography-using-ecc-and-dct_amd", "csrc")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + csrc, src, "-o", out])
-        lib = C.CDLL(out)
-        lib.readback_margin_emu.restype = C.c_int
-        lib.readback_margin_emu.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                            C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64,
-                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        _EMU = lib
-    return _EMU
+    return build_emu("readback_margin_emu.cpp", PROTOTYPES, build_dir, ("-ffp-contract=off",))
 
 
 def host_margin(stego0, table, n_ac, bits, gate, index=None, dither_key=None, block_key=None, first_frame=0, bit_offset=0,

@@ -6,11 +6,10 @@ tests/test_rs_gpu.py, so that the CPU tier runs the host build of svs_rs.hpp (te
 the channel experiment of the README's table (tests/channel_lib.py's frames and model of the channel, tests/fec_lib.py's and
 tests/fec_punctured_lib.py's inner code)."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+from testlib import build_emu
 
 N, K, PARITY, T = 255, 223, 32, 16
 UNCORRECTABLE = 255
@@ -273,25 +272,18 @@ def case(kind, k):
 
 
 # ---- the host build of csrc/svs_rs.hpp (tests/hostemu/rs_emu.cpp) ------------------------------------------------------------------
-_EMU = None
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "secure-video-steganography-using-ecc-and-dct_amd", "csrc")
-EMU_SRC = os.path.join(HERE, "hostemu", "rs_emu.cpp")
+_U64, _P = C.c_uint64, C.c_void_p
+PROTOTYPES = {
+    "rs_emu_decode": (C.c_int, [_P, _U64, _P, _P, _P]),
+    "rs_emu_encode": (C.c_int, [_P, _U64, _P]),
+    "rs_emu_data_bytes": (_U64, [_U64]),
+    "rs_emu_coded_bytes": (_U64, [_U64]),
+}
 
 
 def emu(build_dir=None):
     """tests/hostemu/rs_emu.cpp, compiled once per process with g++ as the other host emulations are"""
-    global _EMU
-    if _EMU is None:
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="rs_emu_"), "libsvs_rs_emu.so")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC, EMU_SRC, "-o", out])
-        lib = C.CDLL(out)
-        lib.rs_emu_decode.restype, lib.rs_emu_decode.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.rs_emu_encode.restype, lib.rs_emu_encode.argtypes = C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]
-        lib.rs_emu_data_bytes.restype, lib.rs_emu_data_bytes.argtypes = C.c_uint64, [C.c_uint64]
-        lib.rs_emu_coded_bytes.restype, lib.rs_emu_coded_bytes.argtypes = C.c_uint64, [C.c_uint64]
-        _EMU = lib
-    return _EMU
+    return build_emu("rs_emu.cpp", PROTOTYPES, build_dir)
 
 
 def emu_decode(received, k, counts=(0, 0), build_dir=None, mask=None):

@@ -198,7 +198,7 @@ def case(kind, k):
 
 
 # ---- the host build of csrc/svs_rs.hpp: rs_lib's (tests/hostemu/rs_emu.cpp), called with a mask ------------------------------------
-CSRC, EMU_SRC, emu = rl.CSRC, rl.EMU_SRC, rl.emu
+emu = rl.emu
 
 
 def emu_decode(received, k, mask=None, counts=(0, 0), build_dir=None):

@@ -4,9 +4,6 @@ float32 step per coefficient, every step one float32 operation in the header's o
 pocketfft forward and inverse -, the tables, frames and options the GPU test runs, the host build of the stepped block bodies of
 csrc/svs_block.hpp (tests/hostemu/stepped_emu.cpp), and the survival experiment of channel_lib with a table in place of delta."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -14,6 +11,7 @@ import channel_lib as cl
 import dither_lib as dl
 import minmove_lib as ml
 import soft_lib as sl
+from testlib import build_emu
 from oracle.qim_dct_oracle import BLOCK, MAX_AC, _blocks_view, _check_plane, _fwd, _inv, bits_from_any
 from svsdct import channel
 
@@ -213,33 +211,18 @@ def payload_for(shape, n_ac=N_AC, seed=3):
 
 
 # ---- the stepped block bodies on the host ---------------------------------------------------------------------------------------
-_EMU = None
+PROTOTYPES = {
+    "stepped_emu_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+                                    C.c_int, C.c_uint64, C.c_uint32]),
+    "stepped_emu_extract": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "stepped_emu_plan": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+}
 
 
 def emu(build_dir=None):
     """tests/hostemu/stepped_emu.cpp, compiled once per process with -ffp-contract=off into build_dir (the CPU test passes a
     temporary directory and so compiles the file itself, as tests/test_requantise_cpu.py compiles channel_emu.cpp)"""
-    global _EMU
-    if _EMU is None:
-        here = os.path.dirname(os.path.abspath(__file__))
-        repo = os.path.dirname(here)
-        src = os.path.join(here, "hostemu", "stepped_emu.cpp")
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="stepped_emu_"),
-                           "libsvs_stepped_emu.so")
-        csrc = os.path.join(repo, "secure-video-steganography-using-ecc-and-dct_amd", "csrc")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + csrc, src, "-o", out])
-        lib = C.CDLL(out)
-        lib.stepped_emu_embed.restype = C.c_int
-        lib.stepped_emu_embed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
-                                          C.c_int, C.c_int, C.c_uint64, C.c_uint32]
-        lib.stepped_emu_extract.restype = C.c_int
-        lib.stepped_emu_extract.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
-                                            C.c_void_p]
-        lib.stepped_emu_plan.restype = C.c_int
-        lib.stepped_emu_plan.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p,
-                                         C.c_void_p]
-        _EMU = lib
-    return _EMU
+    return build_emu("stepped_emu.cpp", PROTOTYPES, build_dir, ("-ffp-contract=off",))
 
 
 def _to_blocks(plane):

@@ -3,15 +3,13 @@ build of the one-lane stepped forms of csrc/svs_readback.hpp (tests/hostemu/step
 run, and the experiment table of the README (what the pass repairs on letterboxed frames, and what the requantisation channel
 then leaves of the payload)."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import channel_lib as cl
 import dither_lib as dl
 import stepped_lib as stl
+from testlib import build_emu
 from keyed_readback_lib import DITHER_KEY, prefix, zigzag
 from readback_lib import content
 from svsdct import channel
@@ -20,29 +18,17 @@ ORDER_KEY = 0x0F1E2D3C4B5A6978
 RULES = stl.RULES
 
 # ---- the one-lane forms on the host ---------------------------------------------------------------------------------------
-_EMU = None
+PROTOTYPES = {
+    "stepped_readback_emu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64,
+                                       C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p,
+                                       C.c_void_p]),
+    "stepped_readback_emu_reciprocals": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
+}
 
 
 def emu(build_dir=None):
     """tests/hostemu/stepped_readback_emu.cpp, compiled once per process with -ffp-contract=off (as stepped_lib.emu)"""
-    global _EMU
-    if _EMU is None:
-        here = os.path.dirname(os.path.abspath(__file__))
-        repo = os.path.dirname(here)
-        src = os.path.join(here, "hostemu", "stepped_readback_emu.cpp")
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="stepped_readback_emu_"),
-                           "libsvs_stepped_readback_emu.so")
-        csrc = os.path.join(repo, "secure-video-steganography-using-ecc-and-dct_amd", "csrc")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + csrc, src, "-o", out])
-        lib = C.CDLL(out)
-        lib.stepped_readback_emu.restype = C.c_int
-        lib.stepped_readback_emu.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                             C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64,
-                                             C.c_uint32, C.c_void_p, C.c_void_p]
-        lib.stepped_readback_emu_reciprocals.restype = C.c_int
-        lib.stepped_readback_emu_reciprocals.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-        _EMU = lib
-    return _EMU
+    return build_emu("stepped_readback_emu.cpp", PROTOTYPES, build_dir, ("-ffp-contract=off",))
 
 
 def host_readback(stego0, table, n_ac, bits, index=None, dither_key=None, block_key=None, first_frame=0, bit_offset=0,

@@ -4,15 +4,13 @@ coefficient, every step one float32 operation in the header's order, on stepped_
 the histogram folded from model bytes with svsdct.soft, the host build of the stepped soft block body
 (tests/hostemu/stepped_soft_emu.cpp), and stepped_lib.survival's experiment read with the soft bytes."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import channel_lib as cl
 import dither_lib as dl
 import stepped_lib as st
+from testlib import build_emu
 from oracle.qim_dct_oracle import BLOCK, MAX_AC, _blocks_view, _check_plane, _fwd
 from svsdct import channel
 from svsdct import soft as sv
@@ -73,36 +71,26 @@ def model_hist(soft, n_frames):
 
 
 # ---- the stepped soft block body on the host --------------------------------------------------------------------------------
-_EMU = None
 PLAN_FIELDS = ("path", "rows", "qm", "stepped", "soft", "vote", "hist", "keyed", "steps_on", "soft_on", "soft_vote", "soft_hist",
                "soft_table_count", "sel_count", "dith_on", "sizeof_soft_args")
 KIND = {"soft": 0, "vote": 1, "hist": 2}
 PATH_EXACT, QM_POW2 = 1, 2          # svs::ExtractPath::EXACT, svs::QM_POW2 (the kernel matrix names the instantiation <8, 2, ..>)
 
 
+PROTOTYPES = {
+    "stepped_soft_emu_bytes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                                         C.c_void_p]),
+    "stepped_soft_emu_uniform": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                                           C.c_void_p]),
+    "stepped_soft_emu_plan": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64,
+                                        C.c_void_p]),
+}
+
+
 def emu(build_dir=None):
     """tests/hostemu/stepped_soft_emu.cpp, compiled once per process with -ffp-contract=off into build_dir (the CPU test passes a
     temporary directory and so compiles the file itself, as stepped_lib.emu)"""
-    global _EMU
-    if _EMU is None:
-        here = os.path.dirname(os.path.abspath(__file__))
-        src = os.path.join(here, "hostemu", "stepped_soft_emu.cpp")
-        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix="stepped_soft_emu_"),
-                           "libsvs_stepped_soft_emu.so")
-        csrc = os.path.join(os.path.dirname(here), "secure-video-steganography-using-ecc-and-dct_amd", "csrc")
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + csrc, src, "-o", out])
-        lib = C.CDLL(out)
-        lib.stepped_soft_emu_bytes.restype = C.c_int
-        lib.stepped_soft_emu_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
-                                               C.c_void_p]
-        lib.stepped_soft_emu_uniform.restype = C.c_int
-        lib.stepped_soft_emu_uniform.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
-                                                 C.c_void_p]
-        lib.stepped_soft_emu_plan.restype = C.c_int
-        lib.stepped_soft_emu_plan.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64,
-                                              C.c_uint64, C.c_void_p]
-        _EMU = lib
-    return _EMU
+    return build_emu("stepped_soft_emu.cpp", PROTOTYPES, build_dir, ("-ffp-contract=off",))
 
 
 def host_soft(gray, table, n_ac=MAX_AC, index=None, key=None, t=0):

@@ -7,14 +7,12 @@ import re
 import numpy as np
 import pytest
 
-from testlib import REPO
+from testlib import REPO, declared_symbols, exported_symbols, nm_dynamic
 from svsdct import batch, native, synth
 
 
 def _declared_symbols():
-    text = open(os.path.join(REPO, "include", "svsdct.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(svs_[a-z0-9_]+)\s*\(", text)))
+    return declared_symbols("svsdct.h")
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,19 +25,13 @@ def test_library_exports_every_declared_symbol():
     assert lib.svs_abi_version() == native.ABI_VERSION == 4
 
 
-def _exported(path):
-    import subprocess
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("svs_"))
-
-
 def test_library_exports_exactly_the_declared_symbols():
     """the product library's svs_* exports ARE the header - no measurement hook, no process-global state
     behind one (round 4 shipped svs_guard_counter_set / svs_ref_copy_dev / svs_ref_read_dev / svs_probe_cvt_pk_u8).  Those live
     in the experiments library, which is the product ABI plus exactly them."""
     from testlib import EXP_LIB_PATH, EXPERIMENT_HOOKS
-    assert _exported(native.LIB_PATH) == _declared_symbols()
-    assert _exported(EXP_LIB_PATH) == sorted(_declared_symbols() + list(EXPERIMENT_HOOKS))
+    assert exported_symbols(native.LIB_PATH) == _declared_symbols()
+    assert exported_symbols(EXP_LIB_PATH) == sorted(_declared_symbols() + list(EXPERIMENT_HOOKS))
     src = open(os.path.join(REPO, "secure-video-steganography-using-ecc-and-dct_amd", "csrc", "svs_capi.hip")).read()
     outside = re.sub(r"#if defined\(SVS_EXPERIMENTS\).*?#e(?:lse|ndif)", "", src, flags=re.S)
     assert "g_guard_counter" not in outside            # the kernels of the product build take no counter
@@ -97,8 +89,7 @@ def test_header_is_plain_c_and_library_links_from_c(tmp_path):
 def test_product_library_reads_no_environment_variable():
     """the shipped library does not even import getenv - experiment knobs (kernel rerouting, occupancy
     caps, SVS_GUARD_SCALE ...) exist only in lib/variants/libsvsdct_exp.so, built with -DSVS_EXPERIMENTS"""
-    import subprocess
-    out = subprocess.run(["nm", "-D", "--undefined-only", native.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    out = nm_dynamic(native.LIB_PATH, "undefined")
     assert "hipLaunchKernel" in out or "hipModuleLaunchKernel" in out or "__hipPushCallConfiguration" in out   # nm really listed imports
     assert "getenv" not in out
     src = open(os.path.join(REPO, "secure-video-steganography-using-ecc-and-dct_amd", "csrc", "svs_capi.hip")).read()

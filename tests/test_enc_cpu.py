@@ -4,16 +4,13 @@ GPU tier runs - and once as a stand-alone program under the address and undefine
 output positions round 2^32, 2^40 and 2^43 bits against the formats evaluated bit by bit; the refusals in the documented order;
 and the ValueErrors of the public path.  Nothing here needs a GPU."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import enc_lib as el
 import rs_lib as rl
-from testlib import REPO
+from testlib import check_header_is_plain_c, check_library_exports, run_sanitized_emu
 from svsdct import batch, enc, fec, native, rs, soft
 from svsdct.native import Planes
 
@@ -21,32 +18,17 @@ I, CAP = native.SVS_ERR_INVALID_ARG, native.SVS_ERR_CAPACITY
 
 
 # ---- the library ----------------------------------------------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "svsenc.h")).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(svs_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_the_library_exports_exactly_the_header():
-    out = subprocess.run(["nm", "-D", "--defined-only", enc.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("svs_"))
-    assert exported == _declared() == sorted(enc.SIGNATURES) and len(exported) == 5
     # the library holds svs_rs.hpp's LFSR table as both Reed-Solomon libraries do, and all are loaded into one process: a dynamic
     # symbol of one would be interposed by another's
-    assert not [line for line in out.splitlines() if any(name in line for name in ("_kernel", "d_lfsr", "d_field"))], out
-    assert enc.load().svs_enc_abi_version() == enc.ABI_VERSION == 1
-    undefined = subprocess.run(["nm", "-D", "--undefined-only", enc.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "hipLaunchKernel" in undefined or "__hipPushCallConfiguration" in undefined       # nm really listed imports
-    assert "getenv" not in undefined                                                         # it reads no environment variable
+    undefined = check_library_exports("svsenc.h", enc, "svs_enc", 5, hidden=("_kernel", "d_lfsr", "d_field"))
+    assert enc.ABI_VERSION == 1
     assert "hipMalloc" not in undefined and "Synchronize" not in undefined                   # allocates nothing, never waits
 
 
 def test_the_header_is_plain_c(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "svsdct.h"\n#include "svsfec.h"\n#include "svsrs.h"\n#include "svsenc.h"\n'
-                   "int main(void) { return SVS_ENC_ABI_VERSION == 1 && SVS_ENC_MAX_TILE_BITS == (1ull << 43) && SVS_ERR_CAPACITY == -4 ? 0 : 1; }\n")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(REPO, "include"), str(src), "-o",
-                           str(tmp_path / "use")])
-    subprocess.check_call([str(tmp_path / "use")])
+    check_header_is_plain_c(tmp_path, ("svsdct.h", "svsfec.h", "svsrs.h", "svsenc.h"),
+                            "SVS_ENC_ABI_VERSION == 1 && SVS_ENC_MAX_TILE_BITS == (1ull << 43) && SVS_ERR_CAPACITY == -4")
 
 
 # ---- the host build against the host encoders and the models ------------------------------------------------------------------------
@@ -94,11 +76,7 @@ def test_the_sanitized_stand_alone_program(tmp_path):
     """the host build's windows, xor networks, interleaves, compaction, LFSR walk and tile, driven by enc_emu.cpp's own main on
     buffers of exactly the bytes a call may touch, under the address and undefined-behaviour sanitizers: a stand-alone program,
     run once; nothing is loaded into python"""
-    exe = str(tmp_path / "enc_emu_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-w", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DENC_EMU_MAIN",
-                           "-I" + el.CSRC, el.EMU_SRC, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "enc emu ok" in out.stdout, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    run_sanitized_emu("enc_emu.cpp", "ENC_EMU_MAIN", tmp_path, "enc emu ok", extra_flags=("-w",))
 
 
 # ---- 64-bit positions ----------------------------------------------------------------------------------------------------------------

@@ -3,44 +3,26 @@ against the NumPy model of tests/fec_lib.py, the refusals in the documented orde
 the model on the GPU test's inputs (and once as a stand-alone program under the address and undefined-behaviour sanitizers),
 the tie rules, and the channel experiment of the README's table.  Nothing here needs a GPU."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import channel_lib as cl
 import fec_lib as fl
-from testlib import REPO
+from testlib import check_header_is_plain_c, check_library_exports, run_sanitized_emu
 from svsdct import batch, fec, native
 
 I, CAP = native.SVS_ERR_INVALID_ARG, native.SVS_ERR_CAPACITY
 
 
 # ---- the library ----------------------------------------------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "svsfec.h")).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(svs_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_the_library_exports_exactly_the_header():
-    out = subprocess.run(["nm", "-D", "--defined-only", fec.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("svs_"))
-    assert exported == _declared() == sorted(fec.SIGNATURES) and len(exported) == 7
-    lib = fec.load()
-    assert lib.svs_fec_abi_version() == fec.ABI_VERSION == 1
-    undefined = subprocess.run(["nm", "-D", "--undefined-only", fec.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "hipLaunchKernel" in undefined or "__hipPushCallConfiguration" in undefined       # nm really listed imports
-    assert "getenv" not in undefined                                                         # it reads no environment variable
+    check_library_exports("svsfec.h", fec, "svs_fec", 7)
+    assert fec.ABI_VERSION == 1
 
 
 def test_the_header_is_plain_c(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "svsdct.h"\n#include "svsfec.h"\nint main(void) { return SVS_FEC_SEGMENT == 512 && SVS_ERR_CAPACITY == -4 ? 0 : 1; }\n')
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(REPO, "include"), str(src), "-o",
-                           str(tmp_path / "use")])
-    subprocess.check_call([str(tmp_path / "use")])
+    check_header_is_plain_c(tmp_path, ("svsdct.h", "svsfec.h"), "SVS_FEC_SEGMENT == 512 && SVS_ERR_CAPACITY == -4")
 
 
 def test_lengths():
@@ -209,11 +191,7 @@ def test_the_tie_rules_on_hard_decisions(emu_dir):
 def test_the_sanitized_stand_alone_program(tmp_path):
     """the host build's step and traceback, driven by fec_emu.cpp's own main, under the address and undefined-behaviour
     sanitizers: a stand-alone program, run once; nothing is loaded into python"""
-    exe = str(tmp_path / "fec_emu_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DFEC_EMU_MAIN",
-                           "-I" + fl.CSRC, fl.EMU_SRC, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "fec emu ok" in out.stdout, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    run_sanitized_emu("fec_emu.cpp", "FEC_EMU_MAIN", tmp_path, "fec emu ok")
 
 
 # ---- the README's table -----------------------------------------------------------------------------------------------------------

@@ -4,13 +4,13 @@ host build of csrc/svs_fec.hpp's window load against the model on the GPU test's
 the address and undefined-behaviour sanitizers); and the channel experiment of the README's punctured table.  Nothing here
 needs a GPU."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
 import fec_lib as fl
 import fec_punctured_lib as pl
+from testlib import run_sanitized_emu
 from svsdct import batch, fec, native
 
 I, CAP = native.SVS_ERR_INVALID_ARG, native.SVS_ERR_CAPACITY
@@ -182,11 +182,7 @@ def test_the_noiseless_round_trip_is_the_identity(emu_dir):
 def test_the_sanitized_stand_alone_program(tmp_path):
     """the host build's window load, driven by fec_punctured_emu.cpp's own main, under the address and undefined-behaviour
     sanitizers: a stand-alone program, run once; nothing is loaded into python"""
-    exe = str(tmp_path / "fec_punctured_emu_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-DFEC_PUNCTURED_EMU_MAIN", "-I" + fl.CSRC, pl.EMU_SRC, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "fec punctured emu ok" in out.stdout, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    run_sanitized_emu("fec_punctured_emu.cpp", "FEC_PUNCTURED_EMU_MAIN", tmp_path, "fec punctured emu ok")
 
 
 # ---- the README's table -------------------------------------------------------------------------------------------------------------

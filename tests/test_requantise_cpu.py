@@ -4,13 +4,12 @@ the host model (tests/channel_lib.py), what the inputs of tests/test_requantise_
 README quotes."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import channel_lib as cl
-from testlib import REPO
+from testlib import build_emu
 from svsdct import channel, native
 from svsdct.native import Planes, Steps
 
@@ -208,11 +207,8 @@ def test_the_gpu_tests_inputs_meet_ties_and_saturate():
 def test_the_host_build_of_the_block_body_is_the_model(tmp_path):
     """csrc/svs_block.hpp requantise_block_exact - what a lane of the kernel runs - compiled for the host, on every frame and
     table of the GPU test: the model's bytes, ties and saturation included"""
-    so = tmp_path / "libchannel_emu.so"
-    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-w", "-I" + os.path.join(PKG, "csrc"),
-                    os.path.join(REPO, "tests", "hostemu", "channel_emu.cpp"), "-o", str(so)], check=True)
-    emu = C.CDLL(str(so)).channel_emu_blocks
-    emu.restype, emu.argtypes = None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    emu = build_emu("channel_emu.cpp", {"channel_emu_blocks": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])}, tmp_path,
+                    ("-ffp-contract=off",)).channel_emu_blocks
     for _, kind, frames in cl.gpu_cases():
         f, h, w = frames.shape
         blocks = np.ascontiguousarray(frames.reshape(f, h // 8, 8, w // 8, 8).transpose(0, 1, 3, 2, 4))

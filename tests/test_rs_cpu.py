@@ -4,16 +4,13 @@ definition, the refusals in the documented order, the host build of csrc/svs_rs.
 (and once as a stand-alone program under the address and undefined-behaviour sanitizers), and the channel experiment of the
 README's table.  Nothing here needs a GPU."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import channel_lib as cl
 import rs_lib as rl
-from testlib import REPO
+from testlib import check_header_is_plain_c, check_library_exports, run_sanitized_emu
 from svsdct import batch, fec, native, rs
 
 I, CAP = native.SVS_ERR_INVALID_ARG, native.SVS_ERR_CAPACITY
@@ -26,31 +23,16 @@ def _hex(a):
 
 
 # ---- the library ----------------------------------------------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "svsrs.h")).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(svs_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_the_library_exports_exactly_the_header():
-    out = subprocess.run(["nm", "-D", "--defined-only", rs.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("svs_"))
-    assert exported == _declared() == sorted(rs.SIGNATURES) and len(exported) == 7
     # both Reed-Solomon libraries hold the kernel and the tables of csrc/svs_rs_decode.hpp and are loaded into one process: a
     # dynamic symbol of either would be interposed by the other's
-    assert not [line for line in out.splitlines() if any(name in line for name in ("decode_kernel", "d_field", "d_lfsr"))], out
-    assert rs.load().svs_rs_abi_version() == rs.ABI_VERSION == 1
-    undefined = subprocess.run(["nm", "-D", "--undefined-only", rs.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "hipLaunchKernel" in undefined or "__hipPushCallConfiguration" in undefined       # nm really listed imports
-    assert "getenv" not in undefined                                                         # it reads no environment variable
+    check_library_exports("svsrs.h", rs, "svs_rs", 7, hidden=("decode_kernel", "d_field", "d_lfsr"))
+    assert rs.ABI_VERSION == 1
 
 
 def test_the_header_is_plain_c(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "svsdct.h"\n#include "svsfec.h"\n#include "svsrs.h"\n'
-                   "int main(void) { return SVS_RS_PARITY == 32 && SVS_RS_UNCORRECTABLE == 255 && SVS_ERR_CAPACITY == -4 ? 0 : 1; }\n")
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(REPO, "include"), str(src), "-o",
-                           str(tmp_path / "use")])
-    subprocess.check_call([str(tmp_path / "use")])
+    check_header_is_plain_c(tmp_path, ("svsdct.h", "svsfec.h", "svsrs.h"),
+                            "SVS_RS_PARITY == 32 && SVS_RS_UNCORRECTABLE == 255 && SVS_ERR_CAPACITY == -4")
 
 
 # ---- the format's known answers ---------------------------------------------------------------------------------------------------
@@ -171,11 +153,7 @@ def test_the_host_build_is_the_model_on_the_gpu_tests_inputs(kind, emu_dir):
 def test_the_sanitized_stand_alone_program(tmp_path):
     """the host build's LFSR, syndromes, Berlekamp-Massey, root search and Forney, driven by rs_emu.cpp's own main, under the
     address and undefined-behaviour sanitizers: a stand-alone program, run once; nothing is loaded into python"""
-    exe = str(tmp_path / "rs_emu_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DRS_EMU_MAIN",
-                           "-I" + rl.CSRC, rl.EMU_SRC, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "rs emu ok" in out.stdout, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    run_sanitized_emu("rs_emu.cpp", "RS_EMU_MAIN", tmp_path, "rs emu ok")
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------

@@ -4,49 +4,30 @@ the format rests on (2 e + f <= 32 returns the sent word, 2 e + f = 33 returns 2
 csrc/svs_rs.hpp against the model (and once as a stand-alone program under the address and undefined-behaviour sanitizers), the
 refusals in the documented order, fec.steps_of_sent_bits against brute force, the refusals of lost_frames, and the lost-frame
 experiment of the README's table.  Nothing here needs a GPU."""
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import rs_lib as rl
 import rse_lib as el
-from testlib import REPO
+from testlib import check_header_is_plain_c, check_library_exports, run_sanitized_emu
 from svsdct import batch, fec, native, rs, rse
 
 I, CAP = native.SVS_ERR_INVALID_ARG, native.SVS_ERR_CAPACITY
 
 
 # ---- the library ----------------------------------------------------------------------------------------------------------------
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "svsrse.h")).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(svs_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_the_library_exports_exactly_the_header():
-    out = subprocess.run(["nm", "-D", "--defined-only", rse.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = sorted(line.split()[-1] for line in out.splitlines() if line.split()[-1].startswith("svs_"))
-    assert exported == _declared() == sorted(rse.SIGNATURES) and len(exported) == 3
     # both Reed-Solomon libraries hold the kernel and the tables of csrc/svs_rs_decode.hpp and are loaded into one process: a
     # dynamic symbol of either would be interposed by the other's
-    assert not [line for line in out.splitlines() if any(name in line for name in ("decode_kernel", "d_field", "d_lfsr"))], out
-    assert rse.load().svs_rse_abi_version() == rse.ABI_VERSION == 1
-    undefined = subprocess.run(["nm", "-D", "--undefined-only", rse.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "hipLaunchKernel" in undefined or "__hipPushCallConfiguration" in undefined       # nm really listed imports
-    assert "getenv" not in undefined                                                         # it reads no environment variable
+    check_library_exports("svsrse.h", rse, "svs_rse", 3, hidden=("decode_kernel", "d_field", "d_lfsr"))
+    assert rse.ABI_VERSION == 1
 
 
 def test_the_header_is_plain_c(tmp_path):
     for order in (("svsdct.h", "svsfec.h", "svsrs.h", "svsrse.h"), ("svsrse.h", "svsrs.h"), ("svsrse.h",)):
-        src = tmp_path / "use.c"
-        src.write_text("".join(f'#include "{h}"\n' for h in order)
-                       + "int main(void) { return SVS_RS_PARITY == 32 && SVS_RS_UNCORRECTABLE == 255 && SVS_RSE_MAX_ERASED == 32 && "
-                         "SVS_ERR_CAPACITY == -4 && SVS_RS_MAX_DATA_BYTES == (1ull << 37) ? 0 : 1; }\n")
-        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(REPO, "include"), str(src), "-o",
-                               str(tmp_path / "use")])
-        subprocess.check_call([str(tmp_path / "use")])
+        check_header_is_plain_c(tmp_path, order, "SVS_RS_PARITY == 32 && SVS_RS_UNCORRECTABLE == 255 && SVS_RSE_MAX_ERASED == 32 && "
+                                                 "SVS_ERR_CAPACITY == -4 && SVS_RS_MAX_DATA_BYTES == (1ull << 37)")
 
 
 # ---- the format's known answers ---------------------------------------------------------------------------------------------------
@@ -175,11 +156,7 @@ def test_the_host_build_without_erasures_is_the_parents_model(kind, emu_dir):
 def test_the_sanitized_stand_alone_program(tmp_path):
     """the host build's screening with a mask, erasure locator, Berlekamp-Massey, root search and Forney, driven by rs_emu.cpp's
     -DRSE_EMU_MAIN main, under the address and undefined-behaviour sanitizers: a stand-alone program, run once; nothing is loaded into python"""
-    exe = str(tmp_path / "rse_emu_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DRSE_EMU_MAIN",
-                           "-I" + el.CSRC, el.EMU_SRC, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "rse emu ok" in out.stdout, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    run_sanitized_emu("rs_emu.cpp", "RSE_EMU_MAIN", tmp_path, "rse emu ok")
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,9 @@ import ctypes
 import glob
 import hashlib
 import os
+import re
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -265,6 +267,77 @@ _PROTOTYPES = {
     "emu_hist_bins": (_C.c_uint32, []),
     "emu_hist_runs": (_C.c_uint32, [_C.c_uint32] * 5 + [_PTR, _C.c_uint32]),
 }
+
+
+HOSTEMU_DIR = os.path.join(REPO, "tests", "hostemu")
+_BUILT = {}
+
+
+def build_emu(source, prototypes, build_dir=None, extra_flags=()):
+    """tests/hostemu/<source> (fec_emu.cpp -> libsvs_fec_emu.so) compiled with g++ against csrc/ into build_dir - a temporary
+    directory when there is none; a CPU test passes its own and so compiles the file itself - and loaded, once per process, with
+    prototypes = {name: (restype, argtypes)} attached.  extra_flags: -ffp-contract=off for an emulation of float code."""
+    if source not in _BUILT:
+        stem = os.path.splitext(source)[0]
+        out = os.path.join(str(build_dir) if build_dir is not None else tempfile.mkdtemp(prefix=stem + "_"), f"libsvs_{stem}.so")
+        subprocess.check_call(["g++", "-O2", *extra_flags, "-std=c++17", "-shared", "-fPIC", "-w", "-I" + CSRC,
+                               os.path.join(HOSTEMU_DIR, source), "-o", out])
+        lib = ctypes.CDLL(out)
+        for name, (res, args) in prototypes.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+        _BUILT[source] = lib
+    return _BUILT[source]
+
+
+def run_sanitized_emu(source, define, tmp_path, says, extra_flags=()):
+    """tests/hostemu/<source> with its own main (-D<define>) as a stand-alone program under the address and undefined-behaviour
+    sanitizers, run once; it must end with status 0 and print `says`.  Nothing is loaded into python."""
+    exe = str(tmp_path / (os.path.splitext(source)[0] + "_main"))
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", *extra_flags, "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-D" + define, "-I" + CSRC, os.path.join(HOSTEMU_DIR, source), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and says in out.stdout, (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+
+
+def declared_symbols(header):
+    """the svs_* functions that include/<header> declares, sorted"""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(svs_[a-z0-9_]+)\s*\(", text)))
+
+
+def nm_dynamic(lib_path, which="defined"):
+    """the text of nm -D --defined-only (or which="undefined": --undefined-only) of a shared library"""
+    return subprocess.run(["nm", "-D", f"--{which}-only", lib_path], capture_output=True, text=True, check=True).stdout
+
+
+def exported_symbols(lib_path):
+    """the svs_* symbols a shared library defines, sorted"""
+    return sorted(line.split()[-1] for line in nm_dynamic(lib_path).splitlines() if line.split()[-1].startswith("svs_"))
+
+
+def check_library_exports(header, binding, prefix, count, hidden=()):
+    """include/<header> declares, the binding module's library exports and its SIGNATURES name the same `count` svs_* symbols; the
+    library reports the binding's ABI version (<prefix>_abi_version), holds no dynamic symbol with one of `hidden` in its name,
+    imports a kernel launch (nm really listed imports) and no getenv (it reads no environment variable).  -> the imports' text"""
+    exported = exported_symbols(binding.LIB_PATH)
+    assert exported == declared_symbols(header) == sorted(binding.SIGNATURES) and len(exported) == count
+    defined = nm_dynamic(binding.LIB_PATH)
+    assert not [line for line in defined.splitlines() if any(name in line for name in hidden)], defined
+    assert getattr(binding.load(), prefix + "_abi_version")() == binding.ABI_VERSION
+    undefined = nm_dynamic(binding.LIB_PATH, "undefined")
+    assert "hipLaunchKernel" in undefined or "__hipPushCallConfiguration" in undefined
+    assert "getenv" not in undefined
+    return undefined
+
+
+def check_header_is_plain_c(tmp_path, headers, expression):
+    """a C99 program that includes `headers` in that order and returns 0 where `expression` holds: no warning, status 0"""
+    src = tmp_path / "use.c"
+    src.write_text("".join(f'#include "{h}"\n' for h in headers) + f"int main(void) {{ return {expression} ? 0 : 1; }}\n")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I" + os.path.join(REPO, "include"), str(src), "-o",
+                           str(tmp_path / "use")])
+    subprocess.check_call([str(tmp_path / "use")])
 
 
 def hostemu():
